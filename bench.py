@@ -13,9 +13,13 @@ pass — the same fixed input for every N (generated once per node: rank 0 write
 ranks map their slices).  `--config 2` / `--config 3` put another config there; `--weak` brings back rounds
 1-2's headline (every rank a configs[1]-sized batch of its own, batches pipelined over three engines).
 
-Rank 0 prints ONE JSON line carrying `roofline` for the dominant kernel (start / stop events attached to
-every launch of the timed region, on the engine's stream) and `cpu_baseline` (the CPU oracle on this
-box's cores on a sample of the headline workload; N = 1 only), plus, at N = 1 (SURVEY.md §8d asks for all of them):
+A plain run measures the headline only: it generates and uploads the input, warms up, times --steps steps, writes
+what the last step computed if --dump-outputs DIR is given (a fixed, seeded sample of the reads: their read types and
+bad regions, float32 / float64 .npy files, at most 64 MB), and prints the line.  Rank 0 prints ONE JSON line carrying
+`roofline` for the dominant kernel (start / stop events attached to every launch of the timed region, on the engine's
+stream).  Everything else takes runs of its own and is measured under --full only: the oracle's check of a sample of
+the reads (`parity`), the per-phase times, `cpu_baseline` (the CPU oracle on this box's cores on the headline workload;
+N = 1 only), plus, at N = 1 (SURVEY.md §8d asks for all of them):
   configs2        configs[2]: 2 M reads / 200 M overlaps (rounds 2-3's headline)
   skewed          configs[3]: 10 k ultra-long reads, 57 M intervals (workgroup / device-wide screens + fallbacks)
   small_batches   configs[1] (100 k reads / 5 M overlaps, -c 4): batches pipelined over three engines,
@@ -258,10 +262,50 @@ def drop_shared(cx):
     cx.shared_files = []
 
 
+NOT_CHECKED = "not checked: the oracle's check of the result runs under --full"
+DUMP_SEED = 20241108
+DUMP_READS = 1 << 20          # the sample's size: every read of a batch up to this
+DUMP_LIMIT = 64 << 20         # bytes, every file together
+
+
+def dump_outputs(cx, got, r0, R, out_dir):
+    """--dump-outputs: what the timed path's last step computed — the engine's result as a caller receives it (bad_offsets,
+    bad_regions, read_type) — on a fixed, seeded sample of the R reads of the whole input (all of them up to DUMP_READS),
+    so that two builds can be compared output for output.  `got` holds this rank's reads r0, r0 + 1, ...; every rank must
+    call this (all_gather), rank 0 writes DIR/read_ids, read_type, bad_offsets (the sample's own region CSR), bad_regions
+    and totals ([reads, regions, reads of type 0, 1, 2] over ALL the reads) as .npy, float64 / float32."""
+    n_local = len(got.read_type)
+    ids = (np.arange(R, dtype=np.int64) if R <= DUMP_READS else
+           np.sort(np.random.default_rng(DUMP_SEED).choice(R, DUMP_READS, replace=False)))
+    mine = ids[(ids >= r0) & (ids < r0 + n_local)] - r0
+    off = np.asarray(got.bad_offsets).astype(np.int64)
+    n = off[mine + 1] - off[mine]
+    rows = np.repeat(off[mine] - np.concatenate(([0], np.cumsum(n)[:-1])), n) + np.arange(int(n.sum()))
+    part = {"n": n, "rt": np.asarray(got.read_type)[mine], "reg": np.asarray(got.bad_regions).reshape(-1, 2)[rows],
+            "totals": np.array([n_local, int(off[-1])] + np.bincount(got.read_type, minlength=3)[:3].tolist(), np.float64)}
+    parts = [part]
+    if cx.dist is not None:
+        parts = [None] * cx.world
+        cx.dist.all_gather_object(parts, part)
+    if cx.rank != 0:
+        return
+    n = np.concatenate([p["n"] for p in parts])
+    out = {"read_ids": ids.astype(np.float64), "read_type": np.concatenate([p["rt"] for p in parts]).astype(np.float32),
+           "bad_offsets": np.concatenate(([0], np.cumsum(n))).astype(np.float64),
+           "bad_regions": np.concatenate([p["reg"] for p in parts]).astype(np.float32),
+           "totals": np.sum([p["totals"] for p in parts], axis=0)}
+    room = (DUMP_LIMIT - sum(a.nbytes for k, a in out.items() if k != "bad_regions") - 4096) // 8
+    out["bad_regions"] = out["bad_regions"][:max(0, room)]  # (only a sample with more than ~5 M regions is cut short)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def resident_block(cx, label, profile, R, O, cov, nc, seed, jitter, steps, warmup, parity_reads, traffic_key=None,
-                   keep_host=False):
+                   keep_host=False, full=True, dump_dir=None):
     """One fixed input for every N, read-partitioned over the ranks: generate, upload, W untimed + K timed
     passes bracketed by barrier + synchronize, max over ranks; dominant-kernel events on every launch.
+    full: also the runs of their own (per-phase times, one engine beside NE) and the oracle's check of a sample.
     Every rank must call this (barriers, all_gather); rank 0 gets the block, the others None."""
     ya, host, torch, ydist, dist = cx.ya, cx.host, cx.torch, cx.ydist, cx.dist
     t0 = time.perf_counter()
@@ -320,8 +364,10 @@ def resident_block(cx, label, profile, R, O, cov, nc, seed, jitter, steps, warmu
                 if k2.endswith("_ms") or k2 in PATH_KEYS or k2 == "timed_runs":
                     t[k2] = [a_ + b_ for a_, b_ in zip(t[k2], v)] if isinstance(v, list) else t[k2] + v
     assert nt == K
+    if dump_dir:  # (batch i ran on engine i mod NE: the last step's result is that engine's)
+        dump_outputs(cx, engs[(K - 1) % NE].fetch(), r0, R, dump_dir)
     one_engine_ms = None
-    if NE > 1 and cx.rank == 0:  # the same passes one at a time on one engine, beside it (never part of `value`)
+    if NE > 1 and cx.rank == 0 and full:  # the same passes one at a time on one engine, beside it (never part of `value`)
         cx.torch.cuda.synchronize()
         t1 = time.perf_counter()
         for _ in range(max(3, K // 2)):
@@ -329,7 +375,7 @@ def resident_block(cx, label, profile, R, O, cov, nc, seed, jitter, steps, warmu
         one_engine_ms = (time.perf_counter() - t1) / max(3, K // 2) * 1e3
     G = int(res.n_regions)
     phases = None
-    if cx.rank == 0:  # per-phase times: two extra passes with events around everything (never part of `value`)
+    if cx.rank == 0 and full:  # per-phase times: two extra passes with events around everything (never part of `value`)
         with ya.Engine(device_id=cx.dev_index, flags=ya.F_TIMING_FULL | cx.args.flags) as fe:
             fe.run_device(*ptrs)
             fe.timing_total(reset=True)
@@ -338,8 +384,7 @@ def resident_block(cx, label, profile, R, O, cov, nc, seed, jitter, steps, warmu
             tf, nf = fe.timing_total()
             phases = {k: tf[k] / max(nf, 1) for k in ("plan_ms", "sweep_small_ms", "sweep_medium_ms", "sweep_general_ms",
                                                       "compact_ms", "total_ms") if tf.get(k)}
-    got = eng.fetch()
-    ok, n_checked = oracle_sample_parity(got, off, iv, ln, cov, nc, parity_reads)
+    ok, n_checked = oracle_sample_parity(eng.fetch(), off, iv, ln, cov, nc, parity_reads) if full else (None, 0)
     per_rank = {"rank": cx.rank, "reads": Rl, "intervals": Il, "ms_per_step": mine / K * 1e3, "regions": G,
                 "parity_sample_ok": ok, "sampled_reads": n_checked}
     if dist is not None:
@@ -378,8 +423,9 @@ def resident_block(cx, label, profile, R, O, cov, nc, seed, jitter, steps, warmu
            "paths": dict({k: int(t.get(k, 0)) for k in PATH_KEYS}, runs=K),
            "healthy_reads_rank0": int(t.get("fused_reads", 0)) - int(t.get("deferred_reads", 0)) if screened else None,
            "deferred_reads_rank0": int(t.get("deferred_reads", 0)) if screened else None,
-           "parity": ("bit-exact vs oracle on %d sampled reads per rank" % per_rank["sampled_reads"])
-                     if all(p["parity_sample_ok"] for p in allr) else "MISMATCH vs oracle",
+           "parity": (NOT_CHECKED if not full else
+                      ("bit-exact vs oracle on %d sampled reads per rank" % per_rank["sampled_reads"])
+                      if all(p["parity_sample_ok"] for p in allr) else "MISMATCH vs oracle"),
            "roofline": roofline_of(ya, t, K, Rl, G, traffic_key if cx.world == 1 else None,
                                    "rank 0's launches; input %.2f GB per GPU%s" % (8 * Il / 1e9,
                                    ", outside the 256 MiB Infinity Cache" if 8 * Il > (256 << 20) else
@@ -388,11 +434,12 @@ def resident_block(cx, label, profile, R, O, cov, nc, seed, jitter, steps, warmu
     return out, keep
 
 
-def small_batches_block(cx, jitter=0, chimeras=0):
+def small_batches_block(cx, jitter=0, chimeras=0, full=True, dump_dir=None):
     """configs[1]: rounds 1-2's headline.  Batches of 100 k reads pipelined over `--engines` engines on one GPU
     from one host thread (yacrd_engine_submit_device / _wait): the plan / follow-on kernels, the
     launch gaps and the host's turn of one batch hide behind the sweep of another.  Weak scaling when N > 1 (every
-    rank its own batch)."""
+    rank its own batch).  full: also the runs of their own (one batch at a time, one launch, per-phase times) and
+    the oracle's check."""
     ya, host, torch, args = cx.ya, cx.host, cx.torch, cx.args
     profile, R, O, cov, nc, seed = CONFIGS[1]
     if args.weak:
@@ -459,9 +506,12 @@ def small_batches_block(cx, jitter=0, chimeras=0):
                 if k2.endswith("_ms") or k2 in ("timed_runs", "screened"):
                     t[k2] = [a + b for a, b in zip(t[k2], v)] if isinstance(v, list) else t[k2] + v
     assert n_timed == K
+    if dump_dir:  # (every rank its own batch: rank k's reads are k * R ... in the sample's numbering)
+        dump_outputs(cx, engs[(K - 1) % NE].fetch(), cx.rank * R, cx.world * R, dump_dir)
     G = int(out.n_regions)
     blk = None
-    if cx.rank == 0:
+    unpredicted, one_launch, phases = None, None, None
+    if cx.rank == 0 and full:
         # one engine, no class-count prediction (the plan's counts come home before the sweeps are launched),
         # nothing in flight: what a caller with ONE batch per process sees once the inputs are in HBM (the CLI)
         with ya.Engine(device_id=cx.dev_index, flags=ya.F_NO_PREDICTION | ya.F_NO_TIMING) as ue:
@@ -499,6 +549,7 @@ def small_batches_block(cx, jitter=0, chimeras=0):
             ph, nf = fe.timing_total()
             phases = {k: ph[k] / nf for k in ("plan_ms", "sweep_small_ms", "sweep_medium_ms", "sweep_general_ms",
                                               "compact_ms", "total_ms", "fused_ms") if ph.get(k)}
+    if cx.rank == 0:
         b_alg = alg_bytes(R, I, G)
         jit = ", dovetail ends reflected (sigma %d)" % jitter if jitter else ""
         if chimeras:
@@ -533,6 +584,8 @@ def small_batches_block(cx, jitter=0, chimeras=0):
             rf["note"] += "; kernel_alone_ms / frac_alone: the same launch by its own events on one engine, one batch at a time, nothing else in flight"
         if reps > 1:
             blk["workload"] += "; the FASTEST of %d timed regions of %d steps (the host's cadence: see timed_regions_ms_per_step)" % (reps, K)
+        blk["parity"] = NOT_CHECKED
+    if cx.rank == 0 and full:
         import oracle
         want = oracle.run(offsets, intervals, lengths.astype(np.uint64), cov, nc, n_threads=usable_cpus())
         got = engs[0].fetch()
@@ -1011,8 +1064,17 @@ def main():
                     help="ranks = GPUs of this node (one process per GPU).  Without WORLD_SIZE in the environment and N > 1, "
                          "bench.py launches itself under torch.distributed.run with N ranks; under a launcher, N must equal "
                          "WORLD_SIZE (default: WORLD_SIZE, else 1)")
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps of the headline (default 20; with --weak: --small-steps)")
+    ap.add_argument("--warmup", type=int, default=None,
+                    help="untimed steps before them (default 3; with --weak: --small-warmup)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything besides the headline's timed steps: the oracle's check of the result, per-phase "
+                         "times, cpu_baseline and, at N = 1, the extra blocks (other configs, small batches, jitter, PCIe, "
+                         "end to end); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what the headline's last step computed to DIR/*.npy (a fixed, "
+                         "seeded sample of the reads; float32 / float64, at most 64 MB)")
     ap.add_argument("--config", type=int, default=4, choices=[1, 2, 3, 4],
                     help="BASELINE.json configs[k] as the headline's fixed input (default 4: the north star's 5 M reads / "
                          "500 M overlaps)")
@@ -1036,7 +1098,7 @@ def main():
     ap.add_argument("--time-every-launch", action="store_true",
                     help="small batches: events on the dominant kernel of EVERY step (default: every 8th step of an engine "
                          "when there are more than 64 steps: the events cost ~10 us per step against a 20 us kernel)")
-    ap.add_argument("--no-extras", action="store_true", help="headline only")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no extra blocks")
     ap.add_argument("--extras-file", type=str, default="", help="where the full object goes (default: bench_extras.json beside bench.py)")
     ap.add_argument("--print-extras", action="store_true", help="also print the full object, on a line BEFORE the compact one")
     ap.add_argument("--sub-steps", type=int, default=10, help="timed steps of the configs[2] / configs[3] sub-blocks")
@@ -1057,16 +1119,16 @@ def main():
     cx = Ctx(args)
     ya, host = cx.ya, cx.host
     rank, world = cx.rank, cx.world
-    extras = world == 1 and not args.no_extras
+    extras = world == 1 and args.full and not args.no_extras
     backend = cx.dist.get_backend() if cx.dist is not None else None
 
     line, head, keep_small, keep_head = None, None, None, None
     if args.weak:
-        if args.steps != ap.get_default("steps"):
+        if args.steps is not None:
             args.small_steps = args.steps
-        if args.warmup != ap.get_default("warmup"):
+        if args.warmup is not None:
             args.small_warmup = args.warmup
-        head, keep_small = small_batches_block(cx, args.jitter, args.chimeras)
+        head, keep_small = small_batches_block(cx, args.jitter, args.chimeras, full=args.full, dump_dir=args.dump_outputs)
         scaling = "weak"
     elif args.config == 1:
         ap.error("configs[1] is the --weak headline (batches of 100 k reads); --config takes 2, 3 or 4")
@@ -1076,10 +1138,12 @@ def main():
         if args.coverage is not None:
             cov = args.coverage
         label = "configs[%d]" % args.config + (" (the north star's target workload)" if args.config == 4 else "")
-        head, keep_head = resident_block(cx, label, profile, R, O, cov, nc, seed, args.jitter, args.steps,
-                                         args.warmup, 50000 if args.config == 4 else 20000,
+        head, keep_head = resident_block(cx, label, profile, R, O, cov, nc, seed, args.jitter,
+                                         20 if args.steps is None else args.steps, 3 if args.warmup is None else args.warmup,
+                                         50000 if args.config == 4 else 20000,
                                          traffic_key=None if args.jitter else "configs[%d]" % args.config,
-                                         keep_host=world == 1 and not args.no_cpu_baseline)
+                                         keep_host=world == 1 and args.full and not args.no_cpu_baseline,
+                                         full=args.full, dump_dir=args.dump_outputs)
         scaling = "strong"
     if rank == 0:
         line = {
@@ -1096,7 +1160,7 @@ def main():
             "vs_baseline": None,
             "dtype": "u32",
             "data": "synthetic",
-            "config": {"workload": ("SCALED x%g (not a measurement): " % args.scale if args.scale != 1.0 else "") + head["workload"] + "; see pcie_inclusive / end_to_end for the rates that include PCIe and the parse",
+            "config": {"workload": ("SCALED x%g (not a measurement): " % args.scale if args.scale != 1.0 else "") + head["workload"] + "; with --full, see pcie_inclusive / end_to_end for the rates that include PCIe and the parse",
                        "parallelism": "read-partition x%d, no collective" % world,
                        "torch_distributed_backend": backend if backend else "none (one process)"},
             "workload_short": ("SCALED x%g (not a measurement): " % args.scale if args.scale != 1.0 else "") + head["workload"].split(", read-partitioned")[0].split("; KERNELS ONLY")[0]

@@ -108,3 +108,75 @@ def test_compact_line_limit_is_enforced_whatever_the_blocks_hold():
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "parity", "roofline", "cpu_baseline"):
         assert k in line, k
+
+
+def _fake_result(R, seed):
+    import numpy as np
+    from yacrd_amd.engine import Result
+    rng = np.random.default_rng(seed)
+    n = rng.integers(0, 4, R)
+    bo = np.concatenate(([0], np.cumsum(n))).astype(np.uint64)
+    br = rng.integers(0, 60000, (int(bo[-1]), 2)).astype(np.uint32)
+    return Result(bo, br, rng.integers(0, 3, R).astype(np.uint8))
+
+
+def test_dump_outputs_is_a_fixed_sample_of_what_the_caller_receives(tmp_path, monkeypatch):
+    """--dump-outputs: the engine's result on a fixed, seeded sample of the reads (all of them when few), as float32 /
+    float64 .npy within the size limit, and the same files whether one rank or two held the reads."""
+    import types
+    import numpy as np
+    import bench
+    one = types.SimpleNamespace(dist=None, world=1, rank=0)
+    got = _fake_result(5000, 1)
+
+    def load(d):
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+    bench.dump_outputs(one, got, 0, 5000, str(tmp_path / "all"))
+    f = load(tmp_path / "all")
+    assert set(f) == {"read_ids", "read_type", "bad_offsets", "bad_regions", "totals"}
+    assert all(a.dtype in (np.float32, np.float64) for a in f.values())
+    assert np.array_equal(f["read_ids"], np.arange(5000)) and np.array_equal(f["read_type"], got.read_type)
+    assert np.array_equal(f["bad_offsets"], got.bad_offsets) and np.array_equal(f["bad_regions"], got.bad_regions)
+    assert f["totals"].tolist() == [5000, int(got.bad_offsets[-1])] + np.bincount(got.read_type, minlength=3).tolist()
+
+    monkeypatch.setattr(bench, "DUMP_READS", 700)  # more reads than the sample holds
+    bench.dump_outputs(one, got, 0, 5000, str(tmp_path / "a"))
+    bench.dump_outputs(one, got, 0, 5000, str(tmp_path / "b"))
+    a, b = load(tmp_path / "a"), load(tmp_path / "b")
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    ids = a["read_ids"].astype(np.int64)
+    assert len(ids) == 700 and len(np.unique(ids)) == 700 and np.all(np.diff(ids) > 0)
+    assert np.array_equal(a["read_type"], got.read_type[ids])
+    off = got.bad_offsets.astype(np.int64)
+    assert np.array_equal(np.diff(a["bad_offsets"]), (off[ids + 1] - off[ids]))
+    want = np.concatenate([got.bad_regions[off[i]:off[i + 1]] for i in ids])
+    assert np.array_equal(a["bad_regions"], want)
+
+    # two ranks, reads [0, 2000) and [2000, 5000): the same files as one rank holding them all
+    from yacrd_amd.engine import Result
+    halves = [Result(got.bad_offsets[:2001], got.bad_regions[:int(got.bad_offsets[2000])], got.read_type[:2000]),
+              Result(got.bad_offsets[2000:] - got.bad_offsets[2000], got.bad_regions[int(got.bad_offsets[2000]):],
+                     got.read_type[2000:])]
+    sent = {}
+
+    class Gather:  # (torch.distributed's all_gather_object, the two ranks called one after the other)
+        def __init__(self, rank):
+            self.rank = rank
+
+        def all_gather_object(self, out, obj):
+            sent[self.rank] = obj
+            out[:] = [sent.get(0), sent.get(1)]
+    bench.dump_outputs(types.SimpleNamespace(dist=Gather(1), world=2, rank=1), halves[1], 2000, 5000, str(tmp_path / "r"))
+    assert not os.path.exists(tmp_path / "r")  # (rank 0 writes)
+    bench.dump_outputs(types.SimpleNamespace(dist=Gather(0), world=2, rank=0), halves[0], 0, 5000, str(tmp_path / "r"))
+    r = load(tmp_path / "r")
+    for k in a:
+        assert np.array_equal(a[k], r[k]), k
+
+    others = 8 * 700 + 4 * 700 + 8 * 701 + 8 * 5  # read_ids, read_type, bad_offsets, totals
+    monkeypatch.setattr(bench, "DUMP_LIMIT", others + 4096 + 8 * 100)  # room for 100 regions only
+    bench.dump_outputs(one, got, 0, 5000, str(tmp_path / "cut"))
+    c = load(tmp_path / "cut")
+    assert len(c["bad_regions"]) == 100 and np.array_equal(c["bad_regions"], a["bad_regions"][:100])

@@ -28,7 +28,7 @@ def _last_json(text):
 
 
 def test_single_gpu_line_scaled(tmp_path):
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "2",
                         "--scale", "0.02", "--small-steps", "20", "--sub-steps", "3", "--sigma100-steps", "2",
                         "--extras-file", str(tmp_path / "extras.json")],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
@@ -84,6 +84,54 @@ def test_single_gpu_line_scaled(tmp_path):
         assert share is None or 0.0 <= share <= 1.0
 
 
+def test_plain_run_is_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full the run is the headline's timed steps and nothing else (no oracle, no cpu_baseline, no extra
+    blocks); --steps sets the timed steps; --dump-outputs writes what the last step computed on a fixed sample of the
+    reads — the oracle's answer on the same input, and the same files from a second run."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    import oracle
+    from yacrd_amd import host
+    dumps = []
+    for run in range(2):
+        out = tmp_path / ("dump%d" % run)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                            "--scale", "0.02", "--dump-outputs", str(out), "--extras-file", str(tmp_path / "extras.json")],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = _last_json(p.stdout)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+            assert k in line, k
+        assert line["steps"] == 7 and line["warmup"] == 2 and line["ms_per_step"] > 0
+        assert line["metric"] == "reads_per_sec_classified" and line["unit"] == "reads/s" and line["dtype"] == "u32"
+        assert "cpu_baseline" not in line and line["parity"].startswith("not checked")
+        assert line["roofline"]["timed_launches"] == 7
+        d = json.loads((tmp_path / "extras.json").read_text())
+        for k in ("configs2", "skewed", "small_batches", "jitter", "end_to_end", "pcie_inclusive", "box"):
+            assert k not in d, k
+        assert d["headline"]["phases_full_timing_ms"] is None
+        files = {f: np.load(out / f) for f in sorted(os.listdir(out))}
+        assert set(files) == {"read_ids.npy", "read_type.npy", "bad_offsets.npy", "bad_regions.npy", "totals.npy"}
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+        dumps.append(files)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+    # the same scaled configs[4] input through the oracle
+    pf, R, O, cov, nc, seed = bench.CONFIGS[4]
+    R, O = max(64, int(R * 0.02)), max(640, int(O * 0.02))
+    offsets, intervals, lengths = host.synth_csr(host.SYNTH_SEQUEL, R, O, seed)
+    bo, br, rt = oracle.run(offsets, intervals, lengths.astype(np.uint64), cov, nc, n_threads=4)
+    f = dumps[0]
+    ids = f["read_ids.npy"].astype(np.int64)
+    assert len(ids) == R and np.array_equal(ids, np.arange(R))  # (100 k reads: all of them)
+    assert np.array_equal(f["read_type.npy"], rt[ids].astype(np.float32))
+    assert np.array_equal(f["bad_offsets.npy"], bo.astype(np.float64))
+    assert np.array_equal(f["bad_regions.npy"], br.reshape(-1, 2).astype(np.float32))
+    assert f["totals.npy"].tolist() == [R, int(bo[-1])] + np.bincount(rt, minlength=3)[:3].tolist()
+
+
 @pytest.mark.parametrize("weak", [False, True])
 def test_two_ranks_on_one_device(weak, tmp_path):
     with socket.socket() as s:
@@ -92,7 +140,7 @@ def test_two_ranks_on_one_device(weak, tmp_path):
     env = dict(os.environ, YACRD_BENCH_DEVICE="0", YACRD_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "6", "--warmup", "2", "--scale", "0.03"]
+           "--gpus", "2", "--full", "--steps", "6", "--warmup", "2", "--scale", "0.03"]
     if weak:
         cmd.append("--weak")
     cmd += ["--extras-file", str(tmp_path / "extras.json")]
@@ -121,7 +169,7 @@ def test_plain_python_with_gpus_2_launches_two_ranks(tmp_path):
     env = dict(os.environ, YACRD_BENCH_DEVICE="0", YACRD_BENCH_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "5", "--warmup", "2",
                         "--scale", "0.03", "--extras-file", str(tmp_path / "extras.json")],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]

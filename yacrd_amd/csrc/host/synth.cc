@@ -87,11 +87,18 @@ void parallel_ranges(uint64_t n, unsigned T, F fn) // fn(t, begin, end) over T c
     for (auto &x : th) x.join();
 }
 
+// What draw_interval reads of a read, side by side: one cache line per read instead of four arrays
+// (configs[4]'s 5 M reads are 80 MB of them, and every line looks up two reads at random).
+struct ReadShape {
+    uint32_t len;
+    uint32_t junction; // 0 = none (2 % of reads: chimera junction)
+    uint32_t win0, win1; // win1 == 0: none (3 % of reads: only a 20 % window is covered)
+};
+
 struct Gen {
     yacrd_synth_cfg cfg;
     std::vector<uint32_t> len;      // read lengths
-    std::vector<uint32_t> junction; // 0 = none (2 % of reads: chimera junction)
-    std::vector<uint32_t> win0, win1; // win1 == 0: none (3 % of reads: only a 20 % window is covered)
+    std::vector<ReadShape> shape;
     std::vector<double> zipf_cdf;   // skewed profile
     uint64_t n_round_robin = 0;
 
@@ -99,9 +106,7 @@ struct Gen {
     {
         const uint64_t R = c.n_reads;
         len.resize(R);
-        junction.assign(R, 0);
-        win0.assign(R, 0);
-        win1.assign(R, 0);
+        shape.assign(R, ReadShape{0, 0, 0, 0});
         const uint32_t pct = (c.flags >> 16) & 0xFFu; // YACRD_SYNTH_F_CHIMERA_PCT
         const double chimera = pct ? std::min(pct, 97u) / 100.0 : 0.02;
         parallel_ranges(R, synth_threads(), [&](unsigned, uint64_t r0, uint64_t r1) {
@@ -118,14 +123,16 @@ struct Gen {
                     L = 200000.0 + rng.uniform() * 800000.0;
                 }
                 len[r] = (uint32_t)L;
+                ReadShape &sh = shape[r];
+                sh.len = len[r];
                 const double u = rng.uniform();
                 if (u < chimera) {
-                    junction[r] = (uint32_t)((0.2 + 0.6 * rng.uniform()) * L);
-                    if (junction[r] == 0) junction[r] = 1;
+                    sh.junction = (uint32_t)((0.2 + 0.6 * rng.uniform()) * L);
+                    if (sh.junction == 0) sh.junction = 1;
                 } else if (u < chimera + 0.03) {
                     const uint32_t w = std::max<uint32_t>(len[r] / 5, 2);
-                    win0[r] = (uint32_t)rng.below(len[r] - w + 1);
-                    win1[r] = win0[r] + w;
+                    sh.win0 = (uint32_t)rng.below(len[r] - w + 1);
+                    sh.win1 = sh.win0 + w;
                 }
             }
         });
@@ -143,11 +150,12 @@ struct Gen {
 
     void draw_interval(Rng &rng, uint32_t r, uint32_t &s, uint32_t &e) const
     {
-        const uint32_t L = len[r];
+        const ReadShape sh = shape[r];
+        const uint32_t L = sh.len;
         int64_t lo = 0, hi = L;
-        if (win1[r]) {
-            lo = win0[r];
-            hi = win1[r];
+        if (sh.win1) {
+            lo = sh.win0;
+            hi = sh.win1;
         }
         const int64_t span = hi - lo;
         int64_t st, en;
@@ -176,7 +184,7 @@ struct Gen {
         st = std::min(std::max(st, lo), hi - 1);
         en = std::min(std::max(en, st + 1), hi);
         const double u = (cfg.flags & 1u) ? 1.0 : rng.uniform();
-        if (u < 2e-3 && !win1[r]) {
+        if (u < 2e-3 && !sh.win1) {
             // abutting intervals without any state: snap both ends to an eighth-of-the-read grid;
             // two snapped intervals of a read often share a grid point (end of one == start of
             // the other), which is what the reference's zero-length-gap quirk needs
@@ -186,8 +194,8 @@ struct Gen {
             st = std::min(st, (int64_t)L - 1);
             en = std::min<int64_t>(std::max(en, st + 1), L);
         }
-        if (junction[r]) { // chimera: nothing crosses the junction
-            const int64_t j = junction[r];
+        if (sh.junction) { // chimera: nothing crosses the junction
+            const int64_t j = sh.junction;
             if (st < j && en > j) {
                 const int64_t cut = 10 + (int64_t)rng.below(91);
                 if ((st + en) / 2 < j) en = std::max(st + 1, j - cut);
@@ -199,11 +207,10 @@ struct Gen {
         e = (uint32_t)en;
     }
 
-    void line(uint64_t i, Line &ln) const
+    // the two reads of line i: the first draws of its stream
+    void pick(uint64_t i, Rng &rng, uint32_t &a, uint32_t &b) const
     {
         const uint64_t R = cfg.n_reads;
-        Rng rng = stream_rng(cfg.seed, 2, i);
-        uint32_t a, b;
         if (cfg.profile == YACRD_SYNTH_SKEWED && i < n_round_robin) {
             a = (uint32_t)((2 * i) % R);
             b = (uint32_t)((2 * i + 1) % R);
@@ -218,6 +225,13 @@ struct Gen {
             b = (uint32_t)rng.below(R - 1);
             if (b >= a) b++;
         }
+    }
+
+    void line(uint64_t i, Line &ln) const
+    {
+        Rng rng = stream_rng(cfg.seed, 2, i);
+        uint32_t a, b;
+        pick(i, rng, a, b);
         ln.a = a;
         ln.b = b;
         draw_interval(rng, a, ln.sa, ln.ea);
@@ -274,11 +288,12 @@ int yacrd_synth_csr(const yacrd_synth_cfg *cfg, uint64_t *offsets, uint32_t *int
     std::vector<std::vector<uint32_t>> cnt(T);
     parallel_ranges(N, T, [&](unsigned t, uint64_t i0, uint64_t i1) {
         cnt[t].assign(R, 0u);
-        Line ln;
-        for (uint64_t i = i0; i < i1; i++) {
-            g.line(i, ln);
-            cnt[t][ln.a]++;
-            cnt[t][ln.b]++;
+        for (uint64_t i = i0; i < i1; i++) { // (the reads of a line only: its intervals are drawn below)
+            Rng rng = stream_rng(g.cfg.seed, 2, i);
+            uint32_t a, b;
+            g.pick(i, rng, a, b);
+            cnt[t][a]++;
+            cnt[t][b]++;
         }
     });
     uint64_t acc = 0;
@@ -294,10 +309,29 @@ int yacrd_synth_csr(const yacrd_synth_cfg *cfg, uint64_t *offsets, uint32_t *int
         lengths[r] = g.len[r];
     }
     offsets[R] = acc;
+    constexpr uint64_t kAhead = 16;
     parallel_ranges(N, T, [&](unsigned t, uint64_t i0, uint64_t i1) {
         Line ln;
         uint32_t *k = cnt[t].data();
         for (uint64_t i = i0; i < i1; i++) { // line order inside every read, like an ingest of the PAF
+            if (i + kAhead < i1) { // (the reads of a line further on: their tables are DRAM misses, start them now)
+                Rng rng = stream_rng(g.cfg.seed, 2, i + kAhead);
+                uint32_t a, b;
+                g.pick(i + kAhead, rng, a, b);
+                __builtin_prefetch(&g.shape[a]);
+                __builtin_prefetch(&g.shape[b]);
+                __builtin_prefetch(&offsets[a]);
+                __builtin_prefetch(&offsets[b]);
+                __builtin_prefetch(&k[a], 1);
+                __builtin_prefetch(&k[b], 1);
+            }
+            if (i + kAhead / 2 < i1) { // (... and, once those have come, where its intervals go)
+                Rng rng = stream_rng(g.cfg.seed, 2, i + kAhead / 2);
+                uint32_t a, b;
+                g.pick(i + kAhead / 2, rng, a, b);
+                __builtin_prefetch(&intervals[2 * (offsets[a] + k[a])], 1);
+                __builtin_prefetch(&intervals[2 * (offsets[b] + k[b])], 1);
+            }
             g.line(i, ln);
             uint64_t p = offsets[ln.a] + k[ln.a]++;
             intervals[2 * p] = ln.sa;
