@@ -386,6 +386,48 @@ void yacrd_reads_free(yacrd_reads *r);
  * file's size; a call into warm buffers is 2-3 times faster than one that has to allocate them): this gives them back. */
 int yacrd_engine_trim(yacrd_engine *e);
 
+/* filter / extract on an OVERLAP file (Filter::run_paf / run_m4, src/editor/filter.rs:140-228; Extract::run_paf / run_m4,
+ * src/editor/extract.rs:144-232) with the decision and the compaction on the GPU (csrc/gpu_edit.hip): the host moves the text
+ * to HBM as the device parser does and brings the kept bytes back, segment by segment, while later segments are still on
+ * their way.  A record is looked at through its first field and field 5 (PAF, tab-separated) or 1 (M4 / MHAP, space-separated);
+ * an id the table does not hold is NotBad (src/stack.rs:164-169); filter keeps a record when both reads are NotBad, extract
+ * when one is not.  Kept lines come out in file order, each ended by exactly one '\n'; empty lines vanish.  The bytes are
+ * those of libyacrd_host's yacrd_edit_file on the same input and table.
+ * The table: names[name_off[r] .. name_off[r + 1]) is read r's id (unique ids: what a detection run and yacrd_report_read
+ * hand out), read_type[r] its type.
+ * YACRD_EFALLBACK, with nothing written: a '"' or a CR anywhere in the text, a line whose field count differs from the first
+ * non-empty line's or is too small to hold the second id, a line that reaches more than 4 MiB beyond its 128 MiB segment, a
+ * compressed or non-regular input, an output path that exists and is no regular file (or is the input), device memory that does
+ * not hold the text, as many bytes again and an eighth.  The caller then runs yacrd_edit_file, which knows the csv syntax, the
+ * codecs and the reference's messages.  The file form writes beside out_path and renames when the last byte is in.
+ * When in_path is the very file (device, inode, size, mtime) the engine's last yacrd_engine_ingest_overlaps parsed and its mirror
+ * is still in HBM, the text is not moved again (stats: mirror_reused = 1).
+ * op: YACRD_OP_FILTER (1) or YACRD_OP_EXTRACT (2) of yacrd_host.h; format: 0 = by name, 1 = PAF, 2 = M4 / MHAP; n_threads: copy
+ * threads as for yacrd_engine_ingest_overlaps (0 = the default).  The buffers stay with the engine: yacrd_engine_trim. */
+typedef struct {
+    uint64_t n_reads;
+    const uint64_t *name_off; /* [n_reads + 1] */
+    const char *names;
+    const uint8_t *read_type; /* [n_reads] */
+} yacrd_type_table;
+typedef struct {
+    uint64_t text_bytes, kept_bytes;
+    uint64_t n_lines; /* non-empty lines */
+    uint64_t n_kept;
+    float text_ms;   /* the text into HBM, with the kernels and the way out of all segments but the last behind it */
+    float table_ms;  /* the names up, the table built */
+    float kernel_ms; /* mark + carry + scan + pack, summed over the segments (device events) */
+    float out_ms;    /* the writer's busy time: kept bytes D2H and into the file */
+    uint32_t mirror_reused;
+} yacrd_edit_stats;
+int yacrd_engine_edit_overlaps(yacrd_engine *e, int op, const char *in_path, const char *out_path, int format, int n_threads,
+                               const yacrd_type_table *types, yacrd_edit_stats *stats /* may be NULL */);
+/* The same over text in host memory (format: 1 or 2), the kept bytes in a buffer of the library's: yacrd_edit_text_free. */
+int yacrd_engine_edit_overlaps_mem(yacrd_engine *e, int op, const char *text, uint64_t n_bytes, int format,
+                                   const yacrd_type_table *types, char **out, uint64_t *out_bytes,
+                                   yacrd_edit_stats *stats /* may be NULL */);
+void yacrd_edit_text_free(char *p);
+
 /* Copy the last device result to host (allocates like yacrd_engine_run). */
 int yacrd_engine_fetch(yacrd_engine *e, yacrd_result *out);
 

@@ -182,6 +182,17 @@ struct yacrd_engine {
     size_t paf_arena_cap = 0;
     void *paf_scratch = nullptr;                 // gpu_paf.hip's device buffers (its type), kept between calls
     void (*paf_scratch_free)(void *) = nullptr;
+    // the mirror a device parse of a whole FILE left in HBM (gpu_paf.hip: still inside its scratch), and which file it was:
+    // the overlap editor (gpu_edit.hip) edits from it when it is handed the same file, instead of moving the text again
+    struct {
+        const unsigned char *p = nullptr; // n bytes + 64 of padding
+        uint64_t n = 0, dev = 0, ino = 0;
+        int64_t mtime_s = 0, mtime_ns = 0;
+        bool valid = false;
+    } mirror;
+    void *edit_scratch = nullptr;                // gpu_edit.hip's device and pinned buffers (its type), kept between calls
+    void (*edit_scratch_free)(void *) = nullptr; // (destroy)
+    void (*edit_scratch_release)(void *) = nullptr; // (yacrd_engine_trim)
 };
 
 

@@ -1,0 +1,760 @@
+// gpu_edit.hip — filter / extract on an OVERLAP file with the decision and the compaction on the GPU
+// (include/yacrd_engine.h: yacrd_engine_edit_overlaps).
+//
+// Reference: Filter::run_paf / run_m4 (src/editor/filter.rs:140-228) and Extract::run_paf / run_m4
+// (src/editor/extract.rs:144-232): a csv reader (not flexible) over the file, the ids of columns 0 and 5 (PAF, tabs)
+// or 0 and 1 (M4 / MHAP, spaces) looked up in the bad-part table — an id it does not hold is NotBad,
+// src/stack.rs:164-169 — and the record written back when both reads are good (filter) or when one is not (extract).
+// The host loop (host/editors.cc: edit_overlaps) does that on one thread with two hash lookups per line; here the host
+// only MOVES the text (gpu_text.h: the parser's mover) and the kept bytes.  On the device:
+//   table    the reads' names uploaded once; an open-addressing table keyed by the name bytes (gp_hash), a slot names
+//            a read, an id is compared against the uploaded bytes; value = the read's type
+//   mark     32 KiB of text staged in LDS per workgroup; a thread takes the lines that START in its 128 bytes: fields
+//            counted, both ids looked up, the verdict written as one bit at the line's first byte.  Bytes are then
+//            counted where they LIE: a byte is kept when the line start at or in front of it is kept; the tile writes
+//            its kept bytes behind its first line start, the bytes in front of it (the tail of a line that began in an
+//            earlier tile) and the verdict of its last line start — which passes through tiles without one
+//   carry    a tile's incoming verdict = that of the nearest earlier tile with a line start; kept bytes per tile
+//   scan     stream.hip's device-wide exclusive scan over the tiles of the segment
+//   pack     the tile staged again, the same keep mask rebuilt from the verdict bits, kept bytes packed in LDS and
+//            stored with 16-byte stores at the tile's offset of the output buffer
+// Every line ends in exactly one '\n' (a last line without one gets it: the text is one byte longer on the device);
+// empty lines are lines that are never kept.  The kept bytes of a segment go home (pinned buffers, one writer thread,
+// in order) while later segments are still being moved and marked.  What the path does not take — a '"' or a CR
+// anywhere, a line whose field count differs from the first line's, a line more than one 4 MiB chunk longer than its
+// segment — comes back as YACRD_EFALLBACK with nothing written: the caller runs the host loop.
+#include "engine_internal.h"
+#include "gpu_text.h"
+
+#include <condition_variable>
+#include <cstdio>
+#include <cstdlib>
+
+using namespace yke;
+
+namespace yk {
+
+constexpr int kEdOver = 1024; // bytes staged beyond the tile: most lines that start in it end there
+constexpr u32 kEdNeedHost = 1u, kEdInternal = 4u;
+
+struct EdTable {
+    const unsigned char *names; // the reads' names, back to back
+    const u64 *name_off;        // [n_reads + 1]
+    const unsigned char *type;  // [n_reads]
+    u32 *slots;                 // [mask + 1]: 0 = empty, else read + 1
+    u32 mask;
+    u32 n_reads;
+};
+
+struct EdArgs {
+    const unsigned char *text;
+    u64 n;     // bytes of text
+    u64 nl;    // n, or n + 1 when the last line has no newline: position n then reads as one
+    u64 avail; // bytes [0, avail) of the mirror have landed (== n for the last segment)
+    EdTable tab;
+    uint4 *kbits;    // a bit per byte (a uint4 per 128 bytes): a KEPT line starts here
+    uint4 *tile;     // per tile: kept bytes behind its first line start, bytes in front of it, flags (1: has a start, 2: its last start is kept)
+    u32 *tile_kept;  // per tile: kept bytes
+    u32 *tile_cin;   // per tile: the line that runs into it is kept
+    const u64 *tile_off; // the segment's exclusive scan of tile_kept (entry t + seg: every segment has one more entry than tiles)
+    const u64 *seg_base; // kept bytes in front of the segment
+    unsigned char *out;
+    unsigned long long *ctl; // [0] lines (non-empty), [1] kept lines, [2] status
+    u32 tile0;       // the launch's first tile
+    u32 seg;
+    u32 delim, ib, n_fields, keep_good; // keep_good: filter (keep when both reads are good); else extract
+};
+
+__global__ __launch_bounds__(256) void ed_table_kernel(EdTable t)
+{
+    const u32 r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= t.n_reads) return;
+    const u64 o = t.name_off[r];
+    const GpBytes names{t.names};
+    u32 s = (u32)gp_hash(names, o, (u32)(t.name_off[r + 1] - o)) & t.mask;
+    while (atomicCAS(&t.slots[s], 0u, r + 1u) != 0u) s = (s + 1u) & t.mask; // (names are unique: no slot is ours already)
+}
+
+// the type of the read named text[p, p + len): 0 (NotBad) when the table does not hold it
+__device__ __forceinline__ u32 ed_lookup(const EdTable &tab, const GpText &t, u64 p, u32 len)
+{
+    u32 s = (u32)gp_hash(t, p, len) & tab.mask;
+    for (;;) {
+        const u32 v = tab.slots[s];
+        if (v == 0u) return 0u;
+        const u64 o = tab.name_off[v - 1u];
+        if (tab.name_off[v] - o == (u64)len) {
+            u32 i = 0;
+            while (i < len && (u32)tab.names[o + i] == t[p + i]) i++;
+            if (i == len) return tab.type[v - 1u];
+        }
+        s = (s + 1u) & tab.mask;
+    }
+}
+
+// bit k of the result: byte k of the 16 is `c`
+__device__ __forceinline__ u32 ed_eq16(const uint4 &v, u32 c)
+{
+    const u32 w[4] = {v.x, v.y, v.z, v.w};
+    const u32 cc = c * 0x01010101u;
+    u32 m = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const u32 x = w[k] ^ cc;
+        const u32 z = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu); // 0x80 in every byte of x that is zero
+        m |= ((((z >> 7) * 0x00204081u) >> 21) & 0xFu) << (4 * k);
+    }
+    return m;
+}
+
+// The tile [tile0, tile0 + want) -> LDS, 16 bytes per thread and step (the mirror is padded by 64 zero bytes and the last
+// step is clipped to whole 16-byte pieces inside it; an inner segment's `avail` is a chunk boundary); the newline mask of
+// the tile's kGpTile bytes -> nlm (a u16 per 16 bytes); returns whether a '"' or a CR lies in the tile.
+__device__ __forceinline__ u32 ed_stage(const EdArgs &a, u64 tile0, u32 window, unsigned char *win, unsigned short *nlm)
+{
+    const u64 lim = a.avail == a.n ? ((a.n + 63) & ~(u64)15) : a.avail;
+    const u32 want = (u32)min((u64)window, lim - tile0);
+    u32 special = 0;
+    for (u32 i = threadIdx.x * 16u; i < (u32)window; i += (u32)kGpT * 16u) {
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (i < want) v = *reinterpret_cast<const uint4 *>(a.text + tile0 + i);
+        *reinterpret_cast<uint4 *>(win + i) = v;
+        if (i < (u32)kGpTile) {
+            u32 nlb = ed_eq16(v, '\n');
+            const u64 at = tile0 + i;
+            if (a.nl > a.n && a.n >= at && a.n < at + 16u) nlb |= 1u << (u32)(a.n - at); // (the newline the last line lacks)
+            nlm[i >> 4] = (unsigned short)nlb;
+            special |= ed_eq16(v, '"') | ed_eq16(v, '\r');
+        }
+    }
+    return special;
+}
+
+struct EdMasks {
+    u64 nl[2], s[2], v[2]; // of the thread's 128 bytes: newlines, line starts, bytes in front of the text's end
+};
+// (after ed_stage and a barrier)
+__device__ __forceinline__ EdMasks ed_starts(const EdArgs &a, u64 tile0, const unsigned char *win, const unsigned short *nlm)
+{
+    EdMasks m;
+    const uint4 q = *reinterpret_cast<const uint4 *>(nlm + threadIdx.x * 8u);
+    m.nl[0] = (u64)q.x | ((u64)q.y << 32);
+    m.nl[1] = (u64)q.z | ((u64)q.w << 32);
+    const u64 lo = tile0 + (u64)threadIdx.x * 128u;
+    const u64 left = lo < a.nl ? a.nl - lo : 0;
+    m.v[0] = left >= 64 ? ~0ull : ((1ull << left) - 1ull);
+    m.v[1] = left >= 128 ? ~0ull : left > 64 ? ((1ull << (left - 64)) - 1ull) : 0ull;
+    u64 prev = 1; // position 0 starts a line; any other does when a newline precedes it
+    if (lo != 0) prev = (threadIdx.x ? (u32)win[threadIdx.x * 128u - 1u] : (u32)a.text[lo - 1]) == '\n' ? 1ull : 0ull;
+    m.s[0] = ((m.nl[0] << 1) | prev) & m.v[0];
+    m.s[1] = ((m.nl[1] << 1) | (m.nl[0] >> 63)) & m.v[1];
+    return m;
+}
+
+// bit i of the result: the nearest bit of `s` at or below i is in `k` (cin when there is none); k is a subset of s
+__device__ __forceinline__ u64 ed_smear(u64 s, u64 k, u64 cin)
+{
+    const u64 p = ~s;
+    const u64 r = ((k << 1) | cin) + p; // a carry runs from behind every kept start (or from cin) up to the next start
+    return k | (p & ~r);
+}
+__device__ __forceinline__ u64 ed_top(u64 s, u64 k) { return (k >> (63 - __clzll((long long)s))) & 1ull; } // s != 0
+
+// The keep mask of the thread's 128 bytes from line starts s and kept starts k; cin: the verdict that runs into the tile.
+// flags: bit 0 the tile has a line start, bit 1 its last one is kept (all threads get them).  sw: 4 u32 of LDS; ends with a barrier.
+__device__ __forceinline__ void ed_keep(const u64 s[2], const u64 k[2], u32 cin_tile, u32 *sw, u64 keep[2], u32 &flags)
+{
+    const bool has = (s[0] | s[1]) != 0;
+    const u64 lastv = has ? (s[1] ? ed_top(s[1], k[1]) : ed_top(s[0], k[0])) : 0ull;
+    const u64 hm = __ballot(has), vm = __ballot(lastv != 0);
+    const u32 lane = lane_id(), wv = threadIdx.x >> 6;
+    if (lane == 0) sw[wv] = hm ? (1u | ((u32)ed_top(hm, vm) << 1)) : 0u;
+    __syncthreads();
+    u32 cin = cin_tile, fl = 0;
+#pragma unroll
+    for (u32 w = 0; w < (u32)kGpT / 64u; w++) {
+        const u32 x = sw[w];
+        if (x & 1u) {
+            if (w < wv) cin = x >> 1;
+            fl = x;
+        }
+    }
+    __syncthreads();
+    const u64 lower = hm & ((1ull << lane) - 1ull);
+    u64 c0 = lower ? ed_top(lower, vm) : (u64)cin;
+    keep[0] = ed_smear(s[0], k[0], c0);
+    const u64 c1 = s[0] ? ed_top(s[0], k[0]) : c0;
+    keep[1] = ed_smear(s[1], k[1], c1);
+    flags = fl;
+}
+
+// ---- mark: the verdict of every line that starts in the tile, and the tile's kept bytes ------------------------
+__global__ __launch_bounds__(kGpT) void ed_mark_kernel(EdArgs a)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char win[kGpTile + kEdOver];
+    __shared__ __attribute__((aligned(16))) unsigned short nlm[kGpTile / 16];
+    __shared__ u32 sw[4], s_first, s_inner;
+    const u32 gt = a.tile0 + blockIdx.x;
+    const u64 tile0 = (u64)gt * (u64)kGpTile;
+    if (threadIdx.x == 0) s_first = 0xFFFFFFFFu, s_inner = 0;
+    u32 status = ed_stage(a, tile0, kGpTile + kEdOver, win, nlm) ? kEdNeedHost : 0u;
+    __syncthreads();
+    const EdMasks m = ed_starts(a, tile0, win, nlm);
+    GpText t;
+    t.lds = win, t.glob = a.text, t.t0 = tile0;
+    t.t1 = min(a.avail, tile0 + (u64)(kGpTile + kEdOver));
+    const u64 lo = tile0 + (u64)threadIdx.x * 128u;
+    u64 k[2] = {0, 0};
+    u32 lines = 0, kept = 0;
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        u64 todo = m.s[h] & ~m.nl[h]; // (an empty line is a start that is never kept)
+        while (todo) {
+            const u32 bit = (u32)__builtin_ctzll(todo);
+            todo &= todo - 1;
+            const u64 p = lo + (u64)h * 64u + bit;
+            if (p >= a.n) break; // (the newline the last line lacks is no line)
+            // fields: the first one's end, field ib's begin and end, how many
+            u32 nf = 1;
+            u64 i = p, end_a = 0, beg_b = 0, end_b = 0;
+            for (;; i++) {
+                if (i >= a.avail) {
+                    if (a.avail < a.n) status |= kEdNeedHost; // (the line reaches into text still on its way)
+                    break;
+                }
+                const u32 c = t[i];
+                if (c == '\n') break;
+                if (c == a.delim) {
+                    if (nf == 1) end_a = i;
+                    if (nf == a.ib) beg_b = i + 1;
+                    if (nf == a.ib + 1) end_b = i;
+                    nf++;
+                }
+            }
+            if (nf == a.ib + 1) end_b = i;
+            if (nf != a.n_fields || nf <= a.ib) { // (csv, not flexible: the host loop words the error)
+                status |= kEdNeedHost;
+                continue;
+            }
+            const u32 ta = ed_lookup(a.tab, t, p, (u32)(end_a - p));
+            const u32 tb = ed_lookup(a.tab, t, beg_b, (u32)(end_b - beg_b));
+            const bool both_good = ta == 0u && tb == 0u;
+            const bool keep = a.keep_good ? both_good : !both_good;
+            lines++;
+            if (keep) kept++, k[h] |= 1ull << bit;
+        }
+    }
+    a.kbits[(u64)gt * (u64)kGpT + threadIdx.x] = make_uint4((u32)k[0], (u32)(k[0] >> 32), (u32)k[1], (u32)(k[1] >> 32));
+    u64 keep[2];
+    u32 flags;
+    ed_keep(m.s, k, 0u, sw, keep, flags);
+    u32 inner = (u32)__popcll(keep[0] & m.v[0]) + (u32)__popcll(keep[1] & m.v[1]);
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        inner += (u32)__shfl_xor((int)inner, d, 64);
+        lines += (u32)__shfl_xor((int)lines, d, 64);
+        kept += (u32)__shfl_xor((int)kept, d, 64);
+    }
+    status = wave_or(status);
+    if (m.s[0] | m.s[1]) atomicMin(&s_first, threadIdx.x * 128u + (m.s[0] ? (u32)__builtin_ctzll(m.s[0]) : 64u + (u32)__builtin_ctzll(m.s[1])));
+    if (lane_id() == 0) {
+        atomicAdd(&s_inner, inner);
+        if (lines) atomicAdd(a.ctl, (unsigned long long)lines);
+        if (kept) atomicAdd(a.ctl + 1, (unsigned long long)kept);
+        if (status) atomicOr(a.ctl + 2, (unsigned long long)status);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const u32 valid = (u32)min((u64)kGpTile, a.nl - tile0);
+        a.tile[gt] = make_uint4(s_inner, min(s_first, valid), flags, 0u);
+    }
+}
+
+// ---- carry: the verdict that runs into every tile of the segment; its kept bytes ----------------------------------
+__global__ __launch_bounds__(256) void ed_carry_kernel(EdArgs a, u32 t_end)
+{
+    const u32 t = a.tile0 + blockIdx.x * 256u + threadIdx.x;
+    if (t >= t_end) return;
+    u32 cin = 0;
+    for (u32 q = t; q-- > 0u;) { // (one step, unless a line is longer than a tile)
+        const u32 f = a.tile[q].z;
+        if (f & 1u) {
+            cin = (f >> 1) & 1u;
+            break;
+        }
+    }
+    const uint4 rec = a.tile[t];
+    a.tile_kept[t] = rec.x + (cin ? rec.y : 0u);
+    a.tile_cin[t] = cin;
+}
+__global__ void ed_base_kernel(u64 *seg_base, u32 seg, const u64 *seg_total)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) seg_base[seg + 1] = seg_base[seg] + *seg_total;
+}
+
+// ---- pack: the tile's kept bytes, packed, to its place in the output ------------------------------------------------
+__global__ __launch_bounds__(kGpT) void ed_pack_kernel(EdArgs a)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char win[kGpTile];
+    __shared__ __attribute__((aligned(16))) unsigned char outb[kGpTile + 16];
+    __shared__ __attribute__((aligned(16))) unsigned short nlm[kGpTile / 16]; // newline masks, then keep masks
+    __shared__ __attribute__((aligned(16))) unsigned short poff[kGpTile / 16]; // where every 16-byte piece's kept bytes go
+    __shared__ u32 sw[4];
+    const u32 gt = a.tile0 + blockIdx.x;
+    const u64 tile0 = (u64)gt * (u64)kGpTile;
+    const u32 want_total = a.tile_kept[gt];
+    if (want_total == 0u) return; // (uniform)
+    (void)ed_stage(a, tile0, kGpTile, win, nlm);
+    __syncthreads();
+    const EdMasks m = ed_starts(a, tile0, win, nlm);
+    if (a.nl > a.n && a.n >= tile0 && a.n < tile0 + (u64)kGpTile && threadIdx.x == 0) win[a.n - tile0] = '\n';
+    const uint4 kb = a.kbits[(u64)gt * (u64)kGpT + threadIdx.x];
+    const u64 k[2] = {(u64)kb.x | ((u64)kb.y << 32), (u64)kb.z | ((u64)kb.w << 32)};
+    u64 keep[2];
+    u32 flags;
+    ed_keep(m.s, k, a.tile_cin[gt], sw, keep, flags); // (its barriers: every thread has read its nlm entries)
+    keep[0] &= m.v[0], keep[1] &= m.v[1];
+    u32 total = 0;
+    const u32 mine = (u32)__popcll(keep[0]) + (u32)__popcll(keep[1]);
+    u32 at = block_excl_add<kGpT>(mine, sw, total);
+    const u64 dst0 = a.seg_base[a.seg] + a.tile_off[(u64)gt + a.seg];
+    const u32 shift = (u32)(dst0 & 15u); // the packed bytes lie in outb as they will in memory: 16-byte pieces match
+    {
+        u32 pk[4], mk[4];
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const u32 m16 = (u32)(keep[j >> 2] >> (16 * (j & 3))) & 0xFFFFu;
+            const u32 o = at + shift;
+            at += (u32)__popc(m16);
+            if (j & 1) pk[j >> 1] |= o << 16, mk[j >> 1] |= m16 << 16;
+            else pk[j >> 1] = o, mk[j >> 1] = m16;
+        }
+        *reinterpret_cast<uint4 *>(poff + threadIdx.x * 8u) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
+        *reinterpret_cast<uint4 *>(nlm + threadIdx.x * 8u) = make_uint4(mk[0], mk[1], mk[2], mk[3]);
+    }
+    __syncthreads();
+    if (total != want_total) { // (the two passes disagree: nothing is stored)
+        if (threadIdx.x == 0) atomicOr(a.ctl + 2, (unsigned long long)kEdInternal);
+        return;
+    }
+    for (u32 piece = threadIdx.x; piece < (u32)kGpTile / 16u; piece += (u32)kGpT) {
+        u32 m16 = nlm[piece];
+        if (m16 == 0u) continue;
+        u32 o = poff[piece];
+        const uint4 v = *reinterpret_cast<const uint4 *>(win + piece * 16u);
+        const u32 w[4] = {v.x, v.y, v.z, v.w};
+        if (m16 == 0xFFFFu && (o & 3u) == 0u) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) *reinterpret_cast<u32 *>(outb + o + 4 * q) = w[q];
+        } else {
+#pragma unroll
+            for (int b = 0; b < 16; b++)
+                if ((m16 >> b) & 1u) outb[o++] = (unsigned char)(w[b >> 2] >> (8 * (b & 3)));
+        }
+    }
+    __syncthreads();
+    // outb[shift, shift + total) -> out[dst0, dst0 + total): whole 16-byte pieces wide, the two ragged ends by bytes
+    unsigned char *base = a.out + (dst0 - shift);
+    const u32 end = shift + total;
+    for (u32 q = threadIdx.x * 16u; q < end; q += (u32)kGpT * 16u) {
+        if (q >= shift && q + 16u <= end) *reinterpret_cast<uint4 *>(base + q) = *reinterpret_cast<const uint4 *>(outb + q);
+        else
+            for (u32 b = max(q, shift); b < min(q + 16u, end); b++) base[b] = outb[b];
+    }
+}
+
+} // namespace yk
+
+namespace {
+
+constexpr size_t kOutPiece = (size_t)4 << 20;
+
+struct EditScratch { // the editor's buffers; they stay with the engine (grow-only), go with yacrd_engine_trim / destroy
+    DevBuf text, out, names, name_off, types, slots, kbits, tile, tile_kept, tile_cin, tile_off, ctl, part;
+    void *pin = nullptr; // two output pieces + the per-segment control words
+    size_t pin_cap = 0;
+    void release()
+    {
+        for (DevBuf *b : {&text, &out, &names, &name_off, &types, &slots, &kbits, &tile, &tile_kept, &tile_cin, &tile_off, &ctl, &part}) b->release();
+        if (pin) (void)hipHostFree(pin);
+        pin = nullptr, pin_cap = 0;
+    }
+    ~EditScratch() { release(); }
+};
+EditScratch *edit_scratch_of(yacrd_engine *e)
+{
+    if (!e->edit_scratch) {
+        e->edit_scratch = new (std::nothrow) EditScratch();
+        e->edit_scratch_free = [](void *p) { delete static_cast<EditScratch *>(p); };
+        e->edit_scratch_release = [](void *p) { static_cast<EditScratch *>(p)->release(); };
+    }
+    return static_cast<EditScratch *>(e->edit_scratch);
+}
+
+// where the kept bytes go: a file descriptor or memory
+struct OutSink {
+    int fd = -1;
+    char *mem = nullptr;
+    u64 at = 0;
+    bool put(const char *p, size_t k)
+    {
+        if (mem) std::memcpy(mem + at, p, k);
+        else
+            for (size_t done = 0; done < k;) {
+                const ssize_t w = ::write(fd, p + done, k - done);
+                if (w < 0 && errno == EINTR) continue;
+                if (w <= 0) return false;
+                done += (size_t)w;
+            }
+        at += k;
+        return true;
+    }
+};
+
+// the field count of the first non-empty line (0: there is none) and whether the text's last byte is a newline
+bool first_line_fields(const TextSource &src, u64 n, char delim, u32 &n_fields, bool &ends_in_newline)
+{
+    n_fields = 0, ends_in_newline = true;
+    if (!n) return true;
+    char last = 0;
+    if (!src.fetch(&last, 1, n - 1)) return false;
+    ends_in_newline = last == '\n';
+    std::vector<char> buf((size_t)std::min<u64>(n, (u64)1 << 20));
+    bool in_line = false;
+    u32 nf = 0;
+    for (u64 off = 0; off < n; off += buf.size()) {
+        const size_t len = (size_t)std::min<u64>(buf.size(), n - off);
+        if (!src.fetch(buf.data(), len, off)) return false;
+        for (size_t i = 0; i < len; i++) {
+            const char c = buf[i];
+            if (c == '\n') {
+                if (in_line) {
+                    n_fields = nf;
+                    return true;
+                }
+                continue;
+            }
+            if (!in_line) in_line = true, nf = 1;
+            if (c == delim) nf++;
+        }
+    }
+    if (in_line) n_fields = nf;
+    return true;
+}
+
+struct EditJob {
+    int op = 0;
+    bool m4 = false;
+    int n_threads = 0;
+    const yacrd_type_table *types = nullptr;
+    bool use_mirror = false; // edit from the parser's mirror (the same file: checked by the caller)
+};
+
+int edit_text(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n, OutSink &sink, yacrd_edit_stats *stats)
+{
+    DeviceGuard guard(e->device);
+    EditScratch *Sp = edit_scratch_of(e);
+    if (!Sp) return fail(YACRD_ENOMEM, "host allocation failed");
+    EditScratch &S = *Sp;
+    const yacrd_type_table &tt = *job.types;
+    const u64 R = tt.n_reads;
+    if (R >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "more reads than the device table holds");
+    if (R && (!tt.name_off || !tt.names || !tt.read_type)) return fail(YACRD_EINVAL, "the type table is incomplete");
+    const u64 name_bytes = R ? tt.name_off[R] : 0;
+    const char delim = job.m4 ? ' ' : '\t';
+    const u32 ib = job.m4 ? 1u : 5u;
+    u32 n_fields = 0;
+    bool ends_nl = true;
+    if (!first_line_fields(src, n, delim, n_fields, ends_nl)) return fail(YACRD_EINVAL, "read error in the overlap file");
+    if (n_fields && n_fields <= ib) return fail(YACRD_EFALLBACK, "the first line has too few fields: the host loop words the error");
+    const u64 nl = n + (ends_nl ? 0 : 1);
+    const u64 n_tiles = (nl + yk::kGpTile - 1) / yk::kGpTile;
+    if (n_tiles >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "file too large for the device editor");
+    const size_t n_segs = (size_t)((n + kTextChunk * kTextSeg - 1) / (kTextChunk * kTextSeg));
+    u64 cap = 1024;
+    while (cap < 2 * R) cap <<= 1;
+    const double t_start = now_ms();
+    {
+        // HBM: the text (unless the parser's mirror serves), as many bytes again for what is kept, a bit per byte, the table
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            const double have = (double)free_b + (double)S.text.cap + (double)S.out.cap + (double)S.kbits.cap + (double)S.names.cap + (double)S.slots.cap;
+            const double need = (job.use_mirror ? 0.0 : (double)n) + (double)nl * 1.125 + (double)nl / 8.0 * 1.125 + (double)name_bytes * 1.125 +
+                                (double)cap * 4.0 + (double)R * 10.0 + (double)n_tiles * 40.0 + (double)((size_t)64 << 20);
+            if (need > have) return fail(YACRD_EFALLBACK, "the file is too large to be edited in this device's free memory: the host loop streams it");
+        }
+    }
+    // ---- buffers
+    const void *mirror_before = S.text.p;
+    if (!job.use_mirror) HIP_TRY(S.text.reserve((size_t)n + 64));
+    const bool blit = !job.use_mirror && S.text.p != mirror_before; // (a fresh mirror fills faster by copy kernel: gpu_paf.hip)
+    if (!job.use_mirror) HIP_TRY(hipMemsetAsync(S.text.as<char>() + n, 0, 64, e->stream));
+    HIP_TRY(S.out.reserve((size_t)nl + 64));
+    HIP_TRY(S.kbits.reserve((size_t)(n_tiles + 1) * yk::kGpT * sizeof(uint4)));
+    HIP_TRY(S.tile.reserve((size_t)(n_tiles + 1) * sizeof(uint4)));
+    HIP_TRY(S.tile_kept.reserve((size_t)(n_tiles + 1) * sizeof(u32)));
+    HIP_TRY(S.tile_cin.reserve((size_t)(n_tiles + 1) * sizeof(u32)));
+    HIP_TRY(S.tile_off.reserve((size_t)(n_tiles + n_segs + 2) * sizeof(u64)));
+    const size_t ctl_words = 8 + n_segs + 2;
+    HIP_TRY(S.ctl.reserve(ctl_words * sizeof(u64)));
+    HIP_TRY(hipMemsetAsync(S.ctl.p, 0, ctl_words * sizeof(u64), e->stream));
+    const size_t pin_need = 2 * kOutPiece + (n_segs + 2) * 4 * sizeof(u64);
+    if (S.pin_cap < pin_need) {
+        if (S.pin) (void)hipHostFree(S.pin);
+        S.pin = nullptr, S.pin_cap = 0;
+        HIP_TRY(hipHostMalloc(&S.pin, pin_need));
+        S.pin_cap = pin_need;
+    }
+    char *pin_out[2] = {(char *)S.pin, (char *)S.pin + kOutPiece};
+    volatile u64 *h_seg = reinterpret_cast<volatile u64 *>((char *)S.pin + 2 * kOutPiece); // per segment: lines, kept, status, kept bytes so far
+    // ---- the table
+    HIP_TRY(S.names.reserve((size_t)name_bytes + 64));
+    HIP_TRY(S.name_off.reserve((size_t)(R + 1) * sizeof(u64)));
+    HIP_TRY(S.types.reserve((size_t)R + 64));
+    HIP_TRY(S.slots.reserve((size_t)cap * sizeof(u32)));
+    HIP_TRY(hipMemsetAsync(S.slots.p, 0, (size_t)cap * sizeof(u32), e->stream));
+    yk::EdTable tab{};
+    tab.names = S.names.as<unsigned char>(), tab.name_off = S.name_off.as<u64>(), tab.type = S.types.as<unsigned char>();
+    tab.slots = S.slots.as<u32>(), tab.mask = (u32)(cap - 1), tab.n_reads = (u32)R;
+    if (R) {
+        if (name_bytes)
+            if (const int rch = h2d(e, S.names.p, tt.names, (size_t)name_bytes)) return rch;
+        if (const int rch = h2d(e, S.name_off.p, tt.name_off, (size_t)(R + 1) * sizeof(u64))) return rch;
+        if (const int rch = h2d(e, S.types.p, tt.read_type, (size_t)R)) return rch;
+        hipLaunchKernelGGL(yk::ed_table_kernel, dim3((u32)((R + 255) / 256)), dim3(256), 0, e->stream, tab);
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const double t_table = now_ms();
+
+    yk::EdArgs ga{};
+    ga.text = job.use_mirror ? e->mirror.p : S.text.as<unsigned char>();
+    ga.n = n, ga.nl = nl;
+    ga.tab = tab;
+    ga.kbits = S.kbits.as<uint4>(), ga.tile = S.tile.as<uint4>(), ga.tile_kept = S.tile_kept.as<u32>(), ga.tile_cin = S.tile_cin.as<u32>();
+    ga.tile_off = S.tile_off.as<u64>();
+    ga.ctl = S.ctl.as<unsigned long long>();
+    u64 *seg_base = S.ctl.as<u64>() + 8;
+    ga.seg_base = seg_base;
+    ga.out = S.out.as<unsigned char>();
+    ga.delim = (u32)(unsigned char)delim, ga.ib = ib, ga.n_fields = n_fields, ga.keep_good = job.op == 1 ? 1u : 0u;
+
+    // ---- per segment: mark, carry, scan, pack on the engine's stream; the writer thread takes it from the segment's event
+    std::vector<hipEvent_t> ev0(n_segs, nullptr), ev1(n_segs, nullptr);
+    hipStream_t wstream = nullptr;
+    hipEvent_t wev[2] = {nullptr, nullptr};
+    std::atomic<int> bad(0); // 1 a HIP call failed, 2 the output could not be written, 3 the text is not for this path
+    std::atomic<size_t> dispatched(0);
+    std::atomic<bool> no_more(false);
+    bool setup_ok = hipStreamCreateWithFlags(&wstream, hipStreamNonBlocking) == hipSuccess;
+    for (int b = 0; b < 2; b++) setup_ok = setup_ok && hipEventCreateWithFlags(&wev[b], hipEventDisableTiming) == hipSuccess;
+    for (size_t s = 0; s < n_segs; s++)
+        setup_ok = setup_ok && hipEventCreate(&ev0[s]) == hipSuccess && hipEventCreate(&ev1[s]) == hipSuccess;
+    double out_busy_ms = 0;
+    auto launch_segment = [&](u64 seg_begin, u64 seg_end, u64 avail) {
+        const size_t s = (size_t)(seg_begin / (kTextChunk * kTextSeg));
+        const u32 t0 = (u32)(seg_begin / yk::kGpTile), t1 = seg_end >= n ? (u32)n_tiles : (u32)(seg_end / yk::kGpTile);
+        ga.avail = avail, ga.tile0 = t0, ga.seg = (u32)s;
+        bool ok = hipEventRecord(ev0[s], e->stream) == hipSuccess;
+        if (t1 > t0) {
+            hipLaunchKernelGGL(yk::ed_mark_kernel, dim3(t1 - t0), dim3(yk::kGpT), 0, e->stream, ga);
+            hipLaunchKernelGGL(yk::ed_carry_kernel, dim3((t1 - t0 + 255) / 256), dim3(256), 0, e->stream, ga, t1);
+        }
+        u64 *seg_off = S.tile_off.as<u64>() + t0 + s;
+        ok = ok && scan_u32_to_u64(e, S.tile_kept.as<u32>() + t0, (u64)(t1 - t0), seg_off, S.part) == YACRD_OK;
+        hipLaunchKernelGGL(yk::ed_base_kernel, dim3(1), dim3(64), 0, e->stream, seg_base, (u32)s, seg_off + (t1 - t0));
+        if (t1 > t0) hipLaunchKernelGGL(yk::ed_pack_kernel, dim3(t1 - t0), dim3(yk::kGpT), 0, e->stream, ga);
+        ok = ok && hipMemcpyAsync((void *)(h_seg + 4 * s), S.ctl.p, 3 * sizeof(u64), hipMemcpyDeviceToHost, e->stream) == hipSuccess;
+        ok = ok && hipMemcpyAsync((void *)(h_seg + 4 * s + 3), seg_base + s + 1, sizeof(u64), hipMemcpyDeviceToHost, e->stream) == hipSuccess;
+        ok = ok && hipEventRecord(ev1[s], e->stream) == hipSuccess;
+        if (!ok) bad = 1;
+        dispatched.store(s + 1, std::memory_order_release);
+    };
+    auto writer = [&]() {
+        if (hipSetDevice(e->device) != hipSuccess) bad = 1;
+        u64 from = 0;
+        for (size_t s = 0; s < n_segs && !bad.load(); s++) {
+            while (dispatched.load(std::memory_order_acquire) <= s && !no_more.load() && !bad.load()) {
+                struct timespec ts = {0, 50000};
+                nanosleep(&ts, nullptr);
+            }
+            if (dispatched.load(std::memory_order_acquire) <= s || bad.load()) break;
+            if (hipEventSynchronize(ev1[s]) != hipSuccess) {
+                bad = 1;
+                break;
+            }
+            if (h_seg[4 * s + 2] != 0) { // (a quote, a CR, a line of another shape: nothing more is written)
+                bad = 3;
+                break;
+            }
+            const u64 upto = h_seg[4 * s + 3];
+            if (upto < from || upto > nl) {
+                bad = 1;
+                break;
+            }
+            const double t0 = now_ms();
+            // [from, upto) of the output buffer, piece by piece: one flies while the other is written
+            const u64 n_pieces = (upto - from + kOutPiece - 1) / kOutPiece;
+            auto fly = [&](u64 k) {
+                const u64 o = from + k * kOutPiece;
+                const size_t len = (size_t)std::min<u64>(kOutPiece, upto - o);
+                if (hipMemcpyAsync(pin_out[k & 1], S.out.as<char>() + o, len, hipMemcpyDeviceToHost, wstream) != hipSuccess ||
+                    hipEventRecord(wev[k & 1], wstream) != hipSuccess)
+                    bad = 1;
+            };
+            if (n_pieces) fly(0);
+            for (u64 k = 0; k < n_pieces && !bad.load(); k++) {
+                if (hipEventSynchronize(wev[k & 1]) != hipSuccess) {
+                    bad = 1;
+                    break;
+                }
+                if (k + 1 < n_pieces) fly(k + 1);
+                const u64 o = from + k * kOutPiece;
+                if (!sink.put(pin_out[k & 1], (size_t)std::min<u64>(kOutPiece, upto - o))) bad = 2;
+            }
+            if (wstream) (void)hipStreamSynchronize(wstream);
+            from = upto;
+            out_busy_ms += now_ms() - t0;
+        }
+    };
+    int moved = 0;
+    if (setup_ok) {
+        std::thread wt(writer);
+        if (job.use_mirror) {
+            for (size_t s = 0; s < n_segs && !bad.load(); s++)
+                launch_segment((u64)s * kTextChunk * kTextSeg, (u64)(s + 1) * kTextChunk * kTextSeg, n);
+        } else {
+            moved = move_text(e, src, 0, n, S.text.as<char>(), blit, job.n_threads,
+                              [&](u64 seg_begin, u64 seg_end, u64 avail) { launch_segment(seg_begin, seg_end, avail); });
+        }
+        no_more = true;
+        const double t_text_done = now_ms();
+        wt.join();
+        (void)hipStreamSynchronize(e->stream);
+        if (stats) stats->text_ms = job.use_mirror ? 0.0f : (float)(t_text_done - t_table);
+    }
+    float kernel_ms = 0;
+    if (setup_ok && !bad.load() && !moved)
+        for (size_t s = 0; s < n_segs; s++) {
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, ev0[s], ev1[s]) == hipSuccess) kernel_ms += ms;
+        }
+    if (wstream) (void)hipStreamDestroy(wstream);
+    for (hipEvent_t x : wev)
+        if (x) (void)hipEventDestroy(x);
+    for (size_t s = 0; s < n_segs; s++) {
+        if (ev0[s]) (void)hipEventDestroy(ev0[s]);
+        if (ev1[s]) (void)hipEventDestroy(ev1[s]);
+    }
+    (void)hipGetLastError();
+    if (!setup_ok) return fail(YACRD_ENODEV, "overlap editor: a HIP stream or event could not be created");
+    if (moved == 2) return fail(YACRD_EINVAL, "read error in the overlap file");
+    if (moved == 3) return fail(YACRD_ENOMEM, "overlap text to HBM: no pinned memory");
+    if (moved || bad.load() == 1) return fail(YACRD_ENODEV, "overlap editor: a HIP call failed");
+    if (bad.load() == 2) return fail(YACRD_EINVAL, "Error during writing of the output file");
+    u64 h_lines = 0, h_kept = 0, h_status = 0, h_bytes = 0;
+    if (n_segs) {
+        h_lines = h_seg[4 * (n_segs - 1)], h_kept = h_seg[4 * (n_segs - 1) + 1], h_status = h_seg[4 * (n_segs - 1) + 2];
+        h_bytes = h_seg[4 * (n_segs - 1) + 3];
+    }
+    if (bad.load() == 3 || (h_status & yk::kEdNeedHost))
+        return fail(YACRD_EFALLBACK, "the text holds a '\"', a CR, a line whose field count differs from the first line's or one that is "
+                                     "megabytes long: the host loop decides");
+    if (h_status) return fail(YACRD_EINTERNAL, "overlap editor: the mark and the pack pass disagree");
+    if (sink.at != h_bytes) return fail(YACRD_EINTERNAL, "overlap editor: fewer bytes written than kept");
+    if (stats) {
+        stats->text_bytes = n;
+        stats->kept_bytes = h_bytes;
+        stats->n_lines = h_lines;
+        stats->n_kept = h_kept;
+        stats->table_ms = (float)(t_table - t_start);
+        stats->kernel_ms = kernel_ms;
+        stats->out_ms = (float)out_busy_ms;
+        stats->mirror_reused = job.use_mirror ? 1u : 0u;
+    }
+    return YACRD_OK;
+}
+
+int edit_args(yacrd_engine *e, int op, const yacrd_type_table *types, yacrd_edit_stats *stats)
+{
+    if (!e || !types) return fail(YACRD_EINVAL, "null argument");
+    if (op != 1 && op != 2) return fail(YACRD_EINVAL, "op: 1 = filter, 2 = extract");
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (e->pending.active || e->host_pending) return fail(YACRD_EINVAL, "the engine has a submitted batch pending");
+    return YACRD_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int yacrd_engine_edit_overlaps(yacrd_engine *e, int op, const char *in_path, const char *out_path, int format, int n_threads,
+                               const yacrd_type_table *types, yacrd_edit_stats *stats)
+{
+    if (const int rca = edit_args(e, op, types, stats)) return rca;
+    if (!in_path || !out_path) return fail(YACRD_EINVAL, "null argument");
+    EditJob job;
+    job.op = op, job.n_threads = n_threads, job.types = types;
+    if (const int rcf = overlap_format(in_path, format, job.m4)) return rcf;
+    const int fd = ::open(in_path, O_RDONLY);
+    if (fd < 0) return fail(YACRD_EFALLBACK, std::string("cannot open ") + in_path + ": the host loop words the error");
+    struct FdGuard {
+        int fd;
+        ~FdGuard() { ::close(fd); }
+    } fdg{fd};
+    struct stat st, ost;
+    if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) return fail(YACRD_EFALLBACK, "not a regular file: the host loop reads it");
+    if (is_compressed_magic(fd)) return fail(YACRD_EFALLBACK, "a compressed file: the host loop inflates it and deflates what it keeps");
+    // the output: written beside its place and moved there when every byte is in it — a text that turns out not to be for
+    // this path (the last segment may say so) leaves nothing behind.  Anything but a new or a regular file is the host loop's.
+    if (lstat(out_path, &ost) == 0) {
+        if (!S_ISREG(ost.st_mode)) return fail(YACRD_EFALLBACK, "the output is not a regular file: the host loop writes it");
+        if (ost.st_dev == st.st_dev && ost.st_ino == st.st_ino) return fail(YACRD_EFALLBACK, "input and output are one file: the host loop's case");
+    }
+    std::string tmp = std::string(out_path) + ".XXXXXX";
+    const int ofd = mkstemp(&tmp[0]);
+    if (ofd < 0) return fail(YACRD_EFALLBACK, std::string("cannot create a file beside ") + out_path + ": the host loop words the error");
+    {
+        const mode_t um = umask(0);
+        umask(um);
+        (void)fchmod(ofd, 0666 & ~um);
+    }
+    job.use_mirror = e->mirror.valid && e->mirror.p && e->mirror.n == (u64)st.st_size && e->mirror.dev == (u64)st.st_dev &&
+                     e->mirror.ino == (u64)st.st_ino && e->mirror.mtime_s == (int64_t)st.st_mtim.tv_sec &&
+                     e->mirror.mtime_ns == (int64_t)st.st_mtim.tv_nsec;
+    TextSource src;
+    src.fd = fd;
+    OutSink sink;
+    sink.fd = ofd;
+    int rc = edit_text(e, job, src, (u64)st.st_size, sink, stats);
+    if (::close(ofd) != 0 && rc == YACRD_OK) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
+    if (rc == YACRD_OK && ::rename(tmp.c_str(), out_path) != 0) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
+    if (rc != YACRD_OK) (void)::unlink(tmp.c_str());
+    return rc;
+}
+
+int yacrd_engine_edit_overlaps_mem(yacrd_engine *e, int op, const char *text, uint64_t n, int format, const yacrd_type_table *types,
+                                   char **out, uint64_t *out_bytes, yacrd_edit_stats *stats)
+{
+    if (const int rca = edit_args(e, op, types, stats)) return rca;
+    if ((!text && n) || !out || !out_bytes) return fail(YACRD_EINVAL, "null argument");
+    *out = nullptr, *out_bytes = 0;
+    EditJob job;
+    job.op = op, job.types = types;
+    if (const int rcf = overlap_format(nullptr, format, job.m4)) return rcf;
+    TextSource src;
+    src.mem = text ? text : "";
+    OutSink sink;
+    sink.mem = (char *)std::malloc((size_t)n + 2);
+    if (!sink.mem) return fail(YACRD_ENOMEM, "host allocation failed");
+    const int rc = edit_text(e, job, src, n, sink, stats);
+    if (rc != YACRD_OK) {
+        std::free(sink.mem);
+        return rc;
+    }
+    *out = sink.mem, *out_bytes = sink.at;
+    return YACRD_OK;
+}
+
+void yacrd_edit_text_free(char *p) { std::free(p); }
+
+} // extern "C"

@@ -23,6 +23,7 @@
 // u32 — makes the call return YACRD_EFALLBACK: the caller runs the host parser, which knows the csv crate's
 // whole syntax and the error messages.  Plain files only (the codecs live in the host library).
 #include "engine_internal.h"
+#include "gpu_text.h"
 #include "radix_sort.h"
 
 #include <fcntl.h>
@@ -68,13 +69,6 @@ struct GpArgs {
                         // inside a line that belongs to the range before (yacrd_engines_ingest_overlaps)
 };
 
-constexpr int kGpT = 256; // threads per workgroup
-
-// pinned host memory -> the mirror, by a kernel (see the host side: used when the mirror is a fresh allocation)
-__global__ __launch_bounds__(256) void gp_blit_kernel(uint4 *__restrict__ dst, const uint4 *__restrict__ src, u64 n16)
-{
-    for (u64 i = (u64)blockIdx.x * 256u + threadIdx.x; i < n16; i += (u64)gridDim.x * 256u) dst[i] = src[i];
-}
 constexpr u32 kNeedHost = 1u, kTableFull = 2u;
 
 // ---- pass 1: how many lines, and is there anything the fast path must not see ------------------------------
@@ -117,22 +111,7 @@ __global__ __launch_bounds__(kGpT) void gp_scan_kernel(GpArgs a)
 // global memory, one cache line per lane and instruction, ran this kernel at 24 GB/s).  A record needs nothing
 // behind its ninth field, so a line of any length costs its start only; fields that reach beyond the staged
 // window (ids of hundreds of bytes) are read from global memory.
-constexpr int kGpTile = kGpT * 128, kGpOver = 1024;
-
-struct GpText {
-    const unsigned char *lds, *glob;
-    u64 t0, t1; // the staged window [t0, t1)
-    __device__ __forceinline__ u32 operator[](u64 i) const { return i - t0 < t1 - t0 ? lds[i - t0] : glob[i]; }
-};
-
-__device__ __forceinline__ u64 gp_hash(const GpText &t, u64 p, u32 n)
-{
-    u64 h = 0xcbf29ce484222325ull ^ ((u64)n * 0x9E3779B97F4A7C15ull);
-    for (u32 i = 0; i < n; i++) h = (h ^ t[p + i]) * 0x100000001b3ull;
-    h ^= h >> 29;
-    h *= 0xbf58476d1ce4e5b9ull;
-    return h ^ (h >> 32);
-}
+constexpr int kGpOver = 1024; // (kGpTile, GpText and gp_hash: gpu_text.h)
 // decimal u64 with an optional '+', at least one digit, then the delimiter (or, for the last field, the line's end);
 // clears `ok` when the field is anything else.  `le` = the text's end: a line ends at '\n' (or "\r\n").
 __device__ __forceinline__ u64 gp_uint(const GpText &t, u64 &q, u64 n, u64 limit, bool last, bool &ok, u32 dl)
@@ -574,10 +553,6 @@ __global__ __launch_bounds__(256) void gm_own_kernel(u32 *own, u32 n_reads, u32 
 
 namespace {
 
-double now_ms()
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 // (first position, slot) pairs by first position, on the engine's stream: radix_sort.h, as many eight-bit passes as keys
 // below `key_bound` need.  The passes go back and forth between the two pairs of arrays (the inputs are scratch: clobbered);
@@ -608,14 +583,6 @@ int sort_by_first_position(yacrd_engine *e, u64 *keys, u64 *keys_out, u32 *slots
         std::swap(va, vb);
     }
     return YACRD_OK;
-}
-// gzip / bzip2 / xz (the magic bytes niffler looks at, src/util.rs:57-70)
-bool is_compressed_magic(int fd)
-{
-    unsigned char mg[6] = {0};
-    const ssize_t k = ::pread(fd, mg, sizeof mg, 0);
-    return k >= 2 && ((mg[0] == 0x1f && mg[1] == 0x8b) || (k >= 3 && mg[0] == 'B' && mg[1] == 'Z' && mg[2] == 'h') ||
-                      (k >= 6 && mg[0] == 0xFD && std::memcmp(mg + 1, "7zXZ", 4) == 0 && mg[5] == 0));
 }
 
 struct Scratch { // the call's device buffers; they stay with the engine (grow-only) and go when it is destroyed
@@ -655,7 +622,9 @@ int yacrd_engine_trim(yacrd_engine *e)
     if (!e) return fail(YACRD_EINVAL, "engine is null");
     if (e->pending.active || e->host_pending) return fail(YACRD_EINVAL, "the engine has a submitted batch pending");
     DeviceGuard guard(e->device);
+    e->mirror.valid = false;
     if (e->paf_scratch) static_cast<Scratch *>(e->paf_scratch)->release();
+    if (e->edit_scratch && e->edit_scratch_release) e->edit_scratch_release(e->edit_scratch);
     return YACRD_OK;
 }
 
@@ -677,46 +646,14 @@ int yacrd_engine_ingest_paf(yacrd_engine *e, const char *path, int n_threads, ui
 } // extern "C"
 
 namespace {
-// where the text comes from: a file (pread) or memory (a compressed file the host has inflated)
-struct TextSource {
-    int fd = -1;
-    const char *mem = nullptr;
-    // `len` bytes at `off` into dst; false = read error
-    bool fetch(char *dst, size_t len, u64 off) const
-    {
-        if (mem) {
-            std::memcpy(dst, mem + off, len);
-            return true;
-        }
-        size_t got = 0;
-        while (got < len) {
-            const ssize_t k = ::pread(fd, dst + got, len - got, (off_t)(off + got));
-            if (k < 0 && errno == EINTR) continue;
-            if (k <= 0) return false;
-            got += (size_t)k;
-        }
-        return true;
-    }
-};
+// (TextSource — a file or memory —, the mover and the format rule: gpu_text.h)
 int ingest_text(yacrd_engine *e, const TextSource &src, u64 n, bool m4, int n_threads, uint32_t coverage, double not_coverage,
                 yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats);
 } // namespace
 
 extern "C" {
 
-static int ingest_format(const char *path, int format, bool &m4)
-{
-    if (format == 0) { // by file name, like util::get_file_type (src/util.rs:39-55)
-        if (!path) return fail(YACRD_EINVAL, "format 0 (by name) needs a file name");
-        const std::string name(path);
-        auto has = [&](const char *x) { return name.find(x) != std::string::npos; };
-        format = (has(".m4") || has(".mhap")) ? 2 : has(".paf") ? 1 : 0;
-        if (format == 0) return fail(YACRD_EINVAL, std::string("cannot tell the overlap format of ") + path);
-    }
-    if (format != 1 && format != 2) return fail(YACRD_EINVAL, "format: 0 = by name, 1 = PAF, 2 = M4");
-    m4 = format == 2;
-    return YACRD_OK;
-}
+static int ingest_format(const char *path, int format, bool &m4) { return overlap_format(path, format, m4); }
 
 int yacrd_engine_ingest_overlaps(yacrd_engine *e, const char *path, int format, int n_threads, uint32_t coverage,
                                  double not_coverage, yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats)
@@ -742,7 +679,15 @@ int yacrd_engine_ingest_overlaps(yacrd_engine *e, const char *path, int format, 
         return fail(YACRD_EFALLBACK, "a compressed file: inflate it (yacrd_text_from_file + yacrd_engine_ingest_overlaps_mem) or take the host parser");
     TextSource src;
     src.fd = fd;
-    return ingest_text(e, src, (u64)st.st_size, m4, n_threads, coverage, not_coverage, out, reads, stats);
+    const int rc = ingest_text(e, src, (u64)st.st_size, m4, n_threads, coverage, not_coverage, out, reads, stats);
+    if (rc == YACRD_OK && e->paf_scratch) { // the whole file lies in the mirror: the overlap editor may start from it (gpu_edit.hip)
+        e->mirror.p = static_cast<Scratch *>(e->paf_scratch)->text.as<unsigned char>();
+        e->mirror.n = (u64)st.st_size;
+        e->mirror.dev = (u64)st.st_dev, e->mirror.ino = (u64)st.st_ino;
+        e->mirror.mtime_s = (int64_t)st.st_mtim.tv_sec, e->mirror.mtime_ns = (int64_t)st.st_mtim.tv_nsec;
+        e->mirror.valid = e->mirror.p != nullptr;
+    }
+    return rc;
 }
 
 int yacrd_engine_ingest_overlaps_mem(yacrd_engine *e, const char *text, uint64_t n, int format, int n_threads, uint32_t coverage,
@@ -789,6 +734,7 @@ int parse_range(yacrd_engine *e, const TextSource &src, u64 file_n, u64 begin, u
     Scratch *Sp = scratch_of(e);
     if (!Sp) return fail(YACRD_ENOMEM, "host allocation failed");
     Scratch &S = *Sp;
+    e->mirror.valid = false; // (the mirror is about to be rewritten)
     // the mirror holds the range and, behind it, up to one chunk more of the file: a line that starts in the range ends there
     // (or the parse says so: kNeedHost)
     constexpr u64 kOverhang = (u64)4 << 20;
@@ -872,87 +818,14 @@ int parse_range(yacrd_engine *e, const TextSource &src, u64 file_n, u64 begin, u
     // segment of kSeg chunks to the scan + parse kernels as soon as it (and the chunk behind it: a tile's overhang,
     // the byte after a CR) has landed — the engine's stream waits for the chunks' copy events, the host for nothing
     {
-        // (the pinned arena stays with the engine: pinning 100 MB costs more than moving 367 MB through it)
         // (128 MiB per scan + parse launch.  The two kernels take 0.9 ms for 367 MB, so what the overlap buys is small;
         // segments of 16 / 32 MiB got in the way of the copy threads: tools/paf_matrix.py, profiles/r03/paf_matrix.log)
-        constexpr size_t kChunk = (size_t)4 << 20, kSeg = 32;
-        static_assert(kChunk % yk::kGpTile == 0, "segments begin on tile boundaries");
-        const size_t n_chunks = (size_t)((n + kChunk - 1) / kChunk);
-        unsigned T = n_threads > 0 ? (unsigned)n_threads : 6u; // (more threads only get in each other's way: 367 MB in 10 ms with 4-8)
-        T = (unsigned)std::max<size_t>(1, std::min<size_t>(std::min(T, 32u), std::max<size_t>(n_chunks, 1)));
-        const size_t n_buf = (size_t)2 * T;
-        if (e->paf_arena_cap < n_buf * kChunk) {
-            if (e->paf_arena) (void)hipHostFree(e->paf_arena);
-            e->paf_arena = nullptr;
-            e->paf_arena_cap = 0;
-            HIP_TRY(hipHostMalloc(&e->paf_arena, n_buf * kChunk));
-            e->paf_arena_cap = n_buf * kChunk;
-        }
-        char *arena = (char *)e->paf_arena;
-        std::vector<hipStream_t> copy(T, nullptr);
-        std::vector<hipEvent_t> ev(n_chunks, nullptr); // one per chunk: recorded behind its copy
-        std::unique_ptr<std::atomic<int>[]> landed(new std::atomic<int>[n_chunks + 1]);
-        for (size_t c = 0; c <= n_chunks; c++) landed[c].store(0);
-        std::atomic<size_t> next(0);
-        std::atomic<int> bad(0);
-        for (unsigned t = 0; t < T; t++)
-            if (hipStreamCreateWithFlags(&copy[t], hipStreamNonBlocking) != hipSuccess) bad = 1;
-        for (size_t c = 0; c < n_chunks; c++)
-            if (hipEventCreateWithFlags(&ev[c], hipEventDisableTiming) != hipSuccess) bad = 1;
-        auto work = [&](unsigned t) { // thread t owns buffers 2t and 2t + 1: one fills while the other flies
-            if (hipSetDevice(e->device) != hipSuccess) bad = 1;
-            long prev[2] = {-1, -1}; // the chunk that last flew from each buffer
-            for (int turn = 0; !bad.load(); turn ^= 1) {
-                const size_t c = next.fetch_add(1);
-                if (c >= n_chunks) break;
-                const size_t b = (size_t)2 * t + (size_t)turn;
-                if (prev[turn] >= 0 && hipEventSynchronize(ev[(size_t)prev[turn]]) != hipSuccess) bad = 1;
-                char *dst = arena + b * kChunk;
-                const size_t off = c * kChunk, clen = (size_t)std::min<u64>(kChunk, n - off);
-                if (!src.fetch(dst, clen, begin + (u64)off)) bad = 2;
-                if (bad.load()) break;
-                if (blit && (clen & 15)) std::memset(dst + clen, 0, 16 - (clen & 15)); // (the file's last piece: zeros, not leftovers, behind it)
-                if (blit) { // (the arena's buffers are 4 MiB: whole 16-byte pieces; the mirror is padded by 64 bytes)
-                    hipLaunchKernelGGL(yk::gp_blit_kernel, dim3(256), dim3(256), 0, copy[t], reinterpret_cast<uint4 *>(S.text.as<char>() + off),
-                                       reinterpret_cast<const uint4 *>(dst), (u64)((clen + 15) / 16));
-                    if (hipEventRecord(ev[c], copy[t]) != hipSuccess) bad = 1;
-                } else if (hipMemcpyAsync(S.text.as<char>() + off, dst, clen, hipMemcpyHostToDevice, copy[t]) != hipSuccess ||
-                           hipEventRecord(ev[c], copy[t]) != hipSuccess)
-                    bad = 1;
-                prev[turn] = (long)c;
-                landed[c].store(1, std::memory_order_release); // (its event is recorded: the dispatcher may wait on it)
-            }
-            if (copy[t]) (void)hipStreamSynchronize(copy[t]);
-        };
-        std::vector<std::thread> th;
-        if (!bad.load())
-            for (unsigned t = 0; t < T; t++) th.emplace_back(work, t);
-        // the dispatcher
-        size_t waited = 0;
-        for (size_t c0 = 0; c0 < n_chunks && !bad.load(); c0 += kSeg) {
-            const size_t c1 = std::min(c0 + kSeg, n_chunks), need = std::min(c1 + 1, n_chunks);
-            while (waited < need && !bad.load()) {
-                if (!landed[waited].load(std::memory_order_acquire)) {
-                    struct timespec ts = {0, 20000};
-                    nanosleep(&ts, nullptr);
-                    continue;
-                }
-                if (hipStreamWaitEvent(e->stream, ev[waited], 0) != hipSuccess) bad = 1;
-                waited++;
-            }
-            if (bad.load()) break;
-            if ((u64)c0 * kChunk < parse_end)
-                launch_segment((u64)c0 * kChunk, std::min<u64>(parse_end, (u64)c1 * kChunk), std::min<u64>(n, (u64)need * kChunk));
-        }
-        for (auto &x : th) x.join();
-        for (hipStream_t s2 : copy)
-            if (s2) (void)hipStreamDestroy(s2);
-        if (bad.load()) (void)hipStreamSynchronize(e->stream); // (kernels may still wait on events about to go)
-        for (hipEvent_t x : ev)
-            if (x) (void)hipEventDestroy(x);
-        if (bad.load() == 2) return fail(YACRD_EINVAL, "read error in the overlap file");
-        if (bad.load()) return fail(YACRD_ENODEV, "PAF text to HBM: a HIP call failed");
-        (void)hipGetLastError();
+        const int bad = move_text(e, src, begin, n, S.text.as<char>(), blit, n_threads, [&](u64 seg_begin, u64 seg_end, u64 avail) {
+            if (seg_begin < parse_end) launch_segment(seg_begin, std::min<u64>(parse_end, seg_end), avail);
+        });
+        if (bad == 2) return fail(YACRD_EINVAL, "read error in the overlap file");
+        if (bad == 3) return fail(YACRD_ENOMEM, "PAF text to HBM: no pinned memory");
+        if (bad) return fail(YACRD_ENODEV, "PAF text to HBM: a HIP call failed");
     }
     const double t_text = now_ms();
 

@@ -1,0 +1,204 @@
+// gpu_text.h — what the translation units that work on overlap TEXT in HBM share: gpu_paf.hip (the device parser) and
+// gpu_edit.hip (filter / extract on overlap files).  Where the text comes from, the mover (pread -> pinned 4 MiB chunks
+// -> the mirror in HBM, a segment handed on as soon as it has landed), the staged-window accessor and the id hash.
+#pragma once
+#include "engine_internal.h"
+
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <time.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cerrno>
+#include <chrono>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <thread>
+#include <vector>
+
+namespace yk {
+
+constexpr int kGpT = 256;           // threads per workgroup
+constexpr int kGpTile = kGpT * 128; // bytes of text per workgroup: a thread takes the lines that START in its 128 bytes
+
+// pinned host memory -> the mirror, by a kernel (used when the mirror is a fresh allocation: see move_text's callers)
+static __global__ __launch_bounds__(256) void gp_blit_kernel(uint4 *__restrict__ dst, const uint4 *__restrict__ src, u64 n16)
+{
+    for (u64 i = (u64)blockIdx.x * 256u + threadIdx.x; i < n16; i += (u64)gridDim.x * 256u) dst[i] = src[i];
+}
+
+// text through a window staged in LDS; what lies outside the window comes from global memory
+struct GpText {
+    const unsigned char *lds, *glob;
+    u64 t0, t1; // the staged window [t0, t1)
+    __device__ __forceinline__ u32 operator[](u64 i) const { return i - t0 < t1 - t0 ? lds[i - t0] : glob[i]; }
+};
+// plain bytes in global memory, as a text
+struct GpBytes {
+    const unsigned char *p;
+    __device__ __forceinline__ u32 operator[](u64 i) const { return p[i]; }
+};
+
+template <class Text>
+__device__ __forceinline__ u64 gp_hash(const Text &t, u64 p, u32 n)
+{
+    u64 h = 0xcbf29ce484222325ull ^ ((u64)n * 0x9E3779B97F4A7C15ull);
+    for (u32 i = 0; i < n; i++) h = (h ^ t[p + i]) * 0x100000001b3ull;
+    h ^= h >> 29;
+    h *= 0xbf58476d1ce4e5b9ull;
+    return h ^ (h >> 32);
+}
+
+} // namespace yk
+
+namespace yke {
+
+inline double now_ms()
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// gzip / bzip2 / xz (the magic bytes niffler looks at, src/util.rs:57-70)
+inline bool is_compressed_magic(int fd)
+{
+    unsigned char mg[6] = {0};
+    const ssize_t k = ::pread(fd, mg, sizeof mg, 0);
+    return k >= 2 && ((mg[0] == 0x1f && mg[1] == 0x8b) || (k >= 3 && mg[0] == 'B' && mg[1] == 'Z' && mg[2] == 'h') ||
+                      (k >= 6 && mg[0] == 0xFD && std::memcmp(mg + 1, "7zXZ", 4) == 0 && mg[5] == 0));
+}
+
+// 0 = by file name, like util::get_file_type (src/util.rs:39-55); 1 = PAF; 2 = M4 / MHAP
+inline int overlap_format(const char *path, int format, bool &m4)
+{
+    if (format == 0) {
+        if (!path) return fail(YACRD_EINVAL, "format 0 (by name) needs a file name");
+        const std::string name(path);
+        auto has = [&](const char *x) { return name.find(x) != std::string::npos; };
+        format = (has(".m4") || has(".mhap")) ? 2 : has(".paf") ? 1 : 0;
+        if (format == 0) return fail(YACRD_EINVAL, std::string("cannot tell the overlap format of ") + path);
+    }
+    if (format != 1 && format != 2) return fail(YACRD_EINVAL, "format: 0 = by name, 1 = PAF, 2 = M4");
+    m4 = format == 2;
+    return YACRD_OK;
+}
+
+// where the text comes from: a file (pread) or memory (a compressed file the host has inflated)
+struct TextSource {
+    int fd = -1;
+    const char *mem = nullptr;
+    // `len` bytes at `off` into dst; false = read error
+    bool fetch(char *dst, size_t len, u64 off) const
+    {
+        if (mem) {
+            std::memcpy(dst, mem + off, len);
+            return true;
+        }
+        size_t got = 0;
+        while (got < len) {
+            const ssize_t k = ::pread(fd, dst + got, len - got, (off_t)(off + got));
+            if (k < 0 && errno == EINTR) continue;
+            if (k <= 0) return false;
+            got += (size_t)k;
+        }
+        return true;
+    }
+};
+
+constexpr size_t kTextChunk = (size_t)4 << 20; // what one pread and one copy move
+constexpr size_t kTextSeg = 32;                // chunks per segment handed on (128 MiB)
+static_assert(kTextChunk % yk::kGpTile == 0, "segments begin on tile boundaries");
+
+// Bytes [begin, begin + n) of `src` -> mirror[0, n): threads pread chunks into the engine's pinned arena, every chunk crosses
+// PCIe at once into the mirror (by copy kernel when `blit`: a fresh allocation; by hipMemcpyAsync into a warm one);
+// THIS thread calls on_segment(seg_begin, seg_end, avail) — byte offsets into the mirror, seg_end a chunk boundary that
+// may lie beyond n — for every kTextSeg chunks as soon as they and the chunk behind them have landed (`avail`: the bytes
+// [0, avail) have), with the engine's stream made to wait for those chunks' copy events: what on_segment launches on
+// e->stream sees the text, the host waits for nothing.  Returns 0, 1 (a HIP call failed), 2 (read error) or 3 (no pinned memory).
+template <class OnSegment>
+int move_text(yacrd_engine *e, const TextSource &src, u64 begin, u64 n, char *mirror, bool blit, int n_threads, OnSegment &&on_segment)
+{
+    // (the pinned arena stays with the engine: pinning 100 MB costs more than moving 367 MB through it)
+    constexpr size_t kChunk = kTextChunk, kSeg = kTextSeg;
+    const size_t n_chunks = (size_t)((n + kChunk - 1) / kChunk);
+    unsigned T = n_threads > 0 ? (unsigned)n_threads : 6u; // (more threads only get in each other's way: 367 MB in 10 ms with 4-8)
+    T = (unsigned)std::max<size_t>(1, std::min<size_t>(std::min(T, 32u), std::max<size_t>(n_chunks, 1)));
+    const size_t n_buf = (size_t)2 * T;
+    if (e->paf_arena_cap < n_buf * kChunk) {
+        if (e->paf_arena) (void)hipHostFree(e->paf_arena);
+        e->paf_arena = nullptr;
+        e->paf_arena_cap = 0;
+        if (hipHostMalloc(&e->paf_arena, n_buf * kChunk) != hipSuccess) {
+            e->paf_arena = nullptr;
+            return 3;
+        }
+        e->paf_arena_cap = n_buf * kChunk;
+    }
+    char *arena = (char *)e->paf_arena;
+    std::vector<hipStream_t> copy(T, nullptr);
+    std::vector<hipEvent_t> ev(n_chunks, nullptr); // one per chunk: recorded behind its copy
+    std::unique_ptr<std::atomic<int>[]> landed(new std::atomic<int>[n_chunks + 1]);
+    for (size_t c = 0; c <= n_chunks; c++) landed[c].store(0);
+    std::atomic<size_t> next(0);
+    std::atomic<int> bad(0);
+    for (unsigned t = 0; t < T; t++)
+        if (hipStreamCreateWithFlags(&copy[t], hipStreamNonBlocking) != hipSuccess) bad = 1;
+    for (size_t c = 0; c < n_chunks; c++)
+        if (hipEventCreateWithFlags(&ev[c], hipEventDisableTiming) != hipSuccess) bad = 1;
+    auto work = [&](unsigned t) { // thread t owns buffers 2t and 2t + 1: one fills while the other flies
+        if (hipSetDevice(e->device) != hipSuccess) bad = 1;
+        long prev[2] = {-1, -1}; // the chunk that last flew from each buffer
+        for (int turn = 0; !bad.load(); turn ^= 1) {
+            const size_t c = next.fetch_add(1);
+            if (c >= n_chunks) break;
+            const size_t b = (size_t)2 * t + (size_t)turn;
+            if (prev[turn] >= 0 && hipEventSynchronize(ev[(size_t)prev[turn]]) != hipSuccess) bad = 1;
+            char *dst = arena + b * kChunk;
+            const size_t off = c * kChunk, clen = (size_t)std::min<u64>(kChunk, n - off);
+            if (!src.fetch(dst, clen, begin + (u64)off)) bad = 2;
+            if (bad.load()) break;
+            if (blit && (clen & 15)) std::memset(dst + clen, 0, 16 - (clen & 15)); // (the file's last piece: zeros, not leftovers, behind it)
+            if (blit) { // (the arena's buffers are 4 MiB: whole 16-byte pieces; the mirror is padded by 64 bytes)
+                hipLaunchKernelGGL(yk::gp_blit_kernel, dim3(256), dim3(256), 0, copy[t], reinterpret_cast<uint4 *>(mirror + off),
+                                   reinterpret_cast<const uint4 *>(dst), (u64)((clen + 15) / 16));
+                if (hipEventRecord(ev[c], copy[t]) != hipSuccess) bad = 1;
+            } else if (hipMemcpyAsync(mirror + off, dst, clen, hipMemcpyHostToDevice, copy[t]) != hipSuccess ||
+                       hipEventRecord(ev[c], copy[t]) != hipSuccess)
+                bad = 1;
+            prev[turn] = (long)c;
+            landed[c].store(1, std::memory_order_release); // (its event is recorded: the dispatcher may wait on it)
+        }
+        if (copy[t]) (void)hipStreamSynchronize(copy[t]);
+    };
+    std::vector<std::thread> th;
+    if (!bad.load())
+        for (unsigned t = 0; t < T; t++) th.emplace_back(work, t);
+    // the dispatcher
+    size_t waited = 0;
+    for (size_t c0 = 0; c0 < n_chunks && !bad.load(); c0 += kSeg) {
+        const size_t c1 = std::min(c0 + kSeg, n_chunks), need = std::min(c1 + 1, n_chunks);
+        while (waited < need && !bad.load()) {
+            if (!landed[waited].load(std::memory_order_acquire)) {
+                struct timespec ts = {0, 20000};
+                nanosleep(&ts, nullptr);
+                continue;
+            }
+            if (hipStreamWaitEvent(e->stream, ev[waited], 0) != hipSuccess) bad = 1;
+            waited++;
+        }
+        if (bad.load()) break;
+        on_segment((u64)c0 * kChunk, (u64)c1 * kChunk, std::min<u64>(n, (u64)need * kChunk));
+    }
+    for (auto &x : th) x.join();
+    for (hipStream_t s2 : copy)
+        if (s2) (void)hipStreamDestroy(s2);
+    if (bad.load()) (void)hipStreamSynchronize(e->stream); // (kernels may still wait on events about to go)
+    for (hipEvent_t x : ev)
+        if (x) (void)hipEventDestroy(x);
+    (void)hipGetLastError();
+    return bad.load();
+}
+
+} // namespace yke

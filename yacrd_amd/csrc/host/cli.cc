@@ -263,7 +263,32 @@ int main(int argc, char **argv)
         const int op = sub == "scrubb" ? YACRD_OP_SCRUBB
                                        : sub == "filter" ? YACRD_OP_FILTER
                                                          : sub == "extract" ? YACRD_OP_EXTRACT : YACRD_OP_SPLIT;
-        if (yacrd_edit_file(op, sub_in.c_str(), sub_out.c_str(), &bp)) die(yacrd_host_last_error());
+        // filter / extract on a PAF / M4 / MHAP: the text goes to HBM, the device decides and packs what is kept
+        // (yacrd_engine_edit_overlaps; from the parser's mirror when it is the file the detection just read).  Whatever that
+        // path does not take — compressed, quoted, CRs, a line of another shape — comes back with nothing written and takes
+        // the host loop below, which knows the whole syntax and the messages.  YACRD_NO_DEVICE_EDITOR=1: the host loop (A/B).
+        int dev_edit = YACRD_EFALLBACK;
+        const char *no_ed = std::getenv("YACRD_NO_DEVICE_EDITOR");
+        const bool sub_ovl = has(sub_in, ".m4") || has(sub_in, ".mhap") || has(sub_in, ".paf");
+        if (sub_ovl && (op == YACRD_OP_FILTER || op == YACRD_OP_EXTRACT) && !(no_ed && *no_ed == '1')) {
+            const yacrd_type_table tt = {bp.n_reads, bp.name_off, bp.names, bp.read_type};
+            yacrd_edit_stats es{};
+            const char *ct = std::getenv("YACRD_COPY_THREADS");
+            dev_edit = yacrd_engine_edit_overlaps(engines[0], op, sub_in.c_str(), sub_out.c_str(), 0, ct && *ct ? std::max(0, std::atoi(ct)) : 0,
+                                                  &tt, &es);
+            if (dev_edit == YACRD_ENOMEM) {
+                std::fprintf(stderr, "[INFO] device editor: %s; falling back to the host loop\n", yacrd_last_error());
+                for (yacrd_engine *en : engines) (void)yacrd_engine_trim(en);
+                dev_edit = YACRD_EFALLBACK;
+            }
+            if (dev_edit != YACRD_OK && dev_edit != YACRD_EFALLBACK) die(yacrd_last_error());
+            if (dev_edit == YACRD_OK && timing)
+                std::fprintf(stderr, "[info] device editor: %llu of %llu lines kept, %llu of %llu bytes, text %.1f ms, table %.1f ms, kernels %.1f ms, "
+                                     "out %.1f ms, mirror_reused=%u\n",
+                             (unsigned long long)es.n_kept, (unsigned long long)es.n_lines, (unsigned long long)es.kept_bytes,
+                             (unsigned long long)es.text_bytes, es.text_ms, es.table_ms, es.kernel_ms, es.out_ms, es.mirror_reused);
+        }
+        if (dev_edit != YACRD_OK && yacrd_edit_file(op, sub_in.c_str(), sub_out.c_str(), &bp)) die(yacrd_host_last_error());
         stage("edit");
     }
 

@@ -47,6 +47,7 @@ EXPORTED_SYMBOLS = [
     "yacrd_stream_finish", "yacrd_stream_last_stats", "yacrd_stream_reset", "yacrd_stream_close",
     "yacrd_engine_ingest_paf", "yacrd_engine_ingest_overlaps", "yacrd_engine_ingest_overlaps_mem", "yacrd_engines_ingest_overlaps",
     "yacrd_engines_ingest_overlaps_mem", "yacrd_reads_free", "yacrd_engine_trim",
+    "yacrd_engine_edit_overlaps", "yacrd_engine_edit_overlaps_mem", "yacrd_edit_text_free",
     "yacrd_stream_device_of", "yacrd_stream_group_open", "yacrd_stream_group_sink", "yacrd_stream_group_finish",
     "yacrd_stream_group_last_stats", "yacrd_stream_group_reset", "yacrd_stream_group_close",
 ]
@@ -72,6 +73,15 @@ class _Reads(ctypes.Structure):
 class _IngestStats(ctypes.Structure):
     _fields_ = [("text_bytes", ctypes.c_uint64), ("n_records", ctypes.c_uint64), ("n_reads", ctypes.c_uint64)] + \
                [(n, ctypes.c_float) for n in ("text_ms", "parse_ms", "build_ms", "run_ms", "d2h_ms")]
+
+
+class _TypeTable(ctypes.Structure):
+    _fields_ = [("n_reads", ctypes.c_uint64), ("name_off", ctypes.c_void_p), ("names", ctypes.c_void_p), ("read_type", ctypes.c_void_p)]
+
+
+class _EditStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("text_bytes", "kept_bytes", "n_lines", "n_kept")] + \
+               [(n, ctypes.c_float) for n in ("text_ms", "table_ms", "kernel_ms", "out_ms")] + [("mirror_reused", ctypes.c_uint32)]
 
 
 class _Cfg(ctypes.Structure):
@@ -261,6 +271,13 @@ def load_library():
                                                       ctypes.POINTER(_Result), ctypes.POINTER(_Reads), ctypes.POINTER(_IngestStats)]
     lib.yacrd_debug_sort_pairs.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]
     lib.yacrd_engine_trim.argtypes = [ctypes.c_void_p]
+    lib.yacrd_engine_edit_overlaps.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
+                                               ctypes.POINTER(_TypeTable), ctypes.POINTER(_EditStats)]
+    lib.yacrd_engine_edit_overlaps_mem.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                                   ctypes.POINTER(_TypeTable), ctypes.POINTER(ctypes.c_void_p),
+                                                   ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_EditStats)]
+    lib.yacrd_edit_text_free.argtypes = [ctypes.c_void_p]
+    lib.yacrd_edit_text_free.restype = None
     lib.yacrd_reads_free.argtypes = [ctypes.POINTER(_Reads)]
     lib.yacrd_reads_free.restype = None
     lib.yacrd_stream_reset.argtypes = [ctypes.c_void_p]
@@ -526,8 +543,55 @@ class Engine:
             out[n] = list(v) if hasattr(v, "__len__") else int(v)
         return out
 
+    def _type_table(self, names, read_type):
+        """(names, read_type) -> a yacrd_type_table and what keeps its memory alive; names: str or bytes, one per read."""
+        blobs = [n if isinstance(n, bytes) else n.encode("utf-8", "surrogateescape") for n in names]
+        off = np.zeros(len(blobs) + 1, np.uint64)
+        if blobs:
+            off[1:] = np.cumsum([len(b) for b in blobs], dtype=np.uint64)
+        blob = ctypes.create_string_buffer(b"".join(blobs), int(off[-1]) + 1)
+        types = np.ascontiguousarray(read_type, dtype=np.uint8)
+        if types.shape != (len(blobs),):
+            raise ValueError("read_type: one type per name")
+        tt = _TypeTable(len(blobs), off.ctypes.data, ctypes.addressof(blob), types.ctypes.data)
+        return tt, (off, blob, types)
+
+    def _edited(self, rc, st):
+        if rc == E_FALLBACK:
+            raise NeedsHostParser(self._lib.yacrd_last_error().decode())
+        _check(self._lib, rc)
+        self.edit_stats = {n: getattr(st, n) for n, _ in _EditStats._fields_}
+        return self.edit_stats
+
+    def edit_overlaps(self, op, src, out_path, names, read_type, fmt=0, n_threads=0):
+        """yacrd_engine_edit_overlaps: filter (op 1) / extract (op 2) the overlap file `src` into `out_path` on the GPU, by the
+        types of the reads `names`; returns the stats (also self.edit_stats).  Raises NeedsHostParser, with nothing written,
+        when the input is the host loop's (host.edit_file)."""
+        tt, keep = self._type_table(names, read_type)
+        st = _EditStats()
+        rc = self._lib.yacrd_engine_edit_overlaps(self._h, int(op), os.fsencode(src), os.fsencode(out_path), int(fmt), int(n_threads),
+                                                  ctypes.byref(tt), ctypes.byref(st))
+        del keep
+        return self._edited(rc, st)
+
+    def edit_overlaps_text(self, op, text, names, read_type, fmt):
+        """yacrd_engine_edit_overlaps_mem: the same over `text` (bytes; fmt 1 = PAF, 2 = M4 / MHAP) -> the kept bytes; the
+        stats are in self.edit_stats."""
+        tt, keep = self._type_table(names, read_type)
+        st = _EditStats()
+        buf = ctypes.create_string_buffer(bytes(text), len(text) + 1)
+        out, n_out = ctypes.c_void_p(), ctypes.c_uint64()
+        rc = self._lib.yacrd_engine_edit_overlaps_mem(self._h, int(op), ctypes.addressof(buf), len(text), int(fmt), ctypes.byref(tt),
+                                                      ctypes.byref(out), ctypes.byref(n_out), ctypes.byref(st))
+        del keep
+        self._edited(rc, st)
+        try:
+            return ctypes.string_at(out.value, int(n_out.value)) if n_out.value else b""
+        finally:
+            self._lib.yacrd_edit_text_free(out)
+
     def trim(self):
-        """yacrd_engine_trim: give the device parser's buffers back."""
+        """yacrd_engine_trim: give the device parser's and the overlap editor's buffers back."""
         _check(self._lib, self._lib.yacrd_engine_trim(self._h))
 
     def fetch(self):
