@@ -428,6 +428,46 @@ int yacrd_engine_edit_overlaps_mem(yacrd_engine *e, int op, const char *text, ui
                                    yacrd_edit_stats *stats /* may be NULL */);
 void yacrd_edit_text_free(char *p);
 
+/* ---- gzip output compressed on the GPU (csrc/gpu_deflate.hip, csrc/deflate_block.h) -----------------------------------
+ * Text -> a BGZF stream (SAM spec 4.1; every gzip reader reads it as gzip, and it inflates member-parallel): the text is
+ * cut into blocks of 65 280 bytes, one workgroup turns a block into one member (LZ77 matches + a dynamic Huffman code
+ * built for the block, or a stored block when that does not shrink it; CRC-32 on the device), the members are packed
+ * end to end in HBM and the 28-byte EOF member closes the stream.  The bytes are a pure function of the text. */
+typedef struct {
+    uint64_t in_bytes, out_bytes, n_members;   /* members without the EOF marker */
+    uint64_t n_stored;                         /* members written as stored blocks */
+    float h2d_ms, kernel_ms, d2h_ms, write_ms; /* kernel_ms from device events, summed over segments */
+} yacrd_gzip_stats;
+
+/* host memory in, one BGZF stream out in a buffer of the library's (yacrd_edit_text_free) */
+int yacrd_engine_gzip_mem(yacrd_engine *e, const char *data, uint64_t n_bytes,
+                          char **out, uint64_t *out_bytes, yacrd_gzip_stats *stats /* may be NULL */);
+
+#ifndef YACRD_BYTE_SINK_DEFINED
+#define YACRD_BYTE_SINK_DEFINED
+typedef struct {
+    void *ctx;
+    int (*write)(void *ctx, const char *p, uint64_t n); /* non-zero = stop */
+} yacrd_byte_sink;
+#endif
+/* A file written as it is produced: bytes arrive through write(), leave as BGZF.  write() copies into a pinned segment
+ * buffer; a full segment (segment_bytes, rounded to whole blocks; 0 = 512 blocks) goes to the device and is compressed
+ * while the caller fills the other of two buffers; its members are fetched and appended to the file when the next segment
+ * is due.  n_buffers is accepted for callers that size a deeper pipeline and is not used yet: one segment is in flight at
+ * a time, two buffers are pinned whatever it says.  The result does not depend on segment_bytes or on how the caller slices its writes.  All
+ * device and pinned memory is taken in open (YACRD_ENOMEM: nothing was written, the caller can fall back); the buffers
+ * stay with the engine (yacrd_engine_trim returns them once the writer is gone).  The file is written beside out_path
+ * and renamed in close.  One writer per engine at a time; the engine runs nothing else meanwhile. */
+typedef struct yacrd_gzip_writer yacrd_gzip_writer;
+int yacrd_gzip_writer_open(yacrd_engine *e, const char *out_path, uint64_t segment_bytes /* 0 = default */,
+                           uint32_t n_buffers /* 0 = default */, yacrd_gzip_writer **out);
+int yacrd_gzip_writer_write(yacrd_gzip_writer *w, const char *p, uint64_t n);
+/* a sink whose write() is yacrd_gzip_writer_write (for libyacrd_host's yacrd_edit_file_to); valid while the writer lives */
+int yacrd_gzip_writer_sink(yacrd_gzip_writer *w, yacrd_byte_sink *sink);
+/* flush, EOF marker, rename; the writer is gone afterwards whatever is returned (on failure nothing is left at out_path) */
+int yacrd_gzip_writer_close(yacrd_gzip_writer *w, yacrd_gzip_stats *stats /* may be NULL */);
+void yacrd_gzip_writer_abort(yacrd_gzip_writer *w); /* nothing is left at out_path */
+
 /* Copy the last device result to host (allocates like yacrd_engine_run). */
 int yacrd_engine_fetch(yacrd_engine *e, yacrd_result *out);
 

@@ -107,6 +107,23 @@ int yacrd_edit_file(int op, const char *in_path, const char *out_path, const yac
  * files take the one-thread loop. */
 int yacrd_edit_file_mt(int op, const char *in_path, const char *out_path, const yacrd_badparts_view *bp, int n_threads);
 
+/* Somebody who takes bytes in order (the engine library's yacrd_gzip_writer hands one out: the edited text leaves as BGZF
+ * compressed on the GPU, and this library still holds no GPU code). */
+#ifndef YACRD_BYTE_SINK_DEFINED
+#define YACRD_BYTE_SINK_DEFINED
+typedef struct {
+    void *ctx;
+    int (*write)(void *ctx, const char *p, uint64_t n); /* non-zero = stop, the edit fails */
+} yacrd_byte_sink;
+#endif
+/* yacrd_edit_file_mt with the edited, UNCOMPRESSED bytes going to `sink` instead of a file.  The input may be plain or
+ * compressed (it is inflated as in yacrd_edit_file).  Same bytes, same order as yacrd_edit_file writes into a plain file.
+ * One thread edits whatever n_threads says: the sink takes its bytes in order from one caller.  After a write() that
+ * returned non-zero the sink is not called again and the call fails. */
+int yacrd_edit_file_to(int op, const char *in_path, const yacrd_badparts_view *bp, int n_threads, const yacrd_byte_sink *sink);
+/* what the file's magic bytes say: 0 none (or unreadable), 1 gzip (BGZF included), 2 bzip2, 3 xz */
+int yacrd_file_compression(const char *path);
+
 /* FromReport (src/stack.rs:176-257): a .yacrd report back into the BadPart table.  read_type is
  * left NULL: classify with yacrd_engine_classify() and the -n of the current invocation. */
 typedef struct yacrd_report yacrd_report;
@@ -128,6 +145,16 @@ typedef struct {
 } yacrd_text;
 int yacrd_text_from_file(const char *path, int n_threads, yacrd_text *out);
 void yacrd_text_free(yacrd_text *t);
+
+/* ---- the device deflate encoder's text, compiled for the host (csrc/deflate_block.h) ------------------------------------
+ * One thread plays the 256 of a workgroup: slow, and byte for byte what yacrd_engine_gzip_mem gives for the same input —
+ * a BGZF stream (members of at most 65 280 bytes of text, LZ77 + a dynamic Huffman code per member, the 28-byte EOF
+ * member last).  For tests and for looking at the encoder without a GPU.  `out`: yacrd_bytes_free. */
+int yacrd_bgzf_encode_host(const char *data, uint64_t n, char **out, uint64_t *out_bytes);
+void yacrd_bytes_free(char *p);
+/* The encoder's code-length construction: freq[n] -> len[n] with no length above `limit` (n in 2..286, limit in 5..15,
+ * 2^limit >= n).  Fewer than two used symbols are given company, as zlib does, so the code is always complete. */
+int yacrd_deflate_code_lengths(const uint32_t *freq, uint32_t n, uint32_t limit, uint8_t *len);
 
 /* ---- synthetic workloads ------------------------------------------------------ */
 enum { YACRD_SYNTH_ONT = 0, YACRD_SYNTH_SEQUEL = 1, YACRD_SYNTH_SKEWED = 2 };

@@ -1424,6 +1424,7 @@ void yacrd_engine_destroy(yacrd_engine *e)
     if (e->paf_arena) (void)hipHostFree(e->paf_arena);
     if (e->paf_scratch && e->paf_scratch_free) e->paf_scratch_free(e->paf_scratch);
     if (e->edit_scratch && e->edit_scratch_free) e->edit_scratch_free(e->edit_scratch);
+    if (e->gzip_scratch && e->gzip_scratch_free) e->gzip_scratch_free(e->gzip_scratch);
     for (int b = 0; b < yacrd_engine::kBounce; b++) {
         if (e->bounce[b]) (void)hipHostFree(e->bounce[b]);
         if (e->bounce_ev[b]) (void)hipEventDestroy(e->bounce_ev[b]);

@@ -193,6 +193,10 @@ struct yacrd_engine {
     void *edit_scratch = nullptr;                // gpu_edit.hip's device and pinned buffers (its type), kept between calls
     void (*edit_scratch_free)(void *) = nullptr; // (destroy)
     void (*edit_scratch_release)(void *) = nullptr; // (yacrd_engine_trim)
+    void *gzip_scratch = nullptr;                // gpu_deflate.hip's device and pinned buffers (its type), kept between calls
+    void (*gzip_scratch_free)(void *) = nullptr;
+    void (*gzip_scratch_release)(void *) = nullptr;
+    bool gzip_busy = false;                      // a yacrd_gzip_writer holds them
 };
 
 

@@ -288,6 +288,35 @@ int main(int argc, char **argv)
                              (unsigned long long)es.n_kept, (unsigned long long)es.n_lines, (unsigned long long)es.kept_bytes,
                              (unsigned long long)es.text_bytes, es.text_ms, es.table_ms, es.kernel_ms, es.out_ms, es.mirror_reused);
         }
+        // A gzip input writes gzip (the reference's contract): the host loop inflates and edits as before, and the edited bytes
+        // leave through a yacrd_gzip_writer — compressed on the device into BGZF — instead of zlib's one thread.  No memory for
+        // it, bzip2 / xz, YACRD_NO_DEVICE_DEFLATE=1: the host path below, unchanged.
+        const char *no_df = std::getenv("YACRD_NO_DEVICE_DEFLATE");
+        if (dev_edit != YACRD_OK && !(no_df && *no_df == '1') && yacrd_file_compression(sub_in.c_str()) == 1) {
+            yacrd_gzip_writer *gw = nullptr;
+            const int rco = yacrd_gzip_writer_open(engines[0], sub_out.c_str(), 0, 0, &gw);
+            if (rco == YACRD_ENOMEM) {
+                std::fprintf(stderr, "[INFO] device deflate: %s; falling back to zlib\n", yacrd_last_error());
+                for (yacrd_engine *en : engines) (void)yacrd_engine_trim(en);
+            } else if (rco != YACRD_OK) die(yacrd_last_error());
+            else {
+                yacrd_byte_sink sink{};
+                (void)yacrd_gzip_writer_sink(gw, &sink);
+                if (yacrd_edit_file_to(op, sub_in.c_str(), &bp, 0, &sink)) {
+                    const std::string why = yacrd_host_last_error(), why_dev = yacrd_last_error();
+                    yacrd_gzip_writer_abort(gw);
+                    die((why_dev.empty() || why != "Error during writing of the output file" ? why : why_dev).c_str());
+                }
+                yacrd_gzip_stats gs{};
+                if (yacrd_gzip_writer_close(gw, &gs) != YACRD_OK) die(yacrd_last_error());
+                if (timing)
+                    std::fprintf(stderr, "[info] device deflate: %llu -> %llu bytes, %llu members (%llu stored), h2d %.1f ms, kernels %.1f ms, "
+                                         "d2h %.1f ms, write %.1f ms\n",
+                                 (unsigned long long)gs.in_bytes, (unsigned long long)gs.out_bytes, (unsigned long long)gs.n_members,
+                                 (unsigned long long)gs.n_stored, gs.h2d_ms, gs.kernel_ms, gs.d2h_ms, gs.write_ms);
+                dev_edit = YACRD_OK;
+            }
+        }
         if (dev_edit != YACRD_OK && yacrd_edit_file(op, sub_in.c_str(), sub_out.c_str(), &bp)) die(yacrd_host_last_error());
         stage("edit");
     }

@@ -137,6 +137,7 @@ struct Writer {
     std::vector<char> buf;
     bool failed = false;
     bool to_memory = false; // everything stays in `buf` (the multi-threaded editors: one chunk's output)
+    const yacrd_byte_sink *sink = nullptr; // the bytes go to somebody else (yacrd_edit_file_to); after a refusal it gets no more
     int open(const char *path, yh::Compression fmt)
     {
         if (os.open(path, fmt)) return 1;
@@ -151,6 +152,11 @@ struct Writer {
     void flush()
     {
         if (buf.empty() || to_memory) return;
+        if (sink) {
+            if (!failed && sink->write(sink->ctx, buf.data(), (uint64_t)buf.size()) != 0) failed = true;
+            buf.clear();
+            return;
+        }
         failed |= !os.write(buf.data(), buf.size());
         buf.clear();
     }
@@ -164,7 +170,7 @@ struct Writer {
     int close()
     {
         flush();
-        const int rc = os.close();
+        const int rc = sink ? 0 : os.close();
         return (failed || rc) ? yh::fail("Error during writing of the output file") : 0;
     }
 };
@@ -431,6 +437,7 @@ int edit_sequences(int op, bool fastq, Reader &in, Writer &out, const BadParts &
     std::vector<uint32_t> poss;
     char suffix[48];
     for (;;) {
+        if (out.sink && out.failed) break; // (the sink has refused: out.close() words the failure, nothing more is parsed)
         RecView v;
         if (!(fastq && fast_fastq(in, v))) {
             const bool ok = fastq ? next_fastq(in, rec, err) : next_fasta(in, rec, err);
@@ -782,6 +789,7 @@ int edit_overlaps(int op, bool paf, Reader &in, Writer &out, const BadParts &bp)
     std::string l, a, b;
     size_t n_fields = 0;
     while (in.line(l)) {
+        if (out.sink && out.failed) break; // (the sink has refused)
         if (!l.empty() && l.back() == '\r') l.pop_back();
         if (l.empty()) continue;
         size_t nf = 1, start_b = std::string::npos, end_a = l.find(delim);
@@ -972,6 +980,42 @@ int yacrd_edit_file_mt(int op, const char *in_path, const char *out_path, const 
                        : edit_overlaps(op, ft == FT_PAF, in, out, table);
     if (rc) return rc;
     return out.close();
+}
+
+int yacrd_edit_file_to(int op, const char *in_path, const yacrd_badparts_view *bp, int n_threads, const yacrd_byte_sink *sink)
+{
+    (void)n_threads; // (the sink takes bytes in order from one caller: the one-thread loop feeds it, for plain inputs as well)
+    if (op < 0 || op > 3 || !in_path || !bp || !sink || !sink->write) return yh::fail("bad argument");
+    if (bp->n_reads && (!bp->read_type || !bp->bad_offsets || !bp->lengths || !bp->name_off))
+        return yh::fail("bad parts table is incomplete (read_type comes from the engine)");
+    const FileType ft = file_type(in_path);
+    const bool seq = ft == FT_FASTA || ft == FT_FASTQ, ovl = ft == FT_PAF || ft == FT_M4;
+    if (ft == FT_NONE || ft == FT_YOVL)
+        return yh::fail(std::string("Format detection of file ") + in_path + " failed");
+    if (!(seq || (ovl && (op == OP_FILTER || op == OP_EXTRACT))))
+        return yh::fail(std::string("Can't run ") + op_name(op) + " on " + type_name(ft) +
+                        " file " + in_path);
+    Reader in;
+    if (in.open(in_path)) return 1;
+    const BadParts table(bp, std::min(yh::usable_cpus(), 3u));
+    Writer out;
+    out.sink = sink;
+    out.buf.reserve(1 << 20);
+    const int rc = seq ? edit_sequences(op, ft == FT_FASTQ, in, out, table)
+                       : edit_overlaps(op, ft == FT_PAF, in, out, table);
+    if (rc) return rc;
+    return out.close();
+}
+
+int yacrd_file_compression(const char *path)
+{
+    if (!path) return 0;
+    unsigned char mg[6] = {0};
+    FILE *f = std::fopen(path, "rb");
+    if (!f) return 0;
+    const size_t k = std::fread(mg, 1, sizeof mg, f);
+    std::fclose(f);
+    return (int)yh::sniff_compression(mg, k);
 }
 
 } // extern "C"

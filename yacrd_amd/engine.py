@@ -48,6 +48,8 @@ EXPORTED_SYMBOLS = [
     "yacrd_engine_ingest_paf", "yacrd_engine_ingest_overlaps", "yacrd_engine_ingest_overlaps_mem", "yacrd_engines_ingest_overlaps",
     "yacrd_engines_ingest_overlaps_mem", "yacrd_reads_free", "yacrd_engine_trim",
     "yacrd_engine_edit_overlaps", "yacrd_engine_edit_overlaps_mem", "yacrd_edit_text_free",
+    "yacrd_engine_gzip_mem", "yacrd_gzip_writer_open", "yacrd_gzip_writer_write", "yacrd_gzip_writer_sink", "yacrd_gzip_writer_close",
+    "yacrd_gzip_writer_abort",
     "yacrd_stream_device_of", "yacrd_stream_group_open", "yacrd_stream_group_sink", "yacrd_stream_group_finish",
     "yacrd_stream_group_last_stats", "yacrd_stream_group_reset", "yacrd_stream_group_close",
 ]
@@ -82,6 +84,14 @@ class _TypeTable(ctypes.Structure):
 class _EditStats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("text_bytes", "kept_bytes", "n_lines", "n_kept")] + \
                [(n, ctypes.c_float) for n in ("text_ms", "table_ms", "kernel_ms", "out_ms")] + [("mirror_reused", ctypes.c_uint32)]
+
+
+class _GzipStats(ctypes.Structure):
+    _fields_ = [("in_bytes", ctypes.c_uint64), ("out_bytes", ctypes.c_uint64), ("n_members", ctypes.c_uint64), ("n_stored", ctypes.c_uint64),
+                ("h2d_ms", ctypes.c_float), ("kernel_ms", ctypes.c_float), ("d2h_ms", ctypes.c_float), ("write_ms", ctypes.c_float)]
+
+
+from .host import ByteSink  # noqa: E402  (yacrd_byte_sink: one structure, declared in both headers)
 
 
 class _Cfg(ctypes.Structure):
@@ -278,6 +288,14 @@ def load_library():
                                                    ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_EditStats)]
     lib.yacrd_edit_text_free.argtypes = [ctypes.c_void_p]
     lib.yacrd_edit_text_free.restype = None
+    lib.yacrd_engine_gzip_mem.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p),
+                                          ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_GzipStats)]
+    lib.yacrd_gzip_writer_open.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
+    lib.yacrd_gzip_writer_write.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
+    lib.yacrd_gzip_writer_sink.argtypes = [ctypes.c_void_p, ctypes.POINTER(ByteSink)]
+    lib.yacrd_gzip_writer_close.argtypes = [ctypes.c_void_p, ctypes.POINTER(_GzipStats)]
+    lib.yacrd_gzip_writer_abort.argtypes = [ctypes.c_void_p]
+    lib.yacrd_gzip_writer_abort.restype = None
     lib.yacrd_reads_free.argtypes = [ctypes.POINTER(_Reads)]
     lib.yacrd_reads_free.restype = None
     lib.yacrd_stream_reset.argtypes = [ctypes.c_void_p]
@@ -590,6 +608,25 @@ class Engine:
         finally:
             self._lib.yacrd_edit_text_free(out)
 
+    def gzip(self, data):
+        """yacrd_engine_gzip_mem: `data` (bytes) -> one BGZF stream (bytes), compressed on the device; the stats are in
+        self.gzip_stats."""
+        data = bytes(data)
+        st = _GzipStats()
+        out, n_out = ctypes.c_void_p(), ctypes.c_uint64()
+        buf = ctypes.create_string_buffer(data, len(data) + 1)
+        _check(self._lib, self._lib.yacrd_engine_gzip_mem(self._h, ctypes.addressof(buf), len(data), ctypes.byref(out), ctypes.byref(n_out),
+                                                          ctypes.byref(st)))
+        self.gzip_stats = {f: getattr(st, f) for f, _ in _GzipStats._fields_}
+        try:
+            return ctypes.string_at(out.value, int(n_out.value))
+        finally:
+            self._lib.yacrd_edit_text_free(out)
+
+    def gzip_writer(self, out_path, segment_bytes=0, n_buffers=0):
+        """A GzipWriter over this engine (yacrd_gzip_writer_open)."""
+        return GzipWriter(self, out_path, segment_bytes, n_buffers)
+
     def trim(self):
         """yacrd_engine_trim: give the device parser's and the overlap editor's buffers back."""
         _check(self._lib, self._lib.yacrd_engine_trim(self._h))
@@ -655,6 +692,62 @@ class Engine:
             _ptr(lengths, ctypes.c_uint32), n_reads, float(not_coverage),
             _ptr(out, ctypes.c_uint8)))
         return out[:n_reads]
+
+
+class GzipWriter:
+    """yacrd_gzip_writer: bytes arrive through write(), leave as a BGZF file compressed on the device.  As a context
+    manager it closes on a clean exit and aborts (nothing is left at out_path) on an exception."""
+
+    def __init__(self, engine, out_path, segment_bytes=0, n_buffers=0):
+        self._lib = engine._lib
+        self._engine = engine
+        self._h = ctypes.c_void_p()
+        self.stats = None
+        _check(self._lib, self._lib.yacrd_gzip_writer_open(engine._h, os.fsencode(out_path), int(segment_bytes), int(n_buffers),
+                                                           ctypes.byref(self._h)))
+
+    def write(self, data):
+        data = bytes(data)
+        if not self._h:
+            raise EngineError("the gzip writer is closed")
+        _check(self._lib, self._lib.yacrd_gzip_writer_write(self._h, data, len(data)))
+        return len(data)
+
+    def sink(self):
+        """A ByteSink (yacrd_gzip_writer_sink) for host.edit_file_to; valid while the writer is open."""
+        s = ByteSink()
+        _check(self._lib, self._lib.yacrd_gzip_writer_sink(self._h, ctypes.byref(s)))
+        return s
+
+    def close(self):
+        if not self._h:
+            return self.stats
+        h, self._h = self._h, ctypes.c_void_p()
+        st = _GzipStats()
+        _check(self._lib, self._lib.yacrd_gzip_writer_close(h, ctypes.byref(st)))
+        self.stats = {f: getattr(st, f) for f, _ in _GzipStats._fields_}
+        return self.stats
+
+    def abort(self):
+        if self._h:
+            h, self._h = self._h, ctypes.c_void_p()
+            self._lib.yacrd_gzip_writer_abort(h)
+
+    def __del__(self):  # (a writer that was dropped: the engine gets its buffers back, nothing is left beside out_path)
+        try:
+            self.abort()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        else:
+            self.abort()
+        return False
 
 
 class PinnedArray:

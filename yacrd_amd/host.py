@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = [
     "yacrd_host_last_error", "yacrd_csr_from_file", "yacrd_csr_from_memory", "yacrd_csr_get",
     "yacrd_csr_find", "yacrd_csr_free", "yacrd_report_write", "yacrd_synth_csr", "yacrd_synth_paf",
     "yacrd_edit_file", "yacrd_edit_file_mt", "yacrd_text_from_file", "yacrd_text_free", "yacrd_report_read", "yacrd_report_get", "yacrd_report_free",
+    "yacrd_edit_file_to", "yacrd_file_compression", "yacrd_bgzf_encode_host", "yacrd_bytes_free", "yacrd_deflate_code_lengths",
     "yacrd_synth_fastq", "yacrd_ingest_stream", "yacrd_ingest_stream_memory", "yacrd_csr_handle_map",
 ]
 
@@ -156,6 +157,12 @@ def load_library():
         lib.yacrd_text_free.restype = None
         lib.yacrd_edit_file_mt.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p,
                                            ctypes.POINTER(_BadParts), ctypes.c_int]
+        lib.yacrd_edit_file_to.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(_BadParts), ctypes.c_int, ctypes.c_void_p]
+        lib.yacrd_file_compression.argtypes = [ctypes.c_char_p]
+        lib.yacrd_bgzf_encode_host.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)]
+        lib.yacrd_bytes_free.argtypes = [ctypes.c_void_p]
+        lib.yacrd_bytes_free.restype = None
+        lib.yacrd_deflate_code_lengths.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
         lib.yacrd_report_read.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
         lib.yacrd_report_get.argtypes = [ctypes.c_void_p, ctypes.POINTER(_BadParts)]
         lib.yacrd_report_free.argtypes = [ctypes.c_void_p]
@@ -288,6 +295,84 @@ def synth_fastq(profile, n_reads, n_overlaps, seed, extra_reads, path, flags=0):
     lib = load_library()
     cfg = _SynthCfg(profile, flags, n_reads, n_overlaps, seed)
     _check(lib, lib.yacrd_synth_fastq(ctypes.byref(cfg), extra_reads, path.encode()))
+
+
+class ByteSink(ctypes.Structure):
+    """yacrd_byte_sink (both headers): somebody who takes bytes in order."""
+    WRITE = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)
+    _fields_ = [("ctx", ctypes.c_void_p), ("write", WRITE)]
+
+
+def _bad_parts(names, lengths, bad_offsets, bad_regions, read_type):
+    """(the yacrd_badparts_view, what must stay alive while it is used)"""
+    blob = b"".join(n.encode() for n in names)
+    name_off = np.zeros(len(names) + 1, dtype=np.uint64)
+    np.cumsum([len(n.encode()) for n in names], out=name_off[1:])
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    bo = np.ascontiguousarray(bad_offsets, dtype=np.uint64)
+    br = np.ascontiguousarray(bad_regions, dtype=np.uint32).reshape(-1)
+    if br.size == 0:
+        br = np.zeros(2, np.uint32)
+    rt = np.ascontiguousarray(read_type, dtype=np.uint8)
+    view = _BadParts(len(names), name_off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), blob,
+                     lengths.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                     bo.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                     br.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                     rt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+    return view, (blob, name_off, lengths, bo, br, rt)
+
+
+def edit_file_to(op, in_path, sink, names, lengths, bad_offsets, bad_regions, read_type, n_threads=0):
+    """yacrd_edit_file_to: the edited, uncompressed bytes go to `sink` instead of a file.  `sink` is a Python callable
+    taking bytes (a false / None result = go on, anything true = stop: the edit fails) or a yacrd_byte_sink structure
+    (GzipWriter.sink())."""
+    lib = load_library()
+    view, keep = _bad_parts(names, lengths, bad_offsets, bad_regions, read_type)
+    if callable(sink):
+        raised = []
+
+        def _write(_ctx, p, n):
+            try:
+                return 1 if sink(ctypes.string_at(p, n)) else 0
+            except Exception as exc:  # (an exception cannot cross the C frames: the edit stops, it is raised below)
+                raised.append(exc)
+                return 1
+        cb = ByteSink.WRITE(_write)
+        s = ByteSink(None, cb)
+    else:
+        raised = []
+        s = sink
+    rc = lib.yacrd_edit_file_to(op, in_path.encode(), ctypes.byref(view), n_threads, ctypes.addressof(s))
+    del keep
+    if raised:
+        raise raised[0]
+    _check(lib, rc)
+
+
+def file_compression(path):
+    """yacrd_file_compression: 0 none, 1 gzip, 2 bzip2, 3 xz, by the magic bytes."""
+    return int(load_library().yacrd_file_compression(os.fsencode(path)))
+
+
+def bgzf_encode_host(data):
+    """yacrd_bgzf_encode_host: the device encoder's text run by one host thread; the bytes Engine.gzip gives."""
+    lib = load_library()
+    data = bytes(data)
+    out, n = ctypes.c_void_p(), ctypes.c_uint64()
+    _check(lib, lib.yacrd_bgzf_encode_host(data, len(data), ctypes.byref(out), ctypes.byref(n)))
+    try:
+        return ctypes.string_at(out.value, int(n.value))
+    finally:
+        lib.yacrd_bytes_free(out)
+
+
+def deflate_code_lengths(freq, limit):
+    """yacrd_deflate_code_lengths: the encoder's length-limited code lengths for a histogram."""
+    lib = load_library()
+    f = np.ascontiguousarray(freq, dtype=np.uint32)
+    out = np.zeros(len(f), np.uint8)
+    _check(lib, lib.yacrd_deflate_code_lengths(f.ctypes.data, len(f), int(limit), out.ctypes.data))
+    return out
 
 
 def edit_file(op, in_path, out_path, names, lengths, bad_offsets, bad_regions, read_type, n_threads=0):
