@@ -443,6 +443,29 @@ typedef struct {
 int yacrd_engine_gzip_mem(yacrd_engine *e, const char *data, uint64_t n_bytes,
                           char **out, uint64_t *out_bytes, yacrd_gzip_stats *stats /* may be NULL */);
 
+/* filter / extract with gzip out: the kept bytes of yacrd_engine_edit_overlaps_mem deflated where the pack pass leaves them
+ * in HBM, so that only members cross the link and reach the file.  `text` is the overlap text in host memory, already
+ * inflated (format 1 = PAF / 2 = M4, MHAP): this library links no zlib, the caller inflates (libyacrd_host's
+ * yacrd_text_from_file is member-parallel for BGZF).  The decision and the kept bytes are those of
+ * yacrd_engine_edit_overlaps_mem; the result is ONE BGZF stream, byte for byte what yacrd_engine_gzip_mem returns for the
+ * kept bytes: blocks of 65 280 bytes counted from the start of the kept stream, the EOF member last (nothing kept: the EOF
+ * member alone).  It does not depend on the editor's segments, on threads or on timing.  As soon as a segment is packed,
+ * its whole blocks are encoded on a stream of their own while later segments are moved, marked and packed; the tail of
+ * fewer than 65 280 bytes waits for the next segment.  Every buffer is taken before the first segment is handed over
+ * (YACRD_ENOMEM: nothing was written, nothing is left behind); they stay with the engine (yacrd_engine_trim).
+ * YACRD_EFALLBACK for the causes of the plain form; found in a later segment, members of earlier ones may already have
+ * left the device: the buffer is freed, the file beside out_path removed, nothing is left at out_path.
+ * es as for the plain form (out_ms: the writer thread's busy time, members D2H and into the file); gs: in_bytes ==
+ * es->kept_bytes, kernel_ms from device events around the encode and pack launches, summed over the batches; d2h_ms
+ * holds the writer's waits for the encoder as well.  The file form writes beside out_path and renames when the EOF member
+ * is in; the memory form returns a buffer of the library's (yacrd_edit_text_free). */
+int yacrd_engine_edit_overlaps_gzip_mem(yacrd_engine *e, int op, const char *text, uint64_t n_bytes, int format,
+                                        const yacrd_type_table *types, char **out, uint64_t *out_bytes,
+                                        yacrd_edit_stats *es /* may be NULL */, yacrd_gzip_stats *gs /* may be NULL */);
+int yacrd_engine_edit_overlaps_gzip_file(yacrd_engine *e, int op, const char *text, uint64_t n_bytes, int format,
+                                         const yacrd_type_table *types, const char *out_path,
+                                         yacrd_edit_stats *es /* may be NULL */, yacrd_gzip_stats *gs /* may be NULL */);
+
 #ifndef YACRD_BYTE_SINK_DEFINED
 #define YACRD_BYTE_SINK_DEFINED
 typedef struct {

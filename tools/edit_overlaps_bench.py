@@ -6,8 +6,17 @@ K timed runs of each after one warm-up:
   (b) moved    yacrd_engine_edit_overlaps, the text moved to HBM (warm buffers), with text_ms / kernel_ms / out_ms
   (c) reused   the same from the mirror the device parser left in HBM
   (d) floor    yacrd_ingest_stats.text_ms of the device parser on the file: what moving the text in costs by itself
-Every output is compared with the host loop's.  One JSON line (appended to --json when given)."""
-import argparse, json, os, sys, time
+Every output is compared with the host loop's.  One JSON line (appended to --json when given).
+
+--gzip --parent-bin PATH [--forms gzip1,bgzf]: the COMMAND on a gzip overlap file,
+    yacrd -i ovl.paf.gz -o r.yacrd -c 3 -n 0.4 <op> -i ovl.paf.gz -o kept.paf.gz
+with the same synthetic PAF as gzip level 1 (one stream) and as BGZF, K timed runs after one warm-up of
+  (a) parent   PATH: the `yacrd` of the parent commit — the file inflated a second time, the host loop, the edited bytes through
+               the gzip writer (its "[info] device deflate:" line)
+  (b) new      this tree's yacrd — the detection's text reused, edited and deflated in HBM (its "[info] device editor + deflate:" line, on stdout)
+and the `edit` stage of YACRD_CLI_TIMING as the figure compared: slowest (b) against fastest (a).  Every output is compared
+with the parent's, byte for byte.  One JSON line per form (appended to --json when given)."""
+import argparse, json, os, re, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import yacrd_amd  # noqa: E402
@@ -19,6 +28,9 @@ ap.add_argument("--overlaps", type=int, default=5_000_000)
 ap.add_argument("--runs", type=int, default=3)
 ap.add_argument("--op", default="filter")
 ap.add_argument("--json", default=None)
+ap.add_argument("--gzip", action="store_true")
+ap.add_argument("--parent-bin", default=None)
+ap.add_argument("--forms", default="gzip1,bgzf")
 a = ap.parse_args()
 op = {"filter": host.OP_FILTER, "extract": host.OP_EXTRACT}[a.op]
 d = os.environ.get("YACRD_EDIT_BENCH_DIR", "/dev/shm")
@@ -40,6 +52,79 @@ def fresh(path):
     if os.path.exists(path):
         os.remove(path)  # (or the open's truncation frees the last run's pages inside the timed region)
 
+
+def gzip_bench():
+    new_bin = os.path.join(ROOT, "yacrd_amd", "bin", "yacrd")
+    if not a.parent_bin or not os.access(a.parent_bin, os.X_OK):
+        sys.exit("--gzip needs --parent-bin: the yacrd binary built from the parent commit")
+    made = [paf]
+    try:
+        host.synth_paf(host.SYNTH_SEQUEL, a.reads, a.overlaps, 20241108 + 5, paf)
+        size = os.path.getsize(paf)
+        for form in a.forms.split(","):
+            src, rep, old, new = tag + form + ".paf.gz", tag + "r.yacrd", tag + "old.paf.gz", tag + "new.paf.gz"
+            made.extend([src, rep, old, new])
+            t0 = time.perf_counter()
+            if form == "gzip1":
+                with open(src, "wb") as f:
+                    subprocess.check_call(["gzip", "-1", "-c", paf], stdout=f)
+            else:
+                with yacrd_amd.Engine(device_id=0) as e, e.gzip_writer(src) as w, open(paf, "rb") as f:
+                    while True:
+                        piece = f.read(1 << 26)
+                        if not piece:
+                            break
+                        w.write(piece)
+            made_s = time.perf_counter() - t0
+
+            def run(binary, out):
+                rows = []
+                for k in range(a.runs + 1):
+                    fresh(out)
+                    fresh(rep)
+                    t0 = time.perf_counter()
+                    p = subprocess.run([binary, "-i", src, "-o", rep, "-t", "0", "-c", "3", "-n", "0.4", a.op, "-i", src, "-o", out],
+                                       capture_output=True, text=True, env=dict(os.environ, YACRD_CLI_TIMING="1"))
+                    wall = time.perf_counter() - t0
+                    assert p.returncode == 0, p.stderr
+                    stages = dict(re.findall(r"^\[timing\] (\S+) ([0-9.]+) s$", p.stderr, re.M))
+                    info = [l for l in (p.stdout + p.stderr).splitlines() if l.startswith("[info] device editor + deflate:") or l.startswith("[info] device deflate:")]
+                    assert len(info) == 1, p.stderr
+                    row = {"edit_s": float(stages["edit"]), "inflate_s": float(stages["inflate"]), "detect_s": float(stages["detect"]), "wall_s": round(wall, 3)}
+                    for name, key in (("inflate", "edit_inflate_ms"), ("text", "text_ms"), ("table", "table_ms"), ("editor kernels", "editor_kernel_ms"),
+                                      ("encoder kernels", "encoder_kernel_ms"), ("kernels", "encoder_kernel_ms"), ("out", "out_ms"), ("h2d", "h2d_ms"),
+                                      ("d2h", "d2h_ms"), ("write", "write_ms")):
+                        m = re.search(r"(?:, |: )%s ([0-9.]+) ms" % name, info[0])
+                        if m and key not in row:
+                            row[key] = float(m.group(1))
+                    m = re.search(r"text_reused=(\d)", info[0])
+                    if m:
+                        row["text_reused"] = int(m.group(1))
+                    if k:
+                        rows.append(row)
+                return rows
+            parent = run(a.parent_bin, old)
+            mine = run(new_bin, new)
+            assert same(old, new), "the new path's file differs from the parent's"
+            worst_new, best_old = max(r["edit_s"] for r in mine), min(r["edit_s"] for r in parent)
+            row = {"reads": a.reads, "overlaps": a.overlaps, "op": a.op, "form": form, "text_bytes": size, "gz_in_bytes": os.path.getsize(src),
+                   "gz_out_bytes": os.path.getsize(new), "make_input_s": round(made_s, 2), "parent": parent, "new": mine,
+                   "edit_stage_slowest_new_s": worst_new, "edit_stage_fastest_parent_s": best_old, "ratio": round(best_old / worst_new, 2)}
+            line = json.dumps(row)
+            print(line, flush=True)
+            if a.json:
+                with open(a.json, "a") as f:
+                    f.write(line + "\n")
+            for x in (src, old, new):
+                fresh(x)
+    finally:
+        for x in made:
+            fresh(x)
+
+
+if a.gzip:
+    gzip_bench()
+    sys.exit(0)
 
 try:
     host.synth_paf(host.SYNTH_SEQUEL, a.reads, a.overlaps, 20241108 + 5, paf)

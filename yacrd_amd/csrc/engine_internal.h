@@ -214,8 +214,17 @@ struct RecSlab {
 int csr_from_records(yacrd_engine *e, const RecSlab *slabs, size_t n_slabs, const u32 *d_map, u64 n_handles, u64 n_reads,
                      DevBuf &cnt, DevBuf &part, DevBuf &err, hipEvent_t done, u64 *n_intervals = nullptr,
                      bool counted = false, u64 iv_bound = 0);
-int scan_u32_to_u64(yacrd_engine *e, const u32 *in, u64 n, u64 *out, DevBuf &part);
+int scan_u32_to_u64(yacrd_engine *e, const u32 *in, u64 n, u64 *out, DevBuf &part, hipStream_t st = nullptr /* the engine's */);
 // host -> HBM at PCIe rate: direct DMA when `src` is pinned, otherwise through the engine's pinned
 // bounce buffers filled by a few copy threads; asynchronous on e->stream only for pinned sources
 int h2d(yacrd_engine *e, void *dst, const void *src, size_t bytes);
+// text that lies in HBM -> BGZF members in HBM, batch by batch (gpu_deflate.hip; used by gpu_edit.hip)
+struct GzDevice {
+    const unsigned char *out[2] = {nullptr, nullptr}; // a batch's members, end to end; batches alternate between the two
+    u64 max_blocks = 0;                               // blocks of 65 280 bytes a batch may hold
+};
+int gzip_device_open(yacrd_engine *e, u64 max_blocks, GzDevice *g);
+int gzip_device_encode(yacrd_engine *e, const GzDevice &g, hipStream_t st, const unsigned char *d_text, u64 n, bool last, int which,
+                       hipEvent_t k0, hipEvent_t k1, volatile u64 *h_bytes, volatile u64 *h_stored);
+void gzip_device_close(yacrd_engine *e);
 } // namespace yke

@@ -77,12 +77,12 @@ constexpr u64 kDefaultSegBlocks = 512;
 constexpr u64 kMaxSegBlocks = 16384; // 1 GiB of slots
 
 struct GzScratch { // stays with the engine (grow-only); goes with yacrd_engine_trim / destroy
-    DevBuf text, slots, out, sizes, off, part, ctl;
+    DevBuf text, slots, out, out2, sizes, off, part, ctl; // (out2: the overlap editor's second batch of members, gzip_device_open)
     void *pin = nullptr; // n_buffers input segments, one output segment, the control words
     size_t pin_cap = 0;
     void release()
     {
-        for (DevBuf *b : {&text, &slots, &out, &sizes, &off, &part, &ctl}) b->release();
+        for (DevBuf *b : {&text, &slots, &out, &out2, &sizes, &off, &part, &ctl}) b->release();
         if (pin) (void)hipHostFree(pin);
         pin = nullptr, pin_cap = 0;
     }
@@ -104,20 +104,63 @@ inline u64 out_bound(u64 blocks) { return blocks * (u64)ydf::kSlot + ydf::kEofBy
 
 namespace yke {
 
-// THE DEVICE-RESIDENT STEP: d_text[0, n) -> a run of BGZF members in S.out (the EOF member behind them when `last`), on the
-// engine's stream, asynchronous; S.off[n_members] = the members' bytes.  n <= the segment the scratch was sized for.
-static int gzip_on_device(yacrd_engine *e, GzScratch &S, const unsigned char *d_text, u64 n, bool last)
+// THE DEVICE-RESIDENT STEP: d_text[0, n) -> a run of BGZF members in `d_out` (the EOF member behind them when `last`), on
+// stream `st`, asynchronous; S.off[n_members] = the members' bytes.  n <= the segment the scratch was sized for; d_text is
+// 16-byte aligned (a block's start in a longer text is: 65 280 = 16 x 4080).
+static int gzip_on_device(yacrd_engine *e, GzScratch &S, hipStream_t st, const unsigned char *d_text, u64 n, bool last, unsigned char *d_out)
 {
     const u32 nb = (u32)((n + ydf::kBlock - 1) / ydf::kBlock);
-    if (nb) hipLaunchKernelGGL(yk::df_encode_kernel, dim3(nb), dim3(256), 0, e->stream, d_text, n, S.slots.as<unsigned char>(), S.sizes.as<u32>(),
+    if (nb) hipLaunchKernelGGL(yk::df_encode_kernel, dim3(nb), dim3(256), 0, st, d_text, n, S.slots.as<unsigned char>(), S.sizes.as<u32>(),
                                S.ctl.as<unsigned long long>());
-    if (const int rc = scan_u32_to_u64(e, S.sizes.as<u32>(), nb, S.off.as<u64>(), S.part)) return rc;
+    if (const int rc = scan_u32_to_u64(e, S.sizes.as<u32>(), nb, S.off.as<u64>(), S.part, st)) return rc;
     if (nb + (last ? 1u : 0u))
-        hipLaunchKernelGGL(yk::df_pack_kernel, dim3(nb + (last ? 1u : 0u)), dim3(256), 0, e->stream, S.slots.as<unsigned char>(), S.sizes.as<u32>(),
-                           S.off.as<u64>(), nb, S.out.as<unsigned char>());
+        hipLaunchKernelGGL(yk::df_pack_kernel, dim3(nb + (last ? 1u : 0u)), dim3(256), 0, st, S.slots.as<unsigned char>(), S.sizes.as<u32>(),
+                           S.off.as<u64>(), nb, d_out);
     HIP_TRY(hipGetLastError());
     return YACRD_OK;
 }
+
+// ---- the same step for text that ALREADY lies in HBM (gpu_edit.hip: the kept bytes of an overlap file) ---------------------
+// open takes every buffer for batches of up to max_blocks blocks — the members of two batches: one is fetched while the
+// next is encoded — and holds the engine's gzip scratch like a writer does; nothing is allocated afterwards.
+int gzip_device_open(yacrd_engine *e, u64 max_blocks, GzDevice *g)
+{
+    if (e->gzip_busy) return fail(YACRD_EINVAL, "the engine already has a gzip writer");
+    GzScratch *S = gzip_scratch_of(e);
+    if (!S) return fail(YACRD_ENOMEM, "host allocation failed");
+    const u64 blocks = std::min(std::max<u64>(max_blocks, 1), kMaxSegBlocks);
+    HIP_TRY(S->slots.reserve((size_t)(blocks * ydf::kSlot)));
+    HIP_TRY(S->out.reserve((size_t)out_bound(blocks) + 64));
+    HIP_TRY(S->out2.reserve((size_t)out_bound(blocks) + 64));
+    HIP_TRY(S->sizes.reserve((size_t)(blocks + 1) * sizeof(u32)));
+    HIP_TRY(S->off.reserve((size_t)(blocks + 2) * sizeof(u64)));
+    HIP_TRY(S->ctl.reserve(64));
+    HIP_TRY(S->part.reserve((size_t)(blocks + 2) * sizeof(u64)));
+    HIP_TRY(hipMemsetAsync(S->ctl.p, 0, 64, e->stream)); // (the caller waits for e->stream before its first batch)
+    g->out[0] = S->out.as<unsigned char>(), g->out[1] = S->out2.as<unsigned char>();
+    g->max_blocks = blocks;
+    e->gzip_busy = true;
+    return YACRD_OK;
+}
+
+// d_text[0, n) (n <= max_blocks blocks) -> members in g.out[which] on stream `st`, events k0 / k1 around the kernels; behind
+// them on the stream the members' bytes (without the EOF member's) land in *h_bytes and the stored members so far in
+// *h_stored: pinned memory.  Asynchronous.
+int gzip_device_encode(yacrd_engine *e, const GzDevice &g, hipStream_t st, const unsigned char *d_text, u64 n, bool last, int which,
+                       hipEvent_t k0, hipEvent_t k1, volatile u64 *h_bytes, volatile u64 *h_stored)
+{
+    GzScratch &S = *static_cast<GzScratch *>(e->gzip_scratch);
+    const u64 nb = (n + ydf::kBlock - 1) / ydf::kBlock;
+    if (nb > g.max_blocks) return fail(YACRD_EINTERNAL, "device deflate: a batch beyond the blocks its buffers were taken for");
+    HIP_TRY(hipEventRecord(k0, st));
+    if (const int rc = gzip_on_device(e, S, st, d_text, n, last, const_cast<unsigned char *>(g.out[which & 1]))) return rc;
+    HIP_TRY(hipEventRecord(k1, st));
+    HIP_TRY(hipMemcpyAsync((void *)h_bytes, S.off.as<u64>() + nb, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync((void *)h_stored, S.ctl.p, sizeof(u64), hipMemcpyDeviceToHost, st));
+    return YACRD_OK;
+}
+
+void gzip_device_close(yacrd_engine *e) { e->gzip_busy = false; }
 
 } // namespace yke
 
@@ -189,7 +232,7 @@ struct yacrd_gzip_writer {
         HIP_TRY(hipEventRecord(ev[0], e->stream));
         if (fill) HIP_TRY(hipMemcpyAsync(S->text.p, src, (size_t)fill, hipMemcpyHostToDevice, e->stream));
         HIP_TRY(hipEventRecord(ev[1], e->stream));
-        if (const int rc = gzip_on_device(e, *S, S->text.as<unsigned char>(), fill, last)) return rc;
+        if (const int rc = gzip_on_device(e, *S, e->stream, S->text.as<unsigned char>(), fill, last, S->out.as<unsigned char>())) return rc;
         HIP_TRY(hipEventRecord(ev[2], e->stream));
         const u64 nb = (fill + ydf::kBlock - 1) / ydf::kBlock;
         HIP_TRY(hipMemcpyAsync((void *)h_ctl, S->off.as<u64>() + nb, sizeof(u64), hipMemcpyDeviceToHost, e->stream));

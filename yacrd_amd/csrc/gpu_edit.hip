@@ -23,6 +23,15 @@
 // in order) while later segments are still being moved and marked.  What the path does not take — a '"' or a CR
 // anywhere, a line whose field count differs from the first line's, a line more than one 4 MiB chunk longer than its
 // segment — comes back as YACRD_EFALLBACK with nothing written: the caller runs the host loop.
+//
+// gzip out (yacrd_engine_edit_overlaps_gzip_mem / _file): the kept bytes are deflated where they lie.  The pack pass writes
+// them contiguously, in file order, so when a segment's pack has finished every whole block of 65 280 bytes behind the last
+// encoded one is complete: the writer thread, which learns the segment's kept count anyway, sends those blocks through
+// gpu_deflate.hip's device-resident step on a stream of its own (a block's start is a multiple of 16 x 4080: the encoder's
+// 16-byte loads stay aligned), the ragged tail waits for the next segment and the last batch carries the EOF member.  What
+// crosses the link and reaches the file are members; one batch is fetched and written while the next is encoded and while
+// later segments are moved, marked and packed.  Blocks are counted from the start of the kept stream, so the bytes are
+// those of yacrd_engine_gzip_mem on the kept bytes whatever the segments, the threads or the timing.
 #include "engine_internal.h"
 #include "gpu_text.h"
 
@@ -396,8 +405,15 @@ struct OutSink {
     int fd = -1;
     char *mem = nullptr;
     u64 at = 0;
+    u64 cap = 0; // of `mem` when it grows (members: their size is not known in advance); 0 = the caller sized it
     bool put(const char *p, size_t k)
     {
+        if (mem && cap && at + k > cap) {
+            const u64 want = std::max<u64>(at + k, cap + cap / 2 + 4096);
+            char *q = (char *)std::realloc(mem, (size_t)want);
+            if (!q) return false;
+            mem = q, cap = want;
+        }
         if (mem) std::memcpy(mem + at, p, k);
         else
             for (size_t done = 0; done < k;) {
@@ -448,7 +464,11 @@ struct EditJob {
     int n_threads = 0;
     const yacrd_type_table *types = nullptr;
     bool use_mirror = false; // edit from the parser's mirror (the same file: checked by the caller)
+    bool gzip = false;       // the sink takes BGZF members of the kept bytes instead of the kept bytes
+    yacrd_gzip_stats *gzip_stats = nullptr;
 };
+
+constexpr u64 kGzBlock = 65280; // deflate_block.h: ydf::kBlock
 
 int edit_text(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n, OutSink &sink, yacrd_edit_stats *stats)
 {
@@ -473,6 +493,8 @@ int edit_text(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n,
     const size_t n_segs = (size_t)((n + kTextChunk * kTextSeg - 1) / (kTextChunk * kTextSeg));
     u64 cap = 1024;
     while (cap < 2 * R) cap <<= 1;
+    // gzip out: a batch is at most a segment's kept bytes and the tail carried into it
+    const u64 gz_blocks = job.gzip ? (std::min<u64>(nl, (u64)(kTextChunk * kTextSeg)) + kGzBlock - 1) / kGzBlock + 1 : 0;
     const double t_start = now_ms();
     {
         // HBM: the text (unless the parser's mirror serves), as many bytes again for what is kept, a bit per byte, the table
@@ -480,7 +502,8 @@ int edit_text(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n,
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
             const double have = (double)free_b + (double)S.text.cap + (double)S.out.cap + (double)S.kbits.cap + (double)S.names.cap + (double)S.slots.cap;
             const double need = (job.use_mirror ? 0.0 : (double)n) + (double)nl * 1.125 + (double)nl / 8.0 * 1.125 + (double)name_bytes * 1.125 +
-                                (double)cap * 4.0 + (double)R * 10.0 + (double)n_tiles * 40.0 + (double)((size_t)64 << 20);
+                                (double)cap * 4.0 + (double)R * 10.0 + (double)n_tiles * 40.0 + (double)((size_t)64 << 20) +
+                                (double)gz_blocks * 65536.0 * 3.0 * 1.125; // (the members' slots and two batches of members)
             if (need > have) return fail(YACRD_EFALLBACK, "the file is too large to be edited in this device's free memory: the host loop streams it");
         }
     }
@@ -498,7 +521,8 @@ int edit_text(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n,
     const size_t ctl_words = 8 + n_segs + 2;
     HIP_TRY(S.ctl.reserve(ctl_words * sizeof(u64)));
     HIP_TRY(hipMemsetAsync(S.ctl.p, 0, ctl_words * sizeof(u64), e->stream));
-    const size_t pin_need = 2 * kOutPiece + (n_segs + 2) * 4 * sizeof(u64);
+    const size_t n_batches = n_segs + 1; // gzip out: one per segment, or the one that only holds the EOF member
+    const size_t pin_need = 2 * kOutPiece + (n_segs + 2) * 4 * sizeof(u64) + (job.gzip ? n_batches * 2 * sizeof(u64) : 0);
     if (S.pin_cap < pin_need) {
         if (S.pin) (void)hipHostFree(S.pin);
         S.pin = nullptr, S.pin_cap = 0;
@@ -507,6 +531,20 @@ int edit_text(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n,
     }
     char *pin_out[2] = {(char *)S.pin, (char *)S.pin + kOutPiece};
     volatile u64 *h_seg = reinterpret_cast<volatile u64 *>((char *)S.pin + 2 * kOutPiece); // per segment: lines, kept, status, kept bytes so far
+    volatile u64 *h_gz = h_seg + (n_segs + 2) * 4;                                          // per batch: its members' bytes, stored members so far
+    // gzip out: every buffer of the encoder is taken here, before the first segment is handed over
+    GzDevice gz;
+    struct GzHold {
+        yacrd_engine *e = nullptr;
+        ~GzHold()
+        {
+            if (e) gzip_device_close(e);
+        }
+    } gz_hold;
+    if (job.gzip) {
+        if (const int rcg = gzip_device_open(e, gz_blocks, &gz)) return rcg;
+        gz_hold.e = e;
+    }
     // ---- the table
     HIP_TRY(S.names.reserve((size_t)name_bytes + 64));
     HIP_TRY(S.name_off.reserve((size_t)(R + 1) * sizeof(u64)));
@@ -540,8 +578,9 @@ int edit_text(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n,
 
     // ---- per segment: mark, carry, scan, pack on the engine's stream; the writer thread takes it from the segment's event
     std::vector<hipEvent_t> ev0(n_segs, nullptr), ev1(n_segs, nullptr);
-    hipStream_t wstream = nullptr;
+    hipStream_t wstream = nullptr, gstream = nullptr; // the way home; the encoder (gzip out)
     hipEvent_t wev[2] = {nullptr, nullptr};
+    std::vector<hipEvent_t> gev0, gev1, gdone; // around the kernels of every batch of the encoder; behind its sizes' way home
     std::atomic<int> bad(0); // 1 a HIP call failed, 2 the output could not be written, 3 the text is not for this path
     std::atomic<size_t> dispatched(0);
     std::atomic<bool> no_more(false);
@@ -549,7 +588,16 @@ int edit_text(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n,
     for (int b = 0; b < 2; b++) setup_ok = setup_ok && hipEventCreateWithFlags(&wev[b], hipEventDisableTiming) == hipSuccess;
     for (size_t s = 0; s < n_segs; s++)
         setup_ok = setup_ok && hipEventCreate(&ev0[s]) == hipSuccess && hipEventCreate(&ev1[s]) == hipSuccess;
-    double out_busy_ms = 0;
+    if (job.gzip) {
+        gev0.assign(n_batches, nullptr), gev1.assign(n_batches, nullptr), gdone.assign(n_batches, nullptr);
+        setup_ok = setup_ok && hipStreamCreateWithFlags(&gstream, hipStreamNonBlocking) == hipSuccess;
+        for (size_t b = 0; b < n_batches; b++)
+            setup_ok = setup_ok && hipEventCreate(&gev0[b]) == hipSuccess && hipEventCreate(&gev1[b]) == hipSuccess &&
+                       hipEventCreateWithFlags(&gdone[b], hipEventDisableTiming) == hipSuccess;
+    }
+    double out_busy_ms = 0, put_ms = 0;
+    u64 gz_text = 0, gz_members = 0, gz_stored = 0; // gzip out: kept bytes encoded, their members, the stored ones
+    size_t gz_sent = 0, gz_got = 0;                 // batches launched / fetched
     auto launch_segment = [&](u64 seg_begin, u64 seg_end, u64 avail) {
         const size_t s = (size_t)(seg_begin / (kTextChunk * kTextSeg));
         const u32 t0 = (u32)(seg_begin / yk::kGpTile), t1 = seg_end >= n ? (u32)n_tiles : (u32)(seg_end / yk::kGpTile);
@@ -569,9 +617,71 @@ int edit_text(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n,
         if (!ok) bad = 1;
         dispatched.store(s + 1, std::memory_order_release);
     };
+    // base[from, upto) in HBM -> the sink, piece by piece: one flies while the other is written
+    auto bring_home = [&](const char *base, u64 from, u64 upto) {
+        const u64 n_pieces = (upto - from + kOutPiece - 1) / kOutPiece;
+        auto fly = [&](u64 k) {
+            const u64 o = from + k * kOutPiece;
+            const size_t len = (size_t)std::min<u64>(kOutPiece, upto - o);
+            if (hipMemcpyAsync(pin_out[k & 1], base + o, len, hipMemcpyDeviceToHost, wstream) != hipSuccess ||
+                hipEventRecord(wev[k & 1], wstream) != hipSuccess)
+                bad = 1;
+        };
+        if (n_pieces) fly(0);
+        for (u64 k = 0; k < n_pieces && !bad.load(); k++) {
+            if (hipEventSynchronize(wev[k & 1]) != hipSuccess) {
+                bad = 1;
+                break;
+            }
+            if (k + 1 < n_pieces) fly(k + 1);
+            const u64 o = from + k * kOutPiece;
+            const double tp = now_ms();
+            if (!sink.put(pin_out[k & 1], (size_t)std::min<u64>(kOutPiece, upto - o))) bad = 2;
+            put_ms += now_ms() - tp;
+        }
+        if (wstream) (void)hipStreamSynchronize(wstream);
+    };
+    // gzip out (both run on the writer thread).  encode: kept bytes [gz_text, upto) -> a batch of members, on the encoder's
+    // stream; the pack that wrote them has finished (the writer has waited for the segment's event).  fetch_batch: the
+    // oldest batch not yet fetched -> the sink.
+    std::vector<u64> gz_eof(n_batches, 0);
+    auto encode = [&](u64 upto, bool last) {
+        const size_t b = gz_sent;
+        const u64 len = upto - gz_text;
+        if (b >= n_batches || len > gz.max_blocks * kGzBlock) {
+            bad = 1;
+            return;
+        }
+        h_gz[2 * b] = h_gz[2 * b + 1] = 0;
+        if (gzip_device_encode(e, gz, gstream, S.out.as<unsigned char>() + gz_text, len, last, (int)(b & 1), gev0[b], gev1[b], h_gz + 2 * b,
+                               h_gz + 2 * b + 1) != YACRD_OK ||
+            hipEventRecord(gdone[b], gstream) != hipSuccess) {
+            bad = 1;
+            return;
+        }
+        gz_eof[b] = last ? 28u : 0u; // (the EOF member: deflate_block.h, ydf::kEofBytes)
+        gz_members += (len + kGzBlock - 1) / kGzBlock;
+        gz_text = upto, gz_sent = b + 1;
+    };
+    auto fetch_batch = [&]() {
+        const size_t b = gz_got;
+        if (hipEventSynchronize(gdone[b]) != hipSuccess) { // (not the stream: the next batch is being encoded on it)
+            bad = 1;
+            return;
+        }
+        const u64 bytes = h_gz[2 * b] + gz_eof[b];
+        if (bytes > gz.max_blocks * 65536u + 28u) {
+            bad = 1;
+            return;
+        }
+        gz_stored = h_gz[2 * b + 1];
+        bring_home(reinterpret_cast<const char *>(gz.out[b & 1]), 0, bytes);
+        gz_got = b + 1;
+    };
     auto writer = [&]() {
         if (hipSetDevice(e->device) != hipSuccess) bad = 1;
         u64 from = 0;
+        size_t seen = 0; // segments taken
         for (size_t s = 0; s < n_segs && !bad.load(); s++) {
             while (dispatched.load(std::memory_order_acquire) <= s && !no_more.load() && !bad.load()) {
                 struct timespec ts = {0, 50000};
@@ -592,27 +702,22 @@ int edit_text(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n,
                 break;
             }
             const double t0 = now_ms();
-            // [from, upto) of the output buffer, piece by piece: one flies while the other is written
-            const u64 n_pieces = (upto - from + kOutPiece - 1) / kOutPiece;
-            auto fly = [&](u64 k) {
-                const u64 o = from + k * kOutPiece;
-                const size_t len = (size_t)std::min<u64>(kOutPiece, upto - o);
-                if (hipMemcpyAsync(pin_out[k & 1], S.out.as<char>() + o, len, hipMemcpyDeviceToHost, wstream) != hipSuccess ||
-                    hipEventRecord(wev[k & 1], wstream) != hipSuccess)
-                    bad = 1;
-            };
-            if (n_pieces) fly(0);
-            for (u64 k = 0; k < n_pieces && !bad.load(); k++) {
-                if (hipEventSynchronize(wev[k & 1]) != hipSuccess) {
-                    bad = 1;
-                    break;
-                }
-                if (k + 1 < n_pieces) fly(k + 1);
-                const u64 o = from + k * kOutPiece;
-                if (!sink.put(pin_out[k & 1], (size_t)std::min<u64>(kOutPiece, upto - o))) bad = 2;
+            if (!job.gzip) bring_home(S.out.as<char>(), from, upto);
+            else {
+                // every whole block that now lies complete behind the last encoded one (the last segment: the tail too, and
+                // the EOF member) goes to the encoder; the batch before it comes home while this one is encoded
+                const bool last = s + 1 == n_segs;
+                const u64 whole = last ? upto : upto / kGzBlock * kGzBlock;
+                if (whole > gz_text || last) encode(whole, last);
+                while (gz_got + 1 < gz_sent && !bad.load()) fetch_batch();
             }
-            if (wstream) (void)hipStreamSynchronize(wstream);
-            from = upto;
+            from = upto, seen = s + 1;
+            out_busy_ms += now_ms() - t0;
+        }
+        if (job.gzip && !bad.load() && seen == n_segs) {
+            const double t0 = now_ms();
+            if (n_segs == 0) encode(0, true); // (an empty text: the EOF member alone)
+            while (gz_got < gz_sent && !bad.load()) fetch_batch();
             out_busy_ms += now_ms() - t0;
         }
     };
@@ -630,6 +735,7 @@ int edit_text(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n,
         const double t_text_done = now_ms();
         wt.join();
         (void)hipStreamSynchronize(e->stream);
+        if (gstream) (void)hipStreamSynchronize(gstream);
         if (stats) stats->text_ms = job.use_mirror ? 0.0f : (float)(t_text_done - t_table);
     }
     float kernel_ms = 0;
@@ -638,7 +744,14 @@ int edit_text(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n,
             float ms = 0;
             if (hipEventElapsedTime(&ms, ev0[s], ev1[s]) == hipSuccess) kernel_ms += ms;
         }
+    float gz_kernel_ms = 0;
+    if (setup_ok && !bad.load() && !moved)
+        for (size_t b = 0; b < gz_sent; b++) gz_kernel_ms += ev_ms(gev0[b], gev1[b]);
     if (wstream) (void)hipStreamDestroy(wstream);
+    if (gstream) (void)hipStreamDestroy(gstream);
+    for (const std::vector<hipEvent_t> *v : {&gev0, &gev1, &gdone})
+        for (hipEvent_t x : *v)
+            if (x) (void)hipEventDestroy(x);
     for (hipEvent_t x : wev)
         if (x) (void)hipEventDestroy(x);
     for (size_t s = 0; s < n_segs; s++) {
@@ -660,7 +773,14 @@ int edit_text(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n,
         return fail(YACRD_EFALLBACK, "the text holds a '\"', a CR, a line whose field count differs from the first line's or one that is "
                                      "megabytes long: the host loop decides");
     if (h_status) return fail(YACRD_EINTERNAL, "overlap editor: the mark and the pack pass disagree");
-    if (sink.at != h_bytes) return fail(YACRD_EINTERNAL, "overlap editor: fewer bytes written than kept");
+    if ((job.gzip ? gz_text : sink.at) != h_bytes) return fail(YACRD_EINTERNAL, "overlap editor: fewer bytes written than kept");
+    if (job.gzip && gz_got != gz_sent) return fail(YACRD_EINTERNAL, "overlap editor: a batch of members was not fetched");
+    if (job.gzip_stats) {
+        yacrd_gzip_stats &g = *job.gzip_stats;
+        g.in_bytes = gz_text, g.out_bytes = sink.at, g.n_members = gz_members, g.n_stored = gz_stored;
+        g.h2d_ms = 0.f, g.kernel_ms = gz_kernel_ms; // (the text lies in HBM already)
+        g.d2h_ms = (float)std::max(0.0, out_busy_ms - put_ms), g.write_ms = (float)put_ms; // (d2h: with the waits for the encoder)
+    }
     if (stats) {
         stats->text_bytes = n;
         stats->kept_bytes = h_bytes;
@@ -753,6 +873,67 @@ int yacrd_engine_edit_overlaps_mem(yacrd_engine *e, int op, const char *text, ui
     }
     *out = sink.mem, *out_bytes = sink.at;
     return YACRD_OK;
+}
+
+int yacrd_engine_edit_overlaps_gzip_mem(yacrd_engine *e, int op, const char *text, uint64_t n, int format, const yacrd_type_table *types,
+                                        char **out, uint64_t *out_bytes, yacrd_edit_stats *es, yacrd_gzip_stats *gs)
+{
+    if (gs) std::memset(gs, 0, sizeof(*gs));
+    if (const int rca = edit_args(e, op, types, es)) return rca;
+    if ((!text && n) || !out || !out_bytes) return fail(YACRD_EINVAL, "null argument");
+    *out = nullptr, *out_bytes = 0;
+    EditJob job;
+    job.op = op, job.types = types, job.gzip = true, job.gzip_stats = gs;
+    if (const int rcf = overlap_format(nullptr, format, job.m4)) return rcf;
+    TextSource src;
+    src.mem = text ? text : "";
+    OutSink sink;
+    sink.cap = (size_t)(n / 4 + 4096); // (PAF text shrinks to about a quarter; the sink grows when it does not)
+    sink.mem = (char *)std::malloc((size_t)sink.cap);
+    if (!sink.mem) return fail(YACRD_ENOMEM, "host allocation failed");
+    const int rc = edit_text(e, job, src, n, sink, es);
+    if (rc != YACRD_OK) { // (members of earlier segments may lie in the buffer: it goes)
+        std::free(sink.mem);
+        if (gs) std::memset(gs, 0, sizeof(*gs));
+        return rc;
+    }
+    *out = sink.mem, *out_bytes = sink.at;
+    return YACRD_OK;
+}
+
+int yacrd_engine_edit_overlaps_gzip_file(yacrd_engine *e, int op, const char *text, uint64_t n, int format, const yacrd_type_table *types,
+                                         const char *out_path, yacrd_edit_stats *es, yacrd_gzip_stats *gs)
+{
+    if (gs) std::memset(gs, 0, sizeof(*gs));
+    if (const int rca = edit_args(e, op, types, es)) return rca;
+    if ((!text && n) || !out_path) return fail(YACRD_EINVAL, "null argument");
+    EditJob job;
+    job.op = op, job.types = types, job.gzip = true, job.gzip_stats = gs;
+    if (const int rcf = overlap_format(nullptr, format, job.m4)) return rcf;
+    struct stat ost;
+    if (lstat(out_path, &ost) == 0 && !S_ISREG(ost.st_mode)) return fail(YACRD_EFALLBACK, "the output is not a regular file: the host loop writes it");
+    // written beside its place and moved there when the EOF member is in: a text that turns out not to be for this path
+    // (a later segment may say so, with members of earlier ones already written) leaves nothing behind
+    std::string tmp = std::string(out_path) + ".XXXXXX";
+    const int ofd = mkstemp(&tmp[0]);
+    if (ofd < 0) return fail(YACRD_EFALLBACK, std::string("cannot create a file beside ") + out_path + ": the host loop words the error");
+    {
+        const mode_t um = umask(0);
+        umask(um);
+        (void)fchmod(ofd, 0666 & ~um);
+    }
+    TextSource src;
+    src.mem = text ? text : "";
+    OutSink sink;
+    sink.fd = ofd;
+    int rc = edit_text(e, job, src, n, sink, es);
+    if (::close(ofd) != 0 && rc == YACRD_OK) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
+    if (rc == YACRD_OK && ::rename(tmp.c_str(), out_path) != 0) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
+    if (rc != YACRD_OK) {
+        (void)::unlink(tmp.c_str());
+        if (gs) std::memset(gs, 0, sizeof(*gs));
+    }
+    return rc;
 }
 
 void yacrd_edit_text_free(char *p) { std::free(p); }

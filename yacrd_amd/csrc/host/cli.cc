@@ -17,6 +17,8 @@
 #include <string>
 #include <vector>
 
+#include <sys/stat.h>
+
 #include "../../../include/yacrd_engine.h"
 #include "../../../include/yacrd_host.h"
 
@@ -269,8 +271,51 @@ int main(int argc, char **argv)
         // the host loop below, which knows the whole syntax and the messages.  YACRD_NO_DEVICE_EDITOR=1: the host loop (A/B).
         int dev_edit = YACRD_EFALLBACK;
         const char *no_ed = std::getenv("YACRD_NO_DEVICE_EDITOR");
+        const char *no_df = std::getenv("YACRD_NO_DEVICE_DEFLATE");
         const bool sub_ovl = has(sub_in, ".m4") || has(sub_in, ".mhap") || has(sub_in, ".paf");
-        if (sub_ovl && (op == YACRD_OP_FILTER || op == YACRD_OP_EXTRACT) && !(no_ed && *no_ed == '1')) {
+        const bool dev_ed = sub_ovl && (op == YACRD_OP_FILTER || op == YACRD_OP_EXTRACT) && !(no_ed && *no_ed == '1');
+        // ... and on a gzip one (what minimap2 | gzip leaves): the inflated text goes to HBM — the detection's, when it read this
+        // very file and still holds it, else inflated here, BGZF member-parallel — and the kept bytes are deflated where the
+        // device packs them: only BGZF members come back (yacrd_engine_edit_overlaps_gzip_file).  What it does not take, no
+        // memory for it, YACRD_NO_DEVICE_EDITOR=1 or YACRD_NO_DEVICE_DEFLATE=1: the host loop into the gzip writer below.
+        if (dev_ed && !(no_df && *no_df == '1') && yacrd_file_compression(sub_in.c_str()) == 1) {
+            const auto t_in = std::chrono::steady_clock::now();
+            yacrd_text own{};
+            const yacrd_text *tx = nullptr;
+            struct stat sa, sb;
+            if (text.data && ::stat(input.c_str(), &sa) == 0 && ::stat(sub_in.c_str(), &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino)
+                tx = &text;
+            else {
+                const int rct = yacrd_text_from_file(sub_in.c_str(), threads == 1 ? 0 : (int)threads, &own);
+                if (rct == 1) die(yacrd_host_last_error());
+                if (rct == 0) tx = &own;
+            }
+            const double inflate_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count();
+            if (tx) {
+                const yacrd_type_table tt = {bp.n_reads, bp.name_off, bp.names, bp.read_type};
+                yacrd_edit_stats es{};
+                yacrd_gzip_stats gs{};
+                dev_edit = yacrd_engine_edit_overlaps_gzip_file(engines[0], op, tx->data, tx->n, has(sub_in, ".m4") || has(sub_in, ".mhap") ? 2 : 1,
+                                                                &tt, sub_out.c_str(), &es, &gs);
+                if (dev_edit == YACRD_ENOMEM) {
+                    std::fprintf(stderr, "[INFO] device editor + deflate: %s; falling back to the host loop\n", yacrd_last_error());
+                    for (yacrd_engine *en : engines) (void)yacrd_engine_trim(en);
+                    dev_edit = YACRD_EFALLBACK;
+                }
+                if (dev_edit != YACRD_OK && dev_edit != YACRD_EFALLBACK) die(yacrd_last_error());
+                // (on stdout: a stderr line that begins "[info] device editor" is the plain editor's — what reads the timing
+                // output tells the two paths apart by it — and no sub-command writes data to stdout)
+                if (dev_edit == YACRD_OK && timing)
+                    std::fprintf(stdout, "[info] device editor + deflate: %llu of %llu lines kept, %llu of %llu bytes -> %llu bytes, %llu members "
+                                         "(%llu stored), inflate %.1f ms, text %.1f ms, table %.1f ms, editor kernels %.1f ms, encoder kernels %.1f ms, "
+                                         "out %.1f ms, text_reused=%d\n",
+                                 (unsigned long long)es.n_kept, (unsigned long long)es.n_lines, (unsigned long long)es.kept_bytes,
+                                 (unsigned long long)es.text_bytes, (unsigned long long)gs.out_bytes, (unsigned long long)gs.n_members,
+                                 (unsigned long long)gs.n_stored, tx == &text ? 0.0 : inflate_ms, es.text_ms, es.table_ms, es.kernel_ms, gs.kernel_ms,
+                                 es.out_ms, tx == &text ? 1 : 0);
+            }
+            yacrd_text_free(&own);
+        } else if (dev_ed) {
             const yacrd_type_table tt = {bp.n_reads, bp.name_off, bp.names, bp.read_type};
             yacrd_edit_stats es{};
             const char *ct = std::getenv("YACRD_COPY_THREADS");
@@ -291,7 +336,6 @@ int main(int argc, char **argv)
         // A gzip input writes gzip (the reference's contract): the host loop inflates and edits as before, and the edited bytes
         // leave through a yacrd_gzip_writer — compressed on the device into BGZF — instead of zlib's one thread.  No memory for
         // it, bzip2 / xz, YACRD_NO_DEVICE_DEFLATE=1: the host path below, unchanged.
-        const char *no_df = std::getenv("YACRD_NO_DEVICE_DEFLATE");
         if (dev_edit != YACRD_OK && !(no_df && *no_df == '1') && yacrd_file_compression(sub_in.c_str()) == 1) {
             yacrd_gzip_writer *gw = nullptr;
             const int rco = yacrd_gzip_writer_open(engines[0], sub_out.c_str(), 0, 0, &gw);

@@ -151,18 +151,19 @@ int csr_from_records(yacrd_engine *e, const RecSlab *slabs, size_t n_slabs, cons
     if (n_intervals) *n_intervals = h_total;
     return YACRD_OK;
 }
-// exclusive prefix sums u32[n] -> u64[n + 1] on the engine's stream (asynchronous)
-int scan_u32_to_u64(yacrd_engine *e, const u32 *in, u64 n, u64 *out, DevBuf &part)
+// exclusive prefix sums u32[n] -> u64[n + 1] on the engine's stream, or on `st` (asynchronous)
+int scan_u32_to_u64(yacrd_engine *e, const u32 *in, u64 n, u64 *out, DevBuf &part, hipStream_t st)
 {
+    if (!st) st = e->stream;
     const u64 nb = (n + yk::kScanTile - 1) / yk::kScanTile;
     HIP_TRY(part.reserve((size_t)(nb + 1) * sizeof(u64)));
     if (!n) {
-        HIP_TRY(hipMemsetAsync(out, 0, sizeof(u64), e->stream));
+        HIP_TRY(hipMemsetAsync(out, 0, sizeof(u64), st));
         return YACRD_OK;
     }
-    hipLaunchKernelGGL(yk::scan_tile_sums_kernel, dim3((u32)nb), dim3(yk::kScanT), 0, e->stream, in, n, part.as<u64>());
-    hipLaunchKernelGGL(yk::scan_parts_kernel, dim3(1), dim3(yk::kScanT), 0, e->stream, part.as<u64>(), nb, out + n);
-    hipLaunchKernelGGL(yk::scan_tiles_kernel, dim3((u32)nb), dim3(yk::kScanT), 0, e->stream, in, n, part.as<u64>(), out);
+    hipLaunchKernelGGL(yk::scan_tile_sums_kernel, dim3((u32)nb), dim3(yk::kScanT), 0, st, in, n, part.as<u64>());
+    hipLaunchKernelGGL(yk::scan_parts_kernel, dim3(1), dim3(yk::kScanT), 0, st, part.as<u64>(), nb, out + n);
+    hipLaunchKernelGGL(yk::scan_tiles_kernel, dim3((u32)nb), dim3(yk::kScanT), 0, st, in, n, part.as<u64>(), out);
     return YACRD_OK;
 }
 } // namespace yke

@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = [
     "yacrd_engine_ingest_paf", "yacrd_engine_ingest_overlaps", "yacrd_engine_ingest_overlaps_mem", "yacrd_engines_ingest_overlaps",
     "yacrd_engines_ingest_overlaps_mem", "yacrd_reads_free", "yacrd_engine_trim",
     "yacrd_engine_edit_overlaps", "yacrd_engine_edit_overlaps_mem", "yacrd_edit_text_free",
+    "yacrd_engine_edit_overlaps_gzip_mem", "yacrd_engine_edit_overlaps_gzip_file",
     "yacrd_engine_gzip_mem", "yacrd_gzip_writer_open", "yacrd_gzip_writer_write", "yacrd_gzip_writer_sink", "yacrd_gzip_writer_close",
     "yacrd_gzip_writer_abort",
     "yacrd_stream_device_of", "yacrd_stream_group_open", "yacrd_stream_group_sink", "yacrd_stream_group_finish",
@@ -286,6 +287,12 @@ def load_library():
     lib.yacrd_engine_edit_overlaps_mem.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
                                                    ctypes.POINTER(_TypeTable), ctypes.POINTER(ctypes.c_void_p),
                                                    ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_EditStats)]
+    lib.yacrd_engine_edit_overlaps_gzip_mem.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                                        ctypes.POINTER(_TypeTable), ctypes.POINTER(ctypes.c_void_p),
+                                                        ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_EditStats), ctypes.POINTER(_GzipStats)]
+    lib.yacrd_engine_edit_overlaps_gzip_file.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                                         ctypes.POINTER(_TypeTable), ctypes.c_char_p, ctypes.POINTER(_EditStats),
+                                                         ctypes.POINTER(_GzipStats)]
     lib.yacrd_edit_text_free.argtypes = [ctypes.c_void_p]
     lib.yacrd_edit_text_free.restype = None
     lib.yacrd_engine_gzip_mem.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p),
@@ -605,6 +612,34 @@ class Engine:
         self._edited(rc, st)
         try:
             return ctypes.string_at(out.value, int(n_out.value)) if n_out.value else b""
+        finally:
+            self._lib.yacrd_edit_text_free(out)
+
+    def edit_overlaps_gzip(self, op, text, names, read_type, fmt, out_path=None):
+        """yacrd_engine_edit_overlaps_gzip_mem / _file: filter (op 1) / extract (op 2) the overlap `text` (inflated; bytes or
+        anything else with the buffer protocol, which is not copied; fmt 1 = PAF, 2 = M4 / MHAP) with the kept bytes deflated
+        on the device where they are packed.  Without out_path -> the BGZF stream (bytes: what gzip() gives for the kept
+        bytes); with it the stream is written there and (edit stats, gzip stats) returned.  Both are also in self.edit_stats
+        and self.gzip_stats.  Raises NeedsHostParser, with nothing written, when the text is the host loop's."""
+        tt, keep = self._type_table(names, read_type)
+        st, gs = _EditStats(), _GzipStats()
+        buf = np.frombuffer(text, dtype=np.uint8)  # (no copy: a text may be gigabytes)
+        n = int(buf.size)
+        addr = ctypes.c_void_p(buf.ctypes.data if n else None)
+        out, n_out = ctypes.c_void_p(), ctypes.c_uint64()
+        if out_path is None:
+            rc = self._lib.yacrd_engine_edit_overlaps_gzip_mem(self._h, int(op), addr, n, int(fmt), ctypes.byref(tt),
+                                                               ctypes.byref(out), ctypes.byref(n_out), ctypes.byref(st), ctypes.byref(gs))
+        else:
+            rc = self._lib.yacrd_engine_edit_overlaps_gzip_file(self._h, int(op), addr, n, int(fmt), ctypes.byref(tt),
+                                                                os.fsencode(out_path), ctypes.byref(st), ctypes.byref(gs))
+        del keep, buf
+        self._edited(rc, st)
+        self.gzip_stats = {f: getattr(gs, f) for f, _ in _GzipStats._fields_}
+        if out_path is not None:
+            return self.edit_stats, self.gzip_stats
+        try:
+            return ctypes.string_at(out.value, int(n_out.value))
         finally:
             self._lib.yacrd_edit_text_free(out)
 
