@@ -13,16 +13,14 @@
 #define YACRD_F_FORCE_GENERAL 1u
 /* use the LDS-sort kernel for the small class instead of the register-sort kernel; A/B only */
 #define YACRD_F_FORCE_LDS_SORT 2u
-/* cross-lane exchanges of the register sort all through the LDS crossbar (ds_swizzle); A/B only */
-#define YACRD_F_XLANE_DS 4u
+/* (4u was YACRD_F_XLANE_DS, 128u YACRD_F_NO_FUSED_LAUNCH, 16384u YACRD_F_SWEEP_TURNS: A/B switches whose paths are gone;
+ * the bits are not reused and, like every unknown bit, ignored) */
 /* no four-reads-per-wavefront row layout: every small read gets a whole wavefront; A/B only */
 #define YACRD_F_WAVE_ONLY 8u
 /* no two-reads-per-wavefront layout for reads of 129..256 intervals; A/B only */
 #define YACRD_F_NO_HALVES 16u
 /* always wait for the plan's class counts (no prediction from the previous run); A/B only */
 #define YACRD_F_NO_PREDICTION 64u
-/* one launch per register-sort class instead of the fused launch; A/B only */
-#define YACRD_F_NO_FUSED_LAUNCH 128u
 /* sort every event: skip the coverage pre-filter (register-sort and LDS classes; A/B, tests) */
 #define YACRD_F_NO_PREFILTER 256u
 /* count the reads the pre-filter thinned (yacrd_timing.prefiltered_reads); one global atomic per
@@ -33,9 +31,6 @@
  * often); 8192: it always does; A/B, tests */
 #define YACRD_F_NO_DEFER 4096u
 #define YACRD_F_ALWAYS_DEFER 8192u
-/* engines that share a device take turns with the dominant sweep launch (a GPU-side event wait:
- * the launch's start / stop events then time that kernel alone); A/B only */
-#define YACRD_F_SWEEP_TURNS 16384u
 /* the screen takes one / two groups of list entries per wavefront whatever the
  * launch's size (default: two from 40 M intervals on, i.e. inputs outside the Infinity Cache); tests, A/B */
 #define YACRD_F_SCREEN_ITEMS_1 262144u

@@ -135,3 +135,44 @@ def test_submit_wait_and_pipelined_engines():
     for e in engs:
         assert e.timing()["one_launch"] == 1
         e.close()
+
+
+def test_timing_totals_over_one_launch_and_default_runs():
+    """yacrd_engine_timing_total over runs that conclude in different places (the one-launch conclusion, the default path's
+    after the one-launch form declined the batch): event counters and milliseconds add, counts follow the last run."""
+    from yacrd_amd import host
+    o, iv, ln = host.synth_csr(host.SYNTH_ONT, 2000, 100000, 20241108)
+    n = np.append(np.diff(o.astype(np.int64)), 300)  # one read of 300 intervals: the one-launch form declines the batch
+    o2 = np.zeros(len(n) + 1, np.uint64)
+    o2[1:] = np.cumsum(n)
+    iv2 = np.concatenate([iv.reshape(-1, 2), np.array([(0, 900)] * 300, np.uint32)])
+    ln2 = np.append(ln, 1000).astype(np.uint32)
+    batches = [(o, iv, ln), (o2, iv2, ln2), (o, iv, ln)]
+    wants = [oracle.run(b[0], b[1].reshape(-1), b[2].astype(np.uint64), 4, 0.4, n_threads=4) for b in batches[:2]]
+    wants.append(wants[0])
+    ts = []
+    with yacrd_amd.Engine(flags=ONE | yacrd_amd.F_TIMING_FULL) as e:
+        for i, (b, want) in enumerate(zip(batches, wants)):
+            assert_same(e.run(b[0], b[1], b[2], 4, 0.4), want, "batch %d" % i)
+            ts.append(e.timing())
+        total, runs = e.timing_total()
+    assert [t["one_launch"] for t in ts] == [1, 0, 1]
+    assert runs == 3
+    for k in ("screened", "one_launch", "predicted", "prediction_misses", "fused_reruns", "build_switches", "sorting_build",
+              "screen_wide", "timed_runs"):
+        assert total[k] == sum(t[k] for t in ts), (k, total[k], [t[k] for t in ts])
+
+    def f32_sum(vals):
+        acc = np.float32(0)
+        for v in vals:
+            acc = np.float32(acc + np.float32(v))
+        return acc
+
+    for k in [name for name in total if name.endswith("_ms") and name != "class_ms"]:
+        assert np.float32(total[k]) == f32_sum(t[k] for t in ts), (k, total[k], [t[k] for t in ts])
+    for c in range(12):
+        assert np.float32(total["class_ms"][c]) == f32_sum(t["class_ms"][c] for t in ts), (c, total["class_ms"], [t["class_ms"] for t in ts])
+    for k in ("n_small", "n_medium", "n_general", "iv_small", "iv_medium", "iv_general", "class_reads", "class_intervals",
+              "fused_reads", "fused_intervals", "prefiltered_reads", "deferred_reads", "deferred_intervals", "screen_items"):
+        assert total[k] == ts[-1][k], (k, total[k], ts[-1][k])
+    assert total["total_ms"] > 0 and ts[1]["plan_ms"] > 0

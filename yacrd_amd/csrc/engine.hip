@@ -6,14 +6,13 @@
 //   -> exact general path (LDS scratch for rejected reads; global scratch for huge reads)
 //   -> compact_classify (single-pass scan) -> sync.
 //   Rare redo: degenerate reads too large for LDS, or bad_regions too small.
-// Several engines may share a device (one host thread each): their batches pipeline, the engines
-// take turns with the dominant sweep launch (BigLane).
+// Several engines may share a device (one host thread each): their batches pipeline.
+// run_on_device is that sequence as a list of phases; each phase takes the engine and the Run (engine_internal.h).
 #include "engine_internal.h"
 
 #include <time.h>
 
 #include <algorithm>
-#include <mutex>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -36,19 +35,44 @@
 
 using namespace yke;
 
+// One reader for the A/B and test knobs of the environment (each is looked up once per process, by its accessor below).
+static uint64_t env_u64(const char *name, uint64_t dflt)
+{
+    const char *v = std::getenv(name);
+    return v ? std::strtoull(v, nullptr, 10) : dflt;
+}
+
 // The deferring build of the fused launch (healthy-read screen) is used from this many intervals in the
 // classes R16 + H16 on (YACRD_DEFER_MIN_IV overrides, for A/B), unless the previous batches deferred more
 // than a quarter of what they screened: then the sorting build runs for kProbeEvery - 1 batches before the
 // screen is tried again.
 static uint64_t defer_min_intervals()
 {
-    static const uint64_t v = [] {
-        const char *e = std::getenv("YACRD_DEFER_MIN_IV");
-        return e ? std::strtoull(e, nullptr, 10) : 4000000ull;
-    }();
+    static const uint64_t v = env_u64("YACRD_DEFER_MIN_IV", 4000000ull);
     return v;
 }
 static constexpr uint32_t kProbeEvery = 16;
+
+// Batches of this many reads and more take the follow-on step as kernels of its own (finish_compact.h: mark_list_kernel +
+// deferred_list_kernel + scan_compact_kernel); YACRD_SPLIT_MIN_READS overrides (A/B: 0 = always, a huge number = never).
+static uint64_t split_min_reads()
+{
+    static const uint64_t v = env_u64("YACRD_SPLIT_MIN_READS", (uint64_t)yk::kPlanSmallReads);
+    return v;
+}
+
+// YACRD_FUSED_SHARE / YACRD_TEST_FUSED_GRID_MULT (A/B, tests): reads per workgroup and turn of screen_wg_fused_kernel (0: the
+// default), and a multiple of its grid
+static uint64_t fused_share_override()
+{
+    static const uint64_t v = std::min<uint64_t>(env_u64("YACRD_FUSED_SHARE", 0), 4096);
+    return v;
+}
+static uint64_t fused_grid_mult()
+{
+    static const uint64_t v = std::max<uint64_t>(1, env_u64("YACRD_TEST_FUSED_GRID_MULT", 1));
+    return v;
+}
 
 namespace yke {
 std::string &err_slot()
@@ -60,67 +84,61 @@ std::string &err_slot()
 
 namespace {
 
-// finish the deferred reads + scan + compact + classify: one kernel (finish_compact.h), then the totals
-// come home.  `sa` carries the run's inputs, stage / counts and the small classes' rejection list.
-// Batches of this many reads and more take the follow-on step as kernels of its own (finish_compact.h: mark_list_kernel +
-// deferred_list_kernel + scan_compact_kernel); YACRD_SPLIT_MIN_READS overrides (A/B: 0 = always, a huge number = never).
-static uint64_t split_min_reads()
+// What every launch's SweepArgs start from: the batch, the stage / counts / closed arrays, the control block; no list; what a
+// sweep rejects goes to the register classes' rejection list, what overflows an LDS sweep to over_med.  Built once per run
+// (Run::base); a launch site takes a copy and sets what its kernel needs on the copy.
+yk::SweepArgs base_sweep_args(const yacrd_engine *e, const Run &R)
 {
-    static const uint64_t v = [] {
-        const char *e = std::getenv("YACRD_SPLIT_MIN_READS");
-        return e ? std::strtoull(e, nullptr, 10) : (uint64_t)yk::kPlanSmallReads;
-    }();
-    return v;
+    yk::SweepArgs sa;
+    sa.off = R.d_off, sa.iv = R.d_iv, sa.len = R.d_len, sa.cov = R.cov, sa.prefilter = R.prefilter;
+    sa.list = nullptr, sa.list_n = nullptr, sa.rec = nullptr, sa.first = 0;
+    sa.stage = e->stage.as<uint2>(), sa.counts = e->counts.as<u32>(), sa.closed = e->closed.as<uint2>(), sa.ctr = R.ctr;
+    sa.rej_list = R.rej_small, sa.rej_count = &R.ctr->rej_small;
+    sa.over_list = R.over_med, sa.over_count = &R.ctr->over_med;
+    return sa;
+}
+// ... and over one list
+yk::SweepArgs list_sweep_args(const Run &R, const u32 *list, const u32 *list_n)
+{
+    yk::SweepArgs sa = R.base;
+    sa.list = list;
+    sa.list_n = list_n;
+    return sa;
 }
 
-static uint64_t fused_share_override()
+// scan + compact + classify (finish_compact.h, one_batch.h): the run's inputs, stage / counts, the register classes' rejection
+// list (the follow-on kernel's sort appends to it), the outputs
+yk::CompactArgs2 compact_args(const yacrd_engine *e, const Run &R)
 {
-    static const uint64_t v = [] {
-        const char *e = std::getenv("YACRD_FUSED_SHARE");
-        return e ? std::min<uint64_t>(std::strtoull(e, nullptr, 10), 4096) : (uint64_t)0;
-    }();
-    return v;
-}
-
-static uint64_t fused_grid_mult()
-{
-    static const uint64_t v = [] {
-        const char *e = std::getenv("YACRD_TEST_FUSED_GRID_MULT");
-        return e ? std::max<uint64_t>(1, std::strtoull(e, nullptr, 10)) : (uint64_t)1;
-    }();
-    return v;
-}
-
-int launch_compact(yacrd_engine *e, const yk::SweepArgs &sa, u32 n_reads, double not_cov, bool screened)
-{
-    const u32 nb = (n_reads + yk::kScanBlock - 1) / yk::kScanBlock;
-    yk::Counters *ctr = e->ctrl2[e->ctrl_cur].as<yk::Counters>();
     yk::CompactArgs2 ca;
-    ca.sweep = sa;
-    ca.sweep.first = 0;
-    ca.sweep.list = nullptr;
-    ca.sweep.list_n = nullptr;
+    ca.sweep = R.base;
     ca.sweep.over_list = nullptr;
     ca.sweep.over_count = nullptr;
-    ca.sweep.rej_list = e->lists.as<u32>() + (size_t)yk::CLS_COUNT * e->last_list_stride;
-    ca.sweep.rej_count = &ctr->rej_small;
-    ca.scan_state = reinterpret_cast<u64 *>(ctr + 1);
-    ca.n_reads = n_reads;
-    ca.not_cov = not_cov;
+    ca.scan_state = reinterpret_cast<u64 *>(R.ctr + 1);
+    ca.n_reads = R.n_reads;
+    ca.not_cov = R.not_cov;
     ca.bad_offsets = e->bad_offsets.as<u64>();
     ca.bad_regions = e->bad_regions.as<uint2>();
     ca.region_cap = (u64)(e->bad_regions.cap / sizeof(uint2));
     ca.read_type = e->read_type.as<uint8_t>();
-    if ((uint64_t)n_reads >= split_min_reads()) {
-        ca.host_ctr = e->h_ctr;
-        if (screened) {
+    ca.host_ctr = e->h_ctr;
+    return ca;
+}
+
+// The follow-on step: finish the deferred reads + scan + compact + classify, and the totals come home.
+int launch_compact(yacrd_engine *e, const Run &R)
+{
+    const u32 n_reads = R.n_reads;
+    const yk::CompactArgs2 ca = compact_args(e, R);
+    if (R.n_reads64 >= split_min_reads()) {
+        if (R.screened) {
             // the marks listed, the list dealt out evenly over a grid that is resident as a whole (finish_compact.h)
             const u32 slabs = (n_reads + yk::kMarkReads - 1) / yk::kMarkReads;
             yk::DeferList dl;
             dl.shard_cap = (slabs / yk::kDeferShards + 1u) * (u32)yk::kMarkReads;
             HIP_TRY(e->dlist.reserve((size_t)yk::kDeferShards * dl.shard_cap * sizeof(u32)));
             dl.list = e->dlist.as<u32>();
-            dl.count = reinterpret_cast<u32 *>(ca.scan_state + nb);
+            dl.count = reinterpret_cast<u32 *>(ca.scan_state + R.nb);
             if (e->compact_calls++) // (a redo of the follow-on step: the list starts over)
                 HIP_TRY(hipMemsetAsync(dl.count, 0, (size_t)yk::kDeferShards * yk::kDeferShardStride * sizeof(u32), e->stream));
             hipLaunchKernelGGL(yk::mark_list_kernel, dim3(slabs), dim3(yk::kMarkThreads), 0, e->stream, ca.sweep.counts, n_reads, dl);
@@ -131,18 +149,11 @@ int launch_compact(yacrd_engine *e, const yk::SweepArgs &sa, u32 n_reads, double
         hipLaunchKernelGGL(yk::scan_compact_kernel<4>, dim3((n_reads + 4 * yk::kScanThreads - 1) / (4 * yk::kScanThreads)), dim3(yk::kScanThreads), 0, e->stream, ca);
         return YACRD_OK;
     }
-#ifdef YK_NO_HANDOVER
-    ca.host_ctr = nullptr;
-    hipLaunchKernelGGL(yk::finish_compact_kernel, dim3(nb), dim3(yk::kScanBlock), 0, e->stream, ca);
-    HIP_TRY(hipMemcpyAsync(e->h_ctr, ctr, sizeof(yk::Counters), hipMemcpyDeviceToHost, e->stream));
-#else
     // The counter block goes home from inside the kernel (its last slab: finish_compact.h): no copy command —
     // a 4 us dispatch of its own — behind it.  (Rounds 2-3 tried this with a ticket per workgroup to find the
     // last one to FINISH: 1 953 same-address tickets on 2 M reads cost more than the copy.  The slab that ends
     // the batch needs no ticket: its look-back has seen everyone else's aggregate.)
-    ca.host_ctr = e->h_ctr;
-    hipLaunchKernelGGL(yk::finish_compact_kernel, dim3(nb), dim3(yk::kScanBlock), 0, e->stream, ca);
-#endif
+    hipLaunchKernelGGL(yk::finish_compact_kernel, dim3((n_reads + yk::kScanBlock - 1) / yk::kScanBlock), dim3(yk::kScanBlock), 0, e->stream, ca);
     return YACRD_OK;
 }
 
@@ -164,20 +175,18 @@ int gather_reads(yacrd_engine *e, const u64 *d_off, const u32 *d_len, const u32 
 
 // Global-memory exact path over `count` reads listed at d_list (host knows the count).
 int run_general_global(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u32 *d_len,
-                       const u32 *d_list, u32 count, u32 cov, hipStream_t stream, u64 *iv_total)
+                       const u32 *d_list, u32 count, u32 cov, hipStream_t stream)
 {
     std::vector<yk::GatherOut> info;
     int rc = gather_reads(e, d_off, d_len, d_list, count, stream, info);
     if (rc) return rc;
     HIP_TRY(e->gen_scratch_off.reserve((size_t)count * sizeof(u64)));
     std::vector<u64> offs(count);
-    u64 tot = 0, gen_iv = 0;
+    u64 tot = 0;
     for (u32 i = 0; i < count; i++) {
         offs[i] = tot;
         tot += 3 * info[i].n + 2;
-        gen_iv += info[i].n;
     }
-    if (iv_total) *iv_total = gen_iv;
     HIP_TRY(e->gen_scratch.reserve((size_t)tot * sizeof(u64)));
     HIP_TRY(hipMemcpyAsync(e->gen_scratch_off.p, offs.data(), (size_t)count * sizeof(u64),
                            hipMemcpyHostToDevice, stream));
@@ -196,9 +205,6 @@ int run_general_global(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, con
     return YACRD_OK;
 }
 
-// Reads with more than 16 384 intervals: device-wide segmented sort + chunked sweep
-// (sweep_big.h).  Reads that turn out to hold a degenerate interval are redone by the exact
-// general kernel afterwards.
 // Reads with more than 16 384 intervals that the trimming filter could not thin: device-wide
 // segmented sort + chunked sweep (sweep_big.h).  Reads that turn out to hold a degenerate interval
 // are appended to `redo` for the exact general kernel.
@@ -271,15 +277,11 @@ int run_big_sort(yacrd_engine *e, const uint2 *d_iv, const std::vector<yk::Gathe
 }
 
 int run_big(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u32 *d_len,
-            const u32 *d_list, u32 count, u32 cov, hipStream_t stream, u64 *iv_total)
+            const u32 *d_list, u32 count, u32 cov, hipStream_t stream)
 {
     std::vector<yk::GatherOut> info;
     int rc = gather_reads(e, d_off, d_len, d_list, count, stream, info);
     if (rc) return rc;
-    if (iv_total) {
-        *iv_total = 0;
-        for (const auto &g : info) *iv_total += g.n;
-    }
     std::vector<u32> redo; // reads for the exact general path (an interval the keys cannot express)
 
     // ---- first attempt: thin the reads with the device-wide pile-trimming filter (sweep_big_trim.h);
@@ -353,12 +355,12 @@ int run_big(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u32 *d_l
         HIP_TRY(hipMemcpyAsync(e->big_redo.p, redo.data(), redo.size() * sizeof(u32),
                                hipMemcpyHostToDevice, stream));
         HIP_TRY(hipStreamSynchronize(stream));
-        rc = run_general_global(e, d_off, d_iv, d_len, e->big_redo.as<u32>(), (u32)redo.size(), cov,
-                                stream, nullptr);
+        rc = run_general_global(e, d_off, d_iv, d_len, e->big_redo.as<u32>(), (u32)redo.size(), cov, stream);
         if (rc) return rc;
     }
     return YACRD_OK;
 }
+
 // The run's final wait: spinning (hipStreamSynchronize) or, with YACRD_F_BLOCKING_WAIT, polling
 // an event and sleeping in between (hipEventSynchronize spins as well, blocking-sync flag or not).
 int wait_for_stream(yacrd_engine *e)
@@ -379,71 +381,34 @@ int wait_for_stream(yacrd_engine *e)
     return YACRD_OK;
 }
 
-int conclude_run(yacrd_engine *e, yk::Counters c0, bool predicted, uint64_t n_reads64, uint64_t n_iv,
-                 const int *cls_b, const int *cls_e, bool fused_marked, bool screened, float extra_ms);
+int conclude_run(yacrd_engine *e, const Run &R, float extra_ms);
 int finish_pending(yacrd_engine *e);
 
-} // namespace
+// ---- the phases of a run, in launch order.  Each takes the engine and the run; what a kernel is handed can be read off
+// its launch site: a copy of R.base with that launch's fields set.
 
-namespace yke {
-// A workgroup of the fused workgroup screen ran out of looks at its queue slot (screen_wg.h: the grid was not resident as a
-// whole): whatever the batch's kernels wrote is void — the batch from the start, the workgroup classes down the three-launch chain.
-static int rerun_without_fused(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u32 *d_len, uint64_t n_reads64,
-                               uint64_t n_iv, uint32_t cov, double not_cov)
+// Every buffer of the run, the control block of this run (zeroed) and the list pointers.
+int reserve_buffers(yacrd_engine *e, Run &R)
 {
-    e->fused_off = true;
-    e->pred_valid = false;
-    const int rc = run_on_device(e, d_off, d_iv, d_len, n_reads64, n_iv, cov, not_cov, false);
-    e->fused_off = false;
-    return rc;
-}
-
-int run_on_device(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u32 *d_len,
-                  uint64_t n_reads64, uint64_t n_iv, uint32_t cov, double not_cov, bool defer)
-{
-    if (n_reads64 >= 0xFFFFFFFFull) return fail(YACRD_EINVAL, "n_reads must be < 2^32 - 1");
-    const u32 n_reads = (u32)n_reads64;
-    if (e->pending.active) return fail(YACRD_EINVAL, "a submitted batch is pending: yacrd_engine_wait first");
-    e->has_result = false;
-    e->timing = yacrd_timing{};
-
-    HIP_TRY(e->bad_offsets.reserve((n_reads64 + 1) * sizeof(u64)));
-    if (n_reads == 0) {
-        HIP_TRY(hipMemsetAsync(e->bad_offsets.p, 0, sizeof(u64), e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        e->last_reads = 0;
-        e->last_regions = 0;
-        e->has_result = true;
-        return YACRD_OK;
-    }
-
-    // YACRD_F_ONE_LAUNCH: a short batch as one kernel (one_batch.h) — unless a debug flag pins another path
-    // — and only where its look-back's progress argument holds (one_batch.h, ADVICE r4): the slabs at the front of an XCD's
-    // contiguous eighth wait for the XCD before it, so up to 7/8 of the slab-finishing wavefronts sit in wave slots for
-    // most of the launch; that needs the 8-XCD part and far more resident slots than waiters.  The cap on the reads is
-    // the kernel's own (32-bit deferred-interval sum), not the follow-on step's A/B knob.
-    const uint64_t ob_waiters = (n_reads64 + yk::kObSlab - 1) / yk::kObSlab * 7 / 8;
-    const bool one_launch = (e->flags & YACRD_F_ONE_LAUNCH) && !e->one_launch_off && n_reads64 < (uint64_t)yk::kObMaxReads &&
-                            e->num_xcc == 8 && 2 * ob_waiters <= (uint64_t)e->num_cu * 4 * YK_OB_OCC &&
-                            !(e->flags & (YACRD_F_FORCE_GENERAL | YACRD_F_WAVE_ONLY | YACRD_F_FORCE_LDS_SORT | YACRD_F_NO_HALVES |
-                                          YACRD_F_NO_PREFILTER | YACRD_F_NO_DEFER | YACRD_F_XLANE_DS | YACRD_F_NO_FUSED_LAUNCH));
+    const u32 n_reads = R.n_reads;
+    const uint64_t n_reads64 = R.n_reads64;
     // (scan-state words: one per slab of the follow-on kernel; one_batch_kernel: one per slab + its arrival counters)
-    const u32 ob_slabs = (n_reads + yk::kObSlab - 1) / yk::kObSlab;
-    const u32 nb = one_launch ? 2 * ob_slabs : (n_reads + yk::kScanBlock - 1) / yk::kScanBlock;
+    R.ob_slabs = (n_reads + yk::kObSlab - 1) / yk::kObSlab;
+    R.nb = R.one_launch ? 2 * R.ob_slabs : (n_reads + yk::kScanBlock - 1) / yk::kScanBlock;
     constexpr int kLists = yk::CLS_COUNT + 9; // class lists + three rejection lists + M2 overflow + what the screens leave of M1 / M2 / BIG + what the one-wavefront screen leaves of M1 / M2
     HIP_TRY(e->lists.reserve((size_t)kLists * n_reads * sizeof(u32)));
     // (long batches: + the shard counters of the follow-on step's list of marked reads, behind the scan words)
-    const size_t shard_ctr_bytes = (!one_launch && n_reads64 >= split_min_reads()) ? (size_t)yk::kDeferShards * yk::kDeferShardStride * sizeof(u32) : 0;
-    const size_t ctrl_bytes = (sizeof(yk::Counters) + (size_t)nb * sizeof(u64) + shard_ctr_bytes + 255) & ~(size_t)255;
+    const size_t shard_ctr_bytes = (!R.one_launch && n_reads64 >= split_min_reads()) ? (size_t)yk::kDeferShards * yk::kDeferShardStride * sizeof(u32) : 0;
+    R.ctrl_bytes = (sizeof(yk::Counters) + (size_t)R.nb * sizeof(u64) + shard_ctr_bytes + 255) & ~(size_t)255;
     e->compact_calls = 0;
     e->ctrl_cur ^= 1;
     const int cur = e->ctrl_cur, other = cur ^ 1;
     for (int i = 0; i < 2; i++) {
         const void *before = e->ctrl2[i].p;
-        HIP_TRY(e->ctrl2[i].reserve(ctrl_bytes));
+        HIP_TRY(e->ctrl2[i].reserve(R.ctrl_bytes));
         if (e->ctrl2[i].p != before) e->ctrl_clean[i] = 0; // fresh allocation: nothing zeroed yet
     }
-    HIP_TRY(e->stage.reserve((size_t)(n_iv + 2 * n_reads64) * sizeof(uint2)));
+    HIP_TRY(e->stage.reserve((size_t)(R.n_iv + 2 * n_reads64) * sizeof(uint2)));
     HIP_TRY(e->counts.reserve((size_t)n_reads * sizeof(u32)));
     HIP_TRY(e->closed.reserve((size_t)n_reads * sizeof(uint2)));
     HIP_TRY(e->read_type.reserve((size_t)n_reads));
@@ -451,549 +416,470 @@ int run_on_device(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u3
         HIP_TRY(e->bad_regions.reserve((size_t)(4 * n_reads64 + 1024) * sizeof(uint2)));
 
     // (a read of M1 has more than 512 intervals, one of M2 more than 4 096: that many records at most)
-    const u32 mrec_cap1 = (u32)std::min<u64>(n_reads64, n_iv / 513 + 1), mrec_cap2 = (u32)std::min<u64>(n_reads64, n_iv / 4097 + 1);
-    HIP_TRY(e->mrec.reserve(((size_t)mrec_cap1 + mrec_cap2) * sizeof(uint4)));
-    u32 *lists = e->lists.as<u32>();
+    R.mrec_cap1 = (u32)std::min<u64>(n_reads64, R.n_iv / 513 + 1), R.mrec_cap2 = (u32)std::min<u64>(n_reads64, R.n_iv / 4097 + 1);
+    HIP_TRY(e->mrec.reserve(((size_t)R.mrec_cap1 + R.mrec_cap2) * sizeof(uint4)));
+    R.lists = e->lists.as<u32>();
     e->last_list_stride = n_reads;
-    auto list_of = [&](int i) { return lists + (size_t)i * n_reads; };
-    u32 *rej_small = list_of(yk::CLS_COUNT), *rej_med = list_of(yk::CLS_COUNT + 1),
-        *rej_big = list_of(yk::CLS_COUNT + 2), *over_med = list_of(yk::CLS_COUNT + 3);
-    u32 *const fb_med[2] = {list_of(yk::CLS_COUNT + 4), list_of(yk::CLS_COUNT + 5)};
-    u32 *const fb_big = list_of(yk::CLS_COUNT + 6);
-    u32 *const fb_stream[2] = {list_of(yk::CLS_COUNT + 7), list_of(yk::CLS_COUNT + 8)};
-    yk::Counters *ctr = e->ctrl2[cur].as<yk::Counters>();
-    const bool full = (e->flags & YACRD_F_TIMING_FULL) != 0;
-    const int xm = (e->flags & YACRD_F_XLANE_DS) ? 1 : 0;
+    R.rej_small = R.list_of(yk::CLS_COUNT), R.rej_med = R.list_of(yk::CLS_COUNT + 1);
+    R.rej_big = R.list_of(yk::CLS_COUNT + 2), R.over_med = R.list_of(yk::CLS_COUNT + 3);
+    R.fb_med[0] = R.list_of(yk::CLS_COUNT + 4), R.fb_med[1] = R.list_of(yk::CLS_COUNT + 5);
+    R.fb_big = R.list_of(yk::CLS_COUNT + 6);
+    R.fb_stream[0] = R.list_of(yk::CLS_COUNT + 7), R.fb_stream[1] = R.list_of(yk::CLS_COUNT + 8);
+    R.ctr = e->ctrl2[cur].as<yk::Counters>();
+    R.base = base_sweep_args(e, R);
 
-    // ---- plan: bin reads by size class.  Only classes that hold reads are launched (an empty
-    // launch costs ~4 us and there are twelve classes), so the host needs the class counts.
-    // Normally that is one sync right here.  When the previous run on this engine had the same
-    // shape (reads, intervals, flags) its class set is used as a PREDICTION instead: the sweeps
-    // are launched without waiting, sized for n_reads, and the prediction is validated against
-    // the real counts at the final sync (a class that was not predicted is launched then and
-    // the compaction redone).  Streams of similar batches never pay the mid-pipeline sync.
     // The control block (counters + scan state) must start out zero.  The engine alternates
     // between two blocks and the plan kernel of a run zeroes the other one, so in steady state no
     // run starts with a fill (hipMemsetAsync = two fill kernels + their launch gaps).
-    if (e->ctrl_clean[cur] < ctrl_bytes) HIP_TRY(hipMemsetAsync(ctr, 0, ctrl_bytes, e->stream));
+    if (e->ctrl_clean[cur] < R.ctrl_bytes) HIP_TRY(hipMemsetAsync(R.ctr, 0, R.ctrl_bytes, e->stream));
     e->ctrl_clean[cur] = 0;
-    const size_t other_bytes = std::min<size_t>(e->ctrl2[other].cap, (size_t)1 << 30) & ~(size_t)3;
-    if (full) HIP_TRY(hipEventRecord(e->ev[EV_START], e->stream));
-    if (one_launch) {
-        yk::OneBatchArgs oa;
-        yk::SweepArgs &s = oa.c.sweep;
-        s.off = d_off, s.iv = d_iv, s.len = d_len, s.list = nullptr, s.list_n = nullptr, s.rec = nullptr, s.first = 0, s.cov = cov;
-        s.prefilter = (e->flags & YACRD_F_COUNT_PREFILTERED) ? 2u : 1u;
-        s.stage = e->stage.as<uint2>(), s.counts = e->counts.as<u32>(), s.closed = e->closed.as<uint2>();
-        s.rej_list = rej_small, s.rej_count = &ctr->rej_small, s.over_list = nullptr, s.over_count = nullptr, s.ctr = ctr;
-        oa.c.scan_state = reinterpret_cast<u64 *>(ctr + 1);
-        oa.c.n_reads = n_reads;
-        oa.c.not_cov = not_cov;
-        oa.c.bad_offsets = e->bad_offsets.as<u64>();
-        oa.c.bad_regions = e->bad_regions.as<uint2>();
-        oa.c.region_cap = (u64)(e->bad_regions.cap / sizeof(uint2));
-        oa.c.read_type = e->read_type.as<uint8_t>();
-        oa.c.host_ctr = e->h_ctr;
-        oa.slab_ctr = oa.c.scan_state + ob_slabs;
-        oa.n_slabs = ob_slabs;
-        oa.zero = e->ctrl2[other].as<u32>();
-        oa.zero_words = (u32)(other_bytes / 4);
-        e->h_ctr->ob_unsupported = 0; // (written from the device only when set)
-        e->h_ctr->scan_ticket = 0;    // (the slab that ends the batch sends the counters home: nb tickets then)
-        // (one wavefront per kObReads reads; slabs go round the XCDs, so the grid is whole rounds of eight slabs)
-        hipLaunchKernelGGL(yk::one_batch_kernel, dim3(((ob_slabs + 7) / 8) * 8 * (u32)(yk::kObSlab / yk::kObReads)), dim3(64), 0, e->stream, oa);
-        e->ctrl_clean[other] = other_bytes;
-        if (full) HIP_TRY(hipEventRecord(e->ev[EV_COMPACT], e->stream));
-        Pending &p = e->pending;
-        p = Pending{};
-        p.active = true, p.one_launch = true;
-        p.d_off = d_off, p.d_iv = d_iv, p.d_len = d_len, p.n_reads = n_reads64, p.n_iv = n_iv, p.cov = cov, p.not_cov = not_cov;
-        for (int i = 0; i < 12; i++) p.cls_b[i] = p.cls_e[i] = -1;
-        return defer ? YACRD_OK : finish_pending(e); // (yacrd_engine_submit_device: the caller waits later)
-    }
-    {
-        const u32 plan_mode = (u32)((e->flags & YACRD_F_FORCE_GENERAL) ? 1
-                                    : (e->flags & (YACRD_F_WAVE_ONLY | YACRD_F_FORCE_LDS_SORT)) ? 2
-                                    : (e->flags & YACRD_F_NO_HALVES) ? 3 : 0);
-        if (n_reads < yk::kPlanSmallReads)
-            hipLaunchKernelGGL((yk::plan_kernel<1, yk::kPlanSmallBlock>), dim3((n_reads + yk::kPlanSmallBlock - 1) / yk::kPlanSmallBlock),
-                               dim3(yk::kPlanSmallBlock), 0, e->stream, d_off, n_reads, lists, ctr, plan_mode, e->ctrl2[other].as<u32>(), (u32)(other_bytes / 4), e->counts.as<u32>(), e->mrec.as<uint4>(), mrec_cap1, mrec_cap2);
-        else // (eight reads per thread — 611 workgroups instead of 1 221 on configs[4] — measured 32.0 us against 29.9: profiles/r05/m_*)
-            hipLaunchKernelGGL(yk::plan_kernel<4>, dim3((n_reads + 4 * yk::kPlanBlock - 1) / (4 * yk::kPlanBlock)),
-                               dim3(yk::kPlanBlock), 0, e->stream, d_off, n_reads, lists, ctr, plan_mode,
-                               e->ctrl2[other].as<u32>(), (u32)(other_bytes / 4), e->counts.as<u32>(), e->mrec.as<uint4>(), mrec_cap1, mrec_cap2);
-    }
-    e->ctrl_clean[other] = other_bytes;
-    if (full) HIP_TRY(hipEventRecord(e->ev[EV_PLAN], e->stream));
+    R.other_bytes = std::min<size_t>(e->ctrl2[other].cap, (size_t)1 << 30) & ~(size_t)3;
+    return YACRD_OK;
+}
 
+// YACRD_F_ONE_LAUNCH: the whole batch as one kernel (one_batch.h).
+int launch_one_batch(yacrd_engine *e, Run &R)
+{
+    const int other = e->ctrl_cur ^ 1;
+    yk::OneBatchArgs oa;
+    oa.c = compact_args(e, R);
+    oa.slab_ctr = oa.c.scan_state + R.ob_slabs;
+    oa.n_slabs = R.ob_slabs;
+    oa.zero = e->ctrl2[other].as<u32>();
+    oa.zero_words = (u32)(R.other_bytes / 4);
+    e->h_ctr->ob_unsupported = 0; // (written from the device only when set)
+    e->h_ctr->scan_ticket = 0;    // (the slab that ends the batch sends the counters home: nb tickets then)
+    // (one wavefront per kObReads reads; slabs go round the XCDs, so the grid is whole rounds of eight slabs)
+    hipLaunchKernelGGL(yk::one_batch_kernel, dim3(((R.ob_slabs + 7) / 8) * 8 * (u32)(yk::kObSlab / yk::kObReads)), dim3(64), 0, e->stream, oa);
+    e->ctrl_clean[other] = R.other_bytes;
+    if (R.full) HIP_TRY(hipEventRecord(e->ev[EV_COMPACT], e->stream));
+    return YACRD_OK;
+}
+
+// plan: bin reads by size class (it also zeroes the other control block for the next run).
+int launch_plan(yacrd_engine *e, Run &R)
+{
+    const int other = e->ctrl_cur ^ 1;
+    const u32 n_reads = R.n_reads;
+    const u32 plan_mode = (u32)((e->flags & YACRD_F_FORCE_GENERAL) ? 1
+                                : (e->flags & (YACRD_F_WAVE_ONLY | YACRD_F_FORCE_LDS_SORT)) ? 2
+                                : (e->flags & YACRD_F_NO_HALVES) ? 3 : 0);
+    if (n_reads < yk::kPlanSmallReads)
+        hipLaunchKernelGGL((yk::plan_kernel<1, yk::kPlanSmallBlock>), dim3((n_reads + yk::kPlanSmallBlock - 1) / yk::kPlanSmallBlock),
+                           dim3(yk::kPlanSmallBlock), 0, e->stream, R.d_off, n_reads, R.lists, R.ctr, plan_mode, e->ctrl2[other].as<u32>(), (u32)(R.other_bytes / 4), e->counts.as<u32>(), e->mrec.as<uint4>(), R.mrec_cap1, R.mrec_cap2);
+    else // (eight reads per thread — 611 workgroups instead of 1 221 on configs[4] — measured 32.0 us against 29.9: profiles/r05/m_*)
+        hipLaunchKernelGGL(yk::plan_kernel<4>, dim3((n_reads + 4 * yk::kPlanBlock - 1) / (4 * yk::kPlanBlock)),
+                           dim3(yk::kPlanBlock), 0, e->stream, R.d_off, n_reads, R.lists, R.ctr, plan_mode,
+                           e->ctrl2[other].as<u32>(), (u32)(R.other_bytes / 4), e->counts.as<u32>(), e->mrec.as<uint4>(), R.mrec_cap1, R.mrec_cap2);
+    e->ctrl_clean[other] = R.other_bytes;
+    if (R.full) HIP_TRY(hipEventRecord(e->ev[EV_PLAN], e->stream));
+    return YACRD_OK;
+}
+
+// Only classes that hold reads are launched (an empty launch costs ~4 us and there are twelve
+// classes), so the host needs the class counts.  Normally that is one sync right here.  When the
+// previous run on this engine had the same shape (reads, intervals, flags) its class set is used as
+// a PREDICTION instead: the sweeps are launched without waiting, sized for n_reads, and the
+// prediction is validated against the real counts at the final sync (a class that was not predicted
+// is launched then and the compaction redone).  Streams of similar batches never pay the
+// mid-pipeline sync.
+int size_launches(yacrd_engine *e, Run &R)
+{
+    const uint64_t n_reads64 = R.n_reads64;
     // (round 6: a batch that holds reads beyond the workgroup classes is predicted too — until then it always waited for the
     // plan's counts, ~20 us of configs[3]'s step —: the device-wide screen is launched for the previous run's count and intervals
     // of such reads, which must come out the same, and must have left nothing to the host-driven sort)
     const bool big_predictable = !(e->flags & YACRD_F_NO_PREFILTER) && e->pred.fb_big == 0;
-    const bool predicted = e->pred_valid && e->pred_reads == n_reads64 && e->pred_iv == n_iv &&
-                           (e->pred.n[yk::CLS_GENERAL] == 0 || big_predictable) &&
-                           !(e->flags & (YACRD_F_FORCE_GENERAL | YACRD_F_NO_PREDICTION));
-    const u32 pred_big_n = predicted ? e->pred.n[yk::CLS_GENERAL] : 0u;
-    const u64 pred_big_iv = predicted ? e->pred.iv[yk::CLS_GENERAL] : 0ull;
-    struct LaunchSet {
-        u32 n[12];     // reads used to size the grid; 0 = class not launched
-        u32 hint[12];  // the class's size as far as the host knows it (its count, or the prediction + a margin): grids of kernels that cover a list of any length
-        u32 first[12]; // first list entry the launch covers (remainder launches)
-        u64 iv[12];    // intervals (to pick the dominant class)
-    } ls{};
-    yk::Counters c0{};
-    const bool tight_grids = !(e->flags & YACRD_F_FORCE_LDS_SORT);
-    if (predicted) {
+    R.predicted = e->pred_valid && e->pred_reads == n_reads64 && e->pred_iv == R.n_iv &&
+                  (e->pred.n[yk::CLS_GENERAL] == 0 || big_predictable) &&
+                  !(e->flags & (YACRD_F_FORCE_GENERAL | YACRD_F_NO_PREDICTION));
+    LaunchSet &ls = R.ls;
+    if (R.predicted) {
         // Register-sort classes: one workgroup per 4..16 reads, so the grid is sized for the
         // predicted count plus a margin (idle workgroups are not free: 19 000 of them cost ~3 us);
         // reads beyond the grid are swept by a remainder launch after the validation.  The LDS
         // classes run grid-stride loops and need no margin.
         for (int cls = 0; cls < yk::CLS_GENERAL; cls++) {
             const u64 p = e->pred.n[cls];
-            const u64 cap = (cls <= yk::CLS_W16 && tight_grids) ? ((p + p / 8 + 64 + 15) & ~(u64)15)
-                                                               : n_reads64;
+            const u64 cap = (cls <= yk::CLS_W16 && R.tight_grids) ? ((p + p / 8 + 64 + 15) & ~(u64)15)
+                                                                 : n_reads64;
             ls.n[cls] = p ? (u32)std::min<u64>(cap, (n_reads64 + 15) & ~(u64)15) : 0;
             ls.hint[cls] = p ? (u32)std::min<u64>(p + p / 8 + 64, n_reads64) : 0;
             ls.iv[cls] = e->pred.iv[cls];
         }
+        R.big_n = e->pred.n[yk::CLS_GENERAL], R.big_iv = e->pred.iv[yk::CLS_GENERAL];
     } else {
-        HIP_TRY(hipMemcpyAsync(e->h_ctr, ctr, sizeof(yk::Counters), hipMemcpyDeviceToHost,
-                               e->stream));
+        HIP_TRY(hipMemcpyAsync(e->h_ctr, R.ctr, sizeof(yk::Counters), hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
-        c0 = *e->h_ctr;
+        R.c0 = *e->h_ctr;
         for (int cls = 0; cls < yk::CLS_GENERAL; cls++) {
-            ls.n[cls] = c0.n[cls];
-            ls.hint[cls] = c0.n[cls];
-            ls.iv[cls] = c0.iv[cls];
+            ls.n[cls] = R.c0.n[cls];
+            ls.hint[cls] = R.c0.n[cls];
+            ls.iv[cls] = R.c0.iv[cls];
+        }
+        R.big_n = R.c0.n[yk::CLS_GENERAL], R.big_iv = R.c0.iv[yk::CLS_GENERAL];
+    }
+    for (int cls = 0; cls < yk::CLS_GENERAL; cls++)
+        if (ls.n[cls] && (R.dom_cls < 0 || ls.iv[cls] > ls.iv[R.dom_cls])) R.dom_cls = cls;
+    return YACRD_OK;
+}
+
+// Kernel-level timing.  An event costs ~3 us of stream time, so by default only the class
+// with the most intervals (the dominant kernel) is bracketed; YACRD_F_TIMING_FULL brackets
+// every launched class and the phases.
+hipError_t before_class(yacrd_engine *e, Run &R, int cls)
+{
+    if (!R.timing_on || !(R.full || cls == R.dom_cls)) return hipSuccess;
+    if (R.n_cls_ev > 0 && R.full) { // the previous class's end mark is this one's begin mark
+        R.cls_b[cls] = R.n_cls_ev - 1;
+        return hipSuccess;
+    }
+    R.cls_b[cls] = R.n_cls_ev;
+    return hipEventRecord(e->ev_cls[R.n_cls_ev++], e->stream);
+}
+hipError_t mark_class(yacrd_engine *e, Run &R, int cls)
+{
+    if (!R.timing_on || !(R.full || cls == R.dom_cls)) return hipSuccess;
+    R.cls_e[cls] = R.n_cls_ev;
+    return hipEventRecord(e->ev_cls[R.n_cls_ev++], e->stream);
+}
+
+// The register-sort classes of `set`: the row / half-wavefront classes R2..H16 in one launch, the one-read-per-wavefront
+// classes W2..W16 a launch each.  (What they reject is looked at after the final sync.)  `again`: a second pass.
+int launch_register_classes(yacrd_engine *e, Run &R, const LaunchSet &set, bool again)
+{
+    yk::Counters *ctr = R.ctr;
+    const bool fuse = !(e->flags & YACRD_F_FORCE_LDS_SORT);
+    if (fuse) {
+        yk::FusedArgs fa;
+        fa.base = R.base; // (list / list_n / first: per class, from the table below)
+        // R16 / H16: the healthy-read screen, the rest left to finish_compact_kernel — unless the last
+        // batches failed the screen too often (e->nodefer_left: see conclude_run)
+        const u64 fused_iv = set.iv[yk::CLS_R16] + set.iv[yk::CLS_H16];
+        const bool defer = R.prefilter && !(e->flags & YACRD_F_NO_DEFER) &&
+                           ((e->flags & YACRD_F_ALWAYS_DEFER) ||
+                            (fused_iv >= defer_min_intervals() && e->nodefer_left == 0));
+        // two groups of list entries per wavefront in the screened classes when the launch streams from
+        // HBM (more than the 256 MiB Infinity Cache holds): twice the loads in flight per wavefront
+        // ... unless the last screened batch left more than a tenth of its reads to the sort: then the one-item build WITH
+        // the second looks (sliding windows, sweep_wave.h) takes the next kProbeEvery - 1 — dovetail ends spread by
+        // hundreds of positions need them (configs[1] at sigma = 100: 79 % decided against 95 %; configs[2] at 300: 79 %
+        // against 97 %), reads that do not are a tenth faster without (conclude_run: wide_left)
+        const bool wide = defer && !(e->flags & YACRD_F_SCREEN_ITEMS_2) && ((e->flags & YACRD_F_SCREEN_WIDE) || e->wide_left > 0);
+        const int items = !defer ? 1
+                          : (wide || (e->flags & YACRD_F_SCREEN_ITEMS_1)) ? 1
+                          : ((e->flags & YACRD_F_SCREEN_ITEMS_2) || fused_iv >= 40000000ull) ? 2 : 1;
+        e->last_items = (uint32_t)items;
+        e->last_wide = wide;
+        if (!again) e->last_build = !defer ? 0 : wide ? 3 : items;
+        fa.base.over_list = nullptr; // (the deferring build marks its reads in counts[])
+        fa.base.over_count = nullptr;
+        fa.n_entries = 0;
+        u32 blocks = 0;
+        bool has_dom = false;
+        for (int cls = yk::CLS_R2; cls <= yk::CLS_H16; cls++) {
+            if (!set.n[cls]) continue;
+            const u32 per = yk::sweep_group_reads_per_block(cls, defer ? yk::kDeferWaves : yk::kFusedWaves) *
+                            (cls >= yk::CLS_R16 ? (u32)items : 1u);
+            blocks += (set.n[cls] + per - 1) / per;
+            fa.cls[fa.n_entries] = (u32)cls;
+            fa.block_end[fa.n_entries] = blocks;
+            fa.list[fa.n_entries] = R.list_of(cls);
+            fa.list_n[fa.n_entries] = &ctr->n[cls];
+            fa.first[fa.n_entries] = set.first[cls];
+            fa.n_entries++;
+            has_dom |= cls == R.dom_cls;
+        }
+        if (fa.n_entries) {
+            const bool mark = R.timing_on && (R.full || has_dom);
+            // the launch's build, chosen once: sorting; screening with one item, with the second looks, with two items
+            void (*kernel)(yk::FusedArgs) = yk::sweep_small_fused_kernel;
+            u32 threads = 64 * yk::kFusedWaves;
+            if (defer && items == 2) kernel = yk::sweep_small_fused_defer2_kernel, threads = 64;
+            else if (defer && wide) kernel = yk::sweep_small_fused_defer_wide_kernel, threads = 64 * yk::kDeferWaves;
+            else if (defer) kernel = yk::sweep_small_fused_defer_kernel, threads = 64 * yk::kDeferWaves;
+            // start / stop events attached to the launch itself (hipExtLaunchKernelGGL): the
+            // kernel's own dispatch timestamps, no event packets before and after it.
+            // (Until round 6 engines that share a device — batches pipelined over several engines — could take turns with
+            // this launch, a GPU-side wait on the previous engine's end-of-sweep event: the hand-over cost ~10 us per batch
+            // (configs[1], three engines: 47.0 us per batch with turns, 38.8 without), and a sweep that fills the GPU leaves
+            // the next one little room to overlap anyway (its bracket grows by ~1 us: what the roofline then reports is on
+            // the safe side).)
+            hipExtLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, e->stream, mark ? e->ev_cls[22] : (hipEvent_t) nullptr,
+                                  mark ? e->ev_cls[23] : (hipEvent_t) nullptr, 0, fa);
+            if (mark) R.fused_marked = true;
+            if (defer && (set.n[yk::CLS_R16] || set.n[yk::CLS_H16])) R.screened = true;
         }
     }
-
-    yk::SweepArgs sa;
-    sa.first = 0;
-    sa.off = d_off;
-    sa.iv = d_iv;
-    sa.len = d_len;
-    sa.cov = cov;
-    sa.prefilter = (e->flags & YACRD_F_NO_PREFILTER) ? 0u : (e->flags & YACRD_F_COUNT_PREFILTERED) ? 2u : 1u;
-    sa.stage = e->stage.as<uint2>();
-    sa.counts = e->counts.as<u32>();
-    sa.closed = e->closed.as<uint2>();
-    sa.ctr = ctr;
-    sa.rec = nullptr;
-    sa.over_list = over_med;
-    sa.over_count = &ctr->over_med;
-
-    // Kernel-level timing.  An event costs ~3 us of stream time, so by default only the class
-    // with the most intervals (the dominant kernel) is bracketed; YACRD_F_TIMING_FULL brackets
-    // every launched class and the phases.
-    int cls_b[12], cls_e[12]; // event indices bracketing each class, -1 = not recorded
-    for (int i = 0; i < 12; i++) cls_b[i] = cls_e[i] = -1;
-    int n_cls_ev = 0, dom_cls = -1;
-    bool timing_on = !(e->flags & YACRD_F_NO_TIMING);
-    if ((e->flags & YACRD_F_TIMING_SAMPLED) && !full && (e->run_seq++ % 8u) != 0) timing_on = false;
-    auto before_class = [&](int cls) -> hipError_t {
-        if (!timing_on || !(full || cls == dom_cls)) return hipSuccess;
-        if (n_cls_ev > 0 && full) { // the previous class's end mark is this one's begin mark
-            cls_b[cls] = n_cls_ev - 1;
-            return hipSuccess;
-        }
-        cls_b[cls] = n_cls_ev;
-        return hipEventRecord(e->ev_cls[n_cls_ev++], e->stream);
-    };
-    auto mark_class = [&](int cls) -> hipError_t {
-        if (!timing_on || !(full || cls == dom_cls)) return hipSuccess;
-        cls_e[cls] = n_cls_ev;
-        return hipEventRecord(e->ev_cls[n_cls_ev++], e->stream);
-    };
-
-    bool fused_marked = false, screened = false;
-    struct MissGuard { // (a miss found by THIS call is reported by its conclude_run and forgotten when the call returns)
-        yacrd_engine *e;
-        bool before;
-        ~MissGuard() { e->miss_pending = before; }
-    } miss_guard{e, e->miss_pending};
-    e->prev_build = e->last_build;
-    e->last_build = -1;
-    // sweeps of the classes in `set` (what the register sweeps reject is looked at after the final sync)
-    auto launch_sweeps = [&](const LaunchSet &set, bool again = false) -> int {
-        sa.rej_list = rej_small;
-        sa.rej_count = &ctr->rej_small;
-        // the row / half-wavefront classes in one launch
-        const bool fuse = !(e->flags & (YACRD_F_FORCE_LDS_SORT | YACRD_F_XLANE_DS |
-                                        YACRD_F_NO_FUSED_LAUNCH));
-        if (fuse) {
-            yk::FusedArgs fa;
-            fa.base = sa;
-            // R16 / H16: the healthy-read screen, the rest left to finish_compact_kernel — unless the last
-            // batches failed the screen too often (e->nodefer_left: see conclude_run)
-            const u64 fused_iv = set.iv[yk::CLS_R16] + set.iv[yk::CLS_H16];
-            const bool defer = sa.prefilter && !(e->flags & YACRD_F_NO_DEFER) &&
-                               ((e->flags & YACRD_F_ALWAYS_DEFER) ||
-                                (fused_iv >= defer_min_intervals() && e->nodefer_left == 0));
-            // two groups of list entries per wavefront in the screened classes when the launch streams from
-            // HBM (more than the 256 MiB Infinity Cache holds): twice the loads in flight per wavefront
-            // ... unless the last screened batch left more than a tenth of its reads to the sort: then the one-item build WITH
-            // the second looks (sliding windows, sweep_wave.h) takes the next kProbeEvery - 1 — dovetail ends spread by
-            // hundreds of positions need them (configs[1] at sigma = 100: 79 % decided against 95 %; configs[2] at 300: 79 %
-            // against 97 %), reads that do not are a tenth faster without (conclude_run: wide_left)
-            const bool wide = defer && !(e->flags & YACRD_F_SCREEN_ITEMS_2) && ((e->flags & YACRD_F_SCREEN_WIDE) || e->wide_left > 0);
-            const int items = !defer ? 1
-                              : (wide || (e->flags & YACRD_F_SCREEN_ITEMS_1)) ? 1
-                              : ((e->flags & YACRD_F_SCREEN_ITEMS_2) || fused_iv >= 40000000ull) ? 2 : 1;
-            e->last_items = (uint32_t)items;
-            e->last_wide = wide;
-            if (!again) e->last_build = !defer ? 0 : wide ? 3 : items;
-            fa.base.over_list = nullptr; // (the deferring build marks its reads in counts[])
-            fa.base.over_count = nullptr;
-            fa.n_entries = 0;
-            u32 blocks = 0;
-            bool has_dom = false;
-            for (int cls = yk::CLS_R2; cls <= yk::CLS_H16; cls++) {
-                if (!set.n[cls]) continue;
-                const u32 per = yk::sweep_group_reads_per_block(cls, defer ? yk::kDeferWaves : yk::kFusedWaves) *
-                                (cls >= yk::CLS_R16 ? (u32)items : 1u);
-                blocks += (set.n[cls] + per - 1) / per;
-                fa.cls[fa.n_entries] = (u32)cls;
-                fa.block_end[fa.n_entries] = blocks;
-                fa.list[fa.n_entries] = list_of(cls);
-                fa.list_n[fa.n_entries] = &ctr->n[cls];
-                fa.first[fa.n_entries] = set.first[cls];
-                fa.n_entries++;
-                has_dom |= cls == dom_cls;
-            }
-            if (fa.n_entries) {
-                const bool mark = timing_on && (full || has_dom);
-                // Engines that share a device (batches pipelined over several engines) may take
-                // turns with this launch (YACRD_F_SWEEP_TURNS: a GPU-side wait on the previous engine's
-                // end-of-sweep event, taken before the bracket opens, so that the bracket times the
-                // kernel alone).  Not the default any more: the hand-over costs ~10 us per batch
-                // (configs[1], three engines: 47.0 us per batch with turns, 38.8 without), and a sweep
-                // that fills the GPU leaves the next one little room to overlap anyway (its bracket
-                // grows by ~1 us: what the roofline then reports is on the safe side).
-                BigLane &lane = g_big_lane[e->device & 63];
-                std::lock_guard<std::mutex> turn(lane.mu);
-                const bool shared = (e->flags & YACRD_F_SWEEP_TURNS) && lane.owner != nullptr && lane.owner != e;
-                if (shared) HIP_TRY(hipStreamWaitEvent(e->stream, lane.last, 0));
-                // start / stop events attached to the launch itself (hipExtLaunchKernelGGL): the
-                // kernel's own dispatch timestamps, no event packets before and after it
-                const bool chain = (e->flags & YACRD_F_SWEEP_TURNS) && (shared || lane.n_engines > 1);
-                if (defer && items == 2)
-                    hipExtLaunchKernelGGL(yk::sweep_small_fused_defer2_kernel, dim3(blocks), dim3(64), 0,
-                                          e->stream, mark ? e->ev_cls[22] : (hipEvent_t) nullptr,
-                                          (mark || chain) ? e->ev_cls[23] : (hipEvent_t) nullptr, 0, fa);
-                else if (defer && wide)
-                    hipExtLaunchKernelGGL(yk::sweep_small_fused_defer_wide_kernel, dim3(blocks), dim3(64 * yk::kDeferWaves), 0,
-                                          e->stream, mark ? e->ev_cls[22] : (hipEvent_t) nullptr,
-                                          (mark || chain) ? e->ev_cls[23] : (hipEvent_t) nullptr, 0, fa);
-                else if (defer)
-                    hipExtLaunchKernelGGL(yk::sweep_small_fused_defer_kernel, dim3(blocks), dim3(64 * yk::kDeferWaves), 0,
-                                          e->stream, mark ? e->ev_cls[22] : (hipEvent_t) nullptr,
-                                          (mark || chain) ? e->ev_cls[23] : (hipEvent_t) nullptr, 0, fa);
-                else
-                    hipExtLaunchKernelGGL(yk::sweep_small_fused_kernel, dim3(blocks), dim3(64 * yk::kFusedWaves), 0,
-                                          e->stream, mark ? e->ev_cls[22] : (hipEvent_t) nullptr,
-                                          (mark || chain) ? e->ev_cls[23] : (hipEvent_t) nullptr, 0, fa);
-                if (mark || chain) {
-                    lane.last = e->ev_cls[23];
-                    lane.owner = e;
-                }
-                if (mark) fused_marked = true;
-                if (defer && (set.n[yk::CLS_R16] || set.n[yk::CLS_H16])) screened = true;
+    for (int cls = fuse ? yk::CLS_W2 : yk::CLS_R2; cls <= yk::CLS_W16; cls++) { // register sort per lane group
+        if (!set.n[cls]) continue;
+        HIP_TRY(before_class(e, R, cls));
+        yk::SweepArgs sa = list_sweep_args(R, R.list_of(cls), &ctr->n[cls]);
+        sa.first = set.first[cls];
+        if (!fuse) { // YACRD_F_FORCE_LDS_SORT
+            const u32 grid = (u32)std::min<uint64_t>(set.n[cls], (uint64_t)e->num_cu * 32);
+            hipLaunchKernelGGL((yk::sweep_lds_kernel<64, (int)yk::kSmallEvents>), dim3(grid), dim3(64), 0, e->stream, sa);
+        } else {
+            switch (cls) {
+            case yk::CLS_W2: yk::launch_sweep_group<64, 2>(sa, set.n[cls], e->stream); break;
+            case yk::CLS_W4: yk::launch_sweep_group<64, 4>(sa, set.n[cls], e->stream); break;
+            case yk::CLS_W8: yk::launch_sweep_group<64, 8>(sa, set.n[cls], e->stream); break;
+            default: yk::launch_sweep_group<64, 16>(sa, set.n[cls], e->stream); break;
             }
         }
-        for (int cls = yk::CLS_R2; cls <= yk::CLS_W16; cls++) { // register sort per lane group
-            if (!set.n[cls] || (fuse && cls <= yk::CLS_H16)) continue;
-            HIP_TRY(before_class(cls));
-            sa.list = list_of(cls);
-            sa.list_n = &ctr->n[cls];
-            sa.first = set.first[cls];
-            if (e->flags & YACRD_F_FORCE_LDS_SORT) {
-                const u32 grid = (u32)std::min<uint64_t>(set.n[cls], (uint64_t)e->num_cu * 32);
-                hipLaunchKernelGGL((yk::sweep_lds_kernel<64, (int)yk::kSmallEvents>), dim3(grid),
-                                   dim3(64), 0, e->stream, sa);
-            } else {
-                switch (cls) {
-                case yk::CLS_R2: yk::launch_sweep_group<16, 2>(sa, set.n[cls], e->stream, xm); break;
-                case yk::CLS_R4: yk::launch_sweep_group<16, 4>(sa, set.n[cls], e->stream, xm); break;
-                case yk::CLS_R8: yk::launch_sweep_group<16, 8>(sa, set.n[cls], e->stream, xm); break;
-                case yk::CLS_R16: yk::launch_sweep_group<16, 16>(sa, set.n[cls], e->stream, xm); break;
-                case yk::CLS_H16: yk::launch_sweep_group<32, 16>(sa, set.n[cls], e->stream, xm); break;
-                case yk::CLS_W2: yk::launch_sweep_group<64, 2>(sa, set.n[cls], e->stream, xm); break;
-                case yk::CLS_W4: yk::launch_sweep_group<64, 4>(sa, set.n[cls], e->stream, xm); break;
-                case yk::CLS_W8: yk::launch_sweep_group<64, 8>(sa, set.n[cls], e->stream, xm); break;
-                default: yk::launch_sweep_group<64, 16>(sa, set.n[cls], e->stream, xm); break;
-                }
-            }
-            HIP_TRY(mark_class(cls));
-        }
-        sa.first = 0;
-        if (full && timing_on) HIP_TRY(hipEventRecord(e->ev[EV_SMALL], e->stream));
+        HIP_TRY(mark_class(e, R, cls));
+    }
+    if (R.full && R.timing_on) HIP_TRY(hipEventRecord(e->ev[EV_SMALL], e->stream));
+    return YACRD_OK;
+}
 
-        // One read per workgroup.  First the healthy-read screen (screen_wg.h: the read in registers, one pass,
-        // closed form); what it cannot finish lands in a fallback list for the trimming filter + LDS sort.
-        for (int k = 0; k < 2; k++) {
-            const int cls = k == 0 ? yk::CLS_MED1 : yk::CLS_MED2;
-            if (!set.n[cls]) continue;
-            HIP_TRY(before_class(cls));
-            sa.list = list_of(cls);
-            sa.list_n = &ctr->n[cls];
-            if (sa.prefilter && !(e->flags & YACRD_F_NO_FUSED_SCREEN) && !e->fused_off && e->screen_fused_wgs_per_cu > 0) {
-                if (again) { // (a second pass over the class: the lists start over)
-                    HIP_TRY(hipMemsetAsync(&ctr->fb_stream[k], 0, sizeof(u32), e->stream));
-                    HIP_TRY(hipMemsetAsync(&ctr->fb_med[k], 0, sizeof(u32), e->stream));
-                }
-                // Two launches (round 6, profiles/r06/m_*): the SCREEN alone — screen_wg_kernel: 100 VGPRs, 8 KB of LDS, no scratch,
-                // one read per workgroup handed out by the dispatcher: 0.118-0.128 ms on configs[3] — appends what it cannot
-                // decide (a fiftieth of the generator's reads) to a list, and screen_wg_fused_kernel takes THAT list: table again,
-                // filtered exact sweep, the whole-read sort for what is left.  With the fallback code inside the screening
-                // launch the same screens took 0.163 ms before a single fallback read ran (128 VGPRs, 88 bytes of scratch
-                // written by every workgroup, 74 KB of LDS), and 0.212 with them.
-                // YACRD_F_STREAM_SCREEN (A/B): the first launch is the one-wavefront-per-read screen (screen_stream.h).
-                const bool stream_first = (e->flags & YACRD_F_STREAM_SCREEN) != 0;
-                {
-                    yk::SweepArgs ss = sa;
-                    ss.over_list = fb_stream[k];
-                    ss.over_count = &ctr->fb_stream[k];
-                    const u32 want = std::max<u32>(set.hint[cls], 1u);
-                    if (stream_first) {
-                        hipLaunchKernelGGL(yk::screen_stream_kernel, dim3((u32)std::min<uint64_t>(want, (uint64_t)e->num_cu * 96)), dim3(64), 0, e->stream, ss);
-                    } else {
-                        static const uint64_t wgk_grid = [] { const char *ev = std::getenv("YACRD_WGK_GRID"); return ev ? std::strtoull(ev, nullptr, 10) : (uint64_t)0; }(); // (A/B)
-                        const u32 gs1 = (u32)std::min<uint64_t>(want, wgk_grid ? wgk_grid : (uint64_t)e->num_cu * 64);
-                        ss.rec = e->mrec.as<uint4>() + (k == 0 ? 0u : mrec_cap1);
-                        hipLaunchKernelGGL(yk::screen_wg_kernel, dim3(gs1), dim3(yk::kWsT), 0, e->stream, ss);
-                    }
-                }
-                yk::ScreenFusedArgs fa;
-                fa.sweep = sa;
-                fa.sweep.list = fb_stream[k], fa.sweep.list_n = &ctr->fb_stream[k];
-                fa.sweep.over_list = over_med;
-                fa.sweep.over_count = &ctr->over_med;
-                fa.sweep.rej_list = k == 0 ? rej_med : rej_big;
-                fa.sweep.rej_count = k == 0 ? &ctr->rej_med : &ctr->rej_big;
-                fa.n_fallback = &ctr->fb_med[k];
-                // (its list is what the screen left: one read per workgroup, a stride loop should the list be longer than the grid.
-                //  YACRD_TEST_FUSED_GRID_MULT / YACRD_FUSED_SHARE, tests / A/B: a multiple of that grid, reads per workgroup and turn)
-                const u64 known = std::max<u32>(set.hint[cls], 1u);
-                u64 share = 1;
-                if (fused_share_override()) share = std::min<u64>(fused_share_override(), (u64)yk::kFusedShareMax);
-                fa.share = (u32)share;
-                const u32 gs = (u32)std::min<u64>(std::min<u64>((known + share - 1) / share, (u64)e->num_cu * 4) * fused_grid_mult(), 0x7FFFFFFFull);
-                hipLaunchKernelGGL(yk::screen_wg_fused_kernel, dim3(gs), dim3(yk::kWsT), 0, e->stream, fa);
-                if (k == 1) { // what does not fit the in-kernel fallback's 16 384 events even filtered (usually nothing)
-                    sa.list = over_med;
-                    sa.list_n = &ctr->over_med;
-                    sa.rej_list = rej_big;
-                    sa.rej_count = &ctr->rej_big;
-                    sa.over_list = over_med; // (cannot happen: 32 768 events hold every M2 read)
-                    sa.over_count = &ctr->over_med;
-                    const u32 grid = (u32)std::min<uint64_t>(set.n[cls], (uint64_t)e->num_cu);
-                    hipLaunchKernelGGL((yk::sweep_lds_kernel<1024, (int)yk::kMedium2Events>), dim3(grid), dim3(1024), 0,
-                                       e->stream, sa);
-                }
-                HIP_TRY(mark_class(cls));
-                continue;
-            }
-            if (sa.prefilter) {
-                if (again) HIP_TRY(hipMemsetAsync(&ctr->fb_med[k], 0, sizeof(u32), e->stream)); // (its entries are done)
-                sa.over_list = fb_med[k];
-                sa.over_count = &ctr->fb_med[k];
-                static const uint64_t wgk_grid = [] { const char *ev = std::getenv("YACRD_WGK_GRID"); return ev ? std::strtoull(ev, nullptr, 10) : (uint64_t)0; }(); // (A/B)
-                const u32 gs = (u32)std::min<uint64_t>(set.n[cls], wgk_grid ? wgk_grid : (uint64_t)e->num_cu * 4);
-                hipLaunchKernelGGL(yk::screen_wg_kernel, dim3(gs), dim3(yk::kWsT), 0, e->stream, sa);
-                sa.list = fb_med[k];
-                sa.list_n = &ctr->fb_med[k];
-            }
-            sa.rej_list = k == 0 ? rej_med : rej_big;
-            sa.rej_count = k == 0 ? &ctr->rej_med : &ctr->rej_big;
-            sa.over_list = over_med;
-            sa.over_count = &ctr->over_med;
-            if (k == 0) {
-                const u32 grid = (u32)std::min<uint64_t>(set.n[cls], (uint64_t)e->num_cu * 4);
-                hipLaunchKernelGGL((yk::sweep_lds_kernel<256, (int)yk::kMedium1Events>), dim3(grid), dim3(256), 0,
-                                   e->stream, sa);
-            } else {
-                if (sa.prefilter) {
-                    // first through the 256-thread kernel (five workgroups per CU): a read whose
-                    // filtered keys fit its 8192-key array is done there, the others land in over_med
-                    const u32 g256 = (u32)std::min<uint64_t>(set.n[cls], (uint64_t)e->num_cu * 5);
-                    hipLaunchKernelGGL((yk::sweep_lds_kernel<256, (int)yk::kMedium1Events>), dim3(g256), dim3(256), 0,
-                                       e->stream, sa);
-                    sa.list = over_med;
-                    sa.list_n = &ctr->over_med;
-                }
-                const u32 grid = (u32)std::min<uint64_t>(set.n[cls], (uint64_t)e->num_cu);
-                hipLaunchKernelGGL((yk::sweep_lds_kernel<1024, (int)yk::kMedium2Events>), dim3(grid), dim3(1024), 0,
-                                   e->stream, sa);
-            }
-            HIP_TRY(mark_class(cls));
+// A workgroup class (k = 0: M1, 1: M2), the screen and its fallback fused.  Two launches (round 6, profiles/r06/m_*): the
+// SCREEN alone — screen_wg_kernel: 100 VGPRs, 8 KB of LDS, no scratch, one read per workgroup handed out by the dispatcher:
+// 0.118-0.128 ms on configs[3] — appends what it cannot decide (a fiftieth of the generator's reads) to a list, and
+// screen_wg_fused_kernel takes THAT list: table again, filtered exact sweep, the whole-read sort for what is left.  With the
+// fallback code inside the screening launch the same screens took 0.163 ms before a single fallback read ran (128 VGPRs,
+// 88 bytes of scratch written by every workgroup, 74 KB of LDS), and 0.212 with them.
+// YACRD_F_STREAM_SCREEN (A/B): the first launch is the one-wavefront-per-read screen (screen_stream.h).
+int launch_workgroup_class_fused_screen(yacrd_engine *e, Run &R, const LaunchSet &set, int k, bool again)
+{
+    yk::Counters *ctr = R.ctr;
+    const int cls = k == 0 ? yk::CLS_MED1 : yk::CLS_MED2;
+    if (again) { // (a second pass over the class: the lists start over)
+        HIP_TRY(hipMemsetAsync(&ctr->fb_stream[k], 0, sizeof(u32), e->stream));
+        HIP_TRY(hipMemsetAsync(&ctr->fb_med[k], 0, sizeof(u32), e->stream));
+    }
+    {
+        yk::SweepArgs ss = list_sweep_args(R, R.list_of(cls), &ctr->n[cls]); // (rej_*: the base's, no screen rejects a read)
+        ss.over_list = R.fb_stream[k];
+        ss.over_count = &ctr->fb_stream[k];
+        const u32 want = std::max<u32>(set.hint[cls], 1u);
+        if (e->flags & YACRD_F_STREAM_SCREEN) {
+            hipLaunchKernelGGL(yk::screen_stream_kernel, dim3((u32)std::min<uint64_t>(want, (uint64_t)e->num_cu * 96)), dim3(64), 0, e->stream, ss);
+        } else {
+            ss.rec = e->mrec.as<uint4>() + (k == 0 ? 0u : R.mrec_cap1);
+            hipLaunchKernelGGL(yk::screen_wg_kernel, dim3((u32)std::min<uint64_t>(want, (uint64_t)e->num_cu * 64)), dim3(yk::kWsT), 0, e->stream, ss);
         }
-        if (full && timing_on) HIP_TRY(hipEventRecord(e->ev[EV_MED], e->stream));
+    }
+    yk::ScreenFusedArgs fa;
+    fa.sweep = list_sweep_args(R, R.fb_stream[k], &ctr->fb_stream[k]); // (over_*: over_med, the base's)
+    fa.sweep.rej_list = k == 0 ? R.rej_med : R.rej_big;
+    fa.sweep.rej_count = k == 0 ? &ctr->rej_med : &ctr->rej_big;
+    fa.n_fallback = &ctr->fb_med[k];
+    // (its list is what the screen left: one read per workgroup, a stride loop should the list be longer than the grid.
+    //  YACRD_TEST_FUSED_GRID_MULT / YACRD_FUSED_SHARE, tests / A/B: a multiple of that grid, reads per workgroup and turn)
+    const u64 known = std::max<u32>(set.hint[cls], 1u);
+    u64 share = 1;
+    if (fused_share_override()) share = std::min<u64>(fused_share_override(), (u64)yk::kFusedShareMax);
+    fa.share = (u32)share;
+    const u32 gs = (u32)std::min<u64>(std::min<u64>((known + share - 1) / share, (u64)e->num_cu * 4) * fused_grid_mult(), 0x7FFFFFFFull);
+    hipLaunchKernelGGL(yk::screen_wg_fused_kernel, dim3(gs), dim3(yk::kWsT), 0, e->stream, fa);
+    if (k == 1) { // what does not fit the in-kernel fallback's 16 384 events even filtered (usually nothing)
+        yk::SweepArgs so = list_sweep_args(R, R.over_med, &ctr->over_med); // (over_*: over_med again — cannot happen: 32 768 events hold every M2 read)
+        so.rej_list = R.rej_big;
+        so.rej_count = &ctr->rej_big;
+        const u32 grid = (u32)std::min<uint64_t>(set.n[cls], (uint64_t)e->num_cu);
+        hipLaunchKernelGGL((yk::sweep_lds_kernel<1024, (int)yk::kMedium2Events>), dim3(grid), dim3(1024), 0, e->stream, so);
+    }
+    return YACRD_OK;
+}
 
-        if (set.n[yk::CLS_MED1]) {
-            sa.list = rej_med;
-            sa.list_n = &ctr->rej_med;
-            sa.rej_list = rej_big;
-            sa.rej_count = &ctr->rej_big;
-            hipLaunchKernelGGL((yk::sweep_general_lds_kernel<1024, 4096>), dim3(e->num_cu),
-                               dim3(1024), 0, e->stream, sa);
-        }
+// A workgroup class down the chain of separate launches (round 3's; YACRD_F_NO_FUSED_SCREEN, YACRD_F_NO_PREFILTER, and the
+// re-run after a fused launch gave up): the screen, then the trimming filter + LDS sort over what it leaves.
+int launch_workgroup_class_chain(yacrd_engine *e, Run &R, const LaunchSet &set, int k, bool again)
+{
+    yk::Counters *ctr = R.ctr;
+    const int cls = k == 0 ? yk::CLS_MED1 : yk::CLS_MED2;
+    const u32 *list = R.list_of(cls), *list_n = &ctr->n[cls];
+    if (R.prefilter) {
+        if (again) HIP_TRY(hipMemsetAsync(&ctr->fb_med[k], 0, sizeof(u32), e->stream)); // (its entries are done)
+        yk::SweepArgs ss = list_sweep_args(R, list, list_n); // (rej_*: the base's, the screen rejects no read)
+        ss.over_list = R.fb_med[k];
+        ss.over_count = &ctr->fb_med[k];
+        const u32 gs = (u32)std::min<uint64_t>(set.n[cls], (uint64_t)e->num_cu * 4);
+        hipLaunchKernelGGL(yk::screen_wg_kernel, dim3(gs), dim3(yk::kWsT), 0, e->stream, ss);
+        list = R.fb_med[k], list_n = &ctr->fb_med[k];
+    }
+    yk::SweepArgs sa = list_sweep_args(R, list, list_n); // (over_*: over_med, the base's)
+    sa.rej_list = k == 0 ? R.rej_med : R.rej_big;
+    sa.rej_count = k == 0 ? &ctr->rej_med : &ctr->rej_big;
+    if (k == 0) {
+        const u32 grid = (u32)std::min<uint64_t>(set.n[cls], (uint64_t)e->num_cu * 4);
+        hipLaunchKernelGGL((yk::sweep_lds_kernel<256, (int)yk::kMedium1Events>), dim3(grid), dim3(256), 0, e->stream, sa);
         return YACRD_OK;
-    };
-    // Reads beyond the LDS classes (the host knows their number and their intervals: batches that hold such
-    // reads are never predicted).  The device-wide healthy-read screen (screen_big.h) first; what it cannot
-    // decide lands in fb_big and takes the trimming filter / the segmented sort after the final sync.
-    // YACRD_F_FORCE_GENERAL / YACRD_F_NO_PREFILTER: the host-driven paths directly.
-    bool big_screened = false;
-    auto launch_huge = [&](u32 count, u64 iv_big, u64 *iv_total, hipStream_t hs) -> int {
-        if (e->flags & YACRD_F_FORCE_GENERAL)
-            return run_general_global(e, d_off, d_iv, d_len, list_of(yk::CLS_GENERAL), count, cov, e->stream, iv_total);
-        if (!sa.prefilter)
-            return run_big(e, d_off, d_iv, d_len, list_of(yk::CLS_GENERAL), count, cov, e->stream, iv_total);
-        if (iv_total) *iv_total = iv_big;
-        const u64 max_chunks = iv_big / yk::kBsChunk + count;
-        if (max_chunks >= 0x7FFFFFFFull) return fail(YACRD_EINVAL, "too many intervals in reads beyond 16384");
-        HIP_TRY(e->bs_seg.reserve((size_t)count * sizeof(yk::BsSeg)));
-        HIP_TRY(e->bs_chunk.reserve((size_t)max_chunks * sizeof(u32)));
-        HIP_TRY(e->bs_hist.reserve((size_t)count * 2 * yk::kBsBins * sizeof(u32)));
-        yk::BsArgs ba;
-        ba.off = d_off, ba.iv = d_iv, ba.len = d_len;
-        ba.list = list_of(yk::CLS_GENERAL);
-        ba.list_n = &ctr->n[yk::CLS_GENERAL];
-        ba.seg = e->bs_seg.as<yk::BsSeg>();
-        ba.chunk_seg = e->bs_chunk.as<u32>();
-        ba.n_chunks = &ctr->bs_chunks;
-        ba.hist = e->bs_hist.as<u32>();
-        ba.max_chunks = (u32)max_chunks, ba.max_segs = count;
-        ba.cov = cov, ba.count_healthy = sa.prefilter == 2 ? 1u : 0u;
-        ba.stage = sa.stage, ba.counts = sa.counts;
-        ba.fb_list = fb_big, ba.fb_count = &ctr->fb_big;
-        ba.ctr = ctr;
-        if (big_screened) HIP_TRY(hipMemsetAsync(&ctr->fb_big, 0, sizeof(u32), hs)); // (a second pass: its entries are done)
-        HIP_TRY(hipMemsetAsync(ba.hist, 0, (size_t)count * 2 * yk::kBsBins * sizeof(u32), hs));
-        hipLaunchKernelGGL(yk::bs_setup_kernel, dim3(1), dim3(1024), 0, hs, ba);
-        hipLaunchKernelGGL(yk::bs_minmax_kernel, dim3((u32)max_chunks), dim3(yk::kBsT), 0, hs, ba);
-        hipLaunchKernelGGL(yk::bs_hist_kernel, dim3((u32)max_chunks), dim3(yk::kBsT), 0, hs, ba);
-        hipLaunchKernelGGL(yk::bs_verdict_kernel, dim3(count), dim3(yk::kBsVT), 0, hs, ba);
-        big_screened = true;
-        return YACRD_OK;
-    };
+    }
+    yk::SweepArgs so = sa; // the 1024-thread kernel's: the class as it stands, or what the 256-thread kernel leaves
+    if (R.prefilter) {
+        // first through the 256-thread kernel (five workgroups per CU): a read whose
+        // filtered keys fit its 8192-key array is done there, the others land in over_med
+        const u32 g256 = (u32)std::min<uint64_t>(set.n[cls], (uint64_t)e->num_cu * 5);
+        hipLaunchKernelGGL((yk::sweep_lds_kernel<256, (int)yk::kMedium1Events>), dim3(g256), dim3(256), 0, e->stream, sa);
+        so.list = R.over_med;
+        so.list_n = &ctr->over_med;
+    }
+    const u32 grid = (u32)std::min<uint64_t>(set.n[cls], (uint64_t)e->num_cu);
+    hipLaunchKernelGGL((yk::sweep_lds_kernel<1024, (int)yk::kMedium2Events>), dim3(grid), dim3(1024), 0, e->stream, so);
+    return YACRD_OK;
+}
 
-    for (int cls = 0; cls < yk::CLS_GENERAL; cls++)
-        if (ls.n[cls] && (dom_cls < 0 || ls.iv[cls] > ls.iv[dom_cls])) dom_cls = cls;
-    if (full) HIP_TRY(hipEventRecord(e->ev[EV_S0], e->stream));
-    // The device-wide screen's four short launches (a dozen microseconds each, dependent, a few hundred workgroups) go out on a
-    // stream of their own BESIDE the other classes' sweeps (round 6): behind them, as until round 5, they were 45 us of
-    // configs[3]'s 0.31 ms with the device mostly idle.  Fork behind the plan, join in front of the follow-on step.
-    int rc = YACRD_OK;
-    u64 gen_iv = 0;
-    const u32 huge_n = predicted ? pred_big_n : c0.n[yk::CLS_GENERAL];
-    const u64 huge_iv = predicted ? pred_big_iv : c0.iv[yk::CLS_GENERAL];
-    const bool huge_now = huge_n != 0;
-    if (huge_now && sa.prefilter && !(e->flags & YACRD_F_FORCE_GENERAL) && e->side == nullptr) {
+// One read per workgroup: M1 and M2.  First the healthy-read screen (screen_wg.h: the read in registers, one pass,
+// closed form); what it cannot finish lands in a fallback list for the trimming filter + LDS sort.
+int launch_workgroup_classes(yacrd_engine *e, Run &R, const LaunchSet &set, bool again)
+{
+    const bool fused_screen = R.prefilter && !(e->flags & YACRD_F_NO_FUSED_SCREEN) && !e->fused_off && e->screen_fused_wgs_per_cu > 0;
+    for (int k = 0; k < 2; k++) {
+        const int cls = k == 0 ? yk::CLS_MED1 : yk::CLS_MED2;
+        if (!set.n[cls]) continue;
+        HIP_TRY(before_class(e, R, cls));
+        const int rc = fused_screen ? launch_workgroup_class_fused_screen(e, R, set, k, again)
+                                    : launch_workgroup_class_chain(e, R, set, k, again);
+        if (rc) return rc;
+        HIP_TRY(mark_class(e, R, cls));
+    }
+    if (R.full && R.timing_on) HIP_TRY(hipEventRecord(e->ev[EV_MED], e->stream));
+    return YACRD_OK;
+}
+
+// What the M1 sweeps rejected (a degenerate interval): the exact path with its scratch in LDS.
+void launch_rejected_medium(yacrd_engine *e, Run &R, const LaunchSet &set)
+{
+    if (!set.n[yk::CLS_MED1]) return;
+    yk::SweepArgs sa = list_sweep_args(R, R.rej_med, &R.ctr->rej_med);
+    sa.rej_list = R.rej_big;
+    sa.rej_count = &R.ctr->rej_big;
+    hipLaunchKernelGGL((yk::sweep_general_lds_kernel<1024, 4096>), dim3(e->num_cu), dim3(1024), 0, e->stream, sa);
+}
+
+// sweeps of the classes in `set`
+int launch_sweeps(yacrd_engine *e, Run &R, const LaunchSet &set, bool again = false)
+{
+    int rc = launch_register_classes(e, R, set, again);
+    if (!rc) rc = launch_workgroup_classes(e, R, set, again);
+    if (!rc) launch_rejected_medium(e, R, set);
+    return rc;
+}
+
+// `count` reads beyond the LDS classes, `iv_big` intervals in all (the plan's counts, or the previous run's: a prediction the
+// final sync checks).  The device-wide healthy-read screen (screen_big.h) on stream `hs`; what it cannot decide lands in fb_big
+// and takes the trimming filter / the segmented sort after the final sync.
+// YACRD_F_FORCE_GENERAL / YACRD_F_NO_PREFILTER: the host-driven paths directly, on the engine's stream.
+int launch_device_wide_screen_on(yacrd_engine *e, Run &R, u32 count, u64 iv_big, hipStream_t hs)
+{
+    yk::Counters *ctr = R.ctr;
+    if (e->flags & YACRD_F_FORCE_GENERAL)
+        return run_general_global(e, R.d_off, R.d_iv, R.d_len, R.list_of(yk::CLS_GENERAL), count, R.cov, e->stream);
+    if (!R.prefilter)
+        return run_big(e, R.d_off, R.d_iv, R.d_len, R.list_of(yk::CLS_GENERAL), count, R.cov, e->stream);
+    const u64 max_chunks = iv_big / yk::kBsChunk + count;
+    if (max_chunks >= 0x7FFFFFFFull) return fail(YACRD_EINVAL, "too many intervals in reads beyond 16384");
+    HIP_TRY(e->bs_seg.reserve((size_t)count * sizeof(yk::BsSeg)));
+    HIP_TRY(e->bs_chunk.reserve((size_t)max_chunks * sizeof(u32)));
+    HIP_TRY(e->bs_hist.reserve((size_t)count * 2 * yk::kBsBins * sizeof(u32)));
+    yk::BsArgs ba;
+    ba.off = R.d_off, ba.iv = R.d_iv, ba.len = R.d_len;
+    ba.list = R.list_of(yk::CLS_GENERAL);
+    ba.list_n = &ctr->n[yk::CLS_GENERAL];
+    ba.seg = e->bs_seg.as<yk::BsSeg>();
+    ba.chunk_seg = e->bs_chunk.as<u32>();
+    ba.n_chunks = &ctr->bs_chunks;
+    ba.hist = e->bs_hist.as<u32>();
+    ba.max_chunks = (u32)max_chunks, ba.max_segs = count;
+    ba.cov = R.cov, ba.count_healthy = R.prefilter == 2 ? 1u : 0u;
+    ba.stage = R.base.stage, ba.counts = R.base.counts;
+    ba.fb_list = R.fb_big, ba.fb_count = &ctr->fb_big;
+    ba.ctr = ctr;
+    if (R.big_screened) HIP_TRY(hipMemsetAsync(&ctr->fb_big, 0, sizeof(u32), hs)); // (a second pass: its entries are done)
+    HIP_TRY(hipMemsetAsync(ba.hist, 0, (size_t)count * 2 * yk::kBsBins * sizeof(u32), hs));
+    hipLaunchKernelGGL(yk::bs_setup_kernel, dim3(1), dim3(1024), 0, hs, ba);
+    hipLaunchKernelGGL(yk::bs_minmax_kernel, dim3((u32)max_chunks), dim3(yk::kBsT), 0, hs, ba);
+    hipLaunchKernelGGL(yk::bs_hist_kernel, dim3((u32)max_chunks), dim3(yk::kBsT), 0, hs, ba);
+    hipLaunchKernelGGL(yk::bs_verdict_kernel, dim3(count), dim3(yk::kBsVT), 0, hs, ba);
+    R.big_screened = true;
+    return YACRD_OK;
+}
+// The device-wide screen's four short launches (a dozen microseconds each, dependent, a few hundred workgroups) go out on a
+// stream of their own BESIDE the other classes' sweeps (round 6): behind them, as until round 5, they were 45 us of
+// configs[3]'s 0.31 ms with the device mostly idle.  Fork behind the plan (launch_device_wide_screen, called in front of the
+// sweeps), join in front of the follow-on step (join_device_wide_screen, called behind them).
+int launch_device_wide_screen(yacrd_engine *e, Run &R)
+{
+    const bool can_fork = R.big_n != 0 && R.prefilter && !(e->flags & YACRD_F_FORCE_GENERAL);
+    if (can_fork && e->side == nullptr) {
         if (hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) != hipSuccess) {
             (void)hipGetLastError();
             e->side = nullptr; // (no side stream: the launches go out behind the other classes', as until round 5)
         }
     }
-    const bool huge_beside = huge_now && sa.prefilter && !(e->flags & YACRD_F_FORCE_GENERAL) && e->side != nullptr;
-    if (huge_beside) {
-        HIP_TRY(hipEventRecord(e->ev_fork, e->stream));
-        HIP_TRY(hipStreamWaitEvent(e->side, e->ev_fork, 0));
-        rc = launch_huge(huge_n, huge_iv, &gen_iv, e->side);
-        if (rc) return rc;
-        HIP_TRY(hipEventRecord(e->ev_join, e->side));
-    }
-    rc = launch_sweeps(ls);
+    R.big_beside = can_fork && e->side != nullptr;
+    if (!R.big_beside) return YACRD_OK;
+    HIP_TRY(hipEventRecord(e->ev_fork, e->stream));
+    HIP_TRY(hipStreamWaitEvent(e->side, e->ev_fork, 0));
+    const int rc = launch_device_wide_screen_on(e, R, R.big_n, R.big_iv, e->side);
     if (rc) return rc;
-    if (huge_now && !huge_beside) {
-        rc = launch_huge(huge_n, huge_iv, &gen_iv, e->stream);
-        if (rc) return rc;
-    }
-    if (huge_beside) HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_join, 0));
-    if (full) HIP_TRY(hipEventRecord(e->ev[EV_GEN], e->stream));
+    HIP_TRY(hipEventRecord(e->ev_join, e->side));
+    return YACRD_OK;
+}
+int join_device_wide_screen(yacrd_engine *e, Run &R)
+{
+    if (R.big_beside) HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_join, 0));
+    else if (R.big_n) return launch_device_wide_screen_on(e, R, R.big_n, R.big_iv, e->stream);
+    return YACRD_OK;
+}
 
-    // ---- follow-on kernel: scan + compact + classify
-    rc = launch_compact(e, sa, n_reads, not_cov, screened);
-    if (rc) return rc;
-    if (full) HIP_TRY(hipEventRecord(e->ev[EV_COMPACT], e->stream));
-    if (defer && predicted) { // yacrd_engine_submit_device: the caller waits later (finish_pending)
-        Pending &p = e->pending;
-        p.active = true;
-        p.d_off = d_off;
-        p.d_iv = d_iv;
-        p.d_len = d_len;
-        p.n_reads = n_reads64;
-        p.n_iv = n_iv;
-        p.cov = cov;
-        p.not_cov = not_cov;
-        for (int cls = 0; cls < 12; cls++) {
-            p.grid_n[cls] = cls < yk::CLS_GENERAL ? ls.n[cls] : 0;
-            p.cls_b[cls] = cls_b[cls];
-            p.cls_e[cls] = cls_e[cls];
-        }
-        p.fused_marked = fused_marked;
-        p.screened = screened;
-        p.big_n = pred_big_n, p.big_iv = pred_big_iv;
-        return YACRD_OK;
-    }
-    // (spinning on the pinned counter block instead of this call was tried: 0.0816 vs 0.078 ms/step)
-    rc = wait_for_stream(e);
-    if (rc) return rc;
-    timing_on = false;
-    if (e->h_ctr->fused_gave_up && !e->fused_off) return rerun_without_fused(e, d_off, d_iv, d_len, n_reads64, n_iv, cov, not_cov);
+// Reads a register sweep (or the follow-on kernel's sort) rejected — an interval the keys cannot
+// express: the exact path with its scratch in LDS.  Rare, so nothing is launched for them before their number is known.
+void launch_rejected_small(yacrd_engine *e, Run &R)
+{
+    yk::SweepArgs sa = list_sweep_args(R, R.rej_small, &R.ctr->rej_small);
+    sa.rej_list = R.rej_med; // cannot happen (n <= 512), kept well defined
+    sa.rej_count = &R.ctr->rej_med;
+    // (a single wavefront per read was tried: 23.9 us vs 20.2 us — the stages are latency
+    // chains, more threads shorten each one)
+    hipLaunchKernelGGL((yk::sweep_general_lds_kernel<256, 512>), dim3(e->num_cu * 2), dim3(256), 0, e->stream, sa);
+}
 
-    // ---- rare slow paths: a class the prediction missed; degenerate reads too large for the
-    // LDS exact path; region overflow.  Each ends with a redo of the compaction.
-    float extra_ms = 0.f;
+// Everything after the final sync, the rare slow paths: a class the prediction missed; degenerate reads too large for the
+// LDS exact path; what the device-wide screen left; region overflow.  Each ends with a redo of the compaction (its time: extra_ms).
+int recover(yacrd_engine *e, Run &R, float &extra_ms)
+{
+    yk::Counters *ctr = R.ctr;
+    int rc = YACRD_OK;
     bool redo = false;
-    if (predicted) {
-        c0 = *e->h_ctr; // the plan's real counts
+    if (R.predicted) {
+        R.c0 = *e->h_ctr; // the plan's real counts
+        const yk::Counters &c0 = R.c0;
         LaunchSet missing{};
         bool any_missing = false;
         for (int cls = 0; cls < yk::CLS_GENERAL; cls++)
-            if (c0.n[cls] > ls.n[cls]) { // class not predicted, or larger than its grid
-                missing.first[cls] = (cls <= yk::CLS_W16 && tight_grids) ? ls.n[cls] : 0;
+            if (c0.n[cls] > R.ls.n[cls]) { // class not predicted, or larger than its grid
+                missing.first[cls] = (cls <= yk::CLS_W16 && R.tight_grids) ? R.ls.n[cls] : 0;
                 missing.n[cls] = c0.n[cls] - missing.first[cls];
                 missing.hint[cls] = missing.n[cls];
                 any_missing = true;
             }
-        const bool big_mismatch = c0.n[yk::CLS_GENERAL] != pred_big_n || c0.iv[yk::CLS_GENERAL] != pred_big_iv;
+        const bool big_mismatch = c0.n[yk::CLS_GENERAL] != R.big_n || c0.iv[yk::CLS_GENERAL] != R.big_iv;
         if (any_missing || big_mismatch) {
             e->miss_pending = true; // (the prediction did not hold: yacrd_timing.prediction_misses)
-            if (!redo) HIP_TRY(hipEventRecord(e->ev[EV_X0], e->stream));
-            if (any_missing && (rc = launch_sweeps(missing, true))) return rc;
-            if (big_mismatch && c0.n[yk::CLS_GENERAL] && (rc = launch_huge(c0.n[yk::CLS_GENERAL], c0.iv[yk::CLS_GENERAL], &gen_iv, e->stream))) return rc;
+            HIP_TRY(hipEventRecord(e->ev[EV_X0], e->stream));
+            if (any_missing && (rc = launch_sweeps(e, R, missing, true))) return rc;
+            if (big_mismatch && c0.n[yk::CLS_GENERAL] &&
+                (rc = launch_device_wide_screen_on(e, R, c0.n[yk::CLS_GENERAL], c0.iv[yk::CLS_GENERAL], e->stream))) return rc;
             // the rejection counters may have grown: bring them home before looking at rej_big
-            HIP_TRY(hipMemcpyAsync(e->h_ctr, ctr, sizeof(yk::Counters), hipMemcpyDeviceToHost,
-                                   e->stream));
+            HIP_TRY(hipMemcpyAsync(e->h_ctr, ctr, sizeof(yk::Counters), hipMemcpyDeviceToHost, e->stream));
             HIP_TRY(hipStreamSynchronize(e->stream));
             redo = true;
         }
     }
-    // Reads a register sweep (or the follow-on kernel's sort) rejected — an interval the keys cannot
-    // express: the exact path with its scratch in LDS, then the compaction once more.  Rare, so nothing is
-    // launched for them before their number is known.  (A redo may reject more: the loop below looks again.)
-    auto exact_small = [&]() {
-        sa.list = rej_small;
-        sa.list_n = &ctr->rej_small;
-        sa.rej_list = rej_med; // cannot happen (n <= 512), kept well defined
-        sa.rej_count = &ctr->rej_med;
-        // (a single wavefront per read was tried: 23.9 us vs 20.2 us — the stages are latency
-        // chains, more threads shorten each one)
-        hipLaunchKernelGGL((yk::sweep_general_lds_kernel<256, 512>), dim3(e->num_cu * 2), dim3(256), 0,
-                           e->stream, sa);
-    };
+    // (A redo of the follow-on kernel may reject more reads: the loop below looks again.)
     u32 rej_small_done = 0;
     if (e->h_ctr->rej_small) {
         if (!redo) HIP_TRY(hipEventRecord(e->ev[EV_X0], e->stream));
-        exact_small();
+        launch_rejected_small(e, R);
         rej_small_done = e->h_ctr->rej_small;
         redo = true;
     }
-    if (big_screened && e->h_ctr->fb_big) { // BIG reads the screen could not decide: trimming filter / segmented sort
+    if (R.big_screened && e->h_ctr->fb_big) { // BIG reads the screen could not decide: trimming filter / segmented sort
         if (!redo) HIP_TRY(hipEventRecord(e->ev[EV_X0], e->stream));
-        rc = run_big(e, d_off, d_iv, d_len, fb_big, e->h_ctr->fb_big, cov, e->stream, nullptr);
+        rc = run_big(e, R.d_off, R.d_iv, R.d_len, R.fb_big, e->h_ctr->fb_big, R.cov, e->stream);
         if (rc) return rc;
         // (its rejections — a degenerate interval in a huge read — went the exact way inside run_big; the other
         // rejection counters may have grown)
@@ -1004,14 +890,14 @@ int run_on_device(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u3
     const u32 n_rej_big = e->h_ctr->rej_big;
     if (n_rej_big) {
         if (!redo) HIP_TRY(hipEventRecord(e->ev[EV_X0], e->stream));
-        rc = run_general_global(e, d_off, d_iv, d_len, rej_big, n_rej_big, cov, e->stream, nullptr);
+        rc = run_general_global(e, R.d_off, R.d_iv, R.d_len, R.rej_big, n_rej_big, R.cov, e->stream);
         if (rc) return rc;
         redo = true;
     }
     for (int attempt = 0; attempt < 4; attempt++) {
         if (!redo && e->h_ctr->rej_small > rej_small_done) { // the redone follow-on kernel rejected reads of its own
             HIP_TRY(hipEventRecord(e->ev[EV_X0], e->stream));
-            exact_small();
+            launch_rejected_small(e, R);
             rej_small_done = e->h_ctr->rej_small;
             redo = true;
         }
@@ -1023,8 +909,8 @@ int run_on_device(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u3
         redo = false;
         // reset the scan state, the ticket and the overflow flag (keep the class counters)
         HIP_TRY(hipMemsetAsync(&ctr->region_overflow, 0, 3 * sizeof(u32), e->stream));
-        HIP_TRY(hipMemsetAsync(ctr + 1, 0, (size_t)nb * sizeof(u64), e->stream));
-        rc = launch_compact(e, sa, n_reads, not_cov, screened);
+        HIP_TRY(hipMemsetAsync(ctr + 1, 0, (size_t)R.nb * sizeof(u64), e->stream));
+        rc = launch_compact(e, R);
         if (rc) return rc;
         HIP_TRY(hipEventRecord(e->ev[EV_X1], e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
@@ -1033,27 +919,154 @@ int run_on_device(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u3
     }
     if (e->h_ctr->region_overflow) return fail(YACRD_EINTERNAL, "bad_regions overflow persisted");
     if (e->h_ctr->rej_small > rej_small_done) return fail(YACRD_EINTERNAL, "rejected reads persisted");
+    return YACRD_OK;
+}
 
-    return conclude_run(e, c0, predicted, n_reads64, n_iv, cls_b, cls_e, fused_marked, screened, extra_ms);
+} // namespace
+
+namespace yke {
+// A workgroup of the fused workgroup screen ran out of looks at its queue slot (screen_wg.h: the grid was not resident as a
+// whole): whatever the batch's kernels wrote is void — the batch from the start, the workgroup classes down the three-launch chain.
+static int rerun_without_fused(yacrd_engine *e, const Run R) // (a copy: the re-run may reuse e->pending)
+{
+    e->fused_off = true;
+    e->pred_valid = false;
+    const int rc = run_on_device(e, R.d_off, R.d_iv, R.d_len, R.n_reads64, R.n_iv, R.cov, R.not_cov, false);
+    e->fused_off = false;
+    return rc;
+}
+
+// The batch is out, its final wait and conclusion are finish_pending's: now, or when the caller comes back for it (`defer`).
+// (The one place that fills e->pending.)
+static int hand_over(yacrd_engine *e, const Run &R, bool defer)
+{
+    e->pending = Pending{true, R.one_launch, R};
+    return defer ? YACRD_OK : finish_pending(e);
+}
+
+// Launch sequence per run: see the head of this file.  `defer` (yacrd_engine_submit_device): return without the final wait
+// where the batch allows it; finish_pending has the rest.
+int run_on_device(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u32 *d_len,
+                  uint64_t n_reads64, uint64_t n_iv, uint32_t cov, double not_cov, bool defer)
+{
+    if (n_reads64 >= 0xFFFFFFFFull) return fail(YACRD_EINVAL, "n_reads must be < 2^32 - 1");
+    if (e->pending.active) return fail(YACRD_EINVAL, "a submitted batch is pending: yacrd_engine_wait first");
+    e->has_result = false;
+    e->timing = yacrd_timing{};
+
+    HIP_TRY(e->bad_offsets.reserve((n_reads64 + 1) * sizeof(u64)));
+    if (n_reads64 == 0) {
+        HIP_TRY(hipMemsetAsync(e->bad_offsets.p, 0, sizeof(u64), e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        e->last_reads = 0;
+        e->last_regions = 0;
+        e->has_result = true;
+        return YACRD_OK;
+    }
+
+    Run R;
+    R.d_off = d_off, R.d_iv = d_iv, R.d_len = d_len;
+    R.n_reads64 = n_reads64, R.n_reads = (u32)n_reads64, R.n_iv = n_iv, R.cov = cov, R.not_cov = not_cov;
+    R.full = (e->flags & YACRD_F_TIMING_FULL) != 0;
+    R.tight_grids = !(e->flags & YACRD_F_FORCE_LDS_SORT);
+    R.prefilter = (e->flags & YACRD_F_NO_PREFILTER) ? 0u : (e->flags & YACRD_F_COUNT_PREFILTERED) ? 2u : 1u;
+    for (int i = 0; i < 12; i++) R.cls_b[i] = R.cls_e[i] = -1;
+    // YACRD_F_ONE_LAUNCH: a short batch as one kernel (one_batch.h) — unless a debug flag pins another path
+    // — and only where its look-back's progress argument holds (one_batch.h, ADVICE r4): the slabs at the front of an XCD's
+    // contiguous eighth wait for the XCD before it, so up to 7/8 of the slab-finishing wavefronts sit in wave slots for
+    // most of the launch; that needs the 8-XCD part and far more resident slots than waiters.  The cap on the reads is
+    // the kernel's own (32-bit deferred-interval sum), not the follow-on step's A/B knob.
+    const uint64_t ob_waiters = (n_reads64 + yk::kObSlab - 1) / yk::kObSlab * 7 / 8;
+    R.one_launch = (e->flags & YACRD_F_ONE_LAUNCH) && !e->one_launch_off && n_reads64 < (uint64_t)yk::kObMaxReads &&
+                   e->num_xcc == 8 && 2 * ob_waiters <= (uint64_t)e->num_cu * 4 * YK_OB_OCC &&
+                   !(e->flags & (YACRD_F_FORCE_GENERAL | YACRD_F_WAVE_ONLY | YACRD_F_FORCE_LDS_SORT | YACRD_F_NO_HALVES |
+                                 YACRD_F_NO_PREFILTER | YACRD_F_NO_DEFER));
+
+    int rc = reserve_buffers(e, R);
+    if (rc) return rc;
+    if (R.full) HIP_TRY(hipEventRecord(e->ev[EV_START], e->stream));
+    if (R.one_launch) {
+        rc = launch_one_batch(e, R);
+        return rc ? rc : hand_over(e, R, defer);
+    }
+    rc = launch_plan(e, R);
+    if (!rc) rc = size_launches(e, R);
+    if (rc) return rc;
+    R.timing_on = !(e->flags & YACRD_F_NO_TIMING);
+    if ((e->flags & YACRD_F_TIMING_SAMPLED) && !R.full && (e->run_seq++ % 8u) != 0) R.timing_on = false;
+    struct MissGuard { // (a miss found by THIS call is reported by its conclude_run and forgotten when the call returns)
+        yacrd_engine *e;
+        bool before;
+        ~MissGuard() { e->miss_pending = before; }
+    } miss_guard{e, e->miss_pending};
+    e->prev_build = e->last_build;
+    e->last_build = -1;
+    if (R.full) HIP_TRY(hipEventRecord(e->ev[EV_S0], e->stream));
+    rc = launch_device_wide_screen(e, R);
+    if (!rc) rc = launch_sweeps(e, R, R.ls);
+    if (!rc) rc = join_device_wide_screen(e, R);
+    if (rc) return rc;
+    if (R.full) HIP_TRY(hipEventRecord(e->ev[EV_GEN], e->stream));
+    rc = launch_compact(e, R); // the follow-on step: scan + compact + classify
+    if (rc) return rc;
+    if (R.full) HIP_TRY(hipEventRecord(e->ev[EV_COMPACT], e->stream));
+    if (defer && R.predicted) return hand_over(e, R, defer); // yacrd_engine_submit_device: the caller waits later
+    // (spinning on the pinned counter block instead of this call was tried: 0.0816 vs 0.078 ms/step)
+    rc = wait_for_stream(e);
+    if (rc) return rc;
+    R.timing_on = false;
+    if (e->h_ctr->fused_gave_up && !e->fused_off) return rerun_without_fused(e, R);
+    float extra_ms = 0.f;
+    rc = recover(e, R, extra_ms);
+    if (rc) return rc;
+    return conclude_run(e, R, extra_ms);
 }
 } // namespace yke
 
 namespace {
 
-// Bookkeeping after a run's last sync: result sizes, the next run's prediction, timing.
-int conclude_run(yacrd_engine *e, yk::Counters c0, bool predicted, uint64_t n_reads64, uint64_t n_iv,
-                 const int *cls_b, const int *cls_e, bool fused_marked, bool screened, float extra_ms)
+// Folds the run's yacrd_timing (e->timing) into the running totals: millisecond fields and event counters add, count fields
+// follow the last run, h2d_ms / d2h_ms are kept (their callers add them: yacrd_engine_run, yacrd_engine_collect).
+void fold_timing(yacrd_engine *e)
 {
-    const bool full = (e->flags & YACRD_F_TIMING_FULL) != 0;
-    const u32 n_reads = (u32)n_reads64;
+    const yacrd_timing &t = e->timing;
+    yacrd_timing &ts = e->timing_sum;
+    const yacrd_timing keep = ts;
+    ts = t; // count fields follow the last run
+    ts.h2d_ms = keep.h2d_ms;
+    ts.d2h_ms = keep.d2h_ms;
+    ts.plan_ms = keep.plan_ms + t.plan_ms;
+    ts.sweep_small_ms = keep.sweep_small_ms + t.sweep_small_ms;
+    ts.sweep_medium_ms = keep.sweep_medium_ms + t.sweep_medium_ms;
+    ts.sweep_general_ms = keep.sweep_general_ms + t.sweep_general_ms;
+    ts.compact_ms = keep.compact_ms + t.compact_ms;
+    ts.total_ms = keep.total_ms + t.total_ms;
+    for (int i = 0; i < 12; i++) ts.class_ms[i] = keep.class_ms[i] + t.class_ms[i];
+    ts.fused_ms = keep.fused_ms + t.fused_ms;
+    ts.screened = keep.screened + t.screened;
+    ts.one_launch = keep.one_launch + t.one_launch;
+    ts.fused_reruns = keep.fused_reruns + t.fused_reruns;
+    ts.screen_wide = keep.screen_wide + t.screen_wide;
+    ts.predicted = keep.predicted + t.predicted;
+    ts.prediction_misses = keep.prediction_misses + t.prediction_misses;
+    ts.build_switches = keep.build_switches + t.build_switches;
+    ts.sorting_build = keep.sorting_build + t.sorting_build;
+    ts.timed_runs = keep.timed_runs + t.timed_runs;
+    e->timing_runs++;
+}
+
+// Bookkeeping after a run's last sync: result sizes, the next run's prediction, timing.
+int conclude_run(yacrd_engine *e, const Run &R, float extra_ms)
+{
+    const bool full = R.full, predicted = R.predicted, screened = R.screened;
     const yk::Counters c1 = *e->h_ctr;
-    if (predicted) c0 = c1; // class counts are final either way
-    e->last_reads = n_reads;
+    const yk::Counters c0 = predicted ? c1 : R.c0; // class counts are final either way
+    e->last_reads = R.n_reads;
     e->last_regions = c1.total_regions;
     e->has_result = true;
     e->pred = c1;
-    e->pred_reads = n_reads64;
-    e->pred_iv = n_iv;
+    e->pred_reads = R.n_reads64;
+    e->pred_iv = R.n_iv;
     e->pred_valid = true;
 
     yacrd_timing &t = e->timing;
@@ -1085,14 +1098,14 @@ int conclude_run(yacrd_engine *e, yk::Counters c0, bool predicted, uint64_t n_re
         t.class_reads[cls] = c0.n[cls];
         t.class_intervals[cls] = c0.iv[cls];
         t.class_ms[cls] = 0.f;
-        if (cls < yk::CLS_GENERAL && cls_b[cls] >= 0 && cls_e[cls] >= 0)
-            t.class_ms[cls] = ev_ms(e->ev_cls[cls_b[cls]], e->ev_cls[cls_e[cls]]);
+        if (cls < yk::CLS_GENERAL && R.cls_b[cls] >= 0 && R.cls_e[cls] >= 0)
+            t.class_ms[cls] = ev_ms(e->ev_cls[R.cls_b[cls]], e->ev_cls[R.cls_e[cls]]);
     }
     t.class_ms[yk::CLS_GENERAL] = (full && c0.n[yk::CLS_GENERAL]) ? t.sweep_general_ms : 0.f;
     t.fused_ms = 0.f;
-    t.timed_runs = fused_marked ? 1u : 0u;
+    t.timed_runs = R.fused_marked ? 1u : 0u;
     for (int cls = 0; cls < yk::CLS_GENERAL; cls++)
-        if (cls_b[cls] >= 0 && cls_e[cls] >= 0) t.timed_runs = 1u;
+        if (R.cls_b[cls] >= 0 && R.cls_e[cls] >= 0) t.timed_runs = 1u;
     t.deferred_reads = c1.deferred;
     t.deferred_intervals = c1.deferred_iv;
     // The next batch's build of the fused launch: when this one screened and more than a quarter of what it
@@ -1118,8 +1131,8 @@ int conclude_run(yacrd_engine *e, yk::Counters c0, bool predicted, uint64_t n_re
     t.sorting_build = e->last_build == 0 ? 1u : 0u;
     t.fused_reads = t.fused_intervals = 0;
     t.prefiltered_reads = c1.prefiltered;
-    if (fused_marked) t.fused_ms = ev_ms(e->ev_cls[22], e->ev_cls[23]);
-    if (!(e->flags & (YACRD_F_FORCE_LDS_SORT | YACRD_F_XLANE_DS | YACRD_F_NO_FUSED_LAUNCH))) {
+    if (R.fused_marked) t.fused_ms = ev_ms(e->ev_cls[22], e->ev_cls[23]);
+    if (!(e->flags & YACRD_F_FORCE_LDS_SORT)) {
         // what the one launch of the classes R2..H16 holds (whether or not this run timed it)
         for (int cls = yk::CLS_R2; cls <= yk::CLS_H16; cls++) {
             t.fused_reads += c0.n[cls];
@@ -1127,29 +1140,7 @@ int conclude_run(yacrd_engine *e, yk::Counters c0, bool predicted, uint64_t n_re
         }
     }
 
-    yacrd_timing &ts = e->timing_sum;
-    const yacrd_timing keep = ts;
-    ts = t; // count fields follow the last run
-    ts.h2d_ms = keep.h2d_ms;
-    ts.d2h_ms = keep.d2h_ms;
-    ts.plan_ms = keep.plan_ms + t.plan_ms;
-    ts.sweep_small_ms = keep.sweep_small_ms + t.sweep_small_ms;
-    ts.sweep_medium_ms = keep.sweep_medium_ms + t.sweep_medium_ms;
-    ts.sweep_general_ms = keep.sweep_general_ms + t.sweep_general_ms;
-    ts.compact_ms = keep.compact_ms + t.compact_ms;
-    ts.total_ms = keep.total_ms + t.total_ms;
-    for (int i = 0; i < 12; i++) ts.class_ms[i] = keep.class_ms[i] + t.class_ms[i];
-    ts.fused_ms = keep.fused_ms + t.fused_ms;
-    ts.screened = keep.screened + t.screened;
-    ts.one_launch = keep.one_launch;
-    ts.fused_reruns = keep.fused_reruns + t.fused_reruns;
-    ts.screen_wide = keep.screen_wide + t.screen_wide;
-    ts.predicted = keep.predicted + t.predicted;
-    ts.prediction_misses = keep.prediction_misses + t.prediction_misses;
-    ts.build_switches = keep.build_switches + t.build_switches;
-    ts.sorting_build = keep.sorting_build + t.sorting_build;
-    ts.timed_runs = keep.timed_runs + t.timed_runs;
-    e->timing_runs++;
+    fold_timing(e);
     return YACRD_OK;
 }
 
@@ -1162,56 +1153,44 @@ int finish_pending(yacrd_engine *e)
     Pending &p = e->pending;
     if (!p.active) return YACRD_OK;
     p.active = false;
+    const Run R = p.run; // (a copy: a batch that is run again may be handed over again)
     int rc = wait_for_stream(e);
     if (rc) return rc;
     if (p.one_launch) {
         // a read beyond 256 intervals, one the sort rejected (the exact path's) or more regions than bad_regions holds:
         // the default path has every redo — the batch takes it from the start
         const yk::Counters c1 = *e->h_ctr;
-        const u32 slabs = (u32)((p.n_reads + yk::kObSlab - 1) / yk::kObSlab);
-        if (c1.ob_unsupported || c1.rej_small || c1.region_overflow || c1.scan_ticket != slabs) {
+        if (c1.ob_unsupported || c1.rej_small || c1.region_overflow || c1.scan_ticket != R.ob_slabs) {
             if (c1.region_overflow) HIP_TRY(e->bad_regions.reserve((size_t)(c1.total_regions + 16) * sizeof(uint2)));
             e->one_launch_off = true;
-            rc = run_on_device(e, p.d_off, p.d_iv, p.d_len, p.n_reads, p.n_iv, p.cov, p.not_cov);
+            rc = run_on_device(e, R.d_off, R.d_iv, R.d_len, R.n_reads64, R.n_iv, R.cov, R.not_cov);
             e->one_launch_off = false;
             return rc;
         }
-        e->last_reads = p.n_reads;
+        e->last_reads = R.n_reads64;
         e->last_regions = c1.total_regions;
         e->has_result = true;
         yacrd_timing &t = e->timing;
         t = yacrd_timing{};
-        if (e->flags & YACRD_F_TIMING_FULL) t.total_ms = ev_ms(e->ev[EV_START], e->ev[EV_COMPACT]);
-        t.n_small = p.n_reads, t.iv_small = p.n_iv;
+        if (R.full) t.total_ms = ev_ms(e->ev[EV_START], e->ev[EV_COMPACT]);
+        t.n_small = R.n_reads64, t.iv_small = R.n_iv;
         t.deferred_reads = c1.deferred, t.deferred_intervals = c1.deferred_iv, t.prefiltered_reads = c1.prefiltered;
         t.screened = 1u, t.screen_items = (uint32_t)yk::kObItems, t.one_launch = 1u;
-        yacrd_timing &ts = e->timing_sum;
-        const yacrd_timing keep = ts;
-        ts = t;
-        ts.h2d_ms = keep.h2d_ms, ts.d2h_ms = keep.d2h_ms;
-        ts.plan_ms = keep.plan_ms, ts.sweep_small_ms = keep.sweep_small_ms, ts.sweep_medium_ms = keep.sweep_medium_ms;
-        ts.sweep_general_ms = keep.sweep_general_ms, ts.compact_ms = keep.compact_ms, ts.total_ms = keep.total_ms + t.total_ms;
-        for (int i = 0; i < 12; i++) ts.class_ms[i] = keep.class_ms[i];
-        ts.fused_ms = keep.fused_ms, ts.screened = keep.screened + 1u, ts.timed_runs = keep.timed_runs;
-        ts.one_launch = keep.one_launch + 1u;
-        ts.screen_wide = keep.screen_wide;
-        ts.fused_reruns = keep.fused_reruns, ts.predicted = keep.predicted, ts.prediction_misses = keep.prediction_misses;
-        ts.build_switches = keep.build_switches, ts.sorting_build = keep.sorting_build;
-        e->timing_runs++;
+        fold_timing(e);
         return YACRD_OK;
     }
     const yk::Counters c = *e->h_ctr;
-    if (c.fused_gave_up && !e->fused_off) return yke::rerun_without_fused(e, p.d_off, p.d_iv, p.d_len, p.n_reads, p.n_iv, p.cov, p.not_cov);
-    bool ok = !c.rej_small && c.n[yk::CLS_GENERAL] == p.big_n && c.iv[yk::CLS_GENERAL] == p.big_iv && !c.fb_big && !c.rej_big && !c.region_overflow;
-    for (int cls = 0; cls < yk::CLS_GENERAL; cls++) ok = ok && c.n[cls] <= p.grid_n[cls];
+    if (c.fused_gave_up && !e->fused_off) return yke::rerun_without_fused(e, R);
+    bool ok = !c.rej_small && c.n[yk::CLS_GENERAL] == R.big_n && c.iv[yk::CLS_GENERAL] == R.big_iv && !c.fb_big && !c.rej_big && !c.region_overflow;
+    for (int cls = 0; cls < yk::CLS_GENERAL; cls++) ok = ok && c.n[cls] <= R.ls.n[cls];
     if (!ok) {
         e->pred_valid = false;
         e->miss_pending = true; // (yacrd_timing.prediction_misses: the re-run's conclude_run reports it)
-        const int rcm = run_on_device(e, p.d_off, p.d_iv, p.d_len, p.n_reads, p.n_iv, p.cov, p.not_cov);
+        const int rcm = run_on_device(e, R.d_off, R.d_iv, R.d_len, R.n_reads64, R.n_iv, R.cov, R.not_cov);
         e->miss_pending = false;
         return rcm;
     }
-    return conclude_run(e, c, true, p.n_reads, p.n_iv, p.cls_b, p.cls_e, p.fused_marked, p.screened, 0.f);
+    return conclude_run(e, R, 0.f);
 }
 
 } // namespace
@@ -1324,9 +1303,6 @@ int fetch_result(yacrd_engine *e, yacrd_result *out)
 }
 } // namespace yke
 
-namespace {
-} // namespace
-
 extern "C" {
 
 int yacrd_abi_version(void) { return YACRD_ABI_VERSION; }
@@ -1389,12 +1365,6 @@ int yacrd_engine_create(const yacrd_engine_cfg *cfg, yacrd_engine **out)
         yacrd_engine_destroy(e);
         return fail(YACRD_ENODEV, std::string("engine setup: ") + hipGetErrorString(err));
     }
-    {
-        BigLane &lane = g_big_lane[dev & 63];
-        std::lock_guard<std::mutex> g(lane.mu);
-        lane.n_engines++;
-        e->in_lane = true;
-    }
     *out = e;
     return YACRD_OK;
 }
@@ -1405,15 +1375,6 @@ void yacrd_engine_destroy(yacrd_engine *e)
     DeviceGuard guard(e->device);
     e->pending.active = false;
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    if (e->in_lane) {
-        BigLane &lane = g_big_lane[e->device & 63];
-        std::lock_guard<std::mutex> g(lane.mu);
-        lane.n_engines--;
-        if (lane.owner == e) { // its event dies with it (its work is done: synchronized above)
-            lane.owner = nullptr;
-            lane.last = nullptr;
-        }
-    }
     DevBuf *bufs[] = {&e->in_off, &e->in_iv, &e->in_len, &e->lists, &e->ctrl2[0], &e->ctrl2[1], &e->stage,
                       &e->counts, &e->closed, &e->gen_sizes, &e->gen_scratch_off,
                       &e->gen_scratch, &e->big_tab, &e->big_keys, &e->big_redo, &e->bt_tab, &e->bt_hist, &e->bt_cur, &e->bt_keys, &e->bs_seg, &e->bs_chunk, &e->bs_hist,

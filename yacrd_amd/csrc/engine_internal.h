@@ -6,7 +6,6 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
-#include <mutex>
 #include <string>
 
 #include "device_common.h"
@@ -62,7 +61,6 @@ struct DevBuf {
 
 enum { EV_START = 0, EV_PLAN, EV_S0, EV_SMALL, EV_MED, EV_GEN, EV_COMPACT, EV_X0, EV_X1, EV_COUNT };
 
-
 struct DeviceGuard {
     int prev = -1;
     explicit DeviceGuard(int dev)
@@ -87,37 +85,68 @@ inline float ev_ms(hipEvent_t a, hipEvent_t b)
 } // namespace yke
 
 
-// One per device: whose dominant sweep went out last (see launch_sweeps).
-struct BigLane {
-    std::mutex mu;
-    hipEvent_t last = nullptr;
-    struct yacrd_engine *owner = nullptr;
-    int n_engines = 0;
-};
-static BigLane g_big_lane[64];
 // (Rounds 4-5 had a FusedLane here: the persistent screen + fallback launches of the engines that share a device took turns.
 // Since round 6 no workgroup of that launch waits for another — screen_wg.h — and engines launch it side by side.)
 
-// A batch that was submitted without waiting for it (yacrd_engine_submit_device).
-struct Pending {
-    bool active = false;
+// What one launch sequence covers, per size class.
+struct LaunchSet {
+    u32 n[12];     // reads used to size the grid; 0 = class not launched
+    u32 hint[12];  // the class's size as far as the host knows it (its count, or the prediction + a margin): grids of kernels that cover a list of any length
+    u32 first[12]; // first list entry the launch covers (remainder launches)
+    u64 iv[12];    // intervals (to pick the dominant class)
+};
+
+// One batch on its way through run_on_device (engine.hip): built once, handed to every phase of the launch sequence.
+struct Run {
+    // the batch
     const u64 *d_off = nullptr;
     const uint2 *d_iv = nullptr;
     const u32 *d_len = nullptr;
-    uint64_t n_reads = 0, n_iv = 0;
+    uint64_t n_reads64 = 0, n_iv = 0;
+    u32 n_reads = 0;
     uint32_t cov = 0;
     double not_cov = 0;
-    u32 grid_n[12] = {};      // reads each class's grid covers
-    u32 big_n = 0;            // reads / intervals beyond the workgroup classes the device-wide screen was launched for (a prediction)
+    // decoded flags
+    bool full = false;        // YACRD_F_TIMING_FULL
+    bool tight_grids = false; // predicted register classes get grids with a margin, not grids for every read
+    u32 prefilter = 0;        // SweepArgs.prefilter
+    bool one_launch = false;  // the batch goes out as one_batch_kernel (one_batch.h)
+    // the control block in use, its scan-state words, and what the plan zeroes of the other block
+    yk::Counters *ctr = nullptr;
+    u32 nb = 0, ob_slabs = 0;
+    size_t ctrl_bytes = 0, other_bytes = 0;
+    // lists of read ids, one stride of n_reads each: the classes, then ...
+    u32 *lists = nullptr;
+    u32 *rej_small = nullptr, *rej_med = nullptr, *rej_big = nullptr; // ... what the register / M1 / M2 and larger sweeps reject,
+    u32 *over_med = nullptr;                                          // M2 reads beyond the 256-thread kernel's keys,
+    u32 *fb_med[2] = {}, *fb_big = nullptr, *fb_stream[2] = {};       // what the screens leave of M1 / M2 / BIG, and the first of two screens of M1 / M2
+    u32 *list_of(int cls) const { return lists + (size_t)cls * n_reads; }
+    u32 mrec_cap1 = 0, mrec_cap2 = 0; // records of plan_kernel for M1 / M2 (plan_compact.h)
+    yk::SweepArgs base{};             // what every launch's SweepArgs start from (engine.hip: base_sweep_args)
+    // what is launched: the plan's counts (c0, after a sync) or the previous run's (predicted)
+    bool predicted = false;
+    yk::Counters c0{};
+    LaunchSet ls{};
+    u32 big_n = 0; // reads / intervals beyond the workgroup classes the device-wide screen is launched for
     u64 big_iv = 0;
-    bool fused_marked = false, screened = false;
-    bool one_launch = false;  // the batch went out as one_batch_kernel (one_batch.h)
-    int cls_b[12] = {}, cls_e[12] = {};
+    bool big_beside = false; // ... on the side stream
+    // kernel-level timing: event indices bracketing each class (-1 = not recorded)
+    int cls_b[12], cls_e[12];
+    int n_cls_ev = 0, dom_cls = -1;
+    bool timing_on = false;
+    // what went out
+    bool fused_marked = false, screened = false, big_screened = false;
+};
+
+// A batch that was submitted without waiting for it (yacrd_engine_submit_device, or the one-launch form before its wait).
+struct Pending {
+    bool active = false;
+    bool one_launch = false;
+    Run run;
 };
 
 struct yacrd_engine {
     Pending pending;
-    bool in_lane = false;
     int device = 0;
     uint32_t flags = 0;
     hipStream_t stream = nullptr;

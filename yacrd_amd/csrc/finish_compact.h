@@ -58,7 +58,7 @@ __device__ YK_FINISH_INLINE void finish_item(const u64 *off, const uint2 *iv, co
     fa.prefilter = 0, fa.stage = stage, fa.counts = counts, fa.rej_list = rej_list, fa.rej_count = rej_count;
     fa.over_list = nullptr, fa.over_count = nullptr, fa.ctr = ctr;
     const LaneConst lc = make_lane_const(lane_id());
-    sweep_group_read<64, K, 0, kFinishWaves>(iv + o, n, length, cov, true, rr, fa, lc);
+    sweep_group_read<64, K, kFinishWaves>(iv + o, n, length, cov, true, rr, fa, lc);
 }
 struct MarkedRead { // what the thread that found the mark already knows about the read (saves the sort one round trip)
     u64 o;

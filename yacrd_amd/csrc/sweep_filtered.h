@@ -118,7 +118,7 @@ __device__ __forceinline__ bool filtered_group_sweep(const SweepArgs &a, const u
             x[4 * q] = t.x, x[4 * q + 1] = t.y, x[4 * q + 2] = t.z, x[4 * q + 3] = t.w;
         }
     }
-    bitonic_sort<LANES, K, 2, 0>(x, lc);
+    bitonic_sort<LANES, K, 2>(x, lc);
 
     // ---- the sweep: depth in front of a key = the kept keys in front (starts - ends) + its block's correction
     i32 corr[K];

@@ -24,7 +24,7 @@ namespace yk {
 // are DPP / ds_swizzle exchanges (same primitives as sweep_wave.h).  Blocks that must come out
 // descending are complemented before and after, so every step below is ascending-only at the
 // block level; directions inside a block are compile-time (register bits) or lane constants.
-template <int M, int J, int XM>
+template <int M, int J>
 __device__ __forceinline__ void striped_step(u32 (&x)[16], const LaneConst &lc)
 {
     constexpr int K = 16, P = 64 * K;
@@ -46,22 +46,22 @@ __device__ __forceinline__ void striped_step(u32 (&x)[16], const LaneConst &lc)
         for (int r = 0; r < K; r++) {
             const bool desc_r = (M >= 64) && (M < P) && ((r & (M / 64)) != 0);
             const u32 sel = desc_r ? ~kj : (kj ^ dir_lane);
-            const u32 t = lane_xor<J, XM>(x[r], lc.addr32);
+            const u32 t = lane_xor<J>(x[r], lc.addr32);
             x[r] = umed3(x[r], t, sel);
         }
     }
 }
-template <int M, int J, int XM>
+template <int M, int J>
 __device__ __forceinline__ void striped_level(u32 (&x)[16], const LaneConst &lc)
 {
-    striped_step<M, J, XM>(x, lc);
-    if constexpr (J > 1) striped_level<M, J / 2, XM>(x, lc);
+    striped_step<M, J>(x, lc);
+    if constexpr (J > 1) striped_level<M, J / 2>(x, lc);
 }
-template <int M, int XM>
+template <int M>
 __device__ __forceinline__ void striped_sort(u32 (&x)[16], const LaneConst &lc)
 {
-    striped_level<M, M / 2, XM>(x, lc);
-    if constexpr (M < 1024) striped_sort<M * 2, XM>(x, lc);
+    striped_level<M, M / 2>(x, lc);
+    if constexpr (M < 1024) striped_sort<M * 2>(x, lc);
 }
 
 // Workgroup sort of P >= 1024 keys in LDS: 1024-key runs sorted in registers, then per level the
@@ -79,7 +79,7 @@ __device__ __forceinline__ void hybrid_sort_lds(u32 *keys, u32 P, const LaneCons
         u32 x[16];
 #pragma unroll
         for (int r = 0; r < 16; r++) x[r] = kb[r * 64] ^ flip;
-        striped_sort<2, 0>(x, lc);
+        striped_sort<2>(x, lc);
 #pragma unroll
         for (int r = 0; r < 16; r++) kb[r * 64] = x[r] ^ flip;
     }
@@ -103,7 +103,7 @@ __device__ __forceinline__ void hybrid_sort_lds(u32 *keys, u32 P, const LaneCons
             u32 x[16];
 #pragma unroll
             for (int r = 0; r < 16; r++) x[r] = kb[r * 64] ^ flip;
-            striped_level<1024, 512, 0>(x, lc);
+            striped_level<1024, 512>(x, lc);
 #pragma unroll
             for (int r = 0; r < 16; r++) kb[r * 64] = x[r] ^ flip;
         }

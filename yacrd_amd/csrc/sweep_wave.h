@@ -37,13 +37,13 @@ constexpr int DPP_ROW_SHR1 = 0x111, DPP_ROW_SHR2 = 0x112, DPP_ROW_SHR4 = 0x114,
               DPP_ROW_SHR8 = 0x118, DPP_WAVE_SHR1 = 0x138, DPP_BCAST15 = 0x142,
               DPP_BCAST31 = 0x143;
 
-// value of lane ^ D.  XM (cross-lane mode): 0 = DPP for xor 1/2/8, LDS crossbar for 4/16/32;
-// 1 = LDS crossbar (ds_swizzle / ds_bpermute) for every stride (fewest VALU instructions).
-template <int D, int XM>
+// value of lane ^ D: DPP for xor 1/2/8, LDS crossbar (ds_swizzle / ds_bpermute) for 4/16/32.
+// (The crossbar for every stride — fewest VALU instructions — was an A/B switch until round 6.)
+template <int D>
 __device__ __forceinline__ u32 lane_xor(u32 x, u32 bperm_addr32)
 {
     if constexpr (D == 32) return (u32)__builtin_amdgcn_ds_bpermute((int)bperm_addr32, (int)x);
-    else if constexpr (XM == 1 || D == 4 || D == 16)
+    else if constexpr (D == 4 || D == 16)
         return (u32)__builtin_amdgcn_ds_swizzle((int)x, (D << 10) | 0x1F);
     else if constexpr (D == 1) return (u32)__builtin_amdgcn_mov_dpp((int)x, DPP_XOR1, 0xF, 0xF, false);
     else if constexpr (D == 2) return (u32)__builtin_amdgcn_mov_dpp((int)x, DPP_XOR2, 0xF, 0xF, false);
@@ -120,7 +120,7 @@ constexpr int ilog2c(int v) { return v <= 1 ? 0 : 1 + ilog2c(v >> 1); }
 
 // ---- bitonic sort of LANES*K keys held as x[K] per lane, element index = lane_in_group*K + r --
 // LANES = 64: one sequence per wavefront; LANES = 16: four independent sequences, one per DPP row.
-template <int LANES, int K, int M, int J, int XM>
+template <int LANES, int K, int M, int J>
 __device__ __forceinline__ void bitonic_step(u32 (&x)[K], const LaneConst &lc)
 {
     constexpr int P = LANES * K;
@@ -131,7 +131,7 @@ __device__ __forceinline__ void bitonic_step(u32 (&x)[K], const LaneConst &lc)
         const u32 sel = lc.k[ilog2c(D)] ^ dirm; // ~0: this lane keeps the larger key
 #pragma unroll
         for (int r = 0; r < K; r++) {
-            const u32 t = lane_xor<D, XM>(x[r], lc.addr32);
+            const u32 t = lane_xor<D>(x[r], lc.addr32);
             x[r] = umed3(x[r], t, sel);
         }
     } else { // partner in another register of the same lane
@@ -154,17 +154,17 @@ __device__ __forceinline__ void bitonic_step(u32 (&x)[K], const LaneConst &lc)
         }
     }
 }
-template <int LANES, int K, int M, int J, int XM>
+template <int LANES, int K, int M, int J>
 __device__ __forceinline__ void bitonic_level(u32 (&x)[K], const LaneConst &lc)
 {
-    bitonic_step<LANES, K, M, J, XM>(x, lc);
-    if constexpr (J > 1) bitonic_level<LANES, K, M, J / 2, XM>(x, lc);
+    bitonic_step<LANES, K, M, J>(x, lc);
+    if constexpr (J > 1) bitonic_level<LANES, K, M, J / 2>(x, lc);
 }
-template <int LANES, int K, int M, int XM>
+template <int LANES, int K, int M>
 __device__ __forceinline__ void bitonic_sort(u32 (&x)[K], const LaneConst &lc)
 {
-    bitonic_level<LANES, K, M, M / 2, XM>(x, lc);
-    if constexpr (M < LANES * K) bitonic_sort<LANES, K, M * 2, XM>(x, lc);
+    bitonic_level<LANES, K, M, M / 2>(x, lc);
+    if constexpr (M < LANES * K) bitonic_sort<LANES, K, M * 2>(x, lc);
 }
 
 // ---- one read per group of LANES lanes, K keys per lane ------------------------------------
@@ -211,7 +211,7 @@ __device__ __forceinline__ u32 gscan_min(u32 v)
 // ---- everything after the event keys are in registers: sort, sweep, regions out ---------------
 // m = number of real keys of the group (the rest are pads); zl_check = the wavefront holds >= 2
 // zero-length intervals (duplicates must be looked for after the sort).
-template <int LANES, int K, int XM>
+template <int LANES, int K>
 __device__ __forceinline__ void sweep_group_keys(u32 (&x)[K], u32 m, u32 len, i32 c,
                                                  bool active, u32 r, u64 badmask, u64 zmask,
                                                  bool zl_check, const SweepArgs &a,
@@ -226,7 +226,7 @@ __device__ __forceinline__ void sweep_group_keys(u32 (&x)[K], u32 m, u32 len, i3
         return a.stage + (a.off[rr] + 2 * (u64)rr);
     };
 
-    bitonic_sort<LANES, K, 2, XM>(x, lc);
+    bitonic_sort<LANES, K, 2>(x, lc);
 
     // two zero-length intervals at one position cannot be expressed by the keys: after the sort
     // they are adjacent equal class-1 keys.  Only looked for when the wavefront saw >= 2 of them.
@@ -762,7 +762,7 @@ __device__ __forceinline__ bool prefilter(const u32 (&x)[K], u32 n, u32 len, i32
 }
 
 // ---- one read per group of LANES lanes: loads, keys, (pre-filter,) sweep ------------------------
-template <int LANES, int K, int XM, int WPB = 4>
+template <int LANES, int K, int WPB = 4>
 __device__ __forceinline__ void sweep_group_read(const uint2 *__restrict__ iv, u32 n, u32 len,
                                                  u32 cov, bool active, u32 r,
                                                  const SweepArgs &a, const LaneConst &lc)
@@ -828,13 +828,12 @@ __device__ __forceinline__ void sweep_group_read(const uint2 *__restrict__ iv, u
             u32 y[K / 2], mf;
             if (prefilter<LANES, K, WPB>(x, n, len, c, y, mf)) {
                 if (a.prefilter == 2 && lig == 0 && active) atomicAdd(&a.ctr->prefiltered, 1u);
-                sweep_group_keys<LANES, K / 2, XM>(y, mf, len, c, active, r, badmask, zmask,
-                                                   zl_check, a, lc);
+                sweep_group_keys<LANES, K / 2>(y, mf, len, c, active, r, badmask, zmask, zl_check, a, lc);
                 return;
             }
         }
     }
-    sweep_group_keys<LANES, K, XM>(x, 2 * n, len, c, active, r, badmask, zmask, zl_check, a, lc);
+    sweep_group_keys<LANES, K>(x, 2 * n, len, c, active, r, badmask, zmask, zl_check, a, lc);
 }
 
 // ---- the OTHER closed form: a read with one stretch of low coverage inside (round 4) ---------------------------------
@@ -1426,7 +1425,7 @@ __device__ __forceinline__ void screen_reads(const SweepArgs &a, const u32 (&r)[
 }
 
 // Body of one workgroup (four wavefronts, 4 * 64/LANES reads) of class (LANES, K).
-template <int LANES, int K, int XM, int WPB = 4>
+template <int LANES, int K, int WPB = 4>
 __device__ __forceinline__ void sweep_group_block(const SweepArgs &a, u32 block)
 {
     const u32 lane = lane_id();
@@ -1446,27 +1445,22 @@ __device__ __forceinline__ void sweep_group_block(const SweepArgs &a, u32 block)
         n = (u32)(a.off[r + 1] - o);
         len = a.len[r];
     }
-    sweep_group_read<LANES, K, XM, WPB>(a.iv + o, n, len, a.cov, active, r, a, lc);
+    sweep_group_read<LANES, K, WPB>(a.iv + o, n, len, a.cov, active, r, a, lc);
 }
 
 // One kernel per (LANES, K): small K keep small register footprints.
-template <int LANES, int K, int XM>
+template <int LANES, int K>
 __global__ __launch_bounds__(256) void sweep_group_kernel(SweepArgs a)
 {
-    sweep_group_block<LANES, K, XM>(a, blockIdx.x);
+    sweep_group_block<LANES, K>(a, blockIdx.x);
 }
 
 template <int LANES, int K>
-inline void launch_sweep_group(const SweepArgs &sa, u32 n_reads, hipStream_t stream, int xlane_mode)
+inline void launch_sweep_group(const SweepArgs &sa, u32 n_reads, hipStream_t stream)
 {
     constexpr u32 per_block = 4u * (64 / LANES); // reads per 256-thread workgroup
     const u32 grid = (n_reads + per_block - 1) / per_block;
-    if (xlane_mode == 1)
-        hipLaunchKernelGGL((sweep_group_kernel<LANES, K, 1>), dim3(grid ? grid : 1), dim3(256), 0,
-                           stream, sa);
-    else
-        hipLaunchKernelGGL((sweep_group_kernel<LANES, K, 0>), dim3(grid ? grid : 1), dim3(256), 0,
-                           stream, sa);
+    hipLaunchKernelGGL((sweep_group_kernel<LANES, K>), dim3(grid ? grid : 1), dim3(256), 0, stream, sa);
 }
 
 // ---- every register-sort class in ONE launch ------------------------------------------------
@@ -1517,16 +1511,16 @@ __device__ __forceinline__ void sweep_small_fused_body(const FusedArgs &f)
     a.first = f.first[e];
     const u32 b = g - first;
     switch (f.cls[e]) { // the one-read-per-wavefront classes stay separate kernels (registers)
-    case CLS_R2: sweep_group_block<16, 2, 0, WPB>(a, b); break;
-    case CLS_R4: sweep_group_block<16, 4, 0, WPB>(a, b); break;
-    case CLS_R8: sweep_group_block<16, 8, 0, WPB>(a, b); break;
+    case CLS_R2: sweep_group_block<16, 2, WPB>(a, b); break;
+    case CLS_R4: sweep_group_block<16, 4, WPB>(a, b); break;
+    case CLS_R8: sweep_group_block<16, 8, WPB>(a, b); break;
     case CLS_R16:
         if constexpr (DEFER) screen_block<16, ITEMS, WIDE>(a, b);
-        else sweep_group_block<16, 16, 0, WPB>(a, b);
+        else sweep_group_block<16, 16, WPB>(a, b);
         break;
     default:
         if constexpr (DEFER) screen_block<32, ITEMS, WIDE>(a, b);
-        else sweep_group_block<32, 16, 0, WPB>(a, b);
+        else sweep_group_block<32, 16, WPB>(a, b);
         break;
     }
 }

@@ -15,19 +15,16 @@ TYPE_NAMES = {NOT_BAD: "NotBad", CHIMERIC: "Chimeric", NOT_COVERED: "NotCovered"
 # test switch from include/yacrd_engine_debug.h
 F_FORCE_GENERAL = 1
 F_FORCE_LDS_SORT = 2
-F_XLANE_DS = 4
 F_WAVE_ONLY = 8
 F_NO_HALVES = 16
 F_TIMING_FULL = 32
 F_NO_PREDICTION = 64
-F_NO_FUSED_LAUNCH = 128
 F_NO_PREFILTER = 256
 F_COUNT_PREFILTERED = 512
 F_NO_TIMING = 1024
 F_BLOCKING_WAIT = 2048
 F_NO_DEFER = 4096
 F_ALWAYS_DEFER = 8192
-F_SWEEP_TURNS = 16384
 F_TIMING_SAMPLED = 32768
 F_STREAM_SCREEN = 65536
 F_SCREEN_ITEMS_1 = 262144
@@ -141,11 +138,11 @@ class _Timing(ctypes.Structure):
 
 CLASS_NAMES = "R2,R4,R8,R16,H16,W2,W4,W8,W16,M1,M2,BIG".split(",")
 CLASS_KERNELS = {  # the HIP kernel behind each class, as rocprofv3 prints it
-    "R2": "sweep_group_kernel<16, 2, 0>", "R4": "sweep_group_kernel<16, 4, 0>",
-    "R8": "sweep_group_kernel<16, 8, 0>", "R16": "sweep_group_kernel<16, 16, 0>",
-    "H16": "sweep_group_kernel<32, 16, 0>", "W2": "sweep_group_kernel<64, 2, 0>",
-    "W4": "sweep_group_kernel<64, 4, 0>", "W8": "sweep_group_kernel<64, 8, 0>",
-    "W16": "sweep_group_kernel<64, 16, 0>",
+    # (R2..H16 share one launch: yacrd_timing.fused_ms; its screening builds are named in bench.py)
+    "R2": "sweep_small_fused_kernel", "R4": "sweep_small_fused_kernel", "R8": "sweep_small_fused_kernel",
+    "R16": "sweep_small_fused_kernel", "H16": "sweep_small_fused_kernel",
+    "W2": "sweep_group_kernel<64, 2>", "W4": "sweep_group_kernel<64, 4>", "W8": "sweep_group_kernel<64, 8>",
+    "W16": "sweep_group_kernel<64, 16>",
     # the workgroup classes: the screen, then the fallback of what it leaves (two launches since round 6: screen_wg.h); the bracket
     # also holds the (usually empty) sweep_lds_kernel<1024, 32768> behind it for M2
     "M1": "screen_wg_kernel + screen_wg_fused_kernel over what it leaves",
