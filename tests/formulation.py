@@ -440,7 +440,7 @@ def healthy_read_regions(intervals, length, cov, nb):
 
 
 def window_screen_regions(intervals, length, cov, nb, W):
-    """sweep_wave.h's healthy-read screen on ORDER STATISTICS (round 3; replaces the exact-position
+    """screen_reg.h's healthy-read screen on ORDER STATISTICS (round 3; replaces the exact-position
     piles of healthy_read_regions).  With a = the (cov+1)-th smallest start and b = the (cov+1)-th
     largest end, a plain read whose starts beyond the first cov+1 all find more than cov intervals open
     is bad exactly in front of a and behind b: src/stack.rs:83-89 assigns first_covered at the first
@@ -727,7 +727,7 @@ def hole_screen_regions(intervals, length, cov, nb, W, max_slides, nbf=64):
 
 
 def hole_fast_regions(intervals, length, cov, nb, W, nbf=64):
-    """hole_screen_regions the way sweep_wave.h computes it (round 4): no second screen of the two halves — a and b,
+    """hole_screen_regions the way sweep_wave.h computed it (round 4; hole_form, up to 1714e90): no second screen of the two halves — a and b,
     the windows' counts F and G and the coarse blocks' depth bounds are the FIRST screen's (window_screen_regions: it
     found them and failed on the depth test of some block), and what the hole adds is looked at where it lies:
       1. istar = the first coarse block whose bound fails; only it and its successor may fail;

@@ -160,7 +160,7 @@ def test_pile_trimming_tiny_exhaustive():
 
 
 def test_window_screen_matches_oracle():
-    """The order-statistics screen of sweep_wave.h (round 3): wherever it applies it equals the oracle —
+    """The order-statistics screen of screen_reg.h (round 3): wherever it applies it equals the oracle —
     piles on one exact position (jitter 0), spread piles, windows, ties on a coarse grid, every window
     size the kernel can be built with and tiny ones that make the windows collide with everything."""
     from formulation import window_screen_regions

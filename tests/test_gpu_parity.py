@@ -385,7 +385,7 @@ def test_screen_on_jittered_profiles(prof, cov):
     from yacrd_amd import host
     R, O = (6000, 300000) if prof == 0 else (3000, 300000)
     # Round 4: sigma = 100 and 300 — the (c+1)-th smallest start lies beyond the screen's
-    # 32-position window for a fifth / most of the ONT-depth reads; the windows slide (sweep_wave.h: kScreenSlides) and
+    # 32-position window for a fifth / most of the ONT-depth reads; the windows slide (screen_reg.h: kScreenSlides) and
     # the screen still decides >= 90 % of them.
     for sflags in (host.SYNTH_F_JITTER, host.SYNTH_F_JITTER | host.synth_f_sigma(8),
                    host.SYNTH_F_JITTER | host.synth_f_sigma(100), host.SYNTH_F_JITTER | host.synth_f_sigma(300)):
@@ -787,7 +787,7 @@ def test_fused_defer_build(cov):
 @pytest.mark.parametrize("prof,cov", [(0, 4), (1, 3), (1, 0), (0, 9)])
 def test_hole_closed_form_on_chimeras(prof, cov):
     """Round 4: a read with ONE stretch of low coverage inside — a chimera — can get its three regions in closed form
-    from the screen (sweep_wave.h: hole_form, a build option; tests/formulation.py::hole_fast_regions is the emulation).
+    from the screen (sweep_wave.h: hole_form up to 1714e90; tests/formulation.py::hole_fast_regions is the emulation).
     30 % chimeras, clamped and spread piles, both builds of the screen: bit-exact with or without it; with it most
     chimeras no longer reach the sort."""
     from yacrd_amd import host
@@ -802,8 +802,8 @@ def test_hole_closed_form_on_chimeras(prof, cov):
                 for rep in range(2):
                     assert_same(e.run(o, iv, ln, cov, 0.4), want, "profile %d cov %d synth flags %d flags %d run %d" % (prof, cov, sflags, flags, rep))
                 t = e.timing()
-                # (the library is built without hole_form by default — sweep_wave.h: YK_HOLE_FORM — where it costs the
-                # screen more than it saves the sort; YACRD_TEST_HOLE_FORM=1 when testing a build that has it)
+                # (the library is built without hole_form — it cost the screen more than it saved the sort, and its kernel
+                # code was removed after 1714e90; YACRD_TEST_HOLE_FORM=1 when testing a build that has it)
                 if os.environ.get("YACRD_TEST_HOLE_FORM") == "1" and flags and cov in (3, 4) and not (sflags & (0xFF << 8)):
                     assert chimeric > R // 5 and t["deferred_reads"] < chimeric // 2, (t["deferred_reads"], chimeric)
 

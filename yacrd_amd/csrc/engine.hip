@@ -23,10 +23,10 @@
 #include "device_common.h"
 #include "plan_compact.h"
 #include "sweep_big.h"
+#include "sweep_wave.h"
 #include "sweep_big_trim.h"
 #include "sweep_general.h"
 #include "sweep_lds.h"
-#include "sweep_wave.h"
 #include "finish_compact.h"
 #include "screen_wg.h"
 #include "screen_stream.h"
@@ -562,7 +562,7 @@ int launch_register_classes(yacrd_engine *e, Run &R, const LaunchSet &set, bool 
         // two groups of list entries per wavefront in the screened classes when the launch streams from
         // HBM (more than the 256 MiB Infinity Cache holds): twice the loads in flight per wavefront
         // ... unless the last screened batch left more than a tenth of its reads to the sort: then the one-item build WITH
-        // the second looks (sliding windows, sweep_wave.h) takes the next kProbeEvery - 1 — dovetail ends spread by
+        // the second looks (sliding windows, screen_reg.h) takes the next kProbeEvery - 1 — dovetail ends spread by
         // hundreds of positions need them (configs[1] at sigma = 100: 79 % decided against 95 %; configs[2] at 300: 79 %
         // against 97 %), reads that do not are a tenth faster without (conclude_run: wide_left)
         const bool wide = defer && !(e->flags & YACRD_F_SCREEN_ITEMS_2) && ((e->flags & YACRD_F_SCREEN_WIDE) || e->wide_left > 0);

@@ -1,7 +1,7 @@
 // finish_compact.h — the follow-on kernel: finish what the screen deferred, then scan + compact + classify.
 //
 // One workgroup of 1024 threads per 1024 consecutive reads, one thread per read.
-//   Phase A  the reads of this slab that the healthy-read screen (sweep_wave.h) marked in counts[] are
+//   Phase A  the reads of this slab that the healthy-read screen (screen_reg.h) marked in counts[] are
 //            sorted here: listed in LDS, one read per wavefront and turn.  (Rounds 1-2 gave them a launch
 //            of their own —
 //            sweep_deferred_kernel: one read per wavefront on 64 lanes, 11 us of a 30 us batch on
@@ -12,9 +12,11 @@
 //            (reference src/editor/mod.rs:85-100).
 #pragma once
 #include "plan_compact.h"
+#include "screen_reg.h"
+#include "sweep_filtered.h"
 #include "sweep_lds.h"
 #include "sweep_wave.h"
-#include "sweep_filtered.h"
+#include "wave_ops.h"
 
 namespace yk {
 
@@ -31,10 +33,6 @@ struct CompactArgs2 {
 };
 
 constexpr int kFinishWaves = kScanBlock / 64;
-#ifndef YK_FINISH_ORDER_REL
-#define YK_FINISH_ORDER_REL __ATOMIC_RELAXED // (A/B: __ATOMIC_RELEASE / __ATOMIC_ACQUIRE, see the look-back below)
-#define YK_FINISH_ORDER_ACQ __ATOMIC_RELAXED
-#endif
 #ifndef YK_FINISH_OCC
 #define YK_FINISH_OCC 8 // register budget of the kernel as wavefronts per SIMD (512 / 8 = 64 VGPRs: two workgroups per CU)
 #endif
@@ -44,14 +42,11 @@ constexpr int kFinishWaves = kScanBlock / 64;
 // workgroups per CU; the 16 / 32-lane layouts with the bin filter in front need 96 and a filter table in LDS,
 // which left one workgroup per CU and made the scan + compaction of EVERY slab twice as slow).
 // One item = one read.  (As a function of its own — not inlined, so that the loop over the items cannot hoist
-// per-lane constants out and hold them next to the sort's keys — it measured the same or slower: YK_FINISH_INLINE.)
-#ifndef YK_FINISH_INLINE
-#define YK_FINISH_INLINE __forceinline__
-#endif
+// per-lane constants out and hold them next to the sort's keys — it measured the same or slower.)
 template <int K>
-__device__ YK_FINISH_INLINE void finish_item(const u64 *off, const uint2 *iv, const u32 *len, uint2 *stage, u32 *counts,
-                                             u32 *rej_list, u32 *rej_count, Counters *ctr, u32 cov, u32 rr, u64 o, u32 n,
-                                             u32 length)
+__device__ __forceinline__ void finish_item(const u64 *off, const uint2 *iv, const u32 *len, uint2 *stage, u32 *counts,
+                                            u32 *rej_list, u32 *rej_count, Counters *ctr, u32 cov, u32 rr, u64 o, u32 n,
+                                            u32 length)
 {
     SweepArgs fa;
     fa.off = off, fa.iv = iv, fa.len = len, fa.list = nullptr, fa.list_n = nullptr, fa.first = 0, fa.cov = cov;
@@ -64,40 +59,18 @@ struct MarkedRead { // what the thread that found the mark already knows about t
     u64 o;
     u32 n, len, idx, pad;
 };
-#ifndef YK_FINISH_FILTERED
-// Phase A through the filtered exact sweep (sweep_filtered.h), two marked reads per wavefront and turn, what the filter leaves sorted
-// whole behind a barrier.  Built, bit-exact (104 parity tests, 1.6 M fuzzed reads) and NOT faster: configs[1] one batch
+// (Phase A through the filtered exact sweep (sweep_filtered.h), two marked reads per wavefront and turn, what the filter leaves sorted
+// whole behind a barrier, was built, bit-exact (104 parity tests, 1.6 M fuzzed reads) and NOT faster: configs[1] one batch
 // at a time 65.2 -> 65.8 us with 128 registers (109 used, no scratch, one workgroup per CU), 70.6 at the kernel's 64 (68 bytes of scratch);
 // pipelined 24.7 -> 26.0 / 25.2; at sigma = 300 53.5 -> 55.7 / 62.1 (profiles/r06/P_finish.log).  A slab's two dozen marked reads are two
 // turns of sixteen wavefronts either way, and the filter's table + the barrier cost what the shorter sweep saves.  The plain sorts with
 // 128 registers (-DYK_FINISH_OCC=4: 99 used, no scratch) measured 25.3 us pipelined / 64.1 one at a time (24.7 / 65.2), 51.5 / 102.7
-// at sigma = 300 (53.5 / 105.2), 390 000 reads 87.4 / 134.9 (87.6 / 129.9): a draw, left at 8.
-#define YK_FINISH_FILTERED 0
-#endif
-template <int LANES, int WPB, int TABW>
-__device__ __forceinline__ bool filtered_turn(const SweepArgs &a, bool active, u32 r, u64 o, u32 n, u32 len, const LaneConst &lc);
-// s_fb / s_nfb (YK_FINISH_FILTERED): the slab's reads the filter did not take, sorted whole behind a barrier (s_nfb starts at 0)
-__device__ __forceinline__ void finish_marked(const SweepArgs &a, u32 bid, u32 n_marked, const MarkedRead *list, unsigned short *s_fb, u32 *s_nfb)
+// at sigma = 300 (53.5 / 105.2), 390 000 reads 87.4 / 134.9 (87.6 / 129.9): a draw, left at 8.  The filtered phase A was removed after
+// 1714e90; the code is in history up to that commit.)
+__device__ __forceinline__ void finish_marked(const SweepArgs &a, u32 bid, u32 n_marked, const MarkedRead *list)
 {
-#if YK_FINISH_FILTERED
-    constexpr int kTabWords = 2 * (2 * kScreenWindow + 32) * 4; // two 32-lane groups
-    const u32 wv = threadIdx.x >> 6, lane = lane_id();
-    const LaneConst lcf = make_lane_const(lane);
-    for (u32 p0 = wv * 2u; p0 < n_marked; p0 += (u32)kFinishWaves * 2u) { // (uniform in the wavefront)
-        const u32 p = p0 + (lane >> 5);
-        const bool have = p < n_marked;
-        const MarkedRead m = list[have ? p : p0];
-        const bool done = filtered_turn<32, kFinishWaves, kTabWords>(a, have, bid * kScanBlock + m.idx, m.o, m.n, m.len, lcf);
-        if (have && !done && (lane & 31u) == 31u) s_fb[atomicAdd(s_nfb, 1u)] = (unsigned short)p;
-    }
-    __syncthreads();
-    const u32 nfb = *s_nfb;
-    for (u32 i = wv; i < nfb; i += (u32)kFinishWaves) { // (uniform in the wavefront)
-        const MarkedRead m = list[s_fb[i]];
-#else
     for (u32 i = threadIdx.x >> 6; i < n_marked; i += (u32)kFinishWaves) { // (uniform in the wavefront)
         const MarkedRead m = list[i];
-#endif
         const u32 rr = bid * kScanBlock + m.idx;
         if (m.n > 128u)
             finish_item<8>(a.off, a.iv, a.len, a.stage, a.counts, a.rej_list, a.rej_count, a.ctr, a.cov, rr, m.o, m.n, m.len);
@@ -114,19 +87,12 @@ __global__ __launch_bounds__(kScanBlock, YK_FINISH_OCC) void finish_compact_kern
     __shared__ u32 s_n;
     __shared__ unsigned long long s_iv;
     __shared__ MarkedRead s_list[kScanBlock]; // the marked reads of the slab
-#if YK_FINISH_FILTERED
-    __shared__ unsigned short s_fb[kScanBlock];
-#else
-    unsigned short *s_fb = nullptr;
-#endif
-    __shared__ u32 s_nfb;
     const SweepArgs &a = c.sweep;
     Counters *ctr = a.ctr;
     if (threadIdx.x == 0) {
         s_bid = atomicAdd(&ctr->scan_ticket, 1u);
         s_n = 0;
         s_iv = 0;
-        s_nfb = 0;
     }
     __syncthreads();
     const u32 bid = s_bid, lane = lane_id();
@@ -158,9 +124,7 @@ __global__ __launch_bounds__(kScanBlock, YK_FINISH_OCC) void finish_compact_kern
     }
     __syncthreads();
     if (s_n) { // uniform in the workgroup
-#ifndef YK_FINISH_SKIP
-        finish_marked(a, bid, s_n, s_list, s_fb, &s_nfb);
-#endif
+        finish_marked(a, bid, s_n, s_list);
         __syncthreads(); // (global stores of this workgroup's wavefronts are visible to each other after it)
         if (threadIdx.x == 0) {
             // returning atomics, waited for: they are performed before this slab publishes its aggregate below, so the
@@ -200,14 +164,13 @@ __global__ __launch_bounds__(kScanBlock, YK_FINISH_OCC) void finish_compact_kern
                 // compiler emits an L2 write-back / invalidate per store / poll: the kernel went from 0.150 to 0.344 ms
                 // on configs[2], profiles/r04/b_ab_split_follow_on.log; on the short batches this kernel still serves:
                 // 20.6 -> 23.0 us for 100 000 reads, 33.7 -> 54.5 us for 390 000, the pipelined batch 26.6 -> 30.0 us,
-                // profiles/r04/m_ab_release_acquire_short_batches.log; -DYK_FINISH_ORDER_REL=__ATOMIC_RELEASE
-                // -DYK_FINISH_ORDER_ACQ=__ATOMIC_ACQUIRE builds it.)
-                __hip_atomic_store(&c.scan_state[bid], kAgg | tot, YK_FINISH_ORDER_REL, __HIP_MEMORY_SCOPE_AGENT);
+                // profiles/r04/m_ab_release_acquire_short_batches.log; the switch for it was removed after 1714e90.)
+                __hip_atomic_store(&c.scan_state[bid], kAgg | tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             for (i32 hi = (i32)bid - 1;; hi -= 64) {
                 const i32 idx = hi - (i32)lane; // lane 0 looks at the nearest predecessor
                 u64 v, pre;
                 for (;;) { // until the window holds no empty entry before its nearest prefix
-                    v = idx >= 0 ? __hip_atomic_load(&c.scan_state[idx], YK_FINISH_ORDER_ACQ, __HIP_MEMORY_SCOPE_AGENT)
+                    v = idx >= 0 ? __hip_atomic_load(&c.scan_state[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                                  : kPre; // before the first workgroup: prefix 0
                     pre = __builtin_amdgcn_ballot_w64((v >> 62) == 2);
                     const u64 before = pre ? ((pre & (0 - pre)) - 1ull) : ~0ull; // lanes nearer than it

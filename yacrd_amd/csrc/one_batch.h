@@ -6,7 +6,7 @@
 // 100 000 reads of which the memory system is busy for ~15.  Here the batch is one grid of one-wavefront workgroups:
 //   S  a wavefront takes 4 x ITEMS consecutive reads: their offsets (one load), their classes (a ballot: <= 128 intervals
 //      -> 16-lane groups, <= 256 -> 32-lane halves; nothing is binned across the batch, so there is nothing to plan),
-//      then the healthy-read screen of sweep_wave.h (screen_reads: the fused launch's code); the verdicts go to counts[] /
+//      then the healthy-read screen of screen_reg.h (screen_reads: the fused launch's code); the verdicts go to counts[] /
 //      closed[] with agent-scope stores;
 //   A  the reads the screen left are sorted right there, one per turn on 64 lanes (finish_item, finish_compact.h), and
 //      their regions and counts said again at agent scope;
@@ -19,7 +19,7 @@
 // a whole L2 per use: the first version with them took 111 us); what the host waits for is one kernel.
 // Measured (configs[1]: 100 000 reads / 10 M intervals; profiles/r04/q_*): S + A 26.6 us under rocprofv3 (the fused screen
 // alone: 18), with the arrivals 27.8, whole kernel 41-45; one batch at a time 51-55 us against 64-66 on the default path.
-// Timestamps inside the kernel (-DYK_OB_STAMPS) put the time in the screening wavefronts, not in phase B: they live 6-20 us
+// Timestamps inside the kernel (a diagnosis build, removed after 1714e90; profiles/r04/q_one_launch_stamps.log) put the time in the screening wavefronts, not in phase B: they live 6-20 us
 // (three dependent trips, two screens, a sort in every fifth), 1 563 of them per XCD on 768 slots; a slab's own phase B is
 // 3-4 us, and a later slab's look-back simply ends when the screening in front of it does.
 // A read of more than 256 intervals (the workgroup / device-wide classes) is not handled here: the kernel raises
@@ -27,6 +27,8 @@
 // which the sort rejected a read (exact path) or the regions outgrew their buffer.
 #pragma once
 #include "finish_compact.h"
+#include "screen_reg.h"
+#include "wave_ops.h"
 
 namespace yk {
 
@@ -82,7 +84,6 @@ struct VerdictsAcrossXcds {
 
 __global__ __launch_bounds__(64, YK_OB_OCC) void one_batch_kernel(OneBatchArgs ob)
 {
-    static_assert(!YK_HOLE_FORM, "the hole form answers through counts[] with plain stores");
     const CompactArgs2 &c = ob.c;
     const SweepArgs &a = c.sweep;
     Counters *ctr = a.ctr;
@@ -91,24 +92,13 @@ __global__ __launch_bounds__(64, YK_OB_OCC) void one_batch_kernel(OneBatchArgs o
     // own L2 — takes a contiguous eighth of the batch (neighbouring reads share cache lines).  (The other arrangement —
     // a slab's wavefronts on one XCD and the slabs round the XCDs, so that the batch is finished front to back and a
     // slab's look-back finds its predecessors done — measured slower: 59 against 53.5 us for the batch,
-    // profiles/r04/q_one_launch_phases.log; -DYK_OB_ROUND_ROBIN builds it.)
+    // profiles/r04/q_one_launch_phases.log; its code was removed after 1714e90.)
     u32 w = blockIdx.x;
-#ifdef YK_OB_ROUND_ROBIN
-    {
-        constexpr u32 kWavesPerSlab = (u32)(kObSlab / kObReads);
-        const u32 x = w & 7u, i = w >> 3;
-        w = ((i / kWavesPerSlab) * 8u + x) * kWavesPerSlab + i % kWavesPerSlab;
-    }
-#else
     {
         const u32 nb = gridDim.x, x = w & 7u, q = nb >> 3, rem = nb & 7u;
         w = x * q + min(x, rem) + (w >> 3);
     }
-#endif
     __shared__ u32 s_def[kObReads];
-#ifdef YK_OB_STAMPS
-    const u64 ob_stamp0 = wall_clock64();
-#endif
     const u32 lane = lane_id();
     const u32 r0 = w * (u32)kObReads;
     if (r0 >= c.n_reads) return; // (the grid is padded to whole rounds of eight slabs)
@@ -216,17 +206,8 @@ __global__ __launch_bounds__(64, YK_OB_OCC) void one_batch_kernel(OneBatchArgs o
         }
     }
 
-#if defined(YK_OB_EXPERIMENT) && YK_OB_EXPERIMENT == 1 // (timing only: phases S and A)
-    return;
-#endif
     // ---- the wavefront arrives at its slab; the last one to arrive takes the slab through phase B
-#ifdef YK_OB_STAMPS // (diagnosis: where the last slabs' time goes; wall clock, 100 MHz)
-    const u64 st_start = ob_stamp0, st_sa = wall_clock64();
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // every store above has been acknowledged
-#ifdef YK_OB_STAMPS
-    const u64 st_acked = wall_clock64();
-#endif
     const u32 slab = r0 / (u32)kObSlab;
     const u32 slab0 = slab * (u32)kObSlab;
     const u32 slab_reads = min(c.n_reads - slab0, (u32)kObSlab);
@@ -236,14 +217,7 @@ __global__ __launch_bounds__(64, YK_OB_OCC) void one_batch_kernel(OneBatchArgs o
                                       __HIP_MEMORY_SCOPE_AGENT);
     const u32 seen_lo = (u32)__builtin_amdgcn_readfirstlane((int)(u32)seen);
     if ((seen_lo & 0xFFFFu) + 1u != (slab_reads + (u32)kObReads - 1u) / (u32)kObReads) return;
-#ifdef YK_OB_STAMPS
-    const u64 st_arrived = wall_clock64();
-    u32 st_hops = 0;
-#endif
 
-#if defined(YK_OB_EXPERIMENT) && YK_OB_EXPERIMENT == 2 // (timing only: S, A and the arrivals)
-    return;
-#endif
     // ---- B: region counts -> scan (decoupled look-back over the slabs) -> CSR, type_of_read
     // Round trips, not bytes, are what this phase costs (it ends the launch): counts[], closed forms, lengths and offsets of
     // the whole slab go out together; the sorted reads' regions (their first three: nearly all have fewer) are asked for
@@ -290,15 +264,9 @@ __global__ __launch_bounds__(64, YK_OB_OCC) void one_batch_kernel(OneBatchArgs o
         if (sorted && g[k] > 2u) s2[k] = slot_at(so[k] + 2);
     }
     constexpr u64 kPre = 2ull << 62, kVal = (1ull << 62) - 1;
-#ifdef YK_OB_STAMPS
-    u64 st_loaded = wall_clock64();
-#endif
     u64 base = 0;
     if (slab > 0) {
         u32 polls = 0;
-#ifdef YK_OB_STAMPS
-        st_loaded = wall_clock64();
-#endif
         for (i32 hi = (i32)slab - 1;; hi -= 64 * kObLook) {
             // 64 x kObLook predecessors per round trip: lane l looks at hi - l, hi - 64 - l, ... (the nearest first)
             u64 part;
@@ -351,16 +319,10 @@ __global__ __launch_bounds__(64, YK_OB_OCC) void one_batch_kernel(OneBatchArgs o
 #pragma unroll
             for (int d = 32; d > 0; d >>= 1) part += __shfl_xor(part, d, 64);
             base += part;
-#ifdef YK_OB_STAMPS
-            st_hops++;
-#endif
             if (found) break;
         }
     }
     const bool last_slab = slab + 1u == ob.n_slabs;
-#ifdef YK_OB_STAMPS
-    const u64 st_looked = wall_clock64();
-#endif
     if (lane == 0) {
         __hip_atomic_store(&c.scan_state[slab], kPre | (base + tot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (last_slab) ctr->total_regions = base + tot;
@@ -442,15 +404,6 @@ __global__ __launch_bounds__(64, YK_OB_OCC) void one_batch_kernel(OneBatchArgs o
             c.read_type[r] = (uint8_t)classify(bad, middle, Lr, c.not_cov);
         }
     }
-#ifdef YK_OB_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const u64 st_end = wall_clock64();
-    if (lane == 0 && (slab % 49u == 48u || last_slab || slab < 2u))
-        printf("slab %u of %u: wave start %llu | S+A %llu | stores acked %llu | arrived %llu | loads+scan %llu | look-back %llu (%u hops) | outputs acked %llu (x10 ns, from the wave's start)\n",
-               slab, ob.n_slabs, (unsigned long long)st_start, (unsigned long long)(st_sa - st_start), (unsigned long long)(st_acked - st_start),
-               (unsigned long long)(st_arrived - st_start), (unsigned long long)(st_loaded - st_start), (unsigned long long)(st_looked - st_start),
-               st_hops, (unsigned long long)(st_end - st_start));
-#endif
 }
 
 } // namespace yk

@@ -16,7 +16,7 @@
 // Reference semantics: src/stack.rs:61-139 via the screen's rule (see screen_wg.h).
 #pragma once
 #include "device_common.h"
-#include "sweep_wave.h"
+#include "wave_ops.h"
 
 namespace yk {
 

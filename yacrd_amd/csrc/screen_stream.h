@@ -24,7 +24,7 @@
 // fiftieth of the class on the generator's reads), which sorts it on its persistent grid as before.
 #pragma once
 #include "device_common.h"
-#include "sweep_wave.h"
+#include "wave_ops.h"
 
 namespace yk {
 

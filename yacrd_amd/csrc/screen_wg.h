@@ -29,32 +29,12 @@
 // decide (8 % of configs[3]'s reads) goes to a fallback list for those kernels.
 #pragma once
 #include "device_common.h"
-#ifndef YK_EXP_NO_COUNT
-#define YK_EXP_NO_COUNT 0
-#endif
-#ifndef YK_EXP_NO_FALLBACK
-#define YK_EXP_NO_FALLBACK 0
-#endif
-#ifndef YK_WG_NT
-#define YK_WG_NT 0 // (1: the workgroup screen's interval loads non-temporal: A/B, profiles/r06/y_*)
-#endif
-#ifndef YK_WS_SIZED
-#define YK_WS_SIZED 1
-#endif
-#ifndef YK_EXP_FILT_STAGE
-#define YK_EXP_FILT_STAGE 0 // (timing experiments only: wg_filtered_read leaves, "done", behind stage 1 .. 4)
-#endif
-#ifndef YK_EXP_SKIP_UNDECIDED
-#define YK_EXP_SKIP_UNDECIDED 0
-#endif
-#ifndef YK_WS_SKIP_DEAD
-#define YK_WS_SKIP_DEAD 0 // (1: groups of T pairs beyond the read are neither loaded nor counted — measured SLOWER, 0.213 -> 0.248 ms on configs[3], profiles/r06/j_*: the uniform branches keep the eight loads from being issued together)
-#endif
-#ifndef YK_EXP_NO_FILTERED
-#define YK_EXP_NO_FILTERED 0
-#endif
+// Removed after 1714e90 (the code is in history up to that commit): the timing-only builds that left out the count, the
+// filtered sweep's stages, the undecided reads or the fallback (wrong results on purpose); non-temporal interval loads
+// (A/B, profiles/r06/y_*); and skipping the groups of T pairs beyond the read — neither loaded nor counted — which measured
+// SLOWER, 0.213 -> 0.248 ms on configs[3], profiles/r06/j_*: the uniform branches keep the eight loads from being issued together.
 #include "sweep_lds.h"
-#include "sweep_wave.h"
+#include "wave_ops.h"
 
 namespace yk {
 
@@ -68,7 +48,7 @@ constexpr int kWsBins = kWsT;
 // tab: kWsBins * 4 words, red: NW x 4, sc: NW + 1 words of LDS; ends with a barrier.
 // (o, n, len: the read's first interval, its intervals, its length — the persistent kernel has them before the turn starts)
 // A thread takes its intervals two at a time (16-byte loads: pair P = tid + kWsT * j holds intervals 2P and 2P + 1, the load
-// clamped to the read's last pair — as the register classes' screen does, sweep_wave.h).
+// clamped to the read's last pair — as the register classes' screen does, screen_reg.h).
 // what the screen learned about a read it could NOT decide, for wg_filtered_read below (the table stays in LDS)
 struct WgVerdict {
     bool plain;   // the table is the read's: every position inside the read and the key range, a span of two windows or more
@@ -92,27 +72,21 @@ __device__ __forceinline__ bool screen_wg_read(const SweepArgs &a, u32 r, u64 o,
     bool fallback = n < 2u; // (len is looked at behind the intervals' loads: it may still be on its way)
 
     // ---- the read's smallest start, largest end, largest start and shortest interval (signed)
-#if YK_WS_SKIP_DEAD
-    auto live = [&](u32 ch, int j) { return 2u * (ch * (u32)(T * R / 2) + (u32)(j * T)) < n; }; // (uniform: group j of chunk ch holds an interval)
-#else
-    auto live = [&](u32, int) { return true; };
-#endif
     uint4 v[R / 2];
     u32 smin = 0xFFFFFFFFu, emax = 0, smax = 0;
     i32 tmin = 0x7FFFFFFF;
     if (!fallback) {
         for (u32 ch = 0; ch < chunks; ch++) {
             const u32 base = ch * (u32)(T * R / 2) + tid; // (pairs)
-            // Round 6: a group of T pairs that lies beyond the read as a whole — uniform: its first interval's index against n —
-            // is neither loaded nor looked at (a read of 5 700 intervals fills six of a chunk's eight groups, a read of 600 one:
-            // the loads, the minima and the count's sixteen instructions + two LDS atomics per slot were spent on all eight).
+            // (Round 6 tried leaving out a group of T pairs that lies beyond the read as a whole — a read of 5 700 intervals fills
+            // six of a chunk's eight groups, a read of 600 one — and it was slower: see the note at the top; the sized builds
+            // below are what stayed.)
 #pragma unroll
             for (int j = 0; j < R / 2; j++) { // (slots beyond the read inside a live group: copies of its last two intervals)
-                if (live(ch, j)) v[j] = load_pair<(YK_WG_NT != 0)>(iv + min(2u * (base + (u32)(j * T)), n - 2u));
+                v[j] = load_pair<false>(iv + min(2u * (base + (u32)(j * T)), n - 2u));
             }
 #pragma unroll
             for (int j = 0; j < R / 2; j++) {
-                if (!live(ch, j)) continue;
                 smin = min(smin, min(v[j].y != 0u ? v[j].x : 0xFFFFFFFFu, v[j].w != 0u ? v[j].z : 0xFFFFFFFFu)); // ((0, 0) intervals are inert: left out)
                 smax = max(smax, max(v[j].x, v[j].z));
                 emax = max(emax, max(v[j].y, v[j].w));
@@ -155,25 +129,20 @@ __device__ __forceinline__ bool screen_wg_read(const SweepArgs &a, u32 r, u64 o,
             const u32 ds = s0 - pmin, dx = e0 - pmin;
             const u32 is = min(ds, (u32)W) + (ds >> sh) + __builtin_elementwise_sub_sat(ds, Tt);
             const u32 ie = min(dx, (u32)W) + (dx >> sh) + __builtin_elementwise_sub_sat(dx, Tt);
-#if !YK_EXP_NO_COUNT // (timing experiments only, tools/build_variant.sh: wrong results)
             if (real && e0 != 0u) {
                 atomicAdd(reinterpret_cast<u32 *>(tb + ((is << 4) + cp)), 1u);
                 atomicAdd(reinterpret_cast<u32 *>(tb + ((ie << 4) + cp)), kEnd);
             }
-#else
-            if (real && e0 != 0u && (is ^ ie) == 0xFFFFFFFFu) tb[0] = 1;
-#endif
         };
         for (u32 ch = 0; ch < chunks; ch++) {
             const u32 base = ch * (u32)(T * R / 2) + tid;
             if (chunks > 1u) {
 #pragma unroll
                 for (int j = 0; j < R / 2; j++)
-                    if (live(ch, j)) v[j] = load_pair<(YK_WG_NT != 0)>(iv + min(2u * (base + (u32)(j * T)), n - 2u));
+                    v[j] = load_pair<false>(iv + min(2u * (base + (u32)(j * T)), n - 2u));
             }
 #pragma unroll
             for (int j = 0; j < R / 2; j++) {
-                if (!live(ch, j)) continue;
                 const u32 i0 = 2u * (base + (u32)(j * T));
                 count(v[j].x, v[j].y, i0 + 1u < n); // (.xy is interval i0 only when i0 + 1 exists too: the clamped last pair)
                 count(v[j].z, v[j].w, i0 < n);
@@ -261,7 +230,7 @@ __device__ __forceinline__ bool screen_wg_read(const SweepArgs &a, u32 r, u32 *t
     return screen_wg_read<kWsR>(a, r, o, (u32)(a.off[r + 1] - o), a.len[r], tab, red, sc, vd);
 }
 // ... by the read's size: 4 / 8 / 12 / 16 slots per thread (round 6: configs[3]'s reads of 5 000-6 000 intervals fill six of the
-// sixteen-slot build's eight pair groups; skipping the dead groups behind uniform branches was slower, see YK_WS_SKIP_DEAD)
+// sixteen-slot build's eight pair groups; skipping the dead groups behind uniform branches was slower, see the note at the top)
 // (o, n: the read's extent when the caller has it — plan_kernel's record —, n = 0xFFFFFFFF: loaded here)
 __device__ __forceinline__ bool screen_wg_read_sized(const SweepArgs &a, u32 r, u64 o, u32 n, u32 *tab, u32 (*red)[4], u32 *sc)
 {
@@ -271,11 +240,9 @@ __device__ __forceinline__ bool screen_wg_read_sized(const SweepArgs &a, u32 r, 
         n = (u32)(a.off[r + 1] - o);
     }
     const u32 len = a.len[r]; // (asked for in front of the intervals, needed behind them: the same round trip)
-#if YK_WS_SIZED
     if (n <= (u32)(kWsT * 4)) return screen_wg_read<4>(a, r, o, n, len, tab, red, sc, vd);   // (uniform)
     if (n <= (u32)(kWsT * 8)) return screen_wg_read<8>(a, r, o, n, len, tab, red, sc, vd);
     if (n <= (u32)(kWsT * 12)) return screen_wg_read<12>(a, r, o, n, len, tab, red, sc, vd);
-#endif
     return screen_wg_read<kWsR>(a, r, o, n, len, tab, red, sc, vd);
 }
 __device__ __forceinline__ bool screen_wg_read(const SweepArgs &a, u32 r, u32 *tab, u32 (*red)[4], u32 *sc)
@@ -313,7 +280,6 @@ __device__ __forceinline__ bool wg_filtered_read(const SweepArgs &a, u32 r, cons
     constexpr u32 kEnd = 1u << 16, kField = kEnd - 1u;
     static_assert(kWsBins == T, "one bin per thread");
     if (!vd.plain || !vd.ends_ok) return false; // (uniform)
-    if (YK_EXP_FILT_STAGE == 1) return true;
     const u32 tid = threadIdx.x, lane = lane_id(), wv = tid >> 6;
     const i32 c = (i32)min(a.cov, 0x3FFFFFFFu);
     const u64 o = a.off[r];
@@ -353,7 +319,6 @@ __device__ __forceinline__ bool wg_filtered_read(const SweepArgs &a, u32 r, cons
     // per bin, where its counters were (every thread has read its own: the scans' barriers lie in between):
     // slot cursor, depth correction, kept
     bins[tid] = make_uint4(cex, (u32)(D - (i32)nex), kept ? 1u : 0u, 0u);
-    if (YK_EXP_FILT_STAGE == 2) return true;
     u32 P = 2;
     while (P < m_tot) P <<= 1;
     for (u32 i = m_tot + tid; i < P; i += T) keys[i] = kNoKey;
@@ -381,10 +346,8 @@ __device__ __forceinline__ bool wg_filtered_read(const SweepArgs &a, u32 r, cons
         }
     }
     __syncthreads(); // (the keys are written)
-    if (YK_EXP_FILT_STAGE == 3) return true;
     if (P >= 1024) hybrid_sort_lds<T>(keys, P, lc);
     else bitonic_sort_lds<T>(keys, P);
-    if (YK_EXP_FILT_STAGE == 4) return true;
     // ---- the sweep: thread t owns the sorted keys [t K, t K + K); depth in front of a key = the kept keys in front
     // (starts - ends) + its bin's correction
     constexpr int KMAX = kWfCap / T;
@@ -561,14 +524,9 @@ __global__ __launch_bounds__(kWsT, YK_WG_OCC) void screen_wg_fused_kernel(Screen
             const u32 r = a.list[b];
             WgVerdict vd;
             if (screen_wg_read(a, r, tab, red, sc, vd)) continue; // (uniform; ends with a barrier)
-#if YK_EXP_SKIP_UNDECIDED // (timing experiments only: the code below is in the kernel and never runs)
-            if (r != 0xFFFFFFFFu) continue;
-#endif
-#if !YK_EXP_NO_FILTERED
             const bool done = wg_filtered_read(a, r, vd, tab, sc, keys, s_masks, lane_const()); // (uniform)
             __syncthreads(); // (the table, sc, the masks and the keys are the next read's)
             if (done) continue;
-#endif
             if (tid == 0) s_mine[mine] = r;
             mine++;
         }
@@ -576,9 +534,7 @@ __global__ __launch_bounds__(kWsT, YK_WG_OCC) void screen_wg_fused_kernel(Screen
         if (tid == 0) atomicAdd(f.n_fallback, mine);
         __syncthreads();
         for (u32 k = 0; k < mine; k++) {
-#if !YK_EXP_NO_FALLBACK // (timing experiments only: the reads are dropped)
             sweep_lds_read<kWsT, kWsFbCap>(a, s_mine[k], keys, sc, lane_const());
-#endif
             __syncthreads(); // keys / sc reused
         }
     }

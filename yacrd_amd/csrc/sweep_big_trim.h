@@ -16,6 +16,7 @@
 #pragma once
 #include "device_common.h"
 #include "sweep_lds.h"
+#include "wave_ops.h"
 
 namespace yk {
 

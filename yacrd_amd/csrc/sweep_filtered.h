@@ -1,7 +1,7 @@
 // sweep_filtered.h — the follow-on step's FILTERED exact sweep (round 5).
 //
 // tests/formulation.py::filtered_sweep_regions is the emulation (fuzzed against the oracle, exhaustive over small
-// multisets).  The reads the healthy-read screen (sweep_wave.h) defers are the reads yacrd looks for: nearly all of
+// multisets).  The reads the healthy-read screen (screen_reg.h) defers are the reads yacrd looks for: nearly all of
 // them healthy at both ENDS and low somewhere inside.  Sorting such a read whole — 2n keys on 64 lanes, 847 VALU
 // instructions per read (profiles/r04) — sorts ~300 events that cannot matter.  Here the screen's own table is built
 // once more (healthy_screen: W one-position bins at either end, LANES coarse blocks in between) and read differently:
@@ -22,7 +22,8 @@
 // every sort step is shared.  Plain reads whose intervals are all at least W long only (the screen's own test);
 // everything else, and every guard that fails, leaves counts[r] marked and returns false: the caller sorts the read.
 #pragma once
-#include "sweep_wave.h"
+#include "screen_reg.h"
+#include "wave_ops.h"
 
 namespace yk {
 

@@ -14,14 +14,14 @@
 // Reads with a degenerate interval are handed to the general queue untouched.
 #pragma once
 #include "device_common.h"
-#include "sweep_wave.h"
+#include "wave_ops.h"
 
 namespace yk {
 
 // ---- register-resident pieces of the workgroup sort ------------------------------------------
 // A wavefront holds a 1024-key block striped over its lanes (element = r*64 + lane, r < 16), so
 // LDS loads/stores are conflict-free, strides >= 64 are register-to-register and strides < 64
-// are DPP / ds_swizzle exchanges (same primitives as sweep_wave.h).  Blocks that must come out
+// are DPP / ds_swizzle exchanges (the primitives of wave_ops.h, as sweep_wave.h).  Blocks that must come out
 // descending are complemented before and after, so every step below is ascending-only at the
 // block level; directions inside a block are compile-time (register bits) or lane constants.
 template <int M, int J>
