@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define YACRD_ABI_VERSION 7 /* 7: yacrd_timing.predicted / prediction_misses / build_switches / sorting_build; 6: yacrd_engines_ingest_overlaps[_mem]; 5: YACRD_F_ONE_LAUNCH, yacrd_timing.one_launch; 4: yacrd_timing.screen_items, yacrd_engine_ingest_overlaps_mem */
+#define YACRD_ABI_VERSION 7 /* (yacrd_engine_ingest_report[_mem] are additive: found by the symbol, like the editors) 7: yacrd_timing.predicted / prediction_misses / build_switches / sorting_build; 6: yacrd_engines_ingest_overlaps[_mem]; 5: YACRD_F_ONE_LAUNCH, yacrd_timing.one_launch; 4: yacrd_timing.screen_items, yacrd_engine_ingest_overlaps_mem */
 
 /* src/editor/mod.rs:42-59 ReadType; numeric encoding is ours, names are the reference's. */
 enum { YACRD_NOT_BAD = 0, YACRD_CHIMERIC = 1, YACRD_NOT_COVERED = 2 };
@@ -490,6 +490,25 @@ int yacrd_gzip_writer_sink(yacrd_gzip_writer *w, yacrd_byte_sink *sink);
 /* flush, EOF marker, rename; the writer is gone afterwards whatever is returned (on failure nothing is left at out_path) */
 int yacrd_gzip_writer_close(yacrd_gzip_writer *w, yacrd_gzip_stats *stats /* may be NULL */);
 void yacrd_gzip_writer_abort(yacrd_gzip_writer *w); /* nothing is left at out_path */
+
+/* ---- a `.yacrd` report read on the GPU (csrc/gpu_report.hip) -------------------------------------------------------------
+ * FromReport (src/stack.rs:176-257) behind src/main.rs:43-60: a report stands in for the overlap file, detection is skipped,
+ * the regions come from the report and type_of_read is redone with this run's not_coverage.  The host only moves the text to
+ * HBM; the device cuts the lines, parses `type \t id \t len \t len_i,begin_i,end_i;...`, interns the ids (an id seen again
+ * REPLACES the earlier row's length and regions and keeps its position), numbers the reads by first appearance, fills the
+ * region CSR and classifies it where it lies.  `out` holds bad_offsets, bad_regions and read_type — exactly what libyacrd_host's
+ * yacrd_report_read + yacrd_report_get and yacrd_engine_classify give —, `reads` the names, name_off and lengths
+ * (n_records: the non-empty lines); released with yacrd_result_free / yacrd_reads_free.  stats: text_ms the text into HBM with
+ * the line count behind it, parse_ms parse + id table + numbering, build_ms gather + scans + fill + types, run_ms 0.
+ * YACRD_EFALLBACK, with nothing returned: a compressed or non-regular file (inflate it and take the _mem form), any line the
+ * host reader calls corrupt (fewer than four columns, a length or a position that is not plain decimal digits or is beyond
+ * 2^32 - 1, a piece with fewer than two commas, a body that ends in ';'), a report beyond the device's free memory.  The
+ * caller then runs yacrd_report_read, which words the error with its line number.  The _mem form takes pageable memory and
+ * needs no padding.  The buffers stay with the engine: yacrd_engine_trim. */
+int yacrd_engine_ingest_report(yacrd_engine *e, const char *path, int n_threads, double not_coverage,
+                               yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats /* may be NULL */);
+int yacrd_engine_ingest_report_mem(yacrd_engine *e, const char *text, uint64_t n_bytes, int n_threads, double not_coverage,
+                                   yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats /* may be NULL */);
 
 /* Copy the last device result to host (allocates like yacrd_engine_run). */
 int yacrd_engine_fetch(yacrd_engine *e, yacrd_result *out);

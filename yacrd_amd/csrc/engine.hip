@@ -1250,6 +1250,16 @@ int h2d(yacrd_engine *e, void *dst, const void *src, size_t bytes)
     return YACRD_OK;
 }
 
+int classify_on_device(yacrd_engine *e, const u64 *d_bad_offsets, const uint2 *d_bad_regions, const u32 *d_len, u32 n_reads, double not_cov,
+                       uint8_t *d_read_type)
+{
+    if (n_reads)
+        hipLaunchKernelGGL(yk::classify_csr_kernel, dim3((n_reads + 255u) / 256u), dim3(256), 0, e->stream, d_bad_offsets, d_bad_regions, d_len,
+                           n_reads, not_cov, d_read_type);
+    HIP_TRY(hipGetLastError());
+    return YACRD_OK;
+}
+
 int fetch_result(yacrd_engine *e, yacrd_result *out)
 {
     if (!out) return fail(YACRD_EINVAL, "out is null");
@@ -1386,6 +1396,7 @@ void yacrd_engine_destroy(yacrd_engine *e)
     if (e->paf_scratch && e->paf_scratch_free) e->paf_scratch_free(e->paf_scratch);
     if (e->edit_scratch && e->edit_scratch_free) e->edit_scratch_free(e->edit_scratch);
     if (e->gzip_scratch && e->gzip_scratch_free) e->gzip_scratch_free(e->gzip_scratch);
+    if (e->report_scratch && e->report_scratch_free) e->report_scratch_free(e->report_scratch);
     for (int b = 0; b < yacrd_engine::kBounce; b++) {
         if (e->bounce[b]) (void)hipHostFree(e->bounce[b]);
         if (e->bounce_ev[b]) (void)hipEventDestroy(e->bounce_ev[b]);

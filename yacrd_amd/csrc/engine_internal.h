@@ -226,6 +226,9 @@ struct yacrd_engine {
     void (*gzip_scratch_free)(void *) = nullptr;
     void (*gzip_scratch_release)(void *) = nullptr;
     bool gzip_busy = false;                      // a yacrd_gzip_writer holds them
+    void *report_scratch = nullptr;              // gpu_report.hip's device buffers (its type), kept between calls
+    void (*report_scratch_free)(void *) = nullptr;
+    void (*report_scratch_release)(void *) = nullptr;
 };
 
 
@@ -233,6 +236,9 @@ namespace yke {
 // the whole launch sequence over a CSR resident in HBM (engine.hip)
 int run_on_device(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u32 *d_len,
                   uint64_t n_reads64, uint64_t n_iv, uint32_t cov, double not_cov, bool defer = false);
+// kernel #2 on a region CSR where it lies in HBM (engine.hip: classify_csr_kernel on the engine's stream; asynchronous)
+int classify_on_device(yacrd_engine *e, const u64 *d_bad_offsets, const uint2 *d_bad_regions, const u32 *d_len, u32 n_reads, double not_cov,
+                       uint8_t *d_read_type);
 // D2H of the last result into a freshly allocated yacrd_result
 int fetch_result(yacrd_engine *e, yacrd_result *out);
 // overlap records in HBM -> the engine's input CSR (stream.hip; blocking), and a u32 -> u64 exclusive scan

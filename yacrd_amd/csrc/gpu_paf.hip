@@ -626,6 +626,7 @@ int yacrd_engine_trim(yacrd_engine *e)
     if (e->paf_scratch) static_cast<Scratch *>(e->paf_scratch)->release();
     if (e->edit_scratch && e->edit_scratch_release) e->edit_scratch_release(e->edit_scratch);
     if (e->gzip_scratch && e->gzip_scratch_release && !e->gzip_busy) e->gzip_scratch_release(e->gzip_scratch);
+    if (e->report_scratch && e->report_scratch_release) e->report_scratch_release(e->report_scratch);
     return YACRD_OK;
 }
 

@@ -42,6 +42,21 @@ struct GpBytes {
     __device__ __forceinline__ u32 operator[](u64 i) const { return p[i]; }
 };
 
+// bit k of the result: byte k of the 16 is `c`
+__device__ __forceinline__ u32 gp_eq16(const uint4 &v, u32 c)
+{
+    const u32 w[4] = {v.x, v.y, v.z, v.w};
+    const u32 cc = c * 0x01010101u;
+    u32 m = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const u32 x = w[k] ^ cc;
+        const u32 z = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu); // 0x80 in every byte of x that is zero
+        m |= ((((z >> 7) * 0x00204081u) >> 21) & 0xFu) << (4 * k);
+    }
+    return m;
+}
+
 template <class Text>
 __device__ __forceinline__ u64 gp_hash(const Text &t, u64 p, u32 n)
 {

@@ -168,18 +168,56 @@ int main(int argc, char **argv)
     // src/main.rs:43-60: a .yacrd input bypasses detection (FromReport), anything else is overlaps
     const bool m4 = has(input, ".m4") || has(input, ".mhap"), paf = has(input, ".paf");
     if (!m4 && !paf && has(input, ".yacrd")) {
-        if (yacrd_report_read(input.c_str(), &rep)) die(yacrd_host_last_error());
-        yacrd_report_get(rep, &bp);
-        rep_types.resize((size_t)bp.n_reads + 1);
-        // type_of_read with this invocation's -n, on the GPU (kernel #2)
-        if (yacrd_engine_classify(engines[0], bp.bad_offsets, bp.bad_regions, bp.lengths, bp.n_reads,
-                                  not_coverage, rep_types.data()) != YACRD_OK)
-            die(yacrd_last_error());
-        bp.read_type = rep_types.data();
-        view.n_reads = bp.n_reads;
-        view.name_off = bp.name_off;
-        view.names = bp.names;
-        view.lengths = bp.lengths;
+        // The report's text goes to HBM and the device parses it, keeps every id's last row at its first position, fills the
+        // region CSR and classifies it with this invocation's -n (yacrd_engine_ingest_report; a compressed report is inflated
+        // first and takes the _mem form, as a compressed overlap file does).  Whatever that reader does not take — a corrupt
+        // line above all — comes back as YACRD_EFALLBACK and takes the host reader below, which words the error with its
+        // line number.  YACRD_NO_DEVICE_REPORT=1: the host reader (A/B).
+        int dev_rep = YACRD_EFALLBACK;
+        const char *no_rep = std::getenv("YACRD_NO_DEVICE_REPORT");
+        if (!(no_rep && *no_rep == '1')) {
+            const char *ct = std::getenv("YACRD_COPY_THREADS");
+            const int copy_threads = ct && *ct ? std::max(0, std::atoi(ct)) : 0;
+            yacrd_ingest_stats is{};
+            const int rct = yacrd_text_from_file(input.c_str(), threads == 1 ? 0 : (int)threads, &text);
+            stage("inflate");
+            // (rct 1, a file that cannot be read or inflated: the host reader below words that error too)
+            dev_rep = rct == 1 ? YACRD_EFALLBACK : rct == 0 ? yacrd_engine_ingest_report_mem(engines[0], text.data, text.n, copy_threads, not_coverage, &res, &dev_reads, &is)
+                               : yacrd_engine_ingest_report(engines[0], input.c_str(), copy_threads, not_coverage, &res, &dev_reads, &is);
+            if (dev_rep == YACRD_ENOMEM) {
+                std::fprintf(stderr, "[INFO] device report reader: %s; falling back to the host reader\n", yacrd_last_error());
+                for (yacrd_engine *en : engines) (void)yacrd_engine_trim(en);
+                dev_rep = YACRD_EFALLBACK;
+            }
+            if (dev_rep != YACRD_OK && dev_rep != YACRD_EFALLBACK) die(yacrd_last_error());
+            if (dev_rep == YACRD_OK && timing)
+                std::fprintf(stderr, "[info] device report reader: %llu reads from %llu lines, %llu bytes%s, text %.1f ms, parse %.1f ms, build %.1f ms, "
+                                     "d2h %.1f ms\n",
+                             (unsigned long long)is.n_reads, (unsigned long long)is.n_records, (unsigned long long)is.text_bytes,
+                             rct == 0 ? " (inflated)" : "", is.text_ms, is.parse_ms, is.build_ms, is.d2h_ms);
+        }
+        if (dev_rep == YACRD_OK) {
+            bp.n_reads = view.n_reads = dev_reads.n_reads;
+            bp.name_off = view.name_off = dev_reads.name_off;
+            bp.names = view.names = dev_reads.names;
+            bp.lengths = view.lengths = dev_reads.lengths;
+            bp.bad_offsets = res.bad_offsets;
+            bp.bad_regions = res.bad_regions;
+            bp.read_type = res.read_type;
+        } else {
+            if (yacrd_report_read(input.c_str(), &rep)) die(yacrd_host_last_error());
+            yacrd_report_get(rep, &bp);
+            rep_types.resize((size_t)bp.n_reads + 1);
+            // type_of_read with this invocation's -n, on the GPU (kernel #2)
+            if (yacrd_engine_classify(engines[0], bp.bad_offsets, bp.bad_regions, bp.lengths, bp.n_reads,
+                                      not_coverage, rep_types.data()) != YACRD_OK)
+                die(yacrd_last_error());
+            bp.read_type = rep_types.data();
+            view.n_reads = bp.n_reads;
+            view.name_off = bp.name_off;
+            view.names = bp.names;
+            view.lengths = bp.lengths;
+        }
     } else {
         int dev_parse = YACRD_EFALLBACK;
         // YACRD_NO_DEVICE_PARSER=1: the host parser for everything (A/B, tools/e2e_cli_paf.py)

@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = [
     "yacrd_stream_finish", "yacrd_stream_last_stats", "yacrd_stream_reset", "yacrd_stream_close",
     "yacrd_engine_ingest_paf", "yacrd_engine_ingest_overlaps", "yacrd_engine_ingest_overlaps_mem", "yacrd_engines_ingest_overlaps",
     "yacrd_engines_ingest_overlaps_mem", "yacrd_reads_free", "yacrd_engine_trim",
+    "yacrd_engine_ingest_report", "yacrd_engine_ingest_report_mem",
     "yacrd_engine_edit_overlaps", "yacrd_engine_edit_overlaps_mem", "yacrd_edit_text_free",
     "yacrd_engine_edit_overlaps_gzip_mem", "yacrd_engine_edit_overlaps_gzip_file",
     "yacrd_engine_gzip_mem", "yacrd_gzip_writer_open", "yacrd_gzip_writer_write", "yacrd_gzip_writer_sink", "yacrd_gzip_writer_close",
@@ -277,6 +278,10 @@ def load_library():
     lib.yacrd_engines_ingest_overlaps_mem.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
                                                       ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_double,
                                                       ctypes.POINTER(_Result), ctypes.POINTER(_Reads), ctypes.POINTER(_IngestStats)]
+    lib.yacrd_engine_ingest_report.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_double, ctypes.POINTER(_Result),
+                                               ctypes.POINTER(_Reads), ctypes.POINTER(_IngestStats)]
+    lib.yacrd_engine_ingest_report_mem.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_double,
+                                                   ctypes.POINTER(_Result), ctypes.POINTER(_Reads), ctypes.POINTER(_IngestStats)]
     lib.yacrd_debug_sort_pairs.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]
     lib.yacrd_engine_trim.argtypes = [ctypes.c_void_p]
     lib.yacrd_engine_edit_overlaps.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
@@ -522,6 +527,27 @@ class Engine:
             addr, n = ctypes.addressof(keep), len(text)
         rc = self._lib.yacrd_engine_ingest_overlaps_mem(self._h, addr, n, int(fmt), int(n_threads), min(int(coverage), 0xFFFFFFFF),
                                                         float(not_coverage), ctypes.byref(res), ctypes.byref(rd), ctypes.byref(st))
+        del keep
+        return self._ingested(rc, res, rd, st)
+
+    def ingest_report(self, path_or_bytes, not_coverage, n_threads=0):
+        """yacrd_engine_ingest_report (a path: str / os.PathLike) or yacrd_engine_ingest_report_mem (bytes, or (address,
+        n_bytes) of a buffer such as host.text_from_file's): a .yacrd report -> (Result, names, lengths, stats) as from
+        ingest_paf / ingest_text, parsed, deduplicated and classified on the GPU (FromReport, src/stack.rs:176-257); raises
+        NeedsHostParser when the report is for host.report_read + classify."""
+        res, rd, st = _Result(), _Reads(), _IngestStats()
+        if isinstance(path_or_bytes, (str, os.PathLike)):
+            rc = self._lib.yacrd_engine_ingest_report(self._h, os.fsencode(path_or_bytes), int(n_threads), float(not_coverage),
+                                                      ctypes.byref(res), ctypes.byref(rd), ctypes.byref(st))
+            return self._ingested(rc, res, rd, st)
+        if isinstance(path_or_bytes, tuple):
+            addr, n = int(path_or_bytes[0]), int(path_or_bytes[1])
+            keep = None
+        else:
+            keep = ctypes.create_string_buffer(bytes(path_or_bytes), len(path_or_bytes))
+            addr, n = ctypes.addressof(keep), len(path_or_bytes)
+        rc = self._lib.yacrd_engine_ingest_report_mem(self._h, addr, n, int(n_threads), float(not_coverage), ctypes.byref(res),
+                                                      ctypes.byref(rd), ctypes.byref(st))
         del keep
         return self._ingested(rc, res, rd, st)
 
