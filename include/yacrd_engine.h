@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define YACRD_ABI_VERSION 7 /* (yacrd_engine_ingest_report[_mem] are additive: found by the symbol, like the editors) 7: yacrd_timing.predicted / prediction_misses / build_switches / sorting_build; 6: yacrd_engines_ingest_overlaps[_mem]; 5: YACRD_F_ONE_LAUNCH, yacrd_timing.one_launch; 4: yacrd_timing.screen_items, yacrd_engine_ingest_overlaps_mem */
+#define YACRD_ABI_VERSION 7 /* (yacrd_engine_ingest_report[_mem] and yacrd_engine_write_report[_mem] are additive: found by the symbol, like the editors) 7: yacrd_timing.predicted / prediction_misses / build_switches / sorting_build; 6: yacrd_engines_ingest_overlaps[_mem]; 5: YACRD_F_ONE_LAUNCH, yacrd_timing.one_launch; 4: yacrd_timing.screen_items, yacrd_engine_ingest_overlaps_mem */
 
 /* src/editor/mod.rs:42-59 ReadType; numeric encoding is ours, names are the reference's. */
 enum { YACRD_NOT_BAD = 0, YACRD_CHIMERIC = 1, YACRD_NOT_COVERED = 2 };
@@ -509,6 +509,46 @@ int yacrd_engine_ingest_report(yacrd_engine *e, const char *path, int n_threads,
                                yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats /* may be NULL */);
 int yacrd_engine_ingest_report_mem(yacrd_engine *e, const char *text, uint64_t n_bytes, int n_threads, double not_coverage,
                                    yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats /* may be NULL */);
+
+/* ---- a `.yacrd` report written on the GPU (csrc/gpu_report_write.hip) ----------------------------------------------------
+ * The report of src/editor/mod.rs:61-83, byte for byte what libyacrd_host's yacrd_report_write writes for the same arrays: one
+ * line per read in table order, `{NotBad|Chimeric|NotCovered} \t id \t len \t piece;piece;... \n`, a piece
+ * `{end - begin as u32, wrapping},{begin},{end}`, an id any bytes.  The device sizes every head and every piece, scans the
+ * sizes and formats the whole text in one buffer in HBM (a thread per read, a thread per region); the text then comes home
+ * in segments through two pinned buffers, segment i + 1 crossing the link while segment i is written.  The file form
+ * writes beside out_path and renames when the last byte is in; the memory form returns a buffer of the library's
+ * (yacrd_edit_text_free).  The bytes do not depend on the segment size.
+ * t == NULL, the RESIDENT form: the arrays are read where the engine's last ingest left them in HBM, nothing is uploaded —
+ * after yacrd_engine_ingest_paf / _overlaps[_mem], the N-engine forms called with ONE engine, or
+ * yacrd_engine_ingest_report[_mem]; any run, submit, stream finish, ingest, classify or yacrd_engine_trim called on the engine
+ * since — whether it succeeded or not, in every form: device, batches, partitioned, group — and there is no such table:
+ * YACRD_EFALLBACK.  Otherwise the table's seven arrays are uploaded first.
+ * YACRD_EFALLBACK, with nothing written and nothing left behind: a read_type beyond 2 (found on the device), bad_offsets or
+ * name_off that do not rise from 0 to their totals, an id of 2^31 bytes, 2^31 reads or regions, an out_path that exists and is no
+ * regular file or beside which no file can be created (it is created before anything is formatted), an existing out_path
+ * with further hard links or one that may not be written (the rename would replace what yacrd_report_write truncates in
+ * place; an existing file's mode is kept).  The caller then runs yacrd_report_write, which owns the messages.
+ * YACRD_ENOMEM: the text's buffer did not fit; nothing was written.  The buffers stay with the engine: yacrd_engine_trim. */
+typedef struct { /* host arrays, as yacrd_reads + yacrd_result hold them */
+    uint64_t n_reads;
+    const uint64_t *name_off; /* R+1 */
+    const char *names;
+    const uint32_t *lengths;      /* R */
+    const uint64_t *bad_offsets;  /* R+1 */
+    const uint32_t *bad_regions;  /* 2*G */
+    const uint8_t *read_type;     /* R */
+} yacrd_report_table;
+typedef struct {
+    uint64_t n_reads, n_regions, text_bytes;
+    float up_ms;     /* the table's upload (device events; ~0 for the resident form) */
+    float kernel_ms; /* size + scan + emit (device events) */
+    float out_ms;    /* the writer's busy time: segments into the file or the buffer */
+    uint32_t resident;
+} yacrd_report_write_stats;
+int yacrd_engine_write_report(yacrd_engine *e, const yacrd_report_table *t /* NULL = resident */, const char *out_path,
+                              yacrd_report_write_stats *st /* may be NULL */);
+int yacrd_engine_write_report_mem(yacrd_engine *e, const yacrd_report_table *t /* NULL = resident */, char **out, uint64_t *out_bytes,
+                                  yacrd_report_write_stats *st /* may be NULL */);
 
 /* Copy the last device result to host (allocates like yacrd_engine_run). */
 int yacrd_engine_fetch(yacrd_engine *e, yacrd_result *out);

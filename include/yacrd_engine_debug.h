@@ -62,6 +62,9 @@ uint64_t yacrd_debug_last_counters(const yacrd_engine *e, void *dst, uint64_t by
  * one device, and makes every engine gather the other engines' records instead of reading them in place: the multi-device
  * branch on a one-GPU box. */
 void yacrd_debug_peer_copy_counts(uint64_t out[3]);
+/* YACRD_TEST_REPORT_SEGMENT=<bytes> (environment, tests; read at every call): the size of the segments in which
+ * yacrd_engine_write_report[_mem] brings the formatted text home, instead of 64 MiB (csrc/gpu_report_write.hip: kReportSegment;
+ * 1 .. 2^30).  The bytes written do not depend on it: tests/test_gpu_report_write.py cuts lines at hundreds of borders. */
 #ifdef __cplusplus
 }
 #endif

@@ -952,6 +952,7 @@ int run_on_device(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u3
     if (n_reads64 >= 0xFFFFFFFFull) return fail(YACRD_EINVAL, "n_reads must be < 2^32 - 1");
     if (e->pending.active) return fail(YACRD_EINVAL, "a submitted batch is pending: yacrd_engine_wait first");
     e->has_result = false;
+    e->resident.valid = false; // (in_len and the result arrays are about to be rewritten)
     e->timing = yacrd_timing{};
 
     HIP_TRY(e->bad_offsets.reserve((n_reads64 + 1) * sizeof(u64)));
@@ -1397,6 +1398,7 @@ void yacrd_engine_destroy(yacrd_engine *e)
     if (e->edit_scratch && e->edit_scratch_free) e->edit_scratch_free(e->edit_scratch);
     if (e->gzip_scratch && e->gzip_scratch_free) e->gzip_scratch_free(e->gzip_scratch);
     if (e->report_scratch && e->report_scratch_free) e->report_scratch_free(e->report_scratch);
+    if (e->report_write_scratch && e->report_write_scratch_free) e->report_write_scratch_free(e->report_write_scratch);
     for (int b = 0; b < yacrd_engine::kBounce; b++) {
         if (e->bounce[b]) (void)hipHostFree(e->bounce[b]);
         if (e->bounce_ev[b]) (void)hipEventDestroy(e->bounce_ev[b]);
@@ -1420,6 +1422,7 @@ int yacrd_engine_run_device(yacrd_engine *e, const void *d_offsets, const void *
                             uint32_t coverage, double not_coverage, yacrd_device_result *out)
 {
     if (!e) return fail(YACRD_EINVAL, "engine is null");
+    e->resident.valid = false; // (first: everything below may rewrite or move in_len and the result arrays)
     if (n_reads && (!d_offsets || !d_lengths)) return fail(YACRD_EINVAL, "null device input");
     if (n_intervals && !d_intervals) return fail(YACRD_EINVAL, "null device intervals");
     if (e->host_pending) return fail(YACRD_EINVAL, "a submitted batch is pending: collect it first");
@@ -1442,6 +1445,7 @@ int yacrd_engine_submit_device(yacrd_engine *e, const void *d_offsets, const voi
                                uint32_t coverage, double not_coverage)
 {
     if (!e) return fail(YACRD_EINVAL, "engine is null");
+    e->resident.valid = false; // (first: everything below may rewrite or move in_len and the result arrays)
     if (n_reads && (!d_offsets || !d_lengths)) return fail(YACRD_EINVAL, "null device input");
     if (n_intervals && !d_intervals) return fail(YACRD_EINVAL, "null device intervals");
     if (e->host_pending) return fail(YACRD_EINVAL, "a submitted batch is pending: collect it first");
@@ -1474,6 +1478,7 @@ int yacrd_engines_run_device_batches(yacrd_engine *const *engines, uint32_t n_en
     if (!engines || n_engines == 0 || (!batches && n_batches)) return fail(YACRD_EINVAL, "bad argument");
     for (uint32_t j = 0; j < n_engines; j++)
         if (!engines[j]) return fail(YACRD_EINVAL, "engine is null");
+    for (uint32_t j = 0; j < n_engines; j++) engines[j]->resident.valid = false;
     std::vector<int64_t> inflight(n_engines, -1); // batch in flight on each engine
     yacrd_device_result res{};
     auto finish = [&](uint32_t j) -> int {
@@ -1540,6 +1545,7 @@ int yacrd_engine_run(yacrd_engine *e, const uint64_t *offsets, const uint32_t *i
                      double not_coverage, yacrd_result *out)
 {
     if (!e) return fail(YACRD_EINVAL, "engine is null");
+    e->resident.valid = false; // (first: everything below may rewrite or move in_len and the result arrays)
     if (!out) return fail(YACRD_EINVAL, "out is null");
     std::memset(out, 0, sizeof(*out));
     if (e->pending.active) return fail(YACRD_EINVAL, "a submitted batch is pending: yacrd_engine_wait first");
@@ -1565,6 +1571,7 @@ int yacrd_engine_submit(yacrd_engine *e, const uint64_t *offsets, const uint32_t
                         double not_coverage)
 {
     if (!e) return fail(YACRD_EINVAL, "engine is null");
+    e->resident.valid = false; // (first: everything below may rewrite or move in_len and the result arrays)
     if (e->pending.active || e->host_pending)
         return fail(YACRD_EINVAL, "a submitted batch is pending: collect it first");
     DeviceGuard guard(e->device);
@@ -1697,6 +1704,7 @@ int yacrd_engines_run_partitioned(yacrd_engine *const *engines, uint32_t n_engin
     std::memset(out, 0, sizeof(*out));
     for (uint32_t p = 0; p < n_engines; p++)
         if (!engines[p]) return fail(YACRD_EINVAL, "null engine");
+    for (uint32_t p = 0; p < n_engines; p++) engines[p]->resident.valid = false;
     std::vector<uint64_t> cuts(n_engines + 1);
     int rc = yacrd_partition_reads(offsets, n_reads, n_engines, cuts.data());
     if (rc) return rc;
@@ -1759,6 +1767,7 @@ int yacrd_engine_classify(yacrd_engine *e, const uint64_t *bad_offsets, const ui
                           uint8_t *read_type)
 {
     if (!e) return fail(YACRD_EINVAL, "engine is null");
+    e->resident.valid = false;
     if (n_reads == 0) return YACRD_OK;
     if (!bad_offsets || !lengths || !read_type) return fail(YACRD_EINVAL, "null argument");
     if (n_reads >= 0xFFFFFFFFull) return fail(YACRD_EINVAL, "n_reads must be < 2^32 - 1");

@@ -219,6 +219,19 @@ struct yacrd_engine {
         int64_t mtime_s = 0, mtime_ns = 0;
         bool valid = false;
     } mirror;
+    // the read table the engine's last ingest left in HBM (gpu_paf.hip with one engine, gpu_report.hip): names, name_off and
+    // lengths where that ingest's scratch (and in_len) hold them; with bad_offsets / bad_regions / read_type they are all a
+    // report is made of (gpu_report_write.hip).  Set by a successful ingest as its last step.  Cleared by the FIRST statement
+    // of every entry point that may rewrite or move one of those buffers, before any reserve or copy, whether the call then
+    // succeeds or not: run, submit, their device, batch and partitioned forms, a stream's or group's finish, every ingest,
+    // classify, trim.
+    struct {
+        const unsigned char *names = nullptr;
+        const u64 *name_off = nullptr; // n_reads + 1
+        const u32 *lengths = nullptr;
+        uint64_t n_reads = 0;
+        bool valid = false;
+    } resident;
     void *edit_scratch = nullptr;                // gpu_edit.hip's device and pinned buffers (its type), kept between calls
     void (*edit_scratch_free)(void *) = nullptr; // (destroy)
     void (*edit_scratch_release)(void *) = nullptr; // (yacrd_engine_trim)
@@ -229,6 +242,9 @@ struct yacrd_engine {
     void *report_scratch = nullptr;              // gpu_report.hip's device buffers (its type), kept between calls
     void (*report_scratch_free)(void *) = nullptr;
     void (*report_scratch_release)(void *) = nullptr;
+    void *report_write_scratch = nullptr;        // gpu_report_write.hip's device and pinned buffers (its type), kept between calls
+    void (*report_write_scratch_free)(void *) = nullptr;
+    void (*report_write_scratch_release)(void *) = nullptr;
 };
 
 

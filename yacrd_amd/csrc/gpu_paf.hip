@@ -623,10 +623,12 @@ int yacrd_engine_trim(yacrd_engine *e)
     if (e->pending.active || e->host_pending) return fail(YACRD_EINVAL, "the engine has a submitted batch pending");
     DeviceGuard guard(e->device);
     e->mirror.valid = false;
+    e->resident.valid = false;
     if (e->paf_scratch) static_cast<Scratch *>(e->paf_scratch)->release();
     if (e->edit_scratch && e->edit_scratch_release) e->edit_scratch_release(e->edit_scratch);
     if (e->gzip_scratch && e->gzip_scratch_release && !e->gzip_busy) e->gzip_scratch_release(e->gzip_scratch);
     if (e->report_scratch && e->report_scratch_release) e->report_scratch_release(e->report_scratch);
+    if (e->report_write_scratch && e->report_write_scratch_release) e->report_write_scratch_release(e->report_write_scratch);
     return YACRD_OK;
 }
 
@@ -661,6 +663,7 @@ int yacrd_engine_ingest_overlaps(yacrd_engine *e, const char *path, int format, 
                                  double not_coverage, yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats)
 {
     if (!e || !path || !out || !reads) return fail(YACRD_EINVAL, "null argument");
+    e->resident.valid = false;
     bool m4 = false;
     if (const int rcf = ingest_format(path, format, m4)) return rcf;
     std::memset(out, 0, sizeof(*out));
@@ -696,6 +699,7 @@ int yacrd_engine_ingest_overlaps_mem(yacrd_engine *e, const char *text, uint64_t
                                      double not_coverage, yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats)
 {
     if (!e || (!text && n) || !out || !reads) return fail(YACRD_EINVAL, "null argument");
+    e->resident.valid = false;
     bool m4 = false;
     if (const int rcf = ingest_format(nullptr, format, m4)) return rcf;
     std::memset(out, 0, sizeof(*out));
@@ -737,6 +741,7 @@ int parse_range(yacrd_engine *e, const TextSource &src, u64 file_n, u64 begin, u
     if (!Sp) return fail(YACRD_ENOMEM, "host allocation failed");
     Scratch &S = *Sp;
     e->mirror.valid = false; // (the mirror is about to be rewritten)
+    e->resident.valid = false;
     // the mirror holds the range and, behind it, up to one chunk more of the file: a line that starts in the range ends there
     // (or the parse says so: kNeedHost)
     constexpr u64 kOverhang = (u64)4 << 20;
@@ -956,6 +961,10 @@ int ingest_text(yacrd_engine *e, const TextSource &src, u64 n, bool m4, int n_th
     };
     rc = body();
     if (rc) yacrd_reads_free(reads);
+    else { // the table stays where it is: a report can be written from it (gpu_report_write.hip)
+        e->resident.names = S.names.as<unsigned char>(), e->resident.name_off = S.name_off.as<u64>(), e->resident.lengths = e->in_len.as<u32>();
+        e->resident.n_reads = R, e->resident.valid = true;
+    }
     return rc;
 }
 
@@ -1420,6 +1429,7 @@ static int group_args(yacrd_engine *const *engines, uint32_t n_engines, yacrd_re
     if (!engines || !n_engines || !out || !reads) return fail(YACRD_EINVAL, "null argument");
     for (uint32_t d = 0; d < n_engines; d++) {
         if (!engines[d]) return fail(YACRD_EINVAL, "engine is null");
+        engines[d]->resident.valid = false; // (an engine that parses no range still gets its reads' lengths in in_len)
         if (engines[d]->pending.active || engines[d]->host_pending) return fail(YACRD_EINVAL, "an engine has a submitted batch pending");
         for (uint32_t k = 0; k < d; k++)
             if (engines[k] == engines[d]) return fail(YACRD_EINVAL, "the same engine twice");

@@ -348,6 +348,7 @@ int read_report(yacrd_engine *e, const TextSource &src, u64 n, int n_threads, do
     ReportScratch *Sp = report_scratch_of(e);
     if (!Sp) return fail(YACRD_ENOMEM, "host allocation failed");
     ReportScratch &S = *Sp;
+    e->resident.valid = false;
     const double t_start = now_ms();
     const u64 n_tiles = (n + yk::kGpTile - 1) / yk::kGpTile;
     if (n_tiles >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "file too large for the device report reader");
@@ -505,12 +506,16 @@ int read_report(yacrd_engine *e, const TextSource &src, u64 n, int n_threads, do
         stats->run_ms = 0.f; // (the types are part of build_ms: one launch behind the fill)
         stats->d2h_ms = (float)(now_ms() - t_build);
     }
+    // the table stays where it is: a report can be written from it (gpu_report_write.hip)
+    e->resident.names = S.names.as<unsigned char>(), e->resident.name_off = S.name_off.as<u64>(), e->resident.lengths = e->in_len.as<u32>();
+    e->resident.n_reads = R, e->resident.valid = true;
     return YACRD_OK;
 }
 
 int report_args(yacrd_engine *e, yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats)
 {
     if (!e || !out || !reads) return fail(YACRD_EINVAL, "null argument");
+    e->resident.valid = false;
     std::memset(out, 0, sizeof(*out));
     std::memset(reads, 0, sizeof(*reads));
     if (stats) std::memset(stats, 0, sizeof(*stats));

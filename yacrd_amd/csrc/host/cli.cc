@@ -163,6 +163,7 @@ int main(int argc, char **argv)
     yacrd_badparts_view bp{};
     yacrd_csr_view view{};
     yacrd_reads dev_reads{};
+    bool table_resident = false; // this invocation's input went through a one-engine device ingest: its table lies in engines[0]'s HBM
     yacrd_text text{}; // a compressed input, inflated (empty otherwise); lives as long as what was parsed from it
 
     // src/main.rs:43-60: a .yacrd input bypasses detection (FromReport), anything else is overlaps
@@ -197,6 +198,7 @@ int main(int argc, char **argv)
                              rct == 0 ? " (inflated)" : "", is.text_ms, is.parse_ms, is.build_ms, is.d2h_ms);
         }
         if (dev_rep == YACRD_OK) {
+            table_resident = true;
             bp.n_reads = view.n_reads = dev_reads.n_reads;
             bp.name_off = view.name_off = dev_reads.name_off;
             bp.names = view.names = dev_reads.names;
@@ -256,6 +258,7 @@ int main(int argc, char **argv)
         }
         if (dev_parse == YACRD_OK) {
             if (std::getenv("YACRD_CLI_TIMING")) std::fprintf(stderr, "[info] device parser: %zu engine(s)\n", engines.size());
+            table_resident = engines.size() == 1;
             view.n_reads = dev_reads.n_reads;
             view.name_off = dev_reads.name_off;
             view.names = dev_reads.names;
@@ -294,8 +297,35 @@ int main(int argc, char **argv)
 
     stage("detect");
     // src/main.rs:62-84: the report, one line per read
-    if (yacrd_report_write(output.c_str(), &view, bp.bad_offsets, bp.bad_regions, bp.read_type))
-        die(yacrd_host_last_error());
+    // The device formats it (yacrd_engine_write_report): from the table the ingest left in HBM when this invocation's input
+    // went through a one-engine device ingest, else from the host arrays, uploaded to engines[0].  Whatever that writer does
+    // not take — a type beyond 2, an output that is no regular file or cannot be created — comes back with nothing written
+    // and takes the host writer below, which owns the messages.  (It leaves the parser's mirror alone: an edit_overlaps
+    // below may still start from it.)  YACRD_NO_DEVICE_REPORT_WRITER=1: the host writer (A/B).  The device writer is the
+    // default because DESIGN 7e's measured table has its slowest warm run ahead of the host writer's fastest at 5 M reads.
+    int dev_write = YACRD_EFALLBACK;
+    {
+        const char *no_rw = std::getenv("YACRD_NO_DEVICE_REPORT_WRITER");
+        if (!(no_rw && *no_rw == '1')) {
+            const yacrd_report_table rt = {view.n_reads, view.name_off, view.names, view.lengths, bp.bad_offsets, bp.bad_regions, bp.read_type};
+            yacrd_report_write_stats ws{};
+            dev_write = yacrd_engine_write_report(engines[0], table_resident ? nullptr : &rt, output.c_str(), &ws);
+            if (dev_write == YACRD_ENOMEM) {
+                std::fprintf(stderr, "[INFO] device report writer: %s; falling back to the host writer\n", yacrd_last_error());
+                for (yacrd_engine *en : engines) (void)yacrd_engine_trim(en);
+                dev_write = YACRD_EFALLBACK;
+            }
+            if (dev_write != YACRD_OK && dev_write != YACRD_EFALLBACK) die(yacrd_last_error());
+            if (dev_write == YACRD_OK && timing)
+                std::fprintf(stderr, "[info] device report writer: %llu reads, %llu regions, %llu bytes, %s, upload %.1f ms, kernels %.1f ms, out %.1f ms\n",
+                             (unsigned long long)ws.n_reads, (unsigned long long)ws.n_regions, (unsigned long long)ws.text_bytes,
+                             ws.resident ? "resident table" : "table uploaded", ws.up_ms, ws.kernel_ms, ws.out_ms);
+        }
+    }
+    if (dev_write != YACRD_OK) {
+        if (timing) std::fprintf(stderr, "[info] host report writer\n");
+        if (yacrd_report_write(output.c_str(), &view, bp.bad_offsets, bp.bad_regions, bp.read_type)) die(yacrd_host_last_error());
+    }
     stage("report");
 
     // src/main.rs:86-118: optional post operation

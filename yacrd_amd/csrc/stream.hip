@@ -326,6 +326,7 @@ int yacrd_stream_finish(yacrd_stream *s, const uint32_t *handle_map, uint64_t n_
                         double not_coverage, yacrd_result *out)
 {
     if (!s || !out) return fail(YACRD_EINVAL, "null argument");
+    s->e->resident.valid = false; // (first: in_len is rewritten below, before the last thing that can fail)
     std::memset(out, 0, sizeof(*out));
     if (n_reads && !lengths) return fail(YACRD_EINVAL, "null lengths");
     if (n_reads >= 0xFFFFFFFFull) return fail(YACRD_EINVAL, "n_reads must be < 2^32 - 1");
@@ -565,6 +566,7 @@ int yacrd_stream_group_finish(yacrd_stream_group *g, const uint32_t *handle_map,
 {
     if (!g || !out) return fail(YACRD_EINVAL, "null argument");
     const uint32_t N = (uint32_t)g->st.size();
+    for (yacrd_stream *s : g->st) s->e->resident.valid = false;
     if (N == 1) {
         g->owned[0] = n_reads;
         return yacrd_stream_finish(g->st[0], handle_map, n_handles, lengths, n_reads, coverage, not_coverage, out);

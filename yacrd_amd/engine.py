@@ -44,7 +44,7 @@ EXPORTED_SYMBOLS = [
     "yacrd_stream_finish", "yacrd_stream_last_stats", "yacrd_stream_reset", "yacrd_stream_close",
     "yacrd_engine_ingest_paf", "yacrd_engine_ingest_overlaps", "yacrd_engine_ingest_overlaps_mem", "yacrd_engines_ingest_overlaps",
     "yacrd_engines_ingest_overlaps_mem", "yacrd_reads_free", "yacrd_engine_trim",
-    "yacrd_engine_ingest_report", "yacrd_engine_ingest_report_mem",
+    "yacrd_engine_ingest_report", "yacrd_engine_ingest_report_mem", "yacrd_engine_write_report", "yacrd_engine_write_report_mem",
     "yacrd_engine_edit_overlaps", "yacrd_engine_edit_overlaps_mem", "yacrd_edit_text_free",
     "yacrd_engine_edit_overlaps_gzip_mem", "yacrd_engine_edit_overlaps_gzip_file",
     "yacrd_engine_gzip_mem", "yacrd_gzip_writer_open", "yacrd_gzip_writer_write", "yacrd_gzip_writer_sink", "yacrd_gzip_writer_close",
@@ -69,6 +69,16 @@ class _Reads(ctypes.Structure):
     _fields_ = [("n_reads", ctypes.c_uint64), ("n_records", ctypes.c_uint64),
                 ("lengths", ctypes.POINTER(ctypes.c_uint32)), ("name_off", ctypes.POINTER(ctypes.c_uint64)),
                 ("names", ctypes.POINTER(ctypes.c_char))]
+
+
+class _ReportTable(ctypes.Structure):  # yacrd_report_table
+    _fields_ = [("n_reads", ctypes.c_uint64)] + \
+               [(n, ctypes.c_void_p) for n in ("name_off", "names", "lengths", "bad_offsets", "bad_regions", "read_type")]
+
+
+class _ReportWriteStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("n_reads", "n_regions", "text_bytes")] + \
+               [(n, ctypes.c_float) for n in ("up_ms", "kernel_ms", "out_ms")] + [("resident", ctypes.c_uint32)]
 
 
 class _IngestStats(ctypes.Structure):
@@ -282,6 +292,10 @@ def load_library():
                                                ctypes.POINTER(_Reads), ctypes.POINTER(_IngestStats)]
     lib.yacrd_engine_ingest_report_mem.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_double,
                                                    ctypes.POINTER(_Result), ctypes.POINTER(_Reads), ctypes.POINTER(_IngestStats)]
+    lib.yacrd_engine_write_report.argtypes = [ctypes.c_void_p, ctypes.POINTER(_ReportTable), ctypes.c_char_p,
+                                              ctypes.POINTER(_ReportWriteStats)]
+    lib.yacrd_engine_write_report_mem.argtypes = [ctypes.c_void_p, ctypes.POINTER(_ReportTable), ctypes.POINTER(ctypes.c_void_p),
+                                                  ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_ReportWriteStats)]
     lib.yacrd_debug_sort_pairs.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]
     lib.yacrd_engine_trim.argtypes = [ctypes.c_void_p]
     lib.yacrd_engine_edit_overlaps.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
@@ -563,6 +577,64 @@ class Engine:
         stats = {n: getattr(st, n) for n, _ in _IngestStats._fields_}
         self._lib.yacrd_reads_free(ctypes.byref(rd))
         return _take(self._lib, res), names, lengths, stats
+
+    def _report_table(self, names, lengths, result):
+        """(names, lengths, Result) -> a pointer to a yacrd_report_table (None: the resident form) and what keeps its memory
+        alive; names: str or bytes, one per read."""
+        if names is None and lengths is None and result is None:
+            return None, None
+        if names is None or lengths is None or result is None:
+            raise ValueError("names, lengths and result: all three, or none for the table the last ingest left on the device")
+        blobs = [n if isinstance(n, bytes) else n.encode("utf-8", "surrogateescape") for n in names]
+        R = len(blobs)
+        off = np.zeros(R + 1, np.uint64)
+        if blobs:
+            off[1:] = np.cumsum([len(b) for b in blobs], dtype=np.uint64)
+        blob = ctypes.create_string_buffer(b"".join(blobs), int(off[-1]) + 1)
+        lens = np.ascontiguousarray(lengths, dtype=np.uint32)
+        bo = np.ascontiguousarray(result.bad_offsets, dtype=np.uint64)
+        br = np.ascontiguousarray(result.bad_regions, dtype=np.uint32).reshape(-1)
+        rt = np.ascontiguousarray(result.read_type, dtype=np.uint8)
+        if lens.shape != (R,) or bo.shape != (R + 1,) or rt.shape != (R,) or (R and br.size != 2 * int(bo[-1])):
+            raise ValueError("the report table's arrays do not fit one another")
+        if br.size == 0:
+            br = np.zeros(2, np.uint32)
+        if R == 0:
+            lens, rt = np.zeros(1, np.uint32), np.zeros(1, np.uint8)
+        t = _ReportTable(R, off.ctypes.data, ctypes.addressof(blob), lens.ctypes.data, bo.ctypes.data, br.ctypes.data, rt.ctypes.data)
+        return ctypes.byref(t), (t, off, blob, lens, bo, br, rt)
+
+    def _report_written(self, rc, st):
+        if rc == E_FALLBACK:
+            raise NeedsHostParser(self._lib.yacrd_last_error().decode())
+        _check(self._lib, rc)
+        self.report_write_stats = {n: getattr(st, n) for n, _ in _ReportWriteStats._fields_}
+        return self.report_write_stats
+
+    def write_report(self, out_path, names=None, lengths=None, result=None):
+        """yacrd_engine_write_report: the .yacrd report of (names, lengths, result) — result: anything with bad_offsets,
+        bad_regions and read_type, such as a Result — formatted on the GPU into out_path, byte for byte the host writer's.
+        All three None: the RESIDENT form, from the table this engine's last ingest_paf / ingest_text / ingest_report left in
+        HBM.  Returns the stats (also self.report_write_stats).  Raises NeedsHostParser, with nothing written, when the table
+        or the output is the host writer's (host: yacrd_report_write) or no ingest's table is resident."""
+        t, keep = self._report_table(names, lengths, result)
+        st = _ReportWriteStats()
+        rc = self._lib.yacrd_engine_write_report(self._h, t, os.fsencode(out_path), ctypes.byref(st))
+        del keep
+        return self._report_written(rc, st)
+
+    def report_text(self, names=None, lengths=None, result=None):
+        """yacrd_engine_write_report_mem: the same report as bytes; the stats are in self.report_write_stats."""
+        t, keep = self._report_table(names, lengths, result)
+        st = _ReportWriteStats()
+        out, n_out = ctypes.c_void_p(), ctypes.c_uint64()
+        rc = self._lib.yacrd_engine_write_report_mem(self._h, t, ctypes.byref(out), ctypes.byref(n_out), ctypes.byref(st))
+        del keep
+        self._report_written(rc, st)
+        try:
+            return ctypes.string_at(out.value, int(n_out.value)) if n_out.value else b""
+        finally:
+            self._lib.yacrd_edit_text_free(out)
 
     def debug_sort_pairs(self, keys, vals, key_bound):
         """yacrd_debug_sort_pairs (tests): (u64 key, u32 value) pairs sorted by key on the device, stable; returns copies."""
