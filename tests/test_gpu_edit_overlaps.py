@@ -52,6 +52,37 @@ def test_reference_unit_vectors_by_file_name(engine, tmp_path):
         assert out.read_text() == text and st["n_kept"] == 2 and st["kept_bytes"] == len(text)
 
 
+_PIECE = 4 << 20  # what one trip home of the kept bytes carries (csrc/gpu_edit.hip: kOutPiece)
+
+
+def _lines_of_64(fmt, total):
+    """`total` bytes of identical 64-byte lines, the last one's final column a character longer or shorter where needed"""
+    head = b"a\t12000\t20\t4500\t-\tb\t10000\t5500\t10000\t4500\t4500\t" if fmt == 1 else b"a b 0.1 2 0 100 450 1000 0 550 900 "
+    line = head + b"7" * (63 - len(head)) + b"\n"
+    n_lines = (total + 32) // 64
+    last = head + b"7" * (63 - len(head) + total - 64 * n_lines) + b"\n"
+    text = line * (n_lines - 1) + last
+    assert len(line) == 64 and len(text) == total and abs(len(last) - 64) <= 1
+    return text, n_lines
+
+
+@pytest.mark.parametrize("fmt", [1, 2], ids=["paf", "m4"])
+@pytest.mark.parametrize("total", [_PIECE - 1, _PIECE, _PIECE + 1, 2 * _PIECE + 1])
+def test_piece_borders_of_the_way_home(engine, tmp_path, fmt, total):
+    """everything is kept (filter, no read is bad): the kept bytes end one byte before, on and one byte behind a piece
+    border of the way home, and behind two pieces — out of memory, into a file and through the encoder"""
+    text, n_lines = _lines_of_64(fmt, total)
+    assert engine.edit_overlaps_text(OP_FILTER, text, [], [], fmt) == text
+    assert engine.edit_stats["n_kept"] == n_lines and engine.edit_stats["kept_bytes"] == total
+    src, out = tmp_path / ("in" + (".paf" if fmt == 1 else ".m4")), tmp_path / "out.txt"
+    src.write_bytes(text)
+    st = engine.edit_overlaps(OP_FILTER, str(src), str(out), [], [])
+    assert out.read_bytes() == text and st["kept_bytes"] == total and st["n_kept"] == n_lines
+    assert gzip.decompress(engine.edit_overlaps_gzip(OP_FILTER, text, [], [], fmt)) == text
+    assert engine.gzip_stats["in_bytes"] == total
+    assert sorted(os.listdir(tmp_path)) == sorted([src.name, out.name])
+
+
 def _streams_equal(a, b):
     with open(a, "rb") as fa, open(b, "rb") as fb:
         while True:

@@ -60,6 +60,47 @@ def test_golden_file_resident_and_table_forms(engine, golden_dir, tmp_path):
     assert engine.report_text() == want  # (the table form leaves the resident table alone)
 
 
+def test_one_engine_through_every_text_path_and_trim(golden_dir, tmp_path):
+    """parser, editor (from the mirror), encoder, report reader and report writer on ONE engine, trim, the same again: the
+    engine's registry of their buffers is walked with every slot live, by trim and by the engine's end"""
+    paf, rep = os.path.join(golden_dir, "reads.paf"), os.path.join(golden_dir, "truth.yacrd")
+
+    def flat(res, names, lengths):
+        return [np.array(res.bad_offsets), np.array(res.bad_regions), np.array(res.read_type), list(names), np.array(lengths)]
+
+    def every_path(e, tag):
+        res, names, lengths, _ = e.ingest_paf(paf, 4, 0.4)
+        out = tmp_path / (tag + ".paf")
+        st = e.edit_overlaps(1, paf, str(out), names, res.read_type)
+        assert st["mirror_reused"] == 1
+        kept = out.read_bytes()
+        blob = e.gzip(kept)
+        res2, names2, lengths2, _ = e.ingest_report(rep, 0.4)
+        dev = tmp_path / (tag + ".yacrd")
+        assert e.write_report(str(dev))["resident"] == 1
+        table = e.report_text([n.encode() for n in names], lengths, res)
+        return flat(res, names, lengths) + [kept, blob] + flat(res2, names2, lengths2) + [dev.read_bytes(), table]
+
+    with yacrd_amd.Engine(device_id=0) as e:
+        first = every_path(e, "first")
+        e.trim()
+        again = every_path(e, "again")
+        assert len(first) == len(again) == 14
+        for a, b in zip(first, again):
+            assert np.array_equal(a, b) if isinstance(a, np.ndarray) else a == b
+        kept, blob = first[5], first[6]
+        assert 0 < len(kept) < os.path.getsize(paf) and len(blob) > 28 and len(first[12]) > 5000 and len(first[13]) > 5000
+        # an open gzip writer holds the encoder's buffers: trim leaves them alone, and the writer ends with the right bytes
+        gz = tmp_path / "kept.gz"
+        w = e.gzip_writer(str(gz))
+        w.write(kept[:len(kept) // 2])
+        e.trim()
+        w.write(kept[len(kept) // 2:])
+        w.close()
+        assert gz.read_bytes() == blob
+        assert not [n for n in os.listdir(tmp_path) if ".gz." in n or ".yacrd." in n or ".paf." in n]
+
+
 def test_fuzz_tables_equal_the_host_writer(engine, tmp_path):
     for seed in range(300):
         t = wc.make_table(seed, tmp_path)

@@ -27,6 +27,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "bgzf_sizes.h" // kBlock, kSlot, kEofBytes
+
 #if defined(__HIPCC__)
 #define YD_FN __device__ __forceinline__
 #define YD_PHASE(tid)                                                                                                  \
@@ -48,15 +50,13 @@ typedef uint16_t u16;
 typedef uint32_t u32;
 typedef uint64_t u64;
 
-constexpr u32 kBlock = 65280;  // bytes of text per member (bgzip's 0xff00)
-constexpr u32 kSlot = 65536;   // a member never exceeds this
 constexpr u32 kT = 256;        // threads of the team
 constexpr u32 kRange = kBlock / kT; // positions whose tokens a thread counts and emits
 constexpr u32 kSub = 1024;     // positions per matching step
 constexpr u32 kHashBits = 12;
 constexpr u32 kMinMatch = 4, kMaxMatch = 257, kMaxDist = 32768;
 constexpr u32 kLit = 286, kDist = 30, kCl = 19;
-constexpr u32 kHdr = 18, kTrailer = 8, kEofBytes = 28;
+constexpr u32 kHdr = 18, kTrailer = 8;
 static_assert(kRange * kT == kBlock, "ranges tile the block");
 static_assert(kBlock + 5 + kHdr + kTrailer <= kSlot, "a stored block fits a member");
 

@@ -1281,18 +1281,11 @@ int fetch_result(yacrd_engine *e, yacrd_result *out)
     const size_t o_reg = (b_off + 63) & ~(size_t)63, o_typ = (o_reg + b_reg + 63) & ~(size_t)63;
     const size_t need = o_typ + b_typ + 64;
     bool staged = need <= ((size_t)1 << 30);
-    if (staged && need > e->h_out_cap) {
-        if (e->h_out) (void)hipHostFree(e->h_out);
-        e->h_out = nullptr;
-        e->h_out_cap = 0;
-        const size_t want = need + need / 4;
-        if (hipHostMalloc(&e->h_out, want) == hipSuccess) e->h_out_cap = want;
-        else {
-            (void)hipGetLastError();
-            staged = false;
-        }
+    if (staged && need > e->h_out.cap && e->h_out.reserve(need + need / 4) != hipSuccess) {
+        (void)hipGetLastError();
+        staged = false;
     }
-    char *h = (char *)e->h_out;
+    char *h = e->h_out.as<char>();
     void *t_off = staged ? (void *)h : (void *)out->bad_offsets;
     void *t_reg = staged ? (void *)(h + o_reg) : (void *)out->bad_regions;
     void *t_typ = staged ? (void *)(h + o_typ) : (void *)out->read_type;
@@ -1380,6 +1373,19 @@ int yacrd_engine_create(const yacrd_engine_cfg *cfg, yacrd_engine **out)
     return YACRD_OK;
 }
 
+// the text paths' buffers go back to the device (their objects stay); the batch path's and the pinned arena stay
+int yacrd_engine_trim(yacrd_engine *e)
+{
+    if (!e) return fail(YACRD_EINVAL, "engine is null");
+    if (e->pending.active || e->host_pending) return fail(YACRD_EINVAL, "the engine has a submitted batch pending");
+    DeviceGuard guard(e->device);
+    e->mirror.valid = false;
+    e->resident.valid = false;
+    for (int k = 0; k < yacrd_engine::kSlots; k++)
+        if (e->scratch[k].p && !(k == yacrd_engine::kGzip && e->gzip_busy)) e->scratch[k].release(e->scratch[k].p);
+    return YACRD_OK;
+}
+
 void yacrd_engine_destroy(yacrd_engine *e)
 {
     if (!e) return;
@@ -1392,13 +1398,10 @@ void yacrd_engine_destroy(yacrd_engine *e)
                       &e->bad_offsets, &e->bad_regions, &e->read_type, &e->dlist};
     for (DevBuf *b : bufs) b->release();
     if (e->h_ctr) (void)hipHostFree(e->h_ctr);
-    if (e->h_out) (void)hipHostFree(e->h_out);
-    if (e->paf_arena) (void)hipHostFree(e->paf_arena);
-    if (e->paf_scratch && e->paf_scratch_free) e->paf_scratch_free(e->paf_scratch);
-    if (e->edit_scratch && e->edit_scratch_free) e->edit_scratch_free(e->edit_scratch);
-    if (e->gzip_scratch && e->gzip_scratch_free) e->gzip_scratch_free(e->gzip_scratch);
-    if (e->report_scratch && e->report_scratch_free) e->report_scratch_free(e->report_scratch);
-    if (e->report_write_scratch && e->report_write_scratch_free) e->report_write_scratch_free(e->report_write_scratch);
+    e->h_out.release();
+    e->paf_arena.release();
+    for (auto &s : e->scratch)
+        if (s.p) s.destroy(s.p);
     for (int b = 0; b < yacrd_engine::kBounce; b++) {
         if (e->bounce[b]) (void)hipHostFree(e->bounce[b]);
         if (e->bounce_ev[b]) (void)hipEventDestroy(e->bounce_ev[b]);

@@ -1,13 +1,19 @@
-// engine_internal.h — host-side internals shared by the translation units of libyacrd_hip.so
-// (engine.hip: batch runs; stream.hip: streaming ingest + CSR build on the GPU).
+// engine_internal.h — host-side internals shared by the translation units of libyacrd_hip.so: engine.hip (batch runs, the
+// engine's life), stream.hip (streaming ingest + CSR build on the GPU) and the text paths gpu_paf.hip, gpu_edit.hip,
+// gpu_deflate.hip, gpu_report.hip, gpu_report_write.hip.  The error slot, device and pinned buffers (DevBuf, PinBuf), the clocks, the
+// owners of a call's events and streams, the engine itself with its registry of the text paths' scratch, the run context.
 #pragma once
 #include "../../include/yacrd_engine_debug.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <chrono>
+#include <new>
 #include <string>
+#include <vector>
 
+#include "bgzf_sizes.h" // (what a batch of GzDevice is counted in, below)
 #include "device_common.h"
 
 namespace yke {
@@ -59,6 +65,77 @@ struct DevBuf {
     }
 };
 
+// pinned host memory, grow-only: exactly the bytes asked for (pinning costs by the byte), nothing after a failed reserve
+struct PinBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    hipError_t reserve(size_t bytes)
+    {
+        if (bytes <= cap) return hipSuccess;
+        release();
+        const hipError_t e = hipHostMalloc(&p, bytes);
+        if (e == hipSuccess) cap = bytes;
+        else p = nullptr;
+        return e;
+    }
+    void release()
+    {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    template <class T>
+    T *as() const
+    {
+        return reinterpret_cast<T *>(p);
+    }
+};
+
+// the events / streams of one call: what was created goes when the holder does
+struct Events {
+    std::vector<hipEvent_t> v;
+    Events() = default;
+    Events(const Events &) = delete;
+    Events &operator=(const Events &) = delete;
+    // n more events; false: one could not be created
+    bool add(size_t n, unsigned flags = hipEventDefault)
+    {
+        for (; n; n--) {
+            hipEvent_t x = nullptr;
+            if (hipEventCreateWithFlags(&x, flags) != hipSuccess) return false;
+            v.push_back(x);
+        }
+        return true;
+    }
+    hipEvent_t operator[](size_t i) const { return v[i]; }
+    ~Events()
+    {
+        for (hipEvent_t x : v) (void)hipEventDestroy(x);
+    }
+};
+struct Streams {
+    std::vector<hipStream_t> v;
+    Streams() = default;
+    Streams(const Streams &) = delete;
+    Streams &operator=(const Streams &) = delete;
+    bool add(size_t n)
+    {
+        for (; n; n--) {
+            hipStream_t x = nullptr;
+            if (hipStreamCreateWithFlags(&x, hipStreamNonBlocking) != hipSuccess) return false;
+            v.push_back(x);
+        }
+        return true;
+    }
+    hipStream_t operator[](size_t i) const { return v[i]; }
+    void clear()
+    {
+        for (hipStream_t x : v) (void)hipStreamDestroy(x);
+        v.clear();
+    }
+    ~Streams() { clear(); }
+};
+
 enum { EV_START = 0, EV_PLAN, EV_S0, EV_SMALL, EV_MED, EV_GEN, EV_COMPACT, EV_X0, EV_X1, EV_COUNT };
 
 struct DeviceGuard {
@@ -74,6 +151,11 @@ struct DeviceGuard {
         if (prev >= 0) (void)hipSetDevice(prev);
     }
 };
+
+inline double now_ms() // host wall clock
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
 
 inline float ev_ms(hipEvent_t a, hipEvent_t b)
 {
@@ -201,16 +283,10 @@ struct yacrd_engine {
     void *bounce[kBounce] = {};
     hipEvent_t bounce_ev[kBounce] = {};
     bool bounce_busy[kBounce] = {};
-    // pinned staging for the results on their way home (fetch_result), grow-only
-    void *h_out = nullptr;
-    size_t h_out_cap = 0;
+    yke::PinBuf h_out; // pinned staging for the results on their way home (fetch_result)
     // a batch submitted from host buffers (yacrd_engine_submit): collect() fetches the result
     bool host_pending = false;
-    // pinned buffers the PAF text passes through on its way to HBM (gpu_paf.hip), grow-only
-    void *paf_arena = nullptr;
-    size_t paf_arena_cap = 0;
-    void *paf_scratch = nullptr;                 // gpu_paf.hip's device buffers (its type), kept between calls
-    void (*paf_scratch_free)(void *) = nullptr;
+    yke::PinBuf paf_arena; // what text passes through on its way to HBM (gpu_text.h: move_text)
     // the mirror a device parse of a whole FILE left in HBM (gpu_paf.hip: still inside its scratch), and which file it was:
     // the overlap editor (gpu_edit.hip) edits from it when it is handed the same file, instead of moving the text again
     struct {
@@ -232,23 +308,30 @@ struct yacrd_engine {
         uint64_t n_reads = 0;
         bool valid = false;
     } resident;
-    void *edit_scratch = nullptr;                // gpu_edit.hip's device and pinned buffers (its type), kept between calls
-    void (*edit_scratch_free)(void *) = nullptr; // (destroy)
-    void (*edit_scratch_release)(void *) = nullptr; // (yacrd_engine_trim)
-    void *gzip_scratch = nullptr;                // gpu_deflate.hip's device and pinned buffers (its type), kept between calls
-    void (*gzip_scratch_free)(void *) = nullptr;
-    void (*gzip_scratch_release)(void *) = nullptr;
-    bool gzip_busy = false;                      // a yacrd_gzip_writer holds them
-    void *report_scratch = nullptr;              // gpu_report.hip's device buffers (its type), kept between calls
-    void (*report_scratch_free)(void *) = nullptr;
-    void (*report_scratch_release)(void *) = nullptr;
-    void *report_write_scratch = nullptr;        // gpu_report_write.hip's device and pinned buffers (its type), kept between calls
-    void (*report_write_scratch_free)(void *) = nullptr;
-    void (*report_write_scratch_release)(void *) = nullptr;
+    // what the text paths keep between calls (their own types: device and pinned buffers, grow-only), made on first use by
+    // yke::scratch_of; yacrd_engine_trim releases their buffers, yacrd_engine_destroy deletes them
+    enum Slot { kPaf = 0, kEdit, kGzip, kReport, kReportWrite, kSlots };
+    struct {
+        void *p = nullptr;
+        void (*destroy)(void *) = nullptr;
+        void (*release)(void *) = nullptr;
+    } scratch[kSlots];
+    bool gzip_busy = false; // a yacrd_gzip_writer or an edit to gzip holds the kGzip slot: trim leaves it alone
 };
 
 
 namespace yke {
+// the engine's scratch of type T, in the slot T names as kScratchSlot (nullptr: no host memory)
+template <class T>
+T *scratch_of(yacrd_engine *e)
+{
+    auto &s = e->scratch[T::kScratchSlot];
+    if (!s.p && (s.p = new (std::nothrow) T())) {
+        s.destroy = [](void *p) { delete static_cast<T *>(p); };
+        s.release = [](void *p) { static_cast<T *>(p)->release(); };
+    }
+    return static_cast<T *>(s.p);
+}
 // the whole launch sequence over a CSR resident in HBM (engine.hip)
 int run_on_device(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u32 *d_len,
                   uint64_t n_reads64, uint64_t n_iv, uint32_t cov, double not_cov, bool defer = false);
@@ -272,7 +355,7 @@ int h2d(yacrd_engine *e, void *dst, const void *src, size_t bytes);
 // text that lies in HBM -> BGZF members in HBM, batch by batch (gpu_deflate.hip; used by gpu_edit.hip)
 struct GzDevice {
     const unsigned char *out[2] = {nullptr, nullptr}; // a batch's members, end to end; batches alternate between the two
-    u64 max_blocks = 0;                               // blocks of 65 280 bytes a batch may hold
+    u64 max_blocks = 0;                               // blocks of ydf::kBlock bytes a batch may hold
 };
 int gzip_device_open(yacrd_engine *e, u64 max_blocks, GzDevice *g);
 int gzip_device_encode(yacrd_engine *e, const GzDevice &g, hipStream_t st, const unsigned char *d_text, u64 n, bool last, int which,

@@ -11,6 +11,8 @@
 #include "engine_internal.h"
 #include "gpu_text.h"
 #include "deflate_block.h"
+#include "host/beside_file.h"
+#include "host/segment_pump.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -77,27 +79,16 @@ constexpr u64 kDefaultSegBlocks = 512;
 constexpr u64 kMaxSegBlocks = 16384; // 1 GiB of slots
 
 struct GzScratch { // stays with the engine (grow-only); goes with yacrd_engine_trim / destroy
+    static constexpr yacrd_engine::Slot kScratchSlot = yacrd_engine::kGzip;
     DevBuf text, slots, out, out2, sizes, off, part, ctl; // (out2: the overlap editor's second batch of members, gzip_device_open)
-    void *pin = nullptr; // n_buffers input segments, one output segment, the control words
-    size_t pin_cap = 0;
+    PinBuf pin; // n_buffers input segments, one output segment, the control words
     void release()
     {
         for (DevBuf *b : {&text, &slots, &out, &out2, &sizes, &off, &part, &ctl}) b->release();
-        if (pin) (void)hipHostFree(pin);
-        pin = nullptr, pin_cap = 0;
+        pin.release();
     }
     ~GzScratch() { release(); }
 };
-GzScratch *gzip_scratch_of(yacrd_engine *e)
-{
-    if (!e->gzip_scratch) {
-        e->gzip_scratch = new (std::nothrow) GzScratch();
-        e->gzip_scratch_free = [](void *p) { delete static_cast<GzScratch *>(p); };
-        e->gzip_scratch_release = [](void *p) { static_cast<GzScratch *>(p)->release(); };
-    }
-    return static_cast<GzScratch *>(e->gzip_scratch);
-}
-
 inline u64 out_bound(u64 blocks) { return blocks * (u64)ydf::kSlot + ydf::kEofBytes; }
 
 } // namespace
@@ -126,7 +117,7 @@ static int gzip_on_device(yacrd_engine *e, GzScratch &S, hipStream_t st, const u
 int gzip_device_open(yacrd_engine *e, u64 max_blocks, GzDevice *g)
 {
     if (e->gzip_busy) return fail(YACRD_EINVAL, "the engine already has a gzip writer");
-    GzScratch *S = gzip_scratch_of(e);
+    GzScratch *S = scratch_of<GzScratch>(e);
     if (!S) return fail(YACRD_ENOMEM, "host allocation failed");
     const u64 blocks = std::min(std::max<u64>(max_blocks, 1), kMaxSegBlocks);
     HIP_TRY(S->slots.reserve((size_t)(blocks * ydf::kSlot)));
@@ -149,7 +140,7 @@ int gzip_device_open(yacrd_engine *e, u64 max_blocks, GzDevice *g)
 int gzip_device_encode(yacrd_engine *e, const GzDevice &g, hipStream_t st, const unsigned char *d_text, u64 n, bool last, int which,
                        hipEvent_t k0, hipEvent_t k1, volatile u64 *h_bytes, volatile u64 *h_stored)
 {
-    GzScratch &S = *static_cast<GzScratch *>(e->gzip_scratch);
+    GzScratch &S = *scratch_of<GzScratch>(e); // (gzip_device_open made it)
     const u64 nb = (n + ydf::kBlock - 1) / ydf::kBlock;
     if (nb > g.max_blocks) return fail(YACRD_EINTERNAL, "device deflate: a batch beyond the blocks its buffers were taken for");
     HIP_TRY(hipEventRecord(k0, st));
@@ -177,34 +168,10 @@ struct yacrd_gzip_writer {
     u64 fill = 0;     // bytes in it
     bool in_flight = false, flight_last = false;
     bool failed = false;
-    // where the bytes go
-    int fd = -1;
-    std::string path, tmp;
-    char *mem = nullptr;
-    u64 mem_cap = 0, mem_at = 0;
+    yseg::BesideFile file; // where the bytes go: a file beside its place (the writer), or growing memory (yacrd_engine_gzip_mem)
+    yseg::Sink sink;
     yacrd_gzip_stats st = {};
 
-    bool put(const char *p, size_t k)
-    {
-        if (fd >= 0) {
-            for (size_t done = 0; done < k;) {
-                const ssize_t w = ::write(fd, p + done, k - done);
-                if (w < 0 && errno == EINTR) continue;
-                if (w <= 0) return false;
-                done += (size_t)w;
-            }
-            return true;
-        }
-        if (mem_at + k > mem_cap) {
-            const u64 want = std::max<u64>(mem_at + k, mem_cap + mem_cap / 2 + 4096);
-            char *q = (char *)std::realloc(mem, (size_t)want);
-            if (!q) return false;
-            mem = q, mem_cap = want;
-        }
-        std::memcpy(mem + mem_at, p, k);
-        mem_at += k;
-        return true;
-    }
     // the segment in flight: wait for it, fetch its members, append them
     int collect()
     {
@@ -218,7 +185,7 @@ struct yacrd_gzip_writer {
         const double t0 = now_ms();
         if (bytes) HIP_TRY(hipMemcpy(pin_out, S->out.p, (size_t)bytes, hipMemcpyDeviceToHost));
         const double t1 = now_ms();
-        if (!put(pin_out, (size_t)bytes)) return fail(YACRD_EINVAL, "Error during writing of the output file");
+        if (!sink.put(pin_out, (size_t)bytes)) return fail(YACRD_EINVAL, "Error during writing of the output file");
         st.d2h_ms += (float)(t1 - t0), st.write_ms += (float)(now_ms() - t1);
         st.out_bytes += bytes;
         st.n_stored = h_ctl[1];
@@ -269,10 +236,9 @@ struct yacrd_gzip_writer {
             (void)hipGetLastError();
             e->gzip_busy = false;
         }
-        if (fd >= 0) ::close(fd);
-        fd = -1;
-        std::free(mem);
-        mem = nullptr;
+        file.drop();
+        std::free(sink.mem);
+        sink.mem = nullptr;
     }
 };
 
@@ -286,7 +252,7 @@ int writer_setup(yacrd_engine *e, u64 segment_bytes, u32 n_buffers, yacrd_gzip_w
     u64 blocks = segment_bytes ? (segment_bytes + ydf::kBlock - 1) / ydf::kBlock : kDefaultSegBlocks;
     blocks = std::min(std::max<u64>(blocks, 1), kMaxSegBlocks);
     n_buffers = 2; // (one segment is in flight while the next is filled: more buffers would only pin more memory)
-    GzScratch *S = gzip_scratch_of(e);
+    GzScratch *S = scratch_of<GzScratch>(e);
     if (!S) return fail(YACRD_ENOMEM, "host allocation failed");
     e->gzip_busy = true, w->e = e; // (from here on the caller drops the writer when something fails)
     const u64 seg = blocks * ydf::kBlock;
@@ -298,20 +264,14 @@ int writer_setup(yacrd_engine *e, u64 segment_bytes, u32 n_buffers, yacrd_gzip_w
     HIP_TRY(S->ctl.reserve(64));
     HIP_TRY(S->part.reserve((size_t)(blocks + 2) * sizeof(u64))); // (the scan's partial sums: at most one per element; nothing is allocated after open)
     const size_t pin_need = (size_t)n_buffers * seg + (size_t)out_bound(blocks) + 64;
-    if (S->pin_cap < pin_need) {
-        if (S->pin) (void)hipHostFree(S->pin);
-        S->pin = nullptr, S->pin_cap = 0;
-        if (hipHostMalloc(&S->pin, pin_need) != hipSuccess) {
-            S->pin = nullptr;
-            (void)hipGetLastError();
-            return fail(YACRD_ENOMEM, "device deflate: no pinned memory");
-        }
-        S->pin_cap = pin_need;
+    if (S->pin.reserve(pin_need) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(YACRD_ENOMEM, "device deflate: no pinned memory");
     }
     HIP_TRY(hipMemsetAsync(S->ctl.p, 0, 64, e->stream));
     for (hipEvent_t &x : w->ev) HIP_TRY(hipEventCreate(&x));
     w->S = S, w->seg_bytes = seg, w->n_buf = n_buffers;
-    w->pin_in = (char *)S->pin;
+    w->pin_in = S->pin.as<char>();
     w->pin_out = w->pin_in + (size_t)n_buffers * seg;
     w->h_ctl = reinterpret_cast<volatile u64 *>(w->pin_out + ((out_bound(blocks) + 15) & ~(u64)15));
     w->h_ctl[0] = w->h_ctl[1] = 0;
@@ -331,13 +291,12 @@ int yacrd_engine_gzip_mem(yacrd_engine *e, const char *data, uint64_t n_bytes, c
     yacrd_gzip_writer w;
     int rc = writer_setup(e, 0, 0, &w);
     if (rc == YACRD_OK) {
-        w.mem = (char *)std::malloc((size_t)(n_bytes / 2 + 4096)), w.mem_cap = w.mem ? n_bytes / 2 + 4096 : 0;
+        w.sink.mem = (char *)std::malloc((size_t)(n_bytes / 2 + 4096)), w.sink.cap = w.sink.mem ? n_bytes / 2 + 4096 : 0; // (none: the sink grows from nothing)
         rc = w.write(data, n_bytes);
         if (rc == YACRD_OK) rc = w.finish();
         if (rc == YACRD_OK) {
-            if (!w.mem) w.mem = (char *)std::malloc(1);
-            *out = w.mem, *out_bytes = w.mem_at;
-            w.mem = nullptr;
+            *out = w.sink.mem, *out_bytes = w.sink.at;
+            w.sink.mem = nullptr;
             if (stats) *stats = w.st;
         }
     }
@@ -354,15 +313,8 @@ int yacrd_gzip_writer_open(yacrd_engine *e, const char *out_path, uint64_t segme
     if (!w) return fail(YACRD_ENOMEM, "host allocation failed");
     int rc = writer_setup(e, segment_bytes, n_buffers, w);
     if (rc == YACRD_OK) {
-        w->path = out_path;
-        w->tmp = w->path + ".XXXXXX";
-        w->fd = mkstemp(&w->tmp[0]);
-        if (w->fd < 0) rc = fail(YACRD_EINVAL, std::string("cannot create a file beside ") + out_path);
-        else {
-            const mode_t um = umask(0);
-            umask(um);
-            (void)fchmod(w->fd, 0666 & ~um);
-        }
+        if (!w->file.open(out_path)) rc = fail(YACRD_EINVAL, std::string("cannot create a file beside ") + out_path);
+        w->sink.fd = w->file.fd;
     }
     if (rc != YACRD_OK) {
         if (w->e) w->drop();
@@ -401,11 +353,7 @@ int yacrd_gzip_writer_close(yacrd_gzip_writer *w, yacrd_gzip_stats *stats)
         DeviceGuard guard(w->e->device);
         rc = w->failed ? fail(YACRD_EINVAL, "the gzip writer has failed before") : w->finish();
     }
-    const int fd = w->fd;
-    w->fd = -1;
-    if (fd >= 0 && ::close(fd) != 0 && rc == YACRD_OK) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
-    if (rc == YACRD_OK && ::rename(w->tmp.c_str(), w->path.c_str()) != 0) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
-    if (rc != YACRD_OK) (void)::unlink(w->tmp.c_str());
+    if (rc == YACRD_OK && !w->file.commit()) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
     if (rc == YACRD_OK && stats) *stats = w->st;
     w->drop();
     delete w;
@@ -415,8 +363,7 @@ int yacrd_gzip_writer_close(yacrd_gzip_writer *w, yacrd_gzip_stats *stats)
 void yacrd_gzip_writer_abort(yacrd_gzip_writer *w)
 {
     if (!w) return;
-    (void)::unlink(w->tmp.c_str());
-    w->drop();
+    w->drop(); // (the file beside the output goes with it)
     delete w;
 }
 

@@ -34,6 +34,8 @@
 // those of yacrd_engine_gzip_mem on the kept bytes whatever the segments, the threads or the timing.
 #include "engine_internal.h"
 #include "gpu_text.h"
+#include "host/beside_file.h"
+#include "host/segment_pump.h"
 
 #include <condition_variable>
 #include <cstdio>
@@ -101,21 +103,6 @@ __device__ __forceinline__ u32 ed_lookup(const EdTable &tab, const GpText &t, u6
     }
 }
 
-// bit k of the result: byte k of the 16 is `c`
-__device__ __forceinline__ u32 ed_eq16(const uint4 &v, u32 c)
-{
-    const u32 w[4] = {v.x, v.y, v.z, v.w};
-    const u32 cc = c * 0x01010101u;
-    u32 m = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const u32 x = w[k] ^ cc;
-        const u32 z = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu); // 0x80 in every byte of x that is zero
-        m |= ((((z >> 7) * 0x00204081u) >> 21) & 0xFu) << (4 * k);
-    }
-    return m;
-}
-
 // The tile [tile0, tile0 + want) -> LDS, 16 bytes per thread and step (the mirror is padded by 64 zero bytes and the last
 // step is clipped to whole 16-byte pieces inside it; an inner segment's `avail` is a chunk boundary); the newline mask of
 // the tile's kGpTile bytes -> nlm (a u16 per 16 bytes); returns whether a '"' or a CR lies in the tile.
@@ -129,11 +116,11 @@ __device__ __forceinline__ u32 ed_stage(const EdArgs &a, u64 tile0, u32 window, 
         if (i < want) v = *reinterpret_cast<const uint4 *>(a.text + tile0 + i);
         *reinterpret_cast<uint4 *>(win + i) = v;
         if (i < (u32)kGpTile) {
-            u32 nlb = ed_eq16(v, '\n');
+            u32 nlb = gp_eq16(v, '\n');
             const u64 at = tile0 + i;
             if (a.nl > a.n && a.n >= at && a.n < at + 16u) nlb |= 1u << (u32)(a.n - at); // (the newline the last line lacks)
             nlm[i >> 4] = (unsigned short)nlb;
-            special |= ed_eq16(v, '"') | ed_eq16(v, '\r');
+            special |= gp_eq16(v, '"') | gp_eq16(v, '\r');
         }
     }
     return special;
@@ -377,55 +364,21 @@ __global__ __launch_bounds__(kGpT) void ed_pack_kernel(EdArgs a)
 namespace {
 
 constexpr size_t kOutPiece = (size_t)4 << 20;
+constexpr u64 kSegBytes = (u64)(kTextChunk * kTextSeg); // the mover's segment: what one round of mark, carry, scan and pack covers
 
 struct EditScratch { // the editor's buffers; they stay with the engine (grow-only), go with yacrd_engine_trim / destroy
+    static constexpr yacrd_engine::Slot kScratchSlot = yacrd_engine::kEdit;
     DevBuf text, out, names, name_off, types, slots, kbits, tile, tile_kept, tile_cin, tile_off, ctl, part;
-    void *pin = nullptr; // two output pieces + the per-segment control words
-    size_t pin_cap = 0;
+    PinBuf pin; // two output pieces + the per-segment control words
     void release()
     {
         for (DevBuf *b : {&text, &out, &names, &name_off, &types, &slots, &kbits, &tile, &tile_kept, &tile_cin, &tile_off, &ctl, &part}) b->release();
-        if (pin) (void)hipHostFree(pin);
-        pin = nullptr, pin_cap = 0;
+        pin.release();
     }
     ~EditScratch() { release(); }
 };
-EditScratch *edit_scratch_of(yacrd_engine *e)
-{
-    if (!e->edit_scratch) {
-        e->edit_scratch = new (std::nothrow) EditScratch();
-        e->edit_scratch_free = [](void *p) { delete static_cast<EditScratch *>(p); };
-        e->edit_scratch_release = [](void *p) { static_cast<EditScratch *>(p)->release(); };
-    }
-    return static_cast<EditScratch *>(e->edit_scratch);
-}
 
-// where the kept bytes go: a file descriptor or memory
-struct OutSink {
-    int fd = -1;
-    char *mem = nullptr;
-    u64 at = 0;
-    u64 cap = 0; // of `mem` when it grows (members: their size is not known in advance); 0 = the caller sized it
-    bool put(const char *p, size_t k)
-    {
-        if (mem && cap && at + k > cap) {
-            const u64 want = std::max<u64>(at + k, cap + cap / 2 + 4096);
-            char *q = (char *)std::realloc(mem, (size_t)want);
-            if (!q) return false;
-            mem = q, cap = want;
-        }
-        if (mem) std::memcpy(mem + at, p, k);
-        else
-            for (size_t done = 0; done < k;) {
-                const ssize_t w = ::write(fd, p + done, k - done);
-                if (w < 0 && errno == EINTR) continue;
-                if (w <= 0) return false;
-                done += (size_t)w;
-            }
-        at += k;
-        return true;
-    }
-};
+using yseg::Sink; // where the kept bytes go: a file descriptor or memory, sized or growing (host/segment_pump.h)
 
 // the field count of the first non-empty line (0: there is none) and whether the text's last byte is a newline
 bool first_line_fields(const TextSource &src, u64 n, char delim, u32 &n_fields, bool &ends_in_newline)
@@ -468,138 +421,155 @@ struct EditJob {
     yacrd_gzip_stats *gzip_stats = nullptr;
 };
 
-constexpr u64 kGzBlock = 65280; // deflate_block.h: ydf::kBlock
-
-int edit_text(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n, OutSink &sink, yacrd_edit_stats *stats)
-{
-    DeviceGuard guard(e->device);
-    EditScratch *Sp = edit_scratch_of(e);
-    if (!Sp) return fail(YACRD_ENOMEM, "host allocation failed");
-    EditScratch &S = *Sp;
-    const yacrd_type_table &tt = *job.types;
-    const u64 R = tt.n_reads;
-    if (R >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "more reads than the device table holds");
-    if (R && (!tt.name_off || !tt.names || !tt.read_type)) return fail(YACRD_EINVAL, "the type table is incomplete");
-    const u64 name_bytes = R ? tt.name_off[R] : 0;
-    const char delim = job.m4 ? ' ' : '\t';
-    const u32 ib = job.m4 ? 1u : 5u;
-    u32 n_fields = 0;
-    bool ends_nl = true;
-    if (!first_line_fields(src, n, delim, n_fields, ends_nl)) return fail(YACRD_EINVAL, "read error in the overlap file");
-    if (n_fields && n_fields <= ib) return fail(YACRD_EFALLBACK, "the first line has too few fields: the host loop words the error");
-    const u64 nl = n + (ends_nl ? 0 : 1);
-    const u64 n_tiles = (nl + yk::kGpTile - 1) / yk::kGpTile;
-    if (n_tiles >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "file too large for the device editor");
-    const size_t n_segs = (size_t)((n + kTextChunk * kTextSeg - 1) / (kTextChunk * kTextSeg));
-    u64 cap = 1024;
-    while (cap < 2 * R) cap <<= 1;
-    // gzip out: a batch is at most a segment's kept bytes and the tail carried into it
-    const u64 gz_blocks = job.gzip ? (std::min<u64>(nl, (u64)(kTextChunk * kTextSeg)) + kGzBlock - 1) / kGzBlock + 1 : 0;
-    const double t_start = now_ms();
+struct GzHold { // the engine's encoder buffers are this edit's until it ends
+    yacrd_engine *e = nullptr;
+    ~GzHold()
     {
+        if (e) gzip_device_close(e);
+    }
+};
+
+// One edit on its way through the device: built once per call (run_edit), its phases in the order they run.
+struct EditRun {
+    yacrd_engine *e;
+    const EditJob &job;
+    const TextSource &src;
+    const u64 n; // bytes of text
+    Sink &sink;
+    yacrd_edit_stats *stats;
+    EditScratch &S;
+    // plan(): sizes
+    u64 R = 0, name_bytes = 0; // reads of the type table, their names' bytes
+    u64 nl = 0, n_tiles = 0;   // n, or n + 1 when the last line lacks its newline; tiles of that
+    size_t n_segs = 0, n_batches = 0; // gzip out: a batch per segment, or the one that only holds the EOF member
+    u64 cap = 1024;            // slots of the id table
+    u64 gz_blocks = 0;         // gzip out: a batch is at most a segment's kept bytes and the tail carried into it
+    u32 n_fields = 0;
+    double t_start = 0, t_table = 0;
+    // reserve(), upload_table()
+    bool blit = false; // a fresh mirror fills faster by copy kernel (gpu_paf.hip)
+    yk::EdArgs ga{};
+    u64 *seg_base = nullptr;
+    volatile u64 *h_seg = nullptr; // pinned, per segment: lines, kept, status, kept bytes so far
+    volatile u64 *h_gz = nullptr;  // pinned, per batch: its members' bytes, stored members so far
+    GzDevice gz;
+    GzHold gz_hold;
+    // run(): the segments' kernels on the engine's stream, the writer thread behind their events
+    Events ev0, ev1;           // around a segment's kernels (timing)
+    Events wev;                // a pinned piece has landed (two; no timing)
+    Events gev0, gev1, gdone;  // around the kernels of every batch of the encoder (timing); behind its sizes' way home (no timing)
+    Streams side;              // [0] the way home; [1] the encoder (gzip out)
+    std::atomic<int> bad{0};   // 1 a HIP call failed, 2 the output could not be written, 3 the text is not for this path
+    std::atomic<size_t> dispatched{0};
+    std::atomic<bool> no_more{false};
+    int moved = 0; // move_text's verdict
+    double out_busy_ms = 0, put_ms = 0;
+    u64 gz_text = 0, gz_members = 0, gz_stored = 0; // gzip out: kept bytes encoded, their members, the stored ones
+    size_t gz_sent = 0, gz_got = 0;                 // batches launched / fetched
+    std::vector<u64> gz_eof;                        // per batch: the EOF member's bytes behind its members
+    float kernel_ms = 0, gz_kernel_ms = 0;
+
+    hipStream_t wstream() const { return side[0]; }
+    hipStream_t gstream() const { return side[1]; }
+
+    // sizes, and whether this device's free memory takes the edit
+    int plan()
+    {
+        const yacrd_type_table &tt = *job.types;
+        R = tt.n_reads;
+        if (R >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "more reads than the device table holds");
+        if (R && (!tt.name_off || !tt.names || !tt.read_type)) return fail(YACRD_EINVAL, "the type table is incomplete");
+        name_bytes = R ? tt.name_off[R] : 0;
+        const char delim = job.m4 ? ' ' : '\t';
+        const u32 ib = job.m4 ? 1u : 5u;
+        bool ends_nl = true;
+        if (!first_line_fields(src, n, delim, n_fields, ends_nl)) return fail(YACRD_EINVAL, "read error in the overlap file");
+        if (n_fields && n_fields <= ib) return fail(YACRD_EFALLBACK, "the first line has too few fields: the host loop words the error");
+        nl = n + (ends_nl ? 0 : 1);
+        n_tiles = (nl + yk::kGpTile - 1) / yk::kGpTile;
+        if (n_tiles >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "file too large for the device editor");
+        n_segs = (size_t)((n + kSegBytes - 1) / kSegBytes);
+        n_batches = n_segs + 1;
+        while (cap < 2 * R) cap <<= 1;
+        gz_blocks = job.gzip ? (std::min<u64>(nl, kSegBytes) + ydf::kBlock - 1) / ydf::kBlock + 1 : 0;
+        ga.delim = (u32)(unsigned char)delim, ga.ib = ib, ga.n_fields = n_fields, ga.keep_good = job.op == 1 ? 1u : 0u;
+        t_start = now_ms();
         // HBM: the text (unless the parser's mirror serves), as many bytes again for what is kept, a bit per byte, the table
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
             const double have = (double)free_b + (double)S.text.cap + (double)S.out.cap + (double)S.kbits.cap + (double)S.names.cap + (double)S.slots.cap;
             const double need = (job.use_mirror ? 0.0 : (double)n) + (double)nl * 1.125 + (double)nl / 8.0 * 1.125 + (double)name_bytes * 1.125 +
                                 (double)cap * 4.0 + (double)R * 10.0 + (double)n_tiles * 40.0 + (double)((size_t)64 << 20) +
-                                (double)gz_blocks * 65536.0 * 3.0 * 1.125; // (the members' slots and two batches of members)
+                                (double)gz_blocks * (double)ydf::kSlot * 3.0 * 1.125; // (the members' slots and two batches of members)
             if (need > have) return fail(YACRD_EFALLBACK, "the file is too large to be edited in this device's free memory: the host loop streams it");
         }
+        return YACRD_OK;
     }
-    // ---- buffers
-    const void *mirror_before = S.text.p;
-    if (!job.use_mirror) HIP_TRY(S.text.reserve((size_t)n + 64));
-    const bool blit = !job.use_mirror && S.text.p != mirror_before; // (a fresh mirror fills faster by copy kernel: gpu_paf.hip)
-    if (!job.use_mirror) HIP_TRY(hipMemsetAsync(S.text.as<char>() + n, 0, 64, e->stream));
-    HIP_TRY(S.out.reserve((size_t)nl + 64));
-    HIP_TRY(S.kbits.reserve((size_t)(n_tiles + 1) * yk::kGpT * sizeof(uint4)));
-    HIP_TRY(S.tile.reserve((size_t)(n_tiles + 1) * sizeof(uint4)));
-    HIP_TRY(S.tile_kept.reserve((size_t)(n_tiles + 1) * sizeof(u32)));
-    HIP_TRY(S.tile_cin.reserve((size_t)(n_tiles + 1) * sizeof(u32)));
-    HIP_TRY(S.tile_off.reserve((size_t)(n_tiles + n_segs + 2) * sizeof(u64)));
-    const size_t ctl_words = 8 + n_segs + 2;
-    HIP_TRY(S.ctl.reserve(ctl_words * sizeof(u64)));
-    HIP_TRY(hipMemsetAsync(S.ctl.p, 0, ctl_words * sizeof(u64), e->stream));
-    const size_t n_batches = n_segs + 1; // gzip out: one per segment, or the one that only holds the EOF member
-    const size_t pin_need = 2 * kOutPiece + (n_segs + 2) * 4 * sizeof(u64) + (job.gzip ? n_batches * 2 * sizeof(u64) : 0);
-    if (S.pin_cap < pin_need) {
-        if (S.pin) (void)hipHostFree(S.pin);
-        S.pin = nullptr, S.pin_cap = 0;
-        HIP_TRY(hipHostMalloc(&S.pin, pin_need));
-        S.pin_cap = pin_need;
-    }
-    char *pin_out[2] = {(char *)S.pin, (char *)S.pin + kOutPiece};
-    volatile u64 *h_seg = reinterpret_cast<volatile u64 *>((char *)S.pin + 2 * kOutPiece); // per segment: lines, kept, status, kept bytes so far
-    volatile u64 *h_gz = h_seg + (n_segs + 2) * 4;                                          // per batch: its members' bytes, stored members so far
-    // gzip out: every buffer of the encoder is taken here, before the first segment is handed over
-    GzDevice gz;
-    struct GzHold {
-        yacrd_engine *e = nullptr;
-        ~GzHold()
-        {
-            if (e) gzip_device_close(e);
+
+    // every buffer of the edit, the encoder's included: nothing is allocated once the first segment is handed over
+    int reserve()
+    {
+        const void *mirror_before = S.text.p;
+        if (!job.use_mirror) HIP_TRY(S.text.reserve((size_t)n + 64));
+        blit = !job.use_mirror && S.text.p != mirror_before;
+        if (!job.use_mirror) HIP_TRY(hipMemsetAsync(S.text.as<char>() + n, 0, 64, e->stream));
+        HIP_TRY(S.out.reserve((size_t)nl + 64));
+        HIP_TRY(S.kbits.reserve((size_t)(n_tiles + 1) * yk::kGpT * sizeof(uint4)));
+        HIP_TRY(S.tile.reserve((size_t)(n_tiles + 1) * sizeof(uint4)));
+        HIP_TRY(S.tile_kept.reserve((size_t)(n_tiles + 1) * sizeof(u32)));
+        HIP_TRY(S.tile_cin.reserve((size_t)(n_tiles + 1) * sizeof(u32)));
+        HIP_TRY(S.tile_off.reserve((size_t)(n_tiles + n_segs + 2) * sizeof(u64)));
+        const size_t ctl_words = 8 + n_segs + 2;
+        HIP_TRY(S.ctl.reserve(ctl_words * sizeof(u64)));
+        HIP_TRY(hipMemsetAsync(S.ctl.p, 0, ctl_words * sizeof(u64), e->stream));
+        HIP_TRY(S.pin.reserve(2 * kOutPiece + (n_segs + 2) * 4 * sizeof(u64) + (job.gzip ? n_batches * 2 * sizeof(u64) : 0)));
+        h_seg = reinterpret_cast<volatile u64 *>(S.pin.as<char>() + 2 * kOutPiece);
+        h_gz = h_seg + (n_segs + 2) * 4;
+        if (job.gzip) {
+            if (const int rcg = gzip_device_open(e, gz_blocks, &gz)) return rcg;
+            gz_hold.e = e;
+            gz_eof.assign(n_batches, 0);
         }
-    } gz_hold;
-    if (job.gzip) {
-        if (const int rcg = gzip_device_open(e, gz_blocks, &gz)) return rcg;
-        gz_hold.e = e;
+        return YACRD_OK;
     }
-    // ---- the table
-    HIP_TRY(S.names.reserve((size_t)name_bytes + 64));
-    HIP_TRY(S.name_off.reserve((size_t)(R + 1) * sizeof(u64)));
-    HIP_TRY(S.types.reserve((size_t)R + 64));
-    HIP_TRY(S.slots.reserve((size_t)cap * sizeof(u32)));
-    HIP_TRY(hipMemsetAsync(S.slots.p, 0, (size_t)cap * sizeof(u32), e->stream));
-    yk::EdTable tab{};
-    tab.names = S.names.as<unsigned char>(), tab.name_off = S.name_off.as<u64>(), tab.type = S.types.as<unsigned char>();
-    tab.slots = S.slots.as<u32>(), tab.mask = (u32)(cap - 1), tab.n_reads = (u32)R;
-    if (R) {
-        if (name_bytes)
-            if (const int rch = h2d(e, S.names.p, tt.names, (size_t)name_bytes)) return rch;
-        if (const int rch = h2d(e, S.name_off.p, tt.name_off, (size_t)(R + 1) * sizeof(u64))) return rch;
-        if (const int rch = h2d(e, S.types.p, tt.read_type, (size_t)R)) return rch;
-        hipLaunchKernelGGL(yk::ed_table_kernel, dim3((u32)((R + 255) / 256)), dim3(256), 0, e->stream, tab);
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    const double t_table = now_ms();
 
-    yk::EdArgs ga{};
-    ga.text = job.use_mirror ? e->mirror.p : S.text.as<unsigned char>();
-    ga.n = n, ga.nl = nl;
-    ga.tab = tab;
-    ga.kbits = S.kbits.as<uint4>(), ga.tile = S.tile.as<uint4>(), ga.tile_kept = S.tile_kept.as<u32>(), ga.tile_cin = S.tile_cin.as<u32>();
-    ga.tile_off = S.tile_off.as<u64>();
-    ga.ctl = S.ctl.as<unsigned long long>();
-    u64 *seg_base = S.ctl.as<u64>() + 8;
-    ga.seg_base = seg_base;
-    ga.out = S.out.as<unsigned char>();
-    ga.delim = (u32)(unsigned char)delim, ga.ib = ib, ga.n_fields = n_fields, ga.keep_good = job.op == 1 ? 1u : 0u;
-
-    // ---- per segment: mark, carry, scan, pack on the engine's stream; the writer thread takes it from the segment's event
-    std::vector<hipEvent_t> ev0(n_segs, nullptr), ev1(n_segs, nullptr);
-    hipStream_t wstream = nullptr, gstream = nullptr; // the way home; the encoder (gzip out)
-    hipEvent_t wev[2] = {nullptr, nullptr};
-    std::vector<hipEvent_t> gev0, gev1, gdone; // around the kernels of every batch of the encoder; behind its sizes' way home
-    std::atomic<int> bad(0); // 1 a HIP call failed, 2 the output could not be written, 3 the text is not for this path
-    std::atomic<size_t> dispatched(0);
-    std::atomic<bool> no_more(false);
-    bool setup_ok = hipStreamCreateWithFlags(&wstream, hipStreamNonBlocking) == hipSuccess;
-    for (int b = 0; b < 2; b++) setup_ok = setup_ok && hipEventCreateWithFlags(&wev[b], hipEventDisableTiming) == hipSuccess;
-    for (size_t s = 0; s < n_segs; s++)
-        setup_ok = setup_ok && hipEventCreate(&ev0[s]) == hipSuccess && hipEventCreate(&ev1[s]) == hipSuccess;
-    if (job.gzip) {
-        gev0.assign(n_batches, nullptr), gev1.assign(n_batches, nullptr), gdone.assign(n_batches, nullptr);
-        setup_ok = setup_ok && hipStreamCreateWithFlags(&gstream, hipStreamNonBlocking) == hipSuccess;
-        for (size_t b = 0; b < n_batches; b++)
-            setup_ok = setup_ok && hipEventCreate(&gev0[b]) == hipSuccess && hipEventCreate(&gev1[b]) == hipSuccess &&
-                       hipEventCreateWithFlags(&gdone[b], hipEventDisableTiming) == hipSuccess;
+    // the reads' names and types -> HBM, the id table over them; the kernels' arguments
+    int upload_table()
+    {
+        const yacrd_type_table &tt = *job.types;
+        HIP_TRY(S.names.reserve((size_t)name_bytes + 64));
+        HIP_TRY(S.name_off.reserve((size_t)(R + 1) * sizeof(u64)));
+        HIP_TRY(S.types.reserve((size_t)R + 64));
+        HIP_TRY(S.slots.reserve((size_t)cap * sizeof(u32)));
+        HIP_TRY(hipMemsetAsync(S.slots.p, 0, (size_t)cap * sizeof(u32), e->stream));
+        yk::EdTable tab{};
+        tab.names = S.names.as<unsigned char>(), tab.name_off = S.name_off.as<u64>(), tab.type = S.types.as<unsigned char>();
+        tab.slots = S.slots.as<u32>(), tab.mask = (u32)(cap - 1), tab.n_reads = (u32)R;
+        if (R) {
+            if (name_bytes)
+                if (const int rch = h2d(e, S.names.p, tt.names, (size_t)name_bytes)) return rch;
+            if (const int rch = h2d(e, S.name_off.p, tt.name_off, (size_t)(R + 1) * sizeof(u64))) return rch;
+            if (const int rch = h2d(e, S.types.p, tt.read_type, (size_t)R)) return rch;
+            hipLaunchKernelGGL(yk::ed_table_kernel, dim3((u32)((R + 255) / 256)), dim3(256), 0, e->stream, tab);
+        }
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        t_table = now_ms();
+        ga.text = job.use_mirror ? e->mirror.p : S.text.as<unsigned char>();
+        ga.n = n, ga.nl = nl;
+        ga.tab = tab;
+        ga.kbits = S.kbits.as<uint4>(), ga.tile = S.tile.as<uint4>(), ga.tile_kept = S.tile_kept.as<u32>(), ga.tile_cin = S.tile_cin.as<u32>();
+        ga.tile_off = S.tile_off.as<u64>();
+        ga.ctl = S.ctl.as<unsigned long long>();
+        seg_base = S.ctl.as<u64>() + 8;
+        ga.seg_base = seg_base;
+        ga.out = S.out.as<unsigned char>();
+        return YACRD_OK;
     }
-    double out_busy_ms = 0, put_ms = 0;
-    u64 gz_text = 0, gz_members = 0, gz_stored = 0; // gzip out: kept bytes encoded, their members, the stored ones
-    size_t gz_sent = 0, gz_got = 0;                 // batches launched / fetched
-    auto launch_segment = [&](u64 seg_begin, u64 seg_end, u64 avail) {
-        const size_t s = (size_t)(seg_begin / (kTextChunk * kTextSeg));
+
+    // a segment has landed (or lies in the mirror): mark, carry, scan, pack on the engine's stream, its counts to the host
+    void launch_segment(u64 seg_begin, u64 seg_end, u64 avail)
+    {
+        const size_t s = (size_t)(seg_begin / kSegBytes);
         const u32 t0 = (u32)(seg_begin / yk::kGpTile), t1 = seg_end >= n ? (u32)n_tiles : (u32)(seg_end / yk::kGpTile);
         ga.avail = avail, ga.tile0 = t0, ga.seg = (u32)s;
         bool ok = hipEventRecord(ev0[s], e->stream) == hipSuccess;
@@ -616,69 +586,73 @@ int edit_text(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n,
         ok = ok && hipEventRecord(ev1[s], e->stream) == hipSuccess;
         if (!ok) bad = 1;
         dispatched.store(s + 1, std::memory_order_release);
-    };
-    // base[from, upto) in HBM -> the sink, piece by piece: one flies while the other is written
-    auto bring_home = [&](const char *base, u64 from, u64 upto) {
-        const u64 n_pieces = (upto - from + kOutPiece - 1) / kOutPiece;
-        auto fly = [&](u64 k) {
-            const u64 o = from + k * kOutPiece;
-            const size_t len = (size_t)std::min<u64>(kOutPiece, upto - o);
-            if (hipMemcpyAsync(pin_out[k & 1], base + o, len, hipMemcpyDeviceToHost, wstream) != hipSuccess ||
-                hipEventRecord(wev[k & 1], wstream) != hipSuccess)
-                bad = 1;
-        };
-        if (n_pieces) fly(0);
-        for (u64 k = 0; k < n_pieces && !bad.load(); k++) {
-            if (hipEventSynchronize(wev[k & 1]) != hipSuccess) {
-                bad = 1;
-                break;
+    }
+
+    // base[from, upto) in HBM -> the sink through the two pinned pieces: one flies while the other is written (host/segment_pump.h)
+    void bring_home(const char *base, u64 from, u64 upto)
+    {
+        struct Dma {
+            EditRun &r;
+            const char *text;
+            bool start(u64 i, char *dst, u64 at, size_t len)
+            {
+                return hipMemcpyAsync(dst, text + at, len, hipMemcpyDeviceToHost, r.wstream()) == hipSuccess &&
+                       hipEventRecord(r.wev[i & 1], r.wstream()) == hipSuccess;
             }
-            if (k + 1 < n_pieces) fly(k + 1);
-            const u64 o = from + k * kOutPiece;
+            bool wait(u64 i) { return !r.bad.load() && hipEventSynchronize(r.wev[i & 1]) == hipSuccess; }
+            void drain() { (void)hipStreamSynchronize(r.wstream()); }
+        } dma{*this, base + from};
+        const int rc = yseg::pump(upto - from, kOutPiece, S.pin.as<char>(), dma, sink, [&](auto put) {
             const double tp = now_ms();
-            if (!sink.put(pin_out[k & 1], (size_t)std::min<u64>(kOutPiece, upto - o))) bad = 2;
+            put();
             put_ms += now_ms() - tp;
-        }
-        if (wstream) (void)hipStreamSynchronize(wstream);
-    };
+        });
+        if (rc == yseg::kLinkFailed && !bad.load()) bad = 1; // (wait also gives up when another thread has set a code: that code stays)
+        if (rc == yseg::kSinkFailed) bad = 2;
+    }
+
     // gzip out (both run on the writer thread).  encode: kept bytes [gz_text, upto) -> a batch of members, on the encoder's
     // stream; the pack that wrote them has finished (the writer has waited for the segment's event).  fetch_batch: the
     // oldest batch not yet fetched -> the sink.
-    std::vector<u64> gz_eof(n_batches, 0);
-    auto encode = [&](u64 upto, bool last) {
+    void encode(u64 upto, bool last)
+    {
         const size_t b = gz_sent;
         const u64 len = upto - gz_text;
-        if (b >= n_batches || len > gz.max_blocks * kGzBlock) {
+        if (b >= n_batches || len > gz.max_blocks * ydf::kBlock) {
             bad = 1;
             return;
         }
         h_gz[2 * b] = h_gz[2 * b + 1] = 0;
-        if (gzip_device_encode(e, gz, gstream, S.out.as<unsigned char>() + gz_text, len, last, (int)(b & 1), gev0[b], gev1[b], h_gz + 2 * b,
+        if (gzip_device_encode(e, gz, gstream(), S.out.as<unsigned char>() + gz_text, len, last, (int)(b & 1), gev0[b], gev1[b], h_gz + 2 * b,
                                h_gz + 2 * b + 1) != YACRD_OK ||
-            hipEventRecord(gdone[b], gstream) != hipSuccess) {
+            hipEventRecord(gdone[b], gstream()) != hipSuccess) {
             bad = 1;
             return;
         }
-        gz_eof[b] = last ? 28u : 0u; // (the EOF member: deflate_block.h, ydf::kEofBytes)
-        gz_members += (len + kGzBlock - 1) / kGzBlock;
+        gz_eof[b] = last ? ydf::kEofBytes : 0u;
+        gz_members += (len + ydf::kBlock - 1) / ydf::kBlock;
         gz_text = upto, gz_sent = b + 1;
-    };
-    auto fetch_batch = [&]() {
+    }
+    void fetch_batch()
+    {
         const size_t b = gz_got;
         if (hipEventSynchronize(gdone[b]) != hipSuccess) { // (not the stream: the next batch is being encoded on it)
             bad = 1;
             return;
         }
         const u64 bytes = h_gz[2 * b] + gz_eof[b];
-        if (bytes > gz.max_blocks * 65536u + 28u) {
+        if (bytes > gz.max_blocks * ydf::kSlot + ydf::kEofBytes) {
             bad = 1;
             return;
         }
         gz_stored = h_gz[2 * b + 1];
         bring_home(reinterpret_cast<const char *>(gz.out[b & 1]), 0, bytes);
         gz_got = b + 1;
-    };
-    auto writer = [&]() {
+    }
+
+    // the writer thread: segment by segment, in order, what the pack has finished goes home (or to the encoder)
+    void writer()
+    {
         if (hipSetDevice(e->device) != hipSuccess) bad = 1;
         u64 from = 0;
         size_t seen = 0; // segments taken
@@ -707,7 +681,7 @@ int edit_text(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n,
                 // every whole block that now lies complete behind the last encoded one (the last segment: the tail too, and
                 // the EOF member) goes to the encoder; the batch before it comes home while this one is encoded
                 const bool last = s + 1 == n_segs;
-                const u64 whole = last ? upto : upto / kGzBlock * kGzBlock;
+                const u64 whole = last ? upto : upto / ydf::kBlock * ydf::kBlock;
                 if (whole > gz_text || last) encode(whole, last);
                 while (gz_got + 1 < gz_sent && !bad.load()) fetch_batch();
             }
@@ -720,13 +694,19 @@ int edit_text(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n,
             while (gz_got < gz_sent && !bad.load()) fetch_batch();
             out_busy_ms += now_ms() - t0;
         }
-    };
-    int moved = 0;
-    if (setup_ok) {
-        std::thread wt(writer);
+    }
+
+    // streams and events, then the text through the device: this thread moves it (or walks the mirror) and launches the
+    // segments, the writer thread takes them from their events.  false: a stream or an event could not be created
+    bool run()
+    {
+        bool setup_ok = side.add(1) && wev.add(2, hipEventDisableTiming) && ev0.add(n_segs) && ev1.add(n_segs);
+        if (job.gzip)
+            setup_ok = setup_ok && side.add(1) && gev0.add(n_batches) && gev1.add(n_batches) && gdone.add(n_batches, hipEventDisableTiming);
+        if (!setup_ok) return false;
+        std::thread wt([this] { writer(); });
         if (job.use_mirror) {
-            for (size_t s = 0; s < n_segs && !bad.load(); s++)
-                launch_segment((u64)s * kTextChunk * kTextSeg, (u64)(s + 1) * kTextChunk * kTextSeg, n);
+            for (size_t s = 0; s < n_segs && !bad.load(); s++) launch_segment((u64)s * kSegBytes, (u64)(s + 1) * kSegBytes, n);
         } else {
             moved = move_text(e, src, 0, n, S.text.as<char>(), blit, job.n_threads,
                               [&](u64 seg_begin, u64 seg_end, u64 avail) { launch_segment(seg_begin, seg_end, avail); });
@@ -735,63 +715,68 @@ int edit_text(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n,
         const double t_text_done = now_ms();
         wt.join();
         (void)hipStreamSynchronize(e->stream);
-        if (gstream) (void)hipStreamSynchronize(gstream);
+        if (job.gzip) (void)hipStreamSynchronize(gstream());
         if (stats) stats->text_ms = job.use_mirror ? 0.0f : (float)(t_text_done - t_table);
-    }
-    float kernel_ms = 0;
-    if (setup_ok && !bad.load() && !moved)
-        for (size_t s = 0; s < n_segs; s++) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, ev0[s], ev1[s]) == hipSuccess) kernel_ms += ms;
+        if (!bad.load() && !moved) {
+            for (size_t s = 0; s < n_segs; s++) {
+                float ms = 0;
+                if (hipEventElapsedTime(&ms, ev0[s], ev1[s]) == hipSuccess) kernel_ms += ms;
+            }
+            for (size_t b = 0; b < gz_sent; b++) gz_kernel_ms += ev_ms(gev0[b], gev1[b]);
         }
-    float gz_kernel_ms = 0;
-    if (setup_ok && !bad.load() && !moved)
-        for (size_t b = 0; b < gz_sent; b++) gz_kernel_ms += ev_ms(gev0[b], gev1[b]);
-    if (wstream) (void)hipStreamDestroy(wstream);
-    if (gstream) (void)hipStreamDestroy(gstream);
-    for (const std::vector<hipEvent_t> *v : {&gev0, &gev1, &gdone})
-        for (hipEvent_t x : *v)
-            if (x) (void)hipEventDestroy(x);
-    for (hipEvent_t x : wev)
-        if (x) (void)hipEventDestroy(x);
-    for (size_t s = 0; s < n_segs; s++) {
-        if (ev0[s]) (void)hipEventDestroy(ev0[s]);
-        if (ev1[s]) (void)hipEventDestroy(ev1[s]);
+        return true;
     }
-    (void)hipGetLastError();
-    if (!setup_ok) return fail(YACRD_ENODEV, "overlap editor: a HIP stream or event could not be created");
-    if (moved == 2) return fail(YACRD_EINVAL, "read error in the overlap file");
-    if (moved == 3) return fail(YACRD_ENOMEM, "overlap text to HBM: no pinned memory");
-    if (moved || bad.load() == 1) return fail(YACRD_ENODEV, "overlap editor: a HIP call failed");
-    if (bad.load() == 2) return fail(YACRD_EINVAL, "Error during writing of the output file");
-    u64 h_lines = 0, h_kept = 0, h_status = 0, h_bytes = 0;
-    if (n_segs) {
-        h_lines = h_seg[4 * (n_segs - 1)], h_kept = h_seg[4 * (n_segs - 1) + 1], h_status = h_seg[4 * (n_segs - 1) + 2];
-        h_bytes = h_seg[4 * (n_segs - 1) + 3];
+
+    // what the mover, the writer and the segments' status words say -> the return code and the stats
+    int verdict(bool ran)
+    {
+        (void)hipGetLastError();
+        if (!ran) return fail(YACRD_ENODEV, "overlap editor: a HIP stream or event could not be created");
+        if (moved == 2) return fail(YACRD_EINVAL, "read error in the overlap file");
+        if (moved == 3) return fail(YACRD_ENOMEM, "overlap text to HBM: no pinned memory");
+        if (moved || bad.load() == 1) return fail(YACRD_ENODEV, "overlap editor: a HIP call failed");
+        if (bad.load() == 2) return fail(YACRD_EINVAL, "Error during writing of the output file");
+        u64 h_lines = 0, h_kept = 0, h_status = 0, h_bytes = 0;
+        if (n_segs) {
+            h_lines = h_seg[4 * (n_segs - 1)], h_kept = h_seg[4 * (n_segs - 1) + 1], h_status = h_seg[4 * (n_segs - 1) + 2];
+            h_bytes = h_seg[4 * (n_segs - 1) + 3];
+        }
+        if (bad.load() == 3 || (h_status & yk::kEdNeedHost))
+            return fail(YACRD_EFALLBACK, "the text holds a '\"', a CR, a line whose field count differs from the first line's or one that is "
+                                         "megabytes long: the host loop decides");
+        if (h_status) return fail(YACRD_EINTERNAL, "overlap editor: the mark and the pack pass disagree");
+        if ((job.gzip ? gz_text : sink.at) != h_bytes) return fail(YACRD_EINTERNAL, "overlap editor: fewer bytes written than kept");
+        if (job.gzip && gz_got != gz_sent) return fail(YACRD_EINTERNAL, "overlap editor: a batch of members was not fetched");
+        if (job.gzip_stats) {
+            yacrd_gzip_stats &g = *job.gzip_stats;
+            g.in_bytes = gz_text, g.out_bytes = sink.at, g.n_members = gz_members, g.n_stored = gz_stored;
+            g.h2d_ms = 0.f, g.kernel_ms = gz_kernel_ms; // (the text lies in HBM already)
+            g.d2h_ms = (float)std::max(0.0, out_busy_ms - put_ms), g.write_ms = (float)put_ms; // (d2h: with the waits for the encoder)
+        }
+        if (stats) {
+            stats->text_bytes = n;
+            stats->kept_bytes = h_bytes;
+            stats->n_lines = h_lines;
+            stats->n_kept = h_kept;
+            stats->table_ms = (float)(t_table - t_start);
+            stats->kernel_ms = kernel_ms;
+            stats->out_ms = (float)out_busy_ms;
+            stats->mirror_reused = job.use_mirror ? 1u : 0u;
+        }
+        return YACRD_OK;
     }
-    if (bad.load() == 3 || (h_status & yk::kEdNeedHost))
-        return fail(YACRD_EFALLBACK, "the text holds a '\"', a CR, a line whose field count differs from the first line's or one that is "
-                                     "megabytes long: the host loop decides");
-    if (h_status) return fail(YACRD_EINTERNAL, "overlap editor: the mark and the pack pass disagree");
-    if ((job.gzip ? gz_text : sink.at) != h_bytes) return fail(YACRD_EINTERNAL, "overlap editor: fewer bytes written than kept");
-    if (job.gzip && gz_got != gz_sent) return fail(YACRD_EINTERNAL, "overlap editor: a batch of members was not fetched");
-    if (job.gzip_stats) {
-        yacrd_gzip_stats &g = *job.gzip_stats;
-        g.in_bytes = gz_text, g.out_bytes = sink.at, g.n_members = gz_members, g.n_stored = gz_stored;
-        g.h2d_ms = 0.f, g.kernel_ms = gz_kernel_ms; // (the text lies in HBM already)
-        g.d2h_ms = (float)std::max(0.0, out_busy_ms - put_ms), g.write_ms = (float)put_ms; // (d2h: with the waits for the encoder)
-    }
-    if (stats) {
-        stats->text_bytes = n;
-        stats->kept_bytes = h_bytes;
-        stats->n_lines = h_lines;
-        stats->n_kept = h_kept;
-        stats->table_ms = (float)(t_table - t_start);
-        stats->kernel_ms = kernel_ms;
-        stats->out_ms = (float)out_busy_ms;
-        stats->mirror_reused = job.use_mirror ? 1u : 0u;
-    }
-    return YACRD_OK;
+};
+
+int run_edit(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n, Sink &sink, yacrd_edit_stats *stats)
+{
+    DeviceGuard guard(e->device);
+    EditScratch *S = scratch_of<EditScratch>(e);
+    if (!S) return fail(YACRD_ENOMEM, "host allocation failed");
+    EditRun r{e, job, src, n, sink, stats, *S};
+    if (const int rc = r.plan()) return rc;
+    if (const int rc = r.reserve()) return rc;
+    if (const int rc = r.upload_table()) return rc;
+    return r.verdict(r.run());
 }
 
 int edit_args(yacrd_engine *e, int op, const yacrd_type_table *types, yacrd_edit_stats *stats)
@@ -817,10 +802,7 @@ int yacrd_engine_edit_overlaps(yacrd_engine *e, int op, const char *in_path, con
     if (const int rcf = overlap_format(in_path, format, job.m4)) return rcf;
     const int fd = ::open(in_path, O_RDONLY);
     if (fd < 0) return fail(YACRD_EFALLBACK, std::string("cannot open ") + in_path + ": the host loop words the error");
-    struct FdGuard {
-        int fd;
-        ~FdGuard() { ::close(fd); }
-    } fdg{fd};
+    FdGuard fdg{fd};
     struct stat st, ost;
     if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) return fail(YACRD_EFALLBACK, "not a regular file: the host loop reads it");
     if (is_compressed_magic(fd)) return fail(YACRD_EFALLBACK, "a compressed file: the host loop inflates it and deflates what it keeps");
@@ -830,25 +812,17 @@ int yacrd_engine_edit_overlaps(yacrd_engine *e, int op, const char *in_path, con
         if (!S_ISREG(ost.st_mode)) return fail(YACRD_EFALLBACK, "the output is not a regular file: the host loop writes it");
         if (ost.st_dev == st.st_dev && ost.st_ino == st.st_ino) return fail(YACRD_EFALLBACK, "input and output are one file: the host loop's case");
     }
-    std::string tmp = std::string(out_path) + ".XXXXXX";
-    const int ofd = mkstemp(&tmp[0]);
-    if (ofd < 0) return fail(YACRD_EFALLBACK, std::string("cannot create a file beside ") + out_path + ": the host loop words the error");
-    {
-        const mode_t um = umask(0);
-        umask(um);
-        (void)fchmod(ofd, 0666 & ~um);
-    }
+    yseg::BesideFile file;
+    if (!file.open(out_path)) return fail(YACRD_EFALLBACK, std::string("cannot create a file beside ") + out_path + ": the host loop words the error");
     job.use_mirror = e->mirror.valid && e->mirror.p && e->mirror.n == (u64)st.st_size && e->mirror.dev == (u64)st.st_dev &&
                      e->mirror.ino == (u64)st.st_ino && e->mirror.mtime_s == (int64_t)st.st_mtim.tv_sec &&
                      e->mirror.mtime_ns == (int64_t)st.st_mtim.tv_nsec;
     TextSource src;
     src.fd = fd;
-    OutSink sink;
-    sink.fd = ofd;
-    int rc = edit_text(e, job, src, (u64)st.st_size, sink, stats);
-    if (::close(ofd) != 0 && rc == YACRD_OK) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
-    if (rc == YACRD_OK && ::rename(tmp.c_str(), out_path) != 0) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
-    if (rc != YACRD_OK) (void)::unlink(tmp.c_str());
+    Sink sink;
+    sink.fd = file.fd;
+    int rc = run_edit(e, job, src, (u64)st.st_size, sink, stats);
+    if (rc == YACRD_OK && !file.commit()) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
     return rc;
 }
 
@@ -863,10 +837,10 @@ int yacrd_engine_edit_overlaps_mem(yacrd_engine *e, int op, const char *text, ui
     if (const int rcf = overlap_format(nullptr, format, job.m4)) return rcf;
     TextSource src;
     src.mem = text ? text : "";
-    OutSink sink;
+    Sink sink;
     sink.mem = (char *)std::malloc((size_t)n + 2);
     if (!sink.mem) return fail(YACRD_ENOMEM, "host allocation failed");
-    const int rc = edit_text(e, job, src, n, sink, stats);
+    const int rc = run_edit(e, job, src, n, sink, stats);
     if (rc != YACRD_OK) {
         std::free(sink.mem);
         return rc;
@@ -887,11 +861,11 @@ int yacrd_engine_edit_overlaps_gzip_mem(yacrd_engine *e, int op, const char *tex
     if (const int rcf = overlap_format(nullptr, format, job.m4)) return rcf;
     TextSource src;
     src.mem = text ? text : "";
-    OutSink sink;
+    Sink sink;
     sink.cap = (size_t)(n / 4 + 4096); // (PAF text shrinks to about a quarter; the sink grows when it does not)
     sink.mem = (char *)std::malloc((size_t)sink.cap);
     if (!sink.mem) return fail(YACRD_ENOMEM, "host allocation failed");
-    const int rc = edit_text(e, job, src, n, sink, es);
+    const int rc = run_edit(e, job, src, n, sink, es);
     if (rc != YACRD_OK) { // (members of earlier segments may lie in the buffer: it goes)
         std::free(sink.mem);
         if (gs) std::memset(gs, 0, sizeof(*gs));
@@ -914,25 +888,15 @@ int yacrd_engine_edit_overlaps_gzip_file(yacrd_engine *e, int op, const char *te
     if (lstat(out_path, &ost) == 0 && !S_ISREG(ost.st_mode)) return fail(YACRD_EFALLBACK, "the output is not a regular file: the host loop writes it");
     // written beside its place and moved there when the EOF member is in: a text that turns out not to be for this path
     // (a later segment may say so, with members of earlier ones already written) leaves nothing behind
-    std::string tmp = std::string(out_path) + ".XXXXXX";
-    const int ofd = mkstemp(&tmp[0]);
-    if (ofd < 0) return fail(YACRD_EFALLBACK, std::string("cannot create a file beside ") + out_path + ": the host loop words the error");
-    {
-        const mode_t um = umask(0);
-        umask(um);
-        (void)fchmod(ofd, 0666 & ~um);
-    }
+    yseg::BesideFile file;
+    if (!file.open(out_path)) return fail(YACRD_EFALLBACK, std::string("cannot create a file beside ") + out_path + ": the host loop words the error");
     TextSource src;
     src.mem = text ? text : "";
-    OutSink sink;
-    sink.fd = ofd;
-    int rc = edit_text(e, job, src, n, sink, es);
-    if (::close(ofd) != 0 && rc == YACRD_OK) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
-    if (rc == YACRD_OK && ::rename(tmp.c_str(), out_path) != 0) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
-    if (rc != YACRD_OK) {
-        (void)::unlink(tmp.c_str());
-        if (gs) std::memset(gs, 0, sizeof(*gs));
-    }
+    Sink sink;
+    sink.fd = file.fd;
+    int rc = run_edit(e, job, src, n, sink, es);
+    if (rc == YACRD_OK && !file.commit()) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
+    if (rc != YACRD_OK && gs) std::memset(gs, 0, sizeof(*gs));
     return rc;
 }
 

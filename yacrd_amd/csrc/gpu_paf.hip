@@ -585,7 +585,8 @@ int sort_by_first_position(yacrd_engine *e, u64 *keys, u64 *keys_out, u32 *slots
     return YACRD_OK;
 }
 
-struct Scratch { // the call's device buffers; they stay with the engine (grow-only) and go when it is destroyed
+struct Scratch { // the call's device buffers; they stay with the engine (grow-only), go with yacrd_engine_trim / destroy
+    static constexpr yacrd_engine::Slot kScratchSlot = yacrd_engine::kPaf;
     DevBuf text, claim, first_pos, slot_cnt, recs, ctl, keys, keys2, slots, slots2, tmp, map, name_len, name_at, name_off,
         names, cnt, part, err, gather, gmap;
     // the merge engine's (yacrd_engines_ingest_overlaps)
@@ -617,21 +618,6 @@ private:
 
 extern "C" {
 
-int yacrd_engine_trim(yacrd_engine *e)
-{
-    if (!e) return fail(YACRD_EINVAL, "engine is null");
-    if (e->pending.active || e->host_pending) return fail(YACRD_EINVAL, "the engine has a submitted batch pending");
-    DeviceGuard guard(e->device);
-    e->mirror.valid = false;
-    e->resident.valid = false;
-    if (e->paf_scratch) static_cast<Scratch *>(e->paf_scratch)->release();
-    if (e->edit_scratch && e->edit_scratch_release) e->edit_scratch_release(e->edit_scratch);
-    if (e->gzip_scratch && e->gzip_scratch_release && !e->gzip_busy) e->gzip_scratch_release(e->gzip_scratch);
-    if (e->report_scratch && e->report_scratch_release) e->report_scratch_release(e->report_scratch);
-    if (e->report_write_scratch && e->report_write_scratch_release) e->report_write_scratch_release(e->report_write_scratch);
-    return YACRD_OK;
-}
-
 void yacrd_reads_free(yacrd_reads *r)
 {
     if (!r) return;
@@ -657,25 +643,20 @@ int ingest_text(yacrd_engine *e, const TextSource &src, u64 n, bool m4, int n_th
 
 extern "C" {
 
-static int ingest_format(const char *path, int format, bool &m4) { return overlap_format(path, format, m4); }
-
 int yacrd_engine_ingest_overlaps(yacrd_engine *e, const char *path, int format, int n_threads, uint32_t coverage,
                                  double not_coverage, yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats)
 {
     if (!e || !path || !out || !reads) return fail(YACRD_EINVAL, "null argument");
     e->resident.valid = false;
     bool m4 = false;
-    if (const int rcf = ingest_format(path, format, m4)) return rcf;
+    if (const int rcf = overlap_format(path, format, m4)) return rcf;
     std::memset(out, 0, sizeof(*out));
     std::memset(reads, 0, sizeof(*reads));
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (e->pending.active || e->host_pending) return fail(YACRD_EINVAL, "the engine has a submitted batch pending");
     const int fd = ::open(path, O_RDONLY);
     if (fd < 0) return fail(YACRD_EINVAL, std::string("cannot open ") + path);
-    struct FdGuard {
-        int fd;
-        ~FdGuard() { ::close(fd); }
-    } fdg{fd};
+    FdGuard fdg{fd};
     struct stat st;
     if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) return fail(YACRD_EFALLBACK, "not a regular file: the host parser reads it");
     // gzip / bzip2 / xz: not text — the caller inflates the file (yacrd_text_from_file, libyacrd_host) and hands the text to
@@ -685,8 +666,8 @@ int yacrd_engine_ingest_overlaps(yacrd_engine *e, const char *path, int format, 
     TextSource src;
     src.fd = fd;
     const int rc = ingest_text(e, src, (u64)st.st_size, m4, n_threads, coverage, not_coverage, out, reads, stats);
-    if (rc == YACRD_OK && e->paf_scratch) { // the whole file lies in the mirror: the overlap editor may start from it (gpu_edit.hip)
-        e->mirror.p = static_cast<Scratch *>(e->paf_scratch)->text.as<unsigned char>();
+    if (rc == YACRD_OK) { // the whole file lies in the mirror: the overlap editor may start from it (gpu_edit.hip)
+        e->mirror.p = scratch_of<Scratch>(e)->text.as<unsigned char>(); // (ingest_text made the scratch)
         e->mirror.n = (u64)st.st_size;
         e->mirror.dev = (u64)st.st_dev, e->mirror.ino = (u64)st.st_ino;
         e->mirror.mtime_s = (int64_t)st.st_mtim.tv_sec, e->mirror.mtime_ns = (int64_t)st.st_mtim.tv_nsec;
@@ -701,7 +682,7 @@ int yacrd_engine_ingest_overlaps_mem(yacrd_engine *e, const char *text, uint64_t
     if (!e || (!text && n) || !out || !reads) return fail(YACRD_EINVAL, "null argument");
     e->resident.valid = false;
     bool m4 = false;
-    if (const int rcf = ingest_format(nullptr, format, m4)) return rcf;
+    if (const int rcf = overlap_format(nullptr, format, m4)) return rcf;
     std::memset(out, 0, sizeof(*out));
     std::memset(reads, 0, sizeof(*reads));
     if (stats) std::memset(stats, 0, sizeof(*stats));
@@ -715,15 +696,6 @@ int yacrd_engine_ingest_overlaps_mem(yacrd_engine *e, const char *text, uint64_t
 
 namespace {
 
-// (allocating and freeing ~0.8 GB of HBM per call cost 1.5 ms of a 15 ms run: the buffers stay with the engine)
-Scratch *scratch_of(yacrd_engine *e)
-{
-    if (!e->paf_scratch) {
-        e->paf_scratch = new (std::nothrow) Scratch();
-        e->paf_scratch_free = [](void *p) { delete static_cast<Scratch *>(p); };
-    }
-    return static_cast<Scratch *>(e->paf_scratch);
-}
 
 // Bytes [begin, begin + len) of the text -> on the engine: the overlap records of the lines that START there (handles = id-table
 // slots), the table, and the range's reads numbered by first appearance INSIDE the range: S.map (slot -> read), S.keys2 (first
@@ -737,7 +709,7 @@ struct RangeOut {
 int parse_range(yacrd_engine *e, const TextSource &src, u64 file_n, u64 begin, u64 len, bool skip_head, bool m4, int n_threads, RangeOut &ro)
 {
     DeviceGuard guard(e->device);
-    Scratch *Sp = scratch_of(e);
+    Scratch *Sp = scratch_of<Scratch>(e);
     if (!Sp) return fail(YACRD_ENOMEM, "host allocation failed");
     Scratch &S = *Sp;
     e->mirror.valid = false; // (the mirror is about to be rewritten)
@@ -918,7 +890,7 @@ int ingest_text(yacrd_engine *e, const TextSource &src, u64 n, bool m4, int n_th
     DeviceGuard guard(e->device);
     RangeOut ro;
     if (const int rcp = parse_range(e, src, n, 0, n, false, m4, n_threads, ro)) return rcp;
-    Scratch &S = *static_cast<Scratch *>(e->paf_scratch);
+    Scratch &S = *scratch_of<Scratch>(e); // (parse_range made it)
     const u32 R = ro.R;
     const u64 n_recs = ro.n_recs, cap = ro.cap, name_bytes = ro.name_bytes;
     const double t_start = ro.t_start, t_text = ro.t_text, t_parse = ro.t_parse;
@@ -1029,7 +1001,7 @@ PeerRoute route_between(int to_dev, int from_dev)
 }
 // the staged route: two pinned buffers per destination engine, a piece flies host -> device while the next one is fetched
 struct StageBuf {
-    void *p[2] = {nullptr, nullptr};
+    PinBuf pin[2];
     hipEvent_t ev[2] = {nullptr, nullptr};
     bool busy[2] = {false, false};
     hipStream_t from_stream = nullptr;
@@ -1037,7 +1009,7 @@ struct StageBuf {
     ~StageBuf()
     {
         for (int i = 0; i < 2; i++) {
-            if (p[i]) (void)hipHostFree(p[i]);
+            pin[i].release();
             if (ev[i]) (void)hipEventDestroy(ev[i]);
         }
         if (from_stream) {
@@ -1051,7 +1023,7 @@ hipError_t copy_staged(yacrd_engine *to, void *dst, yacrd_engine *from, const vo
 {
     StageBuf sb; // (per call: the route is a fallback, its setup cost is not what matters on it)
     for (int i = 0; i < 2; i++) {
-        hipError_t er = hipHostMalloc(&sb.p[i], std::min(bytes, kStagePiece));
+        hipError_t er = sb.pin[i].reserve(std::min(bytes, kStagePiece));
         if (er == hipSuccess) er = hipEventCreateWithFlags(&sb.ev[i], hipEventDisableTiming);
         if (er != hipSuccess) return er;
     }
@@ -1070,11 +1042,11 @@ hipError_t copy_staged(yacrd_engine *to, void *dst, yacrd_engine *from, const vo
         }
         {
             DeviceGuard guard(from->device); // device -> host runs on the SOURCE device's stream
-            hipError_t er = hipMemcpyAsync(sb.p[turn], (const char *)src + at, m, hipMemcpyDeviceToHost, sb.from_stream);
+            hipError_t er = hipMemcpyAsync(sb.pin[turn].p, (const char *)src + at, m, hipMemcpyDeviceToHost, sb.from_stream);
             if (er == hipSuccess) er = hipStreamSynchronize(sb.from_stream);
             if (er != hipSuccess) return er;
         }
-        hipError_t er = hipMemcpyAsync((char *)dst + at, sb.p[turn], m, hipMemcpyHostToDevice, to->stream);
+        hipError_t er = hipMemcpyAsync((char *)dst + at, sb.pin[turn].p, m, hipMemcpyHostToDevice, to->stream);
         if (er == hipSuccess) er = hipEventRecord(sb.ev[turn], to->stream);
         if (er != hipSuccess) return er;
         sb.busy[turn] = true;
@@ -1105,7 +1077,7 @@ int ingest_text_group(yacrd_engine *const *E, uint32_t N, const TextSource &src,
     std::vector<u64> B(N + 1);
     for (uint32_t d = 0; d <= N; d++) B[d] = std::min<u64>(n, (u64)d * per * kChunk);
     for (uint32_t d = 0; d < N; d++)
-        if (!scratch_of(E[d])) return fail(YACRD_ENOMEM, "host allocation failed"); // (every later scratch_of(E[d]) finds it)
+        if (!scratch_of<Scratch>(E[d])) return fail(YACRD_ENOMEM, "host allocation failed"); // (every later scratch_of finds it)
     // ---- does it fit?  Answered here, before anything is allocated or moved (parse_range's own check knows only
     // its range).  Per DEVICE: what its engines' ranges need for the parse (text, records, id table, CSR and region slots of
     // as many reads: ~2.6 x the range, parse_range) plus the records every one of its engines gathers from ranges parsed on
@@ -1121,7 +1093,7 @@ int ingest_text_group(yacrd_engine *const *E, uint32_t N, const TextSource &src,
             uint32_t engines_here = 0;
             for (uint32_t k = 0; k < N; k++)
                 if (E[k]->device == dev) {
-                    Scratch &Sk = *scratch_of(E[k]);
+                    Scratch &Sk = *scratch_of<Scratch>(E[k]);
                     here += (double)(B[k + 1] - B[k]);
                     held += (double)Sk.text.cap + (double)Sk.recs.cap + (double)E[k]->stage.cap + (double)E[k]->in_iv.cap + (double)Sk.gather.cap;
                     engines_here++;
@@ -1179,7 +1151,7 @@ int ingest_text_group(yacrd_engine *const *E, uint32_t N, const TextSource &src,
 
     // ---- the merge, on engine 0
     yacrd_engine *e0 = E[0];
-    Scratch &S0 = *scratch_of(e0);
+    Scratch &S0 = *scratch_of<Scratch>(e0);
     std::vector<u64> eb(A + 1, 0), nb(A + 1, 0);
     for (uint32_t d = 0; d < A; d++) eb[d + 1] = eb[d] + ro[d].R, nb[d + 1] = nb[d] + ro[d].name_bytes;
     const u64 M = eb[A], NB = nb[A];
@@ -1204,7 +1176,7 @@ int ingest_text_group(yacrd_engine *const *E, uint32_t N, const TextSource &src,
         HIP_TRY(S0.g_slot_read.reserve((size_t)capG * sizeof(u32)));
         HIP_TRY(S0.ctl.reserve(64));
         for (uint32_t d = 0; d < A; d++) {
-            Scratch &Sd = *scratch_of(E[d]);
+            Scratch &Sd = *scratch_of<Scratch>(E[d]);
             const size_t R = ro[d].R;
             HIP_TRY(copy_between(e0, S0.m_fp.as<u64>() + eb[d], E[d], Sd.keys2.p, R * sizeof(u64)));
             HIP_TRY(copy_between(e0, S0.m_len.as<u32>() + eb[d], E[d], E[d]->in_len.p, R * sizeof(u32)));
@@ -1298,7 +1270,7 @@ int ingest_text_group(yacrd_engine *const *E, uint32_t N, const TextSource &src,
     rc = run_all(A, [&](uint32_t d) -> int {
         yacrd_engine *e = E[d];
         DeviceGuard guard(e->device);
-        Scratch &S = *scratch_of(e);
+        Scratch &S = *scratch_of<Scratch>(e);
         const size_t R = ro[d].R;
         HIP_TRY(S.gmap.reserve((size_t)(std::max<u64>(R, Rg) + 4) * sizeof(u32)));
         HIP_TRY(copy_between(e, S.gmap.p, e0, S0.m_read.as<u32>() + eb[d], R * sizeof(u32)));
@@ -1321,7 +1293,7 @@ int ingest_text_group(yacrd_engine *const *E, uint32_t N, const TextSource &src,
     rc = run_all(N, [&](uint32_t o) -> int {
         yacrd_engine *e = E[o];
         DeviceGuard guard(e->device);
-        Scratch &S = *scratch_of(e);
+        Scratch &S = *scratch_of<Scratch>(e);
         const u32 lo = cut[o], hi = cut[o + 1], Ro = hi - lo;
         std::vector<RecSlab> slabs(A);
         u64 foreign = 0;
@@ -1333,7 +1305,7 @@ int ingest_text_group(yacrd_engine *const *E, uint32_t N, const TextSource &src,
         HIP_TRY(S.gather.reserve((size_t)foreign * sizeof(yk::OvlRec) + 64));
         u64 at = 0;
         for (uint32_t d = 0; d < A; d++) {
-            Scratch &Sd = *scratch_of(E[d]);
+            Scratch &Sd = *scratch_of<Scratch>(E[d]);
             if (!elsewhere(d)) {
                 slabs[d] = RecSlab{Sd.recs.as<yk::OvlRec>(), ro[d].n_recs};
             } else {
@@ -1447,13 +1419,10 @@ int yacrd_engines_ingest_overlaps(yacrd_engine *const *engines, uint32_t n_engin
     if (n_engines == 1) return yacrd_engine_ingest_overlaps(engines[0], path, format, n_threads, coverage, not_coverage, out, reads, stats);
     if (!path) return fail(YACRD_EINVAL, "null argument");
     bool m4 = false;
-    if (const int rcf = ingest_format(path, format, m4)) return rcf;
+    if (const int rcf = overlap_format(path, format, m4)) return rcf;
     const int fd = ::open(path, O_RDONLY);
     if (fd < 0) return fail(YACRD_EINVAL, std::string("cannot open ") + path);
-    struct FdGuard {
-        int fd;
-        ~FdGuard() { ::close(fd); }
-    } fdg{fd};
+    FdGuard fdg{fd};
     struct stat st;
     if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) return fail(YACRD_EFALLBACK, "not a regular file: the host parser reads it");
     if (is_compressed_magic(fd))
@@ -1474,7 +1443,7 @@ int yacrd_engines_ingest_overlaps_mem(yacrd_engine *const *engines, uint32_t n_e
         return yacrd_engine_ingest_overlaps_mem(engines[0], text, n, format, n_threads, coverage, not_coverage, out, reads, stats);
     if (!text && n) return fail(YACRD_EINVAL, "null argument");
     bool m4 = false;
-    if (const int rcf = ingest_format(nullptr, format, m4)) return rcf;
+    if (const int rcf = overlap_format(nullptr, format, m4)) return rcf;
     TextSource src;
     src.mem = text ? text : "";
     const int rc = ingest_text_group(engines, n_engines, src, n, m4, n_threads, coverage, not_coverage, out, reads, stats);

@@ -318,6 +318,7 @@ __global__ __launch_bounds__(256) void rp_fill_kernel(const unsigned char *t, u6
 namespace {
 
 struct ReportScratch { // the reader's buffers; they stay with the engine (grow-only), go with yacrd_engine_trim / destroy
+    static constexpr yacrd_engine::Slot kScratchSlot = yacrd_engine::kReport;
     DevBuf text, tile_lines, tile_ord, lines, line_slot, line_idlen, claim, first, last, flag, number, reads, n_reg, name_len, name_off, names,
         ctl, part;
     std::vector<DevBuf *> all()
@@ -331,21 +332,12 @@ struct ReportScratch { // the reader's buffers; they stay with the engine (grow-
     }
     ~ReportScratch() { release(); }
 };
-ReportScratch *report_scratch_of(yacrd_engine *e)
-{
-    if (!e->report_scratch) {
-        e->report_scratch = new (std::nothrow) ReportScratch();
-        e->report_scratch_free = [](void *p) { delete static_cast<ReportScratch *>(p); };
-        e->report_scratch_release = [](void *p) { static_cast<ReportScratch *>(p)->release(); };
-    }
-    return static_cast<ReportScratch *>(e->report_scratch);
-}
 
 int read_report(yacrd_engine *e, const TextSource &src, u64 n, int n_threads, double not_coverage, yacrd_result *out, yacrd_reads *reads,
                 yacrd_ingest_stats *stats)
 {
     DeviceGuard guard(e->device);
-    ReportScratch *Sp = report_scratch_of(e);
+    ReportScratch *Sp = scratch_of<ReportScratch>(e);
     if (!Sp) return fail(YACRD_ENOMEM, "host allocation failed");
     ReportScratch &S = *Sp;
     e->resident.valid = false;
@@ -534,10 +526,7 @@ int yacrd_engine_ingest_report(yacrd_engine *e, const char *path, int n_threads,
     if (!path) return fail(YACRD_EINVAL, "null argument");
     const int fd = ::open(path, O_RDONLY);
     if (fd < 0) return fail(YACRD_EFALLBACK, std::string("cannot open ") + path + ": the host reader words the error");
-    struct FdGuard {
-        int fd;
-        ~FdGuard() { ::close(fd); }
-    } fdg{fd};
+    FdGuard fdg{fd};
     struct stat st;
     if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) return fail(YACRD_EFALLBACK, "not a regular file: the host reader reads it");
     if (is_compressed_magic(fd))

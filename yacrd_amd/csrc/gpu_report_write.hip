@@ -22,11 +22,11 @@
 // are read twice, 8 bytes per region and 12 per read are written beside the text.  The text then goes home in segments
 // through two pinned buffers: segment i + 1 crosses the link while segment i is written.
 #include "engine_internal.h"
+#include "host/beside_file.h"
 #include "host/segment_pump.h"
 
 #include <algorithm>
 #include <cerrno>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -195,20 +195,17 @@ u64 report_segment()
     return kReportSegment;
 }
 
-double rw_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 struct ReportWriteScratch { // the writer's buffers; they stay with the engine (grow-only), go with yacrd_engine_trim / destroy
+    static constexpr yacrd_engine::Slot kScratchSlot = yacrd_engine::kReportWrite;
     DevBuf names, name_off, lengths, bad_off, regions, type, piece_len, owner, head_len, P, H, text, ctl, part;
-    void *pin = nullptr; // two segments
-    size_t pin_cap = 0;
+    PinBuf pin; // two segments
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; // in front of the upload, behind it, behind the kernels
     hipEvent_t dma[2] = {nullptr, nullptr};         // a pinned buffer has landed
     std::vector<DevBuf *> all() { return {&names, &name_off, &lengths, &bad_off, &regions, &type, &piece_len, &owner, &head_len, &P, &H, &text, &ctl, &part}; }
     void release()
     {
         for (DevBuf *b : all()) b->release();
-        if (pin) (void)hipHostFree(pin);
-        pin = nullptr, pin_cap = 0;
+        pin.release();
     }
     ~ReportWriteScratch()
     {
@@ -219,17 +216,8 @@ struct ReportWriteScratch { // the writer's buffers; they stay with the engine (
             if (x) (void)hipEventDestroy(x);
     }
 };
-ReportWriteScratch *scratch_of(yacrd_engine *e)
-{
-    if (!e->report_write_scratch) {
-        e->report_write_scratch = new (std::nothrow) ReportWriteScratch();
-        e->report_write_scratch_free = [](void *p) { delete static_cast<ReportWriteScratch *>(p); };
-        e->report_write_scratch_release = [](void *p) { static_cast<ReportWriteScratch *>(p)->release(); };
-    }
-    return static_cast<ReportWriteScratch *>(e->report_write_scratch);
-}
 
-using yseg::Sink; // where the text goes: a file descriptor or memory the caller sized (host/segment_pump.h)
+using yseg::Sink; // where the text goes: a file descriptor or memory sized for it (host/segment_pump.h)
 
 // The table -> its text in S.text; *total its size.  Nothing has left the device when this returns.
 int format_report(yacrd_engine *e, ReportWriteScratch &S, const yacrd_report_table *t, u64 *total, yacrd_report_write_stats *st)
@@ -332,12 +320,7 @@ int send_home(yacrd_engine *e, ReportWriteScratch &S, u64 total, Sink &sink, dou
 {
     if (!total) return YACRD_OK;
     const u64 seg = std::min<u64>(report_segment(), total);
-    if (S.pin_cap < 2 * seg) {
-        if (S.pin) (void)hipHostFree(S.pin);
-        S.pin = nullptr, S.pin_cap = 0;
-        HIP_TRY(hipHostMalloc(&S.pin, (size_t)(2 * seg)));
-        S.pin_cap = (size_t)(2 * seg);
-    }
+    HIP_TRY(S.pin.reserve((size_t)(2 * seg)));
     // (the loop and its segment arithmetic: host/segment_pump.h, which a stand-alone program runs under the sanitizers)
     struct Dma {
         yacrd_engine *e;
@@ -352,10 +335,10 @@ int send_home(yacrd_engine *e, ReportWriteScratch &S, u64 total, Sink &sink, dou
         bool wait(u64 i) { return (bad = hipEventSynchronize(S.dma[i & 1])) == hipSuccess; }
         void drain() { (void)hipStreamSynchronize(e->stream); }
     } dma{e, S};
-    const int rc = yseg::pump(total, seg, (char *)S.pin, dma, sink, [&](auto put) {
-        const double t0 = rw_now_ms();
+    const int rc = yseg::pump(total, seg, S.pin.as<char>(), dma, sink, [&](auto put) {
+        const double t0 = now_ms();
         put();
-        *out_ms += rw_now_ms() - t0;
+        *out_ms += now_ms() - t0;
     });
     if (rc == yseg::kLinkFailed) HIP_TRY(dma.bad);
     if (rc == yseg::kSinkFailed) return fail(YACRD_EINVAL, "Error while writing the yacrd report");
@@ -398,34 +381,23 @@ int yacrd_engine_write_report(yacrd_engine *e, const yacrd_report_table *t, cons
     if (exists && (ost.st_nlink > 1 || ::access(out_path, W_OK) != 0))
         return fail(YACRD_EFALLBACK, "the output may not be written or has other hard links: the host writer writes it in place");
     // (the file is made first: a place where none can be created costs no pass over the table)
-    std::string tmp = std::string(out_path) + ".XXXXXX";
-    const int ofd = mkstemp(&tmp[0]);
-    if (ofd < 0) return fail(YACRD_EFALLBACK, std::string("cannot create a file beside ") + out_path + ": the host writer words the error");
-    if (exists) {
-        (void)fchmod(ofd, ost.st_mode & 07777);
-    } else {
-        const mode_t um = umask(0);
-        umask(um);
-        (void)fchmod(ofd, 0666 & ~um);
-    }
+    yseg::BesideFile file; // (gone again on every way out but the last)
+    if (!file.open(out_path, exists ? &ost : nullptr))
+        return fail(YACRD_EFALLBACK, std::string("cannot create a file beside ") + out_path + ": the host writer words the error");
     DeviceGuard guard(e->device);
-    ReportWriteScratch *Sp = scratch_of(e);
+    ReportWriteScratch *Sp = scratch_of<ReportWriteScratch>(e);
     u64 total = 0;
     if (const int rcf = Sp ? format_report(e, *Sp, t, &total, st) : fail(YACRD_ENOMEM, "host allocation failed")) {
         (void)hipGetLastError();
-        (void)::close(ofd);
-        (void)::unlink(tmp.c_str());
         if (st) std::memset(st, 0, sizeof(*st));
         return rcf;
     }
     Sink sink;
-    sink.fd = ofd;
+    sink.fd = file.fd;
     double out_ms = 0;
     int rc = send_home(e, *Sp, total, sink, &out_ms);
-    if (::close(ofd) != 0 && rc == YACRD_OK) rc = fail(YACRD_EINVAL, "Error while writing the yacrd report");
-    if (rc == YACRD_OK && ::rename(tmp.c_str(), out_path) != 0) rc = fail(YACRD_EINVAL, "Error while writing the yacrd report");
+    if (rc == YACRD_OK && !file.commit()) rc = fail(YACRD_EINVAL, "Error while writing the yacrd report");
     if (rc != YACRD_OK) {
-        (void)::unlink(tmp.c_str());
         if (st) std::memset(st, 0, sizeof(*st));
         return rc;
     }
@@ -439,7 +411,7 @@ int yacrd_engine_write_report_mem(yacrd_engine *e, const yacrd_report_table *t, 
     if (!out || !out_bytes) return fail(YACRD_EINVAL, "null argument");
     *out = nullptr, *out_bytes = 0;
     DeviceGuard guard(e->device);
-    ReportWriteScratch *Sp = scratch_of(e);
+    ReportWriteScratch *Sp = scratch_of<ReportWriteScratch>(e);
     if (!Sp) return fail(YACRD_ENOMEM, "host allocation failed");
     u64 total = 0;
     int rc = format_report(e, *Sp, t, &total, st);

@@ -1,6 +1,7 @@
-// gpu_text.h — what the translation units that work on overlap TEXT in HBM share: gpu_paf.hip (the device parser) and
-// gpu_edit.hip (filter / extract on overlap files).  Where the text comes from, the mover (pread -> pinned 4 MiB chunks
-// -> the mirror in HBM, a segment handed on as soon as it has landed), the staged-window accessor and the id hash.
+// gpu_text.h — what the translation units that work on TEXT in HBM share: gpu_paf.hip (the device parser), gpu_edit.hip
+// (filter / extract on overlap files), gpu_report.hip (the report reader) and gpu_deflate.hip.  Where the text comes from
+// (TextSource, FdGuard, the format rule), the mover (pread -> pinned 4 MiB chunks -> the mirror in HBM, a segment handed on
+// as soon as it has landed), the staged-window accessor, the byte matcher and the id hash.
 #pragma once
 #include "engine_internal.h"
 
@@ -12,7 +13,6 @@
 #include <algorithm>
 #include <atomic>
 #include <cerrno>
-#include <chrono>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -71,11 +71,6 @@ __device__ __forceinline__ u64 gp_hash(const Text &t, u64 p, u32 n)
 
 namespace yke {
 
-inline double now_ms()
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 // gzip / bzip2 / xz (the magic bytes niffler looks at, src/util.rs:57-70)
 inline bool is_compressed_magic(int fd)
 {
@@ -99,6 +94,11 @@ inline int overlap_format(const char *path, int format, bool &m4)
     m4 = format == 2;
     return YACRD_OK;
 }
+
+struct FdGuard { // closes the input when the call returns
+    int fd;
+    ~FdGuard() { ::close(fd); }
+};
 
 // where the text comes from: a file (pread) or memory (a compressed file the host has inflated)
 struct TextSource {
@@ -141,27 +141,15 @@ int move_text(yacrd_engine *e, const TextSource &src, u64 begin, u64 n, char *mi
     unsigned T = n_threads > 0 ? (unsigned)n_threads : 6u; // (more threads only get in each other's way: 367 MB in 10 ms with 4-8)
     T = (unsigned)std::max<size_t>(1, std::min<size_t>(std::min(T, 32u), std::max<size_t>(n_chunks, 1)));
     const size_t n_buf = (size_t)2 * T;
-    if (e->paf_arena_cap < n_buf * kChunk) {
-        if (e->paf_arena) (void)hipHostFree(e->paf_arena);
-        e->paf_arena = nullptr;
-        e->paf_arena_cap = 0;
-        if (hipHostMalloc(&e->paf_arena, n_buf * kChunk) != hipSuccess) {
-            e->paf_arena = nullptr;
-            return 3;
-        }
-        e->paf_arena_cap = n_buf * kChunk;
-    }
-    char *arena = (char *)e->paf_arena;
-    std::vector<hipStream_t> copy(T, nullptr);
-    std::vector<hipEvent_t> ev(n_chunks, nullptr); // one per chunk: recorded behind its copy
+    if (e->paf_arena.reserve(n_buf * kChunk) != hipSuccess) return 3;
+    char *arena = e->paf_arena.as<char>();
+    Events ev; // one per chunk: recorded behind its copy
+    Streams copy;
     std::unique_ptr<std::atomic<int>[]> landed(new std::atomic<int>[n_chunks + 1]);
     for (size_t c = 0; c <= n_chunks; c++) landed[c].store(0);
     std::atomic<size_t> next(0);
     std::atomic<int> bad(0);
-    for (unsigned t = 0; t < T; t++)
-        if (hipStreamCreateWithFlags(&copy[t], hipStreamNonBlocking) != hipSuccess) bad = 1;
-    for (size_t c = 0; c < n_chunks; c++)
-        if (hipEventCreateWithFlags(&ev[c], hipEventDisableTiming) != hipSuccess) bad = 1;
+    if (!copy.add(T) || !ev.add(n_chunks, hipEventDisableTiming)) bad = 1;
     auto work = [&](unsigned t) { // thread t owns buffers 2t and 2t + 1: one fills while the other flies
         if (hipSetDevice(e->device) != hipSuccess) bad = 1;
         long prev[2] = {-1, -1}; // the chunk that last flew from each buffer
@@ -185,7 +173,7 @@ int move_text(yacrd_engine *e, const TextSource &src, u64 begin, u64 n, char *mi
             prev[turn] = (long)c;
             landed[c].store(1, std::memory_order_release); // (its event is recorded: the dispatcher may wait on it)
         }
-        if (copy[t]) (void)hipStreamSynchronize(copy[t]);
+        (void)hipStreamSynchronize(copy[t]);
     };
     std::vector<std::thread> th;
     if (!bad.load())
@@ -207,11 +195,8 @@ int move_text(yacrd_engine *e, const TextSource &src, u64 begin, u64 n, char *mi
         on_segment((u64)c0 * kChunk, (u64)c1 * kChunk, std::min<u64>(n, (u64)need * kChunk));
     }
     for (auto &x : th) x.join();
-    for (hipStream_t s2 : copy)
-        if (s2) (void)hipStreamDestroy(s2);
-    if (bad.load()) (void)hipStreamSynchronize(e->stream); // (kernels may still wait on events about to go)
-    for (hipEvent_t x : ev)
-        if (x) (void)hipEventDestroy(x);
+    copy.clear();
+    if (bad.load()) (void)hipStreamSynchronize(e->stream); // (kernels may still wait on events about to go, with `ev`)
     (void)hipGetLastError();
     return bad.load();
 }

@@ -42,11 +42,6 @@ unsigned usable_cpus()
     return n;
 }
 
-double now_ms()
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 enum { BUF_FREE = 0, BUF_HELD = 1, BUF_FLYING = 2 };
 
 } // namespace
