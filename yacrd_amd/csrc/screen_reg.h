@@ -24,7 +24,8 @@ namespace yk {
 //     two order statistics lie in when the dovetail overlaps end within a few dozen positions of each
 //     other (at exactly 0 / len in SURVEY.md §8d's clamped generator, spread by the overlapper's
 //     chain ends in real data);
-//   * NB = LANES coarse bins of 2^sh positions, one per lane, for every other event.
+//   * NB coarse bins of 2^sh positions, NB / LANES per lane, for every other event (one per lane, except in the
+//     long launch's H16 form: 32 blocks on 16 lanes, below).
 // Every interval must be at least W long (anything shorter: deferred): then no end lies inside the head
 // window and no start inside the tail window, in event order the read is [head window: F starts]
 // [coarse bins][tail window: G ends], and a coarse-counted start of bin i has at least
@@ -41,8 +42,15 @@ namespace yk {
 #define YK_SCREEN_WINDOW 32
 #endif
 constexpr int kScreenWindow = YK_SCREEN_WINDOW; // W: positions per window (a multiple of 32)
-// per group: W head-window bins + LANES coarse blocks + W tail-window bins, 16 bytes (four copies) each
+// per group: W head-window bins + NB coarse blocks + W tail-window bins, 16 bytes (four copies) each
 constexpr int kScreenTabWords = (64 / 16) * (16 + 2 * kScreenWindow) * 4;
+// H16 ROWS (the long launch's H16 form): an H16 read on ONE 16-lane row, sixteen intervals per lane, so that
+// a wavefront screens its four reads as one item and pays the per-item instructions (addresses, zeroing, window reads,
+// the row scans, the verdict) once per four reads instead of once per two.  The read keeps its 32 coarse blocks, two
+// per lane: with 16 blocks (NB = LANES) the depth test fails on 29 % more of the clamped generator's reads and on twice
+// as many at sigma = 100, and those go to the follow-on sort.  Table, sh, a, b, F, G and the depth test are the 32-lane
+// form's, so both forms decide and defer the same reads.  Four groups of 2 W + 32 bins:
+constexpr int kScreenTabWordsRows = (64 / 16) * (32 + 2 * kScreenWindow) * 4;
 template <int WPB, int WORDS = kScreenTabWords> // wavefronts per workgroup; words per wavefront (a kernel of 32-lane groups only needs 768)
 __device__ __forceinline__ u32 *wave_screen_scratch()
 {
@@ -136,16 +144,19 @@ constexpr int kScreenSlides = YK_SCREEN_SLIDES;
 // blocks (where all of a block's ends count as popped before the block's starts).  Dovetail ends spread by hundreds of
 // positions fill the read's last blocks with such ends: 8 % of configs[1]'s reads at sigma = 300 failed the depth test on
 // them alone (tests/formulation.py: tail_ramp; emulation on the generator's reads 91.3 -> 98.3 % decided).
-template <int LANES, int WPB, bool SLID = false, int TABW = kScreenTabWords>
-__device__ __forceinline__ bool healthy_screen(const uint4 (&v)[4], const bool (&real0)[4], const bool (&real1)[4],
+// NB: coarse blocks of the read (a multiple of LANES; a lane owns NB / LANES consecutive ones).  PAIRS: 16-byte pairs of
+// intervals per lane (the caller's array extent).
+template <int LANES, int WPB, bool SLID = false, int TABW = kScreenTabWords, int NB = LANES, int PAIRS = 4>
+__device__ __forceinline__ bool healthy_screen(const uint4 (&v)[PAIRS], const bool (&real0)[PAIRS], const bool (&real1)[PAIRS],
                                                u32 len, i32 c, u32 pmin, u32 pmax, HealthyRead &hr, u32 P = 0, u32 Q = 0,
                                                u32 emin = 0, u32 smax = 0xFFFFFFFFu)
 {
-    constexpr int NB = LANES, W = kScreenWindow, NBIN = 2 * W + NB, GROUPS = 64 / LANES, PER = W / LANES,
-                  ZPER = NBIN / LANES;
+    constexpr int W = kScreenWindow, NBIN = 2 * W + NB, GROUPS = 64 / LANES, PER = W / LANES, ZPER = NBIN / LANES,
+                  CPL = NB / LANES;
     constexpr u32 kEnd = 1u << 10, kField = kEnd - 1u;
     static_assert(W % LANES == 0 && PER >= 1 && W <= 64, "window bins per lane; a window index has six bits");
-    static_assert(NBIN % LANES == 0 && GROUPS * NBIN * 4 <= TABW, "scratch");
+    static_assert(NB % LANES == 0 && NBIN % LANES == 0 && GROUPS * NBIN * 4 <= TABW, "scratch");
+    static_assert(PAIRS * 2 * LANES <= 256, "a counter field has ten bits");
     const u32 lane = lane_id(), lig = lane & (u32)(LANES - 1), grp = lane / (u32)LANES;
     u32 *tab = wave_screen_scratch<WPB, TABW>() + grp * (u32)(NBIN * 4);
     uint4 *bins = reinterpret_cast<uint4 *>(tab);
@@ -183,7 +194,7 @@ __device__ __forceinline__ bool healthy_screen(const uint4 (&v)[4], const bool (
         }
     };
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
+    for (int j = 0; j < PAIRS; j++) {
         count(v[j].x, v[j].y, real0[j]);
         count(v[j].z, v[j].w, real1[j]);
     }
@@ -200,7 +211,14 @@ __device__ __forceinline__ bool healthy_screen(const uint4 (&v)[4], const bool (
         f[q] = ((h4.x + h4.y + h4.z + h4.w) & kField) | ((t4.x + t4.y + t4.z + t4.w) & (kField << 10));
         fw += f[q];
     }
-    const uint4 c4 = bins[(u32)W + lig];
+    // this lane's coarse blocks lig * CPL + q, starts | ends << 10 each
+    u32 wb[CPL], w = 0;
+#pragma unroll
+    for (int q = 0; q < CPL; q++) {
+        const uint4 c4 = bins[(u32)W + lig * (u32)CPL + q];
+        wb[q] = (c4.x + c4.y + c4.z + c4.w) & ((kField << 10) | kField);
+        w += wb[q];
+    }
     const u32 fincl = gscan_add<LANES>(fw); // last lane: F | G << 10
     // a - pmin = the number of window positions whose running count of starts is still below c + 1 (the
     // counts only grow), pmax - b likewise for the ends: both fields at once — adding 512 - (c + 1) to a
@@ -220,12 +238,18 @@ __device__ __forceinline__ bool healthy_screen(const uint4 (&v)[4], const bool (
     const u32 cand = (((u32)PER - ((reached >> 9) & 7u)) << 20) | (((u32)PER - (reached >> 19)) << 26);
     // ---- the coarse bins: a block that holds a coarse-counted start must have more than c intervals
     // open at its head even after all of its ends: F + (starts before it) - (ends up to its last one) > c.
-    // One scan for the counts and the two window indices (each set in one lane only).
-    const u32 w = (c4.x + c4.y + c4.z + c4.w) & ((kField << 10) | kField);
+    // One scan over the lanes' sums for the counts and the two window indices (each set in one lane only); a lane with
+    // several blocks walks them from its exclusive total and hands the scan of minima the shallowest one.
     const u32 wincl = gscan_add<LANES>(w | cand);
-    const u32 ex = wincl - w;
-    const i32 x = (i32)(ex & kField) - (i32)((wincl >> 10) & kField); // starts before - ends through this block
-    const u32 xm = gscan_min<LANES>((w & kField) != 0u ? (u32)(x + 0x10000) : 0xFFFFFFFFu);
+    u32 run = wincl - w, xl = 0xFFFFFFFFu;
+#pragma unroll
+    for (int q = 0; q < CPL; q++) {
+        const u32 ex = run;
+        run += wb[q];
+        const i32 x = (i32)(ex & kField) - (i32)((run >> 10) & kField); // starts before - ends through this block
+        xl = min(xl, (wb[q] & kField) != 0u ? (u32)(x + 0x10000) : 0xFFFFFFFFu);
+    }
+    const u32 xm = gscan_min<LANES>(xl);
     // (meaningful in the group's last lane from here on)
     const i32 F = (i32)(fincl & kField) + (SLID ? (i32)P : 0), G = (i32)(fincl >> 10) + (SLID ? (i32)Q : 0);
     hr.F = F, hr.G = G;
@@ -266,12 +290,15 @@ struct ReadsKnown {
 };
 
 // ITEMS reads per lane group, given by their ids (active[t]: this group has a t-th read; a t with no active group in the
-// wavefront ends the loop).  WPB: wavefronts per workgroup (each has a table of its own in LDS).
-template <int LANES, int ITEMS, bool WIDE, int WPB = 1, class Sink>
+// wavefront ends the loop).  WPB: wavefronts per workgroup (each has a table of its own in LDS).  K: events per lane
+// (K / 4 pairs of intervals), NB: the read's coarse blocks, NT: the launch streams its intervals from HBM (non-temporal
+// loads), TABW: words of the wavefront's table (one size per kernel: every form in it shares the table).
+template <int LANES, int ITEMS, bool WIDE, int WPB = 1, int K = 16, int NB = LANES, bool NT = (ITEMS >= 2),
+          int TABW = kScreenTabWords, class Sink>
 __device__ __forceinline__ void screen_reads(const SweepArgs &a, const u32 (&r)[ITEMS], const bool (&active)[ITEMS], const Sink &sink,
                                              const ReadsKnown<ITEMS> *known = nullptr)
 {
-    constexpr int K = 16;
+    static_assert(K % 4 == 0, "a lane takes its intervals in pairs");
     const u32 lane = lane_id(), lig = lane & (u32)(LANES - 1);
     const i32 c = (i32)min(a.cov, 0x3FFFFFFFu);
     u32 n[ITEMS], len[ITEMS];
@@ -302,7 +329,7 @@ __device__ __forceinline__ void screen_reads(const SweepArgs &a, const u32 (&r)[
         const u32 last2 = two ? n[t] - 2u : 0u;
 #pragma unroll
         for (int j = 0; j < K / 4; j++)
-            v[t][j] = load_pair<(ITEMS >= 2)>(src + min(2u * (lig + (u32)LANES * j), last2)); // (two items: the launch streams from HBM)
+            v[t][j] = load_pair<NT>(src + min(2u * (lig + (u32)LANES * j), last2));
     }
 #pragma unroll
     for (int t = 0; t < ITEMS; t++) {
@@ -340,7 +367,7 @@ __device__ __forceinline__ void screen_reads(const SweepArgs &a, const u32 (&r)[
             real1[j] = i0 < n_eff;
         }
         HealthyRead hr;
-        bool healthy = healthy_screen<LANES, WPB, false, kScreenTabWords>(v[t], real0, real1, len[t], c, pmin, pmax, hr) && !girr;
+        bool healthy = healthy_screen<LANES, WPB, false, TABW, NB>(v[t], real0, real1, len[t], c, pmin, pmax, hr) && !girr;
         if constexpr (kScreenSlides > 0 && WIDE) {
             // a window that came up short of c + 1 (verdict in the group's last lane): slide it (see kScreenSlides).
             // st = need | F << 1 | G << 11 of the last screen (counts clipped to their ten bits)
@@ -381,7 +408,7 @@ __device__ __forceinline__ void screen_reads(const SweepArgs &a, const u32 (&r)[
                     for (int j = 0; j < K / 4; j++) r0[j] = real0[j] && go, r1[j] = real1[j] && go;
                     wave_lds_sync(); // (the table is zeroed again)
                     HealthyRead h2;
-                    const bool ok2 = healthy_screen<LANES, WPB, true, kScreenTabWords>(v[t], r0, r1, len[t], c, pmin + h0, pmax - t0, h2, PQ & 0xFFFFu, PQ >> 16, gemin, gsmax);
+                    const bool ok2 = healthy_screen<LANES, WPB, true, TABW, NB>(v[t], r0, r1, len[t], c, pmin + h0, pmax - t0, h2, PQ & 0xFFFFu, PQ >> 16, gemin, gsmax);
                     st = go ? state_of(!ok2 && (h2.F <= c || h2.G <= c), h2) : 0u; // (meaningful in the group's last lane)
                     if (go) healthy = ok2, hr.a = h2.a, hr.b = h2.b, hr.F = h2.F, hr.G = h2.G;
                 }
@@ -400,7 +427,7 @@ __device__ __forceinline__ void screen_reads(const SweepArgs &a, const u32 (&r)[
     }
 }
 
-template <int LANES, int ITEMS, bool WIDE = false>
+template <int LANES, int ITEMS, bool WIDE = false, int K = 16, int NB = LANES, bool NT = (ITEMS >= 2), int TABW = kScreenTabWords>
 __device__ __forceinline__ void screen_block(const SweepArgs &a, u32 block)
 {
     constexpr u32 GROUPS = 64 / LANES;
@@ -416,7 +443,7 @@ __device__ __forceinline__ void screen_block(const SweepArgs &a, u32 block)
         active[t] = idx < list_n;
         r[t] = active[t] ? a.list[idx] : 0u;
     }
-    screen_reads<LANES, ITEMS, WIDE>(a, r, active, VerdictsToGlobal{a});
+    screen_reads<LANES, ITEMS, WIDE, 1, K, NB, NT, TABW>(a, r, active, VerdictsToGlobal{a});
 }
 
 } // namespace yk

@@ -447,16 +447,21 @@ __device__ __forceinline__ void sweep_small_fused_body(const FusedArgs &f)
     a.list_n = f.list_n[e];
     a.first = f.first[e];
     const u32 b = g - first;
+    // the long launch (two items, no second looks): H16 reads four per wavefront on 16-lane rows (screen_reg.h: H16 ROWS);
+    // R16 keeps its two items of four reads on the same, larger table
+    constexpr bool ROWS = DEFER && ITEMS == 2 && !WIDE;
+    constexpr int TABW = ROWS ? kScreenTabWordsRows : kScreenTabWords;
     switch (f.cls[e]) { // the one-read-per-wavefront classes stay separate kernels (registers)
     case CLS_R2: sweep_group_block<16, 2, WPB>(a, b); break;
     case CLS_R4: sweep_group_block<16, 4, WPB>(a, b); break;
     case CLS_R8: sweep_group_block<16, 8, WPB>(a, b); break;
     case CLS_R16:
-        if constexpr (DEFER) screen_block<16, ITEMS, WIDE>(a, b);
+        if constexpr (DEFER) screen_block<16, ITEMS, WIDE, 16, 16, (ITEMS >= 2), TABW>(a, b);
         else sweep_group_block<16, 16, WPB>(a, b);
         break;
     default:
-        if constexpr (DEFER) screen_block<32, ITEMS, WIDE>(a, b);
+        if constexpr (ROWS) screen_block<16, 1, false, 32, 32, true, TABW>(a, b);
+        else if constexpr (DEFER) screen_block<32, ITEMS, WIDE>(a, b);
         else sweep_group_block<32, 16, WPB>(a, b);
         break;
     }
