@@ -230,6 +230,94 @@ def test_random_texts_cut_every_32_kib(tmp_path, seed):
     assert taken >= 70 and fell_back >= 10 and cut >= 50, last
 
 
+_SHORT_ESTIMATE = r"""
+import os, sys
+import numpy as np
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
+import oracle, yacrd_amd
+from cases import assert_same
+from test_gpu_ingest_group import _same_ingest
+# YACRD_TEST_RANGE_BYTES=2097152 (this process): a text of 6..8 MiB is cut at byte 4 MiB for two engines and for three
+GRAIN, CUT, OVERHANG = 2 << 20, 4 << 20, 4 << 20
+rng = np.random.default_rng(41)
+ids = ["r%03d" % i for i in range(500)]
+
+
+def lines(n, tag=""):
+    a, b = rng.integers(0, len(ids), n).tolist(), rng.integers(0, len(ids), n).tolist()
+    s1, s2 = rng.integers(0, 8000, n).tolist(), rng.integers(0, 8000, n).tolist()
+    d1, d2 = rng.integers(1, 900, n).tolist(), rng.integers(1, 900, n).tolist()
+    return ["%s\t9000\t%d\t%d\t-\t%s\t9000\t%d\t%d%s\n" % (ids[a[i]], s1[i], s1[i] + d1[i], ids[b[i]], s2[i], s2[i] + d2[i], tag)
+            for i in range(n)]
+
+
+def text_with_long_lines_opening(which):
+    # range `which` opens with ~1.1 MiB of lines that carry a 2000-byte tag; every other line has ~40 bytes; the line that
+    # crosses byte 4 MiB is padded so that a new line starts exactly there
+    long_ones = "".join(lines(560, "\ttg:Z:" + "x" * 2000))
+    first = (long_ones if which == 0 else "") + "".join(lines(110000))
+    first = first[:first.rfind("\n", 0, CUT - 300) + 1]
+    pad = "late7\t7000\t10\t900\t+\tr001\t9000\t5\t800\tp:Z:"
+    first += pad + "y" * (CUT - len(first) - len(pad) - 1) + "\n"
+    second = (long_ones if which == 1 else "") + "".join(lines(95000))
+    second = second[:second.rfind("\n", 0, 3 * (1 << 20) + (1 << 19)) + 1]
+    text = first + second
+    assert len(first) == CUT and text[CUT - 1] == "\n" and 3 * GRAIN < len(text) <= 4 * GRAIN
+    return text
+
+
+def record_room(raw, begin, end):
+    # parse_range (gpu_paf.hip), n = the bytes of the range's mirror (the range and up to 4 MiB behind it):
+    #   rec_cap = n / 17 + 2;  sample = min(n, 1 MiB);  nl = newlines in the mirror's first `sample` bytes;
+    #   if (nl) rec_cap = min(rec_cap, (u64)((double)n / (double)sample * (double)nl * 1.25) + 4096);
+    n = min(len(raw), end + (OVERHANG if end < len(raw) else 0)) - begin
+    sample = min(n, 1 << 20)
+    nl = raw.count(b"\n", begin, begin + sample)
+    room = n // 17 + 2
+    return min(room, int(float(n) / float(sample) * float(nl) * 1.25) + 4096) if nl else room
+
+
+engines = [yacrd_amd.Engine() for _ in range(3)]
+for which in (1, 0):
+    text = text_with_long_lines_opening(which)
+    raw = text.encode()
+    records = [raw.count(b"\n", 0, CUT), raw.count(b"\n", CUT)]  # (every line is a record; one starts at CUT)
+    room = [record_room(raw, 0, CUT), record_room(raw, CUT, len(raw))]
+    print("long lines open range %d: %d bytes, records %s, room from the estimate %s, one engine: %d of %d" % (
+        which, len(raw), records, room, sum(records), record_room(raw, 0, len(raw))), flush=True)
+    # the range with the long lines parses twice, the other one once
+    assert records[which] > room[which] and records[1 - which] <= room[1 - which]
+    p = os.path.join(sys.argv[2], "short%d.paf" % which)
+    with open(p, "wb") as f:
+        f.write(raw)
+    one = engines[0].ingest_paf(p, 2, 0.4)
+    w_names, off, iv, ln = oracle.to_csr(oracle.parse_paf(text))
+    assert one[1] == list(w_names) and np.array_equal(one[2].astype(np.uint64), ln)
+    assert one[3]["n_records"] == sum(records)
+    assert_same(one[0], oracle.run(off, iv, ln, 2, 0.4, n_threads=8), "one engine vs oracle")
+    for n in (2, 3):  # (with 3, the third engine owns no text and only sweeps)
+        _same_ingest(yacrd_amd.ingest_overlaps(engines[:n], p, 2, 0.4), one, "long lines open range %d, %d engines" % (which, n))
+print("SHORT_ESTIMATE OK")
+"""
+
+
+def test_a_range_whose_record_estimate_falls_short(tmp_path):
+    """parse_range sizes the record buffer from the line density of the range's first MiB; a range that outgrows it is parsed
+    again with room for every record (the id table and the control words reset in between).  Here the range that BEGINS AT
+    BYTE 4 MiB does — its first MiB holds 2 KB lines, the rest 40-byte ones — while range 0 does not, and the other way
+    round in a second text: 2 and 3 engines against one engine, one engine against the oracle."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    script = tmp_path / "short_estimate.py"
+    script.write_text(_SHORT_ESTIMATE)
+    p = subprocess.run([sys.executable, str(script), root, str(tmp_path)], env=dict(os.environ, YACRD_TEST_RANGE_BYTES="2097152"),
+                       capture_output=True, text=True, timeout=600)
+    print(p.stdout)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+    assert p.stdout.splitlines()[-1] == "SHORT_ESTIMATE OK", p.stdout[-2000:]
+
+
 PEER_WORKER = r"""
 import os, sys
 import numpy as np

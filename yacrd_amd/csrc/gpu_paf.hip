@@ -585,34 +585,118 @@ int sort_by_first_position(yacrd_engine *e, u64 *keys, u64 *keys_out, u32 *slots
     return YACRD_OK;
 }
 
+// the 64-byte control block the kernels count into: lines, records, status bits, number of reads
+struct Ctl {
+    DevBuf buf;
+    struct Words { // a copy on the host (status and n_reads are 32-bit on the device: the upper halves stay zero)
+        unsigned long long lines = 0, records = 0, status = 0, n_reads = 0;
+    };
+    unsigned long long *lines() const { return buf.as<unsigned long long>(); }
+    unsigned long long *records() const { return lines() + 1; }
+    u32 *status() const { return reinterpret_cast<u32 *>(lines() + 2); }
+    u32 *n_reads() const { return reinterpret_cast<u32 *>(lines() + 3); }
+    // what the kernels on the engine's stream have counted (the stream is waited for)
+    int read(yacrd_engine *e, Words &h, bool last_error = true) const
+    {
+        HIP_TRY(hipMemcpyAsync(&h, buf.p, sizeof(h), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        if (last_error) HIP_TRY(hipGetLastError());
+        return YACRD_OK;
+    }
+};
+
+// the open-addressing id table (GpArgs / GmArgs say what a slot holds)
+struct IdTable {
+    DevBuf claim, first_pos, slot_cnt;
+    u64 cap = 0;
+    int reserve(u64 slots)
+    {
+        HIP_TRY(claim.reserve((size_t)slots * sizeof(u64)));
+        HIP_TRY(first_pos.reserve((size_t)slots * sizeof(u64)));
+        HIP_TRY(slot_cnt.reserve((size_t)slots * sizeof(u32)));
+        cap = slots;
+        return YACRD_OK;
+    }
+    // an empty table, and the control words its kernels count into at zero
+    int reset(hipStream_t stream, const Ctl &ctl)
+    {
+        HIP_TRY(hipMemsetAsync(ctl.buf.p, 0, 64, stream));
+        HIP_TRY(hipMemsetAsync(claim.p, 0, (size_t)cap * sizeof(u64), stream));
+        HIP_TRY(hipMemsetAsync(first_pos.p, 0xFF, (size_t)cap * sizeof(u64), stream));
+        HIP_TRY(hipMemsetAsync(slot_cnt.p, 0, (size_t)cap * sizeof(u32), stream));
+        return YACRD_OK;
+    }
+    void release() { for (DevBuf *b : {&claim, &first_pos, &slot_cnt}) b->release(); }
+};
+
+// one numbering of reads by first appearance: a table's occupied slots (keys = first positions), the same sorted, and per
+// read where its name lies (length, position in the text it is taken from, offsets in `names`) and its intervals
+struct ReadList {
+    DevBuf keys, keys2, slots, slots2, name_len, name_at, name_off, names, cnt;
+    // (the kernels read a few elements beyond the last read's)
+    int reserve_reads(u32 n_reads)
+    {
+        HIP_TRY(name_len.reserve((size_t)(n_reads + 4) * sizeof(u32)));
+        HIP_TRY(name_at.reserve((size_t)(n_reads + 1) * sizeof(u64)));
+        HIP_TRY(name_off.reserve((size_t)(n_reads + 2) * sizeof(u64)));
+        HIP_TRY(cnt.reserve((size_t)(n_reads + 4) * sizeof(u32)));
+        return YACRD_OK;
+    }
+    void release() { for (DevBuf *b : {&keys, &keys2, &slots, &slots2, &name_len, &name_at, &name_off, &names, &cnt}) b->release(); }
+};
+
 struct Scratch { // the call's device buffers; they stay with the engine (grow-only), go with yacrd_engine_trim / destroy
     static constexpr yacrd_engine::Slot kScratchSlot = yacrd_engine::kPaf;
-    DevBuf text, claim, first_pos, slot_cnt, recs, ctl, keys, keys2, slots, slots2, tmp, map, name_len, name_at, name_off,
-        names, cnt, part, err, gather, gmap;
-    // the merge engine's (yacrd_engines_ingest_overlaps)
-    DevBuf m_fp, m_len, m_cnt, m_noff, m_names, m_slot, m_read, g_claim, g_fp, g_cnt, g_keys, g_slots, g_keys2, g_slots2, g_slot_read,
-        g_rcnt, g_nlen, g_nat, g_noff, g_names, g_len;
-    size_t bytes()
-    {
-        size_t n = 0;
-        for (DevBuf *b : all()) n += b->cap;
-        return n;
-    }
+    Ctl ctl;
+    IdTable ids;    // the range's
+    ReadList range; // the range's reads: lengths in e->in_len
+    DevBuf text, recs, tmp, map, part, err, gather, gmap;
+    // the merge engine's (yacrd_engines_ingest_overlaps): every range's reads end to end (m_*), the file's table and reads
+    IdTable file_ids;
+    ReadList file; // lengths in g_len
+    DevBuf m_fp, m_len, m_cnt, m_noff, m_names, m_slot, m_read, g_slot_read, g_len;
     void release()
     {
-        for (DevBuf *b : all()) b->release();
+        ids.release(), file_ids.release(), range.release(), file.release();
+        for (DevBuf *b : {&ctl.buf, &text, &recs, &tmp, &map, &part, &err, &gather, &gmap, &m_fp, &m_len, &m_cnt, &m_noff, &m_names, &m_slot,
+                          &m_read, &g_slot_read, &g_len})
+            b->release();
     }
     ~Scratch() { release(); }
 
-private:
-    std::vector<DevBuf *> all()
+    // What every numbering shares (a range's in parse_range, the file's in GroupRun::merge); the caller's checks come behind
+    // collect, its number kernel behind sort_collected.
+    // table -> list.keys / slots: the occupied slots and their first positions; `h`: the control words, h.n_reads slots
+    int collect(yacrd_engine *e, IdTable &t, ReadList &l, Ctl::Words &h)
     {
-        return {&text, &claim, &first_pos, &slot_cnt, &recs, &ctl, &keys, &keys2, &slots, &slots2, &tmp, &map, &name_len,
-                &name_at, &name_off, &names, &cnt, &part, &err, &gather, &gmap, &m_fp, &m_len, &m_cnt, &m_noff, &m_names, &m_slot,
-                &m_read, &g_claim, &g_fp, &g_cnt, &g_keys, &g_slots, &g_keys2, &g_slots2, &g_slot_read, &g_rcnt, &g_nlen, &g_nat, &g_noff,
-                &g_names, &g_len};
+        HIP_TRY(l.keys.reserve((size_t)t.cap * sizeof(u64) + 64));
+        HIP_TRY(l.slots.reserve((size_t)t.cap * sizeof(u32) + 64));
+        hipLaunchKernelGGL(yk::gp_collect_kernel, dim3((u32)std::min<u64>((t.cap + 255) / 256, (u64)e->num_cu * 8)), dim3(256), 0, e->stream,
+                           t.claim.as<u64>(), t.first_pos.as<u64>(), (u32)t.cap, l.keys.as<u64>(), l.slots.as<u32>(), ctl.n_reads());
+        return ctl.read(e, h, false);
+    }
+    // -> list.keys2 / slots2: the same by first position (keys below key_bound)
+    int sort_collected(yacrd_engine *e, ReadList &l, u32 n_reads, u64 key_bound)
+    {
+        HIP_TRY(l.keys2.reserve((size_t)n_reads * sizeof(u64) + 64));
+        HIP_TRY(l.slots2.reserve((size_t)n_reads * sizeof(u32) + 64));
+        if (!n_reads) return YACRD_OK;
+        return sort_by_first_position(e, l.keys.as<u64>(), l.keys2.as<u64>(), l.slots.as<u32>(), l.slots2.as<u32>(), n_reads, key_bound, tmp, part);
+    }
+    // list.name_len / name_at (the number kernel's) -> list.name_off, and list.names gathered from `text`
+    int pack_names(yacrd_engine *e, const unsigned char *text, ReadList &l, u32 n_reads, u64 *name_bytes)
+    {
+        if (const int rcs = scan_u32_to_u64(e, l.name_len.as<u32>(), (u64)n_reads, l.name_off.as<u64>(), part)) return rcs;
+        HIP_TRY(hipMemcpyAsync(name_bytes, l.name_off.as<u64>() + n_reads, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(l.names.reserve((size_t)*name_bytes + 64));
+        if (n_reads)
+            hipLaunchKernelGGL(yk::gp_names_kernel, dim3((n_reads + 255) / 256), dim3(256), 0, e->stream, text, l.name_at.as<u64>(),
+                               l.name_off.as<u64>(), n_reads, l.names.as<unsigned char>());
+        return YACRD_OK;
     }
 };
+
 
 } // namespace
 
@@ -636,70 +720,10 @@ int yacrd_engine_ingest_paf(yacrd_engine *e, const char *path, int n_threads, ui
 } // extern "C"
 
 namespace {
-// (TextSource — a file or memory —, the mover and the format rule: gpu_text.h)
-int ingest_text(yacrd_engine *e, const TextSource &src, u64 n, bool m4, int n_threads, uint32_t coverage, double not_coverage,
-                yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats);
-} // namespace
-
-extern "C" {
-
-int yacrd_engine_ingest_overlaps(yacrd_engine *e, const char *path, int format, int n_threads, uint32_t coverage,
-                                 double not_coverage, yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats)
-{
-    if (!e || !path || !out || !reads) return fail(YACRD_EINVAL, "null argument");
-    e->resident.valid = false;
-    bool m4 = false;
-    if (const int rcf = overlap_format(path, format, m4)) return rcf;
-    std::memset(out, 0, sizeof(*out));
-    std::memset(reads, 0, sizeof(*reads));
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (e->pending.active || e->host_pending) return fail(YACRD_EINVAL, "the engine has a submitted batch pending");
-    const int fd = ::open(path, O_RDONLY);
-    if (fd < 0) return fail(YACRD_EINVAL, std::string("cannot open ") + path);
-    FdGuard fdg{fd};
-    struct stat st;
-    if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) return fail(YACRD_EFALLBACK, "not a regular file: the host parser reads it");
-    // gzip / bzip2 / xz: not text — the caller inflates the file (yacrd_text_from_file, libyacrd_host) and hands the text to
-    // yacrd_engine_ingest_overlaps_mem, or takes the host parser
-    if (is_compressed_magic(fd))
-        return fail(YACRD_EFALLBACK, "a compressed file: inflate it (yacrd_text_from_file + yacrd_engine_ingest_overlaps_mem) or take the host parser");
-    TextSource src;
-    src.fd = fd;
-    const int rc = ingest_text(e, src, (u64)st.st_size, m4, n_threads, coverage, not_coverage, out, reads, stats);
-    if (rc == YACRD_OK) { // the whole file lies in the mirror: the overlap editor may start from it (gpu_edit.hip)
-        e->mirror.p = scratch_of<Scratch>(e)->text.as<unsigned char>(); // (ingest_text made the scratch)
-        e->mirror.n = (u64)st.st_size;
-        e->mirror.dev = (u64)st.st_dev, e->mirror.ino = (u64)st.st_ino;
-        e->mirror.mtime_s = (int64_t)st.st_mtim.tv_sec, e->mirror.mtime_ns = (int64_t)st.st_mtim.tv_nsec;
-        e->mirror.valid = e->mirror.p != nullptr;
-    }
-    return rc;
-}
-
-int yacrd_engine_ingest_overlaps_mem(yacrd_engine *e, const char *text, uint64_t n, int format, int n_threads, uint32_t coverage,
-                                     double not_coverage, yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats)
-{
-    if (!e || (!text && n) || !out || !reads) return fail(YACRD_EINVAL, "null argument");
-    e->resident.valid = false;
-    bool m4 = false;
-    if (const int rcf = overlap_format(nullptr, format, m4)) return rcf;
-    std::memset(out, 0, sizeof(*out));
-    std::memset(reads, 0, sizeof(*reads));
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (e->pending.active || e->host_pending) return fail(YACRD_EINVAL, "the engine has a submitted batch pending");
-    TextSource src;
-    src.mem = text ? text : "";
-    return ingest_text(e, src, n, m4, n_threads, coverage, not_coverage, out, reads, stats);
-}
-
-} // extern "C"
-
-namespace {
-
 
 // Bytes [begin, begin + len) of the text -> on the engine: the overlap records of the lines that START there (handles = id-table
-// slots), the table, and the range's reads numbered by first appearance INSIDE the range: S.map (slot -> read), S.keys2 (first
-// positions * 2 + side, relative to `begin`), e->in_len (lengths), S.cnt (intervals), S.name_off / S.names.  The whole file for
+// slots), the table S.ids, and the range's reads numbered by first appearance INSIDE the range: S.map (slot -> read) and, in
+// S.range, keys2 (first positions * 2 + side, relative to `begin`), cnt (intervals), name_off / names; e->in_len (lengths).  The whole file for
 // one engine; a range per engine for several (yacrd_engines_ingest_overlaps), cut on chunk boundaries.
 struct RangeOut {
     u64 n_recs = 0, cap = 0, name_bytes = 0;
@@ -719,7 +743,7 @@ int parse_range(yacrd_engine *e, const TextSource &src, u64 file_n, u64 begin, u
     constexpr u64 kOverhang = (u64)4 << 20;
     const u64 n = std::min<u64>(file_n, begin + len + (begin + len < file_n ? kOverhang : 0)) - begin; // bytes in the mirror
     const u64 parse_end = len; // lines that start at or behind it are the next range's
-    const double t_start = now_ms();
+    ro.t_start = now_ms();
     {
         // The parse on the device wants the text, a 24-byte record per line, the id table, the CSR and the region
         // slots in HBM at once: ~2.6 x the file (measured: 37.2 GB of text -> 96 GB).  An input beyond that goes to
@@ -745,14 +769,9 @@ int parse_range(yacrd_engine *e, const TextSource &src, u64 file_n, u64 begin, u
     HIP_TRY(hipMemsetAsync(S.text.as<char>() + n, 0, 64, e->stream)); // (the scan reads 16 bytes at a time)
     u64 cap = (u64)1 << 20;
     while (cap < n / 64 && cap < ((u64)1 << 31)) cap <<= 1; // ids are a small fraction of the lines; a full table = fallback
-    HIP_TRY(S.claim.reserve((size_t)cap * sizeof(u64)));
-    HIP_TRY(S.first_pos.reserve((size_t)cap * sizeof(u64)));
-    HIP_TRY(S.slot_cnt.reserve((size_t)cap * sizeof(u32)));
-    HIP_TRY(S.ctl.reserve(64));
-    HIP_TRY(hipMemsetAsync(S.ctl.p, 0, 64, e->stream));
-    HIP_TRY(hipMemsetAsync(S.claim.p, 0, (size_t)cap * sizeof(u64), e->stream));
-    HIP_TRY(hipMemsetAsync(S.first_pos.p, 0xFF, (size_t)cap * sizeof(u64), e->stream));
-    HIP_TRY(hipMemsetAsync(S.slot_cnt.p, 0, (size_t)cap * sizeof(u32), e->stream));
+    if (const int rct = S.ids.reserve(cap)) return rct;
+    HIP_TRY(S.ctl.buf.reserve(64));
+    if (const int rct = S.ids.reset(e->stream, S.ctl)) return rct;
     // Room for the records: the number of lines is only known when the last byte has been scanned, and the parse
     // does not wait for that — so from the line density of the file's first MiB plus a quarter (never more than
     // one record per 17 bytes); a parse that outgrows it is repeated with the exact number below.
@@ -769,13 +788,12 @@ int parse_range(yacrd_engine *e, const TextSource &src, u64 file_n, u64 begin, u
     yk::GpArgs ga{};
     ga.text = S.text.as<unsigned char>();
     ga.n = n;
-    ga.n_lines = S.ctl.as<unsigned long long>();
-    ga.n_recs = S.ctl.as<unsigned long long>() + 1;
-    ga.status = reinterpret_cast<u32 *>(S.ctl.as<unsigned long long>() + 2);
-    u32 *d_nreads = reinterpret_cast<u32 *>(S.ctl.as<unsigned long long>() + 3);
-    ga.claim = S.claim.as<u64>();
-    ga.first_pos = S.first_pos.as<u64>();
-    ga.slot_cnt = S.slot_cnt.as<u32>();
+    ga.n_lines = S.ctl.lines();
+    ga.n_recs = S.ctl.records();
+    ga.status = S.ctl.status();
+    ga.claim = S.ids.claim.as<u64>();
+    ga.first_pos = S.ids.first_pos.as<u64>();
+    ga.slot_cnt = S.ids.slot_cnt.as<u32>();
     ga.mask = (u32)(cap - 1);
     ga.recs = S.recs.as<yk::OvlRec>();
     ga.rec_cap = rec_cap;
@@ -806,82 +824,47 @@ int parse_range(yacrd_engine *e, const TextSource &src, u64 file_n, u64 begin, u
         if (bad == 3) return fail(YACRD_ENOMEM, "PAF text to HBM: no pinned memory");
         if (bad) return fail(YACRD_ENODEV, "PAF text to HBM: a HIP call failed");
     }
-    const double t_text = now_ms();
+    ro.t_text = now_ms();
 
     // ---- what the scan and the parse found
-    unsigned long long h_ctl[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h_ctl, S.ctl.p, sizeof(h_ctl), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipGetLastError());
-    if ((u32)h_ctl[2] & yk::kNeedHost)
+    Ctl::Words found;
+    if (const int rcc = S.ctl.read(e, found)) return rcc;
+    if ((u32)found.status & yk::kNeedHost)
         return fail(YACRD_EFALLBACK, "the text holds a '\"', a lone CR or a line that is not a plain PAF / M4 record (too few "
                                      "columns, a 0x integer, a length beyond u32, an error rate written as inf or .5 ...): the "
                                      "host parser decides");
-    if ((u32)h_ctl[2] & yk::kTableFull) return fail(YACRD_EFALLBACK, "more read ids than the device table holds");
-    const u64 n_lines = h_ctl[0];
-    if (n_lines >= 0x7FFFFFFFull * 2) return fail(YACRD_EFALLBACK, "too many lines for the device parser");
-    u64 n_recs = h_ctl[1];
-    if (n_recs > n_lines + 2) return fail(YACRD_EINTERNAL, "device parser: more records than lines");
+    if ((u32)found.status & yk::kTableFull) return fail(YACRD_EFALLBACK, "more read ids than the device table holds");
+    if (found.lines >= 0x7FFFFFFFull * 2) return fail(YACRD_EFALLBACK, "too many lines for the device parser");
+    const u64 n_recs = found.records;
+    if (n_recs > found.lines + 2) return fail(YACRD_EINTERNAL, "device parser: more records than lines");
     if (n_recs > rec_cap) { // the estimate fell short (line lengths far from uniform): once more, with room for every record
         rec_cap = n_recs + 1;
         HIP_TRY(S.recs.reserve((size_t)rec_cap * sizeof(yk::OvlRec)));
         ga.recs = S.recs.as<yk::OvlRec>();
         ga.rec_cap = rec_cap;
-        HIP_TRY(hipMemsetAsync(S.ctl.p, 0, 64, e->stream));
-        HIP_TRY(hipMemsetAsync(S.claim.p, 0, (size_t)cap * sizeof(u64), e->stream));
-        HIP_TRY(hipMemsetAsync(S.first_pos.p, 0xFF, (size_t)cap * sizeof(u64), e->stream));
-        HIP_TRY(hipMemsetAsync(S.slot_cnt.p, 0, (size_t)cap * sizeof(u32), e->stream));
+        if (const int rct = S.ids.reset(e->stream, S.ctl)) return rct;
         launch_segment(0, parse_end, n);
-        HIP_TRY(hipMemcpyAsync(h_ctl, S.ctl.p, sizeof(h_ctl), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        HIP_TRY(hipGetLastError());
-        if (((u32)h_ctl[2] & (yk::kNeedHost | yk::kTableFull)) || h_ctl[1] != n_recs)
+        if (const int rcc = S.ctl.read(e, found)) return rcc;
+        if (((u32)found.status & (yk::kNeedHost | yk::kTableFull)) || found.records != n_recs)
             return fail(YACRD_EINTERNAL, "device parser: the second parse disagrees with the first");
     }
-    // ---- the reads: occupied slots by first position
-    HIP_TRY(S.keys.reserve((size_t)cap * sizeof(u64) + 64));
-    HIP_TRY(S.slots.reserve((size_t)cap * sizeof(u32) + 64));
-    hipLaunchKernelGGL(yk::gp_collect_kernel, dim3((u32)std::min<u64>((cap + 255) / 256, (u64)e->num_cu * 8)), dim3(256), 0, e->stream,
-                       ga.claim, ga.first_pos, (u32)cap, S.keys.as<u64>(), S.slots.as<u32>(), d_nreads);
-    HIP_TRY(hipMemcpyAsync(h_ctl, S.ctl.p, sizeof(h_ctl), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    const u32 R = (u32)h_ctl[3];
-    const double t_parse = now_ms();
+    // ---- the reads: occupied slots by first position, numbered, their names packed
+    ReadList &L = S.range;
+    if (const int rcc = S.collect(e, S.ids, L, found)) return rcc;
+    const u32 R = ro.R = (u32)found.n_reads;
+    ro.t_parse = now_ms();
     if ((u64)R * 2 > cap && R > 1024) return fail(YACRD_EFALLBACK, "more read ids than the device table holds comfortably");
-
-    // sort (first position, slot)
-    HIP_TRY(S.keys2.reserve((size_t)R * sizeof(u64) + 64));
-    HIP_TRY(S.slots2.reserve((size_t)R * sizeof(u32) + 64));
-    if (R) {
-        const int rcs = sort_by_first_position(e, S.keys.as<u64>(), S.keys2.as<u64>(), S.slots.as<u32>(), S.slots2.as<u32>(), R, 2 * n + 2, S.tmp, S.part);
-        if (rcs) return rcs;
-    }
+    if (const int rcs = S.sort_collected(e, L, R, 2 * n + 2)) return rcs;
     HIP_TRY(S.map.reserve((size_t)cap * sizeof(u32)));
-    HIP_TRY(S.name_len.reserve((size_t)(R + 4) * sizeof(u32)));
-    HIP_TRY(S.name_at.reserve((size_t)(R + 1) * sizeof(u64)));
-    HIP_TRY(S.name_off.reserve((size_t)(R + 2) * sizeof(u64)));
+    if (const int rcr = L.reserve_reads(R)) return rcr;
     HIP_TRY(e->in_len.reserve((size_t)(R + 1) * sizeof(u32)));
-    HIP_TRY(S.cnt.reserve((size_t)(R + 4) * sizeof(u32)));
-    HIP_TRY(hipMemsetAsync(S.cnt.p, 0, (size_t)(R + 4) * sizeof(u32), e->stream));
+    HIP_TRY(hipMemsetAsync(L.cnt.p, 0, (size_t)(R + 4) * sizeof(u32), e->stream));
     HIP_TRY(hipMemsetAsync(S.map.p, 0xFF, (size_t)cap * sizeof(u32), e->stream));
-    const u32 rg = (R + 255) / 256;
     if (R)
-        hipLaunchKernelGGL(yk::gp_number_kernel, dim3(rg), dim3(256), 0, e->stream, ga.text, S.keys2.as<u64>(), S.slots2.as<u32>(),
-                           R, S.map.as<u32>(), e->in_len.as<u32>(), S.name_len.as<u32>(), S.name_at.as<u64>(), S.slot_cnt.as<u32>(), S.cnt.as<u32>(), ga.delim);
-    {
-        const int rcs = scan_u32_to_u64(e, S.name_len.as<u32>(), (u64)R, S.name_off.as<u64>(), S.part);
-        if (rcs) return rcs;
-    }
-    u64 name_bytes = 0;
-    HIP_TRY(hipMemcpyAsync(&name_bytes, S.name_off.as<u64>() + R, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(S.names.reserve((size_t)name_bytes + 64));
-    if (R)
-        hipLaunchKernelGGL(yk::gp_names_kernel, dim3(rg), dim3(256), 0, e->stream, ga.text, S.name_at.as<u64>(), S.name_off.as<u64>(), R,
-                           S.names.as<unsigned char>());
-    ro.n_recs = n_recs, ro.R = R, ro.cap = cap, ro.name_bytes = name_bytes;
-    ro.t_start = t_start, ro.t_text = t_text, ro.t_parse = t_parse;
-    return YACRD_OK;
+        hipLaunchKernelGGL(yk::gp_number_kernel, dim3((R + 255) / 256), dim3(256), 0, e->stream, ga.text, L.keys2.as<u64>(), L.slots2.as<u32>(),
+                           R, S.map.as<u32>(), e->in_len.as<u32>(), L.name_len.as<u32>(), L.name_at.as<u64>(), S.ids.slot_cnt.as<u32>(), L.cnt.as<u32>(), ga.delim);
+    ro.n_recs = n_recs, ro.cap = cap;
+    return S.pack_names(e, ga.text, L, R, &ro.name_bytes);
 }
 
 int ingest_text(yacrd_engine *e, const TextSource &src, u64 n, bool m4, int n_threads, uint32_t coverage, double not_coverage,
@@ -891,53 +874,34 @@ int ingest_text(yacrd_engine *e, const TextSource &src, u64 n, bool m4, int n_th
     RangeOut ro;
     if (const int rcp = parse_range(e, src, n, 0, n, false, m4, n_threads, ro)) return rcp;
     Scratch &S = *scratch_of<Scratch>(e); // (parse_range made it)
-    const u32 R = ro.R;
-    const u64 n_recs = ro.n_recs, cap = ro.cap, name_bytes = ro.name_bytes;
-    const double t_start = ro.t_start, t_text = ro.t_text, t_parse = ro.t_parse;
     // the reads, to the host (while the CSR is built)
-    reads->n_reads = R;
-    reads->n_records = n_recs;
-    reads->lengths = (uint32_t *)std::malloc(((size_t)R + 1) * sizeof(uint32_t));
-    reads->name_off = (uint64_t *)std::malloc(((size_t)R + 1) * sizeof(uint64_t));
-    reads->names = (char *)std::malloc((size_t)name_bytes + 1);
-    if (!reads->lengths || !reads->name_off || !reads->names) {
+    if (const int rch = reads_to_host(e, reads, ro.R, ro.n_recs, e->in_len.p, S.range.name_off.p, S.range.names.p, ro.name_bytes)) return rch;
+    // ---- CSR on the device (csr_build.h through stream.hip's helper), then the engine
+    const RecSlab slab{S.recs.as<yk::OvlRec>(), ro.n_recs};
+    int rc = csr_from_records(e, &slab, 1, S.map.as<u32>(), ro.cap, ro.R, S.range.cnt, S.part, S.err, nullptr, nullptr, true);
+    const double t_build = now_ms();
+    if (!rc) rc = run_on_device(e, e->in_off.as<u64>(), e->in_iv.as<uint2>(), e->in_len.as<u32>(), ro.R, 2 * ro.n_recs, coverage, not_coverage);
+    const double t_run = now_ms();
+    const bool ran = rc == YACRD_OK;
+    if (ran) rc = fetch_result(e, out);
+    if (ran && stats) {
+        stats->text_bytes = n;
+        stats->n_records = ro.n_recs;
+        stats->n_reads = ro.R;
+        stats->text_ms = (float)(ro.t_text - ro.t_start);
+        stats->parse_ms = (float)(ro.t_parse - ro.t_text);
+        stats->build_ms = (float)(t_build - ro.t_parse);
+        stats->run_ms = (float)(t_run - t_build);
+        stats->d2h_ms = (float)(now_ms() - t_run);
+    }
+    if (rc) {
         yacrd_reads_free(reads);
-        return fail(YACRD_ENOMEM, "host allocation failed");
+        return rc;
     }
-    int rc = YACRD_OK;
-    auto body = [&]() -> int {
-        if (R) HIP_TRY(hipMemcpyAsync(reads->lengths, e->in_len.p, (size_t)R * sizeof(u32), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipMemcpyAsync(reads->name_off, S.name_off.p, ((size_t)R + 1) * sizeof(u64), hipMemcpyDeviceToHost, e->stream));
-        if (name_bytes) HIP_TRY(hipMemcpyAsync(reads->names, S.names.p, (size_t)name_bytes, hipMemcpyDeviceToHost, e->stream));
-        // ---- CSR on the device (csr_build.h through stream.hip's helper), then the engine
-        const u64 n_iv = 2 * n_recs;
-        const RecSlab slab{S.recs.as<yk::OvlRec>(), n_recs};
-        const int rcb = csr_from_records(e, &slab, 1, S.map.as<u32>(), cap, R, S.cnt, S.part, S.err, nullptr, nullptr, true);
-        if (rcb) return rcb;
-        const double t_build = now_ms();
-        int rc2 = run_on_device(e, e->in_off.as<u64>(), e->in_iv.as<uint2>(), e->in_len.as<u32>(), R, n_iv, coverage, not_coverage);
-        if (rc2) return rc2;
-        const double t_run = now_ms();
-        rc2 = fetch_result(e, out);
-        if (stats) {
-            stats->text_bytes = n;
-            stats->n_records = n_recs;
-            stats->n_reads = R;
-            stats->text_ms = (float)(t_text - t_start);
-            stats->parse_ms = (float)(t_parse - t_text);
-            stats->build_ms = (float)(t_build - t_parse);
-            stats->run_ms = (float)(t_run - t_build);
-            stats->d2h_ms = (float)(now_ms() - t_run);
-        }
-        return rc2;
-    };
-    rc = body();
-    if (rc) yacrd_reads_free(reads);
-    else { // the table stays where it is: a report can be written from it (gpu_report_write.hip)
-        e->resident.names = S.names.as<unsigned char>(), e->resident.name_off = S.name_off.as<u64>(), e->resident.lengths = e->in_len.as<u32>();
-        e->resident.n_reads = R, e->resident.valid = true;
-    }
-    return rc;
+    // the table stays where it is: a report can be written from it (gpu_report_write.hip)
+    e->resident.names = S.range.names.as<unsigned char>(), e->resident.name_off = S.range.name_off.as<u64>(), e->resident.lengths = e->in_len.as<u32>();
+    e->resident.n_reads = ro.R, e->resident.valid = true;
+    return YACRD_OK;
 }
 
 } // namespace
@@ -1063,26 +1027,75 @@ hipError_t copy_between(yacrd_engine *to, void *dst, yacrd_engine *from, const v
     return copy_staged(to, dst, from, src, bytes);
 }
 
-int ingest_text_group(yacrd_engine *const *E, uint32_t N, const TextSource &src, u64 n, bool m4, int n_threads, uint32_t coverage,
-                      double not_coverage, yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats)
-{
+// the engines' partial results; what is still held when the holder goes is freed
+struct Parts {
+    std::vector<yacrd_result> v;
+    ~Parts() { for (auto &r : v) yacrd_result_free(&r); }
+};
+
+// One file over N engines (yacrd_engines_ingest_overlaps): what the phases share, and the phases in the order
+// ingest_text_group calls them.
+struct GroupRun {
+    yacrd_engine *const *E;
+    const uint32_t N;
+    const u64 n;                        // bytes of text
+    uint32_t A = 0;                     // engines that parse a range (every engine sweeps)
+    std::vector<u64> B;                 // [N + 1] engine d parses the bytes [B[d], B[d + 1])
+    std::vector<RangeOut> ro;           // [A] what parse_range left on every parsing engine
+    std::vector<u64> eb, nb;            // [A + 1] where a range's reads / name bytes begin among all ranges', end to end
+    u32 Rg = 0;                         // reads of the whole file
+    std::vector<u32> h_rcnt, cut;       // [Rg] their intervals; [N + 1] engine o sweeps the reads [cut[o], cut[o + 1])
+    Parts parts;                        // [N] what every engine's sweep found
+    std::vector<double> t_built, t_ran; // [N]
+    double t0 = 0, t_parsed = 0, t_merged = 0;
+    Scratch &scratch(uint32_t d) const { return *scratch_of<Scratch>(E[d]); } // (there from cut_ranges on)
+
+    // fn(d) on `count` host threads, one per engine; the first failure wins, a real error before "not for the device parser"
+    template <class Fn>
+    int run_all(uint32_t count, Fn &&fn)
+    {
+        std::vector<int> codes(count, YACRD_OK);
+        std::vector<std::string> errs(count);
+        std::vector<std::thread> th;
+        for (uint32_t d = 1; d < count; d++)
+            th.emplace_back([&, d] {
+                codes[d] = fn(d);
+                if (codes[d]) errs[d] = err_slot();
+            });
+        codes[0] = fn(0);
+        if (codes[0]) errs[0] = err_slot();
+        for (auto &t : th) t.join();
+        for (uint32_t d = 0; d < count; d++)
+            if (codes[d] && codes[d] != YACRD_EFALLBACK) return fail(codes[d], "engine " + std::to_string(d) + ": " + errs[d]);
+        for (uint32_t d = 0; d < count; d++)
+            if (codes[d]) return fail(codes[d], errs[d]);
+        return (int)YACRD_OK;
+    }
+
     // ---- byte ranges: whole 4 MiB chunks (the parse's segments begin on tile boundaries), the same number for every engine
     // (YACRD_TEST_RANGE_BYTES, tests: a smaller grain — a multiple of the parse's 32 KiB tiles — so that small texts are cut too)
-    static const u64 kChunk = [] {
-        const char *ev = std::getenv("YACRD_TEST_RANGE_BYTES");
-        const u64 v = ev ? std::strtoull(ev, nullptr, 10) : 0;
-        return (v >= (u64)yk::kGpTile && v % (u64)yk::kGpTile == 0) ? v : ((u64)4 << 20);
-    }();
-    const u64 chunks = (n + kChunk - 1) / kChunk, per = (chunks + N - 1) / N;
-    std::vector<u64> B(N + 1);
-    for (uint32_t d = 0; d <= N; d++) B[d] = std::min<u64>(n, (u64)d * per * kChunk);
-    for (uint32_t d = 0; d < N; d++)
-        if (!scratch_of<Scratch>(E[d])) return fail(YACRD_ENOMEM, "host allocation failed"); // (every later scratch_of finds it)
-    // ---- does it fit?  Answered here, before anything is allocated or moved (parse_range's own check knows only
+    int cut_ranges()
+    {
+        static const u64 kChunk = [] {
+            const char *ev = std::getenv("YACRD_TEST_RANGE_BYTES");
+            const u64 v = ev ? std::strtoull(ev, nullptr, 10) : 0;
+            return (v >= (u64)yk::kGpTile && v % (u64)yk::kGpTile == 0) ? v : ((u64)4 << 20);
+        }();
+        const u64 chunks = (n + kChunk - 1) / kChunk, per = (chunks + N - 1) / N;
+        B = std::vector<u64>(N + 1);
+        for (uint32_t d = 0; d <= N; d++) B[d] = std::min<u64>(n, (u64)d * per * kChunk);
+        while (A < N && B[A] < B[A + 1]) A++;
+        for (uint32_t d = 0; d < N; d++)
+            if (!scratch_of<Scratch>(E[d])) return fail(YACRD_ENOMEM, "host allocation failed"); // (every later scratch_of finds it)
+        return YACRD_OK;
+    }
+
+    // ---- does it fit?  Answered before anything is allocated or moved (parse_range's own check knows only
     // its range).  Per DEVICE: what its engines' ranges need for the parse (text, records, id table, CSR and region slots of
     // as many reads: ~2.6 x the range, parse_range) plus the records every one of its engines gathers from ranges parsed on
     // OTHER devices (24 bytes per line, ~0.32 x their text at 75 bytes a line; engines of one device read each other's
     // records in place).  An input beyond that is the host parser's (its stream group needs ~0.5 x the file over all GPUs).
+    int fits()
     {
         std::vector<int> seen;
         for (uint32_t d = 0; d < N; d++) {
@@ -1093,7 +1106,7 @@ int ingest_text_group(yacrd_engine *const *E, uint32_t N, const TextSource &src,
             uint32_t engines_here = 0;
             for (uint32_t k = 0; k < N; k++)
                 if (E[k]->device == dev) {
-                    Scratch &Sk = *scratch_of<Scratch>(E[k]);
+                    Scratch &Sk = scratch(k);
                     here += (double)(B[k + 1] - B[k]);
                     held += (double)Sk.text.cap + (double)Sk.recs.cap + (double)E[k]->stage.cap + (double)E[k]->in_iv.cap + (double)Sk.gather.cap;
                     engines_here++;
@@ -1105,63 +1118,46 @@ int ingest_text_group(yacrd_engine *const *E, uint32_t N, const TextSource &src,
                 return fail(YACRD_EFALLBACK, "the file is too large to be parsed in the GPUs' free memory (ranges + the records gathered "
                                              "from the other GPUs): the host parser streams it");
         }
-    }
-    uint32_t active = 0;
-    while (active < N && B[active] < B[active + 1]) active++;
-    if (active < 2) return ingest_text(E[0], src, n, m4, n_threads, coverage, not_coverage, out, reads, stats);
-    const uint32_t A = active; // engines that parse (every engine sweeps, below)
-    std::vector<char> head_skip(A, 0);
-    for (uint32_t d = 1; d < A; d++) {
-        char c = 0;
-        if (!src.fetch(&c, 1, B[d] - 1)) return fail(YACRD_EINVAL, "read error in the overlap file");
-        head_skip[d] = c != '\n';
-    }
-    const double t0 = now_ms();
-    std::vector<RangeOut> ro(A);
-    std::vector<int> codes(N, YACRD_OK);
-    std::vector<std::string> errs(N);
-    auto run_all = [&](uint32_t count, auto &&fn) { // fn(d) on `count` host threads, one per engine; the first failure wins
-        std::vector<std::thread> th;
-        for (uint32_t d = 1; d < count; d++)
-            th.emplace_back([&, d] {
-                codes[d] = fn(d);
-                if (codes[d]) errs[d] = err_slot();
-            });
-        codes[0] = fn(0);
-        if (codes[0]) errs[0] = err_slot();
-        for (auto &t : th) t.join();
-        // (a real error before "not for the device parser")
-        for (uint32_t d = 0; d < count; d++)
-            if (codes[d] && codes[d] != YACRD_EFALLBACK) return fail(codes[d], "engine " + std::to_string(d) + ": " + errs[d]);
-        for (uint32_t d = 0; d < count; d++)
-            if (codes[d]) return fail(codes[d], errs[d]);
-        return (int)YACRD_OK;
-    };
-    // the threads that move text are shared out (engines on one device share its link as well)
-    const int copy_threads = std::max(1, (n_threads > 0 ? n_threads : 8) / (int)A);
-    int rc = run_all(A, [&](uint32_t d) -> int {
-        const int r = parse_range(E[d], src, n, B[d], B[d + 1] - B[d], head_skip[d] != 0, m4, copy_threads, ro[d]);
-        if (r) return r;
-        DeviceGuard guard(E[d]->device);
-        HIP_TRY(hipStreamSynchronize(E[d]->stream)); // (the names kernel: other engines read what this one made)
         return YACRD_OK;
-    });
-    if (rc) return rc;
-    const double t_parsed = now_ms();
+    }
 
-    // ---- the merge, on engine 0
-    yacrd_engine *e0 = E[0];
-    Scratch &S0 = *scratch_of<Scratch>(e0);
-    std::vector<u64> eb(A + 1, 0), nb(A + 1, 0);
-    for (uint32_t d = 0; d < A; d++) eb[d + 1] = eb[d] + ro[d].R, nb[d + 1] = nb[d] + ro[d].name_bytes;
-    const u64 M = eb[A], NB = nb[A];
-    if (M >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "too many read ids for the device parser");
-    u64 capG = 1024;
-    while (capG < 2 * M) capG <<= 1;
-    u32 Rg = 0;
-    u64 g_name_bytes = 0;
-    std::vector<u32> h_rcnt;
+    // ---- every parsing engine: its range (a range whose first byte continues a line leaves that line to the range before)
+    int parse(const TextSource &src, bool m4, int n_threads)
     {
+        std::vector<char> head_skip(A, 0);
+        for (uint32_t d = 1; d < A; d++) {
+            char c = 0;
+            if (!src.fetch(&c, 1, B[d] - 1)) return fail(YACRD_EINVAL, "read error in the overlap file");
+            head_skip[d] = c != '\n';
+        }
+        t0 = now_ms();
+        ro = std::vector<RangeOut>(A);
+        // the threads that move text are shared out (engines on one device share its link as well)
+        const int copy_threads = std::max(1, (n_threads > 0 ? n_threads : 8) / (int)A);
+        const int rc = run_all(A, [&](uint32_t d) -> int {
+            const int r = parse_range(E[d], src, n, B[d], B[d + 1] - B[d], head_skip[d] != 0, m4, copy_threads, ro[d]);
+            if (r) return r;
+            DeviceGuard guard(E[d]->device);
+            HIP_TRY(hipStreamSynchronize(E[d]->stream)); // (the names kernel: other engines read what this one made)
+            return YACRD_OK;
+        });
+        t_parsed = now_ms();
+        return rc;
+    }
+
+    // ---- engine 0: the ranges' reads end to end (an entry each), interned by name into the file's table; the file's reads
+    // numbered by first position; every entry's read; the reads to the host
+    int merge(yacrd_reads *reads)
+    {
+        yacrd_engine *e0 = E[0];
+        Scratch &S0 = scratch(0);
+        ReadList &L = S0.file;
+        eb = std::vector<u64>(A + 1, 0), nb = std::vector<u64>(A + 1, 0);
+        for (uint32_t d = 0; d < A; d++) eb[d + 1] = eb[d] + ro[d].R, nb[d + 1] = nb[d] + ro[d].name_bytes;
+        const u64 M = eb[A], NB = nb[A];
+        if (M >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "too many read ids for the device parser");
+        u64 capG = 1024;
+        while (capG < 2 * M) capG <<= 1;
         DeviceGuard guard(e0->device);
         HIP_TRY(S0.m_fp.reserve((size_t)(M + 1) * sizeof(u64)));
         HIP_TRY(S0.m_len.reserve((size_t)(M + 1) * sizeof(u32)));
@@ -1170,91 +1166,62 @@ int ingest_text_group(yacrd_engine *const *E, uint32_t N, const TextSource &src,
         HIP_TRY(S0.m_names.reserve((size_t)NB + 64));
         HIP_TRY(S0.m_slot.reserve((size_t)(M + 1) * sizeof(u32)));
         HIP_TRY(S0.m_read.reserve((size_t)(M + 1) * sizeof(u32)));
-        HIP_TRY(S0.g_claim.reserve((size_t)capG * sizeof(u64)));
-        HIP_TRY(S0.g_fp.reserve((size_t)capG * sizeof(u64)));
-        HIP_TRY(S0.g_cnt.reserve((size_t)capG * sizeof(u32)));
+        if (const int rct = S0.file_ids.reserve(capG)) return rct;
         HIP_TRY(S0.g_slot_read.reserve((size_t)capG * sizeof(u32)));
-        HIP_TRY(S0.ctl.reserve(64));
+        HIP_TRY(S0.ctl.buf.reserve(64));
         for (uint32_t d = 0; d < A; d++) {
-            Scratch &Sd = *scratch_of<Scratch>(E[d]);
+            Scratch &Sd = scratch(d);
             const size_t R = ro[d].R;
-            HIP_TRY(copy_between(e0, S0.m_fp.as<u64>() + eb[d], E[d], Sd.keys2.p, R * sizeof(u64)));
+            HIP_TRY(copy_between(e0, S0.m_fp.as<u64>() + eb[d], E[d], Sd.range.keys2.p, R * sizeof(u64)));
             HIP_TRY(copy_between(e0, S0.m_len.as<u32>() + eb[d], E[d], E[d]->in_len.p, R * sizeof(u32)));
-            HIP_TRY(copy_between(e0, S0.m_cnt.as<u32>() + eb[d], E[d], Sd.cnt.p, R * sizeof(u32)));
-            HIP_TRY(copy_between(e0, S0.m_noff.as<u64>() + eb[d], E[d], Sd.name_off.p, R * sizeof(u64)));
-            HIP_TRY(copy_between(e0, S0.m_names.as<char>() + nb[d], E[d], Sd.names.p, (size_t)ro[d].name_bytes));
+            HIP_TRY(copy_between(e0, S0.m_cnt.as<u32>() + eb[d], E[d], Sd.range.cnt.p, R * sizeof(u32)));
+            HIP_TRY(copy_between(e0, S0.m_noff.as<u64>() + eb[d], E[d], Sd.range.name_off.p, R * sizeof(u64)));
+            HIP_TRY(copy_between(e0, S0.m_names.as<char>() + nb[d], E[d], Sd.range.names.p, (size_t)ro[d].name_bytes));
             if (R)
                 hipLaunchKernelGGL(yk::gm_shift_kernel, dim3((u32)((R + 255) / 256)), dim3(256), 0, e0->stream, S0.m_fp.as<u64>() + eb[d],
                                    S0.m_noff.as<u64>() + eb[d], (u64)R, 2 * B[d], nb[d]);
         }
         HIP_TRY(hipMemcpyAsync(S0.m_noff.as<u64>() + M, &NB, sizeof(u64), hipMemcpyHostToDevice, e0->stream));
-        HIP_TRY(hipMemsetAsync(S0.ctl.p, 0, 64, e0->stream));
-        HIP_TRY(hipMemsetAsync(S0.g_claim.p, 0, (size_t)capG * sizeof(u64), e0->stream));
-        HIP_TRY(hipMemsetAsync(S0.g_fp.p, 0xFF, (size_t)capG * sizeof(u64), e0->stream));
-        HIP_TRY(hipMemsetAsync(S0.g_cnt.p, 0, (size_t)capG * sizeof(u32), e0->stream));
+        if (const int rct = S0.file_ids.reset(e0->stream, S0.ctl)) return rct;
         yk::GmArgs gm{};
         gm.names = S0.m_names.as<unsigned char>(), gm.noff = S0.m_noff.as<u64>(), gm.fp = S0.m_fp.as<u64>();
         gm.len = S0.m_len.as<u32>(), gm.cnt = S0.m_cnt.as<u32>(), gm.M = M;
-        gm.claim = S0.g_claim.as<u64>(), gm.first_pos = S0.g_fp.as<u64>(), gm.slot_cnt = S0.g_cnt.as<u32>(), gm.mask = (u32)(capG - 1);
+        gm.claim = S0.file_ids.claim.as<u64>(), gm.first_pos = S0.file_ids.first_pos.as<u64>(), gm.slot_cnt = S0.file_ids.slot_cnt.as<u32>();
+        gm.mask = (u32)(capG - 1);
         gm.entry_slot = S0.m_slot.as<u32>();
-        gm.status = reinterpret_cast<u32 *>(S0.ctl.as<unsigned long long>() + 2);
-        u32 *d_nreads = reinterpret_cast<u32 *>(S0.ctl.as<unsigned long long>() + 3);
+        gm.status = S0.ctl.status();
         const u32 mg = (u32)((M + 255) / 256);
         if (M) hipLaunchKernelGGL(yk::gm_intern_kernel, dim3(mg), dim3(256), 0, e0->stream, gm);
-        HIP_TRY(S0.g_keys.reserve((size_t)capG * sizeof(u64) + 64));
-        HIP_TRY(S0.g_slots.reserve((size_t)capG * sizeof(u32) + 64));
-        hipLaunchKernelGGL(yk::gp_collect_kernel, dim3((u32)std::min<u64>((capG + 255) / 256, (u64)e0->num_cu * 8)), dim3(256), 0, e0->stream,
-                           gm.claim, gm.first_pos, (u32)capG, S0.g_keys.as<u64>(), S0.g_slots.as<u32>(), d_nreads);
-        unsigned long long h_ctl[4] = {0, 0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(h_ctl, S0.ctl.p, sizeof(h_ctl), hipMemcpyDeviceToHost, e0->stream));
-        HIP_TRY(hipStreamSynchronize(e0->stream));
+        Ctl::Words h;
+        if (const int rcc = S0.collect(e0, S0.file_ids, L, h)) return rcc;
         HIP_TRY(hipGetLastError());
-        if ((u32)h_ctl[2]) return fail(YACRD_EINTERNAL, "device parser: the merge table overflowed");
-        Rg = (u32)h_ctl[3];
-        HIP_TRY(S0.g_keys2.reserve((size_t)Rg * sizeof(u64) + 64));
-        HIP_TRY(S0.g_slots2.reserve((size_t)Rg * sizeof(u32) + 64));
-        if (Rg) {
-            const int rcs = sort_by_first_position(e0, S0.g_keys.as<u64>(), S0.g_keys2.as<u64>(), S0.g_slots.as<u32>(), S0.g_slots2.as<u32>(), Rg, 2 * n + 2, S0.tmp, S0.part);
-            if (rcs) return rcs;
-        }
-        HIP_TRY(S0.g_rcnt.reserve((size_t)(Rg + 4) * sizeof(u32)));
-        HIP_TRY(S0.g_nlen.reserve((size_t)(Rg + 4) * sizeof(u32)));
-        HIP_TRY(S0.g_nat.reserve((size_t)(Rg + 1) * sizeof(u64)));
-        HIP_TRY(S0.g_noff.reserve((size_t)(Rg + 2) * sizeof(u64)));
+        if ((u32)h.status) return fail(YACRD_EINTERNAL, "device parser: the merge table overflowed");
+        Rg = (u32)h.n_reads;
+        if (const int rcs = S0.sort_collected(e0, L, Rg, 2 * n + 2)) return rcs;
+        if (const int rcr = L.reserve_reads(Rg)) return rcr;
         HIP_TRY(S0.g_len.reserve((size_t)(Rg + 1) * sizeof(u32)));
-        const u32 rg = (Rg + 255) / 256;
         if (Rg) {
-            hipLaunchKernelGGL(yk::gm_number_kernel, dim3(rg), dim3(256), 0, e0->stream, gm, S0.g_slots2.as<u32>(), Rg, S0.g_slot_read.as<u32>(),
-                               S0.g_rcnt.as<u32>(), S0.g_nlen.as<u32>(), S0.g_nat.as<u64>());
+            hipLaunchKernelGGL(yk::gm_number_kernel, dim3((Rg + 255) / 256), dim3(256), 0, e0->stream, gm, L.slots2.as<u32>(), Rg,
+                               S0.g_slot_read.as<u32>(), L.cnt.as<u32>(), L.name_len.as<u32>(), L.name_at.as<u64>());
             hipLaunchKernelGGL(yk::gm_entry_kernel, dim3(mg), dim3(256), 0, e0->stream, gm, S0.g_slot_read.as<u32>(), S0.m_read.as<u32>(),
                                S0.g_len.as<u32>());
         }
-        if (const int rcs = scan_u32_to_u64(e0, S0.g_nlen.as<u32>(), (u64)Rg, S0.g_noff.as<u64>(), S0.part)) return rcs;
-        HIP_TRY(hipMemcpyAsync(&g_name_bytes, S0.g_noff.as<u64>() + Rg, sizeof(u64), hipMemcpyDeviceToHost, e0->stream));
-        HIP_TRY(hipStreamSynchronize(e0->stream));
-        HIP_TRY(S0.g_names.reserve((size_t)g_name_bytes + 64));
-        if (Rg)
-            hipLaunchKernelGGL(yk::gp_names_kernel, dim3(rg), dim3(256), 0, e0->stream, gm.names, S0.g_nat.as<u64>(), S0.g_noff.as<u64>(), Rg,
-                               S0.g_names.as<unsigned char>());
-        // the reads, to the host
-        reads->n_reads = Rg;
-        reads->n_records = 0;
-        for (uint32_t d = 0; d < A; d++) reads->n_records += ro[d].n_recs;
-        reads->lengths = (uint32_t *)std::malloc(((size_t)Rg + 1) * sizeof(uint32_t));
-        reads->name_off = (uint64_t *)std::malloc(((size_t)Rg + 1) * sizeof(uint64_t));
-        reads->names = (char *)std::malloc((size_t)g_name_bytes + 1);
+        u64 name_bytes = 0;
+        if (const int rcn = S0.pack_names(e0, gm.names, L, Rg, &name_bytes)) return rcn;
+        u64 n_records = 0;
+        for (uint32_t d = 0; d < A; d++) n_records += ro[d].n_recs;
+        if (const int rch = reads_to_host(e0, reads, Rg, n_records, S0.g_len.p, L.name_off.p, L.names.p, name_bytes)) return rch;
         h_rcnt.resize((size_t)Rg + 1);
-        if (!reads->lengths || !reads->name_off || !reads->names) return fail(YACRD_ENOMEM, "host allocation failed");
-        if (Rg) HIP_TRY(hipMemcpyAsync(reads->lengths, S0.g_len.p, (size_t)Rg * sizeof(u32), hipMemcpyDeviceToHost, e0->stream));
-        HIP_TRY(hipMemcpyAsync(reads->name_off, S0.g_noff.p, ((size_t)Rg + 1) * sizeof(u64), hipMemcpyDeviceToHost, e0->stream));
-        if (g_name_bytes) HIP_TRY(hipMemcpyAsync(reads->names, S0.g_names.p, (size_t)g_name_bytes, hipMemcpyDeviceToHost, e0->stream));
-        if (Rg) HIP_TRY(hipMemcpyAsync(h_rcnt.data(), S0.g_rcnt.p, (size_t)Rg * sizeof(u32), hipMemcpyDeviceToHost, e0->stream));
+        if (Rg) HIP_TRY(hipMemcpyAsync(h_rcnt.data(), L.cnt.p, (size_t)Rg * sizeof(u32), hipMemcpyDeviceToHost, e0->stream));
         HIP_TRY(hipStreamSynchronize(e0->stream));
+        return YACRD_OK;
     }
+
     // ---- who sweeps what: contiguous ranges of read numbers with about the same number of intervals each (every engine,
     // also one that had no text to parse)
-    std::vector<u32> cut(N + 1, Rg);
+    void deal()
     {
+        cut = std::vector<u32>(N + 1, Rg);
         u64 total = 0;
         for (u32 g = 0; g < Rg; g++) total += h_rcnt[g];
         u64 run = 0;
@@ -1266,126 +1233,170 @@ int ingest_text_group(yacrd_engine *const *E, uint32_t N, const TextSource &src,
         }
         // (cut[o..N] stay Rg: engines behind the last cut own nothing)
     }
+
     // ---- every parsing engine: its records from table slots to the file's read numbers
-    rc = run_all(A, [&](uint32_t d) -> int {
-        yacrd_engine *e = E[d];
-        DeviceGuard guard(e->device);
-        Scratch &S = *scratch_of<Scratch>(e);
-        const size_t R = ro[d].R;
-        HIP_TRY(S.gmap.reserve((size_t)(std::max<u64>(R, Rg) + 4) * sizeof(u32)));
-        HIP_TRY(copy_between(e, S.gmap.p, e0, S0.m_read.as<u32>() + eb[d], R * sizeof(u32)));
-        hipLaunchKernelGGL(yk::gm_slot_read_kernel, dim3((u32)((ro[d].cap + 255) / 256)), dim3(256), 0, e->stream, S.map.as<u32>(), ro[d].cap,
-                           S.gmap.as<u32>());
-        if (ro[d].n_recs)
-            hipLaunchKernelGGL(yk::gm_rewrite_kernel, dim3((u32)std::min<u64>((ro[d].n_recs + 255) / 256, (u64)e->num_cu * 16)), dim3(256), 0,
-                               e->stream, S.recs.as<yk::OvlRec>(), ro[d].n_recs, S.map.as<u32>());
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        HIP_TRY(hipGetLastError());
-        return YACRD_OK;
-    });
-    if (rc) return rc;
-    const double t_merged = now_ms();
+    int rewrite()
+    {
+        const int rc = run_all(A, [&](uint32_t d) -> int {
+            yacrd_engine *e = E[d];
+            DeviceGuard guard(e->device);
+            Scratch &S = scratch(d);
+            const size_t R = ro[d].R;
+            HIP_TRY(S.gmap.reserve((size_t)(std::max<u64>(R, Rg) + 4) * sizeof(u32)));
+            HIP_TRY(copy_between(e, S.gmap.p, E[0], scratch(0).m_read.as<u32>() + eb[d], R * sizeof(u32)));
+            hipLaunchKernelGGL(yk::gm_slot_read_kernel, dim3((u32)((ro[d].cap + 255) / 256)), dim3(256), 0, e->stream, S.map.as<u32>(), ro[d].cap,
+                               S.gmap.as<u32>());
+            if (ro[d].n_recs)
+                hipLaunchKernelGGL(yk::gm_rewrite_kernel, dim3((u32)std::min<u64>((ro[d].n_recs + 255) / 256, (u64)e->num_cu * 16)), dim3(256), 0,
+                                   e->stream, S.recs.as<yk::OvlRec>(), ro[d].n_recs, S.map.as<u32>());
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            HIP_TRY(hipGetLastError());
+            return YACRD_OK;
+        });
+        t_merged = now_ms();
+        return rc;
+    }
 
     // ---- every engine: the records of ALL ranges (its own in place, the others' copied over when they live on another
     // device), the halves that name its reads kept (csr_build.h: YACRD_HANDLE_ELSEWHERE), CSR, sweep
-    std::vector<yacrd_result> parts(N);
-    std::vector<double> t_built(N, 0), t_ran(N, 0);
-    rc = run_all(N, [&](uint32_t o) -> int {
-        yacrd_engine *e = E[o];
-        DeviceGuard guard(e->device);
-        Scratch &S = *scratch_of<Scratch>(e);
-        const u32 lo = cut[o], hi = cut[o + 1], Ro = hi - lo;
-        std::vector<RecSlab> slabs(A);
-        u64 foreign = 0;
-        // (records parsed by an engine of THIS device are read where they lie; under YACRD_TEST_FORCE_PEER_COPY every other
-        // engine counts as another device's, so that the gather and its copies run on a one-GPU box)
-        auto elsewhere = [&](uint32_t d) { return E[d]->device != e->device || (forced_peer_route() >= 0 && E[d] != e); };
-        for (uint32_t d = 0; d < A; d++)
-            if (elsewhere(d)) foreign += ro[d].n_recs;
-        HIP_TRY(S.gather.reserve((size_t)foreign * sizeof(yk::OvlRec) + 64));
-        u64 at = 0;
-        for (uint32_t d = 0; d < A; d++) {
-            Scratch &Sd = *scratch_of<Scratch>(E[d]);
-            if (!elsewhere(d)) {
-                slabs[d] = RecSlab{Sd.recs.as<yk::OvlRec>(), ro[d].n_recs};
-            } else {
-                yk::OvlRec *dst = S.gather.as<yk::OvlRec>() + at;
-                HIP_TRY(copy_between(e, dst, E[d], Sd.recs.p, (size_t)ro[d].n_recs * sizeof(yk::OvlRec)));
-                slabs[d] = RecSlab{dst, ro[d].n_recs};
-                at += ro[d].n_recs;
+    int build_and_sweep(uint32_t coverage, double not_coverage)
+    {
+        Scratch &S0 = scratch(0); // (the merge's: every read's length and intervals)
+        parts.v = std::vector<yacrd_result>(N);
+        t_built = std::vector<double>(N, 0), t_ran = std::vector<double>(N, 0);
+        return run_all(N, [&](uint32_t o) -> int {
+            yacrd_engine *e = E[o];
+            DeviceGuard guard(e->device);
+            Scratch &S = scratch(o);
+            const u32 lo = cut[o], hi = cut[o + 1], Ro = hi - lo;
+            std::vector<RecSlab> slabs(A);
+            u64 foreign = 0;
+            // (records parsed by an engine of THIS device are read where they lie; under YACRD_TEST_FORCE_PEER_COPY every other
+            // engine counts as another device's, so that the gather and its copies run on a one-GPU box)
+            auto elsewhere = [&](uint32_t d) { return E[d]->device != e->device || (forced_peer_route() >= 0 && E[d] != e); };
+            for (uint32_t d = 0; d < A; d++)
+                if (elsewhere(d)) foreign += ro[d].n_recs;
+            HIP_TRY(S.gather.reserve((size_t)foreign * sizeof(yk::OvlRec) + 64));
+            u64 at = 0;
+            for (uint32_t d = 0; d < A; d++) {
+                Scratch &Sd = scratch(d);
+                if (!elsewhere(d)) {
+                    slabs[d] = RecSlab{Sd.recs.as<yk::OvlRec>(), ro[d].n_recs};
+                } else {
+                    yk::OvlRec *dst = S.gather.as<yk::OvlRec>() + at;
+                    HIP_TRY(copy_between(e, dst, E[d], Sd.recs.p, (size_t)ro[d].n_recs * sizeof(yk::OvlRec)));
+                    slabs[d] = RecSlab{dst, ro[d].n_recs};
+                    at += ro[d].n_recs;
+                }
             }
-        }
-        HIP_TRY(S.gmap.reserve((size_t)(Rg + 4) * sizeof(u32)));
-        if (Rg) hipLaunchKernelGGL(yk::gm_own_kernel, dim3((Rg + 255) / 256), dim3(256), 0, e->stream, S.gmap.as<u32>(), Rg, lo, hi);
-        HIP_TRY(e->in_len.reserve((size_t)(Ro + 1) * sizeof(u32)));
-        HIP_TRY(copy_between(e, e->in_len.p, e0, S0.g_len.as<u32>() + lo, (size_t)Ro * sizeof(u32)));
-        // (the merge has summed every read's intervals over the ranges: the CSR build's count pass — one more pass over
-        // every range's records on every engine — is not needed)
-        HIP_TRY(S.cnt.reserve((size_t)(Ro + 4) * sizeof(u32)));
-        HIP_TRY(copy_between(e, S.cnt.p, e0, S0.g_rcnt.as<u32>() + lo, (size_t)Ro * sizeof(u32)));
-        u64 n_iv = 0, own_iv = 0; // (the engine's CSR holds the intervals of ITS reads: the merge has their counts)
-        for (u32 g = lo; g < hi; g++) own_iv += h_rcnt[g];
-        int r = csr_from_records(e, slabs.data(), slabs.size(), S.gmap.as<u32>(), Rg, Ro, S.cnt, S.part, S.err, nullptr, &n_iv, true,
-                                 own_iv + 1);
-        if (r) return r;
-        t_built[o] = now_ms();
-        r = run_on_device(e, e->in_off.as<u64>(), e->in_iv.as<uint2>(), e->in_len.as<u32>(), Ro, n_iv, coverage, not_coverage);
-        if (r) return r;
-        t_ran[o] = now_ms();
-        return fetch_result(e, &parts[o]);
-    });
-    auto drop = [&]() {
-        for (auto &r : parts) yacrd_result_free(&r);
-    };
-    if (rc) {
-        drop();
-        return rc;
+            HIP_TRY(S.gmap.reserve((size_t)(Rg + 4) * sizeof(u32)));
+            if (Rg) hipLaunchKernelGGL(yk::gm_own_kernel, dim3((Rg + 255) / 256), dim3(256), 0, e->stream, S.gmap.as<u32>(), Rg, lo, hi);
+            HIP_TRY(e->in_len.reserve((size_t)(Ro + 1) * sizeof(u32)));
+            HIP_TRY(copy_between(e, e->in_len.p, E[0], S0.g_len.as<u32>() + lo, (size_t)Ro * sizeof(u32)));
+            // (the merge has summed every read's intervals over the ranges: the CSR build's count pass — one more pass over
+            // every range's records on every engine — is not needed)
+            HIP_TRY(S.range.cnt.reserve((size_t)(Ro + 4) * sizeof(u32)));
+            HIP_TRY(copy_between(e, S.range.cnt.p, E[0], S0.file.cnt.as<u32>() + lo, (size_t)Ro * sizeof(u32)));
+            u64 n_iv = 0, own_iv = 0; // (the engine's CSR holds the intervals of ITS reads: the merge has their counts)
+            for (u32 g = lo; g < hi; g++) own_iv += h_rcnt[g];
+            int r = csr_from_records(e, slabs.data(), slabs.size(), S.gmap.as<u32>(), Rg, Ro, S.range.cnt, S.part, S.err, nullptr, &n_iv, true,
+                                     own_iv + 1);
+            if (r) return r;
+            t_built[o] = now_ms();
+            r = run_on_device(e, e->in_off.as<u64>(), e->in_iv.as<uint2>(), e->in_len.as<u32>(), Ro, n_iv, coverage, not_coverage);
+            if (r) return r;
+            t_ran[o] = now_ms();
+            return fetch_result(e, &parts.v[o]);
+        });
     }
+
     // ---- the results, end to end: the ranges are in first-appearance order already
-    u64 G = 0;
-    for (auto &r : parts) G += r.n_regions;
-    out->bad_offsets = (uint64_t *)std::malloc(((size_t)Rg + 1) * sizeof(uint64_t));
-    out->bad_regions = (uint32_t *)std::malloc((size_t)(2 * G + 2) * sizeof(uint32_t));
-    out->read_type = (uint8_t *)std::malloc((size_t)Rg + 1);
-    if (!out->bad_offsets || !out->bad_regions || !out->read_type) {
-        drop();
-        yacrd_result_free(out);
-        return fail(YACRD_ENOMEM, "host allocation failed");
-    }
-    u64 g0 = 0;
-    for (uint32_t o = 0; o < N; o++) {
-        const u32 lo = cut[o], Ro = cut[o + 1] - lo;
-        if (parts[o].n_reads != Ro) {
-            drop();
+    int stitch(yacrd_result *out)
+    {
+        Parts mine; // (they go when this returns)
+        mine.v.swap(parts.v);
+        u64 G = 0;
+        for (auto &r : mine.v) G += r.n_regions;
+        out->bad_offsets = (uint64_t *)std::malloc(((size_t)Rg + 1) * sizeof(uint64_t));
+        out->bad_regions = (uint32_t *)std::malloc((size_t)(2 * G + 2) * sizeof(uint32_t));
+        out->read_type = (uint8_t *)std::malloc((size_t)Rg + 1);
+        if (!out->bad_offsets || !out->bad_regions || !out->read_type) {
             yacrd_result_free(out);
-            return fail(YACRD_EINTERNAL, "device parser: an engine returned another number of reads than it was given");
+            return fail(YACRD_ENOMEM, "host allocation failed");
         }
-        for (u32 l = 0; l < Ro; l++) out->bad_offsets[lo + l] = g0 + parts[o].bad_offsets[l];
-        if (parts[o].n_regions) std::memcpy(out->bad_regions + 2 * g0, parts[o].bad_regions, (size_t)parts[o].n_regions * 2 * sizeof(uint32_t));
-        if (Ro) std::memcpy(out->read_type + lo, parts[o].read_type, Ro);
-        g0 += parts[o].n_regions;
+        u64 g0 = 0;
+        for (uint32_t o = 0; o < N; o++) {
+            const yacrd_result &part = mine.v[o];
+            const u32 lo = cut[o], Ro = cut[o + 1] - lo;
+            if (part.n_reads != Ro) {
+                yacrd_result_free(out);
+                return fail(YACRD_EINTERNAL, "device parser: an engine returned another number of reads than it was given");
+            }
+            for (u32 l = 0; l < Ro; l++) out->bad_offsets[lo + l] = g0 + part.bad_offsets[l];
+            if (part.n_regions) std::memcpy(out->bad_regions + 2 * g0, part.bad_regions, (size_t)part.n_regions * 2 * sizeof(uint32_t));
+            if (Ro) std::memcpy(out->read_type + lo, part.read_type, Ro);
+            g0 += part.n_regions;
+        }
+        out->bad_offsets[Rg] = g0;
+        out->n_reads = Rg;
+        out->n_regions = g0;
+        return YACRD_OK;
     }
-    out->bad_offsets[Rg] = g0;
-    out->n_reads = Rg;
-    out->n_regions = g0;
-    drop();
-    if (stats) {
+
+    void fill_stats(const yacrd_reads *reads, yacrd_ingest_stats *stats) const
+    {
         stats->text_bytes = n;
         stats->n_records = reads->n_records;
         stats->n_reads = Rg;
-        double tt = 0, tp = 0;
-        for (uint32_t d = 0; d < A; d++) tt = std::max(tt, ro[d].t_text - ro[d].t_start), tp = std::max(tp, ro[d].t_parse - ro[d].t_text);
+        double tt = 0;
+        for (uint32_t d = 0; d < A; d++) tt = std::max(tt, ro[d].t_text - ro[d].t_start);
         stats->text_ms = (float)tt;
         stats->parse_ms = (float)std::max(0.0, (t_parsed - t0) - tt);
-        (void)tp;
         double tb = 0, tr = 0;
         for (uint32_t o = 0; o < N; o++) tb = std::max(tb, t_built[o] - t_merged), tr = std::max(tr, t_ran[o] - t_built[o]);
         stats->build_ms = (float)((t_merged - t_parsed) + tb);
         stats->run_ms = (float)tr;
         stats->d2h_ms = (float)std::max(0.0, now_ms() - t_merged - tb - tr);
     }
+};
+
+int ingest_text_group(yacrd_engine *const *E, uint32_t N, const TextSource &src, u64 n, bool m4, int n_threads, uint32_t coverage,
+                      double not_coverage, yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats)
+{
+    GroupRun g{E, N, n};
+    if (const int rc = g.cut_ranges()) return rc;
+    if (const int rc = g.fits()) return rc;
+    if (g.A < 2) return ingest_text(E[0], src, n, m4, n_threads, coverage, not_coverage, out, reads, stats);
+    if (const int rc = g.parse(src, m4, n_threads)) return rc;
+    if (const int rc = g.merge(reads)) return rc;
+    g.deal();
+    if (const int rc = g.rewrite()) return rc;
+    if (const int rc = g.build_and_sweep(coverage, not_coverage)) return rc;
+    if (const int rc = g.stitch(out)) return rc;
+    if (stats) g.fill_stats(reads, stats);
     return YACRD_OK;
 }
+
+// The overlap file of an ingest, open for the call: a regular file, and text — gzip / bzip2 / xz is not: the caller inflates
+// the file (yacrd_text_from_file, libyacrd_host) and hands the text to `mem_form`, or takes the host parser.
+struct OverlapFile {
+    struct stat st;
+    bool m4 = false; // (overlap_format's, set by the entry point before the file is opened)
+    TextSource src;
+    int open(const char *path, const char *mem_form)
+    {
+        src.fd = ::open(path, O_RDONLY);
+        if (src.fd < 0) return fail(YACRD_EINVAL, std::string("cannot open ") + path);
+        if (fstat(src.fd, &st) != 0 || !S_ISREG(st.st_mode)) return fail(YACRD_EFALLBACK, "not a regular file: the host parser reads it");
+        if (is_compressed_magic(src.fd))
+            return fail(YACRD_EFALLBACK, std::string("a compressed file: inflate it (yacrd_text_from_file + ") + mem_form + ") or take the host parser");
+        return YACRD_OK;
+    }
+    ~OverlapFile()
+    {
+        if (src.fd >= 0) ::close(src.fd);
+    }
+};
 } // namespace
 
 extern "C" {
@@ -1394,6 +1405,41 @@ extern "C" {
 void yacrd_debug_peer_copy_counts(uint64_t out[3])
 {
     for (int i = 0; i < 3; i++) out[i] = g_peer_copies[i].load();
+}
+
+int yacrd_engine_ingest_overlaps(yacrd_engine *e, const char *path, int format, int n_threads, uint32_t coverage,
+                                 double not_coverage, yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats)
+{
+    if (!e || !path || !out || !reads) return fail(YACRD_EINVAL, "null argument");
+    e->resident.valid = false;
+    OverlapFile f;
+    if (const int rcf = overlap_format(path, format, f.m4)) return rcf;
+    zero_outputs(out, reads, stats);
+    if (e->pending.active || e->host_pending) return fail(YACRD_EINVAL, "the engine has a submitted batch pending");
+    if (const int rcf = f.open(path, "yacrd_engine_ingest_overlaps_mem")) return rcf;
+    const int rc = ingest_text(e, f.src, (u64)f.st.st_size, f.m4, n_threads, coverage, not_coverage, out, reads, stats);
+    if (rc == YACRD_OK) { // the whole file lies in the mirror: the overlap editor may start from it (gpu_edit.hip)
+        e->mirror.p = scratch_of<Scratch>(e)->text.as<unsigned char>(); // (ingest_text made the scratch)
+        e->mirror.n = (u64)f.st.st_size;
+        e->mirror.dev = (u64)f.st.st_dev, e->mirror.ino = (u64)f.st.st_ino;
+        e->mirror.mtime_s = (int64_t)f.st.st_mtim.tv_sec, e->mirror.mtime_ns = (int64_t)f.st.st_mtim.tv_nsec;
+        e->mirror.valid = e->mirror.p != nullptr;
+    }
+    return rc;
+}
+
+int yacrd_engine_ingest_overlaps_mem(yacrd_engine *e, const char *text, uint64_t n, int format, int n_threads, uint32_t coverage,
+                                     double not_coverage, yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats)
+{
+    if (!e || (!text && n) || !out || !reads) return fail(YACRD_EINVAL, "null argument");
+    e->resident.valid = false;
+    bool m4 = false;
+    if (const int rcf = overlap_format(nullptr, format, m4)) return rcf;
+    zero_outputs(out, reads, stats);
+    if (e->pending.active || e->host_pending) return fail(YACRD_EINVAL, "the engine has a submitted batch pending");
+    TextSource src;
+    src.mem = text ? text : "";
+    return ingest_text(e, src, n, m4, n_threads, coverage, not_coverage, out, reads, stats);
 }
 
 static int group_args(yacrd_engine *const *engines, uint32_t n_engines, yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats)
@@ -1406,9 +1452,7 @@ static int group_args(yacrd_engine *const *engines, uint32_t n_engines, yacrd_re
         for (uint32_t k = 0; k < d; k++)
             if (engines[k] == engines[d]) return fail(YACRD_EINVAL, "the same engine twice");
     }
-    std::memset(out, 0, sizeof(*out));
-    std::memset(reads, 0, sizeof(*reads));
-    if (stats) std::memset(stats, 0, sizeof(*stats));
+    zero_outputs(out, reads, stats);
     return YACRD_OK;
 }
 
@@ -1418,18 +1462,10 @@ int yacrd_engines_ingest_overlaps(yacrd_engine *const *engines, uint32_t n_engin
     if (const int rca = group_args(engines, n_engines, out, reads, stats)) return rca;
     if (n_engines == 1) return yacrd_engine_ingest_overlaps(engines[0], path, format, n_threads, coverage, not_coverage, out, reads, stats);
     if (!path) return fail(YACRD_EINVAL, "null argument");
-    bool m4 = false;
-    if (const int rcf = overlap_format(path, format, m4)) return rcf;
-    const int fd = ::open(path, O_RDONLY);
-    if (fd < 0) return fail(YACRD_EINVAL, std::string("cannot open ") + path);
-    FdGuard fdg{fd};
-    struct stat st;
-    if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) return fail(YACRD_EFALLBACK, "not a regular file: the host parser reads it");
-    if (is_compressed_magic(fd))
-        return fail(YACRD_EFALLBACK, "a compressed file: inflate it (yacrd_text_from_file + yacrd_engines_ingest_overlaps_mem) or take the host parser");
-    TextSource src;
-    src.fd = fd;
-    const int rc = ingest_text_group(engines, n_engines, src, (u64)st.st_size, m4, n_threads, coverage, not_coverage, out, reads, stats);
+    OverlapFile f;
+    if (const int rcf = overlap_format(path, format, f.m4)) return rcf;
+    if (const int rcf = f.open(path, "yacrd_engines_ingest_overlaps_mem")) return rcf;
+    const int rc = ingest_text_group(engines, n_engines, f.src, (u64)f.st.st_size, f.m4, n_threads, coverage, not_coverage, out, reads, stats);
     if (rc) yacrd_reads_free(reads);
     return rc;
 }

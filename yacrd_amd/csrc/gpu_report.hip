@@ -466,23 +466,9 @@ int read_report(yacrd_engine *e, const TextSource &src, u64 n, int n_threads, do
     const double t_build = now_ms();
 
     // ---- home
-    reads->n_reads = R;
-    reads->n_records = n_lines;
-    reads->lengths = (uint32_t *)std::malloc(((size_t)R + 1) * sizeof(uint32_t));
-    reads->name_off = (uint64_t *)std::malloc(((size_t)R + 1) * sizeof(uint64_t));
-    reads->names = (char *)std::malloc((size_t)name_bytes + 1);
-    if (!reads->lengths || !reads->name_off || !reads->names) {
-        yacrd_reads_free(reads);
-        return fail(YACRD_ENOMEM, "host allocation failed");
-    }
-    auto home = [&]() -> int {
-        if (R) HIP_TRY(hipMemcpyAsync(reads->lengths, e->in_len.p, (size_t)R * sizeof(u32), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipMemcpyAsync(reads->name_off, S.name_off.p, ((size_t)R + 1) * sizeof(u64), hipMemcpyDeviceToHost, e->stream));
-        if (name_bytes) HIP_TRY(hipMemcpyAsync(reads->names, S.names.p, (size_t)name_bytes, hipMemcpyDeviceToHost, e->stream));
-        e->last_reads = R, e->last_regions = G, e->has_result = true;
-        return fetch_result(e, out);
-    };
-    const int rc = home();
+    if (const int rch = reads_to_host(e, reads, (u32)R, n_lines, e->in_len.p, S.name_off.p, S.names.p, name_bytes)) return rch;
+    e->last_reads = R, e->last_regions = G, e->has_result = true;
+    const int rc = fetch_result(e, out);
     if (rc) {
         yacrd_reads_free(reads);
         yacrd_result_free(out);
@@ -508,9 +494,7 @@ int report_args(yacrd_engine *e, yacrd_result *out, yacrd_reads *reads, yacrd_in
 {
     if (!e || !out || !reads) return fail(YACRD_EINVAL, "null argument");
     e->resident.valid = false;
-    std::memset(out, 0, sizeof(*out));
-    std::memset(reads, 0, sizeof(*reads));
-    if (stats) std::memset(stats, 0, sizeof(*stats));
+    zero_outputs(out, reads, stats);
     if (e->pending.active || e->host_pending) return fail(YACRD_EINVAL, "the engine has a submitted batch pending");
     return YACRD_OK;
 }

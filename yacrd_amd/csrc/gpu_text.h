@@ -1,7 +1,7 @@
 // gpu_text.h — what the translation units that work on TEXT in HBM share: gpu_paf.hip (the device parser), gpu_edit.hip
 // (filter / extract on overlap files), gpu_report.hip (the report reader) and gpu_deflate.hip.  Where the text comes from
 // (TextSource, FdGuard, the format rule), the mover (pread -> pinned 4 MiB chunks -> the mirror in HBM, a segment handed on
-// as soon as it has landed), the staged-window accessor, the byte matcher and the id hash.
+// as soon as it has landed), the staged-window accessor, the byte matcher and the id hash; what an ingest's outputs share.
 #pragma once
 #include "engine_internal.h"
 
@@ -121,6 +121,37 @@ struct TextSource {
         return true;
     }
 };
+
+// what an ingest (overlaps or a report) hands back, empty
+inline void zero_outputs(yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats)
+{
+    std::memset(out, 0, sizeof(*out));
+    std::memset(reads, 0, sizeof(*reads));
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+}
+
+// the reads' lengths, name offsets and names from HBM into `reads`, allocated here: copies enqueued on the engine's stream.
+// Whatever fails, `reads` is left empty.  (static, like gp_blit_kernel above: a unit's own copy, so that the library exports
+// what it did before)
+static int reads_to_host(yacrd_engine *e, yacrd_reads *reads, u32 n_reads, u64 n_records, const void *d_lengths, const void *d_name_off,
+                         const void *d_names, u64 name_bytes)
+{
+    reads->n_reads = n_reads;
+    reads->n_records = n_records;
+    reads->lengths = (uint32_t *)std::malloc(((size_t)n_reads + 1) * sizeof(uint32_t));
+    reads->name_off = (uint64_t *)std::malloc(((size_t)n_reads + 1) * sizeof(uint64_t));
+    reads->names = (char *)std::malloc((size_t)name_bytes + 1);
+    auto copies = [&]() -> int {
+        if (!reads->lengths || !reads->name_off || !reads->names) return fail(YACRD_ENOMEM, "host allocation failed");
+        if (n_reads) HIP_TRY(hipMemcpyAsync(reads->lengths, d_lengths, (size_t)n_reads * sizeof(u32), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync(reads->name_off, d_name_off, ((size_t)n_reads + 1) * sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+        if (name_bytes) HIP_TRY(hipMemcpyAsync(reads->names, d_names, (size_t)name_bytes, hipMemcpyDeviceToHost, e->stream));
+        return YACRD_OK;
+    };
+    const int rc = copies();
+    if (rc) yacrd_reads_free(reads);
+    return rc;
+}
 
 constexpr size_t kTextChunk = (size_t)4 << 20; // what one pread and one copy move
 constexpr size_t kTextSeg = 32;                // chunks per segment handed on (128 MiB)
