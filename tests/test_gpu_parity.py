@@ -511,32 +511,38 @@ print("oversized grid: ok")
         assert p.returncode == 0 and "oversized grid: ok" in p.stdout, p.stdout[-2000:] + p.stderr[-3000:]
 
 
+def _device_wide_screen_reads(rng, ns=(16385, 20000, 70000), L=300000):
+    """Reads on the edges of the device-wide screen (screen_big.h, 512-position windows) on a read of length L: the piles'
+    steps are positions, everything else a share of L (at L = 300 000: starts in 600 .. 140 000, intervals of 150 000)."""
+    reads = []
+    for n in ns:
+        deep = [(int(s), int(s) + L // 2) for s in rng.integers(600, L * 14 // 30, size=n - 40)]
+        for step in (1, 100, 511, 512, 513, 5000):
+            left = [(j * step, L - L * 3 // 10 - j) for j in range(20)]
+            right = [(L * 8 // 30 + j, L - j * step) for j in range(20)]
+            base = left + deep + right
+            reads.append((base, L))
+            reads.append((base[:-1] + [(L - 1, L)], L))                         # a start inside the tail window
+            reads.append((base[:-2] + [(L // 2, L // 2)] * 2, L))                # zero-length, doubled, where the read is deep
+            reads.append((base[:-1] + [(0, 0)], L))                             # ... at position 0
+            reads.append((base[:-1] + [(step, step)], L))                       # ... inside the head pile
+            reads.append((base[:-1] + [(3, 2)], L))                             # a reversed interval: the exact path's
+        win = [(L // 3 + int(a), L * 2 // 3 - int(b)) for a, b in rng.integers(0, 300, size=(n, 2))]
+        reads.append((win, L))                                                  # covered only inside a window
+        holed = [(int(s), int(s) + L // 5) for s in rng.integers(0, L * 8 // 30, size=n // 2)] + \
+                [(int(s), int(s) + L // 5) for s in rng.integers(L * 16 // 30, L * 24 // 30, size=n - n // 2)]
+        reads.append((holed, L))                                                # nothing covers the middle
+    return reads
+
+
 @pytest.mark.parametrize("cov", [0, 4, 600])
 def test_device_wide_screen_edges(cov):
     """screen_big.h (reads of more than 16 384 intervals, 512-position windows): piles spread so that the
     (c+1)-th start / end lies inside, on the edge of and beyond the windows, a read covered only inside a
     window, zero-length intervals in the deep middle / in a pile / doubled, a one-position interval at the
     very end (a start inside the tail window), a shallow block in the middle, reads the screen must refuse."""
-    rng = np.random.default_rng(99)
-    reads = []
     L = 300000
-    for n in (16385, 20000, 70000):
-        deep = [(int(s), int(s) + 150000) for s in rng.integers(600, 140000, size=n - 40)]
-        for step in (1, 100, 511, 512, 513, 5000):
-            left = [(j * step, L - 90000 - j) for j in range(20)]
-            right = [(80000 + j, L - j * step) for j in range(20)]
-            base = left + deep + right
-            reads.append((base, L))
-            reads.append((base[:-1] + [(L - 1, L)], L))                         # a start inside the tail window
-            reads.append((base[:-2] + [(150000, 150000)] * 2, L))                # zero-length, doubled, where the read is deep
-            reads.append((base[:-1] + [(0, 0)], L))                             # ... at position 0
-            reads.append((base[:-1] + [(step, step)], L))                       # ... inside the head pile
-            reads.append((base[:-1] + [(3, 2)], L))                             # a reversed interval: the exact path's
-        win = [(100000 + int(a), 200000 - int(b)) for a, b in rng.integers(0, 300, size=(n, 2))]
-        reads.append((win, L))                                                  # covered only inside a window
-        holed = [(int(s), int(s) + 60000) for s in rng.integers(0, 80000, size=n // 2)] + \
-                [(int(s), int(s) + 60000) for s in rng.integers(160000, 240000, size=n - n // 2)]
-        reads.append((holed, L))                                                # nothing covers the middle
+    reads = _device_wide_screen_reads(np.random.default_rng(99), L=L)
     offsets = np.zeros(len(reads) + 1, np.uint64)
     offsets[1:] = np.cumsum([len(iv) for iv, _ in reads])
     intervals = np.array([p for iv, _ in reads for p in iv], dtype=np.uint32)
