@@ -56,6 +56,19 @@ int yacrd_debug_sort_pairs(yacrd_engine *e, uint64_t *keys, uint32_t *vals, uint
  * rejection / fallback list lengths, deferred reads): at most `bytes` of it are copied to dst; returns the block's size.
  * tools/ and tests only: the layout is not part of any ABI. */
 uint64_t yacrd_debug_last_counters(const yacrd_engine *e, void *dst, uint64_t bytes);
+/* the input CSR the sweeps of the engine's last call consumed, brought home from the engine's own buffers in HBM (in_off, in_iv,
+ * in_len: csrc/engine_internal.h) by plain copies on the engine's stream, then a wait; no kernel runs.  It is there after a
+ * successful yacrd_engine_run, yacrd_engine_submit + _collect, yacrd_stream_finish / yacrd_stream_group_finish (every engine of the
+ * group: its share of the reads) and yacrd_engine[s]_ingest_overlaps[_mem] (the device parser; with several engines every engine's
+ * range of the reads) — the paths on which the GPU builds or stages that CSR itself, so tests can compare it with a reference
+ * interval by interval instead of through the sweep's output.  Any other call on the engine that may rewrite, move or release
+ * those buffers or that sweeps the caller's device pointers (the _device and batch forms, ingest_report, classify, trim), and any
+ * failed call, leaves none: then, and while a submitted batch is pending, YACRD_EINVAL is returned and nothing is written.
+ * n_reads / n_intervals are always written on success; with offsets == NULL only they are (sizes first, arrays in a second
+ * call).  offsets: n_reads + 1, intervals: 2 * n_intervals (start, end), lengths: n_reads.  The order of a read's intervals is
+ * the build's (csrc/csr_build.h: whatever its atomics made it); a CSR staged from host arrays comes back bit for bit. */
+int yacrd_debug_last_input_csr(yacrd_engine *e, uint64_t *n_reads, uint64_t *n_intervals, uint64_t *offsets, uint32_t *intervals,
+                               uint32_t *lengths);
 /* cross-engine copies of the N-engine device parser (yacrd_engines_ingest_overlaps) since the library was loaded, by route:
  * [0] same device (hipMemcpyAsync), [1] hipMemcpyPeerAsync, [2] staged through pinned host buffers.
  * YACRD_TEST_FORCE_PEER_COPY=peer|staged (environment, tests) forces route 1 / 2 for EVERY such copy, also between engines of

@@ -10,6 +10,7 @@ import oracle
 import yacrd_amd
 from yacrd_amd import host
 from cases import assert_same
+from input_csr_cases import assert_same_csr
 
 pytestmark = pytest.mark.gpu
 
@@ -28,6 +29,7 @@ def _check(engine, path, cov, nc):
     assert names == list(w_names), "first-appearance order of the reads"
     assert np.array_equal(lengths.astype(np.uint64), ln), "first length seen"
     assert stats["n_reads"] == len(names) and stats["n_records"] * 2 == int(off[-1])
+    assert_same_csr(engine.debug_input_csr(), (off, iv, ln), path)  # the CSR the parse built in HBM, interval by interval
     want = oracle.run(off, iv, ln, cov, nc, n_threads=4)
     assert_same(got, want, path)
     return got, names, lengths, stats
@@ -85,10 +87,9 @@ def test_inputs_for_the_host_parser(engine, tmp_path, text):
     assert engine.run(off, np.array([[0, 5]], dtype=np.uint32), np.array([10], dtype=np.uint32), 0, 0.8).bad_regions.tolist() == [[5, 10]]
 
 
-def test_long_lines_and_ids_across_tiles(engine, tmp_path):
-    """Lines of a few bytes up to several KB (trailing tag columns, as minimap2 -c writes them), ids of up to 3000
-    bytes, empty lines, CRLF — over a few hundred KB, so that line starts, ids and fields fall on and across the
-    32 KiB tiles the parse kernel stages in LDS and the 1 KiB it stages beyond them."""
+def _long_line_texts():
+    """-> (crlf, text) twice: lines of a few bytes up to several KB (trailing tag columns, as minimap2 -c writes them), ids of
+    up to 3000 bytes, empty lines; LF, then CRLF"""
     rng = np.random.default_rng(5)
     ids = ["r%d" % i for i in range(300)] + ["x" * int(n) + str(i) for i, n in enumerate(rng.integers(40, 3000, size=12))]
     lens = {k: int(rng.integers(1000, 100000)) for k in ids}
@@ -108,9 +109,17 @@ def test_long_lines_and_ids_across_tiles(engine, tmp_path):
             if rng.random() < 0.02:
                 out.append("")
         eol = "\r\n" if crlf else "\n"
+        yield crlf, eol.join(out) + eol
+
+
+def test_long_lines_and_ids_across_tiles(engine, tmp_path):
+    """Lines of a few bytes up to several KB (trailing tag columns, as minimap2 -c writes them), ids of up to 3000
+    bytes, empty lines, CRLF — over a few hundred KB, so that line starts, ids and fields fall on and across the
+    32 KiB tiles the parse kernel stages in LDS and the 1 KiB it stages beyond them."""
+    for crlf, text in _long_line_texts():
         p = str(tmp_path / ("long%d.paf" % crlf))
         with open(p, "w", newline="") as f:
-            f.write(eol.join(out) + eol)
+            f.write(text)
         assert os.path.getsize(p) > 300000
         _check(engine, p, 2, 0.4)
 
@@ -232,6 +241,7 @@ def test_random_text_against_the_oracle_ingest(engine, tmp_path, seed):
         assert want is not None, "the device parser accepted what the reference rejects:\n%r" % text
         w_names, off, iv, ln = want
         assert names == list(w_names) and np.array_equal(lengths.astype(np.uint64), ln), text
+        assert_same_csr(engine.debug_input_csr(), (off, iv, ln), "case %d" % case)
         assert_same(got, oracle.run(off, iv, ln, cov, 0.4, n_threads=2), "case %d" % case)
     assert taken >= 200 and fell_back >= 100, (taken, fell_back)
 
@@ -255,6 +265,7 @@ def _check_m4(engine, path, cov, nc):
     w_names, off, iv, ln = oracle.to_csr(reads)
     assert names == list(w_names) and np.array_equal(lengths.astype(np.uint64), ln)
     assert stats["n_reads"] == len(names) and stats["n_records"] * 2 == int(off[-1])
+    assert_same_csr(engine.debug_input_csr(), (off, iv, ln), path)
     assert_same(got, oracle.run(off, iv, ln, cov, nc, n_threads=4), path)
     return got, names, lengths
 

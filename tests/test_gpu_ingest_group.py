@@ -1,6 +1,7 @@
 """yacrd_engines_ingest_overlaps — the N-GPU form of the device parser (every engine parses a byte range of the text, the
 reads are numbered over the whole file on engine 0, every engine sweeps a range of them) — with N engines on ONE device
 against the one-engine call, the host parser and the oracle: same names, lengths, regions and types, bit for bit."""
+import functools
 import os
 
 import numpy as np
@@ -10,6 +11,7 @@ import oracle
 import yacrd_amd
 from yacrd_amd import host
 from cases import assert_same
+from input_csr_cases import assert_same_csr_in_ranges
 
 pytestmark = pytest.mark.gpu
 CHUNK = 4 << 20  # the ranges are cut on 4 MiB boundaries (gpu_paf.hip)
@@ -60,10 +62,29 @@ def _lines(rng, n, ids, tag=0):
     return out
 
 
-@pytest.mark.parametrize("shape", ["newline_last_byte_of_a_range", "line_starts_a_range", "line_straddles", "long_tag_straddles",
-                                   "empty_lines_at_the_cut", "crlf_split_by_the_cut"])
+BOUNDARY_SHAPES = ("newline_last_byte_of_a_range", "line_starts_a_range", "line_straddles", "long_tag_straddles",
+                   "empty_lines_at_the_cut", "crlf_split_by_the_cut")
+
+
+@pytest.mark.parametrize("shape", BOUNDARY_SHAPES)
 def test_lines_at_the_range_boundaries(engines, tmp_path, shape):
     """Two engines: the cut lies at byte 4 MiB.  A line belongs to the range it starts in, whatever lies at the cut."""
+    text, w_names, off, iv, ln = _boundary_case(shape)
+    p = str(tmp_path / "b.paf")
+    with open(p, "w", newline="") as f:
+        f.write(text)
+    one = engines[0].ingest_paf(p, 2, 0.4)
+    assert one[1] == list(w_names)
+    for n in (2, 3):
+        _same_ingest(yacrd_amd.ingest_overlaps(engines[:n], p, 2, 0.4), one, "%s, %d engines" % (shape, n))
+        assert_same_csr_in_ranges([e.debug_input_csr() for e in engines[:n]], (off, iv, ln), "%s, %d engines" % (shape, n))
+    assert_same(one[0], oracle.run(off, iv, ln, 2, 0.4, n_threads=8), shape)
+
+
+@functools.lru_cache(maxsize=None)
+def _boundary_case(shape):
+    """a text of more than 5 MiB with `shape` at byte 4 MiB, where the first range of two engines ends, and the oracle's names
+    and CSR of it (made once per process: tests/test_gpu_input_csr.py takes the same texts)"""
     rng = np.random.default_rng(abs(hash(shape)) % 1000)
     ids = ["read%04d" % i for i in range(700)]
     body = "".join(_lines(rng, 150000, ids))
@@ -90,16 +111,7 @@ def test_lines_at_the_range_boundaries(engines, tmp_path, shape):
     else:  # crlf_split_by_the_cut: '\r' is the range's last byte, '\n' the next one's first
         text = head + padded(special, room - 1) + "\r\n" + tail
         assert text[CHUNK - 1] == "\r" and text[CHUNK] == "\n"
-    p = str(tmp_path / "b.paf")
-    with open(p, "w", newline="") as f:
-        f.write(text)
-    one = engines[0].ingest_paf(p, 2, 0.4)
-    reads = oracle.parse_paf(text)
-    w_names, off, iv, ln = oracle.to_csr(reads)
-    assert one[1] == list(w_names)
-    for n in (2, 3):
-        _same_ingest(yacrd_amd.ingest_overlaps(engines[:n], p, 2, 0.4), one, "%s, %d engines" % (shape, n))
-    assert_same(one[0], oracle.run(off, iv, ln, 2, 0.4, n_threads=8), shape)
+    return (text,) + tuple(oracle.to_csr(oracle.parse_paf(text)))
 
 
 def test_first_appearance_and_first_length_across_ranges(engines, tmp_path):

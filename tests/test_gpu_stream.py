@@ -9,6 +9,7 @@ import pytest
 import oracle
 import yacrd_amd
 from cases import assert_same
+from input_csr_cases import assert_same_csr
 from yacrd_amd import host
 
 pytestmark = pytest.mark.gpu
@@ -32,12 +33,14 @@ def test_streamed_equals_one_shot_equals_oracle(engine, tmp_path, threads, chunk
     want = oracle_for(ref, 4, 0.4)
     one_shot = engine.run(ref.offsets, ref.intervals, ref.lengths, 4, 0.4)
     assert_same(one_shot, want, "one-shot")
+    assert_same_csr(engine.debug_input_csr(), (ref.offsets, ref.intervals, ref.lengths), "one-shot: the staged CSR", exact=True)
     with yacrd_amd.Stream(engine, chunk, nbuf) as st:
         sink = st.sink()
         c = host.ingest_stream(paf, sink, n_threads=threads)
         assert c.names == ref.names and np.array_equal(c.lengths, ref.lengths)
         got = st.finish(c.handle_map, c.lengths, 4, 0.4)
         stats = st.stats()
+        assert_same_csr(engine.debug_input_csr(), (ref.offsets, ref.intervals, ref.lengths), "streamed: the CSR built in HBM")
     assert_same(got, want, "streamed")
     assert stats["n_records"] == 90000 and stats["h2d_bytes"] == 90000 * 24
     assert stats["h2d_busy_ms"] > 0 and stats["build_ms"] > 0

@@ -10,6 +10,7 @@ import pytest
 import oracle
 import yacrd_amd
 from cases import assert_same
+from input_csr_cases import assert_same_csr, handle_of_read, kept_reads
 from yacrd_amd import host
 
 pytestmark = pytest.mark.gpu
@@ -39,6 +40,11 @@ def test_group_equals_oracle(engines, tmp_path, n, threads, chunk, nbuf):
         assert c.names == ref.names and np.array_equal(c.lengths, ref.lengths)
         got = grp.finish(c.handle_map, c.lengths, 4, 0.4)
         stats = [grp.stats(d) for d in range(n)]
+        # every engine built the CSR of its own reads (handle mod N), in first-appearance order, and nothing of the others'
+        owner = np.array([yacrd_amd.stream_device_of(h, n) for h in handle_of_read(c.handle_map, c.n_reads)])
+        for d in range(n):
+            assert_same_csr(engines[d].debug_input_csr(), kept_reads((ref.offsets, ref.intervals, ref.lengths), owner == d),
+                            "group of %d, engine %d" % (n, d))
     assert_same(got, want, "group of %d" % n)
     assert sum(s["reads_owned"] for s in stats) == len(ref.lengths)
     # a record goes to the device of each of its two reads: between one and two copies of it cross PCIe

@@ -952,7 +952,7 @@ int run_on_device(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u3
     if (n_reads64 >= 0xFFFFFFFFull) return fail(YACRD_EINVAL, "n_reads must be < 2^32 - 1");
     if (e->pending.active) return fail(YACRD_EINVAL, "a submitted batch is pending: yacrd_engine_wait first");
     e->has_result = false;
-    e->resident.valid = false; // (in_len and the result arrays are about to be rewritten)
+    e->resident.valid = e->input.valid = false; // (in_len and the result arrays are about to be rewritten)
     e->timing = yacrd_timing{};
 
     HIP_TRY(e->bad_offsets.reserve((n_reads64 + 1) * sizeof(u64)));
@@ -1317,6 +1317,29 @@ uint64_t yacrd_debug_last_counters(const yacrd_engine *e, void *dst, uint64_t by
     return sizeof(yk::Counters);
 }
 
+/* include/yacrd_engine_debug.h: the input CSR of the engine's last call, from in_off / in_iv / in_len (tests) */
+int yacrd_debug_last_input_csr(yacrd_engine *e, uint64_t *n_reads, uint64_t *n_intervals, uint64_t *offsets, uint32_t *intervals,
+                               uint32_t *lengths)
+{
+    if (!e || !n_reads || !n_intervals) return fail(YACRD_EINVAL, "null argument");
+    if (e->pending.active || e->host_pending) return fail(YACRD_EINVAL, "the engine has a submitted batch pending");
+    if (!e->input.valid) return fail(YACRD_EINVAL, "the engine's last call left no input CSR of its own");
+    const uint64_t R = e->input.n_reads, I = e->input.n_iv;
+    if (offsets && ((I && !intervals) || (R && !lengths))) return fail(YACRD_EINVAL, "null argument");
+    // (the record was made from what the build's scan summed: never read past what the call reserved)
+    if ((R && ((R + 1) * sizeof(u64) > e->in_off.cap || R * sizeof(u32) > e->in_len.cap)) || (I && I * sizeof(uint2) > e->in_iv.cap))
+        return fail(YACRD_EINTERNAL, "the input CSR's record does not fit the engine's input buffers");
+    *n_reads = R, *n_intervals = I;
+    if (!offsets) return YACRD_OK;
+    DeviceGuard guard(e->device);
+    offsets[0] = 0; // (a batch without reads stages nothing)
+    if (R) HIP_TRY(hipMemcpyAsync(offsets, e->in_off.p, (size_t)(R + 1) * sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+    if (I) HIP_TRY(hipMemcpyAsync(intervals, e->in_iv.p, (size_t)I * sizeof(uint2), hipMemcpyDeviceToHost, e->stream));
+    if (R) HIP_TRY(hipMemcpyAsync(lengths, e->in_len.p, (size_t)R * sizeof(u32), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return YACRD_OK;
+}
+
 const char *yacrd_last_error(void) { return yke::err_slot().c_str(); }
 
 int yacrd_engine_create(const yacrd_engine_cfg *cfg, yacrd_engine **out)
@@ -1380,7 +1403,7 @@ int yacrd_engine_trim(yacrd_engine *e)
     if (e->pending.active || e->host_pending) return fail(YACRD_EINVAL, "the engine has a submitted batch pending");
     DeviceGuard guard(e->device);
     e->mirror.valid = false;
-    e->resident.valid = false;
+    e->resident.valid = e->input.valid = false;
     for (int k = 0; k < yacrd_engine::kSlots; k++)
         if (e->scratch[k].p && !(k == yacrd_engine::kGzip && e->gzip_busy)) e->scratch[k].release(e->scratch[k].p);
     return YACRD_OK;
@@ -1425,7 +1448,7 @@ int yacrd_engine_run_device(yacrd_engine *e, const void *d_offsets, const void *
                             uint32_t coverage, double not_coverage, yacrd_device_result *out)
 {
     if (!e) return fail(YACRD_EINVAL, "engine is null");
-    e->resident.valid = false; // (first: everything below may rewrite or move in_len and the result arrays)
+    e->resident.valid = e->input.valid = false; // (first: everything below may rewrite or move in_len and the result arrays)
     if (n_reads && (!d_offsets || !d_lengths)) return fail(YACRD_EINVAL, "null device input");
     if (n_intervals && !d_intervals) return fail(YACRD_EINVAL, "null device intervals");
     if (e->host_pending) return fail(YACRD_EINVAL, "a submitted batch is pending: collect it first");
@@ -1448,7 +1471,7 @@ int yacrd_engine_submit_device(yacrd_engine *e, const void *d_offsets, const voi
                                uint32_t coverage, double not_coverage)
 {
     if (!e) return fail(YACRD_EINVAL, "engine is null");
-    e->resident.valid = false; // (first: everything below may rewrite or move in_len and the result arrays)
+    e->resident.valid = e->input.valid = false; // (first: everything below may rewrite or move in_len and the result arrays)
     if (n_reads && (!d_offsets || !d_lengths)) return fail(YACRD_EINVAL, "null device input");
     if (n_intervals && !d_intervals) return fail(YACRD_EINVAL, "null device intervals");
     if (e->host_pending) return fail(YACRD_EINVAL, "a submitted batch is pending: collect it first");
@@ -1481,7 +1504,7 @@ int yacrd_engines_run_device_batches(yacrd_engine *const *engines, uint32_t n_en
     if (!engines || n_engines == 0 || (!batches && n_batches)) return fail(YACRD_EINVAL, "bad argument");
     for (uint32_t j = 0; j < n_engines; j++)
         if (!engines[j]) return fail(YACRD_EINVAL, "engine is null");
-    for (uint32_t j = 0; j < n_engines; j++) engines[j]->resident.valid = false;
+    for (uint32_t j = 0; j < n_engines; j++) engines[j]->resident.valid = engines[j]->input.valid = false;
     std::vector<int64_t> inflight(n_engines, -1); // batch in flight on each engine
     yacrd_device_result res{};
     auto finish = [&](uint32_t j) -> int {
@@ -1548,7 +1571,7 @@ int yacrd_engine_run(yacrd_engine *e, const uint64_t *offsets, const uint32_t *i
                      double not_coverage, yacrd_result *out)
 {
     if (!e) return fail(YACRD_EINVAL, "engine is null");
-    e->resident.valid = false; // (first: everything below may rewrite or move in_len and the result arrays)
+    e->resident.valid = e->input.valid = false; // (first: everything below may rewrite or move in_len and the result arrays)
     if (!out) return fail(YACRD_EINVAL, "out is null");
     std::memset(out, 0, sizeof(*out));
     if (e->pending.active) return fail(YACRD_EINVAL, "a submitted batch is pending: yacrd_engine_wait first");
@@ -1566,6 +1589,7 @@ int yacrd_engine_run(yacrd_engine *e, const uint64_t *offsets, const uint32_t *i
     e->timing_sum.h2d_ms += e->timing.h2d_ms;
     rc = fetch_result(e, out);
     if (!rc) e->timing_sum.d2h_ms += e->timing.d2h_ms;
+    if (!rc) e->input.n_reads = n_reads, e->input.n_iv = n_iv, e->input.valid = true;
     return rc;
 }
 
@@ -1574,7 +1598,7 @@ int yacrd_engine_submit(yacrd_engine *e, const uint64_t *offsets, const uint32_t
                         double not_coverage)
 {
     if (!e) return fail(YACRD_EINVAL, "engine is null");
-    e->resident.valid = false; // (first: everything below may rewrite or move in_len and the result arrays)
+    e->resident.valid = e->input.valid = false; // (first: everything below may rewrite or move in_len and the result arrays)
     if (e->pending.active || e->host_pending)
         return fail(YACRD_EINVAL, "a submitted batch is pending: collect it first");
     DeviceGuard guard(e->device);
@@ -1584,6 +1608,7 @@ int yacrd_engine_submit(yacrd_engine *e, const uint64_t *offsets, const uint32_t
     rc = run_on_device(e, e->in_off.as<u64>(), e->in_iv.as<uint2>(), e->in_len.as<u32>(), n_reads,
                        n_iv, coverage, not_coverage, true);
     if (rc) return rc;
+    e->input.n_reads = n_reads, e->input.n_iv = n_iv; // (valid once the batch is collected)
     e->host_pending = true;
     return YACRD_OK;
 }
@@ -1602,6 +1627,7 @@ int yacrd_engine_collect(yacrd_engine *e, yacrd_result *out)
     e->timing_sum.h2d_ms += e->timing.h2d_ms;
     rc = fetch_result(e, out);
     if (!rc) e->timing_sum.d2h_ms += e->timing.d2h_ms;
+    if (!rc) e->input.valid = true; // (the batch yacrd_engine_submit staged in in_off / in_iv / in_len)
     return rc;
 }
 
@@ -1707,7 +1733,7 @@ int yacrd_engines_run_partitioned(yacrd_engine *const *engines, uint32_t n_engin
     std::memset(out, 0, sizeof(*out));
     for (uint32_t p = 0; p < n_engines; p++)
         if (!engines[p]) return fail(YACRD_EINVAL, "null engine");
-    for (uint32_t p = 0; p < n_engines; p++) engines[p]->resident.valid = false;
+    for (uint32_t p = 0; p < n_engines; p++) engines[p]->resident.valid = engines[p]->input.valid = false;
     std::vector<uint64_t> cuts(n_engines + 1);
     int rc = yacrd_partition_reads(offsets, n_reads, n_engines, cuts.data());
     if (rc) return rc;
@@ -1770,7 +1796,7 @@ int yacrd_engine_classify(yacrd_engine *e, const uint64_t *bad_offsets, const ui
                           uint8_t *read_type)
 {
     if (!e) return fail(YACRD_EINVAL, "engine is null");
-    e->resident.valid = false;
+    e->resident.valid = e->input.valid = false;
     if (n_reads == 0) return YACRD_OK;
     if (!bad_offsets || !lengths || !read_type) return fail(YACRD_EINVAL, "null argument");
     if (n_reads >= 0xFFFFFFFFull) return fail(YACRD_EINVAL, "n_reads must be < 2^32 - 1");

@@ -308,6 +308,15 @@ struct yacrd_engine {
         uint64_t n_reads = 0;
         bool valid = false;
     } resident;
+    // the input CSR the engine's last call left in ITS OWN in_off / in_iv / in_len (yacrd_debug_last_input_csr brings it home:
+    // tests compare it with a reference, interval by interval).  Set as the last step of a successful call that filled those
+    // buffers itself: run, submit + collect, a stream's or group's finish, the device parser with one engine or several.
+    // Cleared, like `resident`, by the first statement of every entry point that may rewrite, move or release them or that
+    // sweeps somebody else's pointers (the device and batch forms, ingest_report, classify, trim), so a failed call leaves none.
+    struct {
+        uint64_t n_reads = 0, n_iv = 0;
+        bool valid = false;
+    } input;
     // what the text paths keep between calls (their own types: device and pinned buffers, grow-only), made on first use by
     // yke::scratch_of; yacrd_engine_trim releases their buffers, yacrd_engine_destroy deletes them
     enum Slot { kPaf = 0, kEdit, kGzip, kReport, kReportWrite, kSlots };

@@ -737,7 +737,7 @@ int parse_range(yacrd_engine *e, const TextSource &src, u64 file_n, u64 begin, u
     if (!Sp) return fail(YACRD_ENOMEM, "host allocation failed");
     Scratch &S = *Sp;
     e->mirror.valid = false; // (the mirror is about to be rewritten)
-    e->resident.valid = false;
+    e->resident.valid = e->input.valid = false;
     // the mirror holds the range and, behind it, up to one chunk more of the file: a line that starts in the range ends there
     // (or the parse says so: kNeedHost)
     constexpr u64 kOverhang = (u64)4 << 20;
@@ -878,7 +878,8 @@ int ingest_text(yacrd_engine *e, const TextSource &src, u64 n, bool m4, int n_th
     if (const int rch = reads_to_host(e, reads, ro.R, ro.n_recs, e->in_len.p, S.range.name_off.p, S.range.names.p, ro.name_bytes)) return rch;
     // ---- CSR on the device (csr_build.h through stream.hip's helper), then the engine
     const RecSlab slab{S.recs.as<yk::OvlRec>(), ro.n_recs};
-    int rc = csr_from_records(e, &slab, 1, S.map.as<u32>(), ro.cap, ro.R, S.range.cnt, S.part, S.err, nullptr, nullptr, true);
+    u64 n_iv = 0; // (what the build's scan summed: two per record)
+    int rc = csr_from_records(e, &slab, 1, S.map.as<u32>(), ro.cap, ro.R, S.range.cnt, S.part, S.err, nullptr, &n_iv, true);
     const double t_build = now_ms();
     if (!rc) rc = run_on_device(e, e->in_off.as<u64>(), e->in_iv.as<uint2>(), e->in_len.as<u32>(), ro.R, 2 * ro.n_recs, coverage, not_coverage);
     const double t_run = now_ms();
@@ -901,6 +902,7 @@ int ingest_text(yacrd_engine *e, const TextSource &src, u64 n, bool m4, int n_th
     // the table stays where it is: a report can be written from it (gpu_report_write.hip)
     e->resident.names = S.range.names.as<unsigned char>(), e->resident.name_off = S.range.name_off.as<u64>(), e->resident.lengths = e->in_len.as<u32>();
     e->resident.n_reads = ro.R, e->resident.valid = true;
+    e->input.n_reads = ro.R, e->input.n_iv = n_iv, e->input.valid = true;
     return YACRD_OK;
 }
 
@@ -1306,7 +1308,9 @@ struct GroupRun {
             r = run_on_device(e, e->in_off.as<u64>(), e->in_iv.as<uint2>(), e->in_len.as<u32>(), Ro, n_iv, coverage, not_coverage);
             if (r) return r;
             t_ran[o] = now_ms();
-            return fetch_result(e, &parts.v[o]);
+            r = fetch_result(e, &parts.v[o]);
+            if (!r) e->input.n_reads = Ro, e->input.n_iv = n_iv, e->input.valid = true;
+            return r;
         });
     }
 
@@ -1371,8 +1375,12 @@ int ingest_text_group(yacrd_engine *const *E, uint32_t N, const TextSource &src,
     if (const int rc = g.merge(reads)) return rc;
     g.deal();
     if (const int rc = g.rewrite()) return rc;
-    if (const int rc = g.build_and_sweep(coverage, not_coverage)) return rc;
-    if (const int rc = g.stitch(out)) return rc;
+    int rc = g.build_and_sweep(coverage, not_coverage);
+    if (!rc) rc = g.stitch(out);
+    if (rc) { // (a failed call leaves no engine with an input CSR to show: yacrd_debug_last_input_csr)
+        for (uint32_t d = 0; d < N; d++) E[d]->input.valid = false;
+        return rc;
+    }
     if (stats) g.fill_stats(reads, stats);
     return YACRD_OK;
 }
@@ -1411,7 +1419,7 @@ int yacrd_engine_ingest_overlaps(yacrd_engine *e, const char *path, int format, 
                                  double not_coverage, yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats)
 {
     if (!e || !path || !out || !reads) return fail(YACRD_EINVAL, "null argument");
-    e->resident.valid = false;
+    e->resident.valid = e->input.valid = false;
     OverlapFile f;
     if (const int rcf = overlap_format(path, format, f.m4)) return rcf;
     zero_outputs(out, reads, stats);
@@ -1432,7 +1440,7 @@ int yacrd_engine_ingest_overlaps_mem(yacrd_engine *e, const char *text, uint64_t
                                      double not_coverage, yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats)
 {
     if (!e || (!text && n) || !out || !reads) return fail(YACRD_EINVAL, "null argument");
-    e->resident.valid = false;
+    e->resident.valid = e->input.valid = false;
     bool m4 = false;
     if (const int rcf = overlap_format(nullptr, format, m4)) return rcf;
     zero_outputs(out, reads, stats);
@@ -1447,7 +1455,7 @@ static int group_args(yacrd_engine *const *engines, uint32_t n_engines, yacrd_re
     if (!engines || !n_engines || !out || !reads) return fail(YACRD_EINVAL, "null argument");
     for (uint32_t d = 0; d < n_engines; d++) {
         if (!engines[d]) return fail(YACRD_EINVAL, "engine is null");
-        engines[d]->resident.valid = false; // (an engine that parses no range still gets its reads' lengths in in_len)
+        engines[d]->resident.valid = engines[d]->input.valid = false; // (an engine that parses no range still gets its reads' lengths in in_len)
         if (engines[d]->pending.active || engines[d]->host_pending) return fail(YACRD_EINVAL, "an engine has a submitted batch pending");
         for (uint32_t k = 0; k < d; k++)
             if (engines[k] == engines[d]) return fail(YACRD_EINVAL, "the same engine twice");

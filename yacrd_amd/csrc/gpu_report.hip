@@ -340,7 +340,7 @@ int read_report(yacrd_engine *e, const TextSource &src, u64 n, int n_threads, do
     ReportScratch *Sp = scratch_of<ReportScratch>(e);
     if (!Sp) return fail(YACRD_ENOMEM, "host allocation failed");
     ReportScratch &S = *Sp;
-    e->resident.valid = false;
+    e->resident.valid = e->input.valid = false;
     const double t_start = now_ms();
     const u64 n_tiles = (n + yk::kGpTile - 1) / yk::kGpTile;
     if (n_tiles >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "file too large for the device report reader");
@@ -493,7 +493,7 @@ int read_report(yacrd_engine *e, const TextSource &src, u64 n, int n_threads, do
 int report_args(yacrd_engine *e, yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats)
 {
     if (!e || !out || !reads) return fail(YACRD_EINVAL, "null argument");
-    e->resident.valid = false;
+    e->resident.valid = e->input.valid = false;
     zero_outputs(out, reads, stats);
     if (e->pending.active || e->host_pending) return fail(YACRD_EINVAL, "the engine has a submitted batch pending");
     return YACRD_OK;

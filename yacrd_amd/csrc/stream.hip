@@ -321,7 +321,7 @@ int yacrd_stream_finish(yacrd_stream *s, const uint32_t *handle_map, uint64_t n_
                         double not_coverage, yacrd_result *out)
 {
     if (!s || !out) return fail(YACRD_EINVAL, "null argument");
-    s->e->resident.valid = false; // (first: in_len is rewritten below, before the last thing that can fail)
+    s->e->resident.valid = s->e->input.valid = false; // (first: in_len is rewritten below, before the last thing that can fail)
     std::memset(out, 0, sizeof(*out));
     if (n_reads && !lengths) return fail(YACRD_EINVAL, "null lengths");
     if (n_reads >= 0xFFFFFFFFull) return fail(YACRD_EINVAL, "n_reads must be < 2^32 - 1");
@@ -379,6 +379,7 @@ int yacrd_stream_finish(yacrd_stream *s, const uint32_t *handle_map, uint64_t n_
     s->stats.run_ms = (float)(now_ms() - t0);
     rc = fetch_result(e, out);
     s->stats.d2h_ms = e->timing.d2h_ms;
+    if (!rc) e->input.n_reads = n_reads, e->input.n_iv = n_iv_here, e->input.valid = true;
     return rc;
 }
 
@@ -561,7 +562,7 @@ int yacrd_stream_group_finish(yacrd_stream_group *g, const uint32_t *handle_map,
 {
     if (!g || !out) return fail(YACRD_EINVAL, "null argument");
     const uint32_t N = (uint32_t)g->st.size();
-    for (yacrd_stream *s : g->st) s->e->resident.valid = false;
+    for (yacrd_stream *s : g->st) s->e->resident.valid = s->e->input.valid = false;
     if (N == 1) {
         g->owned[0] = n_reads;
         return yacrd_stream_finish(g->st[0], handle_map, n_handles, lengths, n_reads, coverage, not_coverage, out);
@@ -624,11 +625,16 @@ int yacrd_stream_group_finish(yacrd_stream_group *g, const uint32_t *handle_map,
     bool any_failed = false;
     for (uint32_t d = 0; d < N; d++) any_failed |= codes[d] != YACRD_OK;
     reset_on_exit.armed = any_failed;
+    // (a group call that fails leaves no engine with an input CSR to show: yacrd_debug_last_input_csr)
+    auto drop_inputs = [&] {
+        for (yacrd_stream *s : g->st) s->e->input.valid = false;
+    };
     for (uint32_t d = 0; d < N; d++)
         if (codes[d]) {
             const int code = codes[d];
             const std::string msg = "device " + std::to_string(d) + ": " + errs[d];
             for (auto &r : parts) yacrd_result_free(&r);
+            drop_inputs();
             return fail(code, msg);
         }
     // merge: first-appearance order again
@@ -640,6 +646,7 @@ int yacrd_stream_group_finish(yacrd_stream_group *g, const uint32_t *handle_map,
     if (!out->bad_offsets || !out->bad_regions || !out->read_type) {
         for (auto &r : parts) yacrd_result_free(&r);
         yacrd_result_free(out);
+        drop_inputs();
         return fail(YACRD_ENOMEM, "host allocation failed");
     }
     std::vector<uint64_t> next(N, 0);

@@ -643,6 +643,24 @@ class Engine:
         _check(self._lib, self._lib.yacrd_debug_sort_pairs(self._h, keys.ctypes.data, vals.ctypes.data, keys.shape[0], int(key_bound)))
         return keys, vals
 
+    def debug_input_csr(self):
+        """yacrd_debug_last_input_csr (tests): the input CSR the engine's last call built or staged in its own buffers in HBM,
+        as (offsets u64[R+1], intervals u32[I,2], lengths u32[R]); None when that call left none (a _device form, ingest_report,
+        trim, a failed call) or a submitted batch is pending."""
+        f = self._lib.yacrd_debug_last_input_csr
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p,
+                      ctypes.c_void_p, ctypes.c_void_p]
+        R, I = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = f(self._h, ctypes.byref(R), ctypes.byref(I), None, None, None)
+        if rc == 1:  # YACRD_EINVAL
+            return None
+        _check(self._lib, rc)
+        off = np.zeros(R.value + 1, dtype=np.uint64)
+        iv = np.zeros((I.value, 2), dtype=np.uint32)
+        ln = np.zeros(R.value, dtype=np.uint32)
+        _check(self._lib, f(self._h, ctypes.byref(R), ctypes.byref(I), off.ctypes.data, iv.ctypes.data, ln.ctypes.data))
+        return off, iv, ln
+
     def debug_counters(self):
         """yacrd_debug_last_counters (tools, tests): the device-side counter block of the last run, by name
         (csrc/device_common.h: struct Counters; the layout is mirrored here and is not part of any ABI)."""
