@@ -75,6 +75,11 @@ int yacrd_debug_last_input_csr(yacrd_engine *e, uint64_t *n_reads, uint64_t *n_i
  * one device, and makes every engine gather the other engines' records instead of reading them in place: the multi-device
  * branch on a one-GPU box. */
 void yacrd_debug_peer_copy_counts(uint64_t out[3]);
+/* bytes the library holds right now, process-wide: [0] device memory, [1] pinned host memory.  Every allocation of
+ * libyacrd_hip.so goes through the two owner types that keep these counts (csrc/engine_internal.h: DevBuf, PinBuf), except
+ * yacrd_pinned_alloc's, which belongs to the caller.  Tests: what is live before an engine, stream or writer is made is live
+ * again once it is closed. */
+void yacrd_debug_live_bytes(uint64_t out[2]);
 /* YACRD_TEST_REPORT_SEGMENT=<bytes> (environment, tests; read at every call): the size of the segments in which
  * yacrd_engine_write_report[_mem] brings the formatted text home, instead of 64 MiB (csrc/gpu_report_write.hip: kReportSegment;
  * 1 .. 2^30).  The bytes written do not depend on it: tests/test_gpu_report_write.py cuts lines at hundreds of borders. */

@@ -12,6 +12,7 @@ import report_cases as rc
 import report_write_cases as wc
 import yacrd_amd
 from yacrd_amd import host
+from yacrd_amd.engine import live_bytes
 
 pytestmark = pytest.mark.gpu
 
@@ -62,7 +63,8 @@ def test_golden_file_resident_and_table_forms(engine, golden_dir, tmp_path):
 
 def test_one_engine_through_every_text_path_and_trim(golden_dir, tmp_path):
     """parser, editor (from the mirror), encoder, report reader and report writer on ONE engine, trim, the same again: the
-    engine's registry of their buffers is walked with every slot live, by trim and by the engine's end"""
+    engine's registry of their buffers is walked with every slot live, by trim and by the engine's end.  The library's count
+    of the bytes it holds (live_bytes) says what each trim gave back and that the engine's end gives back everything"""
     paf, rep = os.path.join(golden_dir, "reads.paf"), os.path.join(golden_dir, "truth.yacrd")
 
     def flat(res, names, lengths):
@@ -81,10 +83,15 @@ def test_one_engine_through_every_text_path_and_trim(golden_dir, tmp_path):
         table = e.report_text([n.encode() for n in names], lengths, res)
         return flat(res, names, lengths) + [kept, blob] + flat(res2, names2, lengths2) + [dev.read_bytes(), table]
 
+    live_before = live_bytes()
     with yacrd_amd.Engine(device_id=0) as e:
         first = every_path(e, "first")
         e.trim()
+        live_trimmed = live_bytes()
         again = every_path(e, "again")
+        e.trim()
+        # (the batch path's buffers are grow-only and the inputs were the same: the text paths' scratch is all that came and went)
+        assert live_bytes() == live_trimmed
         assert len(first) == len(again) == 14
         for a, b in zip(first, again):
             assert np.array_equal(a, b) if isinstance(a, np.ndarray) else a == b
@@ -95,10 +102,14 @@ def test_one_engine_through_every_text_path_and_trim(golden_dir, tmp_path):
         w = e.gzip_writer(str(gz))
         w.write(kept[:len(kept) // 2])
         e.trim()
+        live_writer_open = live_bytes()
         w.write(kept[len(kept) // 2:])
         w.close()
         assert gz.read_bytes() == blob
         assert not [n for n in os.listdir(tmp_path) if ".gz." in n or ".yacrd." in n or ".paf." in n]
+        e.trim()
+        assert live_writer_open[0] > live_bytes()[0]  # (the trim under the open writer left the encoder's buffers)
+    assert live_bytes() == live_before
 
 
 def test_fuzz_tables_equal_the_host_writer(engine, tmp_path):

@@ -121,7 +121,7 @@ yk::CompactArgs2 compact_args(const yacrd_engine *e, const Run &R)
     ca.bad_regions = e->bad_regions.as<uint2>();
     ca.region_cap = (u64)(e->bad_regions.cap / sizeof(uint2));
     ca.read_type = e->read_type.as<uint8_t>();
-    ca.host_ctr = e->h_ctr;
+    ca.host_ctr = e->h_ctr();
     return ca;
 }
 
@@ -366,9 +366,9 @@ int run_big(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u32 *d_l
 int wait_for_stream(yacrd_engine *e)
 {
     if (e->flags & YACRD_F_BLOCKING_WAIT) {
-        HIP_TRY(hipEventRecord(e->ev_done, e->stream));
+        HIP_TRY(hipEventRecord(e->ev_sync[EVS_DONE], e->stream));
         for (;;) {
-            const hipError_t q = hipEventQuery(e->ev_done);
+            const hipError_t q = hipEventQuery(e->ev_sync[EVS_DONE]);
             if (q == hipSuccess) break;
             if (q != hipErrorNotReady) HIP_TRY(q);
             struct timespec ts = {0, 20000};
@@ -447,8 +447,8 @@ int launch_one_batch(yacrd_engine *e, Run &R)
     oa.n_slabs = R.ob_slabs;
     oa.zero = e->ctrl2[other].as<u32>();
     oa.zero_words = (u32)(R.other_bytes / 4);
-    e->h_ctr->ob_unsupported = 0; // (written from the device only when set)
-    e->h_ctr->scan_ticket = 0;    // (the slab that ends the batch sends the counters home: nb tickets then)
+    e->h_ctr()->ob_unsupported = 0; // (written from the device only when set)
+    e->h_ctr()->scan_ticket = 0;    // (the slab that ends the batch sends the counters home: nb tickets then)
     // (one wavefront per kObReads reads; slabs go round the XCDs, so the grid is whole rounds of eight slabs)
     hipLaunchKernelGGL(yk::one_batch_kernel, dim3(((R.ob_slabs + 7) / 8) * 8 * (u32)(yk::kObSlab / yk::kObReads)), dim3(64), 0, e->stream, oa);
     e->ctrl_clean[other] = R.other_bytes;
@@ -509,9 +509,9 @@ int size_launches(yacrd_engine *e, Run &R)
         }
         R.big_n = e->pred.n[yk::CLS_GENERAL], R.big_iv = e->pred.iv[yk::CLS_GENERAL];
     } else {
-        HIP_TRY(hipMemcpyAsync(e->h_ctr, R.ctr, sizeof(yk::Counters), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync(e->h_ctr(), R.ctr, sizeof(yk::Counters), hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
-        R.c0 = *e->h_ctr;
+        R.c0 = *e->h_ctr();
         for (int cls = 0; cls < yk::CLS_GENERAL; cls++) {
             ls.n[cls] = R.c0.n[cls];
             ls.hint[cls] = R.c0.n[cls];
@@ -804,23 +804,21 @@ int launch_device_wide_screen(yacrd_engine *e, Run &R)
 {
     const bool can_fork = R.big_n != 0 && R.prefilter && !(e->flags & YACRD_F_FORCE_GENERAL);
     if (can_fork && e->side == nullptr) {
-        if (hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) != hipSuccess) {
-            (void)hipGetLastError();
-            e->side = nullptr; // (no side stream: the launches go out behind the other classes', as until round 5)
-        }
+        if (e->streams.add(1)) e->side = e->streams[1];
+        else (void)hipGetLastError(); // (no side stream: the launches go out behind the other classes', as until round 5)
     }
     R.big_beside = can_fork && e->side != nullptr;
     if (!R.big_beside) return YACRD_OK;
-    HIP_TRY(hipEventRecord(e->ev_fork, e->stream));
-    HIP_TRY(hipStreamWaitEvent(e->side, e->ev_fork, 0));
+    HIP_TRY(hipEventRecord(e->ev_sync[EVS_FORK], e->stream));
+    HIP_TRY(hipStreamWaitEvent(e->side, e->ev_sync[EVS_FORK], 0));
     const int rc = launch_device_wide_screen_on(e, R, R.big_n, R.big_iv, e->side);
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(e->ev_join, e->side));
+    HIP_TRY(hipEventRecord(e->ev_sync[EVS_JOIN], e->side));
     return YACRD_OK;
 }
 int join_device_wide_screen(yacrd_engine *e, Run &R)
 {
-    if (R.big_beside) HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_join, 0));
+    if (R.big_beside) HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_sync[EVS_JOIN], 0));
     else if (R.big_n) return launch_device_wide_screen_on(e, R, R.big_n, R.big_iv, e->stream);
     return YACRD_OK;
 }
@@ -845,7 +843,7 @@ int recover(yacrd_engine *e, Run &R, float &extra_ms)
     int rc = YACRD_OK;
     bool redo = false;
     if (R.predicted) {
-        R.c0 = *e->h_ctr; // the plan's real counts
+        R.c0 = *e->h_ctr(); // the plan's real counts
         const yk::Counters &c0 = R.c0;
         LaunchSet missing{};
         bool any_missing = false;
@@ -864,30 +862,30 @@ int recover(yacrd_engine *e, Run &R, float &extra_ms)
             if (big_mismatch && c0.n[yk::CLS_GENERAL] &&
                 (rc = launch_device_wide_screen_on(e, R, c0.n[yk::CLS_GENERAL], c0.iv[yk::CLS_GENERAL], e->stream))) return rc;
             // the rejection counters may have grown: bring them home before looking at rej_big
-            HIP_TRY(hipMemcpyAsync(e->h_ctr, ctr, sizeof(yk::Counters), hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipMemcpyAsync(e->h_ctr(), ctr, sizeof(yk::Counters), hipMemcpyDeviceToHost, e->stream));
             HIP_TRY(hipStreamSynchronize(e->stream));
             redo = true;
         }
     }
     // (A redo of the follow-on kernel may reject more reads: the loop below looks again.)
     u32 rej_small_done = 0;
-    if (e->h_ctr->rej_small) {
+    if (e->h_ctr()->rej_small) {
         if (!redo) HIP_TRY(hipEventRecord(e->ev[EV_X0], e->stream));
         launch_rejected_small(e, R);
-        rej_small_done = e->h_ctr->rej_small;
+        rej_small_done = e->h_ctr()->rej_small;
         redo = true;
     }
-    if (R.big_screened && e->h_ctr->fb_big) { // BIG reads the screen could not decide: trimming filter / segmented sort
+    if (R.big_screened && e->h_ctr()->fb_big) { // BIG reads the screen could not decide: trimming filter / segmented sort
         if (!redo) HIP_TRY(hipEventRecord(e->ev[EV_X0], e->stream));
-        rc = run_big(e, R.d_off, R.d_iv, R.d_len, R.fb_big, e->h_ctr->fb_big, R.cov, e->stream);
+        rc = run_big(e, R.d_off, R.d_iv, R.d_len, R.fb_big, e->h_ctr()->fb_big, R.cov, e->stream);
         if (rc) return rc;
         // (its rejections — a degenerate interval in a huge read — went the exact way inside run_big; the other
         // rejection counters may have grown)
-        HIP_TRY(hipMemcpyAsync(e->h_ctr, ctr, sizeof(yk::Counters), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync(e->h_ctr(), ctr, sizeof(yk::Counters), hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
         redo = true;
     }
-    const u32 n_rej_big = e->h_ctr->rej_big;
+    const u32 n_rej_big = e->h_ctr()->rej_big;
     if (n_rej_big) {
         if (!redo) HIP_TRY(hipEventRecord(e->ev[EV_X0], e->stream));
         rc = run_general_global(e, R.d_off, R.d_iv, R.d_len, R.rej_big, n_rej_big, R.cov, e->stream);
@@ -895,15 +893,15 @@ int recover(yacrd_engine *e, Run &R, float &extra_ms)
         redo = true;
     }
     for (int attempt = 0; attempt < 4; attempt++) {
-        if (!redo && e->h_ctr->rej_small > rej_small_done) { // the redone follow-on kernel rejected reads of its own
+        if (!redo && e->h_ctr()->rej_small > rej_small_done) { // the redone follow-on kernel rejected reads of its own
             HIP_TRY(hipEventRecord(e->ev[EV_X0], e->stream));
             launch_rejected_small(e, R);
-            rej_small_done = e->h_ctr->rej_small;
+            rej_small_done = e->h_ctr()->rej_small;
             redo = true;
         }
         if (!redo) {
-            if (!e->h_ctr->region_overflow) break;
-            HIP_TRY(e->bad_regions.reserve((size_t)(e->h_ctr->total_regions + 16) * sizeof(uint2)));
+            if (!e->h_ctr()->region_overflow) break;
+            HIP_TRY(e->bad_regions.reserve((size_t)(e->h_ctr()->total_regions + 16) * sizeof(uint2)));
             HIP_TRY(hipEventRecord(e->ev[EV_X0], e->stream));
         }
         redo = false;
@@ -917,8 +915,8 @@ int recover(yacrd_engine *e, Run &R, float &extra_ms)
         HIP_TRY(hipGetLastError());
         extra_ms += ev_ms(e->ev[EV_X0], e->ev[EV_X1]);
     }
-    if (e->h_ctr->region_overflow) return fail(YACRD_EINTERNAL, "bad_regions overflow persisted");
-    if (e->h_ctr->rej_small > rej_small_done) return fail(YACRD_EINTERNAL, "rejected reads persisted");
+    if (e->h_ctr()->region_overflow) return fail(YACRD_EINTERNAL, "bad_regions overflow persisted");
+    if (e->h_ctr()->rej_small > rej_small_done) return fail(YACRD_EINTERNAL, "rejected reads persisted");
     return YACRD_OK;
 }
 
@@ -1000,6 +998,15 @@ int run_on_device(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u3
         bool before;
         ~MissGuard() { e->miss_pending = before; }
     } miss_guard{e, e->miss_pending};
+    struct SideGuard { // (no way out between the fork and the join leaves the side stream's kernels writing what the next call may free)
+        yacrd_engine *e;
+        const Run &R;
+        bool joined = false;
+        ~SideGuard()
+        {
+            if (R.big_beside && !joined) (void)hipStreamSynchronize(e->side);
+        }
+    } side_guard{e, R};
     e->prev_build = e->last_build;
     e->last_build = -1;
     if (R.full) HIP_TRY(hipEventRecord(e->ev[EV_S0], e->stream));
@@ -1007,6 +1014,7 @@ int run_on_device(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u3
     if (!rc) rc = launch_sweeps(e, R, R.ls);
     if (!rc) rc = join_device_wide_screen(e, R);
     if (rc) return rc;
+    side_guard.joined = true;
     if (R.full) HIP_TRY(hipEventRecord(e->ev[EV_GEN], e->stream));
     rc = launch_compact(e, R); // the follow-on step: scan + compact + classify
     if (rc) return rc;
@@ -1016,7 +1024,7 @@ int run_on_device(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u3
     rc = wait_for_stream(e);
     if (rc) return rc;
     R.timing_on = false;
-    if (e->h_ctr->fused_gave_up && !e->fused_off) return rerun_without_fused(e, R);
+    if (e->h_ctr()->fused_gave_up && !e->fused_off) return rerun_without_fused(e, R);
     float extra_ms = 0.f;
     rc = recover(e, R, extra_ms);
     if (rc) return rc;
@@ -1060,7 +1068,7 @@ void fold_timing(yacrd_engine *e)
 int conclude_run(yacrd_engine *e, const Run &R, float extra_ms)
 {
     const bool full = R.full, predicted = R.predicted, screened = R.screened;
-    const yk::Counters c1 = *e->h_ctr;
+    const yk::Counters c1 = *e->h_ctr();
     const yk::Counters c0 = predicted ? c1 : R.c0; // class counts are final either way
     e->last_reads = R.n_reads;
     e->last_regions = c1.total_regions;
@@ -1160,7 +1168,7 @@ int finish_pending(yacrd_engine *e)
     if (p.one_launch) {
         // a read beyond 256 intervals, one the sort rejected (the exact path's) or more regions than bad_regions holds:
         // the default path has every redo — the batch takes it from the start
-        const yk::Counters c1 = *e->h_ctr;
+        const yk::Counters c1 = *e->h_ctr();
         if (c1.ob_unsupported || c1.rej_small || c1.region_overflow || c1.scan_ticket != R.ob_slabs) {
             if (c1.region_overflow) HIP_TRY(e->bad_regions.reserve((size_t)(c1.total_regions + 16) * sizeof(uint2)));
             e->one_launch_off = true;
@@ -1180,7 +1188,7 @@ int finish_pending(yacrd_engine *e)
         fold_timing(e);
         return YACRD_OK;
     }
-    const yk::Counters c = *e->h_ctr;
+    const yk::Counters c = *e->h_ctr();
     if (c.fused_gave_up && !e->fused_off) return yke::rerun_without_fused(e, R);
     bool ok = !c.rej_small && c.n[yk::CLS_GENERAL] == R.big_n && c.iv[yk::CLS_GENERAL] == R.big_iv && !c.fb_big && !c.rej_big && !c.region_overflow;
     for (int cls = 0; cls < yk::CLS_GENERAL; cls++) ok = ok && c.n[cls] <= R.ls.n[cls];
@@ -1213,10 +1221,12 @@ int h2d(yacrd_engine *e, void *dst, const void *src, size_t bytes)
         return YACRD_OK;
     }
     constexpr size_t kPiece = yacrd_engine::kBounceBytes;
-    for (int b = 0; b < yacrd_engine::kBounce; b++) {
-        if (e->bounce[b]) continue;
-        HIP_TRY(hipHostMalloc(&e->bounce[b], kPiece));
-        HIP_TRY(hipEventCreateWithFlags(&e->bounce_ev[b], hipEventDisableTiming));
+    for (size_t b = e->bounce_ev.v.size(); b < (size_t)yacrd_engine::kBounce; b++) { // (buffer b exists iff its event does)
+        HIP_TRY(e->bounce[b].reserve(kPiece));
+        if (!e->bounce_ev.add(1, hipEventDisableTiming)) {
+            e->bounce[b].release();
+            HIP_TRY(why_not_added());
+        }
     }
     const size_t n_pieces = (bytes + kPiece - 1) / kPiece;
     const int T = (int)std::min<size_t>(yacrd_engine::kBounce / 2, n_pieces);
@@ -1234,8 +1244,8 @@ int h2d(yacrd_engine *e, void *dst, const void *src, size_t bytes)
                 if (w != hipSuccess) errs[t] = w;
             }
             const size_t at2 = piece * kPiece, n = std::min(kPiece, bytes - at2);
-            std::memcpy(e->bounce[b], (const char *)src + at2, n);
-            hipError_t c = hipMemcpyAsync((char *)dst + at2, e->bounce[b], n, hipMemcpyHostToDevice, e->stream);
+            std::memcpy(e->bounce[b].p, (const char *)src + at2, n);
+            hipError_t c = hipMemcpyAsync((char *)dst + at2, e->bounce[b].p, n, hipMemcpyHostToDevice, e->stream);
             if (c == hipSuccess) c = hipEventRecord(e->bounce_ev[b], e->stream);
             if (c != hipSuccess) errs[t] = c;
             e->bounce_busy[b] = true;
@@ -1289,18 +1299,18 @@ int fetch_result(yacrd_engine *e, yacrd_result *out)
     void *t_off = staged ? (void *)h : (void *)out->bad_offsets;
     void *t_reg = staged ? (void *)(h + o_reg) : (void *)out->bad_regions;
     void *t_typ = staged ? (void *)(h + o_typ) : (void *)out->read_type;
-    HIP_TRY(hipEventRecord(e->ev_d2h0, e->stream));
+    HIP_TRY(hipEventRecord(e->ev[EV_D2H0], e->stream));
     HIP_TRY(hipMemcpyAsync(t_off, e->bad_offsets.p, b_off, hipMemcpyDeviceToHost, e->stream));
     if (G) HIP_TRY(hipMemcpyAsync(t_reg, e->bad_regions.p, b_reg, hipMemcpyDeviceToHost, e->stream));
     if (R) HIP_TRY(hipMemcpyAsync(t_typ, e->read_type.p, b_typ, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipEventRecord(e->ev_d2h1, e->stream));
+    HIP_TRY(hipEventRecord(e->ev[EV_D2H1], e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (staged) {
         std::memcpy(out->bad_offsets, t_off, b_off);
         if (G) std::memcpy(out->bad_regions, t_reg, b_reg);
         if (R) std::memcpy(out->read_type, t_typ, b_typ);
     }
-    e->timing.d2h_ms = ev_ms(e->ev_d2h0, e->ev_d2h1);
+    e->timing.d2h_ms = ev_ms(e->ev[EV_D2H0], e->ev[EV_D2H1]);
     out->n_reads = R;
     out->n_regions = G;
     return YACRD_OK;
@@ -1313,7 +1323,7 @@ int yacrd_abi_version(void) { return YACRD_ABI_VERSION; }
 
 uint64_t yacrd_debug_last_counters(const yacrd_engine *e, void *dst, uint64_t bytes)
 {
-    if (e && dst && e->h_ctr) std::memcpy(dst, e->h_ctr, (size_t)std::min<uint64_t>(bytes, sizeof(yk::Counters)));
+    if (e && dst && e->h_ctr()) std::memcpy(dst, e->h_ctr(), (size_t)std::min<uint64_t>(bytes, sizeof(yk::Counters)));
     return sizeof(yk::Counters);
 }
 
@@ -1338,6 +1348,13 @@ int yacrd_debug_last_input_csr(yacrd_engine *e, uint64_t *n_reads, uint64_t *n_i
     if (R) HIP_TRY(hipMemcpyAsync(lengths, e->in_len.p, (size_t)R * sizeof(u32), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return YACRD_OK;
+}
+
+/* include/yacrd_engine_debug.h: what DevBuf / PinBuf hold, process-wide (tests) */
+void yacrd_debug_live_bytes(uint64_t out[2])
+{
+    out[0] = yke::live_bytes()[0].load();
+    out[1] = yke::live_bytes()[1].load();
 }
 
 const char *yacrd_last_error(void) { return yke::err_slot().c_str(); }
@@ -1375,28 +1392,21 @@ int yacrd_engine_create(const yacrd_engine_cfg *cfg, yacrd_engine **out)
             e->screen_fused_wgs_per_cu = std::min(per_cu, 4);
         (void)hipGetLastError();
     }
-    hipError_t err = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
     // (e->side is made by the first batch that needs it: a stream is a hardware queue's worth of scheduling state, and engines
     //  that pipeline short batches — three per device in bench.py — should not double their number for nothing)
-    if (err == hipSuccess) err = hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming);
-    if (err == hipSuccess) err = hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming);
-    for (int i = 0; i < EV_COUNT && err == hipSuccess; i++) err = hipEventCreate(&e->ev[i]);
-    for (int i = 0; i < 24 && err == hipSuccess; i++) err = hipEventCreate(&e->ev_cls[i]);
-    if (err == hipSuccess) err = hipEventCreateWithFlags(&e->ev_done, hipEventBlockingSync | hipEventDisableTiming);
-    if (err == hipSuccess) err = hipEventCreate(&e->ev_h2d0);
-    if (err == hipSuccess) err = hipEventCreate(&e->ev_h2d1);
-    if (err == hipSuccess) err = hipEventCreate(&e->ev_d2h0);
-    if (err == hipSuccess) err = hipEventCreate(&e->ev_d2h1);
-    if (err == hipSuccess) err = hipHostMalloc((void **)&e->h_ctr, sizeof(yk::Counters));
-    if (err != hipSuccess) {
-        yacrd_engine_destroy(e);
-        return fail(YACRD_ENODEV, std::string("engine setup: ") + hipGetErrorString(err));
+    const bool made = e->streams.add(1) && e->ev.add(EV_COUNT) && e->ev_cls.add(24) &&
+                      e->ev_sync.add(1, hipEventBlockingSync | hipEventDisableTiming) && e->ev_sync.add(2, hipEventDisableTiming);
+    if (!made || e->h_ctr_mem.reserve(sizeof(yk::Counters)) != hipSuccess) {
+        yacrd_engine_destroy(e); // (safe on a half-made engine: the owners hold what was made)
+        return fail(YACRD_ENODEV, std::string("engine setup: ") + hipGetErrorString(why_not_added()));
     }
+    e->stream = e->streams[0];
     *out = e;
     return YACRD_OK;
 }
 
-// the text paths' buffers go back to the device (their objects stay); the batch path's and the pinned arena stay
+// the text paths' scratch goes back to the device (yke::scratch_of makes it anew on next use); the batch path's buffers, the
+// pinned arena and a kGzip slot somebody holds stay
 int yacrd_engine_trim(yacrd_engine *e)
 {
     if (!e) return fail(YACRD_EINVAL, "engine is null");
@@ -1405,7 +1415,7 @@ int yacrd_engine_trim(yacrd_engine *e)
     e->mirror.valid = false;
     e->resident.valid = e->input.valid = false;
     for (int k = 0; k < yacrd_engine::kSlots; k++)
-        if (e->scratch[k].p && !(k == yacrd_engine::kGzip && e->gzip_busy)) e->scratch[k].release(e->scratch[k].p);
+        if (!(k == yacrd_engine::kGzip && e->gzip_busy)) e->drop_scratch(k);
     return YACRD_OK;
 }
 
@@ -1413,34 +1423,21 @@ void yacrd_engine_destroy(yacrd_engine *e)
 {
     if (!e) return;
     DeviceGuard guard(e->device);
-    e->pending.active = false;
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    DevBuf *bufs[] = {&e->in_off, &e->in_iv, &e->in_len, &e->lists, &e->ctrl2[0], &e->ctrl2[1], &e->stage,
-                      &e->counts, &e->closed, &e->gen_sizes, &e->gen_scratch_off,
-                      &e->gen_scratch, &e->big_tab, &e->big_keys, &e->big_redo, &e->bt_tab, &e->bt_hist, &e->bt_cur, &e->bt_keys, &e->bs_seg, &e->bs_chunk, &e->bs_hist,
-                      &e->bad_offsets, &e->bad_regions, &e->read_type, &e->dlist};
-    for (DevBuf *b : bufs) b->release();
-    if (e->h_ctr) (void)hipHostFree(e->h_ctr);
-    e->h_out.release();
-    e->paf_arena.release();
-    for (auto &s : e->scratch)
-        if (s.p) s.destroy(s.p);
-    for (int b = 0; b < yacrd_engine::kBounce; b++) {
-        if (e->bounce[b]) (void)hipHostFree(e->bounce[b]);
-        if (e->bounce_ev[b]) (void)hipEventDestroy(e->bounce_ev[b]);
-    }
-    for (int i = 0; i < EV_COUNT; i++)
-        if (e->ev[i]) (void)hipEventDestroy(e->ev[i]);
-    for (int i = 0; i < 24; i++)
-        if (e->ev_cls[i]) (void)hipEventDestroy(e->ev_cls[i]);
-    hipEvent_t extra[] = {e->ev_h2d0, e->ev_h2d1, e->ev_d2h0, e->ev_d2h1, e->ev_done};
-    for (hipEvent_t x : extra)
-        if (x) (void)hipEventDestroy(x);
-    if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-    if (e->ev_join) (void)hipEventDestroy(e->ev_join);
-    if (e->side) (void)hipStreamDestroy(e->side);
-    if (e->stream) (void)hipStreamDestroy(e->stream);
-    delete e;
+    if (e->side) (void)hipStreamSynchronize(e->side);
+    for (int k = 0; k < yacrd_engine::kSlots; k++) e->drop_scratch(k);
+    delete e; // buffers, then events, then streams: the member order of yacrd_engine
+}
+
+// what a caller of the device forms gets: the last result where it lies in HBM
+static void fill_device_result(const yacrd_engine *e, yacrd_device_result *out)
+{
+    if (!out) return;
+    out->n_reads = e->last_reads;
+    out->n_regions = e->last_regions;
+    out->d_bad_offsets = e->bad_offsets.p;
+    out->d_bad_regions = e->bad_regions.p;
+    out->d_read_type = e->read_type.p;
 }
 
 int yacrd_engine_run_device(yacrd_engine *e, const void *d_offsets, const void *d_intervals,
@@ -1456,13 +1453,7 @@ int yacrd_engine_run_device(yacrd_engine *e, const void *d_offsets, const void *
     int rc = run_on_device(e, (const u64 *)d_offsets, (const uint2 *)d_intervals,
                            (const u32 *)d_lengths, n_reads, n_intervals, coverage, not_coverage);
     if (rc) return rc;
-    if (out) {
-        out->n_reads = e->last_reads;
-        out->n_regions = e->last_regions;
-        out->d_bad_offsets = e->bad_offsets.p;
-        out->d_bad_regions = e->bad_regions.p;
-        out->d_read_type = e->read_type.p;
-    }
+    fill_device_result(e, out);
     return YACRD_OK;
 }
 
@@ -1487,13 +1478,7 @@ int yacrd_engine_wait(yacrd_engine *e, yacrd_device_result *out)
     int rc = finish_pending(e);
     if (rc) return rc;
     if (!e->has_result) return fail(YACRD_EINVAL, "nothing was submitted");
-    if (out) {
-        out->n_reads = e->last_reads;
-        out->n_regions = e->last_regions;
-        out->d_bad_offsets = e->bad_offsets.p;
-        out->d_bad_regions = e->bad_regions.p;
-        out->d_read_type = e->read_type.p;
-    }
+    fill_device_result(e, out);
     return YACRD_OK;
 }
 
@@ -1553,7 +1538,7 @@ static int stage_host_inputs(yacrd_engine *e, const uint64_t *offsets, const uin
     HIP_TRY(e->in_off.reserve((size_t)(n_reads + 1) * sizeof(uint64_t)));
     HIP_TRY(e->in_iv.reserve((size_t)(n_iv + 1) * sizeof(uint2)));
     HIP_TRY(e->in_len.reserve((size_t)(n_reads + 1) * sizeof(uint32_t)));
-    HIP_TRY(hipEventRecord(e->ev_h2d0, e->stream));
+    HIP_TRY(hipEventRecord(e->ev[EV_H2D0], e->stream));
     int rc = YACRD_OK;
     if (n_reads) {
         rc = h2d(e, e->in_off.p, offsets, (size_t)(n_reads + 1) * sizeof(uint64_t));
@@ -1561,8 +1546,21 @@ static int stage_host_inputs(yacrd_engine *e, const uint64_t *offsets, const uin
     }
     if (!rc && n_iv) rc = h2d(e, e->in_iv.p, intervals, (size_t)n_iv * sizeof(uint2));
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(e->ev_h2d1, e->stream));
+    HIP_TRY(hipEventRecord(e->ev[EV_H2D1], e->stream));
     *n_iv_out = n_iv;
+    return YACRD_OK;
+}
+
+// the end of a batch that came from host buffers (run, collect): the h2d time, the result, the d2h time; the input CSR that
+// stage_host_inputs left in in_off / in_iv / in_len (e->input.n_reads / n_iv: set by the caller) counts from here on
+static int bring_home(yacrd_engine *e, yacrd_result *out)
+{
+    e->timing.h2d_ms = ev_ms(e->ev[EV_H2D0], e->ev[EV_H2D1]);
+    e->timing_sum.h2d_ms += e->timing.h2d_ms;
+    const int rc = fetch_result(e, out);
+    if (rc) return rc;
+    e->timing_sum.d2h_ms += e->timing.d2h_ms;
+    e->input.valid = true;
     return YACRD_OK;
 }
 
@@ -1585,12 +1583,8 @@ int yacrd_engine_run(yacrd_engine *e, const uint64_t *offsets, const uint32_t *i
     rc = run_on_device(e, e->in_off.as<u64>(), e->in_iv.as<uint2>(), e->in_len.as<u32>(), n_reads,
                        n_iv, coverage, not_coverage);
     if (rc) return rc;
-    e->timing.h2d_ms = ev_ms(e->ev_h2d0, e->ev_h2d1);
-    e->timing_sum.h2d_ms += e->timing.h2d_ms;
-    rc = fetch_result(e, out);
-    if (!rc) e->timing_sum.d2h_ms += e->timing.d2h_ms;
-    if (!rc) e->input.n_reads = n_reads, e->input.n_iv = n_iv, e->input.valid = true;
-    return rc;
+    e->input.n_reads = n_reads, e->input.n_iv = n_iv;
+    return bring_home(e, out);
 }
 
 int yacrd_engine_submit(yacrd_engine *e, const uint64_t *offsets, const uint32_t *intervals,
@@ -1622,13 +1616,7 @@ int yacrd_engine_collect(yacrd_engine *e, yacrd_result *out)
     e->host_pending = false;
     DeviceGuard guard(e->device);
     int rc = finish_pending(e);
-    if (rc) return rc;
-    e->timing.h2d_ms = ev_ms(e->ev_h2d0, e->ev_h2d1);
-    e->timing_sum.h2d_ms += e->timing.h2d_ms;
-    rc = fetch_result(e, out);
-    if (!rc) e->timing_sum.d2h_ms += e->timing.d2h_ms;
-    if (!rc) e->input.valid = true; // (the batch yacrd_engine_submit staged in in_off / in_iv / in_len)
-    return rc;
+    return rc ? rc : bring_home(e, out);
 }
 
 void *yacrd_pinned_alloc(size_t bytes)
@@ -1803,35 +1791,26 @@ int yacrd_engine_classify(yacrd_engine *e, const uint64_t *bad_offsets, const ui
     const uint64_t G = bad_offsets[n_reads];
     if (G && !bad_regions) return fail(YACRD_EINVAL, "null regions");
     DeviceGuard guard(e->device);
-    DevBuf d_off, d_reg, d_len, d_type;
-    int rc = YACRD_OK;
-    auto body = [&]() -> int {
-        HIP_TRY(d_off.reserve((size_t)(n_reads + 1) * sizeof(u64)));
-        HIP_TRY(d_reg.reserve((size_t)(G + 1) * sizeof(uint2)));
-        HIP_TRY(d_len.reserve((size_t)n_reads * sizeof(u32)));
-        HIP_TRY(d_type.reserve((size_t)n_reads));
-        HIP_TRY(hipMemcpyAsync(d_off.p, bad_offsets, (size_t)(n_reads + 1) * sizeof(u64),
+    DevBuf d_off, d_reg, d_len, d_type; // (this call's own: freed on every way out)
+    HIP_TRY(d_off.reserve((size_t)(n_reads + 1) * sizeof(u64)));
+    HIP_TRY(d_reg.reserve((size_t)(G + 1) * sizeof(uint2)));
+    HIP_TRY(d_len.reserve((size_t)n_reads * sizeof(u32)));
+    HIP_TRY(d_type.reserve((size_t)n_reads));
+    HIP_TRY(hipMemcpyAsync(d_off.p, bad_offsets, (size_t)(n_reads + 1) * sizeof(u64),
+                           hipMemcpyHostToDevice, e->stream));
+    if (G)
+        HIP_TRY(hipMemcpyAsync(d_reg.p, bad_regions, (size_t)G * sizeof(uint2),
                                hipMemcpyHostToDevice, e->stream));
-        if (G)
-            HIP_TRY(hipMemcpyAsync(d_reg.p, bad_regions, (size_t)G * sizeof(uint2),
-                                   hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(d_len.p, lengths, (size_t)n_reads * sizeof(u32),
-                               hipMemcpyHostToDevice, e->stream));
-        hipLaunchKernelGGL(yk::classify_csr_kernel, dim3((u32)((n_reads + 255) / 256)), dim3(256), 0,
-                           e->stream, d_off.as<u64>(), d_reg.as<uint2>(), d_len.as<u32>(),
-                           (u32)n_reads, not_coverage, d_type.as<uint8_t>());
-        HIP_TRY(hipMemcpyAsync(read_type, d_type.p, (size_t)n_reads, hipMemcpyDeviceToHost,
-                               e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        HIP_TRY(hipGetLastError());
-        return YACRD_OK;
-    };
-    rc = body();
-    d_off.release();
-    d_reg.release();
-    d_len.release();
-    d_type.release();
-    return rc;
+    HIP_TRY(hipMemcpyAsync(d_len.p, lengths, (size_t)n_reads * sizeof(u32),
+                           hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(yk::classify_csr_kernel, dim3((u32)((n_reads + 255) / 256)), dim3(256), 0,
+                       e->stream, d_off.as<u64>(), d_reg.as<uint2>(), d_len.as<u32>(),
+                       (u32)n_reads, not_coverage, d_type.as<uint8_t>());
+    HIP_TRY(hipMemcpyAsync(read_type, d_type.p, (size_t)n_reads, hipMemcpyDeviceToHost,
+                           e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipGetLastError());
+    return YACRD_OK;
 }
 
 } // extern "C"

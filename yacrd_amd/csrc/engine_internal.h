@@ -1,13 +1,18 @@
 // engine_internal.h — host-side internals shared by the translation units of libyacrd_hip.so: engine.hip (batch runs, the
 // engine's life), stream.hip (streaming ingest + CSR build on the GPU) and the text paths gpu_paf.hip, gpu_edit.hip,
-// gpu_deflate.hip, gpu_report.hip, gpu_report_write.hip.  The error slot, device and pinned buffers (DevBuf, PinBuf), the clocks, the
-// owners of a call's events and streams, the engine itself with its registry of the text paths' scratch, the run context.
+// gpu_deflate.hip, gpu_report.hip, gpu_report_write.hip.  The error slot; the OWNERS of every HIP resource the library takes:
+// DevBuf (device memory), PinBuf (pinned memory), Events, Streams.  Each frees what it holds when it goes, none is copied, and
+// no translation unit calls the runtime's allocate / create / free / destroy functions itself (yacrd_pinned_alloc / _free, whose
+// memory is the caller's, excepted); the two buffer types count the bytes they hold (live_bytes).  Then the clocks, the engine
+// itself, whose members are such owners in the order their destruction needs, with its registry of the text paths' scratch, and
+// the run context.
 #pragma once
 #include "../../include/yacrd_engine_debug.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <atomic>
 #include <chrono>
 #include <new>
 #include <string>
@@ -34,27 +39,48 @@ inline int fail(int code, const std::string &msg)
                              std::string(#expr) + ": " + hipGetErrorString(_e));              \
     } while (0)
 
-struct DevBuf {
+// Bytes of device / pinned memory DevBuf / PinBuf hold right now, process-wide (yacrd_debug_live_bytes: tests).  Touched only
+// where an allocation or a free happens.
+inline std::atomic<uint64_t> *live_bytes() // [0] device, [1] pinned
+{
+    static std::atomic<uint64_t> held[2];
+    return held;
+}
+
+// What DevBuf and PinBuf share: a block of `cap` bytes at `p` that goes when its holder does.  Moves, never copies.
+template <class Mem>
+struct OwnedBuf {
     void *p = nullptr;
     size_t cap = 0;
-    hipError_t reserve(size_t bytes)
+    OwnedBuf() = default;
+    OwnedBuf(const OwnedBuf &) = delete;
+    OwnedBuf &operator=(const OwnedBuf &) = delete;
+    OwnedBuf(OwnedBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    OwnedBuf &operator=(OwnedBuf &&o) noexcept
+    {
+        if (this != &o) {
+            release();
+            p = o.p, cap = o.cap;
+            o.p = nullptr, o.cap = 0;
+        }
+        return *this;
+    }
+    ~OwnedBuf() { release(); }
+    // exactly `bytes` (nothing held after a failure)
+    hipError_t reserve_exact(size_t bytes)
     {
         if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) {
-            e = hipMalloc(&p, bytes);
-            want = bytes;
-        }
-        if (e == hipSuccess) cap = want;
+        release();
+        const hipError_t e = Mem::alloc(&p, bytes);
+        if (e == hipSuccess) live_bytes()[Mem::kCounter] += (cap = bytes);
+        else p = nullptr;
         return e;
     }
     void release()
     {
-        if (p) (void)hipFree(p);
+        if (!p) return;
+        (void)Mem::free(p);
+        live_bytes()[Mem::kCounter] -= cap;
         p = nullptr;
         cap = 0;
     }
@@ -64,31 +90,29 @@ struct DevBuf {
         return reinterpret_cast<T *>(p);
     }
 };
+struct DevMem {
+    static constexpr int kCounter = 0;
+    static hipError_t alloc(void **p, size_t n) { return hipMalloc(p, n); }
+    static hipError_t free(void *p) { return hipFree(p); }
+};
+struct PinMem {
+    static constexpr int kCounter = 1;
+    static hipError_t alloc(void **p, size_t n) { return hipHostMalloc(p, n); }
+    static hipError_t free(void *p) { return hipHostFree(p); }
+};
 
-// pinned host memory, grow-only: exactly the bytes asked for (pinning costs by the byte), nothing after a failed reserve
-struct PinBuf {
-    void *p = nullptr;
-    size_t cap = 0;
+// device memory, grow-only: an eighth of slack so a slightly larger batch fits, the exact size where that does not
+struct DevBuf : OwnedBuf<DevMem> {
     hipError_t reserve(size_t bytes)
     {
         if (bytes <= cap) return hipSuccess;
-        release();
-        const hipError_t e = hipHostMalloc(&p, bytes);
-        if (e == hipSuccess) cap = bytes;
-        else p = nullptr;
-        return e;
+        return reserve_exact(bytes + bytes / 8 + 256) == hipSuccess ? hipSuccess : reserve_exact(bytes);
     }
-    void release()
-    {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <class T>
-    T *as() const
-    {
-        return reinterpret_cast<T *>(p);
-    }
+};
+
+// pinned host memory, grow-only: exactly the bytes asked for (pinning costs by the byte), nothing after a failed reserve
+struct PinBuf : OwnedBuf<PinMem> {
+    hipError_t reserve(size_t bytes) { return reserve_exact(bytes); }
 };
 
 // the events / streams of one call: what was created goes when the holder does
@@ -136,7 +160,15 @@ struct Streams {
     ~Streams() { clear(); }
 };
 
-enum { EV_START = 0, EV_PLAN, EV_S0, EV_SMALL, EV_MED, EV_GEN, EV_COMPACT, EV_X0, EV_X1, EV_COUNT };
+// the error behind an add() or a reserve() that just failed on this thread (never hipSuccess)
+inline hipError_t why_not_added()
+{
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : hipErrorUnknown;
+}
+
+enum { EV_START = 0, EV_PLAN, EV_S0, EV_SMALL, EV_MED, EV_GEN, EV_COMPACT, EV_X0, EV_X1, EV_H2D0, EV_H2D1, EV_D2H0, EV_D2H1, EV_COUNT }; // yacrd_engine::ev
+enum { EVS_DONE = 0, EVS_FORK, EVS_JOIN, EVS_COUNT };                                                                                // yacrd_engine::ev_sync
 
 struct DeviceGuard {
     int prev = -1;
@@ -231,13 +263,14 @@ struct yacrd_engine {
     Pending pending;
     int device = 0;
     uint32_t flags = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t side = nullptr;                       // the device-wide screen's launches, beside the workgroup classes' (run_on_device)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // stream -> side (behind the plan), side -> stream (in front of the follow-on step)
-    hipEvent_t ev[yke::EV_COUNT] = {};
-    hipEvent_t ev_h2d0 = nullptr, ev_h2d1 = nullptr, ev_d2h0 = nullptr, ev_d2h1 = nullptr;
-    hipEvent_t ev_cls[24] = {}; // brackets around class kernels
-    hipEvent_t ev_done = nullptr; // hipEventBlockingSync: the final wait of YACRD_F_BLOCKING_WAIT
+    // Order matters to ~yacrd_engine: members go last-declared first, so every buffer below is freed before the events, and
+    // the events before the streams the buffers were used on (yacrd_engine_destroy has waited for both streams by then).
+    yke::Streams streams;           // owns the two below
+    hipStream_t stream = nullptr;   // streams[0]
+    hipStream_t side = nullptr;     // streams[1], made by the first batch that needs it: the device-wide screen's launches, beside the workgroup classes' (run_on_device)
+    yke::Events ev;      // EV_*: the phases of a run, h2d and d2h (default flags: timed)
+    yke::Events ev_cls;  // 24, brackets around class kernels (timed)
+    yke::Events ev_sync; // EVS_DONE: hipEventBlockingSync, the final wait of YACRD_F_BLOCKING_WAIT; EVS_FORK: stream -> side (behind the plan); EVS_JOIN: side -> stream (in front of the follow-on step); none timed
     int num_cu = 256;
     bool fused_off = false; // this run: the workgroup classes down the three-launch chain (a fused launch gave up: Counters::fused_gave_up)
     int num_xcc = 0; // XCDs of this device / partition (one_batch_kernel's read-to-XCD map assumes 8)
@@ -256,7 +289,8 @@ struct yacrd_engine {
     int ctrl_cur = 0;
     // results
     yke::DevBuf bad_offsets, bad_regions, read_type;
-    yk::Counters *h_ctr = nullptr; // pinned
+    yke::PinBuf h_ctr_mem;
+    yk::Counters *h_ctr() const { return h_ctr_mem.as<yk::Counters>(); }
 
     uint64_t last_reads = 0, last_regions = 0;
     size_t last_list_stride = 0; // reads per class list of the current run (lists = [class][read])
@@ -280,8 +314,8 @@ struct yacrd_engine {
     // buffer says when its DMA is done and it may be refilled
     static constexpr int kBounce = 12;
     static constexpr size_t kBounceBytes = (size_t)4 << 20;
-    void *bounce[kBounce] = {};
-    hipEvent_t bounce_ev[kBounce] = {};
+    yke::Events bounce_ev; // one per buffer that exists: buffers are made in order, each with its event or not at all
+    yke::PinBuf bounce[kBounce];
     bool bounce_busy[kBounce] = {};
     yke::PinBuf h_out; // pinned staging for the results on their way home (fetch_result)
     // a batch submitted from host buffers (yacrd_engine_submit): collect() fetches the result
@@ -317,14 +351,19 @@ struct yacrd_engine {
         uint64_t n_reads = 0, n_iv = 0;
         bool valid = false;
     } input;
-    // what the text paths keep between calls (their own types: device and pinned buffers, grow-only), made on first use by
-    // yke::scratch_of; yacrd_engine_trim releases their buffers, yacrd_engine_destroy deletes them
+    // what the text paths keep between calls (their own types, whose members own their device and pinned buffers, events and
+    // streams; nothing in them outlives a call except capacity), made on first use by yke::scratch_of; yacrd_engine_trim and
+    // yacrd_engine_destroy delete them (drop_scratch), the next use after a trim makes a fresh one
     enum Slot { kPaf = 0, kEdit, kGzip, kReport, kReportWrite, kSlots };
     struct {
         void *p = nullptr;
         void (*destroy)(void *) = nullptr;
-        void (*release)(void *) = nullptr;
     } scratch[kSlots];
+    void drop_scratch(int k)
+    {
+        if (scratch[k].p) scratch[k].destroy(scratch[k].p);
+        scratch[k].p = nullptr;
+    }
     bool gzip_busy = false; // a yacrd_gzip_writer or an edit to gzip holds the kGzip slot: trim leaves it alone
 };
 
@@ -335,10 +374,7 @@ template <class T>
 T *scratch_of(yacrd_engine *e)
 {
     auto &s = e->scratch[T::kScratchSlot];
-    if (!s.p && (s.p = new (std::nothrow) T())) {
-        s.destroy = [](void *p) { delete static_cast<T *>(p); };
-        s.release = [](void *p) { static_cast<T *>(p)->release(); };
-    }
+    if (!s.p && (s.p = new (std::nothrow) T())) s.destroy = [](void *p) { delete static_cast<T *>(p); };
     return static_cast<T *>(s.p);
 }
 // the whole launch sequence over a CSR resident in HBM (engine.hip)

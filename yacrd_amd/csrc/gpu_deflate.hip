@@ -82,12 +82,6 @@ struct GzScratch { // stays with the engine (grow-only); goes with yacrd_engine_
     static constexpr yacrd_engine::Slot kScratchSlot = yacrd_engine::kGzip;
     DevBuf text, slots, out, out2, sizes, off, part, ctl; // (out2: the overlap editor's second batch of members, gzip_device_open)
     PinBuf pin; // n_buffers input segments, one output segment, the control words
-    void release()
-    {
-        for (DevBuf *b : {&text, &slots, &out, &out2, &sizes, &off, &part, &ctl}) b->release();
-        pin.release();
-    }
-    ~GzScratch() { release(); }
 };
 inline u64 out_bound(u64 blocks) { return blocks * (u64)ydf::kSlot + ydf::kEofBytes; }
 
@@ -163,7 +157,7 @@ struct yacrd_gzip_writer {
     u32 n_buf = 2;
     char *pin_in = nullptr, *pin_out = nullptr;
     volatile u64 *h_ctl = nullptr; // [0] bytes of the members of the segment in flight, [1] stored members so far
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; // h2d begin, kernels begin, kernels end
+    Events ev; // h2d begin, kernels begin, kernels end (they go with the writer, behind drop()'s wait)
     u32 cur = 0;      // the buffer being filled
     u64 fill = 0;     // bytes in it
     bool in_flight = false, flight_last = false;
@@ -231,8 +225,6 @@ struct yacrd_gzip_writer {
         if (e) {
             DeviceGuard guard(e->device);
             (void)hipStreamSynchronize(e->stream);
-            for (hipEvent_t x : ev)
-                if (x) (void)hipEventDestroy(x);
             (void)hipGetLastError();
             e->gzip_busy = false;
         }
@@ -269,7 +261,7 @@ int writer_setup(yacrd_engine *e, u64 segment_bytes, u32 n_buffers, yacrd_gzip_w
         return fail(YACRD_ENOMEM, "device deflate: no pinned memory");
     }
     HIP_TRY(hipMemsetAsync(S->ctl.p, 0, 64, e->stream));
-    for (hipEvent_t &x : w->ev) HIP_TRY(hipEventCreate(&x));
+    if (!w->ev.add(3)) HIP_TRY(why_not_added());
     w->S = S, w->seg_bytes = seg, w->n_buf = n_buffers;
     w->pin_in = S->pin.as<char>();
     w->pin_out = w->pin_in + (size_t)n_buffers * seg;

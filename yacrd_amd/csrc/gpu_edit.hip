@@ -370,12 +370,6 @@ struct EditScratch { // the editor's buffers; they stay with the engine (grow-on
     static constexpr yacrd_engine::Slot kScratchSlot = yacrd_engine::kEdit;
     DevBuf text, out, names, name_off, types, slots, kbits, tile, tile_kept, tile_cin, tile_off, ctl, part;
     PinBuf pin; // two output pieces + the per-segment control words
-    void release()
-    {
-        for (DevBuf *b : {&text, &out, &names, &name_off, &types, &slots, &kbits, &tile, &tile_kept, &tile_cin, &tile_off, &ctl, &part}) b->release();
-        pin.release();
-    }
-    ~EditScratch() { release(); }
 };
 
 using yseg::Sink; // where the kept bytes go: a file descriptor or memory, sized or growing (host/segment_pump.h)

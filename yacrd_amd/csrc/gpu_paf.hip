@@ -626,7 +626,6 @@ struct IdTable {
         HIP_TRY(hipMemsetAsync(slot_cnt.p, 0, (size_t)cap * sizeof(u32), stream));
         return YACRD_OK;
     }
-    void release() { for (DevBuf *b : {&claim, &first_pos, &slot_cnt}) b->release(); }
 };
 
 // one numbering of reads by first appearance: a table's occupied slots (keys = first positions), the same sorted, and per
@@ -642,10 +641,9 @@ struct ReadList {
         HIP_TRY(cnt.reserve((size_t)(n_reads + 4) * sizeof(u32)));
         return YACRD_OK;
     }
-    void release() { for (DevBuf *b : {&keys, &keys2, &slots, &slots2, &name_len, &name_at, &name_off, &names, &cnt}) b->release(); }
 };
 
-struct Scratch { // the call's device buffers; they stay with the engine (grow-only), go with yacrd_engine_trim / destroy
+struct Scratch { // the call's device buffers; they stay with the engine (grow-only), the whole object goes with yacrd_engine_trim / destroy
     static constexpr yacrd_engine::Slot kScratchSlot = yacrd_engine::kPaf;
     Ctl ctl;
     IdTable ids;    // the range's
@@ -655,14 +653,6 @@ struct Scratch { // the call's device buffers; they stay with the engine (grow-o
     IdTable file_ids;
     ReadList file; // lengths in g_len
     DevBuf m_fp, m_len, m_cnt, m_noff, m_names, m_slot, m_read, g_slot_read, g_len;
-    void release()
-    {
-        ids.release(), file_ids.release(), range.release(), file.release();
-        for (DevBuf *b : {&ctl.buf, &text, &recs, &tmp, &map, &part, &err, &gather, &gmap, &m_fp, &m_len, &m_cnt, &m_noff, &m_names, &m_slot,
-                          &m_read, &g_slot_read, &g_len})
-            b->release();
-    }
-    ~Scratch() { release(); }
 
     // What every numbering shares (a range's in parse_range, the file's in GroupRun::merge); the caller's checks come behind
     // collect, its number kernel behind sort_collected.
@@ -968,20 +958,15 @@ PeerRoute route_between(int to_dev, int from_dev)
 // the staged route: two pinned buffers per destination engine, a piece flies host -> device while the next one is fetched
 struct StageBuf {
     PinBuf pin[2];
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    Events ev; // one per buffer
     bool busy[2] = {false, false};
-    hipStream_t from_stream = nullptr;
+    Streams from; // one, on the source's device: made and destroyed with that device current
     int from_dev = -1;
     ~StageBuf()
     {
-        for (int i = 0; i < 2; i++) {
-            pin[i].release();
-            if (ev[i]) (void)hipEventDestroy(ev[i]);
-        }
-        if (from_stream) {
-            DeviceGuard guard(from_dev);
-            (void)hipStreamDestroy(from_stream);
-        }
+        if (from.v.empty()) return;
+        DeviceGuard guard(from_dev);
+        from.clear();
     }
 };
 constexpr size_t kStagePiece = (size_t)16 << 20;
@@ -989,15 +974,14 @@ hipError_t copy_staged(yacrd_engine *to, void *dst, yacrd_engine *from, const vo
 {
     StageBuf sb; // (per call: the route is a fallback, its setup cost is not what matters on it)
     for (int i = 0; i < 2; i++) {
-        hipError_t er = sb.pin[i].reserve(std::min(bytes, kStagePiece));
-        if (er == hipSuccess) er = hipEventCreateWithFlags(&sb.ev[i], hipEventDisableTiming);
+        const hipError_t er = sb.pin[i].reserve(std::min(bytes, kStagePiece));
         if (er != hipSuccess) return er;
     }
+    if (!sb.ev.add(2, hipEventDisableTiming)) return why_not_added();
     sb.from_dev = from->device;
     {
         DeviceGuard guard(from->device);
-        const hipError_t er = hipStreamCreateWithFlags(&sb.from_stream, hipStreamNonBlocking);
-        if (er != hipSuccess) return er;
+        if (!sb.from.add(1)) return why_not_added();
     }
     int turn = 0;
     for (size_t at = 0; at < bytes; at += kStagePiece, turn ^= 1) {
@@ -1008,8 +992,8 @@ hipError_t copy_staged(yacrd_engine *to, void *dst, yacrd_engine *from, const vo
         }
         {
             DeviceGuard guard(from->device); // device -> host runs on the SOURCE device's stream
-            hipError_t er = hipMemcpyAsync(sb.pin[turn].p, (const char *)src + at, m, hipMemcpyDeviceToHost, sb.from_stream);
-            if (er == hipSuccess) er = hipStreamSynchronize(sb.from_stream);
+            hipError_t er = hipMemcpyAsync(sb.pin[turn].p, (const char *)src + at, m, hipMemcpyDeviceToHost, sb.from[0]);
+            if (er == hipSuccess) er = hipStreamSynchronize(sb.from[0]);
             if (er != hipSuccess) return er;
         }
         hipError_t er = hipMemcpyAsync((char *)dst + at, sb.pin[turn].p, m, hipMemcpyHostToDevice, to->stream);
@@ -1502,24 +1486,19 @@ int yacrd_debug_sort_pairs(yacrd_engine *e, uint64_t *keys, uint32_t *vals, uint
     if (n >= 0x7FFFFFFFull) return fail(YACRD_EINVAL, "too many pairs");
     DeviceGuard guard(e->device);
     DevBuf k0, k1, v0, v1, tmp, part;
-    auto body = [&]() -> int {
-        HIP_TRY(k0.reserve((size_t)n * sizeof(u64) + 64));
-        HIP_TRY(k1.reserve((size_t)n * sizeof(u64) + 64));
-        HIP_TRY(v0.reserve((size_t)n * sizeof(u32) + 64));
-        HIP_TRY(v1.reserve((size_t)n * sizeof(u32) + 64));
-        if (!n) return YACRD_OK;
-        HIP_TRY(hipMemcpyAsync(k0.p, keys, (size_t)n * sizeof(u64), hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(v0.p, vals, (size_t)n * sizeof(u32), hipMemcpyHostToDevice, e->stream));
-        if (const int rcs = sort_by_first_position(e, k0.as<u64>(), k1.as<u64>(), v0.as<u32>(), v1.as<u32>(), (u32)n, key_bound, tmp, part)) return rcs;
-        HIP_TRY(hipMemcpyAsync(keys, k1.p, (size_t)n * sizeof(u64), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipMemcpyAsync(vals, v1.p, (size_t)n * sizeof(u32), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        HIP_TRY(hipGetLastError());
-        return YACRD_OK;
-    };
-    const int rc = body();
-    for (DevBuf *b : {&k0, &k1, &v0, &v1, &tmp, &part}) b->release();
-    return rc;
+    HIP_TRY(k0.reserve((size_t)n * sizeof(u64) + 64));
+    HIP_TRY(k1.reserve((size_t)n * sizeof(u64) + 64));
+    HIP_TRY(v0.reserve((size_t)n * sizeof(u32) + 64));
+    HIP_TRY(v1.reserve((size_t)n * sizeof(u32) + 64));
+    if (!n) return YACRD_OK;
+    HIP_TRY(hipMemcpyAsync(k0.p, keys, (size_t)n * sizeof(u64), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(v0.p, vals, (size_t)n * sizeof(u32), hipMemcpyHostToDevice, e->stream));
+    if (const int rcs = sort_by_first_position(e, k0.as<u64>(), k1.as<u64>(), v0.as<u32>(), v1.as<u32>(), (u32)n, key_bound, tmp, part)) return rcs;
+    HIP_TRY(hipMemcpyAsync(keys, k1.p, (size_t)n * sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(vals, v1.p, (size_t)n * sizeof(u32), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipGetLastError());
+    return YACRD_OK;
 }
 
 } // extern "C"

@@ -321,16 +321,14 @@ struct ReportScratch { // the reader's buffers; they stay with the engine (grow-
     static constexpr yacrd_engine::Slot kScratchSlot = yacrd_engine::kReport;
     DevBuf text, tile_lines, tile_ord, lines, line_slot, line_idlen, claim, first, last, flag, number, reads, n_reg, name_len, name_off, names,
         ctl, part;
-    std::vector<DevBuf *> all()
+    double held() const // bytes of HBM the scratch holds now (read_report's "does it fit?")
     {
-        return {&text, &tile_lines, &tile_ord, &lines, &line_slot, &line_idlen, &claim, &first, &last, &flag, &number, &reads, &n_reg, &name_len,
-                &name_off, &names, &ctl, &part};
+        double sum = 0;
+        for (const DevBuf *b : {&text, &tile_lines, &tile_ord, &lines, &line_slot, &line_idlen, &claim, &first, &last, &flag, &number, &reads, &n_reg,
+                                &name_len, &name_off, &names, &ctl, &part})
+            sum += (double)b->cap;
+        return sum;
     }
-    void release()
-    {
-        for (DevBuf *b : all()) b->release();
-    }
-    ~ReportScratch() { release(); }
 };
 
 int read_report(yacrd_engine *e, const TextSource &src, u64 n, int n_threads, double not_coverage, yacrd_result *out, yacrd_reads *reads,
@@ -349,8 +347,7 @@ int read_report(yacrd_engine *e, const TextSource &src, u64 n, int n_threads, do
         // text at the worst), the arrays of the result.  Answered before anything is allocated.
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            double have = (double)free_b;
-            for (DevBuf *b : S.all()) have += (double)b->cap;
+            const double have = (double)free_b + S.held();
             if (5.0 * (double)n + (double)((size_t)256 << 20) > have)
                 return fail(YACRD_EFALLBACK, "the report is too large to be read in this device's free memory: the host reader streams it");
         }

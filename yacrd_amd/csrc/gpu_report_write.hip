@@ -199,22 +199,8 @@ struct ReportWriteScratch { // the writer's buffers; they stay with the engine (
     static constexpr yacrd_engine::Slot kScratchSlot = yacrd_engine::kReportWrite;
     DevBuf names, name_off, lengths, bad_off, regions, type, piece_len, owner, head_len, P, H, text, ctl, part;
     PinBuf pin; // two segments
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; // in front of the upload, behind it, behind the kernels
-    hipEvent_t dma[2] = {nullptr, nullptr};         // a pinned buffer has landed
-    std::vector<DevBuf *> all() { return {&names, &name_off, &lengths, &bad_off, &regions, &type, &piece_len, &owner, &head_len, &P, &H, &text, &ctl, &part}; }
-    void release()
-    {
-        for (DevBuf *b : all()) b->release();
-        pin.release();
-    }
-    ~ReportWriteScratch()
-    {
-        release();
-        for (hipEvent_t &x : ev)
-            if (x) (void)hipEventDestroy(x);
-        for (hipEvent_t &x : dma)
-            if (x) (void)hipEventDestroy(x);
-    }
+    Events ev;  // 3, made by the first call: in front of the upload, behind it, behind the kernels
+    Events dma; // 2, untimed: a pinned buffer has landed
 };
 
 using yseg::Sink; // where the text goes: a file descriptor or memory sized for it (host/segment_pump.h)
@@ -223,10 +209,7 @@ using yseg::Sink; // where the text goes: a file descriptor or memory sized for 
 int format_report(yacrd_engine *e, ReportWriteScratch &S, const yacrd_report_table *t, u64 *total, yacrd_report_write_stats *st)
 {
     *total = 0;
-    for (hipEvent_t &x : S.ev)
-        if (!x) HIP_TRY(hipEventCreate(&x));
-    for (hipEvent_t &x : S.dma)
-        if (!x) HIP_TRY(hipEventCreateWithFlags(&x, hipEventDisableTiming));
+    if (!S.ev.add(3 - S.ev.v.size()) || !S.dma.add(2 - S.dma.v.size(), hipEventDisableTiming)) HIP_TRY(why_not_added());
     yk::RwArgs a{};
     u64 R = 0, G = 0;
     HIP_TRY(hipEventRecord(S.ev[0], e->stream));

@@ -48,12 +48,14 @@ enum { BUF_FREE = 0, BUF_HELD = 1, BUF_FLYING = 2 };
 
 struct yacrd_stream {
     yacrd_engine *e = nullptr;
-    hipStream_t copy = nullptr;
+    // (declared in this order so that ~yacrd_stream frees the buffers first, then the events, then the stream)
+    yke::Streams copy; // one
+    yke::Events ev;    // around buffer b's copy: ev[2 b] in front, ev[2 b + 1] behind
+    yke::Events evb;   // around the CSR build
     uint64_t chunk_records = 0;
     uint32_t n_buffers = 0;
-    char *arena = nullptr; // one pinned allocation, n_buffers * chunk bytes
+    yke::PinBuf arena; // one pinned allocation, n_buffers * chunk bytes
     std::vector<int> state;
-    std::vector<hipEvent_t> ev0, ev1; // around each buffer's copy
     std::mutex mu;
     // device side: records land in slabs, back to back
     struct Slab {
@@ -65,7 +67,6 @@ struct yacrd_stream {
     uint64_t n_records = 0;
     double busy_ms = 0;
     yke::DevBuf cnt, part, map, err;
-    hipEvent_t evb0 = nullptr, evb1 = nullptr;
     yacrd_stream_stats stats{};
 };
 
@@ -75,7 +76,7 @@ namespace {
 void retire(yacrd_stream *s, uint32_t b)
 {
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->ev0[b], s->ev1[b]) == hipSuccess) s->busy_ms += ms;
+    if (hipEventElapsedTime(&ms, s->ev[2 * b], s->ev[2 * b + 1]) == hipSuccess) s->busy_ms += ms;
     else (void)hipGetLastError();
     s->state[b] = BUF_FREE;
 }
@@ -180,17 +181,9 @@ int yacrd_stream_open(yacrd_engine *e, uint64_t chunk_records, uint32_t n_buffer
     s->chunk_records = chunk_records;
     s->n_buffers = n_buffers;
     s->state.assign(n_buffers, BUF_FREE);
-    s->ev0.assign(n_buffers, nullptr);
-    s->ev1.assign(n_buffers, nullptr);
-    hipError_t err = hipStreamCreateWithFlags(&s->copy, hipStreamNonBlocking);
-    if (err == hipSuccess)
-        err = hipHostMalloc((void **)&s->arena, (size_t)n_buffers * chunk_records * sizeof(yacrd_ovl_rec));
-    for (uint32_t b = 0; b < n_buffers && err == hipSuccess; b++) {
-        err = hipEventCreate(&s->ev0[b]);
-        if (err == hipSuccess) err = hipEventCreate(&s->ev1[b]);
-    }
-    if (err == hipSuccess) err = hipEventCreate(&s->evb0);
-    if (err == hipSuccess) err = hipEventCreate(&s->evb1);
+    hipError_t err = hipSuccess;
+    if (!s->copy.add(1) || !s->ev.add((size_t)2 * n_buffers) || !s->evb.add(2)) err = why_not_added();
+    else err = s->arena.reserve((size_t)n_buffers * chunk_records * sizeof(yacrd_ovl_rec));
     if (err != hipSuccess) {
         yacrd_stream_close(s);
         return fail(err == hipErrorOutOfMemory ? YACRD_ENOMEM : YACRD_ENODEV,
@@ -222,7 +215,7 @@ int yacrd_stream_acquire(yacrd_stream *s, yacrd_ovl_rec **buf, uint64_t *capacit
                 if (s->state[b] == BUF_FREE) pick = (int)b;
             for (uint32_t b = 0; b < s->n_buffers && pick < 0; b++) {
                 if (s->state[b] != BUF_FLYING) continue;
-                const hipError_t q = hipEventQuery(s->ev1[b]);
+                const hipError_t q = hipEventQuery(s->ev[2 * b + 1]);
                 if (q == hipSuccess) {
                     retire(s, b);
                     pick = (int)b;
@@ -234,7 +227,7 @@ int yacrd_stream_acquire(yacrd_stream *s, yacrd_ovl_rec **buf, uint64_t *capacit
             }
             if (pick >= 0) {
                 s->state[pick] = BUF_HELD;
-                *buf = reinterpret_cast<yacrd_ovl_rec *>(s->arena) + (size_t)pick * s->chunk_records;
+                *buf = s->arena.as<yacrd_ovl_rec>() + (size_t)pick * s->chunk_records;
                 if (capacity) *capacity = s->chunk_records;
                 return YACRD_OK;
             }
@@ -247,7 +240,7 @@ int yacrd_stream_acquire(yacrd_stream *s, yacrd_ovl_rec **buf, uint64_t *capacit
 int yacrd_stream_commit(yacrd_stream *s, yacrd_ovl_rec *buf, uint64_t n)
 {
     if (!s || !buf) return fail(YACRD_EINVAL, "null argument");
-    const size_t at = (size_t)(buf - reinterpret_cast<yacrd_ovl_rec *>(s->arena));
+    const size_t at = (size_t)(buf - s->arena.as<yacrd_ovl_rec>());
     if (at % s->chunk_records != 0 || at / s->chunk_records >= s->n_buffers)
         return fail(YACRD_EINVAL, "not a buffer of this stream");
     const uint32_t b = (uint32_t)(at / s->chunk_records);
@@ -273,20 +266,19 @@ int yacrd_stream_commit(yacrd_stream *s, yacrd_ovl_rec *buf, uint64_t n)
         cap = std::max<uint64_t>(cap, n);
         s->slabs.emplace_back();
         yacrd_stream::Slab &fresh = s->slabs.back();
-        const hipError_t er = hipMalloc(&fresh.buf.p, (size_t)cap * sizeof(yacrd_ovl_rec));
+        const hipError_t er = fresh.buf.reserve_exact((size_t)cap * sizeof(yacrd_ovl_rec));
         if (er != hipSuccess) {
             s->slabs.pop_back();
             s->state[b] = BUF_FREE;
             return fail(YACRD_ENOMEM, std::string("stream slab: ") + hipGetErrorString(er));
         }
-        fresh.buf.cap = (size_t)cap * sizeof(yacrd_ovl_rec);
         fresh.cap = cap;
     }
     yacrd_stream::Slab &sl = s->slabs[s->cur_slab];
     char *dst = sl.buf.as<char>() + (size_t)sl.used * sizeof(yacrd_ovl_rec);
-    HIP_TRY(hipEventRecord(s->ev0[b], s->copy));
-    HIP_TRY(hipMemcpyAsync(dst, buf, (size_t)n * sizeof(yacrd_ovl_rec), hipMemcpyHostToDevice, s->copy));
-    HIP_TRY(hipEventRecord(s->ev1[b], s->copy));
+    HIP_TRY(hipEventRecord(s->ev[2 * b], s->copy[0]));
+    HIP_TRY(hipMemcpyAsync(dst, buf, (size_t)n * sizeof(yacrd_ovl_rec), hipMemcpyHostToDevice, s->copy[0]));
+    HIP_TRY(hipEventRecord(s->ev[2 * b + 1], s->copy[0]));
     sl.used += n;
     s->n_records += n;
     s->state[b] = BUF_FLYING;
@@ -309,7 +301,7 @@ int yacrd_stream_reset(yacrd_stream *s)
     std::lock_guard<std::mutex> g(s->mu);
     for (uint32_t b = 0; b < s->n_buffers; b++)
         if (s->state[b] == BUF_HELD) return fail(YACRD_EINVAL, "a buffer is still held by a parser");
-    HIP_TRY(hipStreamSynchronize(s->copy)); // copies in flight land in slabs that are about to be reused
+    HIP_TRY(hipStreamSynchronize(s->copy[0])); // copies in flight land in slabs that are about to be reused
     for (uint32_t b = 0; b < s->n_buffers; b++)
         if (s->state[b] == BUF_FLYING) retire(s, b);
     stream_reset_locked(s);
@@ -338,13 +330,13 @@ int yacrd_stream_finish(yacrd_stream *s, const uint32_t *handle_map, uint64_t n_
         yacrd_stream *s;
         ~ResetOnExit()
         {
-            (void)hipStreamSynchronize(s->copy); // (copies in flight land in slabs about to be reused)
+            (void)hipStreamSynchronize(s->copy[0]); // (copies in flight land in slabs about to be reused)
             for (uint32_t b = 0; b < s->n_buffers; b++)
                 if (s->state[b] == BUF_FLYING) retire(s, b);
             stream_reset_locked(s);
         }
     } reset_on_exit{s};
-    HIP_TRY(hipStreamSynchronize(s->copy)); // every record is in HBM
+    HIP_TRY(hipStreamSynchronize(s->copy[0])); // every record is in HBM
     for (uint32_t b = 0; b < s->n_buffers; b++)
         if (s->state[b] == BUF_FLYING) retire(s, b);
     const uint64_t n = s->n_records, n_iv = 2 * n;
@@ -360,7 +352,7 @@ int yacrd_stream_finish(yacrd_stream *s, const uint32_t *handle_map, uint64_t n_
         HIP_TRY(s->map.reserve((size_t)n_handles * sizeof(u32)));
         d_map = s->map.as<u32>();
     }
-    HIP_TRY(hipEventRecord(s->evb0, e->stream));
+    HIP_TRY(hipEventRecord(s->evb[0], e->stream));
     int rc = YACRD_OK;
     if (d_map) rc = h2d(e, s->map.p, handle_map, (size_t)n_handles * sizeof(u32));
     if (!rc && n_reads) rc = h2d(e, e->in_len.p, lengths, (size_t)n_reads * sizeof(u32));
@@ -369,9 +361,9 @@ int yacrd_stream_finish(yacrd_stream *s, const uint32_t *handle_map, uint64_t n_
     for (auto &sl : s->slabs)
         if (sl.used) rs.push_back(RecSlab{sl.buf.as<yk::OvlRec>(), sl.used});
     u64 n_iv_here = n_iv;
-    rc = csr_from_records(e, rs.data(), rs.size(), d_map, n_handles, n_reads, s->cnt, s->part, s->err, s->evb1, &n_iv_here);
+    rc = csr_from_records(e, rs.data(), rs.size(), d_map, n_handles, n_reads, s->cnt, s->part, s->err, s->evb[1], &n_iv_here);
     if (rc) return rc;
-    s->stats.build_ms = ev_ms(s->evb0, s->evb1);
+    s->stats.build_ms = ev_ms(s->evb[0], s->evb[1]);
     const double t0 = now_ms();
     rc = run_on_device(e, e->in_off.as<u64>(), e->in_iv.as<uint2>(), e->in_len.as<u32>(), n_reads, n_iv_here,
                        coverage, not_coverage);
@@ -693,20 +685,7 @@ void yacrd_stream_close(yacrd_stream *s)
 {
     if (!s) return;
     DeviceGuard guard(s->e->device);
-    if (s->copy) (void)hipStreamSynchronize(s->copy);
-    for (auto &sl : s->slabs) sl.buf.release();
-    s->cnt.release();
-    s->part.release();
-    s->map.release();
-    s->err.release();
-    if (s->arena) (void)hipHostFree(s->arena);
-    for (hipEvent_t x : s->ev0)
-        if (x) (void)hipEventDestroy(x);
-    for (hipEvent_t x : s->ev1)
-        if (x) (void)hipEventDestroy(x);
-    if (s->evb0) (void)hipEventDestroy(s->evb0);
-    if (s->evb1) (void)hipEventDestroy(s->evb1);
-    if (s->copy) (void)hipStreamDestroy(s->copy);
+    if (!s->copy.v.empty()) (void)hipStreamSynchronize(s->copy[0]);
     delete s;
 }
 

@@ -243,6 +243,15 @@ def peer_copy_counts():
     return [int(x) for x in out]
 
 
+def live_bytes():
+    """yacrd_debug_live_bytes (tests): bytes the library holds right now, process-wide: (device memory, pinned host memory)."""
+    lib = load_library()
+    out = (ctypes.c_uint64 * 2)()
+    lib.yacrd_debug_live_bytes.restype = None
+    lib.yacrd_debug_live_bytes(out)
+    return (int(out[0]), int(out[1]))
+
+
 def load_library():
     global _lib
     if _lib is not None:
