@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define YACRD_ABI_VERSION 7 /* (yacrd_engine_ingest_report[_mem] and yacrd_engine_write_report[_mem] are additive: found by the symbol, like the editors) 7: yacrd_timing.predicted / prediction_misses / build_switches / sorting_build; 6: yacrd_engines_ingest_overlaps[_mem]; 5: YACRD_F_ONE_LAUNCH, yacrd_timing.one_launch; 4: yacrd_timing.screen_items, yacrd_engine_ingest_overlaps_mem */
+#define YACRD_ABI_VERSION 7 /* (yacrd_engine_ingest_report[_mem], yacrd_engine_write_report[_mem] and yacrd_engine_edit_fastq[_mem, _gzip_mem, _gzip_file] are additive: found by the symbol, like the editors) 7: yacrd_timing.predicted / prediction_misses / build_switches / sorting_build; 6: yacrd_engines_ingest_overlaps[_mem]; 5: YACRD_F_ONE_LAUNCH, yacrd_timing.one_launch; 4: yacrd_timing.screen_items, yacrd_engine_ingest_overlaps_mem */
 
 /* src/editor/mod.rs:42-59 ReadType; numeric encoding is ours, names are the reference's. */
 enum { YACRD_NOT_BAD = 0, YACRD_CHIMERIC = 1, YACRD_NOT_COVERED = 2 };
@@ -549,6 +549,46 @@ int yacrd_engine_write_report(yacrd_engine *e, const yacrd_report_table *t /* NU
                               yacrd_report_write_stats *st /* may be NULL */);
 int yacrd_engine_write_report_mem(yacrd_engine *e, const yacrd_report_table *t /* NULL = resident */, char **out, uint64_t *out_bytes,
                                   yacrd_report_write_stats *st /* may be NULL */);
+
+/* ---- scrubb / split / filter / extract on a FASTQ file on the GPU (csrc/gpu_seq_edit.hip) ------------------------------------
+ * The sequence editors of src/editor/{scrubbing,split,filter,extract}.rs on a FASTQ: the text goes to HBM, the device cuts it
+ * into lines (record r is lines 4r .. 4r + 3), looks every record's key — the first whitespace token of its name — up in the
+ * table, applies the op's rule, sizes the output, scans the sizes and gathers the output in one buffer in HBM: a copied record
+ * is the input record's bytes, a cut record `@{name}_{p0}_{p1}[ {desc}]`, that slice of the sequence, `+`, the same slice of
+ * the quality.  The bytes are those of libyacrd_host's yacrd_edit_file on the same input and table.
+ * op: all four YACRD_OP_* of yacrd_host.h.  t: the table, uploaded by the call (names, lengths, region CSR, types; unique
+ * ids); the resident form (t == NULL) is not built: YACRD_EINVAL.
+ * YACRD_EFALLBACK, with nothing written and nothing left beside out_path: a text that is not, as a whole, what the host's
+ * fast path takes — the line count a multiple of four and the last line ended, no CR anywhere, every header `@name[ desc]`
+ * with a name and no blank directly in front of its newline, every third line exactly `+`, sequence and quality of equal
+ * length (0 is allowed); a cut position beyond the record's sequence or a region with begin > end (the host words both);
+ * 2^31 records or output records; a compressed or non-regular input, or one whose name does not say FASTQ, to the file form;
+ * an out_path that is the input or exists and is no regular file; a text and output beyond the device's free memory (both
+ * lie in HBM whole; decided before anything is written).  The caller then runs yacrd_edit_file, which owns the syntax, the
+ * codecs and the messages.  An empty text is an empty output.
+ * The file form writes beside out_path and renames when the last byte is in; buffers of the _mem forms: yacrd_edit_text_free.
+ * The gzip forms mirror yacrd_engine_edit_overlaps_gzip_*: `text` is the inflated FASTQ, the finished output is deflated
+ * where it lies and only members come home; the result is ONE BGZF stream, byte for byte yacrd_engine_gzip_mem of the plain
+ * form's output (nothing kept: the EOF member alone).  The buffers stay with the engine: yacrd_engine_trim. */
+typedef struct {
+    uint64_t text_bytes, out_bytes;
+    uint64_t n_records;     /* of the input */
+    uint64_t n_out_records; /* copied records and cut pieces */
+    float text_ms;   /* the text into HBM, the segments' line counts behind it */
+    float table_ms;  /* the table up, the id table built */
+    float kernel_ms; /* lines + scan + index + plan + scans + pieces + copy (device events) */
+    float out_ms;    /* the output (or its members) D2H and into the file or the buffer */
+} yacrd_seq_edit_stats;
+int yacrd_engine_edit_fastq(yacrd_engine *e, int op, const char *in_path, const char *out_path, int n_threads,
+                            const yacrd_report_table *t, yacrd_seq_edit_stats *st /* may be NULL */);
+int yacrd_engine_edit_fastq_mem(yacrd_engine *e, int op, const char *text, uint64_t n_bytes, const yacrd_report_table *t,
+                                char **out, uint64_t *out_bytes, yacrd_seq_edit_stats *st /* may be NULL */);
+int yacrd_engine_edit_fastq_gzip_mem(yacrd_engine *e, int op, const char *text, uint64_t n_bytes, const yacrd_report_table *t,
+                                     char **out, uint64_t *out_bytes, yacrd_seq_edit_stats *st /* may be NULL */,
+                                     yacrd_gzip_stats *gs /* may be NULL */);
+int yacrd_engine_edit_fastq_gzip_file(yacrd_engine *e, int op, const char *text, uint64_t n_bytes, const yacrd_report_table *t,
+                                      const char *out_path, yacrd_seq_edit_stats *st /* may be NULL */,
+                                      yacrd_gzip_stats *gs /* may be NULL */);
 
 /* Copy the last device result to host (allocates like yacrd_engine_run). */
 int yacrd_engine_fetch(yacrd_engine *e, yacrd_result *out);

@@ -1,0 +1,114 @@
+#!/usr/bin/env python3
+"""tools/edit_fastq_bench.py --parent-bin PATH [--reads R] [--overlaps O] [--runs K] [--ops scrubb,filter] [--forms plain,gzip1,bgzf] [--json PATH]
+scrubb / filter on a FASTQ through the COMMAND, the parent commit's `yacrd` against this tree's, on a synthetic Sequel FASTQ
+(50 000 reads: about 1 GB) in /dev/shm, output there too:
+    yacrd -i s.paf -o r.yacrd -c 3 -n 0.4 <op> -i reads.fastq[.gz] -o out.fastq[.gz]
+with the FASTQ plain, as gzip level 1 (one stream) and as BGZF; K timed runs of each binary after one warm-up, the old output
+removed before the clock starts:
+  (a) parent   PATH: the host editors — chunk-parallel on the plain file; for gzip one thread inflates and edits and the
+               bytes leave through the gzip writer (its "[info] device deflate:" line)
+  (b) new      this tree's yacrd: the text in HBM, cut, decided and gathered there (its "[info] device fastq editor:" line);
+               for gzip the file inflated member-parallel and the output deflated where it lies
+The figures compared are the `edit` stage of YACRD_CLI_TIMING — slowest (b) against fastest (a) — and the wall clock.  Every
+output is compared with the parent's (gzip: the inflated bytes when the streams differ).  One JSON line per op and form,
+appended to --json (default profiles/edit_fastq.json)."""
+import argparse, gzip, json, os, re, subprocess, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import yacrd_amd  # noqa: E402
+from yacrd_amd import host  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--reads", type=int, default=50_000)
+ap.add_argument("--overlaps", type=int, default=5_000_000)
+ap.add_argument("--runs", type=int, default=3)
+ap.add_argument("--ops", default="scrubb,filter")
+ap.add_argument("--forms", default="plain,gzip1,bgzf")
+ap.add_argument("--parent-bin", default=None)
+ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "edit_fastq.json"))
+a = ap.parse_args()
+if not a.parent_bin or not os.access(a.parent_bin, os.X_OK):
+    sys.exit("--parent-bin: the yacrd binary built from the parent commit")
+new_bin = os.path.join(ROOT, "yacrd_amd", "bin", "yacrd")
+d = os.environ.get("YACRD_EDIT_BENCH_DIR", "/dev/shm")
+tag = os.path.join(d, "yacrd_efb_%d_" % os.getpid())
+paf, fq, rep = tag + "s.paf", tag + "s.fastq", tag + "r.yacrd"
+
+
+def fresh(path):
+    if os.path.exists(path):
+        os.remove(path)  # (or the open's truncation frees the last run's pages inside the timed region)
+
+
+def same(x, y, inflate):
+    def chunks(p):
+        with (gzip.open(p, "rb") if inflate else open(p, "rb")) as f:
+            while True:
+                b = f.read(1 << 24)
+                yield b
+                if not b:
+                    return
+    return all(p == q for p, q in zip(chunks(x), chunks(y)))
+
+
+def run(binary, op, src, out):
+    rows = []
+    for k in range(a.runs + 1):
+        fresh(out)
+        fresh(rep)
+        t0 = time.perf_counter()
+        p = subprocess.run([binary, "-i", paf, "-o", rep, "-c", "3", "-n", "0.4", op, "-i", src, "-o", out],
+                           capture_output=True, text=True, env=dict(os.environ, YACRD_CLI_TIMING="1"))
+        wall = time.perf_counter() - t0
+        assert p.returncode == 0, p.stderr
+        stages = dict(re.findall(r"^\[timing\] (\S+) ([0-9.]+) s$", p.stderr, re.M))
+        info = [l for l in p.stderr.splitlines() if l.startswith("[info] device fastq editor:") or l.startswith("[info] device deflate:")]
+        row = {"edit_s": float(stages["edit"]), "wall_s": round(wall, 3), "info": info}
+        if k:
+            rows.append(row)
+    return rows
+
+
+made = [paf, fq, rep]
+try:
+    seed = 20241108 + 5
+    host.synth_paf(host.SYNTH_SEQUEL, a.reads, a.overlaps, seed, paf)
+    host.synth_fastq(host.SYNTH_SEQUEL, a.reads, a.overlaps, seed, a.reads // 200, fq)
+    size = os.path.getsize(fq)
+    for form in a.forms.split(","):
+        ext = ".fastq" if form == "plain" else ".fastq.gz"
+        src = fq if form == "plain" else tag + form + ext
+        if form == "gzip1":
+            with open(src, "wb") as f:
+                subprocess.check_call(["gzip", "-1", "-c", fq], stdout=f)
+        elif form == "bgzf":
+            with yacrd_amd.Engine(device_id=0) as e, e.gzip_writer(src) as w, open(fq, "rb") as f:
+                while True:
+                    piece = f.read(1 << 26)
+                    if not piece:
+                        break
+                    w.write(piece)
+        made.append(src)
+        for op in a.ops.split(","):
+            old, new = tag + "old" + ext, tag + "new" + ext
+            made.extend([old, new])
+            parent = run(a.parent_bin, op, src, old)
+            mine = run(new_bin, op, src, new)
+            assert any(l.startswith("[info] device fastq editor:") for l in mine[-1]["info"]), "the device editor did not run"
+            assert same(old, new, False) or (form != "plain" and same(old, new, True)), "the new path's output differs from the parent's"
+            worst_new, best_old = max(r["edit_s"] for r in mine), min(r["edit_s"] for r in parent)
+            row = {"reads": a.reads, "overlaps": a.overlaps, "op": op, "form": form, "text_bytes": size, "in_bytes": os.path.getsize(src),
+                   "out_bytes": os.path.getsize(new), "parent": parent, "new": mine, "edit_stage_slowest_new_s": worst_new,
+                   "edit_stage_fastest_parent_s": best_old, "ratio": round(best_old / worst_new, 2),
+                   "wall_slowest_new_s": max(r["wall_s"] for r in mine), "wall_fastest_parent_s": min(r["wall_s"] for r in parent)}
+            line = json.dumps(row)
+            print(line, flush=True)
+            with open(a.json, "a") as f:
+                f.write(line + "\n")
+            fresh(old)
+            fresh(new)
+        if src != fq:
+            fresh(src)
+finally:
+    for x in made:
+        fresh(x)

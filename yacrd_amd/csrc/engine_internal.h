@@ -1,6 +1,6 @@
 // engine_internal.h — host-side internals shared by the translation units of libyacrd_hip.so: engine.hip (batch runs, the
 // engine's life), stream.hip (streaming ingest + CSR build on the GPU) and the text paths gpu_paf.hip, gpu_edit.hip,
-// gpu_deflate.hip, gpu_report.hip, gpu_report_write.hip.  The error slot; the OWNERS of every HIP resource the library takes:
+// gpu_deflate.hip, gpu_report.hip, gpu_report_write.hip, gpu_seq_edit.hip.  The error slot; the OWNERS of every HIP resource the library takes:
 // DevBuf (device memory), PinBuf (pinned memory), Events, Streams.  Each frees what it holds when it goes, none is copied, and
 // no translation unit calls the runtime's allocate / create / free / destroy functions itself (yacrd_pinned_alloc / _free, whose
 // memory is the caller's, excepted); the two buffer types count the bytes they hold (live_bytes).  Then the clocks, the engine
@@ -354,7 +354,7 @@ struct yacrd_engine {
     // what the text paths keep between calls (their own types, whose members own their device and pinned buffers, events and
     // streams; nothing in them outlives a call except capacity), made on first use by yke::scratch_of; yacrd_engine_trim and
     // yacrd_engine_destroy delete them (drop_scratch), the next use after a trim makes a fresh one
-    enum Slot { kPaf = 0, kEdit, kGzip, kReport, kReportWrite, kSlots };
+    enum Slot { kPaf = 0, kEdit, kGzip, kReport, kReportWrite, kSeqEdit, kSlots };
     struct {
         void *p = nullptr;
         void (*destroy)(void *) = nullptr;

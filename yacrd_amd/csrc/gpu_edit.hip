@@ -34,6 +34,7 @@
 // those of yacrd_engine_gzip_mem on the kept bytes whatever the segments, the threads or the timing.
 #include "engine_internal.h"
 #include "gpu_text.h"
+#include "edit_table.h"
 #include "host/beside_file.h"
 #include "host/segment_pump.h"
 
@@ -47,15 +48,6 @@ namespace yk {
 
 constexpr int kEdOver = 1024; // bytes staged beyond the tile: most lines that start in it end there
 constexpr u32 kEdNeedHost = 1u, kEdInternal = 4u;
-
-struct EdTable {
-    const unsigned char *names; // the reads' names, back to back
-    const u64 *name_off;        // [n_reads + 1]
-    const unsigned char *type;  // [n_reads]
-    u32 *slots;                 // [mask + 1]: 0 = empty, else read + 1
-    u32 mask;
-    u32 n_reads;
-};
 
 struct EdArgs {
     const unsigned char *text;
@@ -75,33 +67,6 @@ struct EdArgs {
     u32 seg;
     u32 delim, ib, n_fields, keep_good; // keep_good: filter (keep when both reads are good); else extract
 };
-
-__global__ __launch_bounds__(256) void ed_table_kernel(EdTable t)
-{
-    const u32 r = blockIdx.x * 256u + threadIdx.x;
-    if (r >= t.n_reads) return;
-    const u64 o = t.name_off[r];
-    const GpBytes names{t.names};
-    u32 s = (u32)gp_hash(names, o, (u32)(t.name_off[r + 1] - o)) & t.mask;
-    while (atomicCAS(&t.slots[s], 0u, r + 1u) != 0u) s = (s + 1u) & t.mask; // (names are unique: no slot is ours already)
-}
-
-// the type of the read named text[p, p + len): 0 (NotBad) when the table does not hold it
-__device__ __forceinline__ u32 ed_lookup(const EdTable &tab, const GpText &t, u64 p, u32 len)
-{
-    u32 s = (u32)gp_hash(t, p, len) & tab.mask;
-    for (;;) {
-        const u32 v = tab.slots[s];
-        if (v == 0u) return 0u;
-        const u64 o = tab.name_off[v - 1u];
-        if (tab.name_off[v] - o == (u64)len) {
-            u32 i = 0;
-            while (i < len && (u32)tab.names[o + i] == t[p + i]) i++;
-            if (i == len) return tab.type[v - 1u];
-        }
-        s = (s + 1u) & tab.mask;
-    }
-}
 
 // The tile [tile0, tile0 + want) -> LDS, 16 bytes per thread and step (the mirror is padded by 64 zero bytes and the last
 // step is clipped to whole 16-byte pieces inside it; an inner segment's `avail` is a chunk boundary); the newline mask of

@@ -1,0 +1,886 @@
+// gpu_seq_edit.hip — scrubb / split / filter / extract on a FASTQ file with the decision, the sizing and the gather on the GPU
+// (include/yacrd_engine.h: yacrd_engine_edit_fastq).
+//
+// Reference: Scrubbing::run (src/editor/scrubbing.rs:156-236), Split::run (src/editor/split.rs), Filter::run and Extract::run on
+// sequence files: a record's key — the first whitespace token of its name — is looked up in the bad-part table (an id it does not
+// hold is NotBad with no region, src/stack.rs:164-169); filter copies a NotBad record, extract any other; scrubb and split drop
+// NotCovered reads, copy a read with no region (scrubb) or a NotBad one (split) and cut every other at its regions: one read
+// becomes several records `@{name}_{p0}_{p1}[ {desc}]` with that slice of the sequence and of the quality.  The host loop
+// (host/editors.cc: edit_sequences, FASTQ branch; cut_positions) defines the bytes; here the host only MOVES the text
+// (gpu_text.h: the parser's mover) and the output.  On the device:
+//   table    the reads' names, lengths, types and region CSR uploaded once; the id table of edit_table.h over the names
+//   lines    per segment as it lands: the newlines of every 32 KiB tile, and whether a CR lies in it
+//   scan     the tiles' line counts (stream.hip's device-wide scan): the index of every tile's first newline
+//   index    every tile writes the offsets of its newlines to line_end[]: record r is lines 4r .. 4r + 3 — nothing is guessed,
+//            a quality line that begins with '@' is just line 4r + 3
+//   plan     a thread per record: the canonical form checked, the key found and looked up, the op's rule applied, the
+//            record's output pieces and bytes counted
+//   scans    of the pieces and of the bytes
+//   pieces   a thread per record writes its piece descriptors at their scanned places
+//   copy     a workgroup per 4 KiB tile of the OUTPUT: a thread finds the piece that covers its first byte by binary search and
+//            walks on from there; every 4-byte word of the tile is composed in LDS — header bytes formatted, text bytes fetched
+//            with aligned 4-byte loads (neighbouring lanes read neighbouring words) — and the tile is stored with 16-byte stores;
+//            the bytes stored are counted, a total that differs from the scan's is YACRD_EINTERNAL
+// In this version index, plan, pieces and copy wait for the last segment of text, and the text and the whole output lie in HBM.
+// What the path does not take — a CR, a line count that is no multiple of four, a header without '@' or without a name, a
+// "@name \n", a '+' line that is not bare, sequence and quality of different lengths, a cut position beyond the read, a region
+// with begin > end — comes back as YACRD_EFALLBACK with nothing written: the caller runs the host loop.
+//
+// gzip out (yacrd_engine_edit_fastq_gzip_mem / _file): the finished output buffer goes through gpu_deflate.hip's
+// device-resident step, batch by batch (a batch begins on a multiple of 65 280 bytes: the encoder's 16-byte loads stay
+// aligned); one batch comes home while the next is encoded.  Blocks are counted from byte 0 of the output, so the stream is
+// yacrd_engine_gzip_mem's for the same bytes.
+#include "engine_internal.h"
+#include "gpu_text.h"
+#include "edit_table.h"
+#include "host/beside_file.h"
+#include "host/segment_pump.h"
+
+#include <cstdio>
+#include <cstdlib>
+
+using namespace yke;
+
+namespace yk {
+
+constexpr u32 kSqNeedHost = 1u;
+constexpr int kSqOutTile = kGpT * 16; // bytes of output per workgroup of the copy pass
+constexpr u32 kSqCopy = 1u;           // SqPiece::flags: the record as it stands in the text
+constexpr u64 kSqMaxRecord = 0xFF000000ull; // bytes of a record, of a piece: offsets inside them are u32
+
+struct SqPiece { // one record of the output
+    u64 out;     // where its first byte goes
+    u64 rec;     // the input record's '@'
+    u32 len;     // its bytes
+    u32 flags;
+    u32 name_len, desc_len;
+    u32 seq_rel, qual_rel; // the record's sequence / quality line, from `rec`
+    u32 p0, p1;
+};
+static_assert(sizeof(SqPiece) == 48, "host code sizes the piece buffer by this");
+
+struct SqArgs {
+    const unsigned char *text;
+    u64 n;     // bytes of text
+    u64 avail; // bytes [0, avail) have landed (== n for the last segment)
+    EdTable tab;
+    const u32 *lengths;  // [n_reads]
+    const u64 *bad_off;  // [n_reads + 1]
+    const u32 *bad_reg;  // [2 * regions]
+    u32 *tile_nl;        // per text tile: its newlines
+    const u64 *tile_l0;  // their exclusive scan
+    u64 *line_end;       // [n_lines]: where every newline lies
+    u64 n_lines, n_rec;
+    u32 *rec_pieces, *rec_bytes;        // per record: output records, output bytes
+    const u64 *piece_off, *byte_off;    // their exclusive scans
+    SqPiece *pieces;
+    u64 n_pieces, total;                // output records, output bytes
+    unsigned char *out;
+    unsigned long long *ctl; // [0] status, [1] bytes the copy pass stored
+    u32 tile0;               // the launch's first text tile
+    u32 op;
+};
+
+// the tile's newline masks (a u16 per 16 bytes) -> nlm; returns the thread's newline count and ORs a CR into `cr`.  The
+// mirror is padded by 64 zero bytes and the last step is clipped to whole 16-byte pieces inside it; an inner segment's
+// `avail` is a chunk boundary.
+__device__ __forceinline__ u32 sq_stage(const SqArgs &a, u64 tile0, unsigned short *nlm, u32 &cr)
+{
+    const u64 lim = a.avail == a.n ? ((a.n + 63) & ~(u64)15) : a.avail;
+    u32 cnt = 0;
+    for (u32 i = threadIdx.x * 16u; i < (u32)kGpTile; i += (u32)kGpT * 16u) {
+        u32 nlb = 0;
+        if (tile0 + i < lim) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(a.text + tile0 + i);
+            nlb = gp_eq16(v, '\n');
+            cr |= gp_eq16(v, '\r');
+        }
+        if (nlm) nlm[i >> 4] = (unsigned short)nlb;
+        cnt += (u32)__popc(nlb);
+    }
+    return cnt;
+}
+
+// ---- lines: the newlines of every tile of a segment, a CR anywhere -----------------------------------------------------------
+__global__ __launch_bounds__(kGpT) void sq_lines_kernel(SqArgs a)
+{
+    __shared__ u32 sw[kGpT / 64];
+    const u32 gt = a.tile0 + blockIdx.x;
+    u32 cr = 0;
+    u32 cnt = sq_stage(a, (u64)gt * (u64)kGpTile, nullptr, cr);
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) cnt += (u32)__shfl_xor((int)cnt, d, 64);
+    cr = wave_or(cr);
+    if (lane_id() == 0) {
+        sw[threadIdx.x >> 6] = cnt;
+        if (cr) atomicOr(a.ctl, (unsigned long long)kSqNeedHost);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u32 tot = 0;
+#pragma unroll
+        for (int w = 0; w < kGpT / 64; w++) tot += sw[w];
+        a.tile_nl[gt] = tot;
+    }
+}
+
+// ---- index: where every newline lies, in line order ----------------------------------------------------------------------------
+__global__ __launch_bounds__(kGpT) void sq_index_kernel(SqArgs a)
+{
+    __shared__ __attribute__((aligned(16))) unsigned short nlm[kGpTile / 16];
+    __shared__ u32 sw[kGpT / 64];
+    const u32 gt = blockIdx.x;
+    const u64 tile0 = (u64)gt * (u64)kGpTile;
+    u32 cr = 0;
+    (void)sq_stage(a, tile0, nlm, cr);
+    __syncthreads();
+    const uint4 q = *reinterpret_cast<const uint4 *>(nlm + threadIdx.x * 8u);
+    u64 m[2] = {(u64)q.x | ((u64)q.y << 32), (u64)q.z | ((u64)q.w << 32)};
+    u32 tot = 0;
+    const u32 at = block_excl_add<kGpT>((u32)__popcll(m[0]) + (u32)__popcll(m[1]), sw, tot);
+    u64 g = a.tile_l0[gt] + at;
+    const u64 lo = tile0 + (u64)threadIdx.x * 128u;
+#pragma unroll
+    for (int h = 0; h < 2; h++)
+        while (m[h]) {
+            const u32 bit = (u32)__builtin_ctzll(m[h]);
+            m[h] &= m[h] - 1;
+            if (g < a.n_lines) a.line_end[g] = lo + (u64)h * 64u + bit; // (the two passes count alike: always)
+            g++;
+        }
+}
+
+__device__ __forceinline__ u32 sq_digits(u32 v)
+{
+    u32 d = 1;
+    while (v >= 10u) v /= 10u, d++;
+    return d;
+}
+// digit k (from the left) of v, which has nd digits
+__device__ __forceinline__ u32 sq_digit_at(u32 v, u32 nd, u32 k)
+{
+    for (u32 i = nd - 1u - k; i; i--) v /= 10u;
+    return '0' + v % 10u;
+}
+
+// The cut pieces of a read, in order (host/editors.cc: cut_positions and the loop behind it): scrubb takes every region, a
+// leading (0, 0) pair is skipped and `len` closes the list unless it is its last element already — then the odd element is
+// ignored —; split takes the regions that touch neither end.  f(p0, p1) returns false to stop.
+template <class F>
+__device__ __forceinline__ void sq_cuts(u32 op, const u32 *reg, u32 n, u32 len, F &&f)
+{
+    u32 p0 = 0;
+    if (op == 0u) {
+        for (u32 i = 0; i < n; i++) {
+            const u32 b = reg[2 * i], e = reg[2 * i + 1];
+            if (!(i == 0 && b == 0u) && !f(p0, b)) return;
+            p0 = e;
+        }
+        if (p0 != len) (void)f(p0, len);
+    } else {
+        for (u32 i = 0; i < n; i++) {
+            const u32 b = reg[2 * i], e = reg[2 * i + 1];
+            if (b == 0u || e == len) continue;
+            if (!f(p0, b)) return;
+            p0 = e;
+        }
+        (void)f(p0, len);
+    }
+}
+
+// Record r: its canonical form checked, its verdict, its pieces.  EMIT false: the pieces and bytes counted; true: the piece
+// descriptors written.  Returns the status bits.
+template <bool EMIT>
+__device__ __forceinline__ u32 sq_record(const SqArgs &a, u64 r)
+{
+    const unsigned char *t = a.text;
+    const u64 s = r ? a.line_end[4 * r - 1] + 1 : 0;
+    const u64 e0 = a.line_end[4 * r], e1 = a.line_end[4 * r + 1], e2 = a.line_end[4 * r + 2], e3 = a.line_end[4 * r + 3];
+    if (!EMIT) a.rec_pieces[r] = 0u, a.rec_bytes[r] = 0u;
+    const u64 rec_len = e3 + 1 - s;
+    if (rec_len >= kSqMaxRecord) return kSqNeedHost;
+    if (t[s] != '@' || e0 == s + 1) return kSqNeedHost;
+    u64 sp = e0, key_end = e0; // the first blank; the first whitespace of any kind in front of it
+    for (u64 i = s + 1; i < e0; i++) {
+        const u32 c = t[i];
+        if (c == ' ') {
+            sp = i;
+            break;
+        }
+        if ((c == '\t' || c == '\x0c') && key_end == e0) key_end = i;
+    }
+    if (key_end > sp) key_end = sp;
+    if (sp == s + 1 || sp + 1 == e0) return kSqNeedHost; // (no name; "@name \n": the writer drops the blank)
+    if (e2 != e1 + 2 || t[e1 + 1] != '+') return kSqNeedHost;
+    const u64 seq_len64 = e1 - e0 - 1;
+    if (seq_len64 != e3 - e2 - 1) return kSqNeedHost;
+    const u32 seq_len = (u32)seq_len64;
+    const u32 name_len = (u32)(sp - s - 1), desc_len = sp < e0 ? (u32)(e0 - sp - 1) : 0u;
+
+    const u32 read = ed_find(a.tab, GpBytes{t}, s + 1, (u32)(key_end - s - 1));
+    u32 type = 0, n_reg = 0, len = 0;
+    const u32 *reg = nullptr;
+    if (read != kEdNoRead) {
+        type = a.tab.type[read];
+        const u64 o = a.bad_off[read];
+        n_reg = (u32)(a.bad_off[read + 1] - o);
+        reg = a.bad_reg + 2 * o;
+        len = a.lengths[read];
+    }
+    bool copy = false;
+    if (a.op == 1u) copy = type == 0u;
+    else if (a.op == 2u) copy = type != 0u;
+    else if (type == 2u) return 0u; // NotCovered reads are dropped
+    else copy = a.op == 0u ? n_reg == 0u : type == 0u;
+    if (a.op == 1u || a.op == 2u || copy) {
+        if (!copy) return 0u;
+        if (!EMIT) a.rec_pieces[r] = 1u, a.rec_bytes[r] = (u32)rec_len;
+        else {
+            SqPiece p{};
+            p.out = a.byte_off[r], p.rec = s, p.len = (u32)rec_len, p.flags = kSqCopy;
+            a.pieces[a.piece_off[r]] = p;
+        }
+        return 0u;
+    }
+    u32 status = 0, pieces = 0;
+    u64 bytes = 0;
+    const u32 head = 1u + name_len + (desc_len ? 1u + desc_len : 0u) + 1u;
+    sq_cuts(a.op, reg, n_reg, len, [&](u32 p0, u32 p1) {
+        if (p0 > seq_len || p1 > seq_len || p0 > p1) { // (the host prints the reference's [ERROR] line, or fails: its case)
+            status = kSqNeedHost;
+            return false;
+        }
+        const u64 plen = (u64)head + 2u + sq_digits(p0) + sq_digits(p1) + 2ull * (p1 - p0) + 4u;
+        if (EMIT) {
+            SqPiece p{};
+            p.out = a.byte_off[r] + bytes, p.rec = s, p.len = (u32)plen, p.flags = 0u;
+            p.name_len = name_len, p.desc_len = desc_len;
+            p.seq_rel = (u32)(e0 + 1 - s), p.qual_rel = (u32)(e2 + 1 - s);
+            p.p0 = p0, p.p1 = p1;
+            a.pieces[a.piece_off[r] + pieces] = p;
+        }
+        pieces++, bytes += plen;
+        return true;
+    });
+    if (bytes >= kSqMaxRecord) status = kSqNeedHost;
+    if (status) return status;
+    if (!EMIT) a.rec_pieces[r] = pieces, a.rec_bytes[r] = (u32)bytes;
+    return 0u;
+}
+
+// ---- plan / pieces: a thread per record ----------------------------------------------------------------------------------------------
+template <bool EMIT>
+__global__ __launch_bounds__(256) void sq_plan_kernel(SqArgs a)
+{
+    const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+    u32 status = r < a.n_rec ? sq_record<EMIT>(a, r) : 0u;
+    status = wave_or(status);
+    if (status && lane_id() == 0) atomicOr(a.ctl, (unsigned long long)status);
+}
+
+// byte k of piece p: a byte of the text (src, with `rem` bytes of the same run behind it) or a formatted one (lit, src null)
+__device__ __forceinline__ void sq_at(const SqArgs &a, const SqPiece &p, u32 k, const unsigned char *&src, u32 &rem, u32 &lit)
+{
+    const unsigned char *rec = a.text + p.rec;
+    if (p.flags & kSqCopy) {
+        src = rec + k, rem = p.len - k;
+        return;
+    }
+    src = nullptr, rem = 1, lit = '\n';
+    if (k == 0) {
+        lit = '@';
+        return;
+    }
+    k -= 1;
+    if (k < p.name_len) {
+        src = rec + 1 + k, rem = p.name_len - k;
+        return;
+    }
+    k -= p.name_len;
+    const u32 d0 = sq_digits(p.p0), d1 = sq_digits(p.p1);
+    if (k < 2u + d0 + d1) {
+        lit = k == 0 || k == d0 + 1u ? '_' : k <= d0 ? sq_digit_at(p.p0, d0, k - 1u) : sq_digit_at(p.p1, d1, k - d0 - 2u);
+        return;
+    }
+    k -= 2u + d0 + d1;
+    if (p.desc_len) {
+        if (k == 0) {
+            lit = ' ';
+            return;
+        }
+        k -= 1;
+        if (k < p.desc_len) {
+            src = rec + 1 + p.name_len + 1 + k, rem = p.desc_len - k;
+            return;
+        }
+        k -= p.desc_len;
+    }
+    if (k == 0) return; // the header's newline
+    k -= 1;
+    const u32 L = p.p1 - p.p0;
+    if (k < L) {
+        src = rec + p.seq_rel + p.p0 + k, rem = L - k;
+        return;
+    }
+    k -= L;
+    if (k < 3u) {
+        lit = k == 1u ? '+' : '\n';
+        return;
+    }
+    k -= 3u;
+    if (k < L) src = rec + p.qual_rel + p.p0 + k, rem = L - k; // (else: the record's last newline)
+}
+
+// ---- copy: a tile of the output, composed in LDS, stored 16 bytes wide -----------------------------------------------------------
+// Thread t composes words t, t + 256, t + 512 and t + 768 of the tile, so that a wavefront's loads from a run of text are
+// consecutive words; it then stores bytes [16 t, 16 t + 16).  The output buffer is padded to whole 16-byte pieces (the
+// bytes behind the total are zeros).
+__global__ __launch_bounds__(kGpT) void sq_copy_kernel(SqArgs a)
+{
+    __shared__ __attribute__((aligned(16))) u32 tile[kSqOutTile / 4];
+    __shared__ u32 sw[kGpT / 64];
+    const u64 tile0 = (u64)blockIdx.x * (u64)kSqOutTile;
+    u32 stored = 0;
+    u64 pi = 0;
+    SqPiece p{};
+    bool have = false;
+#pragma unroll 1
+    for (u32 w = 0; w < 4u; w++) {
+        const u64 j = tile0 + ((u64)w * (u32)kGpT + threadIdx.x) * 4u;
+        u32 word = 0;
+        if (j < a.total) {
+            if (!have) { // the last piece that begins at or in front of j (piece 0 begins at 0)
+                u64 lo = 0, hi = a.n_pieces;
+                while (hi - lo > 1) {
+                    const u64 mid = lo + (hi - lo) / 2;
+                    if (a.pieces[mid].out <= j) lo = mid;
+                    else hi = mid;
+                }
+                pi = lo, p = a.pieces[lo], have = true;
+            }
+            const u32 nb = (u32)min((u64)4, a.total - j);
+            for (u32 b = 0; b < nb;) {
+                const u64 jj = j + b;
+                while (jj >= p.out + p.len && pi + 1 < a.n_pieces) p = a.pieces[++pi]; // (jj < total: there is such a piece)
+                const unsigned char *src;
+                u32 rem, lit;
+                sq_at(a, p, (u32)(jj - p.out), src, rem, lit);
+                if (src && b == 0 && rem >= 4u) { // four bytes of one run: the aligned words that hold them
+                    const uintptr_t ad = reinterpret_cast<uintptr_t>(src);
+                    const u32 *al = reinterpret_cast<const u32 *>(ad & ~(uintptr_t)3);
+                    const u32 sh = (u32)(ad & 3u) * 8u;
+                    word = al[0];
+                    if (sh) word = (word >> sh) | (al[1] << (32u - sh)); // (al + 1 begins inside the run)
+                    b = 4, stored += 4;
+                } else {
+                    word |= (src ? (u32)*src : lit) << (8u * b);
+                    b++, stored++;
+                }
+            }
+        }
+        tile[w * (u32)kGpT + threadIdx.x] = word;
+    }
+    __syncthreads();
+    const u64 o = tile0 + (u64)threadIdx.x * 16u;
+    if (o < a.total) *reinterpret_cast<uint4 *>(a.out + o) = *reinterpret_cast<const uint4 *>(tile + threadIdx.x * 4u);
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) stored += (u32)__shfl_xor((int)stored, d, 64);
+    if (lane_id() == 0) sw[threadIdx.x >> 6] = stored;
+    __syncthreads();
+    if (threadIdx.x == 0) { // one add per workgroup
+        u32 tot = 0;
+#pragma unroll
+        for (int w = 0; w < kGpT / 64; w++) tot += sw[w];
+        atomicAdd(a.ctl + 1, (unsigned long long)tot);
+    }
+}
+
+} // namespace yk
+
+namespace {
+
+constexpr size_t kOutPiece = (size_t)4 << 20; // (_PIECE of the tests: what one copy home moves)
+constexpr u64 kGzBatchBlocks = 2048;          // blocks of 65 280 bytes per batch of the encoder
+
+struct SeqEditScratch { // the editor's buffers; they stay with the engine (grow-only), go with yacrd_engine_trim / destroy
+    static constexpr yacrd_engine::Slot kScratchSlot = yacrd_engine::kSeqEdit;
+    DevBuf text, out, names, name_off, types, lengths, bad_off, bad_reg, slots, tile_nl, tile_l0, line_end, rec_pieces, rec_bytes, piece_off,
+        byte_off, pieces, ctl, part;
+    PinBuf pin; // two output pieces + the control words
+};
+
+using yseg::Sink;
+
+struct SeqJob {
+    int op = 0;
+    int n_threads = 0;
+    const yacrd_report_table *table = nullptr;
+    bool gzip = false;
+    yacrd_gzip_stats *gzip_stats = nullptr;
+};
+
+struct SeqGzHold { // the engine's encoder buffers are this edit's until it ends
+    yacrd_engine *e = nullptr;
+    ~SeqGzHold()
+    {
+        if (e) gzip_device_close(e);
+    }
+};
+
+// One edit on its way through the device: built once per call (run_seq_edit), its phases in the order they run.
+struct SeqRun {
+    yacrd_engine *e;
+    const SeqJob &job;
+    const TextSource &src;
+    const u64 n;
+    Sink &sink;
+    yacrd_seq_edit_stats *stats;
+    SeqEditScratch &S;
+    u64 R = 0, G = 0, name_bytes = 0, cap = 1024;
+    u64 n_tiles = 0, n_lines = 0, n_rec = 0, n_pieces = 0, total = 0;
+    size_t n_segs = 0;
+    bool blit = false;
+    yk::SqArgs ga{};
+    volatile u64 *h_ctl = nullptr; // pinned: [0..3] what a phase brings home, [4..7] the encoder's words of two batches
+    Events ev;                     // pairs around the kernels of a phase (timing)
+    Events wev;                    // a pinned piece has landed (two; no timing)
+    Events gev, gdone;             // the encoder's batches: pairs around their kernels; behind their sizes' way home
+    Streams side;                  // [0] the way home; [1] the encoder
+    size_t n_ev = 0;
+    GzDevice gz;
+    SeqGzHold gz_hold;
+    double t_start = 0, t_table = 0, t_text = 0, out_busy_ms = 0, put_ms = 0;
+    u64 gz_members = 0, gz_stored = 0;
+    float gz_kernel_ms = 0;
+
+    // whether `need` more bytes of HBM are there, counting what the scratch already holds of them
+    static bool fits(double need, double held)
+    {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return true; // (the reserves then say)
+        return need * 1.125 + (double)((size_t)64 << 20) <= (double)free_b + held;
+    }
+    static int no_room() { return fail(YACRD_EFALLBACK, "the text and its output do not fit this device's free memory: the host loop streams them"); }
+
+    bool ev_open()
+    {
+        return n_ev + 2 <= ev.v.size() && hipEventRecord(ev[n_ev], e->stream) == hipSuccess;
+    }
+    bool ev_close()
+    {
+        n_ev += 2;
+        return hipEventRecord(ev[n_ev - 1], e->stream) == hipSuccess;
+    }
+
+    // the table's shape, the text's last byte, the sizes that follow from n
+    int plan()
+    {
+        const yacrd_report_table &t = *job.table;
+        R = t.n_reads;
+        if (R >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "more reads than the device table holds");
+        if (R && (!t.name_off || !t.names || !t.lengths || !t.bad_offsets || !t.read_type)) return fail(YACRD_EINVAL, "the report table is incomplete");
+        if (R) {
+            if (t.name_off[0] != 0 || t.bad_offsets[0] != 0) return fail(YACRD_EINVAL, "name_off / bad_offsets do not begin at 0");
+            for (u64 r = 0; r < R; r++)
+                if (t.name_off[r + 1] < t.name_off[r] || t.bad_offsets[r + 1] < t.bad_offsets[r])
+                    return fail(YACRD_EINVAL, "name_off / bad_offsets do not rise");
+            name_bytes = t.name_off[R], G = t.bad_offsets[R];
+            if (G >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "more regions than the device table holds");
+            if (G && !t.bad_regions) return fail(YACRD_EINVAL, "the report table is incomplete");
+        }
+        if (n) {
+            char last = 0;
+            if (!src.fetch(&last, 1, n - 1)) return fail(YACRD_EINVAL, "read error in the sequence file");
+            if (last != '\n') return fail(YACRD_EFALLBACK, "the text's last line has no newline: the host loop's case");
+        }
+        n_tiles = (n + yk::kGpTile - 1) / yk::kGpTile;
+        if (n_tiles >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "file too large for the device editor");
+        n_segs = (size_t)((n + kTextChunk * kTextSeg - 1) / (kTextChunk * kTextSeg));
+        while (cap < 2 * R) cap <<= 1;
+        t_start = now_ms();
+        const double held = (double)S.text.cap + (double)S.names.cap + (double)S.slots.cap + (double)S.bad_reg.cap + (double)S.tile_l0.cap;
+        // (the output is at least... unknown yet: asked for again when it is; here the text, the table and the tiles' words)
+        if (!fits((double)n + (double)name_bytes + (double)cap * 4.0 + (double)R * 21.0 + (double)G * 8.0 + (double)n_tiles * 12.0, held)) return no_room();
+        return YACRD_OK;
+    }
+
+    // the text's buffer, the table in HBM, the id table over the names; streams, events, the pinned pieces
+    int upload_table()
+    {
+        const yacrd_report_table &t = *job.table;
+        const void *mirror_before = S.text.p;
+        HIP_TRY(S.text.reserve((size_t)n + 64));
+        blit = S.text.p != mirror_before; // a fresh mirror fills faster by copy kernel (gpu_paf.hip)
+        HIP_TRY(S.tile_nl.reserve((size_t)(n_tiles + 1) * sizeof(u32)));
+        HIP_TRY(S.tile_l0.reserve((size_t)(n_tiles + 2) * sizeof(u64)));
+        HIP_TRY(S.ctl.reserve(64));
+        HIP_TRY(hipMemsetAsync(S.ctl.p, 0, 64, e->stream));
+        HIP_TRY(S.pin.reserve(2 * kOutPiece + 8 * sizeof(u64)));
+        h_ctl = reinterpret_cast<volatile u64 *>(S.pin.as<char>() + 2 * kOutPiece);
+        for (int i = 0; i < 8; i++) h_ctl[i] = 0;
+        if (!side.add(job.gzip ? 2 : 1) || !wev.add(2, hipEventDisableTiming) || !ev.add(2 * n_segs + 8)) HIP_TRY(why_not_added());
+        HIP_TRY(S.names.reserve((size_t)name_bytes + 64));
+        HIP_TRY(S.name_off.reserve((size_t)(R + 1) * sizeof(u64)));
+        HIP_TRY(S.types.reserve((size_t)R + 64));
+        HIP_TRY(S.lengths.reserve((size_t)(R + 1) * sizeof(u32)));
+        HIP_TRY(S.bad_off.reserve((size_t)(R + 1) * sizeof(u64)));
+        HIP_TRY(S.bad_reg.reserve((size_t)(2 * G + 2) * sizeof(u32)));
+        HIP_TRY(S.slots.reserve((size_t)cap * sizeof(u32)));
+        HIP_TRY(hipMemsetAsync(S.slots.p, 0, (size_t)cap * sizeof(u32), e->stream));
+        yk::EdTable tab{};
+        tab.names = S.names.as<unsigned char>(), tab.name_off = S.name_off.as<u64>(), tab.type = S.types.as<unsigned char>();
+        tab.slots = S.slots.as<u32>(), tab.mask = (u32)(cap - 1), tab.n_reads = (u32)R;
+        if (R) {
+            if (name_bytes)
+                if (const int rch = h2d(e, S.names.p, t.names, (size_t)name_bytes)) return rch;
+            if (const int rch = h2d(e, S.name_off.p, t.name_off, (size_t)(R + 1) * sizeof(u64))) return rch;
+            if (const int rch = h2d(e, S.types.p, t.read_type, (size_t)R)) return rch;
+            if (const int rch = h2d(e, S.lengths.p, t.lengths, (size_t)R * sizeof(u32))) return rch;
+            if (const int rch = h2d(e, S.bad_off.p, t.bad_offsets, (size_t)(R + 1) * sizeof(u64))) return rch;
+            if (G)
+                if (const int rch = h2d(e, S.bad_reg.p, t.bad_regions, (size_t)(2 * G) * sizeof(u32))) return rch;
+            hipLaunchKernelGGL(yk::ed_table_kernel, dim3((u32)((R + 255) / 256)), dim3(256), 0, e->stream, tab);
+        }
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        t_table = now_ms();
+        ga.text = S.text.as<unsigned char>(), ga.n = n, ga.avail = n;
+        ga.tab = tab;
+        ga.lengths = S.lengths.as<u32>(), ga.bad_off = S.bad_off.as<u64>(), ga.bad_reg = S.bad_reg.as<u32>();
+        ga.tile_nl = S.tile_nl.as<u32>(), ga.tile_l0 = S.tile_l0.as<u64>();
+        ga.ctl = S.ctl.as<unsigned long long>();
+        ga.op = (u32)job.op;
+        return YACRD_OK;
+    }
+
+    // the text into HBM; the lines of every segment counted as it lands; then the scan of the tiles' counts
+    int move_and_count()
+    {
+        HIP_TRY(hipMemsetAsync(S.text.as<char>() + n, 0, 64, e->stream));
+        bool ok = true;
+        const int moved = move_text(e, src, 0, n, S.text.as<char>(), blit, job.n_threads, [&](u64 seg_begin, u64 seg_end, u64 avail) {
+            const u32 t0 = (u32)(seg_begin / yk::kGpTile), t1 = seg_end >= n ? (u32)n_tiles : (u32)(seg_end / yk::kGpTile);
+            ga.avail = seg_end >= n ? n : std::min<u64>(avail, seg_end); // (a tile of this segment reads nothing behind it)
+            ga.tile0 = t0;
+            ok = ok && ev_open();
+            if (t1 > t0) hipLaunchKernelGGL(yk::sq_lines_kernel, dim3(t1 - t0), dim3(yk::kGpT), 0, e->stream, ga);
+            ok = ok && ev_close();
+        });
+        t_text = now_ms();
+        if (moved == 2) return fail(YACRD_EINVAL, "read error in the sequence file");
+        if (moved == 3) return fail(YACRD_ENOMEM, "sequence text to HBM: no pinned memory");
+        if (moved || !ok) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
+        ga.avail = n;
+        ok = ev_open();
+        if (const int rc = scan_u32_to_u64(e, S.tile_nl.as<u32>(), n_tiles, S.tile_l0.as<u64>(), S.part)) return rc;
+        ok = ok && ev_close();
+        HIP_TRY(hipMemcpyAsync((void *)h_ctl, S.tile_l0.as<u64>() + n_tiles, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync((void *)(h_ctl + 1), S.ctl.p, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipGetLastError());
+        if (!ok) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
+        n_lines = h_ctl[0];
+        if (h_ctl[1] & yk::kSqNeedHost) return fail(YACRD_EFALLBACK, "the text holds a CR: the host loop decides");
+        if (n_lines % 4) return fail(YACRD_EFALLBACK, "the line count is no multiple of four: the host loop decides");
+        n_rec = n_lines / 4;
+        if (n_rec >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "more records than the device editor numbers");
+        return YACRD_OK;
+    }
+
+    // index, plan and the two scans: how many output records, how many bytes
+    int size_output()
+    {
+        if (!fits((double)n_lines * 8.0 + (double)n_rec * 24.0, (double)S.line_end.cap + (double)S.piece_off.cap + (double)S.byte_off.cap)) return no_room();
+        HIP_TRY(S.line_end.reserve((size_t)(n_lines + 1) * sizeof(u64)));
+        HIP_TRY(S.rec_pieces.reserve((size_t)(n_rec + 1) * sizeof(u32)));
+        HIP_TRY(S.rec_bytes.reserve((size_t)(n_rec + 1) * sizeof(u32)));
+        HIP_TRY(S.piece_off.reserve((size_t)(n_rec + 2) * sizeof(u64)));
+        HIP_TRY(S.byte_off.reserve((size_t)(n_rec + 2) * sizeof(u64)));
+        ga.line_end = S.line_end.as<u64>(), ga.n_lines = n_lines, ga.n_rec = n_rec;
+        ga.rec_pieces = S.rec_pieces.as<u32>(), ga.rec_bytes = S.rec_bytes.as<u32>();
+        ga.piece_off = S.piece_off.as<u64>(), ga.byte_off = S.byte_off.as<u64>();
+        bool ok = ev_open();
+        if (n_tiles) hipLaunchKernelGGL(yk::sq_index_kernel, dim3((u32)n_tiles), dim3(yk::kGpT), 0, e->stream, ga);
+        if (n_rec) hipLaunchKernelGGL(yk::sq_plan_kernel<false>, dim3((u32)((n_rec + 255) / 256)), dim3(256), 0, e->stream, ga);
+        if (const int rc = scan_u32_to_u64(e, ga.rec_pieces, n_rec, S.piece_off.as<u64>(), S.part)) return rc;
+        if (const int rc = scan_u32_to_u64(e, ga.rec_bytes, n_rec, S.byte_off.as<u64>(), S.part)) return rc;
+        ok = ok && ev_close();
+        HIP_TRY(hipMemcpyAsync((void *)h_ctl, S.piece_off.as<u64>() + n_rec, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync((void *)(h_ctl + 1), S.byte_off.as<u64>() + n_rec, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync((void *)(h_ctl + 2), S.ctl.p, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipGetLastError());
+        if (!ok) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
+        n_pieces = h_ctl[0], total = h_ctl[1];
+        if (h_ctl[2] & yk::kSqNeedHost)
+            return fail(YACRD_EFALLBACK, "a record that is not \"@name[ desc]\\nseq\\n+\\nqual\\n\", a cut position beyond its read or a region with "
+                                         "begin > end: the host loop decides");
+        if (n_pieces >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "more output records than the device editor numbers");
+        return YACRD_OK;
+    }
+
+    // the output's buffers (the encoder's too), the piece descriptors, the copy pass
+    int gather()
+    {
+        const u64 gz_blocks = job.gzip ? std::min<u64>(kGzBatchBlocks, (total + ydf::kBlock - 1) / ydf::kBlock + 1) : 0;
+        if (!fits((double)total + (double)n_pieces * 48.0 + (double)gz_blocks * (double)ydf::kSlot * 3.0, (double)S.out.cap + (double)S.pieces.cap)) return no_room();
+        const u64 padded = (total + 15) & ~(u64)15;
+        HIP_TRY(S.out.reserve((size_t)padded + 64));
+        HIP_TRY(S.pieces.reserve((size_t)(n_pieces + 1) * sizeof(yk::SqPiece)));
+        if (job.gzip) {
+            if (const int rcg = gzip_device_open(e, gz_blocks, &gz)) return rcg;
+            gz_hold.e = e;
+        }
+        ga.pieces = S.pieces.as<yk::SqPiece>(), ga.n_pieces = n_pieces, ga.total = total, ga.out = S.out.as<unsigned char>();
+        bool ok = ev_open();
+        if (total) {
+            hipLaunchKernelGGL(yk::sq_plan_kernel<true>, dim3((u32)((n_rec + 255) / 256)), dim3(256), 0, e->stream, ga);
+            hipLaunchKernelGGL(yk::sq_copy_kernel, dim3((u32)((total + yk::kSqOutTile - 1) / yk::kSqOutTile)), dim3(yk::kGpT), 0, e->stream, ga);
+        }
+        ok = ok && ev_close();
+        HIP_TRY(hipMemcpyAsync((void *)h_ctl, S.ctl.p, 2 * sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipGetLastError());
+        if (!ok) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
+        if (h_ctl[0] || h_ctl[1] != total) return fail(YACRD_EINTERNAL, "sequence editor: the copy pass stored other bytes than the plan counted");
+        return YACRD_OK;
+    }
+
+    // base[0, len) in HBM -> the sink through the two pinned pieces: one flies while the other is written (host/segment_pump.h)
+    int bring_home(const char *base, u64 len)
+    {
+        struct Dma {
+            SeqRun &r;
+            const char *text;
+            bool start(u64 i, char *dst, u64 at, size_t k)
+            {
+                return hipMemcpyAsync(dst, text + at, k, hipMemcpyDeviceToHost, r.side[0]) == hipSuccess &&
+                       hipEventRecord(r.wev[i & 1], r.side[0]) == hipSuccess;
+            }
+            bool wait(u64 i) { return hipEventSynchronize(r.wev[i & 1]) == hipSuccess; }
+            void drain() { (void)hipStreamSynchronize(r.side[0]); }
+        } dma{*this, base};
+        const int rc = yseg::pump(len, kOutPiece, S.pin.as<char>(), dma, sink, [&](auto put) {
+            const double tp = now_ms();
+            put();
+            put_ms += now_ms() - tp;
+        });
+        if (rc == yseg::kLinkFailed) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed on the way home");
+        if (rc == yseg::kSinkFailed) return fail(YACRD_EINVAL, "Error during writing of the output file");
+        return YACRD_OK;
+    }
+
+    // gzip out: the output, batch by batch, through the encoder on its own stream; batch b comes home while b + 1 is encoded
+    int deflate_home()
+    {
+        const u64 per = gz.max_blocks * ydf::kBlock;
+        const size_t nb = (size_t)std::max<u64>(1, (total + per - 1) / per);
+        if (!gev.add(2 * nb) || !gdone.add(nb, hipEventDisableTiming)) HIP_TRY(why_not_added());
+        HIP_TRY(hipStreamSynchronize(e->stream)); // (gzip_device_open's memset)
+        auto encode = [&](size_t b) -> int {
+            const u64 from = (u64)b * per, len = std::min(per, total - from);
+            volatile u64 *w = h_ctl + 4 + 2 * (b & 1);
+            w[0] = w[1] = 0;
+            if (const int rc = gzip_device_encode(e, gz, side[1], S.out.as<unsigned char>() + from, len, b + 1 == nb, (int)(b & 1), gev[2 * b],
+                                                  gev[2 * b + 1], w, w + 1))
+                return rc;
+            HIP_TRY(hipEventRecord(gdone[b], side[1]));
+            gz_members += (len + ydf::kBlock - 1) / ydf::kBlock;
+            return YACRD_OK;
+        };
+        auto fetch = [&](size_t b) -> int {
+            HIP_TRY(hipEventSynchronize(gdone[b]));
+            volatile u64 *w = h_ctl + 4 + 2 * (b & 1);
+            const u64 bytes = w[0] + (b + 1 == nb ? ydf::kEofBytes : 0u);
+            if (bytes > gz.max_blocks * ydf::kSlot + ydf::kEofBytes) return fail(YACRD_EINTERNAL, "device deflate: more bytes than the members' slots hold");
+            gz_stored = w[1];
+            return bring_home(reinterpret_cast<const char *>(gz.out[b & 1]), bytes);
+        };
+        int rc = YACRD_OK;
+        for (size_t b = 0; b < nb && rc == YACRD_OK; b++) {
+            rc = encode(b);
+            if (rc == YACRD_OK && b) rc = fetch(b - 1);
+        }
+        if (rc == YACRD_OK) rc = fetch(nb - 1);
+        (void)hipStreamSynchronize(side[1]);
+        if (rc == YACRD_OK)
+            for (size_t b = 0; b < nb; b++) gz_kernel_ms += ev_ms(gev[2 * b], gev[2 * b + 1]);
+        return rc;
+    }
+
+    int deliver()
+    {
+        const double t0 = now_ms();
+        int rc = YACRD_OK;
+        if (job.gzip) rc = deflate_home();
+        else {
+            if (sink.fd < 0 && !sink.mem) { // the memory form: the size is known now
+                sink.mem = (char *)std::malloc((size_t)total + 1);
+                if (!sink.mem) return fail(YACRD_ENOMEM, "host allocation failed");
+            }
+            rc = bring_home(S.out.as<char>(), total);
+            if (rc == YACRD_OK && sink.at != total) rc = fail(YACRD_EINTERNAL, "sequence editor: fewer bytes written than counted");
+        }
+        out_busy_ms = now_ms() - t0;
+        if (rc) return rc;
+        if (job.gzip_stats) {
+            yacrd_gzip_stats &g = *job.gzip_stats;
+            g.in_bytes = total, g.out_bytes = sink.at, g.n_members = gz_members, g.n_stored = gz_stored;
+            g.h2d_ms = 0.f, g.kernel_ms = gz_kernel_ms;
+            g.d2h_ms = (float)std::max(0.0, out_busy_ms - put_ms), g.write_ms = (float)put_ms;
+        }
+        if (stats) {
+            stats->text_bytes = n, stats->out_bytes = total, stats->n_records = n_rec, stats->n_out_records = n_pieces;
+            stats->text_ms = (float)(t_text - t_table), stats->table_ms = (float)(t_table - t_start);
+            float k = 0;
+            for (size_t i = 0; i + 1 < n_ev; i += 2) k += ev_ms(ev[i], ev[i + 1]);
+            stats->kernel_ms = k, stats->out_ms = (float)out_busy_ms;
+        }
+        return YACRD_OK;
+    }
+};
+
+int run_seq_edit(yacrd_engine *e, const SeqJob &job, const TextSource &src, u64 n, Sink &sink, yacrd_seq_edit_stats *stats)
+{
+    DeviceGuard guard(e->device);
+    SeqEditScratch *S = scratch_of<SeqEditScratch>(e);
+    if (!S) return fail(YACRD_ENOMEM, "host allocation failed");
+    SeqRun r{e, job, src, n, sink, stats, *S};
+    int rc = r.plan();
+    if (rc == YACRD_OK) rc = r.upload_table();
+    if (rc == YACRD_OK) rc = r.move_and_count();
+    if (rc == YACRD_OK) rc = r.size_output();
+    if (rc == YACRD_OK) rc = r.gather();
+    if (rc == YACRD_OK) rc = r.deliver();
+    (void)hipStreamSynchronize(e->stream); // (whatever failed: nothing of this call is in flight when its events go)
+    for (hipStream_t s : r.side.v) (void)hipStreamSynchronize(s);
+    (void)hipGetLastError();
+    return rc;
+}
+
+int seq_edit_args(yacrd_engine *e, int op, const yacrd_report_table *t, yacrd_seq_edit_stats *st)
+{
+    if (!e) return fail(YACRD_EINVAL, "null argument");
+    if (!t) return fail(YACRD_EINVAL, "the FASTQ editor takes a table (the resident form is not built)");
+    if (op < 0 || op > 3) return fail(YACRD_EINVAL, "op: 0 = scrubb, 1 = filter, 2 = extract, 3 = split");
+    if (st) std::memset(st, 0, sizeof(*st));
+    if (e->pending.active || e->host_pending) return fail(YACRD_EINVAL, "the engine has a submitted batch pending");
+    return YACRD_OK;
+}
+
+// util::get_file_type by name (src/util.rs:39-55), as far as it says FASTQ
+bool named_fastq(const char *path)
+{
+    const std::string name(path);
+    auto has = [&](const char *x) { return name.find(x) != std::string::npos; };
+    if (has(".m4") || has(".mhap") || has(".paf") || has(".yacrd")) return false;
+    return has(".fastq") || has(".fq");
+}
+
+} // namespace
+
+extern "C" {
+
+int yacrd_engine_edit_fastq(yacrd_engine *e, int op, const char *in_path, const char *out_path, int n_threads, const yacrd_report_table *t,
+                            yacrd_seq_edit_stats *st)
+{
+    if (const int rca = seq_edit_args(e, op, t, st)) return rca;
+    if (!in_path || !out_path) return fail(YACRD_EINVAL, "null argument");
+    if (!named_fastq(in_path)) return fail(YACRD_EFALLBACK, "not a FASTQ file by its name: the host loop's case");
+    const int fd = ::open(in_path, O_RDONLY);
+    if (fd < 0) return fail(YACRD_EFALLBACK, std::string("cannot open ") + in_path + ": the host loop words the error");
+    FdGuard fdg{fd};
+    struct stat sst, ost;
+    if (fstat(fd, &sst) != 0 || !S_ISREG(sst.st_mode)) return fail(YACRD_EFALLBACK, "not a regular file: the host loop reads it");
+    if (is_compressed_magic(fd)) return fail(YACRD_EFALLBACK, "a compressed file: inflate it and take the gzip form, or the host loop");
+    if (lstat(out_path, &ost) == 0) {
+        if (!S_ISREG(ost.st_mode)) return fail(YACRD_EFALLBACK, "the output is not a regular file: the host loop writes it");
+        if (ost.st_dev == sst.st_dev && ost.st_ino == sst.st_ino) return fail(YACRD_EFALLBACK, "input and output are one file: the host loop's case");
+    }
+    // written beside its place and moved there when every byte is in it: a text that is not for this path leaves nothing behind
+    yseg::BesideFile file;
+    if (!file.open(out_path)) return fail(YACRD_EFALLBACK, std::string("cannot create a file beside ") + out_path + ": the host loop words the error");
+    SeqJob job;
+    job.op = op, job.n_threads = n_threads, job.table = t;
+    TextSource src;
+    src.fd = fd;
+    Sink sink;
+    sink.fd = file.fd;
+    int rc = run_seq_edit(e, job, src, (u64)sst.st_size, sink, st);
+    if (rc == YACRD_OK && !file.commit()) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
+    if (rc != YACRD_OK && st) std::memset(st, 0, sizeof(*st));
+    return rc;
+}
+
+int yacrd_engine_edit_fastq_mem(yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, char **out, uint64_t *out_bytes,
+                                yacrd_seq_edit_stats *st)
+{
+    if (const int rca = seq_edit_args(e, op, t, st)) return rca;
+    if ((!text && n) || !out || !out_bytes) return fail(YACRD_EINVAL, "null argument");
+    *out = nullptr, *out_bytes = 0;
+    SeqJob job;
+    job.op = op, job.table = t;
+    TextSource src;
+    src.mem = text ? text : "";
+    Sink sink;
+    const int rc = run_seq_edit(e, job, src, n, sink, st);
+    if (rc != YACRD_OK) {
+        std::free(sink.mem);
+        if (st) std::memset(st, 0, sizeof(*st));
+        return rc;
+    }
+    *out = sink.mem, *out_bytes = sink.at;
+    return YACRD_OK;
+}
+
+int yacrd_engine_edit_fastq_gzip_mem(yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, char **out,
+                                     uint64_t *out_bytes, yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs)
+{
+    if (gs) std::memset(gs, 0, sizeof(*gs));
+    if (const int rca = seq_edit_args(e, op, t, st)) return rca;
+    if ((!text && n) || !out || !out_bytes) return fail(YACRD_EINVAL, "null argument");
+    *out = nullptr, *out_bytes = 0;
+    SeqJob job;
+    job.op = op, job.table = t, job.gzip = true, job.gzip_stats = gs;
+    TextSource src;
+    src.mem = text ? text : "";
+    Sink sink;
+    sink.cap = (size_t)(n / 3 + 4096); // (the sink grows when the members need more)
+    sink.mem = (char *)std::malloc((size_t)sink.cap);
+    if (!sink.mem) return fail(YACRD_ENOMEM, "host allocation failed");
+    const int rc = run_seq_edit(e, job, src, n, sink, st);
+    if (rc != YACRD_OK) {
+        std::free(sink.mem);
+        if (st) std::memset(st, 0, sizeof(*st));
+        if (gs) std::memset(gs, 0, sizeof(*gs));
+        return rc;
+    }
+    *out = sink.mem, *out_bytes = sink.at;
+    return YACRD_OK;
+}
+
+int yacrd_engine_edit_fastq_gzip_file(yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, const char *out_path,
+                                      yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs)
+{
+    if (gs) std::memset(gs, 0, sizeof(*gs));
+    if (const int rca = seq_edit_args(e, op, t, st)) return rca;
+    if ((!text && n) || !out_path) return fail(YACRD_EINVAL, "null argument");
+    struct stat ost;
+    if (lstat(out_path, &ost) == 0 && !S_ISREG(ost.st_mode)) return fail(YACRD_EFALLBACK, "the output is not a regular file: the host loop writes it");
+    yseg::BesideFile file;
+    if (!file.open(out_path)) return fail(YACRD_EFALLBACK, std::string("cannot create a file beside ") + out_path + ": the host loop words the error");
+    SeqJob job;
+    job.op = op, job.table = t, job.gzip = true, job.gzip_stats = gs;
+    TextSource src;
+    src.mem = text ? text : "";
+    Sink sink;
+    sink.fd = file.fd;
+    int rc = run_seq_edit(e, job, src, n, sink, st);
+    if (rc == YACRD_OK && !file.commit()) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
+    if (rc != YACRD_OK) {
+        if (st) std::memset(st, 0, sizeof(*st));
+        if (gs) std::memset(gs, 0, sizeof(*gs));
+    }
+    return rc;
+}
+
+} // extern "C"

@@ -1,5 +1,5 @@
 // gpu_text.h — what the translation units that work on TEXT in HBM share: gpu_paf.hip (the device parser), gpu_edit.hip
-// (filter / extract on overlap files), gpu_report.hip (the report reader) and gpu_deflate.hip.  Where the text comes from
+// (filter / extract on overlap files), gpu_seq_edit.hip (the FASTQ editors), gpu_report.hip (the report reader) and gpu_deflate.hip.  Where the text comes from
 // (TextSource, FdGuard, the format rule), the mover (pread -> pinned 4 MiB chunks -> the mirror in HBM, a segment handed on
 // as soon as it has landed), the staged-window accessor, the byte matcher and the id hash; what an ingest's outputs share.
 #pragma once

@@ -401,6 +401,55 @@ int main(int argc, char **argv)
                              (unsigned long long)es.n_kept, (unsigned long long)es.n_lines, (unsigned long long)es.kept_bytes,
                              (unsigned long long)es.text_bytes, es.text_ms, es.table_ms, es.kernel_ms, es.out_ms, es.mirror_reused);
         }
+        // All four sub-commands on a FASTQ: the text goes to HBM, the device cuts it into records, decides, sizes and gathers the
+        // output (yacrd_engine_edit_fastq).  A gzip FASTQ is inflated here — BGZF member-parallel; the detection's text when it
+        // read this very file — and the output is deflated where the device gathers it: only BGZF members come back
+        // (yacrd_engine_edit_fastq_gzip_file).  Whatever that path does not take — anything but canonical four-line records, a
+        // cut position beyond its read — comes back with nothing written and takes the host loop below, which owns the syntax
+        // and the messages.  FASTA, bzip2 / xz, YACRD_NO_DEVICE_EDITOR=1 (and, for gzip, YACRD_NO_DEVICE_DEFLATE=1): the host.
+        const bool sub_fq = !sub_ovl && !has(sub_in, ".yacrd") && (has(sub_in, ".fastq") || has(sub_in, ".fq")) && !(no_ed && *no_ed == '1');
+        const int sub_comp = sub_fq ? yacrd_file_compression(sub_in.c_str()) : -1;
+        if (sub_fq && (sub_comp == 0 || (sub_comp == 1 && !(no_df && *no_df == '1')))) {
+            const yacrd_report_table rt = {bp.n_reads, bp.name_off, bp.names, bp.lengths, bp.bad_offsets, bp.bad_regions, bp.read_type};
+            yacrd_seq_edit_stats ss{};
+            yacrd_gzip_stats gs{};
+            double inflate_ms = 0;
+            bool text_reused = false;
+            if (sub_comp == 1) {
+                const auto t_in = std::chrono::steady_clock::now();
+                yacrd_text own{};
+                const yacrd_text *tx = nullptr;
+                struct stat sa, sb;
+                if (text.data && ::stat(input.c_str(), &sa) == 0 && ::stat(sub_in.c_str(), &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino)
+                    tx = &text, text_reused = true;
+                else if (yacrd_text_from_file(sub_in.c_str(), threads == 1 ? 0 : (int)threads, &own) == 0)
+                    tx = &own; // (a file that cannot be inflated: the host loop below words the error)
+                inflate_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count();
+                if (tx) dev_edit = yacrd_engine_edit_fastq_gzip_file(engines[0], op, tx->data, tx->n, &rt, sub_out.c_str(), &ss, &gs);
+                yacrd_text_free(&own);
+            } else {
+                const char *ct = std::getenv("YACRD_COPY_THREADS");
+                dev_edit = yacrd_engine_edit_fastq(engines[0], op, sub_in.c_str(), sub_out.c_str(), ct && *ct ? std::max(0, std::atoi(ct)) : 0, &rt, &ss);
+            }
+            if (dev_edit == YACRD_ENOMEM) {
+                std::fprintf(stderr, "[INFO] device fastq editor: %s; falling back to the host loop\n", yacrd_last_error());
+                for (yacrd_engine *en : engines) (void)yacrd_engine_trim(en);
+                dev_edit = YACRD_EFALLBACK;
+            }
+            if (dev_edit != YACRD_OK && dev_edit != YACRD_EFALLBACK) die(yacrd_last_error());
+            if (dev_edit == YACRD_OK && timing) {
+                std::fprintf(stderr, "[info] device fastq editor: %llu records -> %llu, %llu bytes -> %llu bytes, text %.1f ms, table %.1f ms, "
+                                     "kernels %.1f ms, out %.1f ms\n",
+                             (unsigned long long)ss.n_records, (unsigned long long)ss.n_out_records, (unsigned long long)ss.text_bytes,
+                             (unsigned long long)ss.out_bytes, ss.text_ms, ss.table_ms, ss.kernel_ms, ss.out_ms);
+                if (sub_comp == 1) // (the encoder's line as the host loop's writer words it: the output lay in HBM, nothing went up)
+                    std::fprintf(stderr, "[info] device deflate: %llu -> %llu bytes, %llu members (%llu stored), h2d %.1f ms, kernels %.1f ms, "
+                                         "d2h %.1f ms, write %.1f ms, inflate %.1f ms, text_reused=%d\n",
+                                 (unsigned long long)gs.in_bytes, (unsigned long long)gs.out_bytes, (unsigned long long)gs.n_members,
+                                 (unsigned long long)gs.n_stored, gs.h2d_ms, gs.kernel_ms, gs.d2h_ms, gs.write_ms, text_reused ? 0.0 : inflate_ms,
+                                 text_reused ? 1 : 0);
+            }
+        }
         // A gzip input writes gzip (the reference's contract): the host loop inflates and edits as before, and the edited bytes
         // leave through a yacrd_gzip_writer — compressed on the device into BGZF — instead of zlib's one thread.  No memory for
         // it, bzip2 / xz, YACRD_NO_DEVICE_DEFLATE=1: the host path below, unchanged.

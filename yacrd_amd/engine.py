@@ -47,6 +47,7 @@ EXPORTED_SYMBOLS = [
     "yacrd_engine_ingest_report", "yacrd_engine_ingest_report_mem", "yacrd_engine_write_report", "yacrd_engine_write_report_mem",
     "yacrd_engine_edit_overlaps", "yacrd_engine_edit_overlaps_mem", "yacrd_edit_text_free",
     "yacrd_engine_edit_overlaps_gzip_mem", "yacrd_engine_edit_overlaps_gzip_file",
+    "yacrd_engine_edit_fastq", "yacrd_engine_edit_fastq_mem", "yacrd_engine_edit_fastq_gzip_mem", "yacrd_engine_edit_fastq_gzip_file",
     "yacrd_engine_gzip_mem", "yacrd_gzip_writer_open", "yacrd_gzip_writer_write", "yacrd_gzip_writer_sink", "yacrd_gzip_writer_close",
     "yacrd_gzip_writer_abort",
     "yacrd_stream_device_of", "yacrd_stream_group_open", "yacrd_stream_group_sink", "yacrd_stream_group_finish",
@@ -93,6 +94,11 @@ class _TypeTable(ctypes.Structure):
 class _EditStats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("text_bytes", "kept_bytes", "n_lines", "n_kept")] + \
                [(n, ctypes.c_float) for n in ("text_ms", "table_ms", "kernel_ms", "out_ms")] + [("mirror_reused", ctypes.c_uint32)]
+
+
+class _SeqEditStats(ctypes.Structure):  # yacrd_seq_edit_stats
+    _fields_ = [(n, ctypes.c_uint64) for n in ("text_bytes", "out_bytes", "n_records", "n_out_records")] + \
+               [(n, ctypes.c_float) for n in ("text_ms", "table_ms", "kernel_ms", "out_ms")]
 
 
 class _GzipStats(ctypes.Structure):
@@ -319,6 +325,18 @@ def load_library():
                                                          ctypes.POINTER(_TypeTable), ctypes.c_char_p, ctypes.POINTER(_EditStats),
                                                          ctypes.POINTER(_GzipStats)]
     lib.yacrd_edit_text_free.argtypes = [ctypes.c_void_p]
+    lib.yacrd_engine_edit_fastq.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int,
+                                            ctypes.POINTER(_ReportTable), ctypes.POINTER(_SeqEditStats)]
+    lib.yacrd_engine_edit_fastq_mem.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(_ReportTable),
+                                                ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64),
+                                                ctypes.POINTER(_SeqEditStats)]
+    lib.yacrd_engine_edit_fastq_gzip_mem.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+                                                     ctypes.POINTER(_ReportTable), ctypes.POINTER(ctypes.c_void_p),
+                                                     ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_SeqEditStats),
+                                                     ctypes.POINTER(_GzipStats)]
+    lib.yacrd_engine_edit_fastq_gzip_file.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+                                                      ctypes.POINTER(_ReportTable), ctypes.c_char_p, ctypes.POINTER(_SeqEditStats),
+                                                      ctypes.POINTER(_GzipStats)]
     lib.yacrd_edit_text_free.restype = None
     lib.yacrd_engine_gzip_mem.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p),
                                           ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_GzipStats)]
@@ -760,6 +778,81 @@ class Engine:
         self.gzip_stats = {f: getattr(gs, f) for f, _ in _GzipStats._fields_}
         if out_path is not None:
             return self.edit_stats, self.gzip_stats
+        try:
+            return ctypes.string_at(out.value, int(n_out.value))
+        finally:
+            self._lib.yacrd_edit_text_free(out)
+
+    def _seq_table(self, names, lengths, result):
+        """(names, lengths, result) -> a yacrd_report_table for the FASTQ editor; result: what run / ingest_* return, or a
+        triple (bad_offsets, bad_regions, read_type)."""
+        if isinstance(result, (tuple, list)) and not hasattr(result, "bad_offsets"):
+            bo, br, rt = result
+
+            class _R:
+                bad_offsets, bad_regions, read_type = bo, br, rt
+            result = _R
+        if len(names) == 0:  # (nothing to look up: every record is NotBad without a region)
+            result = type("_E", (), {"bad_offsets": np.zeros(1, np.uint64), "bad_regions": np.zeros(0, np.uint32),
+                                     "read_type": np.zeros(0, np.uint8)})
+        return self._report_table(names, lengths, result)
+
+    def _seq_edited(self, rc, st):
+        if rc == E_FALLBACK:
+            raise NeedsHostParser(self._lib.yacrd_last_error().decode())
+        _check(self._lib, rc)
+        self.seq_edit_stats = {n: getattr(st, n) for n, _ in _SeqEditStats._fields_}
+        return self.seq_edit_stats
+
+    def edit_fastq(self, op, src, out_path, names, lengths, result, n_threads=0):
+        """yacrd_engine_edit_fastq: scrubb (op 0) / filter (1) / extract (2) / split (3) the plain FASTQ file `src` into
+        `out_path` on the GPU, by the table (names, lengths, result); returns the stats (also self.seq_edit_stats).  Raises
+        NeedsHostParser, with nothing written, when the input is the host loop's (host.edit_file)."""
+        t, keep = self._seq_table(names, lengths, result)
+        st = _SeqEditStats()
+        rc = self._lib.yacrd_engine_edit_fastq(self._h, int(op), os.fsencode(src), os.fsencode(out_path), int(n_threads), t, ctypes.byref(st))
+        del keep
+        return self._seq_edited(rc, st)
+
+    def edit_fastq_text(self, op, text, names, lengths, result):
+        """yacrd_engine_edit_fastq_mem: the same over `text` (bytes or anything else with the buffer protocol, which is not
+        copied) -> the output's bytes; the stats are in self.seq_edit_stats."""
+        t, keep = self._seq_table(names, lengths, result)
+        st = _SeqEditStats()
+        buf = np.frombuffer(text, dtype=np.uint8)
+        n = int(buf.size)
+        out, n_out = ctypes.c_void_p(), ctypes.c_uint64()
+        rc = self._lib.yacrd_engine_edit_fastq_mem(self._h, int(op), ctypes.c_void_p(buf.ctypes.data if n else None), n, t,
+                                                   ctypes.byref(out), ctypes.byref(n_out), ctypes.byref(st))
+        del keep, buf
+        self._seq_edited(rc, st)
+        try:
+            return ctypes.string_at(out.value, int(n_out.value)) if n_out.value else b""
+        finally:
+            self._lib.yacrd_edit_text_free(out)
+
+    def edit_fastq_gzip(self, op, text, names, lengths, result, out_path=None):
+        """yacrd_engine_edit_fastq_gzip_mem / _file: the same over the inflated FASTQ `text` with the output deflated on the
+        device where it is gathered.  Without out_path -> the BGZF stream (bytes: what gzip() gives for edit_fastq_text's
+        bytes); with it the stream is written there and (seq edit stats, gzip stats) returned.  Both are also in
+        self.seq_edit_stats and self.gzip_stats.  Raises NeedsHostParser, with nothing written, when the text is the host loop's."""
+        t, keep = self._seq_table(names, lengths, result)
+        st, gs = _SeqEditStats(), _GzipStats()
+        buf = np.frombuffer(text, dtype=np.uint8)
+        n = int(buf.size)
+        addr = ctypes.c_void_p(buf.ctypes.data if n else None)
+        out, n_out = ctypes.c_void_p(), ctypes.c_uint64()
+        if out_path is None:
+            rc = self._lib.yacrd_engine_edit_fastq_gzip_mem(self._h, int(op), addr, n, t, ctypes.byref(out), ctypes.byref(n_out),
+                                                            ctypes.byref(st), ctypes.byref(gs))
+        else:
+            rc = self._lib.yacrd_engine_edit_fastq_gzip_file(self._h, int(op), addr, n, t, os.fsencode(out_path), ctypes.byref(st),
+                                                             ctypes.byref(gs))
+        del keep, buf
+        self._seq_edited(rc, st)
+        self.gzip_stats = {f: getattr(gs, f) for f, _ in _GzipStats._fields_}
+        if out_path is not None:
+            return self.seq_edit_stats, self.gzip_stats
         try:
             return ctypes.string_at(out.value, int(n_out.value))
         finally:
