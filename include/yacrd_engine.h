@@ -590,6 +590,34 @@ int yacrd_engine_edit_fastq_gzip_file(yacrd_engine *e, int op, const char *text,
                                       const char *out_path, yacrd_seq_edit_stats *st /* may be NULL */,
                                       yacrd_gzip_stats *gs /* may be NULL */);
 
+/* ---- the same on a FASTA file (csrc/gpu_seq_edit.hip) ---------------------------------------------------------------------
+ * A line that begins with '>' starts a record; its name is the header up to the first blank, tab or form feed, its
+ * description everything behind that one byte, its sequence every line up to the next '>' line, concatenated (blank lines
+ * add nothing; blank lines in front of the first header are skipped).  The key is the whole name.  Every record that goes out
+ * is written again: a copied record is `>{name}[ {desc}]` (the separator a blank, dropped with an empty description), a cut
+ * piece `>{name}_{p0}_{p1}` without description; the sequence or its slice follows 80 bases a line, nothing for an empty one.
+ * The bytes are those of yacrd_edit_file on the same input and table.  The device marks the header lines, scans them into
+ * record ordinals and the other lines' lengths into base ordinals, plans per record and gathers per 4 KiB of output: an output
+ * base is found in the input by arithmetic when its record's lines have one width, else by a search over the record's lines.
+ * Arguments, stats, the file form's rename, the _mem buffers and the gzip forms' stream: as the four calls above.
+ * YACRD_EFALLBACK, with nothing written and nothing left beside out_path: a CR anywhere; a last line without its newline; a
+ * line that is not blank in front of the first header; a header without a name (`>`, `> desc`: stricter than the host, which
+ * writes them back); a cut position beyond the record's sequence or a region with begin > end; 2^31 records or output records;
+ * a record, or a read's output, of 0xFF000000 bytes or more; to the file form a compressed or non-regular input, a name that
+ * yacrd_edit_file would not take for FASTA (.fastq / .fq / .paf / .m4 / .mhap / .yacrd win over .fa) and an out_path that is
+ * the input or no regular file; text, line tables (32 bytes a line) and output beyond the device's free memory.
+ * An empty text and a text of blank lines are an empty output. */
+int yacrd_engine_edit_fasta(yacrd_engine *e, int op, const char *in_path, const char *out_path, int n_threads,
+                            const yacrd_report_table *t, yacrd_seq_edit_stats *st /* may be NULL */);
+int yacrd_engine_edit_fasta_mem(yacrd_engine *e, int op, const char *text, uint64_t n_bytes, const yacrd_report_table *t,
+                                char **out, uint64_t *out_bytes, yacrd_seq_edit_stats *st /* may be NULL */);
+int yacrd_engine_edit_fasta_gzip_mem(yacrd_engine *e, int op, const char *text, uint64_t n_bytes, const yacrd_report_table *t,
+                                     char **out, uint64_t *out_bytes, yacrd_seq_edit_stats *st /* may be NULL */,
+                                     yacrd_gzip_stats *gs /* may be NULL */);
+int yacrd_engine_edit_fasta_gzip_file(yacrd_engine *e, int op, const char *text, uint64_t n_bytes, const yacrd_report_table *t,
+                                      const char *out_path, yacrd_seq_edit_stats *st /* may be NULL */,
+                                      yacrd_gzip_stats *gs /* may be NULL */);
+
 /* Copy the last device result to host (allocates like yacrd_engine_run). */
 int yacrd_engine_fetch(yacrd_engine *e, yacrd_result *out);
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/edit_fastq_bench.py --parent-bin PATH [--reads R] [--overlaps O] [--runs K] [--ops scrubb,filter] [--forms plain,gzip1,bgzf] [--json PATH]
+"""tools/edit_fastq_bench.py --parent-bin PATH [--fasta] [--reads R] [--overlaps O] [--runs K] [--ops scrubb,filter] [--forms plain,gzip1,bgzf] [--json PATH]
 scrubb / filter on a FASTQ through the COMMAND, the parent commit's `yacrd` against this tree's, on a synthetic Sequel FASTQ
 (50 000 reads: about 1 GB) in /dev/shm, output there too:
     yacrd -i s.paf -o r.yacrd -c 3 -n 0.4 <op> -i reads.fastq[.gz] -o out.fastq[.gz]
@@ -11,7 +11,9 @@ removed before the clock starts:
                for gzip the file inflated member-parallel and the output deflated where it lies
 The figures compared are the `edit` stage of YACRD_CLI_TIMING — slowest (b) against fastest (a) — and the wall clock.  Every
 output is compared with the parent's (gzip: the inflated bytes when the streams differ).  One JSON line per op and form,
-appended to --json (default profiles/edit_fastq.json)."""
+appended to --json (default profiles/edit_fastq.json).
+--fasta: the same reads as FASTA, 80 bases a line (reads.fasta[.gz]): the device path is yacrd_engine_edit_fasta, its line
+"[info] device fasta editor:", the default --json profiles/edit_fasta.json."""
 import argparse, gzip, json, os, re, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -25,14 +27,29 @@ ap.add_argument("--runs", type=int, default=3)
 ap.add_argument("--ops", default="scrubb,filter")
 ap.add_argument("--forms", default="plain,gzip1,bgzf")
 ap.add_argument("--parent-bin", default=None)
-ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "edit_fastq.json"))
+ap.add_argument("--fasta", action="store_true")
+ap.add_argument("--json", default=None)
 a = ap.parse_args()
+kind = "fasta" if a.fasta else "fastq"
+a.json = a.json or os.path.join(ROOT, "profiles", "edit_%s.json" % kind)
+editor_line = "[info] device %s editor:" % kind
 if not a.parent_bin or not os.access(a.parent_bin, os.X_OK):
     sys.exit("--parent-bin: the yacrd binary built from the parent commit")
 new_bin = os.path.join(ROOT, "yacrd_amd", "bin", "yacrd")
 d = os.environ.get("YACRD_EDIT_BENCH_DIR", "/dev/shm")
 tag = os.path.join(d, "yacrd_efb_%d_" % os.getpid())
 paf, fq, rep = tag + "s.paf", tag + "s.fastq", tag + "r.yacrd"
+
+
+def to_fasta(src, dst):
+    """the FASTQ's records as FASTA, 80 bases a line"""
+    with open(src, "rb") as f, open(dst, "wb") as g:
+        while True:
+            head, seq = f.readline(), f.readline().rstrip(b"\n")
+            if not head:
+                return
+            f.readline(), f.readline()
+            g.write(b">" + head[1:] + b"".join(seq[i:i + 80] + b"\n" for i in range(0, len(seq), 80)))
 
 
 def fresh(path):
@@ -62,7 +79,7 @@ def run(binary, op, src, out):
         wall = time.perf_counter() - t0
         assert p.returncode == 0, p.stderr
         stages = dict(re.findall(r"^\[timing\] (\S+) ([0-9.]+) s$", p.stderr, re.M))
-        info = [l for l in p.stderr.splitlines() if l.startswith("[info] device fastq editor:") or l.startswith("[info] device deflate:")]
+        info = [l for l in p.stderr.splitlines() if l.startswith(editor_line) or l.startswith("[info] device deflate:")]
         row = {"edit_s": float(stages["edit"]), "wall_s": round(wall, 3), "info": info}
         if k:
             rows.append(row)
@@ -74,9 +91,14 @@ try:
     seed = 20241108 + 5
     host.synth_paf(host.SYNTH_SEQUEL, a.reads, a.overlaps, seed, paf)
     host.synth_fastq(host.SYNTH_SEQUEL, a.reads, a.overlaps, seed, a.reads // 200, fq)
+    if a.fasta:
+        to_fasta(fq, tag + "s.fasta")
+        fresh(fq)
+        fq = tag + "s.fasta"
+        made.append(fq)
     size = os.path.getsize(fq)
     for form in a.forms.split(","):
-        ext = ".fastq" if form == "plain" else ".fastq.gz"
+        ext = "." + kind if form == "plain" else "." + kind + ".gz"
         src = fq if form == "plain" else tag + form + ext
         if form == "gzip1":
             with open(src, "wb") as f:
@@ -94,10 +116,10 @@ try:
             made.extend([old, new])
             parent = run(a.parent_bin, op, src, old)
             mine = run(new_bin, op, src, new)
-            assert any(l.startswith("[info] device fastq editor:") for l in mine[-1]["info"]), "the device editor did not run"
+            assert any(l.startswith(editor_line) for l in mine[-1]["info"]), "the device editor did not run"
             assert same(old, new, False) or (form != "plain" and same(old, new, True)), "the new path's output differs from the parent's"
             worst_new, best_old = max(r["edit_s"] for r in mine), min(r["edit_s"] for r in parent)
-            row = {"reads": a.reads, "overlaps": a.overlaps, "op": op, "form": form, "text_bytes": size, "in_bytes": os.path.getsize(src),
+            row = {"kind": kind, "reads": a.reads, "overlaps": a.overlaps, "op": op, "form": form, "text_bytes": size, "in_bytes": os.path.getsize(src),
                    "out_bytes": os.path.getsize(new), "parent": parent, "new": mine, "edit_stage_slowest_new_s": worst_new,
                    "edit_stage_fastest_parent_s": best_old, "ratio": round(best_old / worst_new, 2),
                    "wall_slowest_new_s": max(r["wall_s"] for r in mine), "wall_fastest_parent_s": min(r["wall_s"] for r in parent)}

@@ -1,5 +1,6 @@
-// gpu_seq_edit.hip — scrubb / split / filter / extract on a FASTQ file with the decision, the sizing and the gather on the GPU
-// (include/yacrd_engine.h: yacrd_engine_edit_fastq).
+// gpu_seq_edit.hip — scrubb / split / filter / extract on a FASTQ or FASTA file with the decision, the sizing and the gather on the GPU
+// (include/yacrd_engine.h: yacrd_engine_edit_fastq, yacrd_engine_edit_fasta).  FASTQ first; what FASTA does otherwise stands
+// in front of its kernels below: it shares the mover, the line index, the id table, the way home and the deflate step.
 //
 // Reference: Scrubbing::run (src/editor/scrubbing.rs:156-236), Split::run (src/editor/split.rs), Filter::run and Extract::run on
 // sequence files: a record's key — the first whitespace token of its name — is looked up in the bad-part table (an id it does not
@@ -331,6 +332,35 @@ __device__ __forceinline__ void sq_at(const SqArgs &a, const SqPiece &p, u32 k, 
     if (k < L) src = rec + p.qual_rel + p.p0 + k, rem = L - k; // (else: the record's last newline)
 }
 
+// the composed tile -> the output, 16 bytes per thread; the bytes the workgroup composed -> ctl[1], one add per workgroup
+__device__ __forceinline__ void sq_store_tile(unsigned char *out, u64 total, unsigned long long *ctl, const u32 *tile, u32 *sw, u64 tile0, u32 stored)
+{
+    __syncthreads();
+    const u64 o = tile0 + (u64)threadIdx.x * 16u;
+    if (o < total) *reinterpret_cast<uint4 *>(out + o) = *reinterpret_cast<const uint4 *>(tile + threadIdx.x * 4u);
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) stored += (u32)__shfl_xor((int)stored, d, 64);
+    if (lane_id() == 0) sw[threadIdx.x >> 6] = stored;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u32 tot = 0;
+#pragma unroll
+        for (int w = 0; w < kGpT / 64; w++) tot += sw[w];
+        atomicAdd(ctl + 1, (unsigned long long)tot);
+    }
+}
+
+// four bytes of one run of text: the aligned words that hold them (the word behind begins inside the run when it is read)
+__device__ __forceinline__ u32 sq_load4(const unsigned char *src)
+{
+    const uintptr_t ad = reinterpret_cast<uintptr_t>(src);
+    const u32 *al = reinterpret_cast<const u32 *>(ad & ~(uintptr_t)3);
+    const u32 sh = (u32)(ad & 3u) * 8u;
+    u32 word = al[0];
+    if (sh) word = (word >> sh) | (al[1] << (32u - sh));
+    return word;
+}
+
 // ---- copy: a tile of the output, composed in LDS, stored 16 bytes wide -----------------------------------------------------------
 // Thread t composes words t, t + 256, t + 512 and t + 768 of the tile, so that a wavefront's loads from a run of text are
 // consecutive words; it then stores bytes [16 t, 16 t + 16).  The output buffer is padded to whole 16-byte pieces (the
@@ -366,11 +396,7 @@ __global__ __launch_bounds__(kGpT) void sq_copy_kernel(SqArgs a)
                 u32 rem, lit;
                 sq_at(a, p, (u32)(jj - p.out), src, rem, lit);
                 if (src && b == 0 && rem >= 4u) { // four bytes of one run: the aligned words that hold them
-                    const uintptr_t ad = reinterpret_cast<uintptr_t>(src);
-                    const u32 *al = reinterpret_cast<const u32 *>(ad & ~(uintptr_t)3);
-                    const u32 sh = (u32)(ad & 3u) * 8u;
-                    word = al[0];
-                    if (sh) word = (word >> sh) | (al[1] << (32u - sh)); // (al + 1 begins inside the run)
+                    word = sq_load4(src);
                     b = 4, stored += 4;
                 } else {
                     word |= (src ? (u32)*src : lit) << (8u * b);
@@ -380,19 +406,309 @@ __global__ __launch_bounds__(kGpT) void sq_copy_kernel(SqArgs a)
         }
         tile[w * (u32)kGpT + threadIdx.x] = word;
     }
-    __syncthreads();
-    const u64 o = tile0 + (u64)threadIdx.x * 16u;
-    if (o < a.total) *reinterpret_cast<uint4 *>(a.out + o) = *reinterpret_cast<const uint4 *>(tile + threadIdx.x * 4u);
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) stored += (u32)__shfl_xor((int)stored, d, 64);
-    if (lane_id() == 0) sw[threadIdx.x >> 6] = stored;
-    __syncthreads();
-    if (threadIdx.x == 0) { // one add per workgroup
-        u32 tot = 0;
-#pragma unroll
-        for (int w = 0; w < kGpT / 64; w++) tot += sw[w];
-        atomicAdd(a.ctl + 1, (unsigned long long)tot);
+    sq_store_tile(a.out, a.total, a.ctl, tile, sw, tile0, stored);
+}
+
+// ==== FASTA (yacrd_engine_edit_fasta) ===========================================================================================
+// A record is a '>' line and every line up to the next one; its sequence is those lines without their newlines, and every
+// record that goes out — copied or cut — is written again, 80 bases a line (host/editors.cc: next_fasta, write_fasta).  Behind
+// the line index of the FASTQ path:
+//   mark     a thread per line: head[g] (the line begins with '>'), bases[g] (0 for a header, else the line's length)
+//   scans    head -> the record ordinal of every line; bases -> base_before[g], the bases of the whole text in front of line g
+//   heads    rec_line[r] = the line of header r; a line with bases and no header in front of it is the host loop's error
+//   widths   a thread per line: rec_width[r] = the one width of record r's lines, 0 when a line does not fit
+//   plan     a thread per record: name, separator, description; the name looked up; the op's rule; pieces and bytes counted
+//   pieces   the same walk writes the descriptors
+//   copy     a workgroup per 4 KiB of the output: byte k of a body is row k / 81, column k % 81 — column 80 and the last byte
+//            are newlines, every other byte is base p0 + 80 row + column of the record: the last line of the record whose
+//            base_before is not beyond that base holds it.  A thread keeps the line it last read from, tries the one behind
+//            it and searches what is left of the record otherwise (a walk forward from the tile's first search measured
+//            slower: 3.22 against 2.93 ms); a record whose lines all have one width is addressed without the tables (fa_widths_kernel)
+constexpr u32 kFaWidth = 80; // noodles::fasta::Writer's line
+
+struct FaPiece { // one record of the output
+    u64 out;     // where its first byte goes
+    u64 hdr;     // the input record's '>'
+    u64 base0;   // the ordinal, in the whole text, of the record's first base
+    u64 line0, line1; // the record's lines behind its header
+    u32 len;     // its bytes
+    u32 flags;   // kSqCopy: the whole record with its description; else the piece [p0, p1) named name_p0_p1
+    u32 name_len, desc_len;
+    u32 p0, p1;
+    u32 width;   // every line of the record but the last holds this many bases, the last 1 to `width`; 0: its lines differ
+    u32 pad;
+};
+static_assert(sizeof(FaPiece) == 72, "host code sizes the piece buffer by this");
+
+struct FaArgs {
+    const unsigned char *text;
+    EdTable tab;
+    const u32 *lengths;
+    const u64 *bad_off;
+    const u32 *bad_reg;
+    const u64 *line_end;    // [n_lines]
+    u32 *head, *bases;      // [n_lines]
+    const u64 *line_rec;    // [n_lines + 1]: headers in front of line g
+    const u64 *base_before; // [n_lines + 1]
+    u64 *rec_line;          // [n_rec + 1]: the line of header r; n_lines closes the list
+    u32 *rec_width;         // [n_rec]: the one width of the record's lines, or 0 (fa_widths_kernel)
+    u64 n_lines, n_rec;
+    u32 *rec_pieces, *rec_bytes;
+    const u64 *piece_off, *byte_off;
+    FaPiece *pieces;
+    u64 n_pieces, total;
+    unsigned char *out;
+    unsigned long long *ctl;
+    u32 op;
+};
+
+__global__ __launch_bounds__(256) void fa_mark_kernel(FaArgs a)
+{
+    const u64 g = (u64)blockIdx.x * 256u + threadIdx.x;
+    u32 status = 0;
+    if (g < a.n_lines) {
+        const u64 s = g ? a.line_end[g - 1] + 1 : 0, len = a.line_end[g] - s;
+        const bool head = len && a.text[s] == '>';
+        if (len >= kSqMaxRecord) status = kSqNeedHost;
+        a.head[g] = head ? 1u : 0u;
+        a.bases[g] = head || status ? 0u : (u32)len;
     }
+    status = wave_or(status);
+    if (status && lane_id() == 0) atomicOr(a.ctl, (unsigned long long)status);
+}
+
+__global__ __launch_bounds__(256) void fa_heads_kernel(FaArgs a)
+{
+    const u64 g = (u64)blockIdx.x * 256u + threadIdx.x;
+    u32 status = 0;
+    if (g < a.n_lines) {
+        if (a.head[g]) {
+            a.rec_line[a.line_rec[g]] = g;
+            a.rec_width[a.line_rec[g]] = g + 1 < a.n_lines && !a.head[g + 1] ? a.bases[g + 1] : 0u; // (its first line's; fa_widths_kernel)
+        } else if (a.bases[g] && a.line_rec[g] == 0) status = kSqNeedHost; // bases in front of the first header
+        if (g == 0) a.rec_line[a.n_rec] = a.n_lines;
+    }
+    status = wave_or(status);
+    if (status && lane_id() == 0) atomicOr(a.ctl, (unsigned long long)status);
+}
+
+// The one width of a record's lines, or 0: every line but the last holds as many bases as the first, the last 1 to as many,
+// none is blank.  A record that has it needs no search: base b lies at byte b / w * (w + 1) + b % w of its sequence lines.
+// A thread per line, which clears its record's width when the line does not fit: a record of millions of lines costs what
+// its lines cost anywhere else.  Measured on 400 MB of reads wrapped at 80, scrubb / filter: the closed form took the
+// kernels from 2.93 / 2.13 ms to 2.1 / 1.6 ms.
+__global__ __launch_bounds__(256) void fa_widths_kernel(FaArgs a)
+{
+    const u64 g = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (g >= a.n_lines || a.head[g] || a.line_rec[g] == 0) return;
+    const u64 r = a.line_rec[g] - 1, l0 = a.rec_line[r], l1 = a.rec_line[r + 1];
+    const u32 w = a.bases[l0 + 1], n = a.bases[g]; // (l0 + 1 <= g: the record has this line)
+    if (w == 0u || (g + 1 < l1 ? n != w : n == 0u || n > w)) a.rec_width[r] = 0u;
+}
+
+__device__ __forceinline__ u32 fa_rows(u32 n) { return (n + kFaWidth - 1u) / kFaWidth; }
+
+// Record r: its verdict and its pieces, as sq_record.
+template <bool EMIT>
+__device__ __forceinline__ u32 fa_record(const FaArgs &a, u64 r)
+{
+    const unsigned char *t = a.text;
+    const u64 l0 = a.rec_line[r], l1 = a.rec_line[r + 1];
+    const u64 s = l0 ? a.line_end[l0 - 1] + 1 : 0, e0 = a.line_end[l0];
+    if (!EMIT) a.rec_pieces[r] = 0u, a.rec_bytes[r] = 0u;
+    if (a.line_end[l1 - 1] + 1 - s >= kSqMaxRecord) return kSqNeedHost;
+    u64 sep = s + 1; // the name's end: the first blank, tab or form feed
+    while (sep < e0 && t[sep] != ' ' && t[sep] != '\t' && t[sep] != '\x0c') sep++;
+    if (sep == s + 1) return kSqNeedHost; // (no name: the host writes it back as it stands; the id table holds no such read)
+    const u32 name_len = (u32)(sep - s - 1), desc_len = sep < e0 ? (u32)(e0 - sep - 1) : 0u;
+    const u64 base0 = a.base_before[l0];
+    const u32 seq_len = (u32)(a.base_before[l1] - base0);
+
+    const u32 read = ed_find(a.tab, GpBytes{t}, s + 1, name_len);
+    u32 type = 0, n_reg = 0, len = 0;
+    const u32 *reg = nullptr;
+    if (read != kEdNoRead) {
+        type = a.tab.type[read];
+        const u64 o = a.bad_off[read];
+        n_reg = (u32)(a.bad_off[read + 1] - o);
+        reg = a.bad_reg + 2 * o;
+        len = a.lengths[read];
+    }
+    bool copy = false;
+    if (a.op == 1u) copy = type == 0u;
+    else if (a.op == 2u) copy = type != 0u;
+    else if (type == 2u) return 0u; // NotCovered reads are dropped
+    else copy = a.op == 0u ? n_reg == 0u : type == 0u;
+    if ((a.op == 1u || a.op == 2u) && !copy) return 0u;
+    FaPiece p{};
+    p.hdr = s, p.base0 = base0, p.line0 = l0 + 1, p.line1 = l1, p.name_len = name_len;
+    if (EMIT) p.width = a.rec_width[r];
+    if (copy) {
+        const u64 bytes = 1ull + name_len + (desc_len ? 1ull + desc_len : 0ull) + 1ull + seq_len + fa_rows(seq_len);
+        if (bytes >= kSqMaxRecord) return kSqNeedHost;
+        if (!EMIT) a.rec_pieces[r] = 1u, a.rec_bytes[r] = (u32)bytes;
+        else {
+            p.out = a.byte_off[r], p.len = (u32)bytes, p.flags = kSqCopy, p.desc_len = desc_len, p.p0 = 0u, p.p1 = seq_len;
+            a.pieces[a.piece_off[r]] = p;
+        }
+        return 0u;
+    }
+    u32 status = 0, pieces = 0;
+    u64 bytes = 0;
+    sq_cuts(a.op, reg, n_reg, len, [&](u32 p0, u32 p1) {
+        if (p0 > seq_len || p1 > seq_len || p0 > p1) { // (the host prints the reference's [ERROR] line, or fails: its case)
+            status = kSqNeedHost;
+            return false;
+        }
+        const u32 L = p1 - p0;
+        const u64 plen = 1ull + name_len + 2u + sq_digits(p0) + sq_digits(p1) + 1u + L + fa_rows(L);
+        if (EMIT) {
+            p.out = a.byte_off[r] + bytes, p.len = (u32)plen, p.flags = 0u, p.desc_len = 0u, p.p0 = p0, p.p1 = p1;
+            a.pieces[a.piece_off[r] + pieces] = p;
+        }
+        pieces++, bytes += plen;
+        return true;
+    });
+    if (bytes >= kSqMaxRecord) status = kSqNeedHost;
+    if (status) return status;
+    if (!EMIT) a.rec_pieces[r] = pieces, a.rec_bytes[r] = (u32)bytes;
+    return 0u;
+}
+
+template <bool EMIT>
+__global__ __launch_bounds__(256) void fa_plan_kernel(FaArgs a)
+{
+    const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+    u32 status = r < a.n_rec ? fa_record<EMIT>(a, r) : 0u;
+    status = wave_or(status);
+    if (status && lane_id() == 0) atomicOr(a.ctl, (unsigned long long)status);
+}
+
+struct FaLine { // the input line a thread last took a base from: bases [b0, b1) of the text, its first byte at `start`
+    u64 g, b0, b1, start;
+    bool have;
+};
+
+// the line of piece p that holds base B of the text (p.base0 <= B < base_before[p.line1]): the last one whose base_before is
+// not beyond B — blank lines share their base_before with the line behind them and are never the last.  The line behind the
+// one in hand is tried first, then a search over what is left of the record.
+__device__ __forceinline__ void fa_seek(const FaArgs &a, const FaPiece &p, u64 B, FaLine &ln)
+{
+    if (ln.have && B >= ln.b0 && B < ln.b1) return;
+    u64 lo = p.line0;
+    if (ln.have && B >= ln.b1) {
+        lo = ln.g + 1; // (base_before[lo] == ln.b1 <= B; lo < line1, for B lies in the record)
+        const u64 nb = a.base_before[lo + 1];
+        if (B < nb) {
+            ln.g = lo, ln.b0 = ln.b1, ln.b1 = nb, ln.start = a.line_end[lo - 1] + 1;
+            return;
+        }
+    }
+    u64 hi = p.line1;
+    while (hi - lo > 1) {
+        const u64 mid = lo + (hi - lo) / 2;
+        if (a.base_before[mid] <= B) lo = mid;
+        else hi = mid;
+    }
+    ln.g = lo, ln.b0 = a.base_before[lo], ln.b1 = a.base_before[lo + 1], ln.start = a.line_end[lo - 1] + 1, ln.have = true;
+}
+
+// byte k of piece p, as sq_at
+__device__ __forceinline__ void fa_at(const FaArgs &a, const FaPiece &p, u32 k, FaLine &ln, const unsigned char *&src, u32 &rem, u32 &lit)
+{
+    const unsigned char *rec = a.text + p.hdr;
+    src = nullptr, rem = 1, lit = '\n';
+    if (k == 0) {
+        lit = '>';
+        return;
+    }
+    k -= 1;
+    if (k < p.name_len) {
+        src = rec + 1 + k, rem = p.name_len - k;
+        return;
+    }
+    k -= p.name_len;
+    if (p.flags & kSqCopy) {
+        if (p.desc_len) { // whatever the separator was, a blank
+            if (k == 0) {
+                lit = ' ';
+                return;
+            }
+            k -= 1;
+            if (k < p.desc_len) {
+                src = rec + 1 + p.name_len + 1 + k, rem = p.desc_len - k;
+                return;
+            }
+            k -= p.desc_len;
+        }
+    } else {
+        const u32 d0 = sq_digits(p.p0), d1 = sq_digits(p.p1);
+        if (k < 2u + d0 + d1) {
+            lit = k == 0 || k == d0 + 1u ? '_' : k <= d0 ? sq_digit_at(p.p0, d0, k - 1u) : sq_digit_at(p.p1, d1, k - d0 - 2u);
+            return;
+        }
+        k -= 2u + d0 + d1;
+    }
+    if (k == 0) return; // the header's newline
+    k -= 1;
+    const u32 L = p.p1 - p.p0, row = k / (kFaWidth + 1u), col = k % (kFaWidth + 1u), at = row * kFaWidth + col;
+    if (col == kFaWidth || at >= L) return; // a row's newline; the last row's
+    if (p.width) { // (a.line_end[p.line0 - 1]: the header's newline)
+        const u32 b = p.p0 + at, q = b / p.width, r = b - q * p.width;
+        src = a.text + a.line_end[p.line0 - 1] + 1 + (u64)q * ((u64)p.width + 1u) + r;
+        rem = min(min(p.width - r, kFaWidth - col), L - at);
+        return;
+    }
+    const u64 B = p.base0 + p.p0 + at;
+    fa_seek(a, p, B, ln);
+    src = a.text + ln.start + (B - ln.b0);
+    rem = (u32)min(min(ln.b1 - B, (u64)(kFaWidth - col)), (u64)(L - at));
+}
+
+// ---- copy: as sq_copy_kernel; a word takes the aligned path when its four bytes lie in one input line and one output row --------
+__global__ __launch_bounds__(kGpT) void fa_copy_kernel(FaArgs a)
+{
+    __shared__ __attribute__((aligned(16))) u32 tile[kSqOutTile / 4];
+    __shared__ u32 sw[kGpT / 64];
+    const u64 tile0 = (u64)blockIdx.x * (u64)kSqOutTile;
+    u32 stored = 0;
+    u64 pi = 0;
+    FaPiece p{};
+    FaLine ln{};
+    bool have = false;
+#pragma unroll 1
+    for (u32 w = 0; w < 4u; w++) {
+        const u64 j = tile0 + ((u64)w * (u32)kGpT + threadIdx.x) * 4u;
+        u32 word = 0;
+        if (j < a.total) {
+            if (!have) { // the last piece that begins at or in front of j (piece 0 begins at 0)
+                u64 lo = 0, hi = a.n_pieces;
+                while (hi - lo > 1) {
+                    const u64 mid = lo + (hi - lo) / 2;
+                    if (a.pieces[mid].out <= j) lo = mid;
+                    else hi = mid;
+                }
+                pi = lo, p = a.pieces[lo], have = true;
+            }
+            const u32 nb = (u32)min((u64)4, a.total - j);
+            for (u32 b = 0; b < nb;) {
+                const u64 jj = j + b;
+                while (jj >= p.out + p.len && pi + 1 < a.n_pieces) p = a.pieces[++pi], ln.have = false; // (jj < total: there is such a piece)
+                const unsigned char *src;
+                u32 rem, lit;
+                fa_at(a, p, (u32)(jj - p.out), ln, src, rem, lit);
+                if (src && b == 0 && rem >= 4u) {
+                    word = sq_load4(src);
+                    b = 4, stored += 4;
+                } else {
+                    word |= (src ? (u32)*src : lit) << (8u * b);
+                    b++, stored++;
+                }
+            }
+        }
+        tile[w * (u32)kGpT + threadIdx.x] = word;
+    }
+    sq_store_tile(a.out, a.total, a.ctl, tile, sw, tile0, stored);
 }
 
 } // namespace yk
@@ -406,6 +722,7 @@ struct SeqEditScratch { // the editor's buffers; they stay with the engine (grow
     static constexpr yacrd_engine::Slot kScratchSlot = yacrd_engine::kSeqEdit;
     DevBuf text, out, names, name_off, types, lengths, bad_off, bad_reg, slots, tile_nl, tile_l0, line_end, rec_pieces, rec_bytes, piece_off,
         byte_off, pieces, ctl, part;
+    DevBuf ln_head, ln_bases, ln_rec, base_before, rec_line, rec_width; // FASTA: per line, per record
     PinBuf pin; // two output pieces + the control words
 };
 
@@ -416,6 +733,7 @@ struct SeqJob {
     int n_threads = 0;
     const yacrd_report_table *table = nullptr;
     bool gzip = false;
+    bool fasta = false; // '>' records of any number of lines, written again at 80 columns
     yacrd_gzip_stats *gzip_stats = nullptr;
 };
 
@@ -441,6 +759,7 @@ struct SeqRun {
     size_t n_segs = 0;
     bool blit = false;
     yk::SqArgs ga{};
+    yk::FaArgs fa{}; // (FASTA: what the kernels behind the line index take)
     volatile u64 *h_ctl = nullptr; // pinned: [0..3] what a phase brings home, [4..7] the encoder's words of two batches
     Events ev;                     // pairs around the kernels of a phase (timing)
     Events wev;                    // a pinned piece has landed (two; no timing)
@@ -518,7 +837,7 @@ struct SeqRun {
         HIP_TRY(S.pin.reserve(2 * kOutPiece + 8 * sizeof(u64)));
         h_ctl = reinterpret_cast<volatile u64 *>(S.pin.as<char>() + 2 * kOutPiece);
         for (int i = 0; i < 8; i++) h_ctl[i] = 0;
-        if (!side.add(job.gzip ? 2 : 1) || !wev.add(2, hipEventDisableTiming) || !ev.add(2 * n_segs + 8)) HIP_TRY(why_not_added());
+        if (!side.add(job.gzip ? 2 : 1) || !wev.add(2, hipEventDisableTiming) || !ev.add(2 * n_segs + 10)) HIP_TRY(why_not_added());
         HIP_TRY(S.names.reserve((size_t)name_bytes + 64));
         HIP_TRY(S.name_off.reserve((size_t)(R + 1) * sizeof(u64)));
         HIP_TRY(S.types.reserve((size_t)R + 64));
@@ -580,15 +899,80 @@ struct SeqRun {
         if (!ok) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
         n_lines = h_ctl[0];
         if (h_ctl[1] & yk::kSqNeedHost) return fail(YACRD_EFALLBACK, "the text holds a CR: the host loop decides");
+        if (job.fasta) return YACRD_OK; // (its records are counted on the device: size_fasta)
         if (n_lines % 4) return fail(YACRD_EFALLBACK, "the line count is no multiple of four: the host loop decides");
         n_rec = n_lines / 4;
         if (n_rec >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "more records than the device editor numbers");
         return YACRD_OK;
     }
 
+    // FASTA: index, mark and the two scans over the lines — how many records —, then heads, widths, plan and the scans over the records
+    int size_fasta()
+    {
+        const double line_tables = (double)n_lines * 32.0;
+        if (!fits(line_tables, (double)S.line_end.cap + (double)S.ln_head.cap + (double)S.ln_bases.cap + (double)S.ln_rec.cap + (double)S.base_before.cap))
+            return no_room();
+        HIP_TRY(S.line_end.reserve((size_t)(n_lines + 1) * sizeof(u64)));
+        HIP_TRY(S.ln_head.reserve((size_t)(n_lines + 1) * sizeof(u32)));
+        HIP_TRY(S.ln_bases.reserve((size_t)(n_lines + 1) * sizeof(u32)));
+        HIP_TRY(S.ln_rec.reserve((size_t)(n_lines + 2) * sizeof(u64)));
+        HIP_TRY(S.base_before.reserve((size_t)(n_lines + 2) * sizeof(u64)));
+        ga.line_end = S.line_end.as<u64>(), ga.n_lines = n_lines;
+        fa.text = ga.text, fa.tab = ga.tab, fa.lengths = ga.lengths, fa.bad_off = ga.bad_off, fa.bad_reg = ga.bad_reg;
+        fa.line_end = S.line_end.as<u64>(), fa.head = S.ln_head.as<u32>(), fa.bases = S.ln_bases.as<u32>();
+        fa.line_rec = S.ln_rec.as<u64>(), fa.base_before = S.base_before.as<u64>();
+        fa.n_lines = n_lines, fa.ctl = ga.ctl, fa.op = ga.op;
+        const dim3 line_grid((u32)((n_lines + 255) / 256));
+        bool ok = ev_open();
+        if (n_tiles) hipLaunchKernelGGL(yk::sq_index_kernel, dim3((u32)n_tiles), dim3(yk::kGpT), 0, e->stream, ga);
+        if (n_lines) hipLaunchKernelGGL(yk::fa_mark_kernel, line_grid, dim3(256), 0, e->stream, fa);
+        if (const int rc = scan_u32_to_u64(e, fa.head, n_lines, S.ln_rec.as<u64>(), S.part)) return rc;
+        if (const int rc = scan_u32_to_u64(e, fa.bases, n_lines, S.base_before.as<u64>(), S.part)) return rc;
+        ok = ok && ev_close();
+        HIP_TRY(hipMemcpyAsync((void *)h_ctl, S.ln_rec.as<u64>() + n_lines, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync((void *)(h_ctl + 1), S.ctl.p, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipGetLastError());
+        if (!ok) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
+        n_rec = h_ctl[0];
+        if (h_ctl[1] & yk::kSqNeedHost) return fail(YACRD_EFALLBACK, "a line longer than the device editor's offsets: the host loop decides");
+        if (n_rec >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "more records than the device editor numbers");
+
+        if (!fits((double)n_rec * 36.0, (double)S.rec_line.cap + (double)S.piece_off.cap + (double)S.byte_off.cap)) return no_room();
+        HIP_TRY(S.rec_line.reserve((size_t)(n_rec + 1) * sizeof(u64)));
+        HIP_TRY(S.rec_width.reserve((size_t)(n_rec + 1) * sizeof(u32)));
+        HIP_TRY(S.rec_pieces.reserve((size_t)(n_rec + 1) * sizeof(u32)));
+        HIP_TRY(S.rec_bytes.reserve((size_t)(n_rec + 1) * sizeof(u32)));
+        HIP_TRY(S.piece_off.reserve((size_t)(n_rec + 2) * sizeof(u64)));
+        HIP_TRY(S.byte_off.reserve((size_t)(n_rec + 2) * sizeof(u64)));
+        fa.rec_line = S.rec_line.as<u64>(), fa.rec_width = S.rec_width.as<u32>(), fa.n_rec = n_rec;
+        fa.rec_pieces = S.rec_pieces.as<u32>(), fa.rec_bytes = S.rec_bytes.as<u32>();
+        fa.piece_off = S.piece_off.as<u64>(), fa.byte_off = S.byte_off.as<u64>();
+        ok = ev_open();
+        if (n_lines) hipLaunchKernelGGL(yk::fa_heads_kernel, line_grid, dim3(256), 0, e->stream, fa);
+        if (n_rec) hipLaunchKernelGGL(yk::fa_widths_kernel, line_grid, dim3(256), 0, e->stream, fa);
+        if (n_rec) hipLaunchKernelGGL(yk::fa_plan_kernel<false>, dim3((u32)((n_rec + 255) / 256)), dim3(256), 0, e->stream, fa);
+        if (const int rc = scan_u32_to_u64(e, fa.rec_pieces, n_rec, S.piece_off.as<u64>(), S.part)) return rc;
+        if (const int rc = scan_u32_to_u64(e, fa.rec_bytes, n_rec, S.byte_off.as<u64>(), S.part)) return rc;
+        ok = ok && ev_close();
+        HIP_TRY(hipMemcpyAsync((void *)h_ctl, S.piece_off.as<u64>() + n_rec, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync((void *)(h_ctl + 1), S.byte_off.as<u64>() + n_rec, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync((void *)(h_ctl + 2), S.ctl.p, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipGetLastError());
+        if (!ok) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
+        n_pieces = h_ctl[0], total = h_ctl[1];
+        if (h_ctl[2] & yk::kSqNeedHost)
+            return fail(YACRD_EFALLBACK, "bases in front of the first header, a header without a name, a cut position beyond its read or a region with "
+                                         "begin > end: the host loop decides");
+        if (n_pieces >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "more output records than the device editor numbers");
+        return YACRD_OK;
+    }
+
     // index, plan and the two scans: how many output records, how many bytes
     int size_output()
     {
+        if (job.fasta) return size_fasta();
         if (!fits((double)n_lines * 8.0 + (double)n_rec * 24.0, (double)S.line_end.cap + (double)S.piece_off.cap + (double)S.byte_off.cap)) return no_room();
         HIP_TRY(S.line_end.reserve((size_t)(n_lines + 1) * sizeof(u64)));
         HIP_TRY(S.rec_pieces.reserve((size_t)(n_rec + 1) * sizeof(u32)));
@@ -622,19 +1006,25 @@ struct SeqRun {
     int gather()
     {
         const u64 gz_blocks = job.gzip ? std::min<u64>(kGzBatchBlocks, (total + ydf::kBlock - 1) / ydf::kBlock + 1) : 0;
-        if (!fits((double)total + (double)n_pieces * 48.0 + (double)gz_blocks * (double)ydf::kSlot * 3.0, (double)S.out.cap + (double)S.pieces.cap)) return no_room();
+        const size_t piece_size = job.fasta ? sizeof(yk::FaPiece) : sizeof(yk::SqPiece);
+        if (!fits((double)total + (double)n_pieces * (double)piece_size + (double)gz_blocks * (double)ydf::kSlot * 3.0, (double)S.out.cap + (double)S.pieces.cap)) return no_room();
         const u64 padded = (total + 15) & ~(u64)15;
         HIP_TRY(S.out.reserve((size_t)padded + 64));
-        HIP_TRY(S.pieces.reserve((size_t)(n_pieces + 1) * sizeof(yk::SqPiece)));
+        HIP_TRY(S.pieces.reserve((size_t)(n_pieces + 1) * piece_size));
         if (job.gzip) {
             if (const int rcg = gzip_device_open(e, gz_blocks, &gz)) return rcg;
             gz_hold.e = e;
         }
         ga.pieces = S.pieces.as<yk::SqPiece>(), ga.n_pieces = n_pieces, ga.total = total, ga.out = S.out.as<unsigned char>();
+        fa.pieces = S.pieces.as<yk::FaPiece>(), fa.n_pieces = n_pieces, fa.total = total, fa.out = ga.out;
+        const dim3 out_grid((u32)((total + yk::kSqOutTile - 1) / yk::kSqOutTile));
         bool ok = ev_open();
-        if (total) {
+        if (total && job.fasta) {
+            hipLaunchKernelGGL(yk::fa_plan_kernel<true>, dim3((u32)((n_rec + 255) / 256)), dim3(256), 0, e->stream, fa);
+            hipLaunchKernelGGL(yk::fa_copy_kernel, out_grid, dim3(yk::kGpT), 0, e->stream, fa);
+        } else if (total) {
             hipLaunchKernelGGL(yk::sq_plan_kernel<true>, dim3((u32)((n_rec + 255) / 256)), dim3(256), 0, e->stream, ga);
-            hipLaunchKernelGGL(yk::sq_copy_kernel, dim3((u32)((total + yk::kSqOutTile - 1) / yk::kSqOutTile)), dim3(yk::kGpT), 0, e->stream, ga);
+            hipLaunchKernelGGL(yk::sq_copy_kernel, out_grid, dim3(yk::kGpT), 0, e->stream, ga);
         }
         ok = ok && ev_close();
         HIP_TRY(hipMemcpyAsync((void *)h_ctl, S.ctl.p, 2 * sizeof(u64), hipMemcpyDeviceToHost, e->stream));
@@ -757,10 +1147,11 @@ int run_seq_edit(yacrd_engine *e, const SeqJob &job, const TextSource &src, u64 
     return rc;
 }
 
-int seq_edit_args(yacrd_engine *e, int op, const yacrd_report_table *t, yacrd_seq_edit_stats *st)
+int seq_edit_args(bool fasta, yacrd_engine *e, int op, const yacrd_report_table *t, yacrd_seq_edit_stats *st)
 {
     if (!e) return fail(YACRD_EINVAL, "null argument");
-    if (!t) return fail(YACRD_EINVAL, "the FASTQ editor takes a table (the resident form is not built)");
+    if (!t) return fail(YACRD_EINVAL, fasta ? "the FASTA editor takes a table (the resident form is not built)"
+                                             : "the FASTQ editor takes a table (the resident form is not built)");
     if (op < 0 || op > 3) return fail(YACRD_EINVAL, "op: 0 = scrubb, 1 = filter, 2 = extract, 3 = split");
     if (st) std::memset(st, 0, sizeof(*st));
     if (e->pending.active || e->host_pending) return fail(YACRD_EINVAL, "the engine has a submitted batch pending");
@@ -775,17 +1166,23 @@ bool named_fastq(const char *path)
     if (has(".m4") || has(".mhap") || has(".paf") || has(".yacrd")) return false;
     return has(".fastq") || has(".fq");
 }
-
-} // namespace
-
-extern "C" {
-
-int yacrd_engine_edit_fastq(yacrd_engine *e, int op, const char *in_path, const char *out_path, int n_threads, const yacrd_report_table *t,
-                            yacrd_seq_edit_stats *st)
+// ... and as far as it says FASTA: every other type's mark wins over ".fa"
+bool named_fasta(const char *path)
 {
-    if (const int rca = seq_edit_args(e, op, t, st)) return rca;
+    const std::string name(path);
+    auto has = [&](const char *x) { return name.find(x) != std::string::npos; };
+    if (has(".m4") || has(".mhap") || has(".paf") || has(".yacrd") || has(".fastq") || has(".fq")) return false;
+    return has(".fasta") || has(".fa");
+}
+
+// the four forms, for FASTQ and for FASTA
+int edit_seq_file(bool fasta, yacrd_engine *e, int op, const char *in_path, const char *out_path, int n_threads, const yacrd_report_table *t,
+                  yacrd_seq_edit_stats *st)
+{
+    if (const int rca = seq_edit_args(fasta, e, op, t, st)) return rca;
     if (!in_path || !out_path) return fail(YACRD_EINVAL, "null argument");
-    if (!named_fastq(in_path)) return fail(YACRD_EFALLBACK, "not a FASTQ file by its name: the host loop's case");
+    if (fasta && !named_fasta(in_path)) return fail(YACRD_EFALLBACK, "not a FASTA file by its name: the host loop's case");
+    if (!fasta && !named_fastq(in_path)) return fail(YACRD_EFALLBACK, "not a FASTQ file by its name: the host loop's case");
     const int fd = ::open(in_path, O_RDONLY);
     if (fd < 0) return fail(YACRD_EFALLBACK, std::string("cannot open ") + in_path + ": the host loop words the error");
     FdGuard fdg{fd};
@@ -800,7 +1197,7 @@ int yacrd_engine_edit_fastq(yacrd_engine *e, int op, const char *in_path, const 
     yseg::BesideFile file;
     if (!file.open(out_path)) return fail(YACRD_EFALLBACK, std::string("cannot create a file beside ") + out_path + ": the host loop words the error");
     SeqJob job;
-    job.op = op, job.n_threads = n_threads, job.table = t;
+    job.op = op, job.n_threads = n_threads, job.table = t, job.fasta = fasta;
     TextSource src;
     src.fd = fd;
     Sink sink;
@@ -811,14 +1208,14 @@ int yacrd_engine_edit_fastq(yacrd_engine *e, int op, const char *in_path, const 
     return rc;
 }
 
-int yacrd_engine_edit_fastq_mem(yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, char **out, uint64_t *out_bytes,
-                                yacrd_seq_edit_stats *st)
+int edit_seq_mem(bool fasta, yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, char **out, uint64_t *out_bytes,
+                 yacrd_seq_edit_stats *st)
 {
-    if (const int rca = seq_edit_args(e, op, t, st)) return rca;
+    if (const int rca = seq_edit_args(fasta, e, op, t, st)) return rca;
     if ((!text && n) || !out || !out_bytes) return fail(YACRD_EINVAL, "null argument");
     *out = nullptr, *out_bytes = 0;
     SeqJob job;
-    job.op = op, job.table = t;
+    job.op = op, job.table = t, job.fasta = fasta;
     TextSource src;
     src.mem = text ? text : "";
     Sink sink;
@@ -832,15 +1229,15 @@ int yacrd_engine_edit_fastq_mem(yacrd_engine *e, int op, const char *text, uint6
     return YACRD_OK;
 }
 
-int yacrd_engine_edit_fastq_gzip_mem(yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, char **out,
-                                     uint64_t *out_bytes, yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs)
+int edit_seq_gzip_mem(bool fasta, yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, char **out,
+                      uint64_t *out_bytes, yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs)
 {
     if (gs) std::memset(gs, 0, sizeof(*gs));
-    if (const int rca = seq_edit_args(e, op, t, st)) return rca;
+    if (const int rca = seq_edit_args(fasta, e, op, t, st)) return rca;
     if ((!text && n) || !out || !out_bytes) return fail(YACRD_EINVAL, "null argument");
     *out = nullptr, *out_bytes = 0;
     SeqJob job;
-    job.op = op, job.table = t, job.gzip = true, job.gzip_stats = gs;
+    job.op = op, job.table = t, job.gzip = true, job.gzip_stats = gs, job.fasta = fasta;
     TextSource src;
     src.mem = text ? text : "";
     Sink sink;
@@ -858,18 +1255,18 @@ int yacrd_engine_edit_fastq_gzip_mem(yacrd_engine *e, int op, const char *text, 
     return YACRD_OK;
 }
 
-int yacrd_engine_edit_fastq_gzip_file(yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, const char *out_path,
-                                      yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs)
+int edit_seq_gzip_file(bool fasta, yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, const char *out_path,
+                       yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs)
 {
     if (gs) std::memset(gs, 0, sizeof(*gs));
-    if (const int rca = seq_edit_args(e, op, t, st)) return rca;
+    if (const int rca = seq_edit_args(fasta, e, op, t, st)) return rca;
     if ((!text && n) || !out_path) return fail(YACRD_EINVAL, "null argument");
     struct stat ost;
     if (lstat(out_path, &ost) == 0 && !S_ISREG(ost.st_mode)) return fail(YACRD_EFALLBACK, "the output is not a regular file: the host loop writes it");
     yseg::BesideFile file;
     if (!file.open(out_path)) return fail(YACRD_EFALLBACK, std::string("cannot create a file beside ") + out_path + ": the host loop words the error");
     SeqJob job;
-    job.op = op, job.table = t, job.gzip = true, job.gzip_stats = gs;
+    job.op = op, job.table = t, job.gzip = true, job.gzip_stats = gs, job.fasta = fasta;
     TextSource src;
     src.mem = text ? text : "";
     Sink sink;
@@ -881,6 +1278,52 @@ int yacrd_engine_edit_fastq_gzip_file(yacrd_engine *e, int op, const char *text,
         if (gs) std::memset(gs, 0, sizeof(*gs));
     }
     return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int yacrd_engine_edit_fastq(yacrd_engine *e, int op, const char *in_path, const char *out_path, int n_threads, const yacrd_report_table *t,
+                            yacrd_seq_edit_stats *st)
+{
+    return edit_seq_file(false, e, op, in_path, out_path, n_threads, t, st);
+}
+int yacrd_engine_edit_fastq_mem(yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, char **out, uint64_t *out_bytes,
+                                yacrd_seq_edit_stats *st)
+{
+    return edit_seq_mem(false, e, op, text, n, t, out, out_bytes, st);
+}
+int yacrd_engine_edit_fastq_gzip_mem(yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, char **out,
+                                     uint64_t *out_bytes, yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs)
+{
+    return edit_seq_gzip_mem(false, e, op, text, n, t, out, out_bytes, st, gs);
+}
+int yacrd_engine_edit_fastq_gzip_file(yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, const char *out_path,
+                                      yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs)
+{
+    return edit_seq_gzip_file(false, e, op, text, n, t, out_path, st, gs);
+}
+
+int yacrd_engine_edit_fasta(yacrd_engine *e, int op, const char *in_path, const char *out_path, int n_threads, const yacrd_report_table *t,
+                            yacrd_seq_edit_stats *st)
+{
+    return edit_seq_file(true, e, op, in_path, out_path, n_threads, t, st);
+}
+int yacrd_engine_edit_fasta_mem(yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, char **out, uint64_t *out_bytes,
+                                yacrd_seq_edit_stats *st)
+{
+    return edit_seq_mem(true, e, op, text, n, t, out, out_bytes, st);
+}
+int yacrd_engine_edit_fasta_gzip_mem(yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, char **out,
+                                     uint64_t *out_bytes, yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs)
+{
+    return edit_seq_gzip_mem(true, e, op, text, n, t, out, out_bytes, st, gs);
+}
+int yacrd_engine_edit_fasta_gzip_file(yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, const char *out_path,
+                                      yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs)
+{
+    return edit_seq_gzip_file(true, e, op, text, n, t, out_path, st, gs);
 }
 
 } // extern "C"

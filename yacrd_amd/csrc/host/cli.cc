@@ -406,10 +406,15 @@ int main(int argc, char **argv)
         // read this very file — and the output is deflated where the device gathers it: only BGZF members come back
         // (yacrd_engine_edit_fastq_gzip_file).  Whatever that path does not take — anything but canonical four-line records, a
         // cut position beyond its read — comes back with nothing written and takes the host loop below, which owns the syntax
-        // and the messages.  FASTA, bzip2 / xz, YACRD_NO_DEVICE_EDITOR=1 (and, for gzip, YACRD_NO_DEVICE_DEFLATE=1): the host.
-        const bool sub_fq = !sub_ovl && !has(sub_in, ".yacrd") && (has(sub_in, ".fastq") || has(sub_in, ".fq")) && !(no_ed && *no_ed == '1');
-        const int sub_comp = sub_fq ? yacrd_file_compression(sub_in.c_str()) : -1;
-        if (sub_fq && (sub_comp == 0 || (sub_comp == 1 && !(no_df && *no_df == '1')))) {
+        // and the messages.  bzip2 / xz, YACRD_NO_DEVICE_EDITOR=1 (and, for gzip, YACRD_NO_DEVICE_DEFLATE=1): the host.
+        // A FASTA — what the host calls one by its name — goes the same way through yacrd_engine_edit_fasta[_gzip_file]: records
+        // of any number of lines, written again 80 bases a line.
+        const bool sub_seq = !sub_ovl && !has(sub_in, ".yacrd") && !(no_ed && *no_ed == '1');
+        const bool sub_fq = sub_seq && (has(sub_in, ".fastq") || has(sub_in, ".fq"));
+        const bool sub_fa = sub_seq && !sub_fq && (has(sub_in, ".fasta") || has(sub_in, ".fa"));
+        const char *sub_fmt = sub_fa ? "fasta" : "fastq";
+        const int sub_comp = sub_fq || sub_fa ? yacrd_file_compression(sub_in.c_str()) : -1;
+        if ((sub_fq || sub_fa) && (sub_comp == 0 || (sub_comp == 1 && !(no_df && *no_df == '1')))) {
             const yacrd_report_table rt = {bp.n_reads, bp.name_off, bp.names, bp.lengths, bp.bad_offsets, bp.bad_regions, bp.read_type};
             yacrd_seq_edit_stats ss{};
             yacrd_gzip_stats gs{};
@@ -425,22 +430,22 @@ int main(int argc, char **argv)
                 else if (yacrd_text_from_file(sub_in.c_str(), threads == 1 ? 0 : (int)threads, &own) == 0)
                     tx = &own; // (a file that cannot be inflated: the host loop below words the error)
                 inflate_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count();
-                if (tx) dev_edit = yacrd_engine_edit_fastq_gzip_file(engines[0], op, tx->data, tx->n, &rt, sub_out.c_str(), &ss, &gs);
+                if (tx) dev_edit = (sub_fa ? yacrd_engine_edit_fasta_gzip_file : yacrd_engine_edit_fastq_gzip_file)(engines[0], op, tx->data, tx->n, &rt, sub_out.c_str(), &ss, &gs);
                 yacrd_text_free(&own);
             } else {
                 const char *ct = std::getenv("YACRD_COPY_THREADS");
-                dev_edit = yacrd_engine_edit_fastq(engines[0], op, sub_in.c_str(), sub_out.c_str(), ct && *ct ? std::max(0, std::atoi(ct)) : 0, &rt, &ss);
+                dev_edit = (sub_fa ? yacrd_engine_edit_fasta : yacrd_engine_edit_fastq)(engines[0], op, sub_in.c_str(), sub_out.c_str(), ct && *ct ? std::max(0, std::atoi(ct)) : 0, &rt, &ss);
             }
             if (dev_edit == YACRD_ENOMEM) {
-                std::fprintf(stderr, "[INFO] device fastq editor: %s; falling back to the host loop\n", yacrd_last_error());
+                std::fprintf(stderr, "[INFO] device %s editor: %s; falling back to the host loop\n", sub_fmt, yacrd_last_error());
                 for (yacrd_engine *en : engines) (void)yacrd_engine_trim(en);
                 dev_edit = YACRD_EFALLBACK;
             }
             if (dev_edit != YACRD_OK && dev_edit != YACRD_EFALLBACK) die(yacrd_last_error());
             if (dev_edit == YACRD_OK && timing) {
-                std::fprintf(stderr, "[info] device fastq editor: %llu records -> %llu, %llu bytes -> %llu bytes, text %.1f ms, table %.1f ms, "
+                std::fprintf(stderr, "[info] device %s editor: %llu records -> %llu, %llu bytes -> %llu bytes, text %.1f ms, table %.1f ms, "
                                      "kernels %.1f ms, out %.1f ms\n",
-                             (unsigned long long)ss.n_records, (unsigned long long)ss.n_out_records, (unsigned long long)ss.text_bytes,
+                             sub_fmt, (unsigned long long)ss.n_records, (unsigned long long)ss.n_out_records, (unsigned long long)ss.text_bytes,
                              (unsigned long long)ss.out_bytes, ss.text_ms, ss.table_ms, ss.kernel_ms, ss.out_ms);
                 if (sub_comp == 1) // (the encoder's line as the host loop's writer words it: the output lay in HBM, nothing went up)
                     std::fprintf(stderr, "[info] device deflate: %llu -> %llu bytes, %llu members (%llu stored), h2d %.1f ms, kernels %.1f ms, "

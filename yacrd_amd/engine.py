@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = [
     "yacrd_engine_edit_overlaps", "yacrd_engine_edit_overlaps_mem", "yacrd_edit_text_free",
     "yacrd_engine_edit_overlaps_gzip_mem", "yacrd_engine_edit_overlaps_gzip_file",
     "yacrd_engine_edit_fastq", "yacrd_engine_edit_fastq_mem", "yacrd_engine_edit_fastq_gzip_mem", "yacrd_engine_edit_fastq_gzip_file",
+    "yacrd_engine_edit_fasta", "yacrd_engine_edit_fasta_mem", "yacrd_engine_edit_fasta_gzip_mem", "yacrd_engine_edit_fasta_gzip_file",
     "yacrd_engine_gzip_mem", "yacrd_gzip_writer_open", "yacrd_gzip_writer_write", "yacrd_gzip_writer_sink", "yacrd_gzip_writer_close",
     "yacrd_gzip_writer_abort",
     "yacrd_stream_device_of", "yacrd_stream_group_open", "yacrd_stream_group_sink", "yacrd_stream_group_finish",
@@ -337,6 +338,9 @@ def load_library():
     lib.yacrd_engine_edit_fastq_gzip_file.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
                                                       ctypes.POINTER(_ReportTable), ctypes.c_char_p, ctypes.POINTER(_SeqEditStats),
                                                       ctypes.POINTER(_GzipStats)]
+    for fq, fa in ((getattr(lib, "yacrd_engine_edit_fastq" + form), getattr(lib, "yacrd_engine_edit_fasta" + form))
+                   for form in ("", "_mem", "_gzip_mem", "_gzip_file")):
+        fa.argtypes = fq.argtypes  # (the FASTA calls take what the FASTQ calls take)
     lib.yacrd_edit_text_free.restype = None
     lib.yacrd_engine_gzip_mem.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p),
                                           ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_GzipStats)]
@@ -808,22 +812,49 @@ class Engine:
         """yacrd_engine_edit_fastq: scrubb (op 0) / filter (1) / extract (2) / split (3) the plain FASTQ file `src` into
         `out_path` on the GPU, by the table (names, lengths, result); returns the stats (also self.seq_edit_stats).  Raises
         NeedsHostParser, with nothing written, when the input is the host loop's (host.edit_file)."""
-        t, keep = self._seq_table(names, lengths, result)
-        st = _SeqEditStats()
-        rc = self._lib.yacrd_engine_edit_fastq(self._h, int(op), os.fsencode(src), os.fsencode(out_path), int(n_threads), t, ctypes.byref(st))
-        del keep
-        return self._seq_edited(rc, st)
+        return self._edit_seq_file("fastq", op, src, out_path, names, lengths, result, n_threads)
 
     def edit_fastq_text(self, op, text, names, lengths, result):
         """yacrd_engine_edit_fastq_mem: the same over `text` (bytes or anything else with the buffer protocol, which is not
         copied) -> the output's bytes; the stats are in self.seq_edit_stats."""
+        return self._edit_seq_text("fastq", op, text, names, lengths, result)
+
+    def edit_fastq_gzip(self, op, text, names, lengths, result, out_path=None):
+        """yacrd_engine_edit_fastq_gzip_mem / _file: the same over the inflated FASTQ `text` with the output deflated on the
+        device where it is gathered.  Without out_path -> the BGZF stream (bytes: what gzip() gives for edit_fastq_text's
+        bytes); with it the stream is written there and (seq edit stats, gzip stats) returned.  Both are also in
+        self.seq_edit_stats and self.gzip_stats.  Raises NeedsHostParser, with nothing written, when the text is the host loop's."""
+        return self._edit_seq_gzip("fastq", op, text, names, lengths, result, out_path)
+
+    def edit_fasta(self, op, src, out_path, names, lengths, result, n_threads=0):
+        """yacrd_engine_edit_fasta: edit_fastq for a plain FASTA file: records of any number of lines, the key the whole name,
+        every record that goes out written again 80 bases a line, a cut piece without its description."""
+        return self._edit_seq_file("fasta", op, src, out_path, names, lengths, result, n_threads)
+
+    def edit_fasta_text(self, op, text, names, lengths, result):
+        """yacrd_engine_edit_fasta_mem: edit_fastq_text for FASTA."""
+        return self._edit_seq_text("fasta", op, text, names, lengths, result)
+
+    def edit_fasta_gzip(self, op, text, names, lengths, result, out_path=None):
+        """yacrd_engine_edit_fasta_gzip_mem / _file: edit_fastq_gzip for FASTA (what gzip() gives for edit_fasta_text's bytes)."""
+        return self._edit_seq_gzip("fasta", op, text, names, lengths, result, out_path)
+
+    def _edit_seq_file(self, fmt, op, src, out_path, names, lengths, result, n_threads):
+        t, keep = self._seq_table(names, lengths, result)
+        st = _SeqEditStats()
+        rc = getattr(self._lib, "yacrd_engine_edit_" + fmt)(self._h, int(op), os.fsencode(src), os.fsencode(out_path), int(n_threads), t,
+                                                            ctypes.byref(st))
+        del keep
+        return self._seq_edited(rc, st)
+
+    def _edit_seq_text(self, fmt, op, text, names, lengths, result):
         t, keep = self._seq_table(names, lengths, result)
         st = _SeqEditStats()
         buf = np.frombuffer(text, dtype=np.uint8)
         n = int(buf.size)
         out, n_out = ctypes.c_void_p(), ctypes.c_uint64()
-        rc = self._lib.yacrd_engine_edit_fastq_mem(self._h, int(op), ctypes.c_void_p(buf.ctypes.data if n else None), n, t,
-                                                   ctypes.byref(out), ctypes.byref(n_out), ctypes.byref(st))
+        rc = getattr(self._lib, "yacrd_engine_edit_%s_mem" % fmt)(self._h, int(op), ctypes.c_void_p(buf.ctypes.data if n else None), n, t,
+                                                                  ctypes.byref(out), ctypes.byref(n_out), ctypes.byref(st))
         del keep, buf
         self._seq_edited(rc, st)
         try:
@@ -831,11 +862,7 @@ class Engine:
         finally:
             self._lib.yacrd_edit_text_free(out)
 
-    def edit_fastq_gzip(self, op, text, names, lengths, result, out_path=None):
-        """yacrd_engine_edit_fastq_gzip_mem / _file: the same over the inflated FASTQ `text` with the output deflated on the
-        device where it is gathered.  Without out_path -> the BGZF stream (bytes: what gzip() gives for edit_fastq_text's
-        bytes); with it the stream is written there and (seq edit stats, gzip stats) returned.  Both are also in
-        self.seq_edit_stats and self.gzip_stats.  Raises NeedsHostParser, with nothing written, when the text is the host loop's."""
+    def _edit_seq_gzip(self, fmt, op, text, names, lengths, result, out_path):
         t, keep = self._seq_table(names, lengths, result)
         st, gs = _SeqEditStats(), _GzipStats()
         buf = np.frombuffer(text, dtype=np.uint8)
@@ -843,11 +870,11 @@ class Engine:
         addr = ctypes.c_void_p(buf.ctypes.data if n else None)
         out, n_out = ctypes.c_void_p(), ctypes.c_uint64()
         if out_path is None:
-            rc = self._lib.yacrd_engine_edit_fastq_gzip_mem(self._h, int(op), addr, n, t, ctypes.byref(out), ctypes.byref(n_out),
-                                                            ctypes.byref(st), ctypes.byref(gs))
+            rc = getattr(self._lib, "yacrd_engine_edit_%s_gzip_mem" % fmt)(self._h, int(op), addr, n, t, ctypes.byref(out), ctypes.byref(n_out),
+                                                                           ctypes.byref(st), ctypes.byref(gs))
         else:
-            rc = self._lib.yacrd_engine_edit_fastq_gzip_file(self._h, int(op), addr, n, t, os.fsencode(out_path), ctypes.byref(st),
-                                                             ctypes.byref(gs))
+            rc = getattr(self._lib, "yacrd_engine_edit_%s_gzip_file" % fmt)(self._h, int(op), addr, n, t, os.fsencode(out_path), ctypes.byref(st),
+                                                                            ctypes.byref(gs))
         del keep, buf
         self._seq_edited(rc, st)
         self.gzip_stats = {f: getattr(gs, f) for f, _ in _GzipStats._fields_}
