@@ -443,9 +443,31 @@ typedef struct {
 int yacrd_engine_gzip_mem(yacrd_engine *e, const char *data, uint64_t n_bytes,
                           char **out, uint64_t *out_bytes, yacrd_gzip_stats *stats /* may be NULL */);
 
+/* ---- BGZF inflated on the GPU (csrc/gpu_inflate.hip, csrc/inflate_block.h, csrc/bgzf_walk.h) --------------------------
+ * The other half: a BGZF stream in host memory -> its text.  The host walks the members (no zlib: `1f 8b 08 04`, the `BC`
+ * subfield anywhere in the extra field, BSIZE, the trailer's ISIZE <= 65 536; EOF members anywhere), the stream crosses the
+ * link compressed, and one wavefront per member decodes it in LDS — a full RFC 1951 decoder: stored, fixed and dynamic
+ * blocks, any number per member — checks the member's CRC-32 and ISIZE against what it produced and stores the text at the
+ * member's place.  An empty input and a stream of EOF members give an empty text (a buffer all the same).
+ * YACRD_EFALLBACK, with nothing returned: a stream that is not BGZF from its first member to its last (plain gzip; FNAME,
+ * FCOMMENT or FHCRC set; a BSIZE beyond the input; bytes after the last member), or any member the decoder does not take —
+ * the payload ends early or has bytes left over, block type 3, LEN / NLEN mismatch, over-subscribed or incomplete code
+ * lengths (a single distance code of length 1, which zlib writes, passes), a repeat with nothing in front, HLIT / HDIST
+ * beyond 286 / 30, length symbols 286-287 or distance symbols 30-31, a distance beyond the bytes produced, output beyond
+ * ISIZE or short of it, CRC mismatch.  Stricter than zlib in places, never more lenient: the caller then takes
+ * libyacrd_host's reader, which owns the messages.  The engine stays usable.  `out`: yacrd_edit_text_free.  The buffers
+ * stay with the engine: yacrd_engine_trim.  Additive: found by the symbol. */
+typedef struct {
+    uint64_t in_bytes, out_bytes, n_members; /* members as walked, EOF members among them */
+    float walk_ms, h2d_ms, kernel_ms /* device events */, d2h_ms;
+} yacrd_gunzip_stats;
+int yacrd_engine_gunzip_mem(yacrd_engine *e, const char *bgzf, uint64_t n_bytes,
+                            char **out, uint64_t *out_bytes, yacrd_gunzip_stats *st /* may be NULL */);
+
 /* filter / extract with gzip out: the kept bytes of yacrd_engine_edit_overlaps_mem deflated where the pack pass leaves them
  * in HBM, so that only members cross the link and reach the file.  `text` is the overlap text in host memory, already
- * inflated (format 1 = PAF / 2 = M4, MHAP): this library links no zlib, the caller inflates (libyacrd_host's
+ * inflated (format 1 = PAF / 2 = M4, MHAP): this library links no zlib and inflates BGZF only for the sequence editors
+ * (yacrd_engine_gunzip_mem below the editors' _bgzf_ forms); here the caller inflates (libyacrd_host's
  * yacrd_text_from_file is member-parallel for BGZF).  The decision and the kept bytes are those of
  * yacrd_engine_edit_overlaps_mem; the result is ONE BGZF stream, byte for byte what yacrd_engine_gzip_mem returns for the
  * kept bytes: blocks of 65 280 bytes counted from the start of the kept stream, the EOF member last (nothing kept: the EOF
@@ -589,6 +611,20 @@ int yacrd_engine_edit_fastq_gzip_mem(yacrd_engine *e, int op, const char *text, 
 int yacrd_engine_edit_fastq_gzip_file(yacrd_engine *e, int op, const char *text, uint64_t n_bytes, const yacrd_report_table *t,
                                       const char *out_path, yacrd_seq_edit_stats *st /* may be NULL */,
                                       yacrd_gzip_stats *gs /* may be NULL */);
+/* The BGZF forms mirror the gzip forms argument for argument, with two differences: `bgzf`, n_bytes is the COMPRESSED file in
+ * host memory (read or mapped: no host inflate), and a trailing yacrd_gunzip_stats is added.  The compressed bytes go up through
+ * the editor's mover into a buffer of their own, yacrd_engine_gunzip_mem's device step inflates the members into the
+ * editor's text buffer, and from there the run is the gzip form's: the output is byte for byte that of the gzip form given the
+ * inflated text.  Every YACRD_EFALLBACK cause of the gzip form applies unchanged (the text's last byte is looked at on the
+ * device, behind the inflate), plus yacrd_engine_gunzip_mem's: not BGZF, or a member not taken.  Nothing is written and
+ * nothing is left beside out_path.  us: h2d_ms is the compressed file's way up, kernel_ms the inflate kernel (device
+ * events), d2h_ms 0; st->text_ms covers both.  Additive: found by the symbol. */
+int yacrd_engine_edit_fastq_bgzf_mem(yacrd_engine *e, int op, const char *bgzf, uint64_t n_bytes, const yacrd_report_table *t,
+                                     char **out, uint64_t *out_bytes, yacrd_seq_edit_stats *st /* may be NULL */,
+                                     yacrd_gzip_stats *gs /* may be NULL */, yacrd_gunzip_stats *us /* may be NULL */);
+int yacrd_engine_edit_fastq_bgzf_file(yacrd_engine *e, int op, const char *bgzf, uint64_t n_bytes, const yacrd_report_table *t,
+                                      const char *out_path, yacrd_seq_edit_stats *st /* may be NULL */,
+                                      yacrd_gzip_stats *gs /* may be NULL */, yacrd_gunzip_stats *us /* may be NULL */);
 
 /* ---- the same on a FASTA file (csrc/gpu_seq_edit.hip) ---------------------------------------------------------------------
  * A line that begins with '>' starts a record; its name is the header up to the first blank, tab or form feed, its
@@ -617,6 +653,13 @@ int yacrd_engine_edit_fasta_gzip_mem(yacrd_engine *e, int op, const char *text, 
 int yacrd_engine_edit_fasta_gzip_file(yacrd_engine *e, int op, const char *text, uint64_t n_bytes, const yacrd_report_table *t,
                                       const char *out_path, yacrd_seq_edit_stats *st /* may be NULL */,
                                       yacrd_gzip_stats *gs /* may be NULL */);
+/* ... and the BGZF forms, as for FASTQ */
+int yacrd_engine_edit_fasta_bgzf_mem(yacrd_engine *e, int op, const char *bgzf, uint64_t n_bytes, const yacrd_report_table *t,
+                                     char **out, uint64_t *out_bytes, yacrd_seq_edit_stats *st /* may be NULL */,
+                                     yacrd_gzip_stats *gs /* may be NULL */, yacrd_gunzip_stats *us /* may be NULL */);
+int yacrd_engine_edit_fasta_bgzf_file(yacrd_engine *e, int op, const char *bgzf, uint64_t n_bytes, const yacrd_report_table *t,
+                                      const char *out_path, yacrd_seq_edit_stats *st /* may be NULL */,
+                                      yacrd_gzip_stats *gs /* may be NULL */, yacrd_gunzip_stats *us /* may be NULL */);
 
 /* Copy the last device result to host (allocates like yacrd_engine_run). */
 int yacrd_engine_fetch(yacrd_engine *e, yacrd_result *out);

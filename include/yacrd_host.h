@@ -152,6 +152,11 @@ void yacrd_text_free(yacrd_text *t);
  * member last).  For tests and for looking at the encoder without a GPU.  `out`: yacrd_bytes_free. */
 int yacrd_bgzf_encode_host(const char *data, uint64_t n, char **out, uint64_t *out_bytes);
 void yacrd_bytes_free(char *p);
+/* The device inflate decoder's text (csrc/inflate_block.h) the same way: one thread plays the 64 lanes of a wavefront.
+ * A BGZF stream (csrc/bgzf_walk.h: what counts as one) -> its text; every member's CRC-32 and ISIZE are checked.  Returns
+ * non-zero, with nothing returned, for a stream that is not BGZF or holds a member the decoder does not take (the message
+ * names the member and the cause).  Stricter than zlib in places, never more lenient.  `out`: yacrd_bytes_free. */
+int yacrd_bgzf_decode_host(const char *data, uint64_t n, char **out, uint64_t *out_bytes);
 /* The encoder's code-length construction: freq[n] -> len[n] with no length above `limit` (n in 2..286, limit in 5..15,
  * 2^limit >= n).  Fewer than two used symbols are given company, as zlib does, so the code is always complete. */
 int yacrd_deflate_code_lengths(const uint32_t *freq, uint32_t n, uint32_t limit, uint8_t *len);

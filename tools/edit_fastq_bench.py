@@ -9,6 +9,8 @@ removed before the clock starts:
                bytes leave through the gzip writer (its "[info] device deflate:" line)
   (b) new      this tree's yacrd: the text in HBM, cut, decided and gathered there (its "[info] device fastq editor:" line);
                for gzip the file inflated member-parallel and the output deflated where it lies
+               for BGZF the file goes up compressed and is inflated on the device (its "[info] device inflate:" line;
+               YACRD_NO_DEVICE_INFLATE=1 in the environment gives the rows of the host inflate instead)
 The figures compared are the `edit` stage of YACRD_CLI_TIMING — slowest (b) against fastest (a) — and the wall clock.  Every
 output is compared with the parent's (gzip: the inflated bytes when the streams differ).  One JSON line per op and form,
 appended to --json (default profiles/edit_fastq.json).
@@ -79,7 +81,7 @@ def run(binary, op, src, out):
         wall = time.perf_counter() - t0
         assert p.returncode == 0, p.stderr
         stages = dict(re.findall(r"^\[timing\] (\S+) ([0-9.]+) s$", p.stderr, re.M))
-        info = [l for l in p.stderr.splitlines() if l.startswith(editor_line) or l.startswith("[info] device deflate:")]
+        info = [l for l in p.stderr.splitlines() if l.startswith(editor_line) or l.startswith("[info] device deflate:") or l.startswith("[info] device inflate:")]
         row = {"edit_s": float(stages["edit"]), "wall_s": round(wall, 3), "info": info}
         if k:
             rows.append(row)

@@ -1,6 +1,6 @@
 // engine_internal.h — host-side internals shared by the translation units of libyacrd_hip.so: engine.hip (batch runs, the
 // engine's life), stream.hip (streaming ingest + CSR build on the GPU) and the text paths gpu_paf.hip, gpu_edit.hip,
-// gpu_deflate.hip, gpu_report.hip, gpu_report_write.hip, gpu_seq_edit.hip.  The error slot; the OWNERS of every HIP resource the library takes:
+// gpu_deflate.hip, gpu_inflate.hip, gpu_report.hip, gpu_report_write.hip, gpu_seq_edit.hip.  The error slot; the OWNERS of every HIP resource the library takes:
 // DevBuf (device memory), PinBuf (pinned memory), Events, Streams.  Each frees what it holds when it goes, none is copied, and
 // no translation unit calls the runtime's allocate / create / free / destroy functions itself (yacrd_pinned_alloc / _free, whose
 // memory is the caller's, excepted); the two buffer types count the bytes they hold (live_bytes).  Then the clocks, the engine
@@ -20,6 +20,10 @@
 
 #include "bgzf_sizes.h" // (what a batch of GzDevice is counted in, below)
 #include "device_common.h"
+
+namespace yif {
+struct InfMember; // (inflate_block.h: one member of a BGZF stream, as bgzf_walk.h finds it)
+}
 
 namespace yke {
 
@@ -354,7 +358,7 @@ struct yacrd_engine {
     // what the text paths keep between calls (their own types, whose members own their device and pinned buffers, events and
     // streams; nothing in them outlives a call except capacity), made on first use by yke::scratch_of; yacrd_engine_trim and
     // yacrd_engine_destroy delete them (drop_scratch), the next use after a trim makes a fresh one
-    enum Slot { kPaf = 0, kEdit, kGzip, kReport, kReportWrite, kSeqEdit, kSlots };
+    enum Slot { kPaf = 0, kEdit, kGzip, kReport, kReportWrite, kSeqEdit, kInflate, kSlots };
     struct {
         void *p = nullptr;
         void (*destroy)(void *) = nullptr;
@@ -406,4 +410,21 @@ int gzip_device_open(yacrd_engine *e, u64 max_blocks, GzDevice *g);
 int gzip_device_encode(yacrd_engine *e, const GzDevice &g, hipStream_t st, const unsigned char *d_text, u64 n, bool last, int which,
                        hipEvent_t k0, hipEvent_t k1, volatile u64 *h_bytes, volatile u64 *h_stored);
 void gzip_device_close(yacrd_engine *e);
+// a BGZF stream that lies in HBM -> its text in HBM (gpu_inflate.hip; used by gpu_seq_edit.hip).  open takes the engine's
+// inflate scratch for a stream of comp_bytes and the members the host's walk found (bgzf_walk.h), uploads the member table and
+// zeroes the status word on the engine's stream; the caller then moves the stream's bytes to d.comp (comp_bytes + 64 bytes
+// are there, 16-byte aligned).  run launches the decoder on stream `st`: member m's text to d_text + members[m].out_off,
+// nothing beyond d_text[0, text_bytes); asynchronous.  Behind it *d.status is 0, or the largest yif::InfStatus a member that
+// was not taken gave: the text is then not to be used.  Nothing is held between calls but capacity.
+struct InflateDevice {
+    unsigned char *comp = nullptr;
+    const yif::InfMember *members = nullptr;
+    u32 *status = nullptr;
+    u64 comp_bytes = 0, n_members = 0;
+    bool fresh = false; // `comp` is a new allocation (move_text's `blit`)
+};
+int inflate_device_open(yacrd_engine *e, u64 comp_bytes, const yif::InfMember *members, u64 n_members, InflateDevice *d);
+int inflate_device_run(yacrd_engine *e, const InflateDevice &d, hipStream_t st, unsigned char *d_text, u64 text_bytes);
+// the message of a status word that is not 0 (YACRD_EFALLBACK)
+int inflate_not_taken(u32 status);
 } // namespace yke

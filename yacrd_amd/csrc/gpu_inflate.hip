@@ -1,0 +1,177 @@
+// gpu_inflate.hip — BGZF inflated on the GPU: a stream in HBM -> its text in HBM (include/yacrd_engine.h:
+// yacrd_engine_gunzip_mem; gpu_seq_edit.hip: the editors' _bgzf_ forms).
+//
+//   walk     on the host (bgzf_walk.h, no zlib): every member's payload, sizes and place in the text; what is not BGZF is
+//            the host reader's (YACRD_EFALLBACK)
+//   decode   one 64-thread workgroup — one wavefront — per member: inflate_block.h.  Only the code tables lie in LDS (4.7 KiB)
+//            and the kernel takes 50 VGPRs: 32 wavefronts per CU.  The member's text is written where it belongs in HBM, one
+//            byte per store — members begin at any byte, and no dword that holds bytes of two members is ever written as
+//            one — and a match reads back what this wavefront has stored: one wavefront's accesses to an address are served
+//            in order, nobody else reads the bytes before the kernel ends.  (The whole member in LDS, 70 KiB and two
+//            wavefronts per CU, was built first and took five times as long: DESIGN §7h.)  The payload is read 256 bytes
+//            at a time into the wavefront's registers.
+// A member that is not taken (inflate_block.h: InfStatus) leaves its status in one word (the largest wins); its part of the
+// text then holds whatever was decoded until then, and the caller does not use the text.
+#include "engine_internal.h"
+#include "gpu_text.h"
+#include "bgzf_walk.h"
+#include "inflate_block.h"
+#include "host/segment_pump.h"
+
+#include <cstdio>
+#include <cstdlib>
+
+using namespace yke;
+
+namespace yk {
+
+__global__ __launch_bounds__(64) void inf_kernel(const unsigned char *comp, u64 comp_bytes, const yif::InfMember *members, u32 n_members,
+                                                  unsigned char *text, u64 text_bytes, u32 *status)
+{
+    __shared__ yif::InfShared sh;
+    const u32 m = blockIdx.x;
+    if (m >= n_members) return; // (uniform)
+    const yif::InfMember mm = members[m];
+    const u32 lane = threadIdx.x;
+    const u32 csize = YI_UNI(mm.csize), n = YI_UNI(mm.isize);
+    u32 st = yif::kInfTable; // the table is the host's, from these bytes; what it says is checked against the buffers all the same
+    if (n <= yif::kMaxOut && mm.in_off <= comp_bytes && comp_bytes - mm.in_off >= (u64)csize + 8u && mm.out_off <= text_bytes &&
+        text_bytes - mm.out_off >= n) {
+        const unsigned char *p = comp + mm.in_off;
+        const u32 crc = (u32)p[csize] | ((u32)p[csize + 1] << 8) | ((u32)p[csize + 2] << 16) | ((u32)p[csize + 3] << 24);
+        st = yif::inf_decode_member(sh, p, csize, n, YI_UNI(crc), text + mm.out_off);
+    }
+    if (st != yif::kInfOk && lane == 0) atomicMax(status, st);
+}
+
+} // namespace yk
+
+namespace {
+
+constexpr size_t kHomePiece = (size_t)4 << 20; // what one copy home moves
+
+struct InflateScratch { // stays with the engine (grow-only); goes with yacrd_engine_trim / destroy
+    static constexpr yacrd_engine::Slot kScratchSlot = yacrd_engine::kInflate;
+    DevBuf comp, members, status;
+    DevBuf text; // yacrd_engine_gunzip_mem's (the editors inflate into their own text buffer)
+    PinBuf pin;  // two pieces on their way home, the status word
+};
+
+} // namespace
+
+namespace yke {
+
+int inflate_device_open(yacrd_engine *e, u64 comp_bytes, const yif::InfMember *members, u64 n_members, InflateDevice *d)
+{
+    if (n_members >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "more BGZF members than the device decoder numbers");
+    InflateScratch *S = scratch_of<InflateScratch>(e);
+    if (!S) return fail(YACRD_ENOMEM, "host allocation failed");
+    const void *before = S->comp.p;
+    HIP_TRY(S->comp.reserve((size_t)comp_bytes + 64));
+    HIP_TRY(S->members.reserve((size_t)(n_members + 1) * sizeof(yif::InfMember)));
+    HIP_TRY(S->status.reserve(64));
+    HIP_TRY(hipMemsetAsync(S->status.p, 0, 64, e->stream));
+    HIP_TRY(hipMemsetAsync(S->comp.as<char>() + comp_bytes, 0, 64, e->stream));
+    if (n_members)
+        if (const int rc = h2d(e, S->members.p, members, (size_t)n_members * sizeof(yif::InfMember))) return rc;
+    d->comp = S->comp.as<unsigned char>(), d->members = S->members.as<yif::InfMember>(), d->status = S->status.as<u32>();
+    d->comp_bytes = comp_bytes, d->n_members = n_members, d->fresh = S->comp.p != before;
+    return YACRD_OK;
+}
+
+int inflate_device_run(yacrd_engine *e, const InflateDevice &d, hipStream_t st, unsigned char *d_text, u64 text_bytes)
+{
+    (void)e;
+    if (d.n_members)
+        hipLaunchKernelGGL(yk::inf_kernel, dim3((u32)d.n_members), dim3(64), 0, st, d.comp, d.comp_bytes, d.members, (u32)d.n_members, d_text,
+                           text_bytes, d.status);
+    HIP_TRY(hipGetLastError());
+    return YACRD_OK;
+}
+
+int inflate_not_taken(u32 status)
+{
+    return fail(YACRD_EFALLBACK, std::string("a BGZF member the device decoder does not take (") + yif::inf_status_name(status) + "): the host reader's");
+}
+
+} // namespace yke
+
+extern "C" {
+
+int yacrd_engine_gunzip_mem(yacrd_engine *e, const char *bgzf, uint64_t n_bytes, char **out, uint64_t *out_bytes, yacrd_gunzip_stats *stats)
+{
+    if (!e || (!bgzf && n_bytes) || !out || !out_bytes) return fail(YACRD_EINVAL, "null argument");
+    *out = nullptr, *out_bytes = 0;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (e->pending.active || e->host_pending) return fail(YACRD_EINVAL, "the engine has a submitted batch pending");
+    DeviceGuard guard(e->device);
+    yacrd_gunzip_stats s = {};
+    const double t0 = now_ms();
+    std::vector<yif::InfMember> members;
+    u64 total = 0;
+    if (!ybw::walk(reinterpret_cast<const unsigned char *>(bgzf), n_bytes, members, &total)) return fail(YACRD_EFALLBACK, "not BGZF: the host reader's");
+    s.walk_ms = (float)(now_ms() - t0);
+    s.in_bytes = n_bytes, s.out_bytes = total, s.n_members = members.size();
+    char *res = (char *)std::malloc((size_t)total + 1);
+    if (!res) return fail(YACRD_ENOMEM, "host allocation failed");
+    Events ev, wev; // around the kernel (timed); a piece has landed at home (two)
+    auto run = [&]() -> int {
+        if (members.empty()) return YACRD_OK;
+        InflateDevice d;
+        if (const int rc = inflate_device_open(e, n_bytes, members.data(), members.size(), &d)) return rc;
+        InflateScratch &S = *scratch_of<InflateScratch>(e); // (open made it)
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (double)total * 1.125 + (double)((size_t)64 << 20) > (double)free_b + (double)S.text.cap)
+            return fail(YACRD_EFALLBACK, "the text does not fit this device's free memory: the host reader streams it");
+        HIP_TRY(S.text.reserve((size_t)total + 64));
+        HIP_TRY(S.pin.reserve(2 * kHomePiece + 64));
+        volatile u32 *h_status = reinterpret_cast<volatile u32 *>(S.pin.as<char>() + 2 * kHomePiece);
+        *h_status = 0;
+        if (!ev.add(2) || !wev.add(2, hipEventDisableTiming)) HIP_TRY(why_not_added());
+        const double t1 = now_ms();
+        TextSource src;
+        src.mem = bgzf;
+        const int moved = move_text(e, src, 0, n_bytes, reinterpret_cast<char *>(d.comp), d.fresh, 0, [](u64, u64, u64) {});
+        if (moved == 3) return fail(YACRD_ENOMEM, "BGZF stream to HBM: no pinned memory");
+        if (moved) return fail(YACRD_ENODEV, "device inflate: a HIP call failed");
+        s.h2d_ms = (float)(now_ms() - t1);
+        HIP_TRY(hipEventRecord(ev[0], e->stream));
+        if (const int rc = inflate_device_run(e, d, e->stream, S.text.as<unsigned char>(), total)) return rc;
+        HIP_TRY(hipEventRecord(ev[1], e->stream));
+        HIP_TRY(hipMemcpyAsync((void *)h_status, d.status, sizeof(u32), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipGetLastError());
+        s.kernel_ms = ev_ms(ev[0], ev[1]);
+        if (*h_status) return inflate_not_taken(*h_status);
+        const double t2 = now_ms();
+        struct Dma {
+            yacrd_engine *e;
+            Events &wev;
+            const char *text;
+            bool start(u64 i, char *dst, u64 at, size_t k)
+            {
+                return hipMemcpyAsync(dst, text + at, k, hipMemcpyDeviceToHost, e->stream) == hipSuccess && hipEventRecord(wev[i & 1], e->stream) == hipSuccess;
+            }
+            bool wait(u64 i) { return hipEventSynchronize(wev[i & 1]) == hipSuccess; }
+            void drain() { (void)hipStreamSynchronize(e->stream); }
+        } dma{e, wev, S.text.as<char>()};
+        yseg::Sink sink;
+        sink.mem = res; // (sized here: total bytes)
+        const int rc = yseg::pump(total, kHomePiece, S.pin.as<char>(), dma, sink, [](auto put) { put(); });
+        if (rc != yseg::kPumped || sink.at != total) return fail(YACRD_ENODEV, "device inflate: a HIP call failed on the way home");
+        s.d2h_ms = (float)(now_ms() - t2);
+        return YACRD_OK;
+    };
+    const int rc = run();
+    (void)hipStreamSynchronize(e->stream); // (whatever failed: nothing of this call is in flight when its events go)
+    (void)hipGetLastError();
+    if (rc != YACRD_OK) {
+        std::free(res);
+        return rc;
+    }
+    *out = res, *out_bytes = total;
+    if (stats) *stats = s;
+    return YACRD_OK;
+}
+
+} // extern "C"

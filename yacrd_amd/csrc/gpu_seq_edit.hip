@@ -31,9 +31,15 @@
 // device-resident step, batch by batch (a batch begins on a multiple of 65 280 bytes: the encoder's 16-byte loads stay
 // aligned); one batch comes home while the next is encoded.  Blocks are counted from byte 0 of the output, so the stream is
 // yacrd_engine_gzip_mem's for the same bytes.
+//
+// BGZF in (yacrd_engine_edit_fastq_bgzf_mem / _file): the compressed file crosses the link through the same mover into the
+// inflate scratch's buffer, gpu_inflate.hip's device-resident step inflates its members into the text buffer, and the run goes
+// on from `lines` as above.  The text's last byte, which the other forms read from the host's copy, comes back from the device
+// behind the inflate, with the decoder's status word.
 #include "engine_internal.h"
 #include "gpu_text.h"
 #include "edit_table.h"
+#include "bgzf_walk.h"
 #include "host/beside_file.h"
 #include "host/segment_pump.h"
 
@@ -735,6 +741,11 @@ struct SeqJob {
     bool gzip = false;
     bool fasta = false; // '>' records of any number of lines, written again at 80 columns
     yacrd_gzip_stats *gzip_stats = nullptr;
+    // BGZF in: the compressed file in host memory and its members as the host walked them; the run's `n` is the text they inflate to
+    const char *bgzf = nullptr;
+    u64 bgzf_bytes = 0;
+    const std::vector<yif::InfMember> *members = nullptr;
+    yacrd_gunzip_stats *gunzip_stats = nullptr;
 };
 
 struct SeqGzHold { // the engine's encoder buffers are this edit's until it ends
@@ -771,6 +782,8 @@ struct SeqRun {
     double t_start = 0, t_table = 0, t_text = 0, out_busy_ms = 0, put_ms = 0;
     u64 gz_members = 0, gz_stored = 0;
     float gz_kernel_ms = 0;
+    Events iev; // around the inflate kernel
+    float inf_h2d_ms = 0, inf_kernel_ms = 0;
 
     // whether `need` more bytes of HBM are there, counting what the scratch already holds of them
     static bool fits(double need, double held)
@@ -807,7 +820,7 @@ struct SeqRun {
             if (G >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "more regions than the device table holds");
             if (G && !t.bad_regions) return fail(YACRD_EINVAL, "the report table is incomplete");
         }
-        if (n) {
+        if (n && !job.bgzf) { // (BGZF in: the last byte comes back from the device behind the inflate, inflate_text)
             char last = 0;
             if (!src.fetch(&last, 1, n - 1)) return fail(YACRD_EINVAL, "read error in the sequence file");
             if (last != '\n') return fail(YACRD_EFALLBACK, "the text's last line has no newline: the host loop's case");
@@ -819,7 +832,8 @@ struct SeqRun {
         t_start = now_ms();
         const double held = (double)S.text.cap + (double)S.names.cap + (double)S.slots.cap + (double)S.bad_reg.cap + (double)S.tile_l0.cap;
         // (the output is at least... unknown yet: asked for again when it is; here the text, the table and the tiles' words)
-        if (!fits((double)n + (double)name_bytes + (double)cap * 4.0 + (double)R * 21.0 + (double)G * 8.0 + (double)n_tiles * 12.0, held)) return no_room();
+        const double comp = job.bgzf ? (double)job.bgzf_bytes + (double)job.members->size() * (double)sizeof(yif::InfMember) : 0.0; // (the inflate scratch's)
+        if (!fits((double)n + comp + (double)name_bytes + (double)cap * 4.0 + (double)R * 21.0 + (double)G * 8.0 + (double)n_tiles * 12.0, held)) return no_room();
         return YACRD_OK;
     }
 
@@ -871,8 +885,42 @@ struct SeqRun {
         return YACRD_OK;
     }
 
-    // the text into HBM; the lines of every segment counted as it lands; then the scan of the tiles' counts
-    int move_and_count()
+    // BGZF in: the compressed file into HBM, its members inflated into the text buffer; the decoder's status and the text's last
+    // byte come home; then the lines of every tile in one launch
+    int inflate_text()
+    {
+        InflateDevice d;
+        if (const int rc = inflate_device_open(e, job.bgzf_bytes, job.members->data(), job.members->size(), &d)) return rc;
+        if (!iev.add(2)) HIP_TRY(why_not_added());
+        HIP_TRY(hipMemsetAsync(S.text.as<char>() + n, 0, 64, e->stream));
+        const double t0 = now_ms();
+        TextSource comp;
+        comp.mem = job.bgzf;
+        const int moved = move_text(e, comp, 0, job.bgzf_bytes, reinterpret_cast<char *>(d.comp), d.fresh, job.n_threads, [](u64, u64, u64) {});
+        if (moved == 3) return fail(YACRD_ENOMEM, "sequence text to HBM: no pinned memory");
+        if (moved) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
+        inf_h2d_ms = (float)(now_ms() - t0);
+        HIP_TRY(hipEventRecord(iev[0], e->stream));
+        if (const int rc = inflate_device_run(e, d, e->stream, S.text.as<unsigned char>(), n)) return rc;
+        HIP_TRY(hipEventRecord(iev[1], e->stream));
+        HIP_TRY(hipMemcpyAsync((void *)(h_ctl + 2), d.status, sizeof(u32), hipMemcpyDeviceToHost, e->stream));
+        if (n) HIP_TRY(hipMemcpyAsync((void *)(h_ctl + 3), S.text.as<char>() + (n - 1), 1, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipGetLastError());
+        inf_kernel_ms = ev_ms(iev[0], iev[1]);
+        if ((u32)h_ctl[2]) return inflate_not_taken((u32)h_ctl[2]);
+        if (n && (char)(h_ctl[3] & 255u) != '\n') return fail(YACRD_EFALLBACK, "the text's last line has no newline: the host loop's case");
+        ga.avail = n, ga.tile0 = 0;
+        bool ok = ev_open();
+        if (n_tiles) hipLaunchKernelGGL(yk::sq_lines_kernel, dim3((u32)n_tiles), dim3(yk::kGpT), 0, e->stream, ga);
+        ok = ok && ev_close();
+        t_text = now_ms();
+        if (!ok) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
+        return YACRD_OK;
+    }
+
+    // the text into HBM; the lines of every segment counted as it lands
+    int move_text_in()
     {
         HIP_TRY(hipMemsetAsync(S.text.as<char>() + n, 0, 64, e->stream));
         bool ok = true;
@@ -888,8 +936,15 @@ struct SeqRun {
         if (moved == 2) return fail(YACRD_EINVAL, "read error in the sequence file");
         if (moved == 3) return fail(YACRD_ENOMEM, "sequence text to HBM: no pinned memory");
         if (moved || !ok) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
+        return YACRD_OK;
+    }
+
+    // the text into HBM (moved, or inflated there) with its tiles' lines counted; then the scan of the tiles' counts
+    int move_and_count()
+    {
+        if (const int rc = job.bgzf ? inflate_text() : move_text_in()) return rc;
         ga.avail = n;
-        ok = ev_open();
+        bool ok = ev_open();
         if (const int rc = scan_u32_to_u64(e, S.tile_nl.as<u32>(), n_tiles, S.tile_l0.as<u64>(), S.part)) return rc;
         ok = ok && ev_close();
         HIP_TRY(hipMemcpyAsync((void *)h_ctl, S.tile_l0.as<u64>() + n_tiles, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
@@ -1118,6 +1173,11 @@ struct SeqRun {
             g.h2d_ms = 0.f, g.kernel_ms = gz_kernel_ms;
             g.d2h_ms = (float)std::max(0.0, out_busy_ms - put_ms), g.write_ms = (float)put_ms;
         }
+        if (job.gunzip_stats) {
+            yacrd_gunzip_stats &u = *job.gunzip_stats; // (walk_ms: the caller's)
+            u.in_bytes = job.bgzf_bytes, u.out_bytes = n, u.n_members = job.members->size();
+            u.h2d_ms = inf_h2d_ms, u.kernel_ms = inf_kernel_ms, u.d2h_ms = 0.f;
+        }
         if (stats) {
             stats->text_bytes = n, stats->out_bytes = total, stats->n_records = n_rec, stats->n_out_records = n_pieces;
             stats->text_ms = (float)(t_text - t_table), stats->table_ms = (float)(t_table - t_start);
@@ -1229,15 +1289,31 @@ int edit_seq_mem(bool fasta, yacrd_engine *e, int op, const char *text, uint64_t
     return YACRD_OK;
 }
 
+// BGZF in: `text`, `n` are the compressed file; the walk fills `members`, the job's BGZF fields and `n` (the text's bytes)
+int seq_job_bgzf(SeqJob &job, std::vector<yif::InfMember> &members, const char *&text, uint64_t &n, yacrd_gunzip_stats *us)
+{
+    const double t0 = now_ms();
+    u64 total = 0;
+    if (!ybw::walk(reinterpret_cast<const unsigned char *>(text), n, members, &total)) return fail(YACRD_EFALLBACK, "not BGZF: the host reader's");
+    if (us) us->walk_ms = (float)(now_ms() - t0);
+    job.bgzf = text ? text : "", job.bgzf_bytes = n, job.members = &members, job.gunzip_stats = us;
+    text = "", n = total;
+    return YACRD_OK;
+}
+
 int edit_seq_gzip_mem(bool fasta, yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, char **out,
-                      uint64_t *out_bytes, yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs)
+                      uint64_t *out_bytes, yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs, bool bgzf = false, yacrd_gunzip_stats *us = nullptr)
 {
     if (gs) std::memset(gs, 0, sizeof(*gs));
+    if (us) std::memset(us, 0, sizeof(*us));
     if (const int rca = seq_edit_args(fasta, e, op, t, st)) return rca;
     if ((!text && n) || !out || !out_bytes) return fail(YACRD_EINVAL, "null argument");
     *out = nullptr, *out_bytes = 0;
     SeqJob job;
     job.op = op, job.table = t, job.gzip = true, job.gzip_stats = gs, job.fasta = fasta;
+    std::vector<yif::InfMember> members;
+    if (bgzf)
+        if (const int rcw = seq_job_bgzf(job, members, text, n, us)) return rcw;
     TextSource src;
     src.mem = text ? text : "";
     Sink sink;
@@ -1249,6 +1325,7 @@ int edit_seq_gzip_mem(bool fasta, yacrd_engine *e, int op, const char *text, uin
         std::free(sink.mem);
         if (st) std::memset(st, 0, sizeof(*st));
         if (gs) std::memset(gs, 0, sizeof(*gs));
+        if (us) std::memset(us, 0, sizeof(*us));
         return rc;
     }
     *out = sink.mem, *out_bytes = sink.at;
@@ -1256,16 +1333,20 @@ int edit_seq_gzip_mem(bool fasta, yacrd_engine *e, int op, const char *text, uin
 }
 
 int edit_seq_gzip_file(bool fasta, yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, const char *out_path,
-                       yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs)
+                       yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs, bool bgzf = false, yacrd_gunzip_stats *us = nullptr)
 {
     if (gs) std::memset(gs, 0, sizeof(*gs));
+    if (us) std::memset(us, 0, sizeof(*us));
     if (const int rca = seq_edit_args(fasta, e, op, t, st)) return rca;
     if ((!text && n) || !out_path) return fail(YACRD_EINVAL, "null argument");
+    SeqJob job;
+    std::vector<yif::InfMember> members;
+    if (bgzf) // (before a file is made beside out_path: what is not BGZF leaves nothing)
+        if (const int rcw = seq_job_bgzf(job, members, text, n, us)) return rcw;
     struct stat ost;
     if (lstat(out_path, &ost) == 0 && !S_ISREG(ost.st_mode)) return fail(YACRD_EFALLBACK, "the output is not a regular file: the host loop writes it");
     yseg::BesideFile file;
     if (!file.open(out_path)) return fail(YACRD_EFALLBACK, std::string("cannot create a file beside ") + out_path + ": the host loop words the error");
-    SeqJob job;
     job.op = op, job.table = t, job.gzip = true, job.gzip_stats = gs, job.fasta = fasta;
     TextSource src;
     src.mem = text ? text : "";
@@ -1276,6 +1357,7 @@ int edit_seq_gzip_file(bool fasta, yacrd_engine *e, int op, const char *text, ui
     if (rc != YACRD_OK) {
         if (st) std::memset(st, 0, sizeof(*st));
         if (gs) std::memset(gs, 0, sizeof(*gs));
+        if (us) std::memset(us, 0, sizeof(*us));
     }
     return rc;
 }
@@ -1324,6 +1406,27 @@ int yacrd_engine_edit_fasta_gzip_file(yacrd_engine *e, int op, const char *text,
                                       yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs)
 {
     return edit_seq_gzip_file(true, e, op, text, n, t, out_path, st, gs);
+}
+
+int yacrd_engine_edit_fastq_bgzf_mem(yacrd_engine *e, int op, const char *bgzf, uint64_t n, const yacrd_report_table *t, char **out,
+                                     uint64_t *out_bytes, yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs, yacrd_gunzip_stats *us)
+{
+    return edit_seq_gzip_mem(false, e, op, bgzf, n, t, out, out_bytes, st, gs, true, us);
+}
+int yacrd_engine_edit_fastq_bgzf_file(yacrd_engine *e, int op, const char *bgzf, uint64_t n, const yacrd_report_table *t, const char *out_path,
+                                      yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs, yacrd_gunzip_stats *us)
+{
+    return edit_seq_gzip_file(false, e, op, bgzf, n, t, out_path, st, gs, true, us);
+}
+int yacrd_engine_edit_fasta_bgzf_mem(yacrd_engine *e, int op, const char *bgzf, uint64_t n, const yacrd_report_table *t, char **out,
+                                     uint64_t *out_bytes, yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs, yacrd_gunzip_stats *us)
+{
+    return edit_seq_gzip_mem(true, e, op, bgzf, n, t, out, out_bytes, st, gs, true, us);
+}
+int yacrd_engine_edit_fasta_bgzf_file(yacrd_engine *e, int op, const char *bgzf, uint64_t n, const yacrd_report_table *t, const char *out_path,
+                                      yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs, yacrd_gunzip_stats *us)
+{
+    return edit_seq_gzip_file(true, e, op, bgzf, n, t, out_path, st, gs, true, us);
 }
 
 } // extern "C"

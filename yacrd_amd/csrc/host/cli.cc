@@ -17,7 +17,10 @@
 #include <string>
 #include <vector>
 
+#include <fcntl.h>
+#include <sys/mman.h>
 #include <sys/stat.h>
+#include <unistd.h>
 
 #include "../../../include/yacrd_engine.h"
 #include "../../../include/yacrd_host.h"
@@ -418,8 +421,9 @@ int main(int argc, char **argv)
             const yacrd_report_table rt = {bp.n_reads, bp.name_off, bp.names, bp.lengths, bp.bad_offsets, bp.bad_regions, bp.read_type};
             yacrd_seq_edit_stats ss{};
             yacrd_gzip_stats gs{};
+            yacrd_gunzip_stats us{};
             double inflate_ms = 0;
-            bool text_reused = false;
+            bool text_reused = false, dev_inflate = false;
             if (sub_comp == 1) {
                 const auto t_in = std::chrono::steady_clock::now();
                 yacrd_text own{};
@@ -427,10 +431,36 @@ int main(int argc, char **argv)
                 struct stat sa, sb;
                 if (text.data && ::stat(input.c_str(), &sa) == 0 && ::stat(sub_in.c_str(), &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino)
                     tx = &text, text_reused = true;
-                else if (yacrd_text_from_file(sub_in.c_str(), threads == 1 ? 0 : (int)threads, &own) == 0)
-                    tx = &own; // (a file that cannot be inflated: the host loop below words the error)
-                inflate_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count();
-                if (tx) dev_edit = (sub_fa ? yacrd_engine_edit_fasta_gzip_file : yacrd_engine_edit_fastq_gzip_file)(engines[0], op, tx->data, tx->n, &rt, sub_out.c_str(), &ss, &gs);
+                // A BGZF file the detection does not already hold inflated is mapped as it is and inflated on the device
+                // (yacrd_engine_edit_fastq_bgzf_file: the call itself tells BGZF from plain gzip): no host inflate, and the text
+                // crosses the link compressed.  Any other return than OK — plain gzip, a member the device decoder does not take,
+                // a text the editor hands back, no memory — leaves nothing behind and takes the path below, unchanged.
+                // The default, by DESIGN §7h's rows: the slowest `edit` of three with it is under the fastest of three without, on
+                // scrubb and filter, FASTQ and FASTA.  YACRD_NO_DEVICE_INFLATE=1: the path below outright.
+                const char *no_inf = std::getenv("YACRD_NO_DEVICE_INFLATE");
+                if (!tx && !(no_inf && *no_inf == '1')) {
+                    const int fd = ::open(sub_in.c_str(), O_RDONLY);
+                    struct stat sf;
+                    if (fd >= 0 && ::fstat(fd, &sf) == 0 && S_ISREG(sf.st_mode) && sf.st_size > 0) {
+                        void *m = ::mmap(nullptr, (size_t)sf.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+                        if (m != MAP_FAILED) {
+                            dev_edit = (sub_fa ? yacrd_engine_edit_fasta_bgzf_file : yacrd_engine_edit_fastq_bgzf_file)(
+                                engines[0], op, static_cast<const char *>(m), (uint64_t)sf.st_size, &rt, sub_out.c_str(), &ss, &gs, &us);
+                            ::munmap(m, (size_t)sf.st_size);
+                            dev_inflate = dev_edit == YACRD_OK;
+                            if (dev_edit == YACRD_ENOMEM)
+                                for (yacrd_engine *en : engines) (void)yacrd_engine_trim(en);
+                            if (!dev_inflate) dev_edit = YACRD_EFALLBACK;
+                        }
+                    }
+                    if (fd >= 0) ::close(fd);
+                }
+                if (!dev_inflate) {
+                    if (!tx && yacrd_text_from_file(sub_in.c_str(), threads == 1 ? 0 : (int)threads, &own) == 0)
+                        tx = &own; // (a file that cannot be inflated: the host loop below words the error)
+                    inflate_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count();
+                    if (tx) dev_edit = (sub_fa ? yacrd_engine_edit_fasta_gzip_file : yacrd_engine_edit_fastq_gzip_file)(engines[0], op, tx->data, tx->n, &rt, sub_out.c_str(), &ss, &gs);
+                }
                 yacrd_text_free(&own);
             } else {
                 const char *ct = std::getenv("YACRD_COPY_THREADS");
@@ -447,6 +477,10 @@ int main(int argc, char **argv)
                                      "kernels %.1f ms, out %.1f ms\n",
                              sub_fmt, (unsigned long long)ss.n_records, (unsigned long long)ss.n_out_records, (unsigned long long)ss.text_bytes,
                              (unsigned long long)ss.out_bytes, ss.text_ms, ss.table_ms, ss.kernel_ms, ss.out_ms);
+                if (dev_inflate)
+                    std::fprintf(stderr, "[info] device inflate: %llu members, %llu -> %llu bytes, walk %.1f ms, h2d %.1f ms, kernels %.1f ms\n",
+                                 (unsigned long long)us.n_members, (unsigned long long)us.in_bytes, (unsigned long long)us.out_bytes, us.walk_ms,
+                                 us.h2d_ms, us.kernel_ms);
                 if (sub_comp == 1) // (the encoder's line as the host loop's writer words it: the output lay in HBM, nothing went up)
                     std::fprintf(stderr, "[info] device deflate: %llu -> %llu bytes, %llu members (%llu stored), h2d %.1f ms, kernels %.1f ms, "
                                          "d2h %.1f ms, write %.1f ms, inflate %.1f ms, text_reused=%d\n",

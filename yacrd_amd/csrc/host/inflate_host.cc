@@ -1,0 +1,46 @@
+// inflate_host.cc — the device decoder's text (../inflate_block.h) compiled for the host: one thread plays the 64 lanes of
+// a wavefront, member after member.  What the tests without a GPU pin to zlib and what a sanitizer build runs (tools/
+// inflate_check.cc); nobody's fast path (that is codec.cc's, on zlib).
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../../include/yacrd_host.h"
+#include "../bgzf_walk.h"
+#include "../inflate_block.h"
+#include "host_common.h"
+
+extern "C" {
+
+int yacrd_bgzf_decode_host(const char *data, uint64_t n, char **out, uint64_t *out_bytes)
+{
+    if ((!data && n) || !out || !out_bytes) return yh::fail("bad argument");
+    *out = nullptr, *out_bytes = 0;
+    const unsigned char *d = reinterpret_cast<const unsigned char *>(data);
+    std::vector<yif::InfMember> members;
+    uint64_t total = 0;
+    if (!ybw::walk(d, n, members, &total)) return yh::fail("not BGZF");
+    std::unique_ptr<yif::InfShared> sh(new (std::nothrow) yif::InfShared());
+    char *res = (char *)std::malloc((size_t)total + 1);
+    if (!sh || !res) {
+        std::free(res);
+        return yh::fail("host allocation failed");
+    }
+    for (size_t k = 0; k < members.size(); k++) {
+        const yif::InfMember &m = members[k];
+        const unsigned char *t = d + m.in_off + m.csize; // the trailer: inside the member (the walk)
+        const uint32_t crc = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+        const uint32_t st = yif::inf_decode_member(*sh, d + m.in_off, m.csize, m.isize, crc, reinterpret_cast<unsigned char *>(res) + m.out_off);
+        if (st != yif::kInfOk) {
+            std::free(res);
+            return yh::fail("BGZF member " + std::to_string(k) + " not taken: " + yif::inf_status_name(st));
+        }
+    }
+    *out = res, *out_bytes = total;
+    return 0;
+}
+
+} // extern "C"

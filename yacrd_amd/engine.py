@@ -49,6 +49,8 @@ EXPORTED_SYMBOLS = [
     "yacrd_engine_edit_overlaps_gzip_mem", "yacrd_engine_edit_overlaps_gzip_file",
     "yacrd_engine_edit_fastq", "yacrd_engine_edit_fastq_mem", "yacrd_engine_edit_fastq_gzip_mem", "yacrd_engine_edit_fastq_gzip_file",
     "yacrd_engine_edit_fasta", "yacrd_engine_edit_fasta_mem", "yacrd_engine_edit_fasta_gzip_mem", "yacrd_engine_edit_fasta_gzip_file",
+    "yacrd_engine_gunzip_mem", "yacrd_engine_edit_fastq_bgzf_mem", "yacrd_engine_edit_fastq_bgzf_file",
+    "yacrd_engine_edit_fasta_bgzf_mem", "yacrd_engine_edit_fasta_bgzf_file",
     "yacrd_engine_gzip_mem", "yacrd_gzip_writer_open", "yacrd_gzip_writer_write", "yacrd_gzip_writer_sink", "yacrd_gzip_writer_close",
     "yacrd_gzip_writer_abort",
     "yacrd_stream_device_of", "yacrd_stream_group_open", "yacrd_stream_group_sink", "yacrd_stream_group_finish",
@@ -105,6 +107,11 @@ class _SeqEditStats(ctypes.Structure):  # yacrd_seq_edit_stats
 class _GzipStats(ctypes.Structure):
     _fields_ = [("in_bytes", ctypes.c_uint64), ("out_bytes", ctypes.c_uint64), ("n_members", ctypes.c_uint64), ("n_stored", ctypes.c_uint64),
                 ("h2d_ms", ctypes.c_float), ("kernel_ms", ctypes.c_float), ("d2h_ms", ctypes.c_float), ("write_ms", ctypes.c_float)]
+
+
+class _GunzipStats(ctypes.Structure):  # yacrd_gunzip_stats
+    _fields_ = [(n, ctypes.c_uint64) for n in ("in_bytes", "out_bytes", "n_members")] + \
+               [(n, ctypes.c_float) for n in ("walk_ms", "h2d_ms", "kernel_ms", "d2h_ms")]
 
 
 from .host import ByteSink  # noqa: E402  (yacrd_byte_sink: one structure, declared in both headers)
@@ -342,6 +349,12 @@ def load_library():
                    for form in ("", "_mem", "_gzip_mem", "_gzip_file")):
         fa.argtypes = fq.argtypes  # (the FASTA calls take what the FASTQ calls take)
     lib.yacrd_edit_text_free.restype = None
+    lib.yacrd_engine_gunzip_mem.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p),
+                                            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_GunzipStats)]
+    for fmt in ("fastq", "fasta"):  # (the gzip forms' arguments and a trailing yacrd_gunzip_stats)
+        for form in ("mem", "file"):
+            getattr(lib, "yacrd_engine_edit_%s_bgzf_%s" % (fmt, form)).argtypes = \
+                getattr(lib, "yacrd_engine_edit_%s_gzip_%s" % (fmt, form)).argtypes + [ctypes.POINTER(_GunzipStats)]
     lib.yacrd_engine_gzip_mem.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p),
                                           ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_GzipStats)]
     lib.yacrd_gzip_writer_open.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
@@ -862,21 +875,56 @@ class Engine:
         finally:
             self._lib.yacrd_edit_text_free(out)
 
-    def _edit_seq_gzip(self, fmt, op, text, names, lengths, result, out_path):
+    def edit_fastq_bgzf(self, op, blob, names, lengths, result, out_path=None):
+        """yacrd_engine_edit_fastq_bgzf_mem / _file: edit_fastq_gzip over the COMPRESSED file `blob` (BGZF; bytes or anything
+        else with the buffer protocol): it crosses the link as it is and is inflated on the device.  The result is
+        edit_fastq_gzip's for the inflated text; the inflate's stats are in self.gunzip_stats.  Raises NeedsHostParser, with
+        nothing written, also when `blob` is not BGZF or holds a member the device decoder does not take."""
+        return self._edit_seq_gzip("fastq", op, blob, names, lengths, result, out_path, bgzf=True)
+
+    def edit_fasta_bgzf(self, op, blob, names, lengths, result, out_path=None):
+        """yacrd_engine_edit_fasta_bgzf_mem / _file: edit_fastq_bgzf for FASTA."""
+        return self._edit_seq_gzip("fasta", op, blob, names, lengths, result, out_path, bgzf=True)
+
+    def gunzip(self, data):
+        """yacrd_engine_gunzip_mem: a BGZF stream (bytes) -> its text (bytes), inflated on the device; the stats are in
+        self.gunzip_stats.  Raises NeedsHostParser, with nothing returned, when `data` is not BGZF or holds a member the
+        device decoder does not take (host.text_from_file reads those)."""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        n = int(buf.size)
+        st = _GunzipStats()
+        out, n_out = ctypes.c_void_p(), ctypes.c_uint64()
+        rc = self._lib.yacrd_engine_gunzip_mem(self._h, ctypes.c_void_p(buf.ctypes.data if n else None), n, ctypes.byref(out), ctypes.byref(n_out),
+                                               ctypes.byref(st))
+        del buf
+        if rc == E_FALLBACK:
+            raise NeedsHostParser(self._lib.yacrd_last_error().decode())
+        _check(self._lib, rc)
+        self.gunzip_stats = {f: getattr(st, f) for f, _ in _GunzipStats._fields_}
+        try:
+            return ctypes.string_at(out.value, int(n_out.value)) if n_out.value else b""
+        finally:
+            self._lib.yacrd_edit_text_free(out)
+
+    def _edit_seq_gzip(self, fmt, op, text, names, lengths, result, out_path, bgzf=False):
         t, keep = self._seq_table(names, lengths, result)
-        st, gs = _SeqEditStats(), _GzipStats()
+        st, gs, us = _SeqEditStats(), _GzipStats(), _GunzipStats()
+        more = (ctypes.byref(us),) if bgzf else ()
+        kind = "bgzf" if bgzf else "gzip"
         buf = np.frombuffer(text, dtype=np.uint8)
         n = int(buf.size)
         addr = ctypes.c_void_p(buf.ctypes.data if n else None)
         out, n_out = ctypes.c_void_p(), ctypes.c_uint64()
         if out_path is None:
-            rc = getattr(self._lib, "yacrd_engine_edit_%s_gzip_mem" % fmt)(self._h, int(op), addr, n, t, ctypes.byref(out), ctypes.byref(n_out),
-                                                                           ctypes.byref(st), ctypes.byref(gs))
+            rc = getattr(self._lib, "yacrd_engine_edit_%s_%s_mem" % (fmt, kind))(self._h, int(op), addr, n, t, ctypes.byref(out), ctypes.byref(n_out),
+                                                                                 ctypes.byref(st), ctypes.byref(gs), *more)
         else:
-            rc = getattr(self._lib, "yacrd_engine_edit_%s_gzip_file" % fmt)(self._h, int(op), addr, n, t, os.fsencode(out_path), ctypes.byref(st),
-                                                                            ctypes.byref(gs))
+            rc = getattr(self._lib, "yacrd_engine_edit_%s_%s_file" % (fmt, kind))(self._h, int(op), addr, n, t, os.fsencode(out_path), ctypes.byref(st),
+                                                                                  ctypes.byref(gs), *more)
         del keep, buf
         self._seq_edited(rc, st)
+        if bgzf:
+            self.gunzip_stats = {f: getattr(us, f) for f, _ in _GunzipStats._fields_}
         self.gzip_stats = {f: getattr(gs, f) for f, _ in _GzipStats._fields_}
         if out_path is not None:
             return self.seq_edit_stats, self.gzip_stats

@@ -31,7 +31,7 @@ EXPORTED_SYMBOLS = [
     "yacrd_host_last_error", "yacrd_csr_from_file", "yacrd_csr_from_memory", "yacrd_csr_get",
     "yacrd_csr_find", "yacrd_csr_free", "yacrd_report_write", "yacrd_synth_csr", "yacrd_synth_paf",
     "yacrd_edit_file", "yacrd_edit_file_mt", "yacrd_text_from_file", "yacrd_text_free", "yacrd_report_read", "yacrd_report_get", "yacrd_report_free",
-    "yacrd_edit_file_to", "yacrd_file_compression", "yacrd_bgzf_encode_host", "yacrd_bytes_free", "yacrd_deflate_code_lengths",
+    "yacrd_edit_file_to", "yacrd_file_compression", "yacrd_bgzf_encode_host", "yacrd_bgzf_decode_host", "yacrd_bytes_free", "yacrd_deflate_code_lengths",
     "yacrd_synth_fastq", "yacrd_ingest_stream", "yacrd_ingest_stream_memory", "yacrd_csr_handle_map",
 ]
 
@@ -160,6 +160,7 @@ def load_library():
         lib.yacrd_edit_file_to.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(_BadParts), ctypes.c_int, ctypes.c_void_p]
         lib.yacrd_file_compression.argtypes = [ctypes.c_char_p]
         lib.yacrd_bgzf_encode_host.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)]
+        lib.yacrd_bgzf_decode_host.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)]
         lib.yacrd_bytes_free.argtypes = [ctypes.c_void_p]
         lib.yacrd_bytes_free.restype = None
         lib.yacrd_deflate_code_lengths.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
@@ -360,6 +361,19 @@ def bgzf_encode_host(data):
     data = bytes(data)
     out, n = ctypes.c_void_p(), ctypes.c_uint64()
     _check(lib, lib.yacrd_bgzf_encode_host(data, len(data), ctypes.byref(out), ctypes.byref(n)))
+    try:
+        return ctypes.string_at(out.value, int(n.value))
+    finally:
+        lib.yacrd_bytes_free(out)
+
+
+def bgzf_decode_host(data):
+    """yacrd_bgzf_decode_host: the device decoder's text run by one host thread; the bytes Engine.gunzip gives.  Raises
+    HostError (the message names the cause) for a stream that is not BGZF or holds a member the decoder does not take."""
+    lib = load_library()
+    data = bytes(data)
+    out, n = ctypes.c_void_p(), ctypes.c_uint64()
+    _check(lib, lib.yacrd_bgzf_decode_host(data, len(data), ctypes.byref(out), ctypes.byref(n)))
     try:
         return ctypes.string_at(out.value, int(n.value))
     finally:
