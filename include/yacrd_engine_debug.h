@@ -45,6 +45,16 @@
 /* the screen always runs in its one-item build with the second looks (sliding windows; by default only after a batch that
  * deferred more than a tenth of what it screened); tests, A/B */
 #define YACRD_F_SCREEN_WIDE 2097152u
+/* The long launch takes its H16 reads (129 .. 256 intervals) by read index instead of from the plan's class list, so it is
+ * launched FIRST and the plan and every other register class run beside it on the engine's side stream (csrc/screen_reg.h:
+ * screen_block_rows).  By default only where it pays: a long batch (the two-items build, at least 400 000
+ * reads) that is at least 7/8 H16 with no read beyond 512 intervals, as far as the previous run's counts (or, without a
+ * prediction, intervals / reads) say.  YACRD_F_SCREEN_DIRECT: wherever it is legal, at any batch size and without that rule; it
+ * implies the long-launch build as YACRD_F_ALWAYS_DEFER | YACRD_F_SCREEN_ITEMS_2 does; tests.  YACRD_F_NO_SCREEN_DIRECT: never; A/B.
+ * With YACRD_F_TIMING_FULL a direct run's yacrd_timing.plan_ms is the plan's own bracket on the side stream (it no longer
+ * precedes the sweeps), and sweep_small_ms spans the screen and everything beside it. */
+#define YACRD_F_SCREEN_DIRECT 8388608u
+#define YACRD_F_NO_SCREEN_DIRECT 16777216u
 
 /* the device parser's sort on its own (yacrd_amd/csrc/radix_sort.h): (key, value) pairs in host memory, sorted in place by key,
  * stable; keys must be below key_bound (it decides the number of passes); tests only */
@@ -80,6 +90,9 @@ void yacrd_debug_peer_copy_counts(uint64_t out[3]);
  * yacrd_pinned_alloc's, which belongs to the caller.  Tests: what is live before an engine, stream or writer is made is live
  * again once it is closed. */
 void yacrd_debug_live_bytes(uint64_t out[2]);
+/* runs of this engine whose long launch went out direct (YACRD_F_SCREEN_DIRECT above) since it was created; a batch that is
+ * run again (a missed prediction) counts each time */
+uint64_t yacrd_debug_direct_runs(const yacrd_engine *e);
 /* YACRD_TEST_REPORT_SEGMENT=<bytes> (environment, tests; read at every call): the size of the segments in which
  * yacrd_engine_write_report[_mem] brings the formatted text home, instead of 64 MiB (csrc/gpu_report_write.hip: kReportSegment;
  * 1 .. 2^30).  The bytes written do not depend on it: tests/test_gpu_report_write.py cuts lines at hundreds of borders. */

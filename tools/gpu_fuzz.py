@@ -20,7 +20,9 @@ budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 rng = np.random.default_rng(int(time.time()) & 0xFFFF)
 t0, rounds, reads, ones = time.time(), 0, 0, 0
 cflags = (yacrd_amd.F_ALWAYS_DEFER | (yacrd_amd.F_SCREEN_ITEMS_2 if os.environ.get("YACRD_FUZZ_ITEMS2") else 0)
-          | (yacrd_amd.F_SCREEN_WIDE if os.environ.get("YACRD_FUZZ_WIDE") else 0))
+          | (yacrd_amd.F_SCREEN_WIDE if os.environ.get("YACRD_FUZZ_WIDE") else 0)
+          # the long launch by read index, plan and other classes beside it (csrc/screen_reg.h: screen_block_rows), at any size
+          | (yacrd_amd.F_SCREEN_DIRECT if os.environ.get("YACRD_FUZZ_DIRECT") else 0))
 if os.environ.get("YACRD_FUZZ_ONE_LAUNCH"):  # the one-launch form of short batches (csrc/one_batch.h) where it applies
     cflags = yacrd_amd.F_ONE_LAUNCH
 with yacrd_amd.Engine(flags=cflags) as e, yacrd_amd.Engine(flags=yacrd_amd.F_NO_PREFILTER) as ref:
@@ -50,4 +52,6 @@ with yacrd_amd.Engine(flags=cflags) as e, yacrd_amd.Engine(flags=yacrd_amd.F_NO_
         rounds += 1
         reads += R
         ones += int(e.timing().get("one_launch", 0))
-print("gpu_fuzz: %d rounds, %d reads, all bit-exact%s" % (rounds, reads, " (%d batches as one launch)" % ones if ones else ""))
+    direct = e.direct_runs()
+print("gpu_fuzz: %d rounds, %d reads, all bit-exact%s%s" % (rounds, reads, " (%d batches as one launch)" % ones if ones else "",
+                                                          " (%d runs direct)" % direct if direct else ""))

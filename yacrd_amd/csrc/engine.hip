@@ -6,6 +6,8 @@
 //   -> exact general path (LDS scratch for rejected reads; global scratch for huge reads)
 //   -> compact_classify (single-pass scan) -> sync.
 //   Rare redo: degenerate reads too large for LDS, or bad_regions too small.
+// A long batch of mostly H16 reads goes out DIRECT (choose_direct): the long launch first, by read index, on the engine's
+// stream; plan, counts and the other register classes beside it on the side stream; joined in front of the rest.
 // Several engines may share a device (one host thread each): their batches pipeline.
 // run_on_device is that sequence as a list of phases; each phase takes the engine and the Run (engine_internal.h).
 #include "engine_internal.h"
@@ -464,6 +466,16 @@ int launch_plan(yacrd_engine *e, Run &R)
     const u32 plan_mode = (u32)((e->flags & YACRD_F_FORCE_GENERAL) ? 1
                                 : (e->flags & (YACRD_F_WAVE_ONLY | YACRD_F_FORCE_LDS_SORT)) ? 2
                                 : (e->flags & YACRD_F_NO_HALVES) ? 3 : 0);
+    if (R.direct) { // beside the long launch, on the side stream: 256-thread workgroups (plan_compact.h), H16 counted only
+        constexpr u32 per_wg = (u32)(yk::kPlanSidePer * yk::kPlanSideBlock);
+        if (R.full) HIP_TRY(hipEventRecord(e->ev[EV_PLAN0], e->side));
+        hipLaunchKernelGGL((yk::plan_kernel<yk::kPlanSidePer, yk::kPlanSideBlock>), dim3((n_reads + per_wg - 1) / per_wg), dim3(yk::kPlanSideBlock), 0, e->side,
+                           R.d_off, n_reads, R.lists, R.ctr, plan_mode | yk::kPlanDirect, e->ctrl2[other].as<u32>(), (u32)(R.other_bytes / 4),
+                           e->counts.as<u32>(), e->mrec.as<uint4>(), R.mrec_cap1, R.mrec_cap2);
+        e->ctrl_clean[other] = R.other_bytes;
+        if (R.full) HIP_TRY(hipEventRecord(e->ev[EV_PLAN], e->side));
+        return YACRD_OK;
+    }
     if (n_reads < yk::kPlanSmallReads)
         hipLaunchKernelGGL((yk::plan_kernel<1, yk::kPlanSmallBlock>), dim3((n_reads + yk::kPlanSmallBlock - 1) / yk::kPlanSmallBlock),
                            dim3(yk::kPlanSmallBlock), 0, e->stream, R.d_off, n_reads, R.lists, R.ctr, plan_mode, e->ctrl2[other].as<u32>(), (u32)(R.other_bytes / 4), e->counts.as<u32>(), e->mrec.as<uint4>(), R.mrec_cap1, R.mrec_cap2);
@@ -483,16 +495,60 @@ int launch_plan(yacrd_engine *e, Run &R)
 // prediction is validated against the real counts at the final sync (a class that was not predicted
 // is launched then and the compaction redone).  Streams of similar batches never pay the
 // mid-pipeline sync.
-int size_launches(yacrd_engine *e, Run &R)
+bool prediction_holds(const yacrd_engine *e, const Run &R)
 {
-    const uint64_t n_reads64 = R.n_reads64;
     // (round 6: a batch that holds reads beyond the workgroup classes is predicted too — until then it always waited for the
     // plan's counts, ~20 us of configs[3]'s step —: the device-wide screen is launched for the previous run's count and intervals
     // of such reads, which must come out the same, and must have left nothing to the host-driven sort)
     const bool big_predictable = !(e->flags & YACRD_F_NO_PREFILTER) && e->pred.fb_big == 0;
-    R.predicted = e->pred_valid && e->pred_reads == n_reads64 && e->pred_iv == R.n_iv &&
-                  (e->pred.n[yk::CLS_GENERAL] == 0 || big_predictable) &&
-                  !(e->flags & (YACRD_F_FORCE_GENERAL | YACRD_F_NO_PREDICTION));
+    return e->pred_valid && e->pred_reads == R.n_reads64 && e->pred_iv == R.n_iv &&
+           (e->pred.n[yk::CLS_GENERAL] == 0 || big_predictable) &&
+           !(e->flags & (YACRD_F_FORCE_GENERAL | YACRD_F_NO_PREDICTION));
+}
+
+// Whether this run's long launch goes out DIRECT (screen_reg.h: screen_block_rows; Run::direct).  Legal where the register
+// classes' launch is the long-launch build — deferring, two items, no second looks, the default prefilter and plan mode —;
+// worth it where nearly every row of the launch holds an H16 read and nothing needs the host between the plan and the
+// follow-on step.  A wrong guess costs idle rows, never a result.  R.predicted is set.
+bool choose_direct(yacrd_engine *e, const Run &R)
+{
+    const uint32_t f = e->flags;
+    if (f & YACRD_F_NO_SCREEN_DIRECT) return false;
+    // flags that pin another path or another build, and the counting prefilter (one more writer of the control block)
+    if (f & (YACRD_F_FORCE_GENERAL | YACRD_F_WAVE_ONLY | YACRD_F_FORCE_LDS_SORT | YACRD_F_NO_HALVES | YACRD_F_NO_PREFILTER |
+             YACRD_F_COUNT_PREFILTERED | YACRD_F_NO_DEFER | YACRD_F_SCREEN_ITEMS_1 | YACRD_F_SCREEN_WIDE))
+        return false;
+    const bool forced = (f & YACRD_F_SCREEN_DIRECT) != 0;
+    if (!forced) {
+        // the build launch_register_classes would choose must be the two-items one
+        if (!(f & YACRD_F_ALWAYS_DEFER) && e->nodefer_left != 0) return false;
+        if (!(f & YACRD_F_SCREEN_ITEMS_2) && e->wide_left != 0) return false;
+        if (R.n_reads64 < (uint64_t)yk::kPlanSmallReads) return false;
+        if (R.predicted) {
+            const yk::Counters &p = e->pred;
+            const u64 fused_iv = p.iv[yk::CLS_R16] + p.iv[yk::CLS_H16];
+            if (!(f & YACRD_F_SCREEN_ITEMS_2) && fused_iv < 40000000ull) return false;
+            if (!(f & YACRD_F_ALWAYS_DEFER) && fused_iv < defer_min_intervals()) return false;
+            if (8 * (u64)p.n[yk::CLS_H16] < 7 * R.n_reads64) return false;
+            if (p.n[yk::CLS_MED1] || p.n[yk::CLS_MED2] || p.n[yk::CLS_GENERAL]) return false;
+        } else {
+            // no counts yet: the mean read is H16 and the batch is long enough for the two-items build whatever its classes hold
+            if (!(f & YACRD_F_SCREEN_ITEMS_2) && R.n_iv < 40000000ull) return false;
+            if (!(f & YACRD_F_ALWAYS_DEFER) && R.n_iv < defer_min_intervals()) return false;
+            if (!(R.n_iv > 128 * R.n_reads64 && R.n_iv <= 256 * R.n_reads64)) return false;
+        }
+    }
+    if (e->side == nullptr) {
+        if (e->streams.add(1)) e->side = e->streams[1];
+        else (void)hipGetLastError(); // (no side stream: the list form, as ever)
+    }
+    return e->side != nullptr;
+}
+
+// (a direct run: the counter copy and the wait are the side stream's, the long launch is already running)
+int size_launches(yacrd_engine *e, Run &R)
+{
+    const uint64_t n_reads64 = R.n_reads64;
     LaunchSet &ls = R.ls;
     if (R.predicted) {
         // Register-sort classes: one workgroup per 4..16 reads, so the grid is sized for the
@@ -509,8 +565,9 @@ int size_launches(yacrd_engine *e, Run &R)
         }
         R.big_n = e->pred.n[yk::CLS_GENERAL], R.big_iv = e->pred.iv[yk::CLS_GENERAL];
     } else {
-        HIP_TRY(hipMemcpyAsync(e->h_ctr(), R.ctr, sizeof(yk::Counters), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
+        const hipStream_t hs = R.direct ? e->side : e->stream;
+        HIP_TRY(hipMemcpyAsync(e->h_ctr(), R.ctr, sizeof(yk::Counters), hipMemcpyDeviceToHost, hs));
+        HIP_TRY(hipStreamSynchronize(hs));
         R.c0 = *e->h_ctr();
         for (int cls = 0; cls < yk::CLS_GENERAL; cls++) {
             ls.n[cls] = R.c0.n[cls];
@@ -518,6 +575,12 @@ int size_launches(yacrd_engine *e, Run &R)
             ls.iv[cls] = R.c0.iv[cls];
         }
         R.big_n = R.c0.n[yk::CLS_GENERAL], R.big_iv = R.c0.iv[yk::CLS_GENERAL];
+    }
+    if (R.direct) {
+        // the direct launch covers every read of the batch: H16 is never "missing" or "larger than its grid" (recover,
+        // finish_pending), whatever the plan counts, and its list — which nobody wrote — is never asked for
+        ls.n[yk::CLS_H16] = (u32)std::min<u64>((n_reads64 + 15) & ~(u64)15, 0xFFFFFFFFull);
+        ls.hint[yk::CLS_H16] = R.n_reads;
     }
     for (int cls = 0; cls < yk::CLS_GENERAL; cls++)
         if (ls.n[cls] && (R.dom_cls < 0 || ls.iv[cls] > ls.iv[R.dom_cls])) R.dom_cls = cls;
@@ -527,58 +590,64 @@ int size_launches(yacrd_engine *e, Run &R)
 // Kernel-level timing.  An event costs ~3 us of stream time, so by default only the class
 // with the most intervals (the dominant kernel) is bracketed; YACRD_F_TIMING_FULL brackets
 // every launched class and the phases.
-hipError_t before_class(yacrd_engine *e, Run &R, int cls)
+// `hs`: the stream the class is launched on (the engine's; a direct run's minor register classes: the side stream).
+hipError_t before_class(yacrd_engine *e, Run &R, int cls, hipStream_t hs)
 {
     if (!R.timing_on || !(R.full || cls == R.dom_cls)) return hipSuccess;
-    if (R.n_cls_ev > 0 && R.full) { // the previous class's end mark is this one's begin mark
+    if (R.n_cls_ev > 0 && R.full && R.cls_ev_stream == hs) { // the previous class's end mark is this one's begin mark
         R.cls_b[cls] = R.n_cls_ev - 1;
         return hipSuccess;
     }
     R.cls_b[cls] = R.n_cls_ev;
-    return hipEventRecord(e->ev_cls[R.n_cls_ev++], e->stream);
+    R.cls_ev_stream = hs;
+    return hipEventRecord(e->ev_cls[R.n_cls_ev++], hs);
 }
-hipError_t mark_class(yacrd_engine *e, Run &R, int cls)
+hipError_t mark_class(yacrd_engine *e, Run &R, int cls, hipStream_t hs)
 {
     if (!R.timing_on || !(R.full || cls == R.dom_cls)) return hipSuccess;
     R.cls_e[cls] = R.n_cls_ev;
-    return hipEventRecord(e->ev_cls[R.n_cls_ev++], e->stream);
+    R.cls_ev_stream = hs;
+    return hipEventRecord(e->ev_cls[R.n_cls_ev++], hs);
 }
 
 // The register-sort classes of `set`: the row / half-wavefront classes R2..H16 in one launch, the one-read-per-wavefront
 // classes W2..W16 a launch each.  (What they reject is looked at after the final sync.)  `again`: a second pass.
+// A direct run (launch_direct_screen has the H16 reads): the first pass goes out on the side stream, in the long-launch build.
 int launch_register_classes(yacrd_engine *e, Run &R, const LaunchSet &set, bool again)
 {
     yk::Counters *ctr = R.ctr;
     const bool fuse = !(e->flags & YACRD_F_FORCE_LDS_SORT);
+    const hipStream_t hs = (R.direct && !again) ? e->side : e->stream;
     if (fuse) {
         yk::FusedArgs fa;
         fa.base = R.base; // (list / list_n / first: per class, from the table below)
         // R16 / H16: the healthy-read screen, the rest left to finish_compact_kernel — unless the last
         // batches failed the screen too often (e->nodefer_left: see conclude_run)
         const u64 fused_iv = set.iv[yk::CLS_R16] + set.iv[yk::CLS_H16];
-        const bool defer = R.prefilter && !(e->flags & YACRD_F_NO_DEFER) &&
-                           ((e->flags & YACRD_F_ALWAYS_DEFER) ||
-                            (fused_iv >= defer_min_intervals() && e->nodefer_left == 0));
+        const bool defer = R.direct || (R.prefilter && !(e->flags & YACRD_F_NO_DEFER) &&
+                                        ((e->flags & YACRD_F_ALWAYS_DEFER) ||
+                                         (fused_iv >= defer_min_intervals() && e->nodefer_left == 0)));
         // two groups of list entries per wavefront in the screened classes when the launch streams from
         // HBM (more than the 256 MiB Infinity Cache holds): twice the loads in flight per wavefront
         // ... unless the last screened batch left more than a tenth of its reads to the sort: then the one-item build WITH
         // the second looks (sliding windows, screen_reg.h) takes the next kProbeEvery - 1 — dovetail ends spread by
         // hundreds of positions need them (configs[1] at sigma = 100: 79 % decided against 95 %; configs[2] at 300: 79 %
         // against 97 %), reads that do not are a tenth faster without (conclude_run: wide_left)
-        const bool wide = defer && !(e->flags & YACRD_F_SCREEN_ITEMS_2) && ((e->flags & YACRD_F_SCREEN_WIDE) || e->wide_left > 0);
+        const bool wide = defer && !R.direct && !(e->flags & YACRD_F_SCREEN_ITEMS_2) && ((e->flags & YACRD_F_SCREEN_WIDE) || e->wide_left > 0);
         const int items = !defer ? 1
                           : (wide || (e->flags & YACRD_F_SCREEN_ITEMS_1)) ? 1
-                          : ((e->flags & YACRD_F_SCREEN_ITEMS_2) || fused_iv >= 40000000ull) ? 2 : 1;
+                          : (R.direct || (e->flags & YACRD_F_SCREEN_ITEMS_2) || fused_iv >= 40000000ull) ? 2 : 1;
         e->last_items = (uint32_t)items;
         e->last_wide = wide;
         if (!again) e->last_build = !defer ? 0 : wide ? 3 : items;
         fa.base.over_list = nullptr; // (the deferring build marks its reads in counts[])
         fa.base.over_count = nullptr;
         fa.n_entries = 0;
+        fa.direct = 0, fa.n_reads = R.n_reads;
         u32 blocks = 0;
         bool has_dom = false;
         for (int cls = yk::CLS_R2; cls <= yk::CLS_H16; cls++) {
-            if (!set.n[cls]) continue;
+            if (!set.n[cls] || (R.direct && cls == yk::CLS_H16)) continue; // (a direct run's H16 reads: launch_direct_screen)
             const u32 per = yk::sweep_group_reads_per_block(cls, defer ? yk::kDeferWaves : yk::kFusedWaves) *
                             (cls >= yk::CLS_R16 ? (u32)items : 1u);
             blocks += (set.n[cls] + per - 1) / per;
@@ -591,7 +660,7 @@ int launch_register_classes(yacrd_engine *e, Run &R, const LaunchSet &set, bool 
             has_dom |= cls == R.dom_cls;
         }
         if (fa.n_entries) {
-            const bool mark = R.timing_on && (R.full || has_dom);
+            const bool mark = R.timing_on && (R.full || has_dom) && !R.direct; // (a direct run's bracket is the long launch's)
             // the launch's build, chosen once: sorting; screening with one item, with the second looks, with two items
             void (*kernel)(yk::FusedArgs) = yk::sweep_small_fused_kernel;
             u32 threads = 64 * yk::kFusedWaves;
@@ -605,7 +674,7 @@ int launch_register_classes(yacrd_engine *e, Run &R, const LaunchSet &set, bool 
             // (configs[1], three engines: 47.0 us per batch with turns, 38.8 without), and a sweep that fills the GPU leaves
             // the next one little room to overlap anyway (its bracket grows by ~1 us: what the roofline then reports is on
             // the safe side).)
-            hipExtLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, e->stream, mark ? e->ev_cls[22] : (hipEvent_t) nullptr,
+            hipExtLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, hs, mark ? e->ev_cls[22] : (hipEvent_t) nullptr,
                                   mark ? e->ev_cls[23] : (hipEvent_t) nullptr, 0, fa);
             if (mark) R.fused_marked = true;
             if (defer && (set.n[yk::CLS_R16] || set.n[yk::CLS_H16])) R.screened = true;
@@ -613,24 +682,49 @@ int launch_register_classes(yacrd_engine *e, Run &R, const LaunchSet &set, bool 
     }
     for (int cls = fuse ? yk::CLS_W2 : yk::CLS_R2; cls <= yk::CLS_W16; cls++) { // register sort per lane group
         if (!set.n[cls]) continue;
-        HIP_TRY(before_class(e, R, cls));
+        HIP_TRY(before_class(e, R, cls, hs));
         yk::SweepArgs sa = list_sweep_args(R, R.list_of(cls), &ctr->n[cls]);
         sa.first = set.first[cls];
         if (!fuse) { // YACRD_F_FORCE_LDS_SORT
             const u32 grid = (u32)std::min<uint64_t>(set.n[cls], (uint64_t)e->num_cu * 32);
-            hipLaunchKernelGGL((yk::sweep_lds_kernel<64, (int)yk::kSmallEvents>), dim3(grid), dim3(64), 0, e->stream, sa);
+            hipLaunchKernelGGL((yk::sweep_lds_kernel<64, (int)yk::kSmallEvents>), dim3(grid), dim3(64), 0, hs, sa);
         } else {
             switch (cls) {
-            case yk::CLS_W2: yk::launch_sweep_group<64, 2>(sa, set.n[cls], e->stream); break;
-            case yk::CLS_W4: yk::launch_sweep_group<64, 4>(sa, set.n[cls], e->stream); break;
-            case yk::CLS_W8: yk::launch_sweep_group<64, 8>(sa, set.n[cls], e->stream); break;
-            default: yk::launch_sweep_group<64, 16>(sa, set.n[cls], e->stream); break;
+            case yk::CLS_W2: yk::launch_sweep_group<64, 2>(sa, set.n[cls], hs); break;
+            case yk::CLS_W4: yk::launch_sweep_group<64, 4>(sa, set.n[cls], hs); break;
+            case yk::CLS_W8: yk::launch_sweep_group<64, 8>(sa, set.n[cls], hs); break;
+            default: yk::launch_sweep_group<64, 16>(sa, set.n[cls], hs); break;
             }
         }
-        HIP_TRY(mark_class(e, R, cls));
+        HIP_TRY(mark_class(e, R, cls, hs));
     }
-    if (R.full && R.timing_on) HIP_TRY(hipEventRecord(e->ev[EV_SMALL], e->stream));
+    // (a direct run's first pass: run_on_device records the mark behind the join)
+    if (R.full && R.timing_on && hs == e->stream) HIP_TRY(hipEventRecord(e->ev[EV_SMALL], e->stream));
     return YACRD_OK;
+}
+
+// A direct run's long launch: every H16 read of the batch by its index, four rows per wavefront (screen_reg.h:
+// screen_block_rows), on the engine's stream and in front of everything else — it reads no list and no class count.
+void launch_direct_screen(yacrd_engine *e, Run &R)
+{
+    yk::FusedArgs fa;
+    fa.base = R.base;
+    fa.base.over_list = nullptr;
+    fa.base.over_count = nullptr;
+    fa.n_entries = 1;
+    fa.cls[0] = (u32)yk::CLS_H16;
+    fa.block_end[0] = R.n_reads / 4u + (R.n_reads % 4u ? 1u : 0u);
+    fa.first[0] = 0;
+    fa.list[0] = nullptr;
+    fa.list_n[0] = nullptr;
+    fa.direct = 1, fa.n_reads = R.n_reads;
+    const bool mark = R.timing_on; // (start / stop events attached to the launch: no packets of their own)
+    hipExtLaunchKernelGGL(yk::sweep_small_fused_defer2_kernel, dim3(fa.block_end[0]), dim3(64), 0, e->stream, mark ? e->ev_cls[22] : (hipEvent_t) nullptr,
+                          mark ? e->ev_cls[23] : (hipEvent_t) nullptr, 0, fa);
+    if (mark) R.fused_marked = true;
+    R.screened = true;
+    e->last_items = 2, e->last_wide = false, e->last_build = 2;
+    e->direct_runs++;
 }
 
 // A workgroup class (k = 0: M1, 1: M2), the screen and its fallback fused.  Two launches (round 6, profiles/r06/m_*): the
@@ -729,11 +823,11 @@ int launch_workgroup_classes(yacrd_engine *e, Run &R, const LaunchSet &set, bool
     for (int k = 0; k < 2; k++) {
         const int cls = k == 0 ? yk::CLS_MED1 : yk::CLS_MED2;
         if (!set.n[cls]) continue;
-        HIP_TRY(before_class(e, R, cls));
+        HIP_TRY(before_class(e, R, cls, e->stream));
         const int rc = fused_screen ? launch_workgroup_class_fused_screen(e, R, set, k, again)
                                     : launch_workgroup_class_chain(e, R, set, k, again);
         if (rc) return rc;
-        HIP_TRY(mark_class(e, R, cls));
+        HIP_TRY(mark_class(e, R, cls, e->stream));
     }
     if (R.full && R.timing_on) HIP_TRY(hipEventRecord(e->ev[EV_MED], e->stream));
     return YACRD_OK;
@@ -802,7 +896,8 @@ int launch_device_wide_screen_on(yacrd_engine *e, Run &R, u32 count, u64 iv_big,
 // sweeps), join in front of the follow-on step (join_device_wide_screen, called behind them).
 int launch_device_wide_screen(yacrd_engine *e, Run &R)
 {
-    const bool can_fork = R.big_n != 0 && R.prefilter && !(e->flags & YACRD_F_FORCE_GENERAL);
+    // (a direct run's side stream and fork / join events are taken: its device-wide screen goes out behind the join)
+    const bool can_fork = R.big_n != 0 && R.prefilter && !(e->flags & YACRD_F_FORCE_GENERAL) && !R.direct;
     if (can_fork && e->side == nullptr) {
         if (e->streams.add(1)) e->side = e->streams[1];
         else (void)hipGetLastError(); // (no side stream: the launches go out behind the other classes', as until round 5)
@@ -988,11 +1083,10 @@ int run_on_device(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u3
         rc = launch_one_batch(e, R);
         return rc ? rc : hand_over(e, R, defer);
     }
-    rc = launch_plan(e, R);
-    if (!rc) rc = size_launches(e, R);
-    if (rc) return rc;
     R.timing_on = !(e->flags & YACRD_F_NO_TIMING);
     if ((e->flags & YACRD_F_TIMING_SAMPLED) && !R.full && (e->run_seq++ % 8u) != 0) R.timing_on = false;
+    R.predicted = prediction_holds(e, R);
+    R.direct = choose_direct(e, R);
     struct MissGuard { // (a miss found by THIS call is reported by its conclude_run and forgotten when the call returns)
         yacrd_engine *e;
         bool before;
@@ -1004,17 +1098,42 @@ int run_on_device(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u3
         bool joined = false;
         ~SideGuard()
         {
-            if (R.big_beside && !joined) (void)hipStreamSynchronize(e->side);
+            if ((R.big_beside || R.direct) && !joined) (void)hipStreamSynchronize(e->side);
         }
     } side_guard{e, R};
     e->prev_build = e->last_build;
     e->last_build = -1;
-    if (R.full) HIP_TRY(hipEventRecord(e->ev[EV_S0], e->stream));
-    rc = launch_device_wide_screen(e, R);
-    if (!rc) rc = launch_sweeps(e, R, R.ls);
-    if (!rc) rc = join_device_wide_screen(e, R);
-    if (rc) return rc;
-    side_guard.joined = true;
+    if (R.direct) {
+        // DIRECT: the long launch first, on the engine's stream; beside it, behind the fork, the plan (an unpredicted run:
+        // and the host's wait for its counts) and the other register classes; the engine's stream joins them in front of
+        // the workgroup classes, the device-wide screen and the follow-on step.  Ordering is by the two events alone.
+        HIP_TRY(hipEventRecord(e->ev_sync[EVS_FORK], e->stream));
+        if (R.full) HIP_TRY(hipEventRecord(e->ev[EV_S0], e->stream));
+        launch_direct_screen(e, R);
+        HIP_TRY(hipStreamWaitEvent(e->side, e->ev_sync[EVS_FORK], 0));
+        rc = launch_plan(e, R);
+        if (!rc) rc = size_launches(e, R);
+        if (!rc) rc = launch_register_classes(e, R, R.ls, false);
+        if (rc) return rc;
+        HIP_TRY(hipEventRecord(e->ev_sync[EVS_JOIN], e->side));
+        HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_sync[EVS_JOIN], 0));
+        side_guard.joined = true;
+        if (R.full && R.timing_on) HIP_TRY(hipEventRecord(e->ev[EV_SMALL], e->stream));
+        rc = launch_workgroup_classes(e, R, R.ls, false);
+        if (!rc) launch_rejected_medium(e, R, R.ls);
+        if (!rc) rc = join_device_wide_screen(e, R); // (nothing was forked for it: its launches go out here)
+        if (rc) return rc;
+    } else {
+        rc = launch_plan(e, R);
+        if (!rc) rc = size_launches(e, R);
+        if (rc) return rc;
+        if (R.full) HIP_TRY(hipEventRecord(e->ev[EV_S0], e->stream));
+        rc = launch_device_wide_screen(e, R);
+        if (!rc) rc = launch_sweeps(e, R, R.ls);
+        if (!rc) rc = join_device_wide_screen(e, R);
+        if (rc) return rc;
+        side_guard.joined = true;
+    }
     if (R.full) HIP_TRY(hipEventRecord(e->ev[EV_GEN], e->stream));
     rc = launch_compact(e, R); // the follow-on step: scan + compact + classify
     if (rc) return rc;
@@ -1084,12 +1203,13 @@ int conclude_run(yacrd_engine *e, const Run &R, float extra_ms)
     t.plan_ms = t.sweep_small_ms = t.sweep_medium_ms = t.sweep_general_ms = t.compact_ms = 0.f;
     t.total_ms = 0.f;
     if (full) {
-        t.plan_ms = ev_ms(e->ev[EV_START], e->ev[EV_PLAN]);
+        // (a direct run: the plan's own bracket on the side stream — it runs beside the long launch, not in front of it)
+        t.plan_ms = ev_ms(e->ev[R.direct ? EV_PLAN0 : EV_START], e->ev[EV_PLAN]);
         t.sweep_small_ms = ev_ms(e->ev[EV_S0], e->ev[EV_SMALL]);
         t.sweep_medium_ms = ev_ms(e->ev[EV_SMALL], e->ev[EV_MED]);
         t.sweep_general_ms = ev_ms(e->ev[EV_MED], e->ev[EV_GEN]);
         t.compact_ms = ev_ms(e->ev[EV_GEN], e->ev[EV_COMPACT]);
-        t.total_ms = (predicted ? ev_ms(e->ev[EV_START], e->ev[EV_COMPACT])
+        t.total_ms = ((predicted || R.direct) ? ev_ms(e->ev[EV_START], e->ev[EV_COMPACT])
                                 : t.plan_ms + ev_ms(e->ev[EV_S0], e->ev[EV_COMPACT])) + extra_ms;
     }
     t.n_small = 0;
@@ -1351,6 +1471,8 @@ int yacrd_debug_last_input_csr(yacrd_engine *e, uint64_t *n_reads, uint64_t *n_i
 }
 
 /* include/yacrd_engine_debug.h: what DevBuf / PinBuf hold, process-wide (tests) */
+uint64_t yacrd_debug_direct_runs(const yacrd_engine *e) { return e ? e->direct_runs : 0; }
+
 void yacrd_debug_live_bytes(uint64_t out[2])
 {
     out[0] = yke::live_bytes()[0].load();

@@ -171,7 +171,7 @@ inline hipError_t why_not_added()
     return e != hipSuccess ? e : hipErrorUnknown;
 }
 
-enum { EV_START = 0, EV_PLAN, EV_S0, EV_SMALL, EV_MED, EV_GEN, EV_COMPACT, EV_X0, EV_X1, EV_H2D0, EV_H2D1, EV_D2H0, EV_D2H1, EV_COUNT }; // yacrd_engine::ev
+enum { EV_START = 0, EV_PLAN, EV_S0, EV_SMALL, EV_MED, EV_GEN, EV_COMPACT, EV_X0, EV_X1, EV_H2D0, EV_H2D1, EV_D2H0, EV_D2H1, EV_PLAN0, EV_COUNT }; // yacrd_engine::ev (EV_PLAN0: in front of the plan on the side stream, a direct run)
 enum { EVS_DONE = 0, EVS_FORK, EVS_JOIN, EVS_COUNT };                                                                                // yacrd_engine::ev_sync
 
 struct DeviceGuard {
@@ -248,9 +248,13 @@ struct Run {
     u32 big_n = 0; // reads / intervals beyond the workgroup classes the device-wide screen is launched for
     u64 big_iv = 0;
     bool big_beside = false; // ... on the side stream
+    // DIRECT (engine.hip: choose_direct): the long launch takes the H16 reads by index and goes out first on the engine's stream;
+    // the plan and the other register classes run beside it on the side stream, joined in front of the workgroup classes
+    bool direct = false;
     // kernel-level timing: event indices bracketing each class (-1 = not recorded)
     int cls_b[12], cls_e[12];
     int n_cls_ev = 0, dom_cls = -1;
+    hipStream_t cls_ev_stream = nullptr; // the stream of the last class mark (a mark is shared by neighbours on one stream only)
     bool timing_on = false;
     // what went out
     bool fused_marked = false, screened = false, big_screened = false;
@@ -271,10 +275,10 @@ struct yacrd_engine {
     // the events before the streams the buffers were used on (yacrd_engine_destroy has waited for both streams by then).
     yke::Streams streams;           // owns the two below
     hipStream_t stream = nullptr;   // streams[0]
-    hipStream_t side = nullptr;     // streams[1], made by the first batch that needs it: the device-wide screen's launches, beside the workgroup classes' (run_on_device)
+    hipStream_t side = nullptr;     // streams[1], made by the first batch that needs it: the device-wide screen's launches, beside the workgroup classes', or a direct run's plan and minor register classes, beside its long launch (run_on_device)
     yke::Events ev;      // EV_*: the phases of a run, h2d and d2h (default flags: timed)
     yke::Events ev_cls;  // 24, brackets around class kernels (timed)
-    yke::Events ev_sync; // EVS_DONE: hipEventBlockingSync, the final wait of YACRD_F_BLOCKING_WAIT; EVS_FORK: stream -> side (behind the plan); EVS_JOIN: side -> stream (in front of the follow-on step); none timed
+    yke::Events ev_sync; // EVS_DONE: hipEventBlockingSync, the final wait of YACRD_F_BLOCKING_WAIT; EVS_FORK: stream -> side (behind the plan; a direct run: in front of everything); EVS_JOIN: side -> stream (in front of the follow-on step); none timed
     int num_cu = 256;
     bool fused_off = false; // this run: the workgroup classes down the three-launch chain (a fused launch gave up: Counters::fused_gave_up)
     int num_xcc = 0; // XCDs of this device / partition (one_batch_kernel's read-to-XCD map assumes 8)
@@ -313,6 +317,7 @@ struct yacrd_engine {
     bool one_launch_off = false; // (while a batch the one-launch form could not take is run again on the default path)
     int last_build = -1, prev_build = -1; // build of the register classes' launch in the last run / the one before (-1: none; 0 sorting, 1 / 2 screening with one / two items, 3 second looks)
     bool miss_pending = false;            // the run in progress is the synchronous re-run of a batch whose prediction did not hold
+    uint64_t direct_runs = 0;  // runs that went out direct (yacrd_debug_direct_runs)
     uint32_t nodefer_left = 0; // batches the sorting build of the fused launch still takes before the screen is tried again
     // pinned bounce buffers for pageable inputs (yke::h2d), allocated on first use; an event per
     // buffer says when its DMA is done and it may be refilled

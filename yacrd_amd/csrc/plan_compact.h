@@ -24,12 +24,21 @@ constexpr int kPlanSmallBlock = YK_PLAN_SMALL_BLOCK; // threads per workgroup of
 // the device's CUs busy for 9-11 us instead of 7: with the three-dispatch chain of round 3 PER = 1 gives 24.4 us
 // per pipelined batch against 26.6 and 64.5 against 68 us for one batch at a time (round 2, five dispatches,
 // measured it the other way round: 27.9 against 26.0).
+// mode bit kPlanDirect (the long launch takes its H16 reads by index, beside this kernel: screen_reg.h, screen_block_rows):
+// an H16 read is counted — ctr->n / iv[CLS_H16]: timing, the roofline's bytes, the prediction — but gets no list entry and
+// its count word is left alone: the screen, running at the same time, owns it.  That launch is off the critical path and
+// shares the device with the screen's one-wavefront workgroups (6 per SIMD, 144 KB of LDS per CU): BLK = 256 fits beside them,
+// 1 024 threads would wait for a CU to drain.
+constexpr u32 kPlanDirect = 8u, kPlanModeMask = 7u;
+constexpr int kPlanSideBlock = 256, kPlanSidePer = 8;
 template <int PER, int BLK = kPlanBlock>
 __global__ __launch_bounds__(BLK) void plan_kernel(const u64 *off, u32 n_reads, u32 *lists,
-                                                   Counters *ctr, u32 mode, u32 *zero,
+                                                   Counters *ctr, u32 mode_bits, u32 *zero,
                                                    u32 zero_words, u32 *counts, uint4 *mrec, u32 mrec_cap1, u32 mrec_cap2)
 {
     constexpr int kPlanBlock = BLK; // (shadows the long batches' constant)
+    const u32 mode = mode_bits & kPlanModeMask;
+    const bool direct = (mode_bits & kPlanDirect) != 0u;
     for (u32 i = blockIdx.x * kPlanBlock + threadIdx.x; i < zero_words; i += gridDim.x * kPlanBlock)
         zero[i] = 0;
     __shared__ u32 s_cnt[CLS_COUNT];
@@ -103,7 +112,7 @@ __global__ __launch_bounds__(BLK) void plan_kernel(const u64 *off, u32 n_reads, 
 #pragma unroll
     for (int k = 0; k < kPlanPer; k++) {
         const u32 r = blockIdx.x * (u32)kPlanReads + (u32)k * kPlanBlock + threadIdx.x;
-        if (cls[k] != CLS_COUNT) {
+        if (cls[k] != CLS_COUNT && !(direct && cls[k] == CLS_H16)) {
             const u64 pos = s_base[cls[k]] + local[k];
             lists[(u64)cls[k] * n_reads + pos] = r;
             // A read's region count starts out as "closed form: see closed[r]" (round 5): the screen then answers a read

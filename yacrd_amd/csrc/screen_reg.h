@@ -271,12 +271,15 @@ __device__ __forceinline__ bool healthy_screen(const uint4 (&v)[PAIRS], const bo
 // of a short batch (one_batch.h) keeps them in its workgroup's LDS.
 struct VerdictsToGlobal {
     const SweepArgs &a;
+    bool own_count = false; // the direct launch (screen_block_rows): the plan left the read's count word alone, kClosedForm is written here
     __device__ __forceinline__ void closed(u32 r, u32 ra, u32 rb, u32 len) const
     {
         // counts[r] says kClosedForm since the plan kernel: ONE store per decided read, its (a, b) — or, for a read with no
         // bad region at all, the count 0 in four bytes
-        if (ra != 0 || rb != len) a.closed[r] = make_uint2(ra, rb);
-        else a.counts[r] = 0;
+        if (ra != 0 || rb != len) {
+            a.closed[r] = make_uint2(ra, rb);
+            if (own_count) a.counts[r] = kClosedForm;
+        } else a.counts[r] = 0;
         if (a.prefilter == 2) atomicAdd(&a.ctr->prefiltered, 1u);
     }
     __device__ __forceinline__ void deferred(u32 r) const { a.counts[r] = kDeferredMark; }
@@ -444,6 +447,54 @@ __device__ __forceinline__ void screen_block(const SweepArgs &a, u32 block)
         r[t] = active[t] ? a.list[idx] : 0u;
     }
     screen_reads<LANES, ITEMS, WIDE, 1, K, NB, NT, TABW>(a, r, active, VerdictsToGlobal{a});
+}
+
+// Whether a read of n intervals is of class H16: plan_kernel's mode-0 rule 256 < 2 n <= 512 (plan_compact.h), as the direct
+// launch below states it on a read's extent.
+constexpr u32 kH16MinIntervals = 129, kH16MaxIntervals = 256;
+__device__ __forceinline__ bool is_h16(u64 n) { return n >= (u64)kH16MinIntervals && n <= (u64)kH16MaxIntervals; }
+
+// The long launch's workgroup of H16 ROWS: one wavefront, four reads, a 16-lane row each (screen_block<16, 1, false, 32, 32,
+// true> with the extents fetched here).  Two ways to its reads:
+//   * from the plan's class list, rows = list entries first + 4 block .. + 3: list entry, then extent and length, then
+//     intervals — three dependent round trips;
+//   * DIRECT, by the read index: rows = reads first + 4 block .. + 3, a row whose read is not H16 idle.  Two
+//     round trips, no list and no list length read, so the launch does not wait for the plan: the engine starts it first and
+//     runs the plan and the other classes beside it (engine.hip).  The plan then leaves an H16 read's count word to this
+//     launch (VerdictsToGlobal::own_count).  A batch that is mostly H16 loses little to idle rows; any batch comes out right.
+// Either way a row's read goes through the same screen_reads form: the same reads are decided and deferred.
+template <int TABW>
+__device__ __forceinline__ void screen_block_rows(const SweepArgs &a, u32 block, bool direct, u32 n_reads)
+{
+    const u32 grp = lane_id() / 16u;
+    u32 r[1] = {0u};
+    bool active[1] = {false};
+    ReadsKnown<1> k;
+    k.o[0] = 0, k.n[0] = 0, k.len[0] = 0;
+    if (direct) { // (uniform)
+        const u32 r0 = a.first + block * 4u;
+        if (r0 >= n_reads) return;
+        r[0] = r0 + grp;
+        if (r[0] < n_reads) {
+            const ulonglong2 oo = load_extent(a.off + r[0]); // off[r], off[r + 1]: one load
+            k.len[0] = a.len[r[0]];                           // (beside the extent, not behind it: of an idle row as well)
+            active[0] = is_h16(oo.y - oo.x);
+            k.o[0] = oo.x, k.n[0] = (u32)(oo.y - oo.x);
+        }
+        if (__builtin_amdgcn_ballot_w64(active[0]) == 0) return; // uniform: no H16 read among the four
+    } else {
+        const u32 list_n = *a.list_n;
+        const u32 idx0 = a.first + block * 4u;
+        if (idx0 >= list_n) return; // grids may be sized for more reads than the class holds
+        active[0] = idx0 + grp < list_n;
+        if (active[0]) {
+            r[0] = a.list[idx0 + grp];
+            const ulonglong2 oo = load_extent(a.off + r[0]);
+            k.len[0] = a.len[r[0]];
+            k.o[0] = oo.x, k.n[0] = (u32)(oo.y - oo.x);
+        }
+    }
+    screen_reads<16, 1, false, 1, 32, 32, true, TABW>(a, r, active, VerdictsToGlobal{a, direct}, &k);
 }
 
 } // namespace yk

@@ -424,6 +424,8 @@ struct FusedArgs {
     u32 first[5];             // SweepArgs.first per class
     const u32 *list[5];
     const u32 *list_n[5];
+    u32 direct;               // the long launch's H16 rows by read index (screen_reg.h: screen_block_rows): one entry, CLS_H16, no list
+    u32 n_reads;              // ... the batch's reads
 };
 
 template <bool DEFER, int WPB, int ITEMS = 1, bool WIDE = false>
@@ -460,7 +462,7 @@ __device__ __forceinline__ void sweep_small_fused_body(const FusedArgs &f)
         else sweep_group_block<16, 16, WPB>(a, b);
         break;
     default:
-        if constexpr (ROWS) screen_block<16, 1, false, 32, 32, true, TABW>(a, b);
+        if constexpr (ROWS) screen_block_rows<TABW>(a, b, f.direct != 0u, f.n_reads);
         else if constexpr (DEFER) screen_block<32, ITEMS, WIDE>(a, b);
         else sweep_group_block<32, 16, WPB>(a, b);
         break;

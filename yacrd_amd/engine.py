@@ -31,6 +31,13 @@ F_SCREEN_ITEMS_1 = 262144
 F_SCREEN_ITEMS_2 = 524288
 F_NO_FUSED_SCREEN = 1048576
 F_SCREEN_WIDE = 2097152
+F_SCREEN_DIRECT = 8388608  # the long launch takes H16 reads by index, the plan runs beside it: wherever legal (tests) ...
+F_NO_SCREEN_DIRECT = 16777216  # ... never (A/B)
+# debug symbols beside the flags (include/yacrd_engine_debug.h); EXPORTED_SYMBOLS below is yacrd_engine.h's list alone
+DEBUG_SYMBOLS = [
+    "yacrd_debug_sort_pairs", "yacrd_debug_last_counters", "yacrd_debug_last_input_csr", "yacrd_debug_peer_copy_counts",
+    "yacrd_debug_live_bytes", "yacrd_debug_direct_runs",
+]
 F_ONE_LAUNCH = 4194304  # include/yacrd_engine.h: a short batch as ONE kernel launch (csrc/one_batch.h)
 
 # every symbol include/yacrd_engine.h declares
@@ -724,6 +731,13 @@ class Engine:
             v = getattr(c, n)
             out[n] = list(v) if hasattr(v, "__len__") else int(v)
         return out
+
+    def direct_runs(self):
+        """yacrd_debug_direct_runs (tests, tools): runs of this engine whose long launch took its H16 reads by index, beside
+        the plan (F_SCREEN_DIRECT; csrc/screen_reg.h: screen_block_rows)."""
+        self._lib.yacrd_debug_direct_runs.restype = ctypes.c_uint64
+        self._lib.yacrd_debug_direct_runs.argtypes = [ctypes.c_void_p]
+        return int(self._lib.yacrd_debug_direct_runs(self._h))
 
     def _type_table(self, names, read_type):
         """(names, read_type) -> a yacrd_type_table and what keeps its memory alive; names: str or bytes, one per read."""
