@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import edit_fastq_cases as fq
 import yacrd_amd
 from edit_fasta_cases import (BASES_FIRST, CHIMERIC, NOT_COVERED, OPS, OP_EXTRACT, OP_FILTER, OP_SCRUBB, OP_SPLIT, Table, _regions, fallback_cases,
                               fuzz_cases, host_loop, lay_out, restate)
@@ -76,6 +77,69 @@ def test_fuzz_zero_fallbacks(engine, tmp_path):
             assert (st["text_bytes"], st["out_bytes"], st["n_records"], st["n_out_records"]) == (len(text), len(want), n_in, n_out), (tag, op)
         n += 1
     assert n >= 150
+
+
+# ---- one pipeline, two formats ---------------------------------------------------------------------------------------------------
+def _fastq_records(out):
+    lines = out.split(b"\n")
+    return [(lines[i][1:].partition(b" ")[0], lines[i][1:].partition(b" ")[2], lines[i + 1]) for i in range(0, len(lines) - 1, 4)]
+
+
+def _fasta_records(out):
+    recs = []
+    for chunk in out.split(b">")[1:]:
+        head, _, body = chunk.partition(b"\n")
+        recs.append((head.partition(b" ")[0], head.partition(b" ")[2], body.replace(b"\n", b"")))
+    return recs
+
+
+@pytest.fixture(scope="module")
+def same_reads():
+    """260 reads of 1 to 400 bases (the plan crosses a workgroup), their table — types as the oracle derives them from the regions —,
+    the reads as FASTQ, and what a FASTA of them is laid out from"""
+    import oracle
+    rng = random.Random(20250117)
+    heads, seqs, quals, names, lens, regs = [], [], [], [], [], []
+    for i in range(260):
+        n = rng.randint(1, 400)
+        name = b"r%d" % i + bytes(rng.choice(b"abcXYZ.:|/-") for _ in range(rng.randint(0, 12)))  # (no '_': a cut piece's name is no read's)
+        heads.append(name + (b" " + fq._token(rng, rng.randint(1, 30)) if rng.random() < 0.5 else b""))
+        seqs.append(fq._bases(rng, n)), quals.append(fq._quals(rng, n))
+        if rng.random() < 0.75:  # (else: absent from the table)
+            names.append(name), lens.append(n), regs.append(fq._regions(rng, rng.choice(fq._SHAPES), n))
+    table = Table(names, lens, regs, [oracle.type_of_read(l, r, 0.4) for l, r in zip(lens, regs)])
+    fastq = b"".join(b"@" + h + b"\n" + s + b"\n+\n" + q + b"\n" for h, s, q in zip(heads, seqs, quals))
+    return heads, seqs, table, fastq
+
+
+@pytest.mark.parametrize("width", [80, "ragged"])
+def test_fastq_and_fasta_of_the_same_reads_agree(engine, same_reads, width):
+    """the two instantiations of the shared plan and copy kernels, on the same reads and the same table: the same output
+    records under the same names with the same bases, for all four ops; input lines of 80 bases (the closed form) and ragged
+    ones (the search).  Each output is what the restatement of its format says, and what oracle/editors.py says"""
+    from oracle import editors as oracle_editors
+    heads, seqs, table, fastq = same_reads
+    rng = random.Random(5)
+    fasta = b"".join(b">" + h + b"\n" + lay_out(rng, s, width) for h, s in zip(heads, seqs))
+    names, lengths, bo, br, rt = table.arrays()
+    ot = fq.oracle_table(table)
+    assert ot is not None
+    read_names = {h.partition(b" ")[0] for h in heads}
+    n_cut = 0
+    for op in OPS:
+        got_q = engine.edit_fastq_text(op, fastq, names, lengths, (bo, br, rt))
+        got_a = engine.edit_fasta_text(op, fasta, names, lengths, (bo, br, rt))
+        want_q = oracle_editors.edit_fastq(fq.OP_NAMES[op], fastq, ot, 0.4)
+        assert got_q == want_q and got_q == fq.restate(fastq, op, table)[0], op
+        assert got_a == restate(fasta, op, table)[0], op
+        rq, ra, ro = _fastq_records(got_q), _fasta_records(got_a), _fastq_records(want_q)
+        assert len(rq) > 20, op
+        assert [r[0] for r in ra] == [r[0] for r in rq] == [r[0] for r in ro], op
+        assert [r[2] for r in ra] == [r[2] for r in rq] == [r[2] for r in ro], op
+        copied = [k for k, r in enumerate(rq) if r[0] in read_names]
+        assert [ra[k][1] for k in copied] == [rq[k][1] for k in copied] == [ro[k][1] for k in copied], op  # (a cut FASTA piece drops it)
+        n_cut += len(rq) - len(copied)
+    assert n_cut > 100
 
 
 # ---- rows and words: every length against every input width -------------------------------------------------------------------

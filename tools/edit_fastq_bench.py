@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/edit_fastq_bench.py --parent-bin PATH [--fasta] [--reads R] [--overlaps O] [--runs K] [--ops scrubb,filter] [--forms plain,gzip1,bgzf] [--json PATH]
+"""tools/edit_fastq_bench.py --parent-bin PATH [--parent-again] [--fasta] [--reads R] [--overlaps O] [--runs K] [--ops scrubb,filter] [--forms plain,gzip1,bgzf] [--json PATH]
 scrubb / filter on a FASTQ through the COMMAND, the parent commit's `yacrd` against this tree's, on a synthetic Sequel FASTQ
 (50 000 reads: about 1 GB) in /dev/shm, output there too:
     yacrd -i s.paf -o r.yacrd -c 3 -n 0.4 <op> -i reads.fastq[.gz] -o out.fastq[.gz]
@@ -15,7 +15,9 @@ The figures compared are the `edit` stage of YACRD_CLI_TIMING — slowest (b) ag
 output is compared with the parent's (gzip: the inflated bytes when the streams differ).  One JSON line per op and form,
 appended to --json (default profiles/edit_fastq.json).
 --fasta: the same reads as FASTA, 80 bases a line (reads.fasta[.gz]): the device path is yacrd_engine_edit_fasta, its line
-"[info] device fasta editor:", the default --json profiles/edit_fasta.json."""
+"[info] device fasta editor:", the default --json profiles/edit_fasta.json.
+--parent-again: a second series of the parent behind the new one ("parent_again" in the row): what drifted meanwhile shows.
+Where the parent has a device editor too, the figure to compare is the `kernels ... ms` of the info lines, not the stage."""
 import argparse, gzip, json, os, re, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -30,6 +32,7 @@ ap.add_argument("--ops", default="scrubb,filter")
 ap.add_argument("--forms", default="plain,gzip1,bgzf")
 ap.add_argument("--parent-bin", default=None)
 ap.add_argument("--fasta", action="store_true")
+ap.add_argument("--parent-again", action="store_true")
 ap.add_argument("--json", default=None)
 a = ap.parse_args()
 kind = "fasta" if a.fasta else "fastq"
@@ -118,6 +121,7 @@ try:
             made.extend([old, new])
             parent = run(a.parent_bin, op, src, old)
             mine = run(new_bin, op, src, new)
+            again = run(a.parent_bin, op, src, old) if a.parent_again else None
             assert any(l.startswith(editor_line) for l in mine[-1]["info"]), "the device editor did not run"
             assert same(old, new, False) or (form != "plain" and same(old, new, True)), "the new path's output differs from the parent's"
             worst_new, best_old = max(r["edit_s"] for r in mine), min(r["edit_s"] for r in parent)
@@ -125,6 +129,8 @@ try:
                    "out_bytes": os.path.getsize(new), "parent": parent, "new": mine, "edit_stage_slowest_new_s": worst_new,
                    "edit_stage_fastest_parent_s": best_old, "ratio": round(best_old / worst_new, 2),
                    "wall_slowest_new_s": max(r["wall_s"] for r in mine), "wall_fastest_parent_s": min(r["wall_s"] for r in parent)}
+            if again:
+                row["parent_again"] = again
             line = json.dumps(row)
             print(line, flush=True)
             with open(a.json, "a") as f:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/edit_overlaps_bench.py [--reads R] [--overlaps O] [--runs K] [--op filter|extract] [--json PATH]
+"""tools/edit_overlaps_bench.py [--parent-again] [--reads R] [--overlaps O] [--runs K] [--op filter|extract] [--json PATH]
 filter / extract on an OVERLAP file, host loop against device editor, on a synthetic PAF in /dev/shm (output there too);
 K timed runs of each after one warm-up:
   (a) host     yacrd_edit_file: the one-thread loop (seconds, GB/s of input)
@@ -15,7 +15,8 @@ with the same synthetic PAF as gzip level 1 (one stream) and as BGZF, K timed ru
                the gzip writer (its "[info] device deflate:" line)
   (b) new      this tree's yacrd — the detection's text reused, edited and deflated in HBM (its "[info] device editor + deflate:" line, on stdout)
 and the `edit` stage of YACRD_CLI_TIMING as the figure compared: slowest (b) against fastest (a).  Every output is compared
-with the parent's, byte for byte.  One JSON line per form (appended to --json when given)."""
+with the parent's, byte for byte.  One JSON line per form (appended to --json when given).
+--parent-again: a second series of the parent behind the new one ("parent_again" in the row): what drifted meanwhile shows."""
 import argparse, json, os, re, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -30,6 +31,7 @@ ap.add_argument("--op", default="filter")
 ap.add_argument("--json", default=None)
 ap.add_argument("--gzip", action="store_true")
 ap.add_argument("--parent-bin", default=None)
+ap.add_argument("--parent-again", action="store_true")
 ap.add_argument("--forms", default="gzip1,bgzf")
 a = ap.parse_args()
 op = {"filter": host.OP_FILTER, "extract": host.OP_EXTRACT}[a.op]
@@ -105,11 +107,15 @@ def gzip_bench():
                 return rows
             parent = run(a.parent_bin, old)
             mine = run(new_bin, new)
+            if a.parent_again:
+                again = run(a.parent_bin, old)
             assert same(old, new), "the new path's file differs from the parent's"
             worst_new, best_old = max(r["edit_s"] for r in mine), min(r["edit_s"] for r in parent)
             row = {"reads": a.reads, "overlaps": a.overlaps, "op": a.op, "form": form, "text_bytes": size, "gz_in_bytes": os.path.getsize(src),
                    "gz_out_bytes": os.path.getsize(new), "make_input_s": round(made_s, 2), "parent": parent, "new": mine,
                    "edit_stage_slowest_new_s": worst_new, "edit_stage_fastest_parent_s": best_old, "ratio": round(best_old / worst_new, 2)}
+            if a.parent_again:
+                row["parent_again"] = again
             line = json.dumps(row)
             print(line, flush=True)
             if a.json:

@@ -252,6 +252,19 @@ __device__ __forceinline__ u32 block_or(u32 v, u32 *sc)
     return r;
 }
 template <int T>
+__device__ __forceinline__ u32 block_add(u32 v, u32 *sc)
+{
+    v = wave_incl_add(v); // (lane 63: the wavefront's sum)
+    if (T == 64) return __shfl(v, 63, 64);
+    if (lane_id() == 63) sc[threadIdx.x >> 6] = v;
+    __syncthreads();
+    u32 r = 0;
+#pragma unroll
+    for (u32 w = 0; w < T / 64; w++) r += sc[w];
+    __syncthreads();
+    return r;
+}
+template <int T>
 __device__ __forceinline__ u32 block_max(u32 v, u32 *sc)
 {
     v = wave_max(v);

@@ -1,6 +1,7 @@
-// edit_table.h — the name table the editors share: gpu_edit.hip (overlap files) and gpu_seq_edit.hip (FASTQ).  The reads'
-// names uploaded once; an open-addressing table keyed by the name bytes (gp_hash), a slot names a read, an id is compared
-// against the uploaded bytes.  ed_lookup answers the read's type, ed_find the read itself.
+// edit_table.h — the name table the editors share: gpu_edit.hip (overlap files) and gpu_seq_edit.hip (FASTQ and FASTA).  The
+// reads' names uploaded once (EdTableOwner, which holds the buffers); an open-addressing table keyed by the name bytes
+// (gp_hash), a slot names a read, an id is compared against the uploaded bytes.  ed_lookup answers the read's type, ed_find
+// the read itself.
 #pragma once
 #include "gpu_text.h"
 
@@ -62,3 +63,32 @@ __device__ __forceinline__ u32 ed_find(const EdTable &tab, const Text &t, u64 p,
 }
 
 } // namespace yk
+
+namespace yke {
+
+// The table's buffers in HBM: a member of an editor's scratch, so they stay with the engine and go with yacrd_engine_trim /
+// destroy.  upload: R reads' names (name_bytes of them), name offsets and types -> HBM and the table of `cap` slots (a power of
+// two, >= 2 R) over the names, on the engine's stream; the caller waits for the stream.  No read or no name byte: nothing of
+// that is copied, and without a read nothing is launched.
+struct EdTableOwner {
+    DevBuf names, name_off, types, slots;
+    int upload(yacrd_engine *e, const char *h_names, const uint64_t *h_name_off, const uint8_t *h_type, u64 R, u64 name_bytes, u64 cap, yk::EdTable *tab)
+    {
+        HIP_TRY(names.reserve((size_t)name_bytes + 64));
+        HIP_TRY(name_off.reserve((size_t)(R + 1) * sizeof(u64)));
+        HIP_TRY(types.reserve((size_t)R + 64));
+        HIP_TRY(slots.reserve((size_t)cap * sizeof(u32)));
+        HIP_TRY(hipMemsetAsync(slots.p, 0, (size_t)cap * sizeof(u32), e->stream));
+        tab->names = names.as<unsigned char>(), tab->name_off = name_off.as<u64>(), tab->type = types.as<unsigned char>();
+        tab->slots = slots.as<u32>(), tab->mask = (u32)(cap - 1), tab->n_reads = (u32)R;
+        if (!R) return YACRD_OK;
+        if (name_bytes)
+            if (const int rch = h2d(e, names.p, h_names, (size_t)name_bytes)) return rch;
+        if (const int rch = h2d(e, name_off.p, h_name_off, (size_t)(R + 1) * sizeof(u64))) return rch;
+        if (const int rch = h2d(e, types.p, h_type, (size_t)R)) return rch;
+        hipLaunchKernelGGL(yk::ed_table_kernel, dim3((u32)((R + 255) / 256)), dim3(256), 0, e->stream, *tab);
+        return YACRD_OK;
+    }
+};
+
+} // namespace yke

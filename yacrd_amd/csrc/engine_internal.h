@@ -415,6 +415,21 @@ int gzip_device_open(yacrd_engine *e, u64 max_blocks, GzDevice *g);
 int gzip_device_encode(yacrd_engine *e, const GzDevice &g, hipStream_t st, const unsigned char *d_text, u64 n, bool last, int which,
                        hipEvent_t k0, hipEvent_t k1, volatile u64 *h_bytes, volatile u64 *h_stored);
 void gzip_device_close(yacrd_engine *e);
+struct GzHold { // the engine's encoder buffers are one edit's, from its gzip_device_open until it ends
+    yacrd_engine *e = nullptr;
+    ~GzHold()
+    {
+        if (e) gzip_device_close(e);
+    }
+};
+// what an editor that deflated its output where it lay reports: `busy_ms` the way out as a whole, `put_ms` the sink's part of it
+inline void fill_gzip_stats(yacrd_gzip_stats *g, u64 in_bytes, u64 out_bytes, u64 members, u64 stored, float kernel_ms, double busy_ms, double put_ms)
+{
+    if (!g) return;
+    g->in_bytes = in_bytes, g->out_bytes = out_bytes, g->n_members = members, g->n_stored = stored;
+    g->h2d_ms = 0.f, g->kernel_ms = kernel_ms; // (the text lies in HBM already)
+    g->d2h_ms = (float)(busy_ms > put_ms ? busy_ms - put_ms : 0.0), g->write_ms = (float)put_ms; // (d2h: with the waits for the encoder)
+}
 // a BGZF stream that lies in HBM -> its text in HBM (gpu_inflate.hip; used by gpu_seq_edit.hip).  open takes the engine's
 // inflate scratch for a stream of comp_bytes and the members the host's walk found (bgzf_walk.h), uploads the member table and
 // zeroes the status word on the engine's stream; the caller then moves the stream's bytes to d.comp (comp_bytes + 64 bytes

@@ -333,7 +333,8 @@ constexpr u64 kSegBytes = (u64)(kTextChunk * kTextSeg); // the mover's segment: 
 
 struct EditScratch { // the editor's buffers; they stay with the engine (grow-only), go with yacrd_engine_trim / destroy
     static constexpr yacrd_engine::Slot kScratchSlot = yacrd_engine::kEdit;
-    DevBuf text, out, names, name_off, types, slots, kbits, tile, tile_kept, tile_cin, tile_off, ctl, part;
+    DevBuf text, out, kbits, tile, tile_kept, tile_cin, tile_off, ctl, part;
+    EdTableOwner table; // the reads' names and types, the id table over them
     PinBuf pin; // two output pieces + the per-segment control words
 };
 
@@ -378,14 +379,6 @@ struct EditJob {
     bool use_mirror = false; // edit from the parser's mirror (the same file: checked by the caller)
     bool gzip = false;       // the sink takes BGZF members of the kept bytes instead of the kept bytes
     yacrd_gzip_stats *gzip_stats = nullptr;
-};
-
-struct GzHold { // the engine's encoder buffers are this edit's until it ends
-    yacrd_engine *e = nullptr;
-    ~GzHold()
-    {
-        if (e) gzip_device_close(e);
-    }
 };
 
 // One edit on its way through the device: built once per call (run_edit), its phases in the order they run.
@@ -456,7 +449,7 @@ struct EditRun {
         // HBM: the text (unless the parser's mirror serves), as many bytes again for what is kept, a bit per byte, the table
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const double have = (double)free_b + (double)S.text.cap + (double)S.out.cap + (double)S.kbits.cap + (double)S.names.cap + (double)S.slots.cap;
+            const double have = (double)free_b + (double)S.text.cap + (double)S.out.cap + (double)S.kbits.cap + (double)S.table.names.cap + (double)S.table.slots.cap;
             const double need = (job.use_mirror ? 0.0 : (double)n) + (double)nl * 1.125 + (double)nl / 8.0 * 1.125 + (double)name_bytes * 1.125 +
                                 (double)cap * 4.0 + (double)R * 10.0 + (double)n_tiles * 40.0 + (double)((size_t)64 << 20) +
                                 (double)gz_blocks * (double)ydf::kSlot * 3.0 * 1.125; // (the members' slots and two batches of members)
@@ -496,21 +489,8 @@ struct EditRun {
     int upload_table()
     {
         const yacrd_type_table &tt = *job.types;
-        HIP_TRY(S.names.reserve((size_t)name_bytes + 64));
-        HIP_TRY(S.name_off.reserve((size_t)(R + 1) * sizeof(u64)));
-        HIP_TRY(S.types.reserve((size_t)R + 64));
-        HIP_TRY(S.slots.reserve((size_t)cap * sizeof(u32)));
-        HIP_TRY(hipMemsetAsync(S.slots.p, 0, (size_t)cap * sizeof(u32), e->stream));
         yk::EdTable tab{};
-        tab.names = S.names.as<unsigned char>(), tab.name_off = S.name_off.as<u64>(), tab.type = S.types.as<unsigned char>();
-        tab.slots = S.slots.as<u32>(), tab.mask = (u32)(cap - 1), tab.n_reads = (u32)R;
-        if (R) {
-            if (name_bytes)
-                if (const int rch = h2d(e, S.names.p, tt.names, (size_t)name_bytes)) return rch;
-            if (const int rch = h2d(e, S.name_off.p, tt.name_off, (size_t)(R + 1) * sizeof(u64))) return rch;
-            if (const int rch = h2d(e, S.types.p, tt.read_type, (size_t)R)) return rch;
-            hipLaunchKernelGGL(yk::ed_table_kernel, dim3((u32)((R + 255) / 256)), dim3(256), 0, e->stream, tab);
-        }
+        if (const int rc = S.table.upload(e, tt.names, tt.name_off, tt.read_type, R, name_bytes, cap, &tab)) return rc;
         HIP_TRY(hipStreamSynchronize(e->stream));
         t_table = now_ms();
         ga.text = job.use_mirror ? e->mirror.p : S.text.as<unsigned char>();
@@ -550,17 +530,7 @@ struct EditRun {
     // base[from, upto) in HBM -> the sink through the two pinned pieces: one flies while the other is written (host/segment_pump.h)
     void bring_home(const char *base, u64 from, u64 upto)
     {
-        struct Dma {
-            EditRun &r;
-            const char *text;
-            bool start(u64 i, char *dst, u64 at, size_t len)
-            {
-                return hipMemcpyAsync(dst, text + at, len, hipMemcpyDeviceToHost, r.wstream()) == hipSuccess &&
-                       hipEventRecord(r.wev[i & 1], r.wstream()) == hipSuccess;
-            }
-            bool wait(u64 i) { return !r.bad.load() && hipEventSynchronize(r.wev[i & 1]) == hipSuccess; }
-            void drain() { (void)hipStreamSynchronize(r.wstream()); }
-        } dma{*this, base + from};
+        HomeLink dma{base + from, wstream(), {wev[0], wev[1]}, &bad};
         const int rc = yseg::pump(upto - from, kOutPiece, S.pin.as<char>(), dma, sink, [&](auto put) {
             const double tp = now_ms();
             put();
@@ -706,12 +676,7 @@ struct EditRun {
         if (h_status) return fail(YACRD_EINTERNAL, "overlap editor: the mark and the pack pass disagree");
         if ((job.gzip ? gz_text : sink.at) != h_bytes) return fail(YACRD_EINTERNAL, "overlap editor: fewer bytes written than kept");
         if (job.gzip && gz_got != gz_sent) return fail(YACRD_EINTERNAL, "overlap editor: a batch of members was not fetched");
-        if (job.gzip_stats) {
-            yacrd_gzip_stats &g = *job.gzip_stats;
-            g.in_bytes = gz_text, g.out_bytes = sink.at, g.n_members = gz_members, g.n_stored = gz_stored;
-            g.h2d_ms = 0.f, g.kernel_ms = gz_kernel_ms; // (the text lies in HBM already)
-            g.d2h_ms = (float)std::max(0.0, out_busy_ms - put_ms), g.write_ms = (float)put_ms; // (d2h: with the waits for the encoder)
-        }
+        fill_gzip_stats(job.gzip_stats, gz_text, sink.at, gz_members, gz_stored, gz_kernel_ms, out_busy_ms, put_ms);
         if (stats) {
             stats->text_bytes = n;
             stats->kept_bytes = h_bytes;

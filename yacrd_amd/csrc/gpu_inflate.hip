@@ -144,17 +144,7 @@ int yacrd_engine_gunzip_mem(yacrd_engine *e, const char *bgzf, uint64_t n_bytes,
         s.kernel_ms = ev_ms(ev[0], ev[1]);
         if (*h_status) return inflate_not_taken(*h_status);
         const double t2 = now_ms();
-        struct Dma {
-            yacrd_engine *e;
-            Events &wev;
-            const char *text;
-            bool start(u64 i, char *dst, u64 at, size_t k)
-            {
-                return hipMemcpyAsync(dst, text + at, k, hipMemcpyDeviceToHost, e->stream) == hipSuccess && hipEventRecord(wev[i & 1], e->stream) == hipSuccess;
-            }
-            bool wait(u64 i) { return hipEventSynchronize(wev[i & 1]) == hipSuccess; }
-            void drain() { (void)hipStreamSynchronize(e->stream); }
-        } dma{e, wev, S.text.as<char>()};
+        HomeLink dma{S.text.as<char>(), e->stream, {wev[0], wev[1]}};
         yseg::Sink sink;
         sink.mem = res; // (sized here: total bytes)
         const int rc = yseg::pump(total, kHomePiece, S.pin.as<char>(), dma, sink, [](auto put) { put(); });

@@ -22,6 +22,7 @@
 // are read twice, 8 bytes per region and 12 per read are written beside the text.  The text then goes home in segments
 // through two pinned buffers: segment i + 1 crosses the link while segment i is written.
 #include "engine_internal.h"
+#include "gpu_text.h"
 #include "host/beside_file.h"
 #include "host/segment_pump.h"
 
@@ -305,19 +306,7 @@ int send_home(yacrd_engine *e, ReportWriteScratch &S, u64 total, Sink &sink, dou
     const u64 seg = std::min<u64>(report_segment(), total);
     HIP_TRY(S.pin.reserve((size_t)(2 * seg)));
     // (the loop and its segment arithmetic: host/segment_pump.h, which a stand-alone program runs under the sanitizers)
-    struct Dma {
-        yacrd_engine *e;
-        ReportWriteScratch &S;
-        hipError_t bad = hipSuccess;
-        bool start(u64 i, char *dst, u64 at, size_t len)
-        {
-            bad = hipMemcpyAsync(dst, S.text.as<char>() + at, len, hipMemcpyDeviceToHost, e->stream);
-            if (bad == hipSuccess) bad = hipEventRecord(S.dma[i & 1], e->stream);
-            return bad == hipSuccess;
-        }
-        bool wait(u64 i) { return (bad = hipEventSynchronize(S.dma[i & 1])) == hipSuccess; }
-        void drain() { (void)hipStreamSynchronize(e->stream); }
-    } dma{e, S};
+    HomeLink dma{S.text.as<char>(), e->stream, {S.dma[0], S.dma[1]}};
     const int rc = yseg::pump(total, seg, S.pin.as<char>(), dma, sink, [&](auto put) {
         const double t0 = now_ms();
         put();

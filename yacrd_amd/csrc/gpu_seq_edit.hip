@@ -1,6 +1,11 @@
 // gpu_seq_edit.hip — scrubb / split / filter / extract on a FASTQ or FASTA file with the decision, the sizing and the gather on the GPU
-// (include/yacrd_engine.h: yacrd_engine_edit_fastq, yacrd_engine_edit_fasta).  FASTQ first; what FASTA does otherwise stands
-// in front of its kernels below: it shares the mover, the line index, the id table, the way home and the deflate step.
+// (include/yacrd_engine.h: yacrd_engine_edit_fastq, yacrd_engine_edit_fasta).  One pipeline with a format plugged in: the
+// mover, the line index, the id table, the op's rule (seq_verdict), the plan and copy kernels (seq_plan_kernel<Format, EMIT>,
+// seq_copy_kernel<Format>), the way home and the deflate step know no format.  A format is a struct — Fastq, Fasta — with its
+// kernel arguments (SeqArgs and what is its own), its piece descriptor, record<EMIT>() (where a record's lines lie, its
+// canonical form, name, key, description and byte arithmetic), at() (byte k of a piece) and a per-thread cursor; on the host,
+// its front in SeqRun::size_output (what numbers the records) and its message.  The stages are told for FASTQ here; what
+// FASTA does otherwise stands in front of its kernels below.
 //
 // Reference: Scrubbing::run (src/editor/scrubbing.rs:156-236), Split::run (src/editor/split.rs), Filter::run and Extract::run on
 // sequence files: a record's key — the first whitespace token of its name — is looked up in the bad-part table (an id it does not
@@ -45,6 +50,8 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
+#include <type_traits>
 
 using namespace yke;
 
@@ -66,27 +73,38 @@ struct SqPiece { // one record of the output
 };
 static_assert(sizeof(SqPiece) == 48, "host code sizes the piece buffer by this");
 
-struct SqArgs {
+struct SeqArgs { // what the kernels of both formats read; SqArgs and FaArgs (below) add what is theirs
     const unsigned char *text;
-    u64 n;     // bytes of text
-    u64 avail; // bytes [0, avail) have landed (== n for the last segment)
     EdTable tab;
     const u32 *lengths;  // [n_reads]
     const u64 *bad_off;  // [n_reads + 1]
     const u32 *bad_reg;  // [2 * regions]
-    u32 *tile_nl;        // per text tile: its newlines
-    const u64 *tile_l0;  // their exclusive scan
     u64 *line_end;       // [n_lines]: where every newline lies
     u64 n_lines, n_rec;
     u32 *rec_pieces, *rec_bytes;        // per record: output records, output bytes
     const u64 *piece_off, *byte_off;    // their exclusive scans
-    SqPiece *pieces;
     u64 n_pieces, total;                // output records, output bytes
     unsigned char *out;
     unsigned long long *ctl; // [0] status, [1] bytes the copy pass stored
-    u32 tile0;               // the launch's first text tile
     u32 op;
 };
+
+struct SqArgs : SeqArgs {
+    u64 n;     // bytes of text
+    u64 avail; // bytes [0, avail) have landed (== n for the last segment)
+    u32 *tile_nl;        // per text tile: its newlines
+    const u64 *tile_l0;  // their exclusive scan
+    u32 tile0;           // the launch's first text tile
+    SqPiece *pieces;
+};
+static_assert(std::is_trivially_copyable<SqArgs>::value, "a kernel argument by value");
+
+// a thread's status bits -> ctl[0]: ORed over the wavefront, one atomic from lane 0
+__device__ __forceinline__ void seq_status(unsigned long long *ctl, u32 status)
+{
+    status = wave_or(status);
+    if (status && lane_id() == 0) atomicOr(ctl, (unsigned long long)status);
+}
 
 // the tile's newline masks (a u16 per 16 bytes) -> nlm; returns the thread's newline count and ORs a CR into `cr`.  The
 // mirror is padded by 64 zero bytes and the last step is clipped to whole 16-byte pieces inside it; an inner segment's
@@ -114,21 +132,10 @@ __global__ __launch_bounds__(kGpT) void sq_lines_kernel(SqArgs a)
     __shared__ u32 sw[kGpT / 64];
     const u32 gt = a.tile0 + blockIdx.x;
     u32 cr = 0;
-    u32 cnt = sq_stage(a, (u64)gt * (u64)kGpTile, nullptr, cr);
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) cnt += (u32)__shfl_xor((int)cnt, d, 64);
-    cr = wave_or(cr);
-    if (lane_id() == 0) {
-        sw[threadIdx.x >> 6] = cnt;
-        if (cr) atomicOr(a.ctl, (unsigned long long)kSqNeedHost);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u32 tot = 0;
-#pragma unroll
-        for (int w = 0; w < kGpT / 64; w++) tot += sw[w];
-        a.tile_nl[gt] = tot;
-    }
+    const u32 cnt = sq_stage(a, (u64)gt * (u64)kGpTile, nullptr, cr);
+    seq_status(a.ctl, cr ? kSqNeedHost : 0u);
+    const u32 tot = block_add<kGpT>(cnt, sw);
+    if (threadIdx.x == 0) a.tile_nl[gt] = tot;
 }
 
 // ---- index: where every newline lies, in line order ----------------------------------------------------------------------------
@@ -195,165 +202,61 @@ __device__ __forceinline__ void sq_cuts(u32 op, const u32 *reg, u32 n, u32 len, 
     }
 }
 
-// Record r: its canonical form checked, its verdict, its pieces.  EMIT false: the pieces and bytes counted; true: the piece
-// descriptors written.  Returns the status bits.
-template <bool EMIT>
-__device__ __forceinline__ u32 sq_record(const SqArgs &a, u64 r)
+// ---- what becomes of a record: the one place that knows the op's rule -----------------------------------------------------------
+enum : u32 { kSeqDrop = 0, kSeqCopy = 1, kSeqCut = 2 };
+struct SeqVerdict {
+    u32 what;           // kSeqDrop, kSeqCopy: the record as it stands; kSeqCut: at the read's regions
+    u32 type, n_reg, len; // the read's type, regions and length: zeros for an id the table does not hold
+    const u32 *reg;
+};
+// the read named text[key, key + key_len): filter copies a NotBad record, extract any other; scrubb and split drop NotCovered
+// reads, copy a read with no region (scrubb) or a NotBad one (split) and cut every other
+__device__ __forceinline__ SeqVerdict seq_verdict(const SeqArgs &a, u64 key, u32 key_len)
 {
-    const unsigned char *t = a.text;
-    const u64 s = r ? a.line_end[4 * r - 1] + 1 : 0;
-    const u64 e0 = a.line_end[4 * r], e1 = a.line_end[4 * r + 1], e2 = a.line_end[4 * r + 2], e3 = a.line_end[4 * r + 3];
-    if (!EMIT) a.rec_pieces[r] = 0u, a.rec_bytes[r] = 0u;
-    const u64 rec_len = e3 + 1 - s;
-    if (rec_len >= kSqMaxRecord) return kSqNeedHost;
-    if (t[s] != '@' || e0 == s + 1) return kSqNeedHost;
-    u64 sp = e0, key_end = e0; // the first blank; the first whitespace of any kind in front of it
-    for (u64 i = s + 1; i < e0; i++) {
-        const u32 c = t[i];
-        if (c == ' ') {
-            sp = i;
-            break;
-        }
-        if ((c == '\t' || c == '\x0c') && key_end == e0) key_end = i;
-    }
-    if (key_end > sp) key_end = sp;
-    if (sp == s + 1 || sp + 1 == e0) return kSqNeedHost; // (no name; "@name \n": the writer drops the blank)
-    if (e2 != e1 + 2 || t[e1 + 1] != '+') return kSqNeedHost;
-    const u64 seq_len64 = e1 - e0 - 1;
-    if (seq_len64 != e3 - e2 - 1) return kSqNeedHost;
-    const u32 seq_len = (u32)seq_len64;
-    const u32 name_len = (u32)(sp - s - 1), desc_len = sp < e0 ? (u32)(e0 - sp - 1) : 0u;
-
-    const u32 read = ed_find(a.tab, GpBytes{t}, s + 1, (u32)(key_end - s - 1));
-    u32 type = 0, n_reg = 0, len = 0;
-    const u32 *reg = nullptr;
+    SeqVerdict v{};
+    const u32 read = ed_find(a.tab, GpBytes{a.text}, key, key_len);
     if (read != kEdNoRead) {
-        type = a.tab.type[read];
+        v.type = a.tab.type[read];
         const u64 o = a.bad_off[read];
-        n_reg = (u32)(a.bad_off[read + 1] - o);
-        reg = a.bad_reg + 2 * o;
-        len = a.lengths[read];
+        v.n_reg = (u32)(a.bad_off[read + 1] - o);
+        v.reg = a.bad_reg + 2 * o;
+        v.len = a.lengths[read];
     }
-    bool copy = false;
-    if (a.op == 1u) copy = type == 0u;
-    else if (a.op == 2u) copy = type != 0u;
-    else if (type == 2u) return 0u; // NotCovered reads are dropped
-    else copy = a.op == 0u ? n_reg == 0u : type == 0u;
-    if (a.op == 1u || a.op == 2u || copy) {
-        if (!copy) return 0u;
-        if (!EMIT) a.rec_pieces[r] = 1u, a.rec_bytes[r] = (u32)rec_len;
-        else {
-            SqPiece p{};
-            p.out = a.byte_off[r], p.rec = s, p.len = (u32)rec_len, p.flags = kSqCopy;
-            a.pieces[a.piece_off[r]] = p;
-        }
-        return 0u;
-    }
+    if (a.op == 1u) v.what = v.type == 0u ? kSeqCopy : kSeqDrop;
+    else if (a.op == 2u) v.what = v.type != 0u ? kSeqCopy : kSeqDrop;
+    else if (v.type == 2u) v.what = kSeqDrop;
+    else v.what = (a.op == 0u ? v.n_reg == 0u : v.type == 0u) ? kSeqCopy : kSeqCut;
+    return v;
+}
+
+// Record r, of seq_len bases, cut: piece(p0, p1, k, at) answers the bytes of output record k, which begins `at` bytes into
+// what the record becomes, and (EMIT) writes its descriptor.  EMIT false: the pieces and their bytes counted.
+template <bool EMIT, class P>
+__device__ __forceinline__ u32 seq_cut(const SeqArgs &a, u64 r, const SeqVerdict &v, u32 seq_len, P &&piece)
+{
     u32 status = 0, pieces = 0;
     u64 bytes = 0;
-    const u32 head = 1u + name_len + (desc_len ? 1u + desc_len : 0u) + 1u;
-    sq_cuts(a.op, reg, n_reg, len, [&](u32 p0, u32 p1) {
+    sq_cuts(a.op, v.reg, v.n_reg, v.len, [&](u32 p0, u32 p1) {
         if (p0 > seq_len || p1 > seq_len || p0 > p1) { // (the host prints the reference's [ERROR] line, or fails: its case)
             status = kSqNeedHost;
             return false;
         }
-        const u64 plen = (u64)head + 2u + sq_digits(p0) + sq_digits(p1) + 2ull * (p1 - p0) + 4u;
-        if (EMIT) {
-            SqPiece p{};
-            p.out = a.byte_off[r] + bytes, p.rec = s, p.len = (u32)plen, p.flags = 0u;
-            p.name_len = name_len, p.desc_len = desc_len;
-            p.seq_rel = (u32)(e0 + 1 - s), p.qual_rel = (u32)(e2 + 1 - s);
-            p.p0 = p0, p.p1 = p1;
-            a.pieces[a.piece_off[r] + pieces] = p;
-        }
+        const u64 plen = piece(p0, p1, pieces, bytes);
         pieces++, bytes += plen;
         return true;
     });
     if (bytes >= kSqMaxRecord) status = kSqNeedHost;
-    if (status) return status;
-    if (!EMIT) a.rec_pieces[r] = pieces, a.rec_bytes[r] = (u32)bytes;
-    return 0u;
+    if (!EMIT && !status) a.rec_pieces[r] = pieces, a.rec_bytes[r] = (u32)bytes;
+    return status;
 }
 
-// ---- plan / pieces: a thread per record ----------------------------------------------------------------------------------------------
-template <bool EMIT>
-__global__ __launch_bounds__(256) void sq_plan_kernel(SqArgs a)
+// ---- plan / pieces: a thread per record.  Format::record<EMIT>(a, r): the record's lines found, its canonical form checked,
+// its verdict, its pieces; EMIT false: the pieces and bytes counted; true: the piece descriptors written.  Returns the status bits.
+template <class Format, bool EMIT>
+__global__ __launch_bounds__(256) void seq_plan_kernel(typename Format::Args a)
 {
     const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
-    u32 status = r < a.n_rec ? sq_record<EMIT>(a, r) : 0u;
-    status = wave_or(status);
-    if (status && lane_id() == 0) atomicOr(a.ctl, (unsigned long long)status);
-}
-
-// byte k of piece p: a byte of the text (src, with `rem` bytes of the same run behind it) or a formatted one (lit, src null)
-__device__ __forceinline__ void sq_at(const SqArgs &a, const SqPiece &p, u32 k, const unsigned char *&src, u32 &rem, u32 &lit)
-{
-    const unsigned char *rec = a.text + p.rec;
-    if (p.flags & kSqCopy) {
-        src = rec + k, rem = p.len - k;
-        return;
-    }
-    src = nullptr, rem = 1, lit = '\n';
-    if (k == 0) {
-        lit = '@';
-        return;
-    }
-    k -= 1;
-    if (k < p.name_len) {
-        src = rec + 1 + k, rem = p.name_len - k;
-        return;
-    }
-    k -= p.name_len;
-    const u32 d0 = sq_digits(p.p0), d1 = sq_digits(p.p1);
-    if (k < 2u + d0 + d1) {
-        lit = k == 0 || k == d0 + 1u ? '_' : k <= d0 ? sq_digit_at(p.p0, d0, k - 1u) : sq_digit_at(p.p1, d1, k - d0 - 2u);
-        return;
-    }
-    k -= 2u + d0 + d1;
-    if (p.desc_len) {
-        if (k == 0) {
-            lit = ' ';
-            return;
-        }
-        k -= 1;
-        if (k < p.desc_len) {
-            src = rec + 1 + p.name_len + 1 + k, rem = p.desc_len - k;
-            return;
-        }
-        k -= p.desc_len;
-    }
-    if (k == 0) return; // the header's newline
-    k -= 1;
-    const u32 L = p.p1 - p.p0;
-    if (k < L) {
-        src = rec + p.seq_rel + p.p0 + k, rem = L - k;
-        return;
-    }
-    k -= L;
-    if (k < 3u) {
-        lit = k == 1u ? '+' : '\n';
-        return;
-    }
-    k -= 3u;
-    if (k < L) src = rec + p.qual_rel + p.p0 + k, rem = L - k; // (else: the record's last newline)
-}
-
-// the composed tile -> the output, 16 bytes per thread; the bytes the workgroup composed -> ctl[1], one add per workgroup
-__device__ __forceinline__ void sq_store_tile(unsigned char *out, u64 total, unsigned long long *ctl, const u32 *tile, u32 *sw, u64 tile0, u32 stored)
-{
-    __syncthreads();
-    const u64 o = tile0 + (u64)threadIdx.x * 16u;
-    if (o < total) *reinterpret_cast<uint4 *>(out + o) = *reinterpret_cast<const uint4 *>(tile + threadIdx.x * 4u);
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) stored += (u32)__shfl_xor((int)stored, d, 64);
-    if (lane_id() == 0) sw[threadIdx.x >> 6] = stored;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u32 tot = 0;
-#pragma unroll
-        for (int w = 0; w < kGpT / 64; w++) tot += sw[w];
-        atomicAdd(ctl + 1, (unsigned long long)tot);
-    }
+    seq_status(a.ctl, r < a.n_rec ? Format::template record<EMIT>(a, r) : 0u);
 }
 
 // four bytes of one run of text: the aligned words that hold them (the word behind begins inside the run when it is read)
@@ -367,18 +270,32 @@ __device__ __forceinline__ u32 sq_load4(const unsigned char *src)
     return word;
 }
 
+// the composed tile -> the output, 16 bytes per thread; the bytes the workgroup composed -> ctl[1], one add per workgroup
+__device__ __forceinline__ void sq_store_tile(unsigned char *out, u64 total, unsigned long long *ctl, const u32 *tile, u32 *sw, u64 tile0, u32 stored)
+{
+    __syncthreads();
+    const u64 o = tile0 + (u64)threadIdx.x * 16u;
+    if (o < total) *reinterpret_cast<uint4 *>(out + o) = *reinterpret_cast<const uint4 *>(tile + threadIdx.x * 4u);
+    const u32 tot = block_add<kGpT>(stored, sw);
+    if (threadIdx.x == 0) atomicAdd(ctl + 1, (unsigned long long)tot);
+}
+
 // ---- copy: a tile of the output, composed in LDS, stored 16 bytes wide -----------------------------------------------------------
 // Thread t composes words t, t + 256, t + 512 and t + 768 of the tile, so that a wavefront's loads from a run of text are
 // consecutive words; it then stores bytes [16 t, 16 t + 16).  The output buffer is padded to whole 16-byte pieces (the
-// bytes behind the total are zeros).
-__global__ __launch_bounds__(kGpT) void sq_copy_kernel(SqArgs a)
+// bytes behind the total are zeros).  Format::at(a, p, k, cursor, src, rem, lit): byte k of piece p is a byte of the text (src,
+// with `rem` bytes of the same run behind it) or a formatted one (lit, src null); a word takes the aligned path when its four
+// bytes lie in one run.  The cursor is the thread's own between calls and is reset when the piece advances.
+template <class Format>
+__global__ __launch_bounds__(kGpT) void seq_copy_kernel(typename Format::Args a)
 {
     __shared__ __attribute__((aligned(16))) u32 tile[kSqOutTile / 4];
     __shared__ u32 sw[kGpT / 64];
     const u64 tile0 = (u64)blockIdx.x * (u64)kSqOutTile;
     u32 stored = 0;
     u64 pi = 0;
-    SqPiece p{};
+    typename Format::Piece p{};
+    typename Format::Cursor cur{};
     bool have = false;
 #pragma unroll 1
     for (u32 w = 0; w < 4u; w++) {
@@ -397,10 +314,10 @@ __global__ __launch_bounds__(kGpT) void sq_copy_kernel(SqArgs a)
             const u32 nb = (u32)min((u64)4, a.total - j);
             for (u32 b = 0; b < nb;) {
                 const u64 jj = j + b;
-                while (jj >= p.out + p.len && pi + 1 < a.n_pieces) p = a.pieces[++pi]; // (jj < total: there is such a piece)
+                while (jj >= p.out + p.len && pi + 1 < a.n_pieces) p = a.pieces[++pi], cur.reset(); // (jj < total: there is such a piece)
                 const unsigned char *src;
                 u32 rem, lit;
-                sq_at(a, p, (u32)(jj - p.out), src, rem, lit);
+                Format::at(a, p, (u32)(jj - p.out), cur, src, rem, lit);
                 if (src && b == 0 && rem >= 4u) { // four bytes of one run: the aligned words that hold them
                     word = sq_load4(src);
                     b = 4, stored += 4;
@@ -414,6 +331,119 @@ __global__ __launch_bounds__(kGpT) void sq_copy_kernel(SqArgs a)
     }
     sq_store_tile(a.out, a.total, a.ctl, tile, sw, tile0, stored);
 }
+
+// ==== FASTQ: record r is lines 4r .. 4r + 3 ======================================================================================
+struct Fastq {
+    using Args = SqArgs;
+    using Piece = SqPiece;
+    struct Cursor { // (a piece's bytes are found from the piece alone)
+        __device__ __forceinline__ void reset() {}
+    };
+
+    template <bool EMIT>
+    static __device__ __forceinline__ u32 record(const SqArgs &a, u64 r)
+    {
+        const unsigned char *t = a.text;
+        const u64 s = r ? a.line_end[4 * r - 1] + 1 : 0;
+        const u64 e0 = a.line_end[4 * r], e1 = a.line_end[4 * r + 1], e2 = a.line_end[4 * r + 2], e3 = a.line_end[4 * r + 3];
+        if (!EMIT) a.rec_pieces[r] = 0u, a.rec_bytes[r] = 0u;
+        const u64 rec_len = e3 + 1 - s;
+        if (rec_len >= kSqMaxRecord) return kSqNeedHost;
+        if (t[s] != '@' || e0 == s + 1) return kSqNeedHost;
+        u64 sp = e0, key_end = e0; // the first blank; the first whitespace of any kind in front of it
+        for (u64 i = s + 1; i < e0; i++) {
+            const u32 c = t[i];
+            if (c == ' ') {
+                sp = i;
+                break;
+            }
+            if ((c == '\t' || c == '\x0c') && key_end == e0) key_end = i;
+        }
+        if (key_end > sp) key_end = sp;
+        if (sp == s + 1 || sp + 1 == e0) return kSqNeedHost; // (no name; "@name \n": the writer drops the blank)
+        if (e2 != e1 + 2 || t[e1 + 1] != '+') return kSqNeedHost;
+        const u64 seq_len64 = e1 - e0 - 1;
+        if (seq_len64 != e3 - e2 - 1) return kSqNeedHost;
+        const u32 name_len = (u32)(sp - s - 1), desc_len = sp < e0 ? (u32)(e0 - sp - 1) : 0u;
+
+        const SeqVerdict v = seq_verdict(a, s + 1, (u32)(key_end - s - 1));
+        if (v.what == kSeqDrop) return 0u;
+        if (v.what == kSeqCopy) {
+            if (!EMIT) a.rec_pieces[r] = 1u, a.rec_bytes[r] = (u32)rec_len;
+            else {
+                SqPiece p{};
+                p.out = a.byte_off[r], p.rec = s, p.len = (u32)rec_len, p.flags = kSqCopy;
+                a.pieces[a.piece_off[r]] = p;
+            }
+            return 0u;
+        }
+        const u32 head = 1u + name_len + (desc_len ? 1u + desc_len : 0u) + 1u;
+        return seq_cut<EMIT>(a, r, v, (u32)seq_len64, [&](u32 p0, u32 p1, u32 k, u64 at) {
+            const u64 plen = (u64)head + 2u + sq_digits(p0) + sq_digits(p1) + 2ull * (p1 - p0) + 4u;
+            if (EMIT) {
+                SqPiece p{};
+                p.out = a.byte_off[r] + at, p.rec = s, p.len = (u32)plen, p.flags = 0u;
+                p.name_len = name_len, p.desc_len = desc_len;
+                p.seq_rel = (u32)(e0 + 1 - s), p.qual_rel = (u32)(e2 + 1 - s);
+                p.p0 = p0, p.p1 = p1;
+                a.pieces[a.piece_off[r] + k] = p;
+            }
+            return plen;
+        });
+    }
+
+    static __device__ __forceinline__ void at(const SqArgs &a, const SqPiece &p, u32 k, Cursor &, const unsigned char *&src, u32 &rem, u32 &lit)
+    {
+        const unsigned char *rec = a.text + p.rec;
+        if (p.flags & kSqCopy) {
+            src = rec + k, rem = p.len - k;
+            return;
+        }
+        src = nullptr, rem = 1, lit = '\n';
+        if (k == 0) {
+            lit = '@';
+            return;
+        }
+        k -= 1;
+        if (k < p.name_len) {
+            src = rec + 1 + k, rem = p.name_len - k;
+            return;
+        }
+        k -= p.name_len;
+        const u32 d0 = sq_digits(p.p0), d1 = sq_digits(p.p1);
+        if (k < 2u + d0 + d1) {
+            lit = k == 0 || k == d0 + 1u ? '_' : k <= d0 ? sq_digit_at(p.p0, d0, k - 1u) : sq_digit_at(p.p1, d1, k - d0 - 2u);
+            return;
+        }
+        k -= 2u + d0 + d1;
+        if (p.desc_len) {
+            if (k == 0) {
+                lit = ' ';
+                return;
+            }
+            k -= 1;
+            if (k < p.desc_len) {
+                src = rec + 1 + p.name_len + 1 + k, rem = p.desc_len - k;
+                return;
+            }
+            k -= p.desc_len;
+        }
+        if (k == 0) return; // the header's newline
+        k -= 1;
+        const u32 L = p.p1 - p.p0;
+        if (k < L) {
+            src = rec + p.seq_rel + p.p0 + k, rem = L - k;
+            return;
+        }
+        k -= L;
+        if (k < 3u) {
+            lit = k == 1u ? '+' : '\n';
+            return;
+        }
+        k -= 3u;
+        if (k < L) src = rec + p.qual_rel + p.p0 + k, rem = L - k; // (else: the record's last newline)
+    }
+};
 
 // ==== FASTA (yacrd_engine_edit_fasta) ===========================================================================================
 // A record is a '>' line and every line up to the next one; its sequence is those lines without their newlines, and every
@@ -446,27 +476,15 @@ struct FaPiece { // one record of the output
 };
 static_assert(sizeof(FaPiece) == 72, "host code sizes the piece buffer by this");
 
-struct FaArgs {
-    const unsigned char *text;
-    EdTable tab;
-    const u32 *lengths;
-    const u64 *bad_off;
-    const u32 *bad_reg;
-    const u64 *line_end;    // [n_lines]
+struct FaArgs : SeqArgs {
     u32 *head, *bases;      // [n_lines]
     const u64 *line_rec;    // [n_lines + 1]: headers in front of line g
     const u64 *base_before; // [n_lines + 1]
     u64 *rec_line;          // [n_rec + 1]: the line of header r; n_lines closes the list
     u32 *rec_width;         // [n_rec]: the one width of the record's lines, or 0 (fa_widths_kernel)
-    u64 n_lines, n_rec;
-    u32 *rec_pieces, *rec_bytes;
-    const u64 *piece_off, *byte_off;
     FaPiece *pieces;
-    u64 n_pieces, total;
-    unsigned char *out;
-    unsigned long long *ctl;
-    u32 op;
 };
+static_assert(std::is_trivially_copyable<FaArgs>::value, "a kernel argument by value");
 
 __global__ __launch_bounds__(256) void fa_mark_kernel(FaArgs a)
 {
@@ -479,8 +497,7 @@ __global__ __launch_bounds__(256) void fa_mark_kernel(FaArgs a)
         a.head[g] = head ? 1u : 0u;
         a.bases[g] = head || status ? 0u : (u32)len;
     }
-    status = wave_or(status);
-    if (status && lane_id() == 0) atomicOr(a.ctl, (unsigned long long)status);
+    seq_status(a.ctl, status);
 }
 
 __global__ __launch_bounds__(256) void fa_heads_kernel(FaArgs a)
@@ -494,8 +511,7 @@ __global__ __launch_bounds__(256) void fa_heads_kernel(FaArgs a)
         } else if (a.bases[g] && a.line_rec[g] == 0) status = kSqNeedHost; // bases in front of the first header
         if (g == 0) a.rec_line[a.n_rec] = a.n_lines;
     }
-    status = wave_or(status);
-    if (status && lane_id() == 0) atomicOr(a.ctl, (unsigned long long)status);
+    seq_status(a.ctl, status);
 }
 
 // The one width of a record's lines, or 0: every line but the last holds as many bases as the first, the last 1 to as many,
@@ -514,85 +530,10 @@ __global__ __launch_bounds__(256) void fa_widths_kernel(FaArgs a)
 
 __device__ __forceinline__ u32 fa_rows(u32 n) { return (n + kFaWidth - 1u) / kFaWidth; }
 
-// Record r: its verdict and its pieces, as sq_record.
-template <bool EMIT>
-__device__ __forceinline__ u32 fa_record(const FaArgs &a, u64 r)
-{
-    const unsigned char *t = a.text;
-    const u64 l0 = a.rec_line[r], l1 = a.rec_line[r + 1];
-    const u64 s = l0 ? a.line_end[l0 - 1] + 1 : 0, e0 = a.line_end[l0];
-    if (!EMIT) a.rec_pieces[r] = 0u, a.rec_bytes[r] = 0u;
-    if (a.line_end[l1 - 1] + 1 - s >= kSqMaxRecord) return kSqNeedHost;
-    u64 sep = s + 1; // the name's end: the first blank, tab or form feed
-    while (sep < e0 && t[sep] != ' ' && t[sep] != '\t' && t[sep] != '\x0c') sep++;
-    if (sep == s + 1) return kSqNeedHost; // (no name: the host writes it back as it stands; the id table holds no such read)
-    const u32 name_len = (u32)(sep - s - 1), desc_len = sep < e0 ? (u32)(e0 - sep - 1) : 0u;
-    const u64 base0 = a.base_before[l0];
-    const u32 seq_len = (u32)(a.base_before[l1] - base0);
-
-    const u32 read = ed_find(a.tab, GpBytes{t}, s + 1, name_len);
-    u32 type = 0, n_reg = 0, len = 0;
-    const u32 *reg = nullptr;
-    if (read != kEdNoRead) {
-        type = a.tab.type[read];
-        const u64 o = a.bad_off[read];
-        n_reg = (u32)(a.bad_off[read + 1] - o);
-        reg = a.bad_reg + 2 * o;
-        len = a.lengths[read];
-    }
-    bool copy = false;
-    if (a.op == 1u) copy = type == 0u;
-    else if (a.op == 2u) copy = type != 0u;
-    else if (type == 2u) return 0u; // NotCovered reads are dropped
-    else copy = a.op == 0u ? n_reg == 0u : type == 0u;
-    if ((a.op == 1u || a.op == 2u) && !copy) return 0u;
-    FaPiece p{};
-    p.hdr = s, p.base0 = base0, p.line0 = l0 + 1, p.line1 = l1, p.name_len = name_len;
-    if (EMIT) p.width = a.rec_width[r];
-    if (copy) {
-        const u64 bytes = 1ull + name_len + (desc_len ? 1ull + desc_len : 0ull) + 1ull + seq_len + fa_rows(seq_len);
-        if (bytes >= kSqMaxRecord) return kSqNeedHost;
-        if (!EMIT) a.rec_pieces[r] = 1u, a.rec_bytes[r] = (u32)bytes;
-        else {
-            p.out = a.byte_off[r], p.len = (u32)bytes, p.flags = kSqCopy, p.desc_len = desc_len, p.p0 = 0u, p.p1 = seq_len;
-            a.pieces[a.piece_off[r]] = p;
-        }
-        return 0u;
-    }
-    u32 status = 0, pieces = 0;
-    u64 bytes = 0;
-    sq_cuts(a.op, reg, n_reg, len, [&](u32 p0, u32 p1) {
-        if (p0 > seq_len || p1 > seq_len || p0 > p1) { // (the host prints the reference's [ERROR] line, or fails: its case)
-            status = kSqNeedHost;
-            return false;
-        }
-        const u32 L = p1 - p0;
-        const u64 plen = 1ull + name_len + 2u + sq_digits(p0) + sq_digits(p1) + 1u + L + fa_rows(L);
-        if (EMIT) {
-            p.out = a.byte_off[r] + bytes, p.len = (u32)plen, p.flags = 0u, p.desc_len = 0u, p.p0 = p0, p.p1 = p1;
-            a.pieces[a.piece_off[r] + pieces] = p;
-        }
-        pieces++, bytes += plen;
-        return true;
-    });
-    if (bytes >= kSqMaxRecord) status = kSqNeedHost;
-    if (status) return status;
-    if (!EMIT) a.rec_pieces[r] = pieces, a.rec_bytes[r] = (u32)bytes;
-    return 0u;
-}
-
-template <bool EMIT>
-__global__ __launch_bounds__(256) void fa_plan_kernel(FaArgs a)
-{
-    const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
-    u32 status = r < a.n_rec ? fa_record<EMIT>(a, r) : 0u;
-    status = wave_or(status);
-    if (status && lane_id() == 0) atomicOr(a.ctl, (unsigned long long)status);
-}
-
 struct FaLine { // the input line a thread last took a base from: bases [b0, b1) of the text, its first byte at `start`
     u64 g, b0, b1, start;
     bool have;
+    __device__ __forceinline__ void reset() { have = false; }
 };
 
 // the line of piece p that holds base B of the text (p.base0 <= B < base_before[p.line1]): the last one whose base_before is
@@ -619,103 +560,103 @@ __device__ __forceinline__ void fa_seek(const FaArgs &a, const FaPiece &p, u64 B
     ln.g = lo, ln.b0 = a.base_before[lo], ln.b1 = a.base_before[lo + 1], ln.start = a.line_end[lo - 1] + 1, ln.have = true;
 }
 
-// byte k of piece p, as sq_at
-__device__ __forceinline__ void fa_at(const FaArgs &a, const FaPiece &p, u32 k, FaLine &ln, const unsigned char *&src, u32 &rem, u32 &lit)
-{
-    const unsigned char *rec = a.text + p.hdr;
-    src = nullptr, rem = 1, lit = '\n';
-    if (k == 0) {
-        lit = '>';
-        return;
-    }
-    k -= 1;
-    if (k < p.name_len) {
-        src = rec + 1 + k, rem = p.name_len - k;
-        return;
-    }
-    k -= p.name_len;
-    if (p.flags & kSqCopy) {
-        if (p.desc_len) { // whatever the separator was, a blank
-            if (k == 0) {
-                lit = ' ';
-                return;
+struct Fasta {
+    using Args = FaArgs;
+    using Piece = FaPiece;
+    using Cursor = FaLine;
+
+    template <bool EMIT>
+    static __device__ __forceinline__ u32 record(const FaArgs &a, u64 r)
+    {
+        const unsigned char *t = a.text;
+        const u64 l0 = a.rec_line[r], l1 = a.rec_line[r + 1];
+        const u64 s = l0 ? a.line_end[l0 - 1] + 1 : 0, e0 = a.line_end[l0];
+        if (!EMIT) a.rec_pieces[r] = 0u, a.rec_bytes[r] = 0u;
+        if (a.line_end[l1 - 1] + 1 - s >= kSqMaxRecord) return kSqNeedHost;
+        u64 sep = s + 1; // the name's end: the first blank, tab or form feed
+        while (sep < e0 && t[sep] != ' ' && t[sep] != '\t' && t[sep] != '\x0c') sep++;
+        if (sep == s + 1) return kSqNeedHost; // (no name: the host writes it back as it stands; the id table holds no such read)
+        const u32 name_len = (u32)(sep - s - 1), desc_len = sep < e0 ? (u32)(e0 - sep - 1) : 0u;
+        const u64 base0 = a.base_before[l0];
+        const u32 seq_len = (u32)(a.base_before[l1] - base0);
+
+        const SeqVerdict v = seq_verdict(a, s + 1, name_len);
+        if (v.what == kSeqDrop) return 0u;
+        FaPiece p{};
+        p.hdr = s, p.base0 = base0, p.line0 = l0 + 1, p.line1 = l1, p.name_len = name_len;
+        if (EMIT) p.width = a.rec_width[r];
+        if (v.what == kSeqCopy) {
+            const u64 bytes = 1ull + name_len + (desc_len ? 1ull + desc_len : 0ull) + 1ull + seq_len + fa_rows(seq_len);
+            if (bytes >= kSqMaxRecord) return kSqNeedHost;
+            if (!EMIT) a.rec_pieces[r] = 1u, a.rec_bytes[r] = (u32)bytes;
+            else {
+                p.out = a.byte_off[r], p.len = (u32)bytes, p.flags = kSqCopy, p.desc_len = desc_len, p.p0 = 0u, p.p1 = seq_len;
+                a.pieces[a.piece_off[r]] = p;
             }
-            k -= 1;
-            if (k < p.desc_len) {
-                src = rec + 1 + p.name_len + 1 + k, rem = p.desc_len - k;
-                return;
-            }
-            k -= p.desc_len;
+            return 0u;
         }
-    } else {
-        const u32 d0 = sq_digits(p.p0), d1 = sq_digits(p.p1);
-        if (k < 2u + d0 + d1) {
-            lit = k == 0 || k == d0 + 1u ? '_' : k <= d0 ? sq_digit_at(p.p0, d0, k - 1u) : sq_digit_at(p.p1, d1, k - d0 - 2u);
+        return seq_cut<EMIT>(a, r, v, seq_len, [&](u32 p0, u32 p1, u32 k, u64 at) {
+            const u32 L = p1 - p0;
+            const u64 plen = 1ull + name_len + 2u + sq_digits(p0) + sq_digits(p1) + 1u + L + fa_rows(L);
+            if (EMIT) {
+                p.out = a.byte_off[r] + at, p.len = (u32)plen, p.flags = 0u, p.desc_len = 0u, p.p0 = p0, p.p1 = p1;
+                a.pieces[a.piece_off[r] + k] = p;
+            }
+            return plen;
+        });
+    }
+
+    static __device__ __forceinline__ void at(const FaArgs &a, const FaPiece &p, u32 k, FaLine &ln, const unsigned char *&src, u32 &rem, u32 &lit)
+    {
+        const unsigned char *rec = a.text + p.hdr;
+        src = nullptr, rem = 1, lit = '\n';
+        if (k == 0) {
+            lit = '>';
             return;
         }
-        k -= 2u + d0 + d1;
-    }
-    if (k == 0) return; // the header's newline
-    k -= 1;
-    const u32 L = p.p1 - p.p0, row = k / (kFaWidth + 1u), col = k % (kFaWidth + 1u), at = row * kFaWidth + col;
-    if (col == kFaWidth || at >= L) return; // a row's newline; the last row's
-    if (p.width) { // (a.line_end[p.line0 - 1]: the header's newline)
-        const u32 b = p.p0 + at, q = b / p.width, r = b - q * p.width;
-        src = a.text + a.line_end[p.line0 - 1] + 1 + (u64)q * ((u64)p.width + 1u) + r;
-        rem = min(min(p.width - r, kFaWidth - col), L - at);
-        return;
-    }
-    const u64 B = p.base0 + p.p0 + at;
-    fa_seek(a, p, B, ln);
-    src = a.text + ln.start + (B - ln.b0);
-    rem = (u32)min(min(ln.b1 - B, (u64)(kFaWidth - col)), (u64)(L - at));
-}
-
-// ---- copy: as sq_copy_kernel; a word takes the aligned path when its four bytes lie in one input line and one output row --------
-__global__ __launch_bounds__(kGpT) void fa_copy_kernel(FaArgs a)
-{
-    __shared__ __attribute__((aligned(16))) u32 tile[kSqOutTile / 4];
-    __shared__ u32 sw[kGpT / 64];
-    const u64 tile0 = (u64)blockIdx.x * (u64)kSqOutTile;
-    u32 stored = 0;
-    u64 pi = 0;
-    FaPiece p{};
-    FaLine ln{};
-    bool have = false;
-#pragma unroll 1
-    for (u32 w = 0; w < 4u; w++) {
-        const u64 j = tile0 + ((u64)w * (u32)kGpT + threadIdx.x) * 4u;
-        u32 word = 0;
-        if (j < a.total) {
-            if (!have) { // the last piece that begins at or in front of j (piece 0 begins at 0)
-                u64 lo = 0, hi = a.n_pieces;
-                while (hi - lo > 1) {
-                    const u64 mid = lo + (hi - lo) / 2;
-                    if (a.pieces[mid].out <= j) lo = mid;
-                    else hi = mid;
-                }
-                pi = lo, p = a.pieces[lo], have = true;
-            }
-            const u32 nb = (u32)min((u64)4, a.total - j);
-            for (u32 b = 0; b < nb;) {
-                const u64 jj = j + b;
-                while (jj >= p.out + p.len && pi + 1 < a.n_pieces) p = a.pieces[++pi], ln.have = false; // (jj < total: there is such a piece)
-                const unsigned char *src;
-                u32 rem, lit;
-                fa_at(a, p, (u32)(jj - p.out), ln, src, rem, lit);
-                if (src && b == 0 && rem >= 4u) {
-                    word = sq_load4(src);
-                    b = 4, stored += 4;
-                } else {
-                    word |= (src ? (u32)*src : lit) << (8u * b);
-                    b++, stored++;
-                }
-            }
+        k -= 1;
+        if (k < p.name_len) {
+            src = rec + 1 + k, rem = p.name_len - k;
+            return;
         }
-        tile[w * (u32)kGpT + threadIdx.x] = word;
+        k -= p.name_len;
+        if (p.flags & kSqCopy) {
+            if (p.desc_len) { // whatever the separator was, a blank
+                if (k == 0) {
+                    lit = ' ';
+                    return;
+                }
+                k -= 1;
+                if (k < p.desc_len) {
+                    src = rec + 1 + p.name_len + 1 + k, rem = p.desc_len - k;
+                    return;
+                }
+                k -= p.desc_len;
+            }
+        } else {
+            const u32 d0 = sq_digits(p.p0), d1 = sq_digits(p.p1);
+            if (k < 2u + d0 + d1) {
+                lit = k == 0 || k == d0 + 1u ? '_' : k <= d0 ? sq_digit_at(p.p0, d0, k - 1u) : sq_digit_at(p.p1, d1, k - d0 - 2u);
+                return;
+            }
+            k -= 2u + d0 + d1;
+        }
+        if (k == 0) return; // the header's newline
+        k -= 1;
+        const u32 L = p.p1 - p.p0, row = k / (kFaWidth + 1u), col = k % (kFaWidth + 1u), at = row * kFaWidth + col;
+        if (col == kFaWidth || at >= L) return; // a row's newline; the last row's
+        if (p.width) { // (a.line_end[p.line0 - 1]: the header's newline)
+            const u32 b = p.p0 + at, q = b / p.width, r = b - q * p.width;
+            src = a.text + a.line_end[p.line0 - 1] + 1 + (u64)q * ((u64)p.width + 1u) + r;
+            rem = min(min(p.width - r, kFaWidth - col), L - at);
+            return;
+        }
+        const u64 B = p.base0 + p.p0 + at;
+        fa_seek(a, p, B, ln);
+        src = a.text + ln.start + (B - ln.b0);
+        rem = (u32)min(min(ln.b1 - B, (u64)(kFaWidth - col)), (u64)(L - at));
     }
-    sq_store_tile(a.out, a.total, a.ctl, tile, sw, tile0, stored);
-}
+};
 
 } // namespace yk
 
@@ -726,8 +667,8 @@ constexpr u64 kGzBatchBlocks = 2048;          // blocks of 65 280 bytes per batc
 
 struct SeqEditScratch { // the editor's buffers; they stay with the engine (grow-only), go with yacrd_engine_trim / destroy
     static constexpr yacrd_engine::Slot kScratchSlot = yacrd_engine::kSeqEdit;
-    DevBuf text, out, names, name_off, types, lengths, bad_off, bad_reg, slots, tile_nl, tile_l0, line_end, rec_pieces, rec_bytes, piece_off,
-        byte_off, pieces, ctl, part;
+    DevBuf text, out, lengths, bad_off, bad_reg, tile_nl, tile_l0, line_end, rec_pieces, rec_bytes, piece_off, byte_off, pieces, ctl, part;
+    EdTableOwner table; // the reads' names and types, the id table over them
     DevBuf ln_head, ln_bases, ln_rec, base_before, rec_line, rec_width; // FASTA: per line, per record
     PinBuf pin; // two output pieces + the control words
 };
@@ -746,14 +687,6 @@ struct SeqJob {
     u64 bgzf_bytes = 0;
     const std::vector<yif::InfMember> *members = nullptr;
     yacrd_gunzip_stats *gunzip_stats = nullptr;
-};
-
-struct SeqGzHold { // the engine's encoder buffers are this edit's until it ends
-    yacrd_engine *e = nullptr;
-    ~SeqGzHold()
-    {
-        if (e) gzip_device_close(e);
-    }
 };
 
 // One edit on its way through the device: built once per call (run_seq_edit), its phases in the order they run.
@@ -778,7 +711,7 @@ struct SeqRun {
     Streams side;                  // [0] the way home; [1] the encoder
     size_t n_ev = 0;
     GzDevice gz;
-    SeqGzHold gz_hold;
+    GzHold gz_hold;
     double t_start = 0, t_table = 0, t_text = 0, out_busy_ms = 0, put_ms = 0;
     u64 gz_members = 0, gz_stored = 0;
     float gz_kernel_ms = 0;
@@ -802,6 +735,29 @@ struct SeqRun {
     {
         n_ev += 2;
         return hipEventRecord(ev[n_ev - 1], e->stream) == hipSuccess;
+    }
+    // the end of a phase: these device words -> h_ctl[0 .. k), the stream waited for; `ok`: what its event pair said
+    int bring_words(bool ok, std::initializer_list<const void *> words)
+    {
+        size_t k = 0;
+        for (const void *w : words) HIP_TRY(hipMemcpyAsync((void *)(h_ctl + k++), w, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipGetLastError());
+        if (!ok) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
+        return YACRD_OK;
+    }
+
+    // a format's kernel arguments: the common part is filled once, in `ga`
+    yk::SqArgs &args(yk::Fastq) { return ga; }
+    yk::FaArgs &args(yk::Fasta)
+    {
+        static_cast<yk::SeqArgs &>(fa) = ga;
+        return fa;
+    }
+    template <class Format, bool EMIT>
+    void launch_plan()
+    {
+        if (n_rec) hipLaunchKernelGGL((yk::seq_plan_kernel<Format, EMIT>), dim3((u32)((n_rec + 255) / 256)), dim3(256), 0, e->stream, args(Format{}));
     }
 
     // the table's shape, the text's last byte, the sizes that follow from n
@@ -830,7 +786,7 @@ struct SeqRun {
         n_segs = (size_t)((n + kTextChunk * kTextSeg - 1) / (kTextChunk * kTextSeg));
         while (cap < 2 * R) cap <<= 1;
         t_start = now_ms();
-        const double held = (double)S.text.cap + (double)S.names.cap + (double)S.slots.cap + (double)S.bad_reg.cap + (double)S.tile_l0.cap;
+        const double held = (double)S.text.cap + (double)S.table.names.cap + (double)S.table.slots.cap + (double)S.bad_reg.cap + (double)S.tile_l0.cap;
         // (the output is at least... unknown yet: asked for again when it is; here the text, the table and the tiles' words)
         const double comp = job.bgzf ? (double)job.bgzf_bytes + (double)job.members->size() * (double)sizeof(yif::InfMember) : 0.0; // (the inflate scratch's)
         if (!fits((double)n + comp + (double)name_bytes + (double)cap * 4.0 + (double)R * 21.0 + (double)G * 8.0 + (double)n_tiles * 12.0, held)) return no_room();
@@ -852,32 +808,19 @@ struct SeqRun {
         h_ctl = reinterpret_cast<volatile u64 *>(S.pin.as<char>() + 2 * kOutPiece);
         for (int i = 0; i < 8; i++) h_ctl[i] = 0;
         if (!side.add(job.gzip ? 2 : 1) || !wev.add(2, hipEventDisableTiming) || !ev.add(2 * n_segs + 10)) HIP_TRY(why_not_added());
-        HIP_TRY(S.names.reserve((size_t)name_bytes + 64));
-        HIP_TRY(S.name_off.reserve((size_t)(R + 1) * sizeof(u64)));
-        HIP_TRY(S.types.reserve((size_t)R + 64));
         HIP_TRY(S.lengths.reserve((size_t)(R + 1) * sizeof(u32)));
         HIP_TRY(S.bad_off.reserve((size_t)(R + 1) * sizeof(u64)));
         HIP_TRY(S.bad_reg.reserve((size_t)(2 * G + 2) * sizeof(u32)));
-        HIP_TRY(S.slots.reserve((size_t)cap * sizeof(u32)));
-        HIP_TRY(hipMemsetAsync(S.slots.p, 0, (size_t)cap * sizeof(u32), e->stream));
-        yk::EdTable tab{};
-        tab.names = S.names.as<unsigned char>(), tab.name_off = S.name_off.as<u64>(), tab.type = S.types.as<unsigned char>();
-        tab.slots = S.slots.as<u32>(), tab.mask = (u32)(cap - 1), tab.n_reads = (u32)R;
+        if (const int rc = S.table.upload(e, t.names, t.name_off, t.read_type, R, name_bytes, cap, &ga.tab)) return rc;
         if (R) {
-            if (name_bytes)
-                if (const int rch = h2d(e, S.names.p, t.names, (size_t)name_bytes)) return rch;
-            if (const int rch = h2d(e, S.name_off.p, t.name_off, (size_t)(R + 1) * sizeof(u64))) return rch;
-            if (const int rch = h2d(e, S.types.p, t.read_type, (size_t)R)) return rch;
             if (const int rch = h2d(e, S.lengths.p, t.lengths, (size_t)R * sizeof(u32))) return rch;
             if (const int rch = h2d(e, S.bad_off.p, t.bad_offsets, (size_t)(R + 1) * sizeof(u64))) return rch;
             if (G)
                 if (const int rch = h2d(e, S.bad_reg.p, t.bad_regions, (size_t)(2 * G) * sizeof(u32))) return rch;
-            hipLaunchKernelGGL(yk::ed_table_kernel, dim3((u32)((R + 255) / 256)), dim3(256), 0, e->stream, tab);
         }
         HIP_TRY(hipStreamSynchronize(e->stream));
         t_table = now_ms();
         ga.text = S.text.as<unsigned char>(), ga.n = n, ga.avail = n;
-        ga.tab = tab;
         ga.lengths = S.lengths.as<u32>(), ga.bad_off = S.bad_off.as<u64>(), ga.bad_reg = S.bad_reg.as<u32>();
         ga.tile_nl = S.tile_nl.as<u32>(), ga.tile_l0 = S.tile_l0.as<u64>();
         ga.ctl = S.ctl.as<unsigned long long>();
@@ -947,13 +890,10 @@ struct SeqRun {
         bool ok = ev_open();
         if (const int rc = scan_u32_to_u64(e, S.tile_nl.as<u32>(), n_tiles, S.tile_l0.as<u64>(), S.part)) return rc;
         ok = ok && ev_close();
-        HIP_TRY(hipMemcpyAsync((void *)h_ctl, S.tile_l0.as<u64>() + n_tiles, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipMemcpyAsync((void *)(h_ctl + 1), S.ctl.p, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        HIP_TRY(hipGetLastError());
-        if (!ok) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
+        if (const int rc = bring_words(ok, {S.tile_l0.as<u64>() + n_tiles, S.ctl.p})) return rc;
         n_lines = h_ctl[0];
         if (h_ctl[1] & yk::kSqNeedHost) return fail(YACRD_EFALLBACK, "the text holds a CR: the host loop decides");
+        ga.n_lines = n_lines;
         if (job.fasta) return YACRD_OK; // (its records are counted on the device: size_fasta)
         if (n_lines % 4) return fail(YACRD_EFALLBACK, "the line count is no multiple of four: the host loop decides");
         n_rec = n_lines / 4;
@@ -961,7 +901,23 @@ struct SeqRun {
         return YACRD_OK;
     }
 
-    // FASTA: index, mark and the two scans over the lines — how many records —, then heads, widths, plan and the scans over the records
+    void launch_index()
+    {
+        if (n_tiles) hipLaunchKernelGGL(yk::sq_index_kernel, dim3((u32)n_tiles), dim3(yk::kGpT), 0, e->stream, ga);
+    }
+
+    // FASTQ's front: the line index, in the bracket of the plan
+    int size_fastq()
+    {
+        if (!fits((double)n_lines * 8.0 + (double)n_rec * 24.0, (double)S.line_end.cap + (double)S.piece_off.cap + (double)S.byte_off.cap)) return no_room();
+        HIP_TRY(S.line_end.reserve((size_t)(n_lines + 1) * sizeof(u64)));
+        ga.line_end = S.line_end.as<u64>();
+        return size_records<yk::Fastq>([&] { launch_index(); },
+                                       "a record that is not \"@name[ desc]\\nseq\\n+\\nqual\\n\", a cut position beyond its read or a region with "
+                                       "begin > end: the host loop decides");
+    }
+
+    // FASTA's front: index, mark and the two scans over the lines — how many records —, then heads and widths in the bracket of the plan
     int size_fasta()
     {
         const double line_tables = (double)n_lines * 32.0;
@@ -972,23 +928,17 @@ struct SeqRun {
         HIP_TRY(S.ln_bases.reserve((size_t)(n_lines + 1) * sizeof(u32)));
         HIP_TRY(S.ln_rec.reserve((size_t)(n_lines + 2) * sizeof(u64)));
         HIP_TRY(S.base_before.reserve((size_t)(n_lines + 2) * sizeof(u64)));
-        ga.line_end = S.line_end.as<u64>(), ga.n_lines = n_lines;
-        fa.text = ga.text, fa.tab = ga.tab, fa.lengths = ga.lengths, fa.bad_off = ga.bad_off, fa.bad_reg = ga.bad_reg;
-        fa.line_end = S.line_end.as<u64>(), fa.head = S.ln_head.as<u32>(), fa.bases = S.ln_bases.as<u32>();
+        ga.line_end = S.line_end.as<u64>();
+        fa.head = S.ln_head.as<u32>(), fa.bases = S.ln_bases.as<u32>();
         fa.line_rec = S.ln_rec.as<u64>(), fa.base_before = S.base_before.as<u64>();
-        fa.n_lines = n_lines, fa.ctl = ga.ctl, fa.op = ga.op;
         const dim3 line_grid((u32)((n_lines + 255) / 256));
         bool ok = ev_open();
-        if (n_tiles) hipLaunchKernelGGL(yk::sq_index_kernel, dim3((u32)n_tiles), dim3(yk::kGpT), 0, e->stream, ga);
-        if (n_lines) hipLaunchKernelGGL(yk::fa_mark_kernel, line_grid, dim3(256), 0, e->stream, fa);
+        launch_index();
+        if (n_lines) hipLaunchKernelGGL(yk::fa_mark_kernel, line_grid, dim3(256), 0, e->stream, args(yk::Fasta{}));
         if (const int rc = scan_u32_to_u64(e, fa.head, n_lines, S.ln_rec.as<u64>(), S.part)) return rc;
         if (const int rc = scan_u32_to_u64(e, fa.bases, n_lines, S.base_before.as<u64>(), S.part)) return rc;
         ok = ok && ev_close();
-        HIP_TRY(hipMemcpyAsync((void *)h_ctl, S.ln_rec.as<u64>() + n_lines, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipMemcpyAsync((void *)(h_ctl + 1), S.ctl.p, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        HIP_TRY(hipGetLastError());
-        if (!ok) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
+        if (const int rc = bring_words(ok, {S.ln_rec.as<u64>() + n_lines, S.ctl.p})) return rc;
         n_rec = h_ctl[0];
         if (h_ctl[1] & yk::kSqNeedHost) return fail(YACRD_EFALLBACK, "a line longer than the device editor's offsets: the host loop decides");
         if (n_rec >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "more records than the device editor numbers");
@@ -996,114 +946,76 @@ struct SeqRun {
         if (!fits((double)n_rec * 36.0, (double)S.rec_line.cap + (double)S.piece_off.cap + (double)S.byte_off.cap)) return no_room();
         HIP_TRY(S.rec_line.reserve((size_t)(n_rec + 1) * sizeof(u64)));
         HIP_TRY(S.rec_width.reserve((size_t)(n_rec + 1) * sizeof(u32)));
-        HIP_TRY(S.rec_pieces.reserve((size_t)(n_rec + 1) * sizeof(u32)));
-        HIP_TRY(S.rec_bytes.reserve((size_t)(n_rec + 1) * sizeof(u32)));
-        HIP_TRY(S.piece_off.reserve((size_t)(n_rec + 2) * sizeof(u64)));
-        HIP_TRY(S.byte_off.reserve((size_t)(n_rec + 2) * sizeof(u64)));
-        fa.rec_line = S.rec_line.as<u64>(), fa.rec_width = S.rec_width.as<u32>(), fa.n_rec = n_rec;
-        fa.rec_pieces = S.rec_pieces.as<u32>(), fa.rec_bytes = S.rec_bytes.as<u32>();
-        fa.piece_off = S.piece_off.as<u64>(), fa.byte_off = S.byte_off.as<u64>();
-        ok = ev_open();
-        if (n_lines) hipLaunchKernelGGL(yk::fa_heads_kernel, line_grid, dim3(256), 0, e->stream, fa);
-        if (n_rec) hipLaunchKernelGGL(yk::fa_widths_kernel, line_grid, dim3(256), 0, e->stream, fa);
-        if (n_rec) hipLaunchKernelGGL(yk::fa_plan_kernel<false>, dim3((u32)((n_rec + 255) / 256)), dim3(256), 0, e->stream, fa);
-        if (const int rc = scan_u32_to_u64(e, fa.rec_pieces, n_rec, S.piece_off.as<u64>(), S.part)) return rc;
-        if (const int rc = scan_u32_to_u64(e, fa.rec_bytes, n_rec, S.byte_off.as<u64>(), S.part)) return rc;
-        ok = ok && ev_close();
-        HIP_TRY(hipMemcpyAsync((void *)h_ctl, S.piece_off.as<u64>() + n_rec, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipMemcpyAsync((void *)(h_ctl + 1), S.byte_off.as<u64>() + n_rec, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipMemcpyAsync((void *)(h_ctl + 2), S.ctl.p, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        HIP_TRY(hipGetLastError());
-        if (!ok) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
-        n_pieces = h_ctl[0], total = h_ctl[1];
-        if (h_ctl[2] & yk::kSqNeedHost)
-            return fail(YACRD_EFALLBACK, "bases in front of the first header, a header without a name, a cut position beyond its read or a region with "
-                                         "begin > end: the host loop decides");
-        if (n_pieces >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "more output records than the device editor numbers");
-        return YACRD_OK;
+        fa.rec_line = S.rec_line.as<u64>(), fa.rec_width = S.rec_width.as<u32>();
+        return size_records<yk::Fasta>(
+            [&] {
+                if (n_lines) hipLaunchKernelGGL(yk::fa_heads_kernel, line_grid, dim3(256), 0, e->stream, args(yk::Fasta{}));
+                if (n_rec) hipLaunchKernelGGL(yk::fa_widths_kernel, line_grid, dim3(256), 0, e->stream, args(yk::Fasta{}));
+            },
+            "bases in front of the first header, a header without a name, a cut position beyond its read or a region with "
+            "begin > end: the host loop decides");
     }
 
-    // index, plan and the two scans: how many output records, how many bytes
-    int size_output()
+    // what both formats do once the records are numbered: in one bracket the format's own kernels (`front`), the plan and the
+    // two scans; how many output records, how many bytes.  `not_taken`: what the plan's status bit says in this format
+    template <class Format, class Front>
+    int size_records(Front &&front, const char *not_taken)
     {
-        if (job.fasta) return size_fasta();
-        if (!fits((double)n_lines * 8.0 + (double)n_rec * 24.0, (double)S.line_end.cap + (double)S.piece_off.cap + (double)S.byte_off.cap)) return no_room();
-        HIP_TRY(S.line_end.reserve((size_t)(n_lines + 1) * sizeof(u64)));
         HIP_TRY(S.rec_pieces.reserve((size_t)(n_rec + 1) * sizeof(u32)));
         HIP_TRY(S.rec_bytes.reserve((size_t)(n_rec + 1) * sizeof(u32)));
         HIP_TRY(S.piece_off.reserve((size_t)(n_rec + 2) * sizeof(u64)));
         HIP_TRY(S.byte_off.reserve((size_t)(n_rec + 2) * sizeof(u64)));
-        ga.line_end = S.line_end.as<u64>(), ga.n_lines = n_lines, ga.n_rec = n_rec;
+        ga.n_rec = n_rec;
         ga.rec_pieces = S.rec_pieces.as<u32>(), ga.rec_bytes = S.rec_bytes.as<u32>();
         ga.piece_off = S.piece_off.as<u64>(), ga.byte_off = S.byte_off.as<u64>();
         bool ok = ev_open();
-        if (n_tiles) hipLaunchKernelGGL(yk::sq_index_kernel, dim3((u32)n_tiles), dim3(yk::kGpT), 0, e->stream, ga);
-        if (n_rec) hipLaunchKernelGGL(yk::sq_plan_kernel<false>, dim3((u32)((n_rec + 255) / 256)), dim3(256), 0, e->stream, ga);
+        front();
+        launch_plan<Format, false>();
         if (const int rc = scan_u32_to_u64(e, ga.rec_pieces, n_rec, S.piece_off.as<u64>(), S.part)) return rc;
         if (const int rc = scan_u32_to_u64(e, ga.rec_bytes, n_rec, S.byte_off.as<u64>(), S.part)) return rc;
         ok = ok && ev_close();
-        HIP_TRY(hipMemcpyAsync((void *)h_ctl, S.piece_off.as<u64>() + n_rec, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipMemcpyAsync((void *)(h_ctl + 1), S.byte_off.as<u64>() + n_rec, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipMemcpyAsync((void *)(h_ctl + 2), S.ctl.p, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        HIP_TRY(hipGetLastError());
-        if (!ok) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
+        if (const int rc = bring_words(ok, {S.piece_off.as<u64>() + n_rec, S.byte_off.as<u64>() + n_rec, S.ctl.p})) return rc;
         n_pieces = h_ctl[0], total = h_ctl[1];
-        if (h_ctl[2] & yk::kSqNeedHost)
-            return fail(YACRD_EFALLBACK, "a record that is not \"@name[ desc]\\nseq\\n+\\nqual\\n\", a cut position beyond its read or a region with "
-                                         "begin > end: the host loop decides");
+        if (h_ctl[2] & yk::kSqNeedHost) return fail(YACRD_EFALLBACK, not_taken);
         if (n_pieces >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "more output records than the device editor numbers");
         return YACRD_OK;
     }
 
+    // the line index and what is the format's own in front of the plan, then the plan and the two scans
+    int size_output() { return job.fasta ? size_fasta() : size_fastq(); }
+
     // the output's buffers (the encoder's too), the piece descriptors, the copy pass
+    template <class Format>
     int gather()
     {
         const u64 gz_blocks = job.gzip ? std::min<u64>(kGzBatchBlocks, (total + ydf::kBlock - 1) / ydf::kBlock + 1) : 0;
-        const size_t piece_size = job.fasta ? sizeof(yk::FaPiece) : sizeof(yk::SqPiece);
-        if (!fits((double)total + (double)n_pieces * (double)piece_size + (double)gz_blocks * (double)ydf::kSlot * 3.0, (double)S.out.cap + (double)S.pieces.cap)) return no_room();
+        using Piece = typename Format::Piece;
+        if (!fits((double)total + (double)n_pieces * (double)sizeof(Piece) + (double)gz_blocks * (double)ydf::kSlot * 3.0, (double)S.out.cap + (double)S.pieces.cap)) return no_room();
         const u64 padded = (total + 15) & ~(u64)15;
         HIP_TRY(S.out.reserve((size_t)padded + 64));
-        HIP_TRY(S.pieces.reserve((size_t)(n_pieces + 1) * piece_size));
+        HIP_TRY(S.pieces.reserve((size_t)(n_pieces + 1) * sizeof(Piece)));
         if (job.gzip) {
             if (const int rcg = gzip_device_open(e, gz_blocks, &gz)) return rcg;
             gz_hold.e = e;
         }
-        ga.pieces = S.pieces.as<yk::SqPiece>(), ga.n_pieces = n_pieces, ga.total = total, ga.out = S.out.as<unsigned char>();
-        fa.pieces = S.pieces.as<yk::FaPiece>(), fa.n_pieces = n_pieces, fa.total = total, fa.out = ga.out;
-        const dim3 out_grid((u32)((total + yk::kSqOutTile - 1) / yk::kSqOutTile));
+        ga.n_pieces = n_pieces, ga.total = total, ga.out = S.out.as<unsigned char>();
+        args(Format{}).pieces = S.pieces.as<Piece>();
         bool ok = ev_open();
-        if (total && job.fasta) {
-            hipLaunchKernelGGL(yk::fa_plan_kernel<true>, dim3((u32)((n_rec + 255) / 256)), dim3(256), 0, e->stream, fa);
-            hipLaunchKernelGGL(yk::fa_copy_kernel, out_grid, dim3(yk::kGpT), 0, e->stream, fa);
-        } else if (total) {
-            hipLaunchKernelGGL(yk::sq_plan_kernel<true>, dim3((u32)((n_rec + 255) / 256)), dim3(256), 0, e->stream, ga);
-            hipLaunchKernelGGL(yk::sq_copy_kernel, out_grid, dim3(yk::kGpT), 0, e->stream, ga);
+        if (total) {
+            launch_plan<Format, true>();
+            hipLaunchKernelGGL(yk::seq_copy_kernel<Format>, dim3((u32)((total + yk::kSqOutTile - 1) / yk::kSqOutTile)), dim3(yk::kGpT), 0, e->stream, args(Format{}));
         }
         ok = ok && ev_close();
-        HIP_TRY(hipMemcpyAsync((void *)h_ctl, S.ctl.p, 2 * sizeof(u64), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        HIP_TRY(hipGetLastError());
-        if (!ok) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
+        if (const int rc = bring_words(ok, {S.ctl.p, S.ctl.as<u64>() + 1})) return rc;
         if (h_ctl[0] || h_ctl[1] != total) return fail(YACRD_EINTERNAL, "sequence editor: the copy pass stored other bytes than the plan counted");
         return YACRD_OK;
     }
+    int gather() { return job.fasta ? gather<yk::Fasta>() : gather<yk::Fastq>(); }
 
     // base[0, len) in HBM -> the sink through the two pinned pieces: one flies while the other is written (host/segment_pump.h)
     int bring_home(const char *base, u64 len)
     {
-        struct Dma {
-            SeqRun &r;
-            const char *text;
-            bool start(u64 i, char *dst, u64 at, size_t k)
-            {
-                return hipMemcpyAsync(dst, text + at, k, hipMemcpyDeviceToHost, r.side[0]) == hipSuccess &&
-                       hipEventRecord(r.wev[i & 1], r.side[0]) == hipSuccess;
-            }
-            bool wait(u64 i) { return hipEventSynchronize(r.wev[i & 1]) == hipSuccess; }
-            void drain() { (void)hipStreamSynchronize(r.side[0]); }
-        } dma{*this, base};
+        HomeLink dma{base, side[0], {wev[0], wev[1]}};
         const int rc = yseg::pump(len, kOutPiece, S.pin.as<char>(), dma, sink, [&](auto put) {
             const double tp = now_ms();
             put();
@@ -1167,12 +1079,7 @@ struct SeqRun {
         }
         out_busy_ms = now_ms() - t0;
         if (rc) return rc;
-        if (job.gzip_stats) {
-            yacrd_gzip_stats &g = *job.gzip_stats;
-            g.in_bytes = total, g.out_bytes = sink.at, g.n_members = gz_members, g.n_stored = gz_stored;
-            g.h2d_ms = 0.f, g.kernel_ms = gz_kernel_ms;
-            g.d2h_ms = (float)std::max(0.0, out_busy_ms - put_ms), g.write_ms = (float)put_ms;
-        }
+        fill_gzip_stats(job.gzip_stats, total, sink.at, gz_members, gz_stored, gz_kernel_ms, out_busy_ms, put_ms);
         if (job.gunzip_stats) {
             yacrd_gunzip_stats &u = *job.gunzip_stats; // (walk_ms: the caller's)
             u.in_bytes = job.bgzf_bytes, u.out_bytes = n, u.n_members = job.members->size();
@@ -1218,31 +1125,83 @@ int seq_edit_args(bool fasta, yacrd_engine *e, int op, const yacrd_report_table 
     return YACRD_OK;
 }
 
-// util::get_file_type by name (src/util.rs:39-55), as far as it says FASTQ
-bool named_fastq(const char *path)
+// util::get_file_type by name (src/util.rs:39-55), as far as it says FASTQ or FASTA: every other type's mark wins over ".fa"
+bool named_as(bool fasta, const char *path)
 {
     const std::string name(path);
     auto has = [&](const char *x) { return name.find(x) != std::string::npos; };
     if (has(".m4") || has(".mhap") || has(".paf") || has(".yacrd")) return false;
-    return has(".fastq") || has(".fq");
-}
-// ... and as far as it says FASTA: every other type's mark wins over ".fa"
-bool named_fasta(const char *path)
-{
-    const std::string name(path);
-    auto has = [&](const char *x) { return name.find(x) != std::string::npos; };
-    if (has(".m4") || has(".mhap") || has(".paf") || has(".yacrd") || has(".fastq") || has(".fq")) return false;
-    return has(".fasta") || has(".fa");
+    const bool fastq = has(".fastq") || has(".fq");
+    return fasta ? !fastq && (has(".fasta") || has(".fa")) : fastq;
 }
 
-// the four forms, for FASTQ and for FASTA
+// One call of a form: its job, where the text comes from and where the bytes go.  The forms share their front (enter, text_in)
+// and their way out (leave).
+struct SeqCall {
+    yacrd_seq_edit_stats *st;
+    yacrd_gzip_stats *gs;
+    yacrd_gunzip_stats *us;
+    SeqJob job;
+    std::vector<yif::InfMember> members;
+    TextSource src;
+    Sink sink;
+
+    // the stats zeroed, the arguments checked, the job named
+    int enter(bool fasta, yacrd_engine *e, int op, const yacrd_report_table *t, bool gzip)
+    {
+        if (gs) std::memset(gs, 0, sizeof(*gs));
+        if (us) std::memset(us, 0, sizeof(*us));
+        if (const int rc = seq_edit_args(fasta, e, op, t, st)) return rc;
+        job.op = op, job.table = t, job.fasta = fasta, job.gzip = gzip, job.gzip_stats = gs;
+        return YACRD_OK;
+    }
+    // the text in memory.  BGZF in: `text`, `n` are the compressed file; the walk — before a file is made beside an out_path:
+    // what is not BGZF leaves nothing — fills `members` and the job's BGZF fields, and `n` becomes the text's bytes
+    int text_in(const char *text, uint64_t &n, bool bgzf)
+    {
+        if (bgzf) {
+            const double t0 = now_ms();
+            u64 total = 0;
+            if (!ybw::walk(reinterpret_cast<const unsigned char *>(text), n, members, &total)) return fail(YACRD_EFALLBACK, "not BGZF: the host reader's");
+            if (us) us->walk_ms = (float)(now_ms() - t0);
+            job.bgzf = text ? text : "", job.bgzf_bytes = n, job.members = &members, job.gunzip_stats = us;
+            text = "", n = total;
+        }
+        src.mem = text ? text : "";
+        return YACRD_OK;
+    }
+    // the way out: a call that failed leaves zeroed stats and no memory
+    int leave(int rc)
+    {
+        if (rc == YACRD_OK) return rc;
+        if (st) std::memset(st, 0, sizeof(*st));
+        if (gs) std::memset(gs, 0, sizeof(*gs));
+        if (us) std::memset(us, 0, sizeof(*us));
+        if (sink.fd < 0) std::free(sink.mem), sink.mem = nullptr;
+        return rc;
+    }
+    // the run, into a file written beside its place and moved there when every byte is in it: a text that is not for this
+    // path leaves nothing behind
+    int run_to_file(yacrd_engine *e, uint64_t n, const char *out_path)
+    {
+        yseg::BesideFile file;
+        if (!file.open(out_path)) return fail(YACRD_EFALLBACK, std::string("cannot create a file beside ") + out_path + ": the host loop words the error");
+        sink.fd = file.fd;
+        int rc = run_seq_edit(e, job, src, n, sink, st);
+        if (rc == YACRD_OK && !file.commit()) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
+        return leave(rc);
+    }
+};
+
+// the forms, for FASTQ and for FASTA: a file to a file; memory to memory, gzip out or not; memory to a file, gzip out
 int edit_seq_file(bool fasta, yacrd_engine *e, int op, const char *in_path, const char *out_path, int n_threads, const yacrd_report_table *t,
                   yacrd_seq_edit_stats *st)
 {
-    if (const int rca = seq_edit_args(fasta, e, op, t, st)) return rca;
+    SeqCall c{st, nullptr, nullptr};
+    if (const int rca = c.enter(fasta, e, op, t, false)) return rca;
     if (!in_path || !out_path) return fail(YACRD_EINVAL, "null argument");
-    if (fasta && !named_fasta(in_path)) return fail(YACRD_EFALLBACK, "not a FASTA file by its name: the host loop's case");
-    if (!fasta && !named_fastq(in_path)) return fail(YACRD_EFALLBACK, "not a FASTQ file by its name: the host loop's case");
+    if (!named_as(fasta, in_path))
+        return fail(YACRD_EFALLBACK, fasta ? "not a FASTA file by its name: the host loop's case" : "not a FASTQ file by its name: the host loop's case");
     const int fd = ::open(in_path, O_RDONLY);
     if (fd < 0) return fail(YACRD_EFALLBACK, std::string("cannot open ") + in_path + ": the host loop words the error");
     FdGuard fdg{fd};
@@ -1253,113 +1212,39 @@ int edit_seq_file(bool fasta, yacrd_engine *e, int op, const char *in_path, cons
         if (!S_ISREG(ost.st_mode)) return fail(YACRD_EFALLBACK, "the output is not a regular file: the host loop writes it");
         if (ost.st_dev == sst.st_dev && ost.st_ino == sst.st_ino) return fail(YACRD_EFALLBACK, "input and output are one file: the host loop's case");
     }
-    // written beside its place and moved there when every byte is in it: a text that is not for this path leaves nothing behind
-    yseg::BesideFile file;
-    if (!file.open(out_path)) return fail(YACRD_EFALLBACK, std::string("cannot create a file beside ") + out_path + ": the host loop words the error");
-    SeqJob job;
-    job.op = op, job.n_threads = n_threads, job.table = t, job.fasta = fasta;
-    TextSource src;
-    src.fd = fd;
-    Sink sink;
-    sink.fd = file.fd;
-    int rc = run_seq_edit(e, job, src, (u64)sst.st_size, sink, st);
-    if (rc == YACRD_OK && !file.commit()) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
-    if (rc != YACRD_OK && st) std::memset(st, 0, sizeof(*st));
-    return rc;
+    c.job.n_threads = n_threads;
+    c.src.fd = fd;
+    return c.run_to_file(e, (u64)sst.st_size, out_path);
 }
 
 int edit_seq_mem(bool fasta, yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, char **out, uint64_t *out_bytes,
-                 yacrd_seq_edit_stats *st)
+                 yacrd_seq_edit_stats *st, bool gzip = false, yacrd_gzip_stats *gs = nullptr, bool bgzf = false, yacrd_gunzip_stats *us = nullptr)
 {
-    if (const int rca = seq_edit_args(fasta, e, op, t, st)) return rca;
+    SeqCall c{st, gs, us};
+    if (const int rca = c.enter(fasta, e, op, t, gzip)) return rca;
     if ((!text && n) || !out || !out_bytes) return fail(YACRD_EINVAL, "null argument");
     *out = nullptr, *out_bytes = 0;
-    SeqJob job;
-    job.op = op, job.table = t, job.fasta = fasta;
-    TextSource src;
-    src.mem = text ? text : "";
-    Sink sink;
-    const int rc = run_seq_edit(e, job, src, n, sink, st);
-    if (rc != YACRD_OK) {
-        std::free(sink.mem);
-        if (st) std::memset(st, 0, sizeof(*st));
-        return rc;
+    if (const int rcw = c.text_in(text, n, bgzf)) return rcw;
+    if (gzip) { // (plain: the run sizes the memory when it knows the output's bytes)
+        c.sink.cap = (size_t)(n / 3 + 4096); // (the sink grows when the members need more)
+        c.sink.mem = (char *)std::malloc((size_t)c.sink.cap);
+        if (!c.sink.mem) return fail(YACRD_ENOMEM, "host allocation failed");
     }
-    *out = sink.mem, *out_bytes = sink.at;
-    return YACRD_OK;
-}
-
-// BGZF in: `text`, `n` are the compressed file; the walk fills `members`, the job's BGZF fields and `n` (the text's bytes)
-int seq_job_bgzf(SeqJob &job, std::vector<yif::InfMember> &members, const char *&text, uint64_t &n, yacrd_gunzip_stats *us)
-{
-    const double t0 = now_ms();
-    u64 total = 0;
-    if (!ybw::walk(reinterpret_cast<const unsigned char *>(text), n, members, &total)) return fail(YACRD_EFALLBACK, "not BGZF: the host reader's");
-    if (us) us->walk_ms = (float)(now_ms() - t0);
-    job.bgzf = text ? text : "", job.bgzf_bytes = n, job.members = &members, job.gunzip_stats = us;
-    text = "", n = total;
-    return YACRD_OK;
-}
-
-int edit_seq_gzip_mem(bool fasta, yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, char **out,
-                      uint64_t *out_bytes, yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs, bool bgzf = false, yacrd_gunzip_stats *us = nullptr)
-{
-    if (gs) std::memset(gs, 0, sizeof(*gs));
-    if (us) std::memset(us, 0, sizeof(*us));
-    if (const int rca = seq_edit_args(fasta, e, op, t, st)) return rca;
-    if ((!text && n) || !out || !out_bytes) return fail(YACRD_EINVAL, "null argument");
-    *out = nullptr, *out_bytes = 0;
-    SeqJob job;
-    job.op = op, job.table = t, job.gzip = true, job.gzip_stats = gs, job.fasta = fasta;
-    std::vector<yif::InfMember> members;
-    if (bgzf)
-        if (const int rcw = seq_job_bgzf(job, members, text, n, us)) return rcw;
-    TextSource src;
-    src.mem = text ? text : "";
-    Sink sink;
-    sink.cap = (size_t)(n / 3 + 4096); // (the sink grows when the members need more)
-    sink.mem = (char *)std::malloc((size_t)sink.cap);
-    if (!sink.mem) return fail(YACRD_ENOMEM, "host allocation failed");
-    const int rc = run_seq_edit(e, job, src, n, sink, st);
-    if (rc != YACRD_OK) {
-        std::free(sink.mem);
-        if (st) std::memset(st, 0, sizeof(*st));
-        if (gs) std::memset(gs, 0, sizeof(*gs));
-        if (us) std::memset(us, 0, sizeof(*us));
-        return rc;
-    }
-    *out = sink.mem, *out_bytes = sink.at;
+    if (const int rc = c.leave(run_seq_edit(e, c.job, c.src, n, c.sink, st))) return rc;
+    *out = c.sink.mem, *out_bytes = c.sink.at;
     return YACRD_OK;
 }
 
 int edit_seq_gzip_file(bool fasta, yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, const char *out_path,
                        yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs, bool bgzf = false, yacrd_gunzip_stats *us = nullptr)
 {
-    if (gs) std::memset(gs, 0, sizeof(*gs));
-    if (us) std::memset(us, 0, sizeof(*us));
-    if (const int rca = seq_edit_args(fasta, e, op, t, st)) return rca;
+    SeqCall c{st, gs, us};
+    if (const int rca = c.enter(fasta, e, op, t, true)) return rca;
     if ((!text && n) || !out_path) return fail(YACRD_EINVAL, "null argument");
-    SeqJob job;
-    std::vector<yif::InfMember> members;
-    if (bgzf) // (before a file is made beside out_path: what is not BGZF leaves nothing)
-        if (const int rcw = seq_job_bgzf(job, members, text, n, us)) return rcw;
+    if (const int rcw = c.text_in(text, n, bgzf)) return rcw;
     struct stat ost;
     if (lstat(out_path, &ost) == 0 && !S_ISREG(ost.st_mode)) return fail(YACRD_EFALLBACK, "the output is not a regular file: the host loop writes it");
-    yseg::BesideFile file;
-    if (!file.open(out_path)) return fail(YACRD_EFALLBACK, std::string("cannot create a file beside ") + out_path + ": the host loop words the error");
-    job.op = op, job.table = t, job.gzip = true, job.gzip_stats = gs, job.fasta = fasta;
-    TextSource src;
-    src.mem = text ? text : "";
-    Sink sink;
-    sink.fd = file.fd;
-    int rc = run_seq_edit(e, job, src, n, sink, st);
-    if (rc == YACRD_OK && !file.commit()) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
-    if (rc != YACRD_OK) {
-        if (st) std::memset(st, 0, sizeof(*st));
-        if (gs) std::memset(gs, 0, sizeof(*gs));
-        if (us) std::memset(us, 0, sizeof(*us));
-    }
-    return rc;
+    return c.run_to_file(e, n, out_path);
 }
 
 } // namespace
@@ -1379,7 +1264,7 @@ int yacrd_engine_edit_fastq_mem(yacrd_engine *e, int op, const char *text, uint6
 int yacrd_engine_edit_fastq_gzip_mem(yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, char **out,
                                      uint64_t *out_bytes, yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs)
 {
-    return edit_seq_gzip_mem(false, e, op, text, n, t, out, out_bytes, st, gs);
+    return edit_seq_mem(false, e, op, text, n, t, out, out_bytes, st, true, gs);
 }
 int yacrd_engine_edit_fastq_gzip_file(yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, const char *out_path,
                                       yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs)
@@ -1400,7 +1285,7 @@ int yacrd_engine_edit_fasta_mem(yacrd_engine *e, int op, const char *text, uint6
 int yacrd_engine_edit_fasta_gzip_mem(yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, char **out,
                                      uint64_t *out_bytes, yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs)
 {
-    return edit_seq_gzip_mem(true, e, op, text, n, t, out, out_bytes, st, gs);
+    return edit_seq_mem(true, e, op, text, n, t, out, out_bytes, st, true, gs);
 }
 int yacrd_engine_edit_fasta_gzip_file(yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, const char *out_path,
                                       yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs)
@@ -1411,7 +1296,7 @@ int yacrd_engine_edit_fasta_gzip_file(yacrd_engine *e, int op, const char *text,
 int yacrd_engine_edit_fastq_bgzf_mem(yacrd_engine *e, int op, const char *bgzf, uint64_t n, const yacrd_report_table *t, char **out,
                                      uint64_t *out_bytes, yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs, yacrd_gunzip_stats *us)
 {
-    return edit_seq_gzip_mem(false, e, op, bgzf, n, t, out, out_bytes, st, gs, true, us);
+    return edit_seq_mem(false, e, op, bgzf, n, t, out, out_bytes, st, true, gs, true, us);
 }
 int yacrd_engine_edit_fastq_bgzf_file(yacrd_engine *e, int op, const char *bgzf, uint64_t n, const yacrd_report_table *t, const char *out_path,
                                       yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs, yacrd_gunzip_stats *us)
@@ -1421,7 +1306,7 @@ int yacrd_engine_edit_fastq_bgzf_file(yacrd_engine *e, int op, const char *bgzf,
 int yacrd_engine_edit_fasta_bgzf_mem(yacrd_engine *e, int op, const char *bgzf, uint64_t n, const yacrd_report_table *t, char **out,
                                      uint64_t *out_bytes, yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs, yacrd_gunzip_stats *us)
 {
-    return edit_seq_gzip_mem(true, e, op, bgzf, n, t, out, out_bytes, st, gs, true, us);
+    return edit_seq_mem(true, e, op, bgzf, n, t, out, out_bytes, st, true, gs, true, us);
 }
 int yacrd_engine_edit_fasta_bgzf_file(yacrd_engine *e, int op, const char *bgzf, uint64_t n, const yacrd_report_table *t, const char *out_path,
                                       yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs, yacrd_gunzip_stats *us)

@@ -1,7 +1,9 @@
 // gpu_text.h — what the translation units that work on TEXT in HBM share: gpu_paf.hip (the device parser), gpu_edit.hip
-// (filter / extract on overlap files), gpu_seq_edit.hip (the FASTQ editors), gpu_report.hip (the report reader) and gpu_deflate.hip.  Where the text comes from
-// (TextSource, FdGuard, the format rule), the mover (pread -> pinned 4 MiB chunks -> the mirror in HBM, a segment handed on
-// as soon as it has landed), the staged-window accessor, the byte matcher and the id hash; what an ingest's outputs share.
+// (filter / extract on overlap files), gpu_seq_edit.hip (the FASTQ and FASTA editors), gpu_report.hip (the report reader),
+// gpu_report_write.hip (the report writer), gpu_deflate.hip and gpu_inflate.hip.  Where the text comes from (TextSource, FdGuard,
+// the format rule), the mover (pread -> pinned 4 MiB chunks -> the mirror in HBM, a segment handed on as soon as it has
+// landed), the way home (HomeLink: what the editors, the report writer and the inflater plug into host/segment_pump.h), the
+// staged-window accessor, the byte matcher and the id hash; what an ingest's outputs share.
 #pragma once
 #include "engine_internal.h"
 
@@ -120,6 +122,25 @@ struct TextSource {
         }
         return true;
     }
+};
+
+// the way home of a text that lies in HBM: the link yseg::pump (host/segment_pump.h) drives.  src[at, at + len) is copied to a
+// pinned piece on `stream`, with the event of that piece behind it.  `stop`, where given, is a word another thread sets to
+// end the run: wait then gives up without touching `bad`, which holds the HIP error of a call that failed.
+struct HomeLink {
+    const char *src;
+    hipStream_t stream;
+    hipEvent_t landed[2];
+    const std::atomic<int> *stop = nullptr;
+    hipError_t bad = hipSuccess;
+    bool start(u64 i, char *dst, u64 at, size_t len)
+    {
+        bad = hipMemcpyAsync(dst, src + at, len, hipMemcpyDeviceToHost, stream);
+        if (bad == hipSuccess) bad = hipEventRecord(landed[i & 1], stream);
+        return bad == hipSuccess;
+    }
+    bool wait(u64 i) { return !(stop && stop->load()) && (bad = hipEventSynchronize(landed[i & 1])) == hipSuccess; }
+    void drain() { (void)hipStreamSynchronize(stream); }
 };
 
 // what an ingest (overlaps or a report) hands back, empty
