@@ -93,6 +93,18 @@ void yacrd_debug_live_bytes(uint64_t out[2]);
 /* runs of this engine whose long launch went out direct (YACRD_F_SCREEN_DIRECT above) since it was created; a batch that is
  * run again (a missed prediction) counts each time */
 uint64_t yacrd_debug_direct_runs(const yacrd_engine *e);
+/* the reads beyond 16 384 intervals of the engine's last completed run, by the tier of the cascade that decided them (DESIGN.md
+ * 3.3; every tier is exact, so the result does not say):
+ *   [0] the device-wide screen (csrc/screen_big.h): the class count minus its fallback list;
+ *   [1] thinned by the trimming filter and swept in LDS (csrc/sweep_big_trim.h: BT_TRIMMED);
+ *   [2] entered the segmented sort (csrc/sweep_big.h);
+ *   [3] handed to the exact kernel (csrc/sweep_general.h) from any of these: a reversed interval met by the filter, a read the
+ *       sort's pass A found degenerate, a thinned read the LDS sweep rejected, the whole class under YACRD_F_FORCE_GENERAL.
+ * A read counts once per tier it ENTERED: a thinned read that bt_sweep_kernel then rejects is under [1] and [3], a read the
+ * sort sends on under [2] and [3]; [0] + [1] + [2] + (reads in [3] that entered neither [1] nor [2]) is the class count.
+ * After a missed class prediction the device-wide screen goes out twice: the final pass is reported, not the sum.  A
+ * batch that ran as one launch (YACRD_F_ONE_LAUNCH) has no such reads: all four are 0. */
+void yacrd_debug_big_routes(const yacrd_engine *e, uint64_t out[4]);
 /* YACRD_TEST_REPORT_SEGMENT=<bytes> (environment, tests; read at every call): the size of the segments in which
  * yacrd_engine_write_report[_mem] brings the formatted text home, instead of 64 MiB (csrc/gpu_report_write.hip: kReportSegment;
  * 1 .. 2^30).  The bytes written do not depend on it: tests/test_gpu_report_write.py cuts lines at hundreds of borders. */

@@ -175,13 +175,17 @@ int gather_reads(yacrd_engine *e, const u64 *d_off, const u32 *d_len, const u32 
     return YACRD_OK;
 }
 
-// Global-memory exact path over `count` reads listed at d_list (host knows the count).
+// Global-memory exact path over `count` reads listed at d_list (host knows the count).  Those beyond 16 384 intervals are
+// counted in big_routes[3]: the lists it is given also hold smaller reads (rej_big: the LDS classes' rejections; the whole
+// batch under YACRD_F_FORCE_GENERAL).
 int run_general_global(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u32 *d_len,
                        const u32 *d_list, u32 count, u32 cov, hipStream_t stream)
 {
     std::vector<yk::GatherOut> info;
     int rc = gather_reads(e, d_off, d_len, d_list, count, stream, info);
     if (rc) return rc;
+    for (const auto &g : info)
+        if (2 * g.n > (u64)yk::kMedium2Events) e->big_routes[3]++;
     HIP_TRY(e->gen_scratch_off.reserve((size_t)count * sizeof(u64)));
     std::vector<u64> offs(count);
     u64 tot = 0;
@@ -214,6 +218,7 @@ int run_big_sort(yacrd_engine *e, const uint2 *d_iv, const std::vector<yk::Gathe
                  hipStream_t stream, std::vector<u32> &redo)
 {
     const u32 count = (u32)info.size();
+    e->big_routes[2] += count;
     std::vector<yk::BigSeg> segs(count);
     std::vector<u32> chunk_seg;
     u64 key_off = 0;
@@ -341,7 +346,10 @@ int run_big(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u32 *d_l
         HIP_TRY(hipGetLastError());
         std::vector<yk::GatherOut> rest;
         for (u32 i = 0; i < count; i++) {
-            if (bs[i].flags & yk::BT_TRIMMED) continue;
+            if (bs[i].flags & yk::BT_TRIMMED) {
+                e->big_routes[1]++; // (bt_sweep_kernel may still have rejected it: then it is in rej_big as well)
+                continue;
+            }
             if (bs[i].flags & yk::BT_BAD) redo.push_back(info[i].read);
             else rest.push_back(info[i]);
         }
@@ -859,6 +867,7 @@ int launch_sweeps(yacrd_engine *e, Run &R, const LaunchSet &set, bool again = fa
 int launch_device_wide_screen_on(yacrd_engine *e, Run &R, u32 count, u64 iv_big, hipStream_t hs)
 {
     yk::Counters *ctr = R.ctr;
+    e->big_routes[1] = e->big_routes[2] = e->big_routes[3] = 0; // (a second pass, behind a missed prediction, starts over)
     if (e->flags & YACRD_F_FORCE_GENERAL)
         return run_general_global(e, R.d_off, R.d_iv, R.d_len, R.list_of(yk::CLS_GENERAL), count, R.cov, e->stream);
     if (!R.prefilter)
@@ -953,6 +962,11 @@ int recover(yacrd_engine *e, Run &R, float &extra_ms)
         if (any_missing || big_mismatch) {
             e->miss_pending = true; // (the prediction did not hold: yacrd_timing.prediction_misses)
             HIP_TRY(hipEventRecord(e->ev[EV_X0], e->stream));
+            // (the device-wide screen's first pass counted the reads it decided — of the min(real, predicted) it looked at,
+            // all but its fallback list — and the second pass counts every one again: take the first count back)
+            if (big_mismatch && R.big_screened && R.prefilter == 2)
+                HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)&ctr->prefiltered,
+                                          (int)(c0.prefiltered - (std::min(c0.n[yk::CLS_GENERAL], R.big_n) - c0.fb_big)), 1, e->stream));
             if (any_missing && (rc = launch_sweeps(e, R, missing, true))) return rc;
             if (big_mismatch && c0.n[yk::CLS_GENERAL] &&
                 (rc = launch_device_wide_screen_on(e, R, c0.n[yk::CLS_GENERAL], c0.iv[yk::CLS_GENERAL], e->stream))) return rc;
@@ -1047,6 +1061,7 @@ int run_on_device(yacrd_engine *e, const u64 *d_off, const uint2 *d_iv, const u3
     e->has_result = false;
     e->resident.valid = e->input.valid = false; // (in_len and the result arrays are about to be rewritten)
     e->timing = yacrd_timing{};
+    for (uint64_t &r : e->big_routes) r = 0;
 
     HIP_TRY(e->bad_offsets.reserve((n_reads64 + 1) * sizeof(u64)));
     if (n_reads64 == 0) {
@@ -1192,6 +1207,7 @@ int conclude_run(yacrd_engine *e, const Run &R, float extra_ms)
     e->last_reads = R.n_reads;
     e->last_regions = c1.total_regions;
     e->has_result = true;
+    e->big_routes[0] = R.big_screened ? (uint64_t)c0.n[yk::CLS_GENERAL] - c1.fb_big : 0; // (the last pass's fallback list)
     e->pred = c1;
     e->pred_reads = R.n_reads64;
     e->pred_iv = R.n_iv;
@@ -1472,6 +1488,10 @@ int yacrd_debug_last_input_csr(yacrd_engine *e, uint64_t *n_reads, uint64_t *n_i
 
 /* include/yacrd_engine_debug.h: what DevBuf / PinBuf hold, process-wide (tests) */
 uint64_t yacrd_debug_direct_runs(const yacrd_engine *e) { return e ? e->direct_runs : 0; }
+void yacrd_debug_big_routes(const yacrd_engine *e, uint64_t out[4])
+{
+    for (int i = 0; i < 4; i++) out[i] = e ? e->big_routes[i] : 0;
+}
 
 void yacrd_debug_live_bytes(uint64_t out[2])
 {

@@ -318,6 +318,9 @@ struct yacrd_engine {
     int last_build = -1, prev_build = -1; // build of the register classes' launch in the last run / the one before (-1: none; 0 sorting, 1 / 2 screening with one / two items, 3 second looks)
     bool miss_pending = false;            // the run in progress is the synchronous re-run of a batch whose prediction did not hold
     uint64_t direct_runs = 0;  // runs that went out direct (yacrd_debug_direct_runs)
+    // the last run's reads beyond 16 384 intervals by the tier that decided them (yacrd_debug_big_routes): [0] device-wide
+    // screen (conclude_run), [1] thinned and swept in LDS, [2] entered the segmented sort, [3] handed to the exact kernel
+    uint64_t big_routes[4] = {0, 0, 0, 0};
     uint32_t nodefer_left = 0; // batches the sorting build of the fused launch still takes before the screen is tried again
     // pinned bounce buffers for pageable inputs (yke::h2d), allocated on first use; an event per
     // buffer says when its DMA is done and it may be refilled

@@ -36,7 +36,7 @@ F_NO_SCREEN_DIRECT = 16777216  # ... never (A/B)
 # debug symbols beside the flags (include/yacrd_engine_debug.h); EXPORTED_SYMBOLS below is yacrd_engine.h's list alone
 DEBUG_SYMBOLS = [
     "yacrd_debug_sort_pairs", "yacrd_debug_last_counters", "yacrd_debug_last_input_csr", "yacrd_debug_peer_copy_counts",
-    "yacrd_debug_live_bytes", "yacrd_debug_direct_runs",
+    "yacrd_debug_live_bytes", "yacrd_debug_direct_runs", "yacrd_debug_big_routes",
 ]
 F_ONE_LAUNCH = 4194304  # include/yacrd_engine.h: a short batch as ONE kernel launch (csrc/one_batch.h)
 
@@ -738,6 +738,16 @@ class Engine:
         self._lib.yacrd_debug_direct_runs.restype = ctypes.c_uint64
         self._lib.yacrd_debug_direct_runs.argtypes = [ctypes.c_void_p]
         return int(self._lib.yacrd_debug_direct_runs(self._h))
+
+    def big_routes(self):
+        """yacrd_debug_big_routes (tests, tools): the last completed run's reads beyond 16 384 intervals by the tier that
+        decided them: (device-wide screen, thinned and swept in LDS, entered the segmented sort, handed to the exact kernel).
+        A thinned read the LDS sweep rejects, and a read the sort finds degenerate, count under their tier and the last."""
+        out = (ctypes.c_uint64 * 4)()
+        self._lib.yacrd_debug_big_routes.restype = None
+        self._lib.yacrd_debug_big_routes.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._lib.yacrd_debug_big_routes(self._h, out)
+        return tuple(int(v) for v in out)
 
     def _type_table(self, names, read_type):
         """(names, read_type) -> a yacrd_type_table and what keeps its memory alive; names: str or bytes, one per read."""
