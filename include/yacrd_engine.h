@@ -464,6 +464,26 @@ typedef struct {
 int yacrd_engine_gunzip_mem(yacrd_engine *e, const char *bgzf, uint64_t n_bytes,
                             char **out, uint64_t *out_bytes, yacrd_gunzip_stats *st /* may be NULL */);
 
+/* yacrd_engine_ingest_overlaps_mem and yacrd_engine_ingest_report_mem over a BGZF stream as it lies in host memory (read
+ * or mapped: no host inflate).  The host walks the members, the COMPRESSED bytes go up in the mover's 4 MiB chunks, and for
+ * every 128 MiB of them that has landed the members that have become complete are decoded by one launch on the engine's
+ * stream (csrc/bgzf_plan.h names them); the parser's / the reader's scan runs over every 128 MiB of TEXT that is whole behind
+ * those launches, as it does over plain text that lands.  `out`, `reads` and the resident table are bit for bit those of the
+ * _mem form on the inflated text.  stats->text_bytes is the inflated size, text_ms covers the way up and the inflate; `us`
+ * as in the editors' _bgzf_ forms: walk_ms, h2d_ms (the compressed bytes), kernel_ms (the decoder's launches, by device
+ * events), d2h_ms 0.  YACRD_EFALLBACK, with nothing returned and the engine usable: a stream that is not BGZF, a member the
+ * decoder does not take (yacrd_engine_gunzip_mem's list; the decoder's status is read before anything is sized from the text,
+ * and wins over what the parser made of it), the _mem forms' own causes in the text, a text beyond the device's free memory
+ * (which now also holds the compressed bytes and the member table).  The caller then inflates on the host
+ * (yacrd_text_from_file) and takes the _mem form or the host parser.  Additive: found by the symbol. */
+int yacrd_engine_ingest_overlaps_bgzf_mem(yacrd_engine *e, const char *bgzf, uint64_t n_bytes, int format /* 1 PAF, 2 M4 */,
+                                          int n_threads, uint32_t coverage, double not_coverage, yacrd_result *out,
+                                          yacrd_reads *reads, yacrd_ingest_stats *stats /* may be NULL */,
+                                          yacrd_gunzip_stats *us /* may be NULL */);
+int yacrd_engine_ingest_report_bgzf_mem(yacrd_engine *e, const char *bgzf, uint64_t n_bytes, int n_threads, double not_coverage,
+                                        yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats /* may be NULL */,
+                                        yacrd_gunzip_stats *us /* may be NULL */);
+
 /* filter / extract with gzip out: the kept bytes of yacrd_engine_edit_overlaps_mem deflated where the pack pass leaves them
  * in HBM, so that only members cross the link and reach the file.  `text` is the overlap text in host memory, already
  * inflated (format 1 = PAF / 2 = M4, MHAP): this library links no zlib and inflates BGZF only for the sequence editors

@@ -157,6 +157,14 @@ void yacrd_bytes_free(char *p);
  * non-zero, with nothing returned, for a stream that is not BGZF or holds a member the decoder does not take (the message
  * names the member and the cause).  Stricter than zlib in places, never more lenient.  `out`: yacrd_bytes_free. */
 int yacrd_bgzf_decode_host(const char *data, uint64_t n, char **out, uint64_t *out_bytes);
+/* The planner of the segment-wise device inflate (csrc/bgzf_plan.h) over a BGZF stream and a schedule: landed[k] is the
+ * number of compressed bytes in HBM at call k (it never falls).  chunk / seg_chunks: the text segments' unit and length in
+ * units; 0 = the mover's (4 MiB, 32).  members_out: in_off, csize, isize, out_off per member of the walk; steps_out, eight
+ * words per step: the call k that gave it, the member range [m0, m1) to launch, the text inflated behind that launch, the
+ * text segment [t0, t1) to hand on (t0 == t1: none) with its avail, and 1 in the step that ends the text.  Both through
+ * yacrd_bytes_free.  Non-zero: not BGZF, or a falling schedule. */
+int yacrd_bgzf_plan_segments(const char *data, uint64_t n, const uint64_t *landed, uint64_t n_landed, uint64_t chunk, uint64_t seg_chunks,
+                             uint64_t **members_out, uint64_t *n_members, uint64_t **steps_out, uint64_t *n_steps);
 /* The encoder's code-length construction: freq[n] -> len[n] with no length above `limit` (n in 2..286, limit in 5..15,
  * 2^limit >= n).  Fewer than two used symbols are given company, as zlib does, so the code is always complete. */
 int yacrd_deflate_code_lengths(const uint32_t *freq, uint32_t n, uint32_t limit, uint8_t *len);

@@ -14,6 +14,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <functional>
 #include <new>
 #include <string>
 #include <vector>
@@ -448,6 +449,30 @@ struct InflateDevice {
 };
 int inflate_device_open(yacrd_engine *e, u64 comp_bytes, const yif::InfMember *members, u64 n_members, InflateDevice *d);
 int inflate_device_run(yacrd_engine *e, const InflateDevice &d, hipStream_t st, unsigned char *d_text, u64 text_bytes);
+// the same for members [m0, m1) of the table alone (inflate_device_run: all of them): what move_bgzf_text launches as the stream lands
+int inflate_device_run_range(yacrd_engine *e, const InflateDevice &d, hipStream_t st, unsigned char *d_text, u64 text_bytes, u64 m0, u64 m1);
+// device bytes the inflate scratch holds (the stream's buffer and the member table): what a caller's does-it-fit check may count as free
+u64 inflate_device_held(yacrd_engine *e);
 // the message of a status word that is not 0 (YACRD_EFALLBACK)
 int inflate_not_taken(u32 status);
+// A BGZF stream in host memory -> its text at d_text[0, text_bytes) in HBM, inflated while it lands (gpu_inflate.hip; used by
+// gpu_paf.hip and gpu_report.hip).  move_text (gpu_text.h) carries the COMPRESSED bytes into the inflate scratch; for every
+// segment of them that has landed the planner (bgzf_plan.h) names the members that have become complete, which are launched
+// on e->stream — it waits for the chunks' copy events already — and the text segments that are whole behind that launch,
+// each handed to on_text_segment(t0, t1, avail) under move_text's contract: what the consumer launches on e->stream sees the
+// text, the host waits for nothing.  Returns move_text's codes (0; 1 a HIP call failed, or *rc the code of an open that
+// failed; 2; 3).  Behind the stream *bm.d.status is the decoder's status word (inflate_device_run), for the caller to read
+// with its own first synchronisation and BEFORE it sizes anything from what the text says; bm.kernel_ms() after that.
+// (the record-room estimate of a text that is not in host memory: host/inflate_sample.cc)
+bool bgzf_head_lines(const unsigned char *comp, uint64_t comp_bytes, const yif::InfMember *members, uint64_t n_members, uint64_t max_text,
+                     uint64_t *text, uint64_t *lines);
+struct BgzfMove {
+    InflateDevice d;
+    Events ev; // a timed pair around every launch
+    size_t n_ev = 0, n_launches = 0;
+    float h2d_ms = 0.f;
+    float kernel_ms() const;
+};
+int move_bgzf_text(yacrd_engine *e, const char *comp_src, u64 comp_bytes, const std::vector<yif::InfMember> &members, unsigned char *d_text,
+                   u64 text_bytes, int n_threads, const std::function<void(u64, u64, u64)> &on_text_segment, BgzfMove &bm, int *rc);
 } // namespace yke

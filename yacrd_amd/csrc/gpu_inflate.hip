@@ -1,5 +1,6 @@
 // gpu_inflate.hip — BGZF inflated on the GPU: a stream in HBM -> its text in HBM (include/yacrd_engine.h:
-// yacrd_engine_gunzip_mem; gpu_seq_edit.hip: the editors' _bgzf_ forms).
+// yacrd_engine_gunzip_mem; gpu_seq_edit.hip: the editors' _bgzf_ forms; gpu_paf.hip / gpu_report.hip: the _bgzf_mem ingests,
+// through move_bgzf_text below, which decodes the members of every landed segment while the rest of the stream is on its way).
 //
 //   walk     on the host (bgzf_walk.h, no zlib): every member's payload, sizes and place in the text; what is not BGZF is
 //            the host reader's (YACRD_EFALLBACK)
@@ -14,6 +15,7 @@
 // text then holds whatever was decoded until then, and the caller does not use the text.
 #include "engine_internal.h"
 #include "gpu_text.h"
+#include "bgzf_plan.h"
 #include "bgzf_walk.h"
 #include "inflate_block.h"
 #include "host/segment_pump.h"
@@ -25,12 +27,13 @@ using namespace yke;
 
 namespace yk {
 
-__global__ __launch_bounds__(64) void inf_kernel(const unsigned char *comp, u64 comp_bytes, const yif::InfMember *members, u32 n_members,
+// members [m0, m1) of the table, one workgroup each
+__global__ __launch_bounds__(64) void inf_kernel(const unsigned char *comp, u64 comp_bytes, const yif::InfMember *members, u32 m0, u32 m1,
                                                   unsigned char *text, u64 text_bytes, u32 *status)
 {
     __shared__ yif::InfShared sh;
-    const u32 m = blockIdx.x;
-    if (m >= n_members) return; // (uniform)
+    const u32 m = m0 + blockIdx.x; // (m1 < 2^31: inflate_device_open)
+    if (m >= m1) return; // (uniform)
     const yif::InfMember mm = members[m];
     const u32 lane = threadIdx.x;
     const u32 csize = YI_UNI(mm.csize), n = YI_UNI(mm.isize);
@@ -79,14 +82,83 @@ int inflate_device_open(yacrd_engine *e, u64 comp_bytes, const yif::InfMember *m
     return YACRD_OK;
 }
 
-int inflate_device_run(yacrd_engine *e, const InflateDevice &d, hipStream_t st, unsigned char *d_text, u64 text_bytes)
+int inflate_device_run_range(yacrd_engine *e, const InflateDevice &d, hipStream_t st, unsigned char *d_text, u64 text_bytes, u64 m0, u64 m1)
 {
     (void)e;
-    if (d.n_members)
-        hipLaunchKernelGGL(yk::inf_kernel, dim3((u32)d.n_members), dim3(64), 0, st, d.comp, d.comp_bytes, d.members, (u32)d.n_members, d_text,
+    if (m0 > m1 || m1 > d.n_members) return fail(YACRD_EINTERNAL, "device inflate: a member range outside the table");
+    if (m1 > m0)
+        hipLaunchKernelGGL(yk::inf_kernel, dim3((u32)(m1 - m0)), dim3(64), 0, st, d.comp, d.comp_bytes, d.members, (u32)m0, (u32)m1, d_text,
                            text_bytes, d.status);
     HIP_TRY(hipGetLastError());
     return YACRD_OK;
+}
+
+int inflate_device_run(yacrd_engine *e, const InflateDevice &d, hipStream_t st, unsigned char *d_text, u64 text_bytes)
+{
+    return inflate_device_run_range(e, d, st, d_text, text_bytes, 0, d.n_members);
+}
+
+u64 inflate_device_held(yacrd_engine *e)
+{
+    const auto &s = e->scratch[InflateScratch::kScratchSlot];
+    const InflateScratch *S = static_cast<const InflateScratch *>(s.p);
+    return S ? (u64)S->comp.cap + (u64)S->members.cap : 0;
+}
+
+float BgzfMove::kernel_ms() const
+{
+    float k = 0;
+    for (size_t i = 0; i + 1 < n_ev; i += 2) k += ev_ms(ev[i], ev[i + 1]);
+    return k;
+}
+
+int move_bgzf_text(yacrd_engine *e, const char *comp_src, u64 comp_bytes, const std::vector<yif::InfMember> &members, unsigned char *d_text,
+                   u64 text_bytes, int n_threads, const std::function<void(u64, u64, u64)> &on_text_segment, BgzfMove &bm, int *rc_out)
+{
+    static_assert(ybw::kPlanChunk == kTextChunk && ybw::kPlanSeg == kTextSeg, "the planner's segments are move_text's");
+    *rc_out = YACRD_OK;
+    if ((*rc_out = inflate_device_open(e, comp_bytes, members.data(), members.size(), &bm.d))) return 1;
+    // one pair of timed events around every launch: a launch per landed segment of the stream, and one to end with
+    const size_t n_pairs = (size_t)((comp_bytes + kTextChunk * kTextSeg - 1) / (kTextChunk * kTextSeg)) + 2;
+    if (!bm.ev.add(2 * n_pairs)) {
+        *rc_out = fail(YACRD_ENODEV, "device inflate: no events");
+        return 1;
+    }
+    // (measurements only: the whole stream up first, then one launch — what the segment-wise launches are compared with)
+    const char *whole_env = std::getenv("YACRD_BGZF_ONE_LAUNCH");
+    const bool whole = whole_env && whole_env[0] == '1';
+    ybw::SegmentPlan plan(members.data(), members.size(), text_bytes);
+    int bad = 0; // a HIP call of a launch failed
+    auto landed = [&](u64 have) {
+        ybw::PlanStep s;
+        while (!bad && plan.next(have, s)) {
+            if (s.m1 > s.m0) {
+                if (bm.n_ev + 2 > bm.ev.v.size() || hipEventRecord(bm.ev[bm.n_ev], e->stream) != hipSuccess ||
+                    inflate_device_run_range(e, bm.d, e->stream, d_text, text_bytes, s.m0, s.m1) != YACRD_OK ||
+                    hipEventRecord(bm.ev[bm.n_ev + 1], e->stream) != hipSuccess) {
+                    bad = 1;
+                    break;
+                }
+                bm.n_ev += 2, bm.n_launches++;
+            }
+            if (s.t1 > s.t0) on_text_segment(s.t0, s.t1, s.avail);
+        }
+    };
+    const double t0 = now_ms();
+    TextSource src;
+    src.mem = comp_src;
+    const int moved = move_text(e, src, 0, comp_bytes, reinterpret_cast<char *>(bm.d.comp), bm.d.fresh, n_threads, [&](u64, u64, u64 avail) {
+        if (!whole || avail == comp_bytes) landed(avail);
+    });
+    bm.h2d_ms = (float)(now_ms() - t0);
+    if (moved) return moved;
+    landed(comp_bytes); // (a stream of no bytes has no segment; otherwise nothing is left to do)
+    if (bad || !plan.done()) {
+        (void)hipStreamSynchronize(e->stream);
+        (void)hipGetLastError();
+        return 1;
+    }
+    return 0;
 }
 
 int inflate_not_taken(u32 status)

@@ -720,8 +720,26 @@ struct RangeOut {
     u32 R = 0;
     double t_start = 0, t_text = 0, t_parse = 0;
 };
-int parse_range(yacrd_engine *e, const TextSource &src, u64 file_n, u64 begin, u64 len, bool skip_head, bool m4, int n_threads, RangeOut &ro)
+int parse_range(yacrd_engine *e, TextProducer &tp, u64 file_n, u64 begin, u64 len, bool skip_head, bool m4, int n_threads, RangeOut &ro)
 {
+    const TextSource &src = tp.src;
+    if (tp.bgzf && (begin || len != file_n)) return fail(YACRD_EINTERNAL, "device parser: a BGZF text is parsed whole");
+    // (no text on the host to take the line density from: the first members, at most 1 MiB of text, are decoded here — 13 ms
+    // on one thread, beside the allocations below)
+    struct HeadSample {
+        std::thread th;
+        u64 text = 0, lines = 0;
+        bool ok = false;
+        ~HeadSample()
+        {
+            if (th.joinable()) th.join();
+        }
+    } head_sample;
+    if (tp.bgzf)
+        head_sample.th = std::thread([&head_sample, bz = tp.bgzf] {
+            head_sample.ok = bgzf_head_lines(reinterpret_cast<const unsigned char *>(bz->comp), bz->comp_bytes, bz->members.data(), bz->members.size(),
+                                             (u64)1 << 20, &head_sample.text, &head_sample.lines);
+        });
     DeviceGuard guard(e->device);
     Scratch *Sp = scratch_of<Scratch>(e);
     if (!Sp) return fail(YACRD_ENOMEM, "host allocation failed");
@@ -740,9 +758,10 @@ int parse_range(yacrd_engine *e, const TextSource &src, u64 file_n, u64 begin, u
         // the host parser, whose streamed records need ~0.5 x: answered here, before anything is allocated.
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            // (a BGZF stream: its compressed bytes and the member table lie in HBM beside the text)
             const double have = (double)free_b + (double)S.text.cap + (double)S.recs.cap + (double)e->stage.cap +
-                                (double)e->in_iv.cap + (double)S.gather.cap;
-            if (2.6 * (double)n + (double)((size_t)256 << 20) > have)
+                                (double)e->in_iv.cap + (double)S.gather.cap + (tp.bgzf ? (double)inflate_device_held(e) : 0.0);
+            if (2.6 * (double)n + (tp.bgzf ? tp.bgzf->device_bytes() : 0.0) + (double)((size_t)256 << 20) > have)
                 return fail(YACRD_EFALLBACK, "the file is too large to be parsed in this device's free memory: the host parser streams it");
         }
     }
@@ -766,7 +785,11 @@ int parse_range(yacrd_engine *e, const TextSource &src, u64 file_n, u64 begin, u
     // does not wait for that — so from the line density of the file's first MiB plus a quarter (never more than
     // one record per 17 bytes); a parse that outgrows it is repeated with the exact number below.
     u64 rec_cap = n / 17 + 2;
-    {
+    if (tp.bgzf) { // (a member that is not taken, or no line in the sample: the bound)
+        head_sample.th.join();
+        if (head_sample.ok && head_sample.lines)
+            rec_cap = std::min<u64>(rec_cap, (u64)((double)n / (double)head_sample.text * (double)head_sample.lines * 1.25) + 4096);
+    } else {
         const size_t sample = (size_t)std::min<u64>(n, (u64)1 << 20);
         std::vector<char> head(sample + 1);
         if (!src.fetch(head.data(), sample, begin)) return fail(YACRD_EINVAL, "read error in the overlap file");
@@ -807,9 +830,12 @@ int parse_range(yacrd_engine *e, const TextSource &src, u64 file_n, u64 begin, u
     {
         // (128 MiB per scan + parse launch.  The two kernels take 0.9 ms for 367 MB, so what the overlap buys is small;
         // segments of 16 / 32 MiB got in the way of the copy threads: tools/paf_matrix.py, profiles/r03/paf_matrix.log)
-        const int bad = move_text(e, src, begin, n, S.text.as<char>(), blit, n_threads, [&](u64 seg_begin, u64 seg_end, u64 avail) {
+        // (a BGZF stream: the segments are the inflated text's, each behind the launches that decoded it)
+        int rc_open = YACRD_OK;
+        const int bad = tp.move(e, begin, n, S.text.as<char>(), blit, n_threads, [&](u64 seg_begin, u64 seg_end, u64 avail) {
             if (seg_begin < parse_end) launch_segment(seg_begin, std::min<u64>(parse_end, seg_end), avail);
-        });
+        }, &rc_open);
+        if (rc_open) return rc_open;
         if (bad == 2) return fail(YACRD_EINVAL, "read error in the overlap file");
         if (bad == 3) return fail(YACRD_ENOMEM, "PAF text to HBM: no pinned memory");
         if (bad) return fail(YACRD_ENODEV, "PAF text to HBM: a HIP call failed");
@@ -817,8 +843,12 @@ int parse_range(yacrd_engine *e, const TextSource &src, u64 file_n, u64 begin, u
     ro.t_text = now_ms();
 
     // ---- what the scan and the parse found
+    // (the inflate's status word first: a text decoded from a member that was not taken may say anything)
     Ctl::Words found;
+    u32 inflate_status = 0;
+    if (const int rci = tp.fetch_inflate_status(e, &inflate_status)) return rci;
     if (const int rcc = S.ctl.read(e, found)) return rcc;
+    if (inflate_status) return inflate_not_taken(inflate_status);
     if ((u32)found.status & yk::kNeedHost)
         return fail(YACRD_EFALLBACK, "the text holds a '\"', a lone CR or a line that is not a plain PAF / M4 record (too few "
                                      "columns, a 0x integer, a length beyond u32, an error rate written as inf or .5 ...): the "
@@ -857,12 +887,12 @@ int parse_range(yacrd_engine *e, const TextSource &src, u64 file_n, u64 begin, u
     return S.pack_names(e, ga.text, L, R, &ro.name_bytes);
 }
 
-int ingest_text(yacrd_engine *e, const TextSource &src, u64 n, bool m4, int n_threads, uint32_t coverage, double not_coverage,
+int ingest_text(yacrd_engine *e, TextProducer tp, u64 n, bool m4, int n_threads, uint32_t coverage, double not_coverage,
                 yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats)
 {
     DeviceGuard guard(e->device);
     RangeOut ro;
-    if (const int rcp = parse_range(e, src, n, 0, n, false, m4, n_threads, ro)) return rcp;
+    if (const int rcp = parse_range(e, tp, n, 0, n, false, m4, n_threads, ro)) return rcp;
     Scratch &S = *scratch_of<Scratch>(e); // (parse_range made it)
     // the reads, to the host (while the CSR is built)
     if (const int rch = reads_to_host(e, reads, ro.R, ro.n_recs, e->in_len.p, S.range.name_off.p, S.range.names.p, ro.name_bytes)) return rch;
@@ -1121,7 +1151,8 @@ struct GroupRun {
         // the threads that move text are shared out (engines on one device share its link as well)
         const int copy_threads = std::max(1, (n_threads > 0 ? n_threads : 8) / (int)A);
         const int rc = run_all(A, [&](uint32_t d) -> int {
-            const int r = parse_range(E[d], src, n, B[d], B[d + 1] - B[d], head_skip[d] != 0, m4, copy_threads, ro[d]);
+            TextProducer plain(src);
+            const int r = parse_range(E[d], plain, n, B[d], B[d + 1] - B[d], head_skip[d] != 0, m4, copy_threads, ro[d]);
             if (r) return r;
             DeviceGuard guard(E[d]->device);
             HIP_TRY(hipStreamSynchronize(E[d]->stream)); // (the names kernel: other engines read what this one made)
@@ -1432,6 +1463,30 @@ int yacrd_engine_ingest_overlaps_mem(yacrd_engine *e, const char *text, uint64_t
     TextSource src;
     src.mem = text ? text : "";
     return ingest_text(e, src, n, m4, n_threads, coverage, not_coverage, out, reads, stats);
+}
+
+int yacrd_engine_ingest_overlaps_bgzf_mem(yacrd_engine *e, const char *bgzf, uint64_t n_bytes, int format, int n_threads, uint32_t coverage,
+                                          double not_coverage, yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats, yacrd_gunzip_stats *us)
+{
+    if (!e || (!bgzf && n_bytes) || !out || !reads) return fail(YACRD_EINVAL, "null argument");
+    e->resident.valid = e->input.valid = false;
+    bool m4 = false;
+    if (const int rcf = overlap_format(nullptr, format, m4)) return rcf;
+    zero_outputs(out, reads, stats);
+    if (us) std::memset(us, 0, sizeof(*us));
+    if (e->pending.active || e->host_pending) return fail(YACRD_EINVAL, "the engine has a submitted batch pending");
+    BgzfIn in;
+    if (const int rcw = in.walk(bgzf, n_bytes)) return rcw;
+    TextProducer tp;
+    tp.bgzf = &in;
+    const int rc = ingest_text(e, tp, in.text_bytes, m4, n_threads, coverage, not_coverage, out, reads, stats);
+    {
+        DeviceGuard guard(e->device);
+        (void)hipStreamSynchronize(e->stream); // (whatever failed: nothing of this call is in flight when its events go)
+        (void)hipGetLastError();
+        if (rc == YACRD_OK) in.stats(us);
+    }
+    return rc;
 }
 
 static int group_args(yacrd_engine *const *engines, uint32_t n_engines, yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats)

@@ -331,7 +331,8 @@ struct ReportScratch { // the reader's buffers; they stay with the engine (grow-
     }
 };
 
-int read_report(yacrd_engine *e, const TextSource &src, u64 n, int n_threads, double not_coverage, yacrd_result *out, yacrd_reads *reads,
+// (the text: plain, or a BGZF stream inflated in HBM as it lands — gpu_text.h: TextProducer)
+int read_report(yacrd_engine *e, TextProducer tp, u64 n, int n_threads, double not_coverage, yacrd_result *out, yacrd_reads *reads,
                 yacrd_ingest_stats *stats)
 {
     DeviceGuard guard(e->device);
@@ -347,8 +348,8 @@ int read_report(yacrd_engine *e, const TextSource &src, u64 n, int n_threads, do
         // text at the worst), the arrays of the result.  Answered before anything is allocated.
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const double have = (double)free_b + S.held();
-            if (5.0 * (double)n + (double)((size_t)256 << 20) > have)
+            const double have = (double)free_b + S.held() + (tp.bgzf ? (double)inflate_device_held(e) : 0.0);
+            if (5.0 * (double)n + (tp.bgzf ? tp.bgzf->device_bytes() : 0.0) + (double)((size_t)256 << 20) > have)
                 return fail(YACRD_EFALLBACK, "the report is too large to be read in this device's free memory: the host reader streams it");
         }
     }
@@ -368,23 +369,28 @@ int read_report(yacrd_engine *e, const TextSource &src, u64 n, int n_threads, do
     ga.status = S.ctl.as<u32>();
 
     // ---- the text: every segment's lines are counted as it lands
-    if (n) {
-        const int bad = move_text(e, src, 0, n, S.text.as<char>(), blit, n_threads, [&](u64 seg_begin, u64 seg_end, u64) {
+    if (n || tp.bgzf) { // (a BGZF stream of no text still has members to be taken)
+        int rc_open = YACRD_OK;
+        const int bad = tp.move(e, 0, n, S.text.as<char>(), blit, n_threads, [&](u64 seg_begin, u64 seg_end, u64) {
             const u32 t0 = (u32)(seg_begin / yk::kGpTile), t1 = seg_end >= n ? (u32)n_tiles : (u32)(seg_end / yk::kGpTile);
             ga.tile0 = t0, ga.tile1 = t1;
             // (a line start's blankness looks one byte ahead: the chunk behind the segment has landed, gpu_text.h)
             if (t1 > t0) hipLaunchKernelGGL(yk::rp_count_kernel, dim3(t1 - t0), dim3(yk::kGpT), 0, e->stream, ga);
-        });
+        }, &rc_open);
+        if (rc_open) return rc_open;
         if (bad == 2) return fail(YACRD_EINVAL, "read error in the report");
         if (bad == 3) return fail(YACRD_ENOMEM, "report text to HBM: no pinned memory");
         if (bad) return fail(YACRD_ENODEV, "report text to HBM: a HIP call failed");
     }
     if (const int rcs = scan_u32_to_u64(e, S.tile_lines.as<u32>(), n_tiles, S.tile_ord.as<u64>(), S.part)) return rcs;
     u64 n_lines = 0;
+    u32 inflate_status = 0; // (with the line count, before anything is sized from what the text says)
+    if (const int rci = tp.fetch_inflate_status(e, &inflate_status)) return rci;
     HIP_TRY(hipMemcpyAsync(&n_lines, S.tile_ord.as<u64>() + n_tiles, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipGetLastError());
     const double t_text = now_ms();
+    if (inflate_status) return inflate_not_taken(inflate_status);
     if (n_lines >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "too many lines for the device report reader");
 
     // ---- parse + intern
@@ -525,6 +531,26 @@ int yacrd_engine_ingest_report_mem(yacrd_engine *e, const char *text, uint64_t n
     TextSource src;
     src.mem = text ? text : "";
     return read_report(e, src, n_bytes, n_threads, not_coverage, out, reads, stats);
+}
+
+int yacrd_engine_ingest_report_bgzf_mem(yacrd_engine *e, const char *bgzf, uint64_t n_bytes, int n_threads, double not_coverage, yacrd_result *out,
+                                        yacrd_reads *reads, yacrd_ingest_stats *stats, yacrd_gunzip_stats *us)
+{
+    if (const int rca = report_args(e, out, reads, stats)) return rca;
+    if (us) std::memset(us, 0, sizeof(*us));
+    if (!bgzf && n_bytes) return fail(YACRD_EINVAL, "null argument");
+    BgzfIn in;
+    if (const int rcw = in.walk(bgzf, n_bytes)) return rcw;
+    TextProducer tp;
+    tp.bgzf = &in;
+    const int rc = read_report(e, tp, in.text_bytes, n_threads, not_coverage, out, reads, stats);
+    {
+        DeviceGuard guard(e->device);
+        (void)hipStreamSynchronize(e->stream); // (whatever failed: nothing of this call is in flight when its events go)
+        (void)hipGetLastError();
+        if (rc == YACRD_OK) in.stats(us);
+    }
+    return rc;
 }
 
 } // extern "C"

@@ -6,6 +6,7 @@
 // staged-window accessor, the byte matcher and the id hash; what an ingest's outputs share.
 #pragma once
 #include "engine_internal.h"
+#include "bgzf_walk.h"
 
 #include <fcntl.h>
 #include <sys/stat.h>
@@ -252,5 +253,56 @@ int move_text(yacrd_engine *e, const TextSource &src, u64 begin, u64 n, char *mi
     (void)hipGetLastError();
     return bad.load();
 }
+
+// What a reader of text (the device parser, the report reader) takes its text from: plain text through move_text, or — with
+// `bgzf` — a BGZF stream in host memory, inflated in HBM as it lands (move_bgzf_text, gpu_inflate.hip).  The walk is the entry
+// point's; `move` holds what the inflate leaves behind for the reader: the status word's place and the timed events.
+struct BgzfIn {
+    const char *comp = nullptr;
+    u64 comp_bytes = 0, text_bytes = 0;
+    std::vector<yif::InfMember> members;
+    float walk_ms = 0.f;
+    BgzfMove move;
+    // not BGZF: YACRD_EFALLBACK
+    int walk(const char *bgzf, u64 n_bytes)
+    {
+        const double t0 = now_ms();
+        comp = bgzf ? bgzf : "", comp_bytes = n_bytes;
+        if (!ybw::walk(reinterpret_cast<const unsigned char *>(comp), n_bytes, members, &text_bytes)) return fail(YACRD_EFALLBACK, "not BGZF: the host reader's");
+        walk_ms = (float)(now_ms() - t0);
+        return YACRD_OK;
+    }
+    // device bytes the inflate wants beside the text
+    double device_bytes() const { return (double)comp_bytes + (double)(members.size() + 1) * sizeof(yif::InfMember) + 128.0; }
+    // (behind a synchronisation of the engine's stream)
+    void stats(yacrd_gunzip_stats *us) const
+    {
+        if (!us) return;
+        us->in_bytes = comp_bytes, us->out_bytes = text_bytes, us->n_members = members.size();
+        us->walk_ms = walk_ms, us->h2d_ms = move.h2d_ms, us->kernel_ms = move.kernel_ms(), us->d2h_ms = 0.f;
+    }
+};
+struct TextProducer {
+    TextSource src;
+    BgzfIn *bgzf = nullptr;
+    TextProducer() = default;
+    TextProducer(const TextSource &s) : src(s) {}
+    // text[0, n) -> mirror: move_text's contract and codes either way (plain text: bytes [begin, begin + n) of the source)
+    template <class OnSegment>
+    int move(yacrd_engine *e, u64 begin, u64 n, char *mirror, bool blit, int n_threads, OnSegment &&on_segment, int *rc_open)
+    {
+        *rc_open = YACRD_OK;
+        if (!bgzf) return move_text(e, src, begin, n, mirror, blit, n_threads, on_segment);
+        return move_bgzf_text(e, bgzf->comp, bgzf->comp_bytes, bgzf->members, reinterpret_cast<unsigned char *>(mirror), n, n_threads, on_segment,
+                              bgzf->move, rc_open);
+    }
+    // the decoder's status word on its way to *h_status, enqueued on the engine's stream: read it behind the next synchronisation
+    int fetch_inflate_status(yacrd_engine *e, u32 *h_status) const
+    {
+        *h_status = 0;
+        if (bgzf && bgzf->move.d.status) HIP_TRY(hipMemcpyAsync(h_status, bgzf->move.d.status, sizeof(u32), hipMemcpyDeviceToHost, e->stream));
+        return YACRD_OK;
+    }
+};
 
 } // namespace yke

@@ -73,6 +73,38 @@ bool parse_u64(const char *s, unsigned long long &v)
 
 bool has(const std::string &s, const char *needle) { return s.find(needle) != std::string::npos; }
 
+// a regular file that begins with the gzip magic, mapped as it is for the engine's _bgzf_mem forms (which tell BGZF from plain gzip)
+struct GzipMap {
+    void *m = MAP_FAILED;
+    size_t n = 0;
+    bool open(const char *path)
+    {
+        const int fd = ::open(path, O_RDONLY);
+        struct stat st;
+        if (fd >= 0 && ::fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size >= 2) {
+            unsigned char mg[2] = {0, 0};
+            if (::pread(fd, mg, 2, 0) == 2 && mg[0] == 0x1f && mg[1] == 0x8b) {
+                n = (size_t)st.st_size;
+                m = ::mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0);
+            }
+        }
+        if (fd >= 0) ::close(fd);
+        return m != MAP_FAILED;
+    }
+    const char *data() const { return static_cast<const char *>(m); }
+    ~GzipMap()
+    {
+        if (m != MAP_FAILED) ::munmap(m, n);
+    }
+};
+
+void print_device_inflate(const yacrd_gunzip_stats &us)
+{
+    std::fprintf(stderr, "[info] device inflate: %llu members, %llu -> %llu bytes, walk %.1f ms, h2d %.1f ms, kernels %.1f ms\n",
+                 (unsigned long long)us.n_members, (unsigned long long)us.in_bytes, (unsigned long long)us.out_bytes, us.walk_ms, us.h2d_ms,
+                 us.kernel_ms);
+}
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -171,6 +203,23 @@ int main(int argc, char **argv)
 
     // src/main.rs:43-60: a .yacrd input bypasses detection (FromReport), anything else is overlaps
     const bool m4 = has(input, ".m4") || has(input, ".mhap"), paf = has(input, ".paf");
+    // A gzip input of the detection with ONE engine is mapped as it is and offered to the engine's _bgzf_mem form first: a BGZF
+    // file crosses the link compressed and is inflated in HBM while it lands, the host inflates nothing.  Whatever
+    // that form hands back (YACRD_EFALLBACK: plain gzip, a member the device decoder does not take, the parser's / the reader's
+    // own causes; no memory) leaves nothing behind and takes the route below, unchanged.  bzip2, xz and --gpus N > 1 never try
+    // it; YACRD_NO_DEVICE_INFLATE=1 skips it, as for the sequence editors.  When a sub-command will edit this very file, the host
+    // inflate stays: the overlap editors want the detection's host text, and inflating twice costs more than the link saves.
+    // The default, by DESIGN 7i's rows (the slowest `ingest` of three with it against the fastest of three without): a `.yacrd`
+    // report takes it (113-133 ms against 155-157 ms on the 5 M-read report); an overlap file takes it with
+    // YACRD_DEVICE_INFLATE=1 only (110-158 ms against 145-198 ms on the 367 MB PAF: the slowest is not under the fastest).
+    const char *no_inf_in = std::getenv("YACRD_NO_DEVICE_INFLATE"), *yes_inf_in = std::getenv("YACRD_DEVICE_INFLATE");
+    const bool report_in = !m4 && !paf && has(input, ".yacrd");
+    bool bgzf_route = engines.size() == 1 && !(no_inf_in && *no_inf_in == '1') && (report_in || (yes_inf_in && *yes_inf_in == '1'));
+    if (bgzf_route && !sub.empty()) {
+        struct stat sa, sb;
+        if (::stat(input.c_str(), &sa) == 0 && ::stat(sub_in.c_str(), &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino) bgzf_route = false;
+    }
+
     if (!m4 && !paf && has(input, ".yacrd")) {
         // The report's text goes to HBM and the device parses it, keeps every id's last row at its first position, fills the
         // region CSR and classifies it with this invocation's -n (yacrd_engine_ingest_report; a compressed report is inflated
@@ -183,11 +232,25 @@ int main(int argc, char **argv)
             const char *ct = std::getenv("YACRD_COPY_THREADS");
             const int copy_threads = ct && *ct ? std::max(0, std::atoi(ct)) : 0;
             yacrd_ingest_stats is{};
-            const int rct = yacrd_text_from_file(input.c_str(), threads == 1 ? 0 : (int)threads, &text);
-            stage("inflate");
-            // (rct 1, a file that cannot be read or inflated: the host reader below words that error too)
-            dev_rep = rct == 1 ? YACRD_EFALLBACK : rct == 0 ? yacrd_engine_ingest_report_mem(engines[0], text.data, text.n, copy_threads, not_coverage, &res, &dev_reads, &is)
-                               : yacrd_engine_ingest_report(engines[0], input.c_str(), copy_threads, not_coverage, &res, &dev_reads, &is);
+            yacrd_gunzip_stats us{};
+            GzipMap gm;
+            if (bgzf_route && gm.open(input.c_str())) {
+                dev_rep = yacrd_engine_ingest_report_bgzf_mem(engines[0], gm.data(), gm.n, copy_threads, not_coverage, &res, &dev_reads, &is, &us);
+                if (dev_rep == YACRD_ENOMEM) {
+                    for (yacrd_engine *en : engines) (void)yacrd_engine_trim(en);
+                    dev_rep = YACRD_EFALLBACK;
+                }
+                if (dev_rep != YACRD_OK && dev_rep != YACRD_EFALLBACK) die(yacrd_last_error());
+            }
+            const bool dev_inflate = dev_rep == YACRD_OK;
+            int rct = 0;
+            if (!dev_inflate) {
+                rct = yacrd_text_from_file(input.c_str(), threads == 1 ? 0 : (int)threads, &text);
+                stage("inflate");
+                // (rct 1, a file that cannot be read or inflated: the host reader below words that error too)
+                dev_rep = rct == 1 ? YACRD_EFALLBACK : rct == 0 ? yacrd_engine_ingest_report_mem(engines[0], text.data, text.n, copy_threads, not_coverage, &res, &dev_reads, &is)
+                                   : yacrd_engine_ingest_report(engines[0], input.c_str(), copy_threads, not_coverage, &res, &dev_reads, &is);
+            }
             if (dev_rep == YACRD_ENOMEM) {
                 std::fprintf(stderr, "[INFO] device report reader: %s; falling back to the host reader\n", yacrd_last_error());
                 for (yacrd_engine *en : engines) (void)yacrd_engine_trim(en);
@@ -198,7 +261,8 @@ int main(int argc, char **argv)
                 std::fprintf(stderr, "[info] device report reader: %llu reads from %llu lines, %llu bytes%s, text %.1f ms, parse %.1f ms, build %.1f ms, "
                                      "d2h %.1f ms\n",
                              (unsigned long long)is.n_reads, (unsigned long long)is.n_records, (unsigned long long)is.text_bytes,
-                             rct == 0 ? " (inflated)" : "", is.text_ms, is.parse_ms, is.build_ms, is.d2h_ms);
+                             dev_inflate ? " (inflated in HBM)" : rct == 0 ? " (inflated)" : "", is.text_ms, is.parse_ms, is.build_ms, is.d2h_ms);
+            if (dev_inflate && timing) print_device_inflate(us);
         }
         if (dev_rep == YACRD_OK) {
             table_resident = true;
@@ -243,15 +307,29 @@ int main(int argc, char **argv)
             const int copy_threads = ct && *ct ? std::max(0, std::atoi(ct)) : 0;
             // a gzip / bzip2 / xz file (src/util.rs:57-70 sniffs every input): inflated into memory first — BGZF members on
             // every usable CPU, any other stream on one thread, which then is the wall clock whichever parser follows
-            const int rct = yacrd_text_from_file(input.c_str(), threads == 1 ? 0 : (int)threads, &text);
-            if (rct == 1) die(yacrd_host_last_error());
-            stage("inflate");
-            if (rct == 0)
-                dev_parse = yacrd_engines_ingest_overlaps_mem(engines.data(), (uint32_t)engines.size(), text.data, text.n, m4 ? 2 : 1,
-                                                              copy_threads, cov32, not_coverage, &res, &dev_reads, nullptr);
-            else
-                dev_parse = yacrd_engines_ingest_overlaps(engines.data(), (uint32_t)engines.size(), input.c_str(), m4 ? 2 : 1, copy_threads,
-                                                          cov32, not_coverage, &res, &dev_reads, nullptr);
+            yacrd_gunzip_stats us{};
+            GzipMap gm;
+            if (bgzf_route && gm.open(input.c_str())) {
+                dev_parse = yacrd_engine_ingest_overlaps_bgzf_mem(engines[0], gm.data(), gm.n, m4 ? 2 : 1, copy_threads, cov32, not_coverage, &res,
+                                                                  &dev_reads, nullptr, &us);
+                if (dev_parse == YACRD_ENOMEM) {
+                    for (yacrd_engine *en : engines) (void)yacrd_engine_trim(en);
+                    dev_parse = YACRD_EFALLBACK;
+                }
+                if (dev_parse != YACRD_OK && dev_parse != YACRD_EFALLBACK) die(yacrd_last_error());
+                if (dev_parse == YACRD_OK && timing) print_device_inflate(us);
+            }
+            if (dev_parse != YACRD_OK) {
+                const int rct = yacrd_text_from_file(input.c_str(), threads == 1 ? 0 : (int)threads, &text);
+                if (rct == 1) die(yacrd_host_last_error());
+                stage("inflate");
+                if (rct == 0)
+                    dev_parse = yacrd_engines_ingest_overlaps_mem(engines.data(), (uint32_t)engines.size(), text.data, text.n, m4 ? 2 : 1,
+                                                                  copy_threads, cov32, not_coverage, &res, &dev_reads, nullptr);
+                else
+                    dev_parse = yacrd_engines_ingest_overlaps(engines.data(), (uint32_t)engines.size(), input.c_str(), m4 ? 2 : 1, copy_threads,
+                                                              cov32, not_coverage, &res, &dev_reads, nullptr);
+            }
             if (dev_parse == YACRD_ENOMEM) { // HBM ran out on the way (the parse wants ~2.6 x the file): the streamed host parse needs a fifth
                 std::fprintf(stderr, "[INFO] device parser: %s; falling back to the host parser\n", yacrd_last_error());
                 for (yacrd_engine *en : engines) (void)yacrd_engine_trim(en);
@@ -478,9 +556,7 @@ int main(int argc, char **argv)
                              sub_fmt, (unsigned long long)ss.n_records, (unsigned long long)ss.n_out_records, (unsigned long long)ss.text_bytes,
                              (unsigned long long)ss.out_bytes, ss.text_ms, ss.table_ms, ss.kernel_ms, ss.out_ms);
                 if (dev_inflate)
-                    std::fprintf(stderr, "[info] device inflate: %llu members, %llu -> %llu bytes, walk %.1f ms, h2d %.1f ms, kernels %.1f ms\n",
-                                 (unsigned long long)us.n_members, (unsigned long long)us.in_bytes, (unsigned long long)us.out_bytes, us.walk_ms,
-                                 us.h2d_ms, us.kernel_ms);
+                    print_device_inflate(us);
                 if (sub_comp == 1) // (the encoder's line as the host loop's writer words it: the output lay in HBM, nothing went up)
                     std::fprintf(stderr, "[info] device deflate: %llu -> %llu bytes, %llu members (%llu stored), h2d %.1f ms, kernels %.1f ms, "
                                          "d2h %.1f ms, write %.1f ms, inflate %.1f ms, text_reused=%d\n",

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../../include/yacrd_host.h"
+#include "../bgzf_plan.h"
 #include "../bgzf_walk.h"
 #include "../inflate_block.h"
 #include "host_common.h"
@@ -40,6 +41,38 @@ int yacrd_bgzf_decode_host(const char *data, uint64_t n, char **out, uint64_t *o
         }
     }
     *out = res, *out_bytes = total;
+    return 0;
+}
+
+int yacrd_bgzf_plan_segments(const char *data, uint64_t n, const uint64_t *landed, uint64_t n_landed, uint64_t chunk, uint64_t seg_chunks,
+                             uint64_t **members_out, uint64_t *n_members, uint64_t **steps_out, uint64_t *n_steps)
+{
+    if ((!data && n) || (!landed && n_landed) || !members_out || !n_members || !steps_out || !n_steps) return yh::fail("bad argument");
+    *members_out = *steps_out = nullptr, *n_members = *n_steps = 0;
+    for (uint64_t k = 1; k < n_landed; k++)
+        if (landed[k] < landed[k - 1]) return yh::fail("the landed bytes fall");
+    std::vector<yif::InfMember> members;
+    uint64_t total = 0;
+    if (!ybw::walk(reinterpret_cast<const unsigned char *>(data), n, members, &total)) return yh::fail("not BGZF");
+    std::vector<uint64_t> steps;
+    try {
+        ybw::SegmentPlan plan(members.data(), members.size(), total, chunk ? chunk : ybw::kPlanChunk, seg_chunks ? seg_chunks : ybw::kPlanSeg);
+        ybw::PlanStep s;
+        for (uint64_t k = 0; k < n_landed; k++)
+            while (plan.next(landed[k], s)) steps.insert(steps.end(), {k, s.m0, s.m1, s.inflated, s.t0, s.t1, s.avail, s.last ? 1u : 0u});
+    } catch (...) {
+        return yh::fail("host allocation failed");
+    }
+    uint64_t *mo = (uint64_t *)std::malloc((members.size() * 4 + 1) * sizeof(uint64_t));
+    uint64_t *so = (uint64_t *)std::malloc((steps.size() + 1) * sizeof(uint64_t));
+    if (!mo || !so) {
+        std::free(mo), std::free(so);
+        return yh::fail("host allocation failed");
+    }
+    for (size_t k = 0; k < members.size(); k++)
+        mo[4 * k] = members[k].in_off, mo[4 * k + 1] = members[k].csize, mo[4 * k + 2] = members[k].isize, mo[4 * k + 3] = members[k].out_off;
+    if (!steps.empty()) std::memcpy(so, steps.data(), steps.size() * sizeof(uint64_t));
+    *members_out = mo, *n_members = members.size(), *steps_out = so, *n_steps = steps.size() / 8;
     return 0;
 }
 

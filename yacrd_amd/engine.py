@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = [
     "yacrd_stream_finish", "yacrd_stream_last_stats", "yacrd_stream_reset", "yacrd_stream_close",
     "yacrd_engine_ingest_paf", "yacrd_engine_ingest_overlaps", "yacrd_engine_ingest_overlaps_mem", "yacrd_engines_ingest_overlaps",
     "yacrd_engines_ingest_overlaps_mem", "yacrd_reads_free", "yacrd_engine_trim",
+    "yacrd_engine_ingest_overlaps_bgzf_mem", "yacrd_engine_ingest_report_bgzf_mem",
     "yacrd_engine_ingest_report", "yacrd_engine_ingest_report_mem", "yacrd_engine_write_report", "yacrd_engine_write_report_mem",
     "yacrd_engine_edit_overlaps", "yacrd_engine_edit_overlaps_mem", "yacrd_edit_text_free",
     "yacrd_engine_edit_overlaps_gzip_mem", "yacrd_engine_edit_overlaps_gzip_file",
@@ -322,6 +323,12 @@ def load_library():
                                                ctypes.POINTER(_Reads), ctypes.POINTER(_IngestStats)]
     lib.yacrd_engine_ingest_report_mem.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_double,
                                                    ctypes.POINTER(_Result), ctypes.POINTER(_Reads), ctypes.POINTER(_IngestStats)]
+    lib.yacrd_engine_ingest_overlaps_bgzf_mem.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
+                                                          ctypes.c_uint32, ctypes.c_double, ctypes.POINTER(_Result), ctypes.POINTER(_Reads),
+                                                          ctypes.POINTER(_IngestStats), ctypes.POINTER(_GunzipStats)]
+    lib.yacrd_engine_ingest_report_bgzf_mem.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_double,
+                                                        ctypes.POINTER(_Result), ctypes.POINTER(_Reads), ctypes.POINTER(_IngestStats),
+                                                        ctypes.POINTER(_GunzipStats)]
     lib.yacrd_engine_write_report.argtypes = [ctypes.c_void_p, ctypes.POINTER(_ReportTable), ctypes.c_char_p,
                                               ctypes.POINTER(_ReportWriteStats)]
     lib.yacrd_engine_write_report_mem.argtypes = [ctypes.c_void_p, ctypes.POINTER(_ReportTable), ctypes.POINTER(ctypes.c_void_p),
@@ -616,7 +623,39 @@ class Engine:
         del keep
         return self._ingested(rc, res, rd, st)
 
-    def _ingested(self, rc, res, rd, st):
+    def ingest_bgzf(self, blob, coverage, not_coverage, n_threads=0, fmt=1):
+        """yacrd_engine_ingest_overlaps_bgzf_mem: ingest_text over a BGZF stream (bytes, or (address, n_bytes)) as it is — the
+        compressed bytes go up and are inflated in HBM while they land.  (Result, names, lengths, stats) as from ingest_text
+        of the inflated text; stats["inflate"]: the inflate's figures (n_members, in_bytes, out_bytes, walk_ms, h2d_ms,
+        kernel_ms).  Raises NeedsHostParser, with nothing returned, when `blob` is not BGZF, holds a member the device decoder
+        does not take, or inflates to a text ingest_text refuses."""
+        res, rd, st, us = _Result(), _Reads(), _IngestStats(), _GunzipStats()
+        addr, n, keep = self._host_bytes(blob)
+        rc = self._lib.yacrd_engine_ingest_overlaps_bgzf_mem(self._h, addr, n, int(fmt), int(n_threads), min(int(coverage), 0xFFFFFFFF),
+                                                             float(not_coverage), ctypes.byref(res), ctypes.byref(rd), ctypes.byref(st),
+                                                             ctypes.byref(us))
+        del keep
+        return self._ingested(rc, res, rd, st, us)
+
+    def ingest_report_bgzf(self, blob, not_coverage, n_threads=0):
+        """yacrd_engine_ingest_report_bgzf_mem: ingest_report over a BGZF stream (bytes, or (address, n_bytes)) as it is;
+        returns and raises as ingest_bgzf does."""
+        res, rd, st, us = _Result(), _Reads(), _IngestStats(), _GunzipStats()
+        addr, n, keep = self._host_bytes(blob)
+        rc = self._lib.yacrd_engine_ingest_report_bgzf_mem(self._h, addr, n, int(n_threads), float(not_coverage), ctypes.byref(res),
+                                                           ctypes.byref(rd), ctypes.byref(st), ctypes.byref(us))
+        del keep
+        return self._ingested(rc, res, rd, st, us)
+
+    @staticmethod
+    def _host_bytes(blob):
+        """(address, n_bytes, what keeps them alive) of bytes or of an (address, n_bytes) pair"""
+        if isinstance(blob, tuple):
+            return int(blob[0]), int(blob[1]), None
+        keep = ctypes.create_string_buffer(bytes(blob), len(blob))
+        return ctypes.addressof(keep), len(blob), keep
+
+    def _ingested(self, rc, res, rd, st, us=None):
         if rc == E_FALLBACK:
             raise NeedsHostParser(self._lib.yacrd_last_error().decode())
         _check(self._lib, rc)
@@ -626,6 +665,8 @@ class Engine:
         blob = ctypes.string_at(rd.names, int(off[-1])) if R else b""
         names = [blob[int(off[i]):int(off[i + 1])].decode("utf-8", "surrogateescape") for i in range(R)]
         stats = {n: getattr(st, n) for n, _ in _IngestStats._fields_}
+        if us is not None:
+            stats["inflate"] = {f: getattr(us, f) for f, _ in _GunzipStats._fields_}
         self._lib.yacrd_reads_free(ctypes.byref(rd))
         return _take(self._lib, res), names, lengths, stats
 

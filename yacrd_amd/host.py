@@ -32,7 +32,7 @@ EXPORTED_SYMBOLS = [
     "yacrd_csr_find", "yacrd_csr_free", "yacrd_report_write", "yacrd_synth_csr", "yacrd_synth_paf",
     "yacrd_edit_file", "yacrd_edit_file_mt", "yacrd_text_from_file", "yacrd_text_free", "yacrd_report_read", "yacrd_report_get", "yacrd_report_free",
     "yacrd_edit_file_to", "yacrd_file_compression", "yacrd_bgzf_encode_host", "yacrd_bgzf_decode_host", "yacrd_bytes_free", "yacrd_deflate_code_lengths",
-    "yacrd_synth_fastq", "yacrd_ingest_stream", "yacrd_ingest_stream_memory", "yacrd_csr_handle_map",
+    "yacrd_synth_fastq", "yacrd_ingest_stream", "yacrd_ingest_stream_memory", "yacrd_csr_handle_map", "yacrd_bgzf_plan_segments",
 ]
 
 OP_SCRUBB, OP_FILTER, OP_EXTRACT, OP_SPLIT = 0, 1, 2, 3
@@ -161,6 +161,9 @@ def load_library():
         lib.yacrd_file_compression.argtypes = [ctypes.c_char_p]
         lib.yacrd_bgzf_encode_host.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)]
         lib.yacrd_bgzf_decode_host.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)]
+        lib.yacrd_bgzf_plan_segments.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                                 ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64),
+                                                 ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)]
         lib.yacrd_bytes_free.argtypes = [ctypes.c_void_p]
         lib.yacrd_bytes_free.restype = None
         lib.yacrd_deflate_code_lengths.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
@@ -378,6 +381,26 @@ def bgzf_decode_host(data):
         return ctypes.string_at(out.value, int(n.value))
     finally:
         lib.yacrd_bytes_free(out)
+
+
+def bgzf_plan_segments(data, landed, chunk=0, seg_chunks=0):
+    """yacrd_bgzf_plan_segments: the segment-wise inflate's planner over a BGZF stream and a schedule of landed compressed
+    bytes -> (members u64[M,4]: in_off, csize, isize, out_off; steps u64[S,8]: call, m0, m1, inflated, t0, t1, avail, last).
+    chunk / seg_chunks 0: the mover's 4 MiB and 32."""
+    lib = load_library()
+    data = bytes(data)
+    sched = np.ascontiguousarray(landed, dtype=np.uint64)
+    mo, so = ctypes.c_void_p(), ctypes.c_void_p()
+    nm, ns = ctypes.c_uint64(), ctypes.c_uint64()
+    _check(lib, lib.yacrd_bgzf_plan_segments(data, len(data), sched.ctypes.data, len(sched), int(chunk), int(seg_chunks), ctypes.byref(mo),
+                                             ctypes.byref(nm), ctypes.byref(so), ctypes.byref(ns)))
+    try:
+        members = np.frombuffer(ctypes.string_at(mo.value, int(nm.value) * 32), dtype=np.uint64).reshape(-1, 4).copy()
+        steps = np.frombuffer(ctypes.string_at(so.value, int(ns.value) * 64), dtype=np.uint64).reshape(-1, 8).copy()
+    finally:
+        lib.yacrd_bytes_free(mo)
+        lib.yacrd_bytes_free(so)
+    return members, steps
 
 
 def deflate_code_lengths(freq, limit):
