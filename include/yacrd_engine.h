@@ -507,6 +507,46 @@ int yacrd_engine_edit_overlaps_gzip_mem(yacrd_engine *e, int op, const char *tex
 int yacrd_engine_edit_overlaps_gzip_file(yacrd_engine *e, int op, const char *text, uint64_t n_bytes, int format,
                                          const yacrd_type_table *types, const char *out_path,
                                          yacrd_edit_stats *es /* may be NULL */, yacrd_gzip_stats *gs /* may be NULL */);
+/* filter / extract on a BGZF overlap file as it is: `bgzf`, n_bytes is the COMPRESSED file in host memory (read or mapped);
+ * the host inflates nothing.  The compressed bytes go up once, the members of every landed segment are inflated into the
+ * editor's text buffer (yacrd_engine_ingest_overlaps_bgzf_mem's mover), and every whole segment of TEXT is marked, scanned
+ * and packed behind the launches that decoded it.  format 1 = PAF / 2 = M4, MHAP.  gzip_out 0: the kept bytes, those of
+ * yacrd_engine_edit_overlaps_mem on the inflated text; gzip_out 1: ONE BGZF stream, byte for byte what
+ * yacrd_engine_edit_overlaps_gzip_mem returns for that text.  The host decodes, for the two things the plan must know before
+ * the first launch (the first non-empty line's field count; whether the text ends in a newline), the stream's first members
+ * — at most 1 MiB of text, no further than that line's end — and its last one.
+ * es->text_bytes is the inflated size; us: walk_ms, h2d_ms of the compressed bytes, kernel_ms of the decoder by device events,
+ * d2h_ms 0; gs is zero with gzip_out 0.
+ * YACRD_EFALLBACK — nothing written, nothing left at or beside out_path, es / gs / us zeroed, the engine usable — for a
+ * stream that is not BGZF, a member the decoder does not take (its status word is read before anything the editor's kernels
+ * made of the text, and wins: kept bytes of earlier segments may have reached the sink by then, so the memory form frees its
+ * buffer and the file form removes the file beside out_path), a first line longer than the host's sample, the plain forms'
+ * own causes in the text, and a text beyond the device's free memory.  The file form's rules for out_path are those of
+ * yacrd_engine_edit_overlaps_gzip_file.  Additive: found by the symbol. */
+int yacrd_engine_edit_overlaps_bgzf_mem(yacrd_engine *e, int op, const char *bgzf, uint64_t n_bytes, int format,
+                                        const yacrd_type_table *types, int gzip_out /* 0 | 1 */, char **out, uint64_t *out_bytes,
+                                        yacrd_edit_stats *es /* may be NULL */, yacrd_gzip_stats *gs /* may be NULL */,
+                                        yacrd_gunzip_stats *us /* may be NULL */);
+int yacrd_engine_edit_overlaps_bgzf_file(yacrd_engine *e, int op, const char *bgzf, uint64_t n_bytes, int format,
+                                         const yacrd_type_table *types, int gzip_out /* 0 | 1 */, const char *out_path,
+                                         yacrd_edit_stats *es /* may be NULL */, yacrd_gzip_stats *gs /* may be NULL */,
+                                         yacrd_gunzip_stats *us /* may be NULL */);
+/* filter / extract on the overlap text that the engine's last successful overlap ingest left in HBM: nothing goes up
+ * (es->mirror_reused 1, text_ms 0); the bytes are those of the forms above.  The text is recorded, with its size, its format
+ * and the two things the plan asks of it, by every one-engine overlap ingest that leaves the whole text in HBM:
+ * yacrd_engine_ingest_overlaps, _overlaps_mem and _overlaps_bgzf_mem (a group of several engines leaves none).  Whatever
+ * rewrites or frees that text — the next ingest of any kind, whether it succeeds or not, yacrd_engine_trim — ends it; the
+ * report writer and the editors leave it alone.  A text that came from memory or from a BGZF stream carries no file identity:
+ * yacrd_engine_edit_overlaps never takes it for its file.  With no such text: YACRD_EINVAL, "no overlap text is resident" —
+ * no fallback, the caller's logic is wrong.  YACRD_EFALLBACK, nothing written: the plain forms' own causes in the text, no
+ * device memory, and a resident text whose ingest could not take the plan's two facts (a BGZF text whose first line is longer
+ * than the 1 MiB the host samples; a read error in the file): the host loop's.  Additive: found by the symbol. */
+int yacrd_engine_edit_overlaps_resident_mem(yacrd_engine *e, int op, const yacrd_type_table *types, int gzip_out /* 0 | 1 */,
+                                            char **out, uint64_t *out_bytes, yacrd_edit_stats *es /* may be NULL */,
+                                            yacrd_gzip_stats *gs /* may be NULL */);
+int yacrd_engine_edit_overlaps_resident_file(yacrd_engine *e, int op, const yacrd_type_table *types, int gzip_out /* 0 | 1 */,
+                                             const char *out_path, yacrd_edit_stats *es /* may be NULL */,
+                                             yacrd_gzip_stats *gs /* may be NULL */);
 
 #ifndef YACRD_BYTE_SINK_DEFINED
 #define YACRD_BYTE_SINK_DEFINED

@@ -165,6 +165,13 @@ int yacrd_bgzf_decode_host(const char *data, uint64_t n, char **out, uint64_t *o
  * yacrd_bytes_free.  Non-zero: not BGZF, or a falling schedule. */
 int yacrd_bgzf_plan_segments(const char *data, uint64_t n, const uint64_t *landed, uint64_t n_landed, uint64_t chunk, uint64_t seg_chunks,
                              uint64_t **members_out, uint64_t *n_members, uint64_t **steps_out, uint64_t *n_steps);
+/* What the device overlap editor asks of a BGZF text before its first launch (csrc/host/inflate_sample.cc, the decoder's
+ * host build): *n_fields, the number of fields under `delim` of the text's first non-empty line (0: there is none), and
+ * *ends_nl, 1 when the text's last byte is '\n' (1 for a text of no bytes).  Decoded for it: the first members, at most
+ * 1 MiB of text and no further than that line's end, and the last member that holds text.  Non-zero, with a message: not
+ * BGZF; one of those members is not taken by the decoder (the message names the cause); the first non-empty line is not
+ * complete within the sample although the text goes on. */
+int yacrd_bgzf_text_ends(const char *data, uint64_t n, int delim, uint32_t *n_fields, int *ends_nl);
 /* The encoder's code-length construction: freq[n] -> len[n] with no length above `limit` (n in 2..286, limit in 5..15,
  * 2^limit >= n).  Fewer than two used symbols are given company, as zlib does, so the code is always complete. */
 int yacrd_deflate_code_lengths(const uint32_t *freq, uint32_t n, uint32_t limit, uint8_t *len);

@@ -16,6 +16,14 @@ with the same synthetic PAF as gzip level 1 (one stream) and as BGZF, K timed ru
   (b) new      this tree's yacrd — the detection's text reused, edited and deflated in HBM (its "[info] device editor + deflate:" line, on stdout)
 and the `edit` stage of YACRD_CLI_TIMING as the figure compared: slowest (b) against fastest (a).  Every output is compared
 with the parent's, byte for byte.  One JSON line per form (appended to --json when given).
+--bgzf-in [--parent-bin PATH]: the same command on the synthetic PAF as BGZF, for the detection's own file and for a copy of it
+(another inode), K timed runs after one warm-up of
+  (a) host inflate    PATH, or without it this tree's yacrd with YACRD_NO_DEVICE_INFLATE=1 (the parent's route, unchanged)
+  (b) device inflate  this tree's yacrd with YACRD_DEVICE_INFLATE=1: the file ingested compressed and edited where the ingest left
+                      it (resident=1), or — the copy — inflated in HBM by the editor's own _bgzf_ form
+with the stages inflate + detect + edit of YACRD_CLI_TIMING as the figure compared (slowest (b) against fastest (a)), the
+editor's and the decoder's own stats per run, every output compared byte for byte (-c 4 -n 0.4 here).  One JSON line per case, and one
+more for the same calls warm in ONE process: Engine.ingest_bgzf + edit_overlaps_resident, and edit_overlaps_bgzf, K runs after a warm-up.
 --parent-again: a second series of the parent behind the new one ("parent_again" in the row): what drifted meanwhile shows."""
 import argparse, json, os, re, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,6 +38,7 @@ ap.add_argument("--runs", type=int, default=3)
 ap.add_argument("--op", default="filter")
 ap.add_argument("--json", default=None)
 ap.add_argument("--gzip", action="store_true")
+ap.add_argument("--bgzf-in", action="store_true")
 ap.add_argument("--parent-bin", default=None)
 ap.add_argument("--parent-again", action="store_true")
 ap.add_argument("--forms", default="gzip1,bgzf")
@@ -92,7 +101,7 @@ def gzip_bench():
                     stages = dict(re.findall(r"^\[timing\] (\S+) ([0-9.]+) s$", p.stderr, re.M))
                     info = [l for l in (p.stdout + p.stderr).splitlines() if l.startswith("[info] device editor + deflate:") or l.startswith("[info] device deflate:")]
                     assert len(info) == 1, p.stderr
-                    row = {"edit_s": float(stages["edit"]), "inflate_s": float(stages["inflate"]), "detect_s": float(stages["detect"]), "wall_s": round(wall, 3)}
+                    row = {"edit_s": float(stages["edit"]), "inflate_s": float(stages.get("inflate", 0.0)), "detect_s": float(stages["detect"]), "wall_s": round(wall, 3)}
                     for name, key in (("inflate", "edit_inflate_ms"), ("text", "text_ms"), ("table", "table_ms"), ("editor kernels", "editor_kernel_ms"),
                                       ("encoder kernels", "encoder_kernel_ms"), ("kernels", "encoder_kernel_ms"), ("out", "out_ms"), ("h2d", "h2d_ms"),
                                       ("d2h", "d2h_ms"), ("write", "write_ms")):
@@ -128,6 +137,118 @@ def gzip_bench():
             fresh(x)
 
 
+def bgzf_in_bench():
+    """--bgzf-in: the command on a BGZF overlap file with the device inflate (YACRD_DEVICE_INFLATE=1: ingested compressed and
+    edited where the ingest left it; for another BGZF file, the editor's own _bgzf_ form) against the host inflate"""
+    new_bin = os.path.join(ROOT, "yacrd_amd", "bin", "yacrd")
+    old_bin = a.parent_bin or new_bin  # (without the parent's binary: this tree's with the device inflate switched off, the parent's route)
+    if a.parent_bin and not os.access(a.parent_bin, os.X_OK):
+        sys.exit("--parent-bin: not an executable")
+    src, cp, rep, old, new = tag + "in.paf.gz", tag + "copy.paf.gz", tag + "r.yacrd", tag + "old.paf.gz", tag + "new.paf.gz"
+    made = [paf, src, cp, rep, old, new]
+    try:
+        host.synth_paf(host.SYNTH_SEQUEL, a.reads, a.overlaps, 20241108 + 5, paf)
+        size = os.path.getsize(paf)
+        with yacrd_amd.Engine(device_id=0) as e, e.gzip_writer(src) as w, open(paf, "rb") as f:
+            while True:
+                piece = f.read(1 << 26)
+                if not piece:
+                    break
+                w.write(piece)
+        with open(src, "rb") as f, open(cp, "wb") as g:
+            g.write(f.read())
+        fresh(paf)
+
+        def run(binary, sub_in, out, **env):
+            rows = []
+            base = {k: v for k, v in os.environ.items() if k not in ("YACRD_DEVICE_INFLATE", "YACRD_NO_DEVICE_INFLATE")}
+            for k in range(a.runs + 1):
+                fresh(out)
+                fresh(rep)
+                t0 = time.perf_counter()
+                p = subprocess.run([binary, "-i", src, "-o", rep, "-t", "0", "-c", "4", "-n", "0.4", a.op, "-i", sub_in, "-o", out],
+                                   capture_output=True, text=True, env=dict(base, YACRD_CLI_TIMING="1", **env))
+                wall = time.perf_counter() - t0
+                assert p.returncode == 0, p.stderr
+                stages = {k2: float(v) for k2, v in re.findall(r"^\[timing\] (\S+) ([0-9.]+) s$", p.stderr, re.M)}
+                info = [l for l in p.stdout.splitlines() if l.startswith("[info] device editor + deflate:")]
+                assert len(info) == 1, p.stdout + p.stderr
+                row = {"ingest_to_edit_s": round(stages.get("inflate", 0.0) + stages["detect"] + stages["edit"], 4), "wall_s": round(wall, 3),
+                       "inflate_s": stages.get("inflate", 0.0), "detect_s": stages["detect"], "edit_s": stages["edit"]}
+                for name, key in (("inflate", "edit_inflate_ms"), ("text", "text_ms"), ("table", "table_ms"), ("editor kernels", "editor_kernel_ms"),
+                                  ("encoder kernels", "encoder_kernel_ms"), ("out", "out_ms")):
+                    m = re.search(r", %s ([0-9.]+) ms" % name, info[0])
+                    if m:
+                        row[key] = float(m.group(1))
+                for flag in ("text_reused", "resident", "device_inflate"):
+                    m = re.search(r"%s=(\d)" % flag, info[0])
+                    if m:
+                        row[flag] = int(m.group(1))
+                for l in p.stderr.splitlines():
+                    m = re.match(r"\[info\] device inflate: .* walk ([0-9.]+) ms, h2d ([0-9.]+) ms, kernels ([0-9.]+) ms", l)
+                    if m:
+                        row["inflate_walk_ms"], row["inflate_h2d_ms"], row["inflate_kernel_ms"] = (float(x) for x in m.groups())
+                if k:
+                    rows.append(row)
+            return rows
+
+        for case, sub_in in (("same file", src), ("another file", cp)):
+            parent = run(old_bin, sub_in, old, **({} if a.parent_bin else {"YACRD_NO_DEVICE_INFLATE": "1"}))
+            mine = run(new_bin, sub_in, new, YACRD_DEVICE_INFLATE="1")
+            assert all(r.get("device_inflate") == 1 for r in mine), mine
+            assert same(old, new), "the new route's file differs from the other's"
+            worst_new, best_old = max(r["ingest_to_edit_s"] for r in mine), min(r["ingest_to_edit_s"] for r in parent)
+            row = {"reads": a.reads, "overlaps": a.overlaps, "op": a.op, "case": case, "text_bytes": size, "bgzf_in_bytes": os.path.getsize(src),
+                   "gz_out_bytes": os.path.getsize(new), "other": "parent binary" if a.parent_bin else "this binary, YACRD_NO_DEVICE_INFLATE=1",
+                   "host_inflate": parent, "device_inflate": mine, "slowest_device_inflate_s": worst_new, "fastest_host_inflate_s": best_old,
+                   "device_inflate_is_default_by_the_rule": worst_new < best_old}
+            line = json.dumps(row)
+            print(line, flush=True)
+            if a.json:
+                with open(a.json, "a") as f:
+                    f.write(line + "\n")
+
+        # warm, in one process: the calls the two routes are made of, K timed after one warm-up each, by their own stats
+        import numpy as np
+        blob = np.fromfile(src, dtype=np.uint8)
+        warm = {"case": "warm in-process", "op": a.op, "text_bytes": size, "bgzf_in_bytes": int(blob.size), "ingest_bgzf": [], "edit_resident": [],
+                "edit_bgzf": []}
+        rnd = lambda d: {k2: (round(v, 2) if isinstance(v, float) else v) for k2, v in d.items()}  # noqa: E731
+        with yacrd_amd.Engine(device_id=0) as e:
+            for k in range(a.runs + 1):
+                t0 = time.perf_counter()
+                res, names, lengths, st = e.ingest_bgzf((blob.ctypes.data, int(blob.size)), 4, 0.4)
+                t1 = time.perf_counter()
+                fresh(new)
+                es, gs = e.edit_overlaps_resident(op, names, res.read_type, out_path=new)
+                t2 = time.perf_counter()
+                assert es["mirror_reused"] == 1 and same(old, new)
+                if k:
+                    inf = st.pop("inflate")
+                    warm["ingest_bgzf"].append({"s": round(t1 - t0, 4), **rnd(st), "inflate": rnd(inf)})
+                    warm["edit_resident"].append({"s": round(t2 - t1, 4), "edit": rnd(es), "gzip": rnd(gs)})
+            for k in range(a.runs + 1):
+                fresh(new)
+                t0 = time.perf_counter()
+                es, gs = e.edit_overlaps_bgzf(op, blob, names, res.read_type, 1, out_path=new)
+                dt = time.perf_counter() - t0
+                assert same(old, new)
+                if k:
+                    warm["edit_bgzf"].append({"s": round(dt, 4), "edit": rnd(es), "gzip": rnd(gs), "inflate": rnd(e.inflate_stats)})
+            e.trim()
+        line = json.dumps(warm)
+        print(line, flush=True)
+        if a.json:
+            with open(a.json, "a") as f:
+                f.write(line + "\n")
+    finally:
+        for x in made:
+            fresh(x)
+
+
+if a.bgzf_in:
+    bgzf_in_bench()
+    sys.exit(0)
 if a.gzip:
     gzip_bench()
     sys.exit(0)

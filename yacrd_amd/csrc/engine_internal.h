@@ -334,13 +334,20 @@ struct yacrd_engine {
     // a batch submitted from host buffers (yacrd_engine_submit): collect() fetches the result
     bool host_pending = false;
     yke::PinBuf paf_arena; // what text passes through on its way to HBM (gpu_text.h: move_text)
-    // the mirror a device parse of a whole FILE left in HBM (gpu_paf.hip: still inside its scratch), and which file it was:
-    // the overlap editor (gpu_edit.hip) edits from it when it is handed the same file, instead of moving the text again
+    // the mirror a one-engine device parse of a whole overlap text left in HBM (gpu_paf.hip: still inside its scratch).  With
+    // from_file, which file it was: the overlap editor (gpu_edit.hip) edits from it when it is handed the same file, instead of
+    // moving the text again; a text that came from memory or from a BGZF stream has no file identity and never passes for one.
+    // With facts, what the editor's plan asks of the text (gpu_text.h: first_line_fields), taken when the ingest had the text,
+    // the file or the stream at hand: the _resident_ forms edit from the mirror with nothing but these.  Cleared (valid) by
+    // the first statement of everything that rewrites or frees the parser's text, and of every ingest: the resident text is
+    // the last successful overlap ingest's.
     struct {
         const unsigned char *p = nullptr; // n bytes + 64 of padding
         uint64_t n = 0, dev = 0, ino = 0;
         int64_t mtime_s = 0, mtime_ns = 0;
-        bool valid = false;
+        bool valid = false, from_file = false;
+        bool facts = false, m4 = false, ends_nl = true;
+        uint32_t n_fields = 0;
     } mirror;
     // the read table the engine's last ingest left in HBM (gpu_paf.hip with one engine, gpu_report.hip): names, name_off and
     // lengths where that ingest's scratch (and in_len) hold them; with bad_offsets / bad_regions / read_type they are all a
@@ -466,6 +473,11 @@ int inflate_not_taken(u32 status);
 // (the record-room estimate of a text that is not in host memory: host/inflate_sample.cc)
 bool bgzf_head_lines(const unsigned char *comp, uint64_t comp_bytes, const yif::InfMember *members, uint64_t n_members, uint64_t max_text,
                      uint64_t *text, uint64_t *lines);
+// (what the overlap editor's plan asks of a text that is not in host memory — the first non-empty line's field count, the
+// last byte — from the first members and the last one: host/inflate_sample.cc.  0; 1 a member not taken, *status the cause;
+// 2 the first non-empty line is not complete inside max_text bytes and the text goes on; 3 no memory)
+int bgzf_text_ends(const unsigned char *comp, uint64_t comp_bytes, const yif::InfMember *members, uint64_t n_members, uint64_t max_text,
+                   unsigned char delim, uint32_t *n_fields, bool *ends_nl, uint32_t *status);
 struct BgzfMove {
     InflateDevice d;
     Events ev; // a timed pair around every launch

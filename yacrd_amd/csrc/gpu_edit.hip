@@ -32,6 +32,16 @@
 // crosses the link and reaches the file are members; one batch is fetched and written while the next is encoded and while
 // later segments are moved, marked and packed.  Blocks are counted from the start of the kept stream, so the bytes are
 // those of yacrd_engine_gzip_mem on the kept bytes whatever the segments, the threads or the timing.
+//
+// BGZF in (yacrd_engine_edit_overlaps_bgzf_mem / _file): the text comes from a TextProducer (gpu_text.h), as the
+// parser's does — a BGZF stream in host memory goes up compressed, its members are inflated into the editor's text buffer as
+// they land (gpu_inflate.hip: move_bgzf_text) and every whole segment of text is handed to launch_segment behind the launches
+// that decoded it.  What plan() must know before the first launch comes from the stream's first and last members, decoded on
+// the host (host/inflate_sample.cc).  The decoder's status word is read in verdict() before anything else and wins: the
+// kernels may have run over any bytes by then (their reads are bounded whatever the text holds), and the sink may hold kept
+// bytes of earlier segments — the file beside out_path goes, the buffer is freed.
+// Resident (yacrd_engine_edit_overlaps_resident_mem / _file): the mirror of the engine's last one-engine overlap ingest, with
+// the plan's facts recorded beside it (engine_internal.h: mirror); nothing goes up.
 #include "engine_internal.h"
 #include "gpu_text.h"
 #include "edit_table.h"
@@ -340,43 +350,13 @@ struct EditScratch { // the editor's buffers; they stay with the engine (grow-on
 
 using yseg::Sink; // where the kept bytes go: a file descriptor or memory, sized or growing (host/segment_pump.h)
 
-// the field count of the first non-empty line (0: there is none) and whether the text's last byte is a newline
-bool first_line_fields(const TextSource &src, u64 n, char delim, u32 &n_fields, bool &ends_in_newline)
-{
-    n_fields = 0, ends_in_newline = true;
-    if (!n) return true;
-    char last = 0;
-    if (!src.fetch(&last, 1, n - 1)) return false;
-    ends_in_newline = last == '\n';
-    std::vector<char> buf((size_t)std::min<u64>(n, (u64)1 << 20));
-    bool in_line = false;
-    u32 nf = 0;
-    for (u64 off = 0; off < n; off += buf.size()) {
-        const size_t len = (size_t)std::min<u64>(buf.size(), n - off);
-        if (!src.fetch(buf.data(), len, off)) return false;
-        for (size_t i = 0; i < len; i++) {
-            const char c = buf[i];
-            if (c == '\n') {
-                if (in_line) {
-                    n_fields = nf;
-                    return true;
-                }
-                continue;
-            }
-            if (!in_line) in_line = true, nf = 1;
-            if (c == delim) nf++;
-        }
-    }
-    if (in_line) n_fields = nf;
-    return true;
-}
-
 struct EditJob {
     int op = 0;
     bool m4 = false;
     int n_threads = 0;
     const yacrd_type_table *types = nullptr;
     bool use_mirror = false; // edit from the parser's mirror (the same file: checked by the caller)
+    bool resident = false;   // ... with nothing but the mirror: what the plan asks of the text was recorded with it
     bool gzip = false;       // the sink takes BGZF members of the kept bytes instead of the kept bytes
     yacrd_gzip_stats *gzip_stats = nullptr;
 };
@@ -385,8 +365,8 @@ struct EditJob {
 struct EditRun {
     yacrd_engine *e;
     const EditJob &job;
-    const TextSource &src;
-    const u64 n; // bytes of text
+    TextProducer &tp; // plain text, or a BGZF stream inflated in HBM as it lands (gpu_text.h)
+    const u64 n;      // bytes of text
     Sink &sink;
     yacrd_edit_stats *stats;
     EditScratch &S;
@@ -404,6 +384,8 @@ struct EditRun {
     u64 *seg_base = nullptr;
     volatile u64 *h_seg = nullptr; // pinned, per segment: lines, kept, status, kept bytes so far
     volatile u64 *h_gz = nullptr;  // pinned, per batch: its members' bytes, stored members so far
+    volatile u32 *h_inflate = nullptr; // pinned: the decoder's status word (a BGZF text), fetched behind the last segment
+    int rc_open = YACRD_OK;            // the code of an inflate that could not be set up
     GzDevice gz;
     GzHold gz_hold;
     // run(): the segments' kernels on the engine's stream, the writer thread behind their events
@@ -435,7 +417,12 @@ struct EditRun {
         const char delim = job.m4 ? ' ' : '\t';
         const u32 ib = job.m4 ? 1u : 5u;
         bool ends_nl = true;
-        if (!first_line_fields(src, n, delim, n_fields, ends_nl)) return fail(YACRD_EINVAL, "read error in the overlap file");
+        // what the host needs of the text before the first launch: recorded with the mirror, sampled from the stream's first
+        // and last members (no text on the host), or read from the text
+        if (job.resident) n_fields = e->mirror.n_fields, ends_nl = e->mirror.ends_nl;
+        else if (tp.bgzf) {
+            if (const int rcs = tp.bgzf->text_ends(delim, n_fields, ends_nl)) return rcs;
+        } else if (!first_line_fields(tp.src, n, delim, n_fields, ends_nl)) return fail(YACRD_EINVAL, "read error in the overlap file");
         if (n_fields && n_fields <= ib) return fail(YACRD_EFALLBACK, "the first line has too few fields: the host loop words the error");
         nl = n + (ends_nl ? 0 : 1);
         n_tiles = (nl + yk::kGpTile - 1) / yk::kGpTile;
@@ -449,8 +436,10 @@ struct EditRun {
         // HBM: the text (unless the parser's mirror serves), as many bytes again for what is kept, a bit per byte, the table
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const double have = (double)free_b + (double)S.text.cap + (double)S.out.cap + (double)S.kbits.cap + (double)S.table.names.cap + (double)S.table.slots.cap;
-            const double need = (job.use_mirror ? 0.0 : (double)n) + (double)nl * 1.125 + (double)nl / 8.0 * 1.125 + (double)name_bytes * 1.125 +
+            // (a BGZF stream: its compressed bytes and the member table lie in HBM beside the text; the inflate scratch counts as held)
+            const double have = (double)free_b + (double)S.text.cap + (double)S.out.cap + (double)S.kbits.cap + (double)S.table.names.cap +
+                                (double)S.table.slots.cap + (tp.bgzf ? (double)inflate_device_held(e) : 0.0);
+            const double need = (job.use_mirror ? 0.0 : (double)n) + (tp.bgzf ? tp.bgzf->device_bytes() : 0.0) + (double)nl * 1.125 + (double)nl / 8.0 * 1.125 + (double)name_bytes * 1.125 +
                                 (double)cap * 4.0 + (double)R * 10.0 + (double)n_tiles * 40.0 + (double)((size_t)64 << 20) +
                                 (double)gz_blocks * (double)ydf::kSlot * 3.0 * 1.125; // (the members' slots and two batches of members)
             if (need > have) return fail(YACRD_EFALLBACK, "the file is too large to be edited in this device's free memory: the host loop streams it");
@@ -474,9 +463,11 @@ struct EditRun {
         const size_t ctl_words = 8 + n_segs + 2;
         HIP_TRY(S.ctl.reserve(ctl_words * sizeof(u64)));
         HIP_TRY(hipMemsetAsync(S.ctl.p, 0, ctl_words * sizeof(u64), e->stream));
-        HIP_TRY(S.pin.reserve(2 * kOutPiece + (n_segs + 2) * 4 * sizeof(u64) + (job.gzip ? n_batches * 2 * sizeof(u64) : 0)));
+        HIP_TRY(S.pin.reserve(2 * kOutPiece + (n_segs + 2) * 4 * sizeof(u64) + (job.gzip ? n_batches * 2 * sizeof(u64) : 0) + sizeof(u64)));
         h_seg = reinterpret_cast<volatile u64 *>(S.pin.as<char>() + 2 * kOutPiece);
         h_gz = h_seg + (n_segs + 2) * 4;
+        h_inflate = reinterpret_cast<volatile u32 *>(h_gz + (job.gzip ? n_batches * 2 : 0));
+        *h_inflate = 0;
         if (job.gzip) {
             if (const int rcg = gzip_device_open(e, gz_blocks, &gz)) return rcg;
             gz_hold.e = e;
@@ -637,8 +628,11 @@ struct EditRun {
         if (job.use_mirror) {
             for (size_t s = 0; s < n_segs && !bad.load(); s++) launch_segment((u64)s * kSegBytes, (u64)(s + 1) * kSegBytes, n);
         } else {
-            moved = move_text(e, src, 0, n, S.text.as<char>(), blit, job.n_threads,
-                              [&](u64 seg_begin, u64 seg_end, u64 avail) { launch_segment(seg_begin, seg_end, avail); });
+            // (a BGZF stream: the segments are the inflated text's, each behind the launches that decoded it; the decoder's
+            // status word follows the last of them home, for verdict() to read before anything else)
+            moved = tp.move(e, 0, n, S.text.as<char>(), blit, job.n_threads,
+                            [&](u64 seg_begin, u64 seg_end, u64 avail) { launch_segment(seg_begin, seg_end, avail); }, &rc_open);
+            if (!moved && tp.fetch_inflate_status(e, const_cast<u32 *>(h_inflate)) != YACRD_OK) moved = 1;
         }
         no_more = true;
         const double t_text_done = now_ms();
@@ -661,6 +655,10 @@ struct EditRun {
     {
         (void)hipGetLastError();
         if (!ran) return fail(YACRD_ENODEV, "overlap editor: a HIP stream or event could not be created");
+        // the inflate's status word first: a text decoded from a member that was not taken may hold anything, and whatever the
+        // kernels and the writer made of it (a refusal, a count, bytes already in the sink) says nothing
+        if (h_inflate && *h_inflate) return inflate_not_taken(*h_inflate);
+        if (rc_open) return rc_open;
         if (moved == 2) return fail(YACRD_EINVAL, "read error in the overlap file");
         if (moved == 3) return fail(YACRD_ENOMEM, "overlap text to HBM: no pinned memory");
         if (moved || bad.load() == 1) return fail(YACRD_ENODEV, "overlap editor: a HIP call failed");
@@ -691,16 +689,111 @@ struct EditRun {
     }
 };
 
-int run_edit(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n, Sink &sink, yacrd_edit_stats *stats)
+int run_edit(yacrd_engine *e, const EditJob &job, TextProducer &tp, u64 n, Sink &sink, yacrd_edit_stats *stats)
 {
     DeviceGuard guard(e->device);
     EditScratch *S = scratch_of<EditScratch>(e);
     if (!S) return fail(YACRD_ENOMEM, "host allocation failed");
-    EditRun r{e, job, src, n, sink, stats, *S};
+    EditRun r{e, job, tp, n, sink, stats, *S};
     if (const int rc = r.plan()) return rc;
     if (const int rc = r.reserve()) return rc;
     if (const int rc = r.upload_table()) return rc;
     return r.verdict(r.run());
+}
+int run_edit(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n, Sink &sink, yacrd_edit_stats *stats)
+{
+    TextProducer tp(src);
+    return run_edit(e, job, tp, n, sink, stats);
+}
+
+int edit_args(yacrd_engine *e, int op, const yacrd_type_table *types, yacrd_edit_stats *stats);
+
+// ---- what the _bgzf_ and _resident_ forms share: where the output goes ------------------------------------------------------
+// memory: the kept bytes are at most the text and its added newline; members start at a quarter of the text and grow
+int edit_to_mem(yacrd_engine *e, const EditJob &job, TextProducer &tp, u64 n, char **out, uint64_t *out_bytes, yacrd_edit_stats *es)
+{
+    Sink sink;
+    if (job.gzip) sink.cap = (size_t)(n / 4 + 4096);
+    sink.mem = (char *)std::malloc(job.gzip ? (size_t)sink.cap : (size_t)n + 2);
+    if (!sink.mem) return fail(YACRD_ENOMEM, "host allocation failed");
+    const int rc = run_edit(e, job, tp, n, sink, es);
+    if (rc != YACRD_OK) { // (kept bytes or members of earlier segments may lie in the buffer: it goes)
+        std::free(sink.mem);
+        return rc;
+    }
+    *out = sink.mem, *out_bytes = sink.at;
+    return YACRD_OK;
+}
+// a file: yacrd_engine_edit_overlaps_gzip_file's rules — written beside its place and moved there when every byte is in it
+int edit_to_file(yacrd_engine *e, const EditJob &job, TextProducer &tp, u64 n, const char *out_path, yacrd_edit_stats *es)
+{
+    struct stat ost;
+    if (lstat(out_path, &ost) == 0 && !S_ISREG(ost.st_mode)) return fail(YACRD_EFALLBACK, "the output is not a regular file: the host loop writes it");
+    yseg::BesideFile file;
+    if (!file.open(out_path)) return fail(YACRD_EFALLBACK, std::string("cannot create a file beside ") + out_path + ": the host loop words the error");
+    Sink sink;
+    sink.fd = file.fd;
+    int rc = run_edit(e, job, tp, n, sink, es);
+    if (rc == YACRD_OK && !file.commit()) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
+    return rc;
+}
+
+// One call of the _bgzf_ forms (out_path, or out and out_bytes): the walk on the host, everything else on the device
+int edit_bgzf(yacrd_engine *e, int op, const char *bgzf, uint64_t n_bytes, int format, const yacrd_type_table *types, int gzip_out, const char *out_path,
+              char **out, uint64_t *out_bytes, yacrd_edit_stats *es, yacrd_gzip_stats *gs, yacrd_gunzip_stats *us)
+{
+    if (gs) std::memset(gs, 0, sizeof(*gs));
+    if (us) std::memset(us, 0, sizeof(*us));
+    if (out) *out = nullptr;
+    if (out_bytes) *out_bytes = 0;
+    if (const int rca = edit_args(e, op, types, es)) return rca;
+    if ((!bgzf && n_bytes) || (!out_path && (!out || !out_bytes))) return fail(YACRD_EINVAL, "null argument");
+    if (gzip_out != 0 && gzip_out != 1) return fail(YACRD_EINVAL, "gzip_out: 0 = the kept bytes, 1 = a BGZF stream of them");
+    EditJob job;
+    job.op = op, job.types = types, job.gzip = gzip_out == 1, job.gzip_stats = gzip_out == 1 ? gs : nullptr;
+    if (const int rcf = overlap_format(nullptr, format, job.m4)) return rcf;
+    BgzfIn in;
+    if (const int rcw = in.walk(bgzf, n_bytes)) return rcw;
+    TextProducer tp;
+    tp.bgzf = &in;
+    int rc = out_path ? edit_to_file(e, job, tp, in.text_bytes, out_path, es) : edit_to_mem(e, job, tp, in.text_bytes, out, out_bytes, es);
+    {
+        DeviceGuard guard(e->device);
+        (void)hipStreamSynchronize(e->stream); // (whatever failed: nothing of this call is in flight when its events go)
+        (void)hipGetLastError();
+        if (rc == YACRD_OK) in.stats(us);
+    }
+    if (rc != YACRD_OK) {
+        if (es) std::memset(es, 0, sizeof(*es));
+        if (gs) std::memset(gs, 0, sizeof(*gs));
+    }
+    return rc;
+}
+
+// One call of the _resident_ forms: the text the engine's last successful overlap ingest left in HBM, nothing goes up
+int edit_resident(yacrd_engine *e, int op, const yacrd_type_table *types, int gzip_out, const char *out_path, char **out, uint64_t *out_bytes,
+                  yacrd_edit_stats *es, yacrd_gzip_stats *gs)
+{
+    if (gs) std::memset(gs, 0, sizeof(*gs));
+    if (out) *out = nullptr;
+    if (out_bytes) *out_bytes = 0;
+    if (const int rca = edit_args(e, op, types, es)) return rca;
+    if (!out_path && (!out || !out_bytes)) return fail(YACRD_EINVAL, "null argument");
+    if (gzip_out != 0 && gzip_out != 1) return fail(YACRD_EINVAL, "gzip_out: 0 = the kept bytes, 1 = a BGZF stream of them");
+    if (!e->mirror.valid || !e->mirror.p)
+        return fail(YACRD_EINVAL, "no overlap text is resident: the engine's last ingest was no one-engine overlap ingest that succeeded");
+    if (!e->mirror.facts) // (the ingest could not say what the plan asks: a first line beyond the BGZF sample, a read error)
+        return fail(YACRD_EFALLBACK, "the resident text's first line could not be sampled at ingest time: the host loop words the error");
+    EditJob job;
+    job.op = op, job.types = types, job.gzip = gzip_out == 1, job.gzip_stats = gzip_out == 1 ? gs : nullptr;
+    job.m4 = e->mirror.m4, job.use_mirror = job.resident = true;
+    TextProducer tp; // (never asked: the mirror is walked)
+    int rc = out_path ? edit_to_file(e, job, tp, e->mirror.n, out_path, es) : edit_to_mem(e, job, tp, e->mirror.n, out, out_bytes, es);
+    if (rc != YACRD_OK) {
+        if (es) std::memset(es, 0, sizeof(*es));
+        if (gs) std::memset(gs, 0, sizeof(*gs));
+    }
+    return rc;
 }
 
 int edit_args(yacrd_engine *e, int op, const yacrd_type_table *types, yacrd_edit_stats *stats)
@@ -738,7 +831,8 @@ int yacrd_engine_edit_overlaps(yacrd_engine *e, int op, const char *in_path, con
     }
     yseg::BesideFile file;
     if (!file.open(out_path)) return fail(YACRD_EFALLBACK, std::string("cannot create a file beside ") + out_path + ": the host loop words the error");
-    job.use_mirror = e->mirror.valid && e->mirror.p && e->mirror.n == (u64)st.st_size && e->mirror.dev == (u64)st.st_dev &&
+    // (a mirror that did not come from a file has no identity: it never matches one)
+    job.use_mirror = e->mirror.valid && e->mirror.from_file && e->mirror.p && e->mirror.n == (u64)st.st_size && e->mirror.dev == (u64)st.st_dev &&
                      e->mirror.ino == (u64)st.st_ino && e->mirror.mtime_s == (int64_t)st.st_mtim.tv_sec &&
                      e->mirror.mtime_ns == (int64_t)st.st_mtim.tv_nsec;
     TextSource src;
@@ -822,6 +916,34 @@ int yacrd_engine_edit_overlaps_gzip_file(yacrd_engine *e, int op, const char *te
     if (rc == YACRD_OK && !file.commit()) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
     if (rc != YACRD_OK && gs) std::memset(gs, 0, sizeof(*gs));
     return rc;
+}
+
+int yacrd_engine_edit_overlaps_bgzf_mem(yacrd_engine *e, int op, const char *bgzf, uint64_t n_bytes, int format, const yacrd_type_table *types,
+                                        int gzip_out, char **out, uint64_t *out_bytes, yacrd_edit_stats *es, yacrd_gzip_stats *gs, yacrd_gunzip_stats *us)
+{
+    if (!out || !out_bytes) return fail(YACRD_EINVAL, "null argument");
+    return edit_bgzf(e, op, bgzf, n_bytes, format, types, gzip_out, nullptr, out, out_bytes, es, gs, us);
+}
+
+int yacrd_engine_edit_overlaps_bgzf_file(yacrd_engine *e, int op, const char *bgzf, uint64_t n_bytes, int format, const yacrd_type_table *types,
+                                         int gzip_out, const char *out_path, yacrd_edit_stats *es, yacrd_gzip_stats *gs, yacrd_gunzip_stats *us)
+{
+    if (!out_path) return fail(YACRD_EINVAL, "null argument");
+    return edit_bgzf(e, op, bgzf, n_bytes, format, types, gzip_out, out_path, nullptr, nullptr, es, gs, us);
+}
+
+int yacrd_engine_edit_overlaps_resident_mem(yacrd_engine *e, int op, const yacrd_type_table *types, int gzip_out, char **out, uint64_t *out_bytes,
+                                            yacrd_edit_stats *es, yacrd_gzip_stats *gs)
+{
+    if (!out || !out_bytes) return fail(YACRD_EINVAL, "null argument");
+    return edit_resident(e, op, types, gzip_out, nullptr, out, out_bytes, es, gs);
+}
+
+int yacrd_engine_edit_overlaps_resident_file(yacrd_engine *e, int op, const yacrd_type_table *types, int gzip_out, const char *out_path,
+                                             yacrd_edit_stats *es, yacrd_gzip_stats *gs)
+{
+    if (!out_path) return fail(YACRD_EINVAL, "null argument");
+    return edit_resident(e, op, types, gzip_out, out_path, nullptr, nullptr, es, gs);
 }
 
 void yacrd_edit_text_free(char *p) { std::free(p); }

@@ -1420,6 +1420,21 @@ struct OverlapFile {
         if (src.fd >= 0) ::close(src.fd);
     }
 };
+
+// A one-engine ingest has left the whole text in the parser's scratch: the overlap editor may start from it (gpu_edit.hip).
+// `st`: the file it was, or nullptr for a text from memory or a BGZF stream — no file identity, never taken for a file.
+// `facts`: n_fields and ends_nl are first_line_fields' answers for the text (the _resident_ forms need them).
+void record_mirror(yacrd_engine *e, u64 n, bool m4, const struct stat *st, bool facts, u32 n_fields, bool ends_nl)
+{
+    auto &m = e->mirror;
+    m.p = scratch_of<Scratch>(e)->text.as<unsigned char>(); // (ingest_text made the scratch)
+    m.n = n, m.m4 = m4;
+    m.from_file = st != nullptr;
+    m.dev = st ? (u64)st->st_dev : 0, m.ino = st ? (u64)st->st_ino : 0;
+    m.mtime_s = st ? (int64_t)st->st_mtim.tv_sec : 0, m.mtime_ns = st ? (int64_t)st->st_mtim.tv_nsec : 0;
+    m.facts = facts, m.n_fields = n_fields, m.ends_nl = ends_nl;
+    m.valid = m.p != nullptr;
+}
 } // namespace
 
 extern "C" {
@@ -1434,6 +1449,7 @@ int yacrd_engine_ingest_overlaps(yacrd_engine *e, const char *path, int format, 
                                  double not_coverage, yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats)
 {
     if (!e || !path || !out || !reads) return fail(YACRD_EINVAL, "null argument");
+    e->mirror.valid = false; // (the resident overlap text is the last SUCCESSFUL ingest's)
     e->resident.valid = e->input.valid = false;
     OverlapFile f;
     if (const int rcf = overlap_format(path, format, f.m4)) return rcf;
@@ -1442,11 +1458,10 @@ int yacrd_engine_ingest_overlaps(yacrd_engine *e, const char *path, int format, 
     if (const int rcf = f.open(path, "yacrd_engine_ingest_overlaps_mem")) return rcf;
     const int rc = ingest_text(e, f.src, (u64)f.st.st_size, f.m4, n_threads, coverage, not_coverage, out, reads, stats);
     if (rc == YACRD_OK) { // the whole file lies in the mirror: the overlap editor may start from it (gpu_edit.hip)
-        e->mirror.p = scratch_of<Scratch>(e)->text.as<unsigned char>(); // (ingest_text made the scratch)
-        e->mirror.n = (u64)f.st.st_size;
-        e->mirror.dev = (u64)f.st.st_dev, e->mirror.ino = (u64)f.st.st_ino;
-        e->mirror.mtime_s = (int64_t)f.st.st_mtim.tv_sec, e->mirror.mtime_ns = (int64_t)f.st.st_mtim.tv_nsec;
-        e->mirror.valid = e->mirror.p != nullptr;
+        u32 n_fields = 0;
+        bool ends_nl = true;
+        const bool facts = first_line_fields(f.src, (u64)f.st.st_size, f.m4 ? ' ' : '\t', n_fields, ends_nl);
+        record_mirror(e, (u64)f.st.st_size, f.m4, &f.st, facts, n_fields, ends_nl);
     }
     return rc;
 }
@@ -1455,6 +1470,7 @@ int yacrd_engine_ingest_overlaps_mem(yacrd_engine *e, const char *text, uint64_t
                                      double not_coverage, yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats)
 {
     if (!e || (!text && n) || !out || !reads) return fail(YACRD_EINVAL, "null argument");
+    e->mirror.valid = false; // (the resident overlap text is the last SUCCESSFUL ingest's)
     e->resident.valid = e->input.valid = false;
     bool m4 = false;
     if (const int rcf = overlap_format(nullptr, format, m4)) return rcf;
@@ -1462,13 +1478,21 @@ int yacrd_engine_ingest_overlaps_mem(yacrd_engine *e, const char *text, uint64_t
     if (e->pending.active || e->host_pending) return fail(YACRD_EINVAL, "the engine has a submitted batch pending");
     TextSource src;
     src.mem = text ? text : "";
-    return ingest_text(e, src, n, m4, n_threads, coverage, not_coverage, out, reads, stats);
+    const int rc = ingest_text(e, src, n, m4, n_threads, coverage, not_coverage, out, reads, stats);
+    if (rc == YACRD_OK) { // (the text is still the caller's to read: what the resident editor asks of it, now)
+        u32 n_fields = 0;
+        bool ends_nl = true;
+        const bool facts = first_line_fields(src, n, m4 ? ' ' : '\t', n_fields, ends_nl);
+        record_mirror(e, n, m4, nullptr, facts, n_fields, ends_nl);
+    }
+    return rc;
 }
 
 int yacrd_engine_ingest_overlaps_bgzf_mem(yacrd_engine *e, const char *bgzf, uint64_t n_bytes, int format, int n_threads, uint32_t coverage,
                                           double not_coverage, yacrd_result *out, yacrd_reads *reads, yacrd_ingest_stats *stats, yacrd_gunzip_stats *us)
 {
     if (!e || (!bgzf && n_bytes) || !out || !reads) return fail(YACRD_EINVAL, "null argument");
+    e->mirror.valid = false; // (the resident overlap text is the last SUCCESSFUL ingest's)
     e->resident.valid = e->input.valid = false;
     bool m4 = false;
     if (const int rcf = overlap_format(nullptr, format, m4)) return rcf;
@@ -1486,6 +1510,14 @@ int yacrd_engine_ingest_overlaps_bgzf_mem(yacrd_engine *e, const char *bgzf, uin
         (void)hipGetLastError();
         if (rc == YACRD_OK) in.stats(us);
     }
+    if (rc == YACRD_OK) { // (no text on the host: the first members and the last one, decoded there)
+        u32 n_fields = 0;
+        bool ends_nl = true;
+        u32 status = 0; // (the helper itself, not BgzfIn::text_ends: a sample that cannot say leaves this call's success, and the last error, as they are)
+        const bool facts = bgzf_text_ends(reinterpret_cast<const unsigned char *>(in.comp), in.comp_bytes, in.members.data(), in.members.size(),
+                                          (u64)1 << 20, (unsigned char)(m4 ? ' ' : '\t'), &n_fields, &ends_nl, &status) == 0;
+        record_mirror(e, in.text_bytes, m4, nullptr, facts, n_fields, ends_nl);
+    }
     return rc;
 }
 
@@ -1494,6 +1526,7 @@ static int group_args(yacrd_engine *const *engines, uint32_t n_engines, yacrd_re
     if (!engines || !n_engines || !out || !reads) return fail(YACRD_EINVAL, "null argument");
     for (uint32_t d = 0; d < n_engines; d++) {
         if (!engines[d]) return fail(YACRD_EINVAL, "engine is null");
+        engines[d]->mirror.valid = false; // (a group leaves no engine with the whole text)
         engines[d]->resident.valid = engines[d]->input.valid = false; // (an engine that parses no range still gets its reads' lengths in in_len)
         if (engines[d]->pending.active || engines[d]->host_pending) return fail(YACRD_EINVAL, "an engine has a submitted batch pending");
         for (uint32_t k = 0; k < d; k++)

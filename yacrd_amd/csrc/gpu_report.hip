@@ -339,6 +339,7 @@ int read_report(yacrd_engine *e, TextProducer tp, u64 n, int n_threads, double n
     ReportScratch *Sp = scratch_of<ReportScratch>(e);
     if (!Sp) return fail(YACRD_ENOMEM, "host allocation failed");
     ReportScratch &S = *Sp;
+    e->mirror.valid = false; // (the engine's last ingest is no overlap ingest any more: no overlap text is resident)
     e->resident.valid = e->input.valid = false;
     const double t_start = now_ms();
     const u64 n_tiles = (n + yk::kGpTile - 1) / yk::kGpTile;

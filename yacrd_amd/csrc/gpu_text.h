@@ -125,6 +125,39 @@ struct TextSource {
     }
 };
 
+// What the overlap editor (gpu_edit.hip) asks of a text before its first launch, and what an ingest records with the mirror it
+// leaves (gpu_paf.hip): the field count of the first non-empty line (0: there is none) and whether the text's last byte is a
+// newline.  (a text that is not in host memory: bgzf_text_ends, host/inflate_sample.cc, gives the same answers)
+inline bool first_line_fields(const TextSource &src, u64 n, char delim, u32 &n_fields, bool &ends_in_newline)
+{
+    n_fields = 0, ends_in_newline = true;
+    if (!n) return true;
+    char last = 0;
+    if (!src.fetch(&last, 1, n - 1)) return false;
+    ends_in_newline = last == '\n';
+    std::vector<char> buf((size_t)std::min<u64>(n, (u64)1 << 20));
+    bool in_line = false;
+    u32 nf = 0;
+    for (u64 off = 0; off < n; off += buf.size()) {
+        const size_t len = (size_t)std::min<u64>(buf.size(), n - off);
+        if (!src.fetch(buf.data(), len, off)) return false;
+        for (size_t i = 0; i < len; i++) {
+            const char c = buf[i];
+            if (c == '\n') {
+                if (in_line) {
+                    n_fields = nf;
+                    return true;
+                }
+                continue;
+            }
+            if (!in_line) in_line = true, nf = 1;
+            if (c == delim) nf++;
+        }
+    }
+    if (in_line) n_fields = nf;
+    return true;
+}
+
 // the way home of a text that lies in HBM: the link yseg::pump (host/segment_pump.h) drives.  src[at, at + len) is copied to a
 // pinned piece on `stream`, with the event of that piece behind it.  `stop`, where given, is a word another thread sets to
 // end the run: wait then gives up without touching `bad`, which holds the HIP error of a call that failed.
@@ -270,6 +303,19 @@ struct BgzfIn {
         comp = bgzf ? bgzf : "", comp_bytes = n_bytes;
         if (!ybw::walk(reinterpret_cast<const unsigned char *>(comp), n_bytes, members, &text_bytes)) return fail(YACRD_EFALLBACK, "not BGZF: the host reader's");
         walk_ms = (float)(now_ms() - t0);
+        return YACRD_OK;
+    }
+    // first_line_fields' answers for the inflated text, from the first members and the last one, decoded on the host (at most
+    // 1 MiB and 64 KiB of text).  YACRD_EFALLBACK: one of them is not taken (the device would say the same), or the first
+    // non-empty line outgrows the sample
+    int text_ends(char delim, u32 &n_fields, bool &ends_in_newline) const
+    {
+        u32 status = 0;
+        const int rc = bgzf_text_ends(reinterpret_cast<const unsigned char *>(comp), comp_bytes, members.data(), members.size(), (u64)1 << 20,
+                                      (unsigned char)delim, &n_fields, &ends_in_newline, &status);
+        if (rc == 1) return inflate_not_taken(status);
+        if (rc == 2) return fail(YACRD_EFALLBACK, "the first line is longer than the sample decoded on the host: the host loop words the error");
+        if (rc) return fail(YACRD_ENOMEM, "host allocation failed");
         return YACRD_OK;
     }
     // device bytes the inflate wants beside the text

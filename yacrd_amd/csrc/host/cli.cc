@@ -208,17 +208,35 @@ int main(int argc, char **argv)
     // that form hands back (YACRD_EFALLBACK: plain gzip, a member the device decoder does not take, the parser's / the reader's
     // own causes; no memory) leaves nothing behind and takes the route below, unchanged.  bzip2, xz and --gpus N > 1 never try
     // it; YACRD_NO_DEVICE_INFLATE=1 skips it, as for the sequence editors.  When a sub-command will edit this very file, the host
-    // inflate stays: the overlap editors want the detection's host text, and inflating twice costs more than the link saves.
+    // inflate stays — the sequence editors want the detection's host text, and inflating twice costs more than the link saves —
+    // unless that sub-command is the device overlap editor with the device deflate (filter / extract on this gzip PAF / M4):
+    // it edits the text the ingest leaves inflated in HBM (yacrd_engine_edit_overlaps_resident_file), so the file
+    // goes up compressed once and only BGZF members come home.
     // The default, by DESIGN 7i's rows (the slowest `ingest` of three with it against the fastest of three without): a `.yacrd`
     // report takes it (113-133 ms against 155-157 ms on the 5 M-read report); an overlap file takes it with
     // YACRD_DEVICE_INFLATE=1 only (110-158 ms against 145-198 ms on the 367 MB PAF: the slowest is not under the fastest).
+    // The combined route of 7j (ingest compressed, edit resident) and the editor's own _bgzf_ form for another BGZF file are the
+    // default by the same rule (DESIGN 7j's table, tools/edit_overlaps_bench.py --bgzf-in --parent-bin on that PAF, the stages
+    // inflate + detect + edit): 0.254-0.262 s against the parent's 0.322-0.354 s on the detection's own file, 0.333-0.336 s
+    // against 0.451-0.467 s on a copy of it.
     const char *no_inf_in = std::getenv("YACRD_NO_DEVICE_INFLATE"), *yes_inf_in = std::getenv("YACRD_DEVICE_INFLATE");
     const bool report_in = !m4 && !paf && has(input, ".yacrd");
-    bool bgzf_route = engines.size() == 1 && !(no_inf_in && *no_inf_in == '1') && (report_in || (yes_inf_in && *yes_inf_in == '1'));
-    if (bgzf_route && !sub.empty()) {
+    // the device overlap editor with the device deflate will run on sub_in (if it is gzip; the editor's section looks)
+    const bool sub_dev_ovl_gz = [&] {
+        const char *no_ed = std::getenv("YACRD_NO_DEVICE_EDITOR"), *no_df = std::getenv("YACRD_NO_DEVICE_DEFLATE");
+        return (sub == "filter" || sub == "extract") && (has(sub_in, ".m4") || has(sub_in, ".mhap") || has(sub_in, ".paf")) &&
+               !(no_ed && *no_ed == '1') && !(no_df && *no_df == '1');
+    }();
+    const bool inflate_on = engines.size() == 1 && !(no_inf_in && *no_inf_in == '1');
+    const bool ovl_inflate_on = inflate_on && yes_inf_in && *yes_inf_in == '1';
+    bool sub_same_file = false;
+    if (!sub.empty()) {
         struct stat sa, sb;
-        if (::stat(input.c_str(), &sa) == 0 && ::stat(sub_in.c_str(), &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino) bgzf_route = false;
+        sub_same_file = ::stat(input.c_str(), &sa) == 0 && ::stat(sub_in.c_str(), &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino;
     }
+    bool bgzf_route = inflate_on && (report_in || ovl_inflate_on || (sub_dev_ovl_gz && sub_same_file));
+    if (bgzf_route && sub_same_file && !sub_dev_ovl_gz) bgzf_route = false;
+    bool ovl_resident = false; // the detection's overlap text lies inflated in engines[0]'s HBM (and nowhere on the host)
 
     if (!m4 && !paf && has(input, ".yacrd")) {
         // The report's text goes to HBM and the device parses it, keeps every id's last row at its first position, fills the
@@ -318,6 +336,7 @@ int main(int argc, char **argv)
                 }
                 if (dev_parse != YACRD_OK && dev_parse != YACRD_EFALLBACK) die(yacrd_last_error());
                 if (dev_parse == YACRD_OK && timing) print_device_inflate(us);
+                ovl_resident = dev_parse == YACRD_OK;
             }
             if (dev_parse != YACRD_OK) {
                 const int rct = yacrd_text_from_file(input.c_str(), threads == 1 ? 0 : (int)threads, &text);
@@ -427,43 +446,72 @@ int main(int argc, char **argv)
         // very file and still holds it, else inflated here, BGZF member-parallel — and the kept bytes are deflated where the
         // device packs them: only BGZF members come back (yacrd_engine_edit_overlaps_gzip_file).  What it does not take, no
         // memory for it, YACRD_NO_DEVICE_EDITOR=1 or YACRD_NO_DEVICE_DEFLATE=1: the host loop into the gzip writer below.
+        // With the device inflate on (one engine; see the route decision above for the default), a BGZF file is not inflated on
+        // the host at all.  The detection's own file: its text lies inflated in HBM behind yacrd_engine_ingest_overlaps_bgzf_mem,
+        // and yacrd_engine_edit_overlaps_resident_file edits it there.  Another BGZF file: mapped and offered to
+        // yacrd_engine_edit_overlaps_bgzf_file, which inflates it in HBM as it lands.  YACRD_EFALLBACK or no memory from either
+        // (plain gzip above all) leaves nothing behind and takes the route below, unchanged: inflate on the host, then
+        // yacrd_engine_edit_overlaps_gzip_file, then the host loop.
         if (dev_ed && !(no_df && *no_df == '1') && yacrd_file_compression(sub_in.c_str()) == 1) {
-            const auto t_in = std::chrono::steady_clock::now();
-            yacrd_text own{};
-            const yacrd_text *tx = nullptr;
-            struct stat sa, sb;
-            if (text.data && ::stat(input.c_str(), &sa) == 0 && ::stat(sub_in.c_str(), &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino)
-                tx = &text;
-            else {
-                const int rct = yacrd_text_from_file(sub_in.c_str(), threads == 1 ? 0 : (int)threads, &own);
-                if (rct == 1) die(yacrd_host_last_error());
-                if (rct == 0) tx = &own;
-            }
-            const double inflate_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count();
-            if (tx) {
-                const yacrd_type_table tt = {bp.n_reads, bp.name_off, bp.names, bp.read_type};
-                yacrd_edit_stats es{};
-                yacrd_gzip_stats gs{};
-                dev_edit = yacrd_engine_edit_overlaps_gzip_file(engines[0], op, tx->data, tx->n, has(sub_in, ".m4") || has(sub_in, ".mhap") ? 2 : 1,
-                                                                &tt, sub_out.c_str(), &es, &gs);
-                if (dev_edit == YACRD_ENOMEM) {
-                    std::fprintf(stderr, "[INFO] device editor + deflate: %s; falling back to the host loop\n", yacrd_last_error());
+            const yacrd_type_table tt = {bp.n_reads, bp.name_off, bp.names, bp.read_type};
+            const int sub_fmt_ovl = has(sub_in, ".m4") || has(sub_in, ".mhap") ? 2 : 1;
+            yacrd_edit_stats es{};
+            yacrd_gzip_stats gs{};
+            // what a device call handed back: no memory is a fallback too, behind a trim; any other error ends the run
+            auto settled = [&](int rc, const char *to) {
+                if (rc == YACRD_ENOMEM) {
+                    std::fprintf(stderr, "[INFO] device editor + deflate: %s; falling back to %s\n", yacrd_last_error(), to);
                     for (yacrd_engine *en : engines) (void)yacrd_engine_trim(en);
-                    dev_edit = YACRD_EFALLBACK;
+                    rc = YACRD_EFALLBACK;
                 }
-                if (dev_edit != YACRD_OK && dev_edit != YACRD_EFALLBACK) die(yacrd_last_error());
-                // (on stdout: a stderr line that begins "[info] device editor" is the plain editor's — what reads the timing
-                // output tells the two paths apart by it — and no sub-command writes data to stdout)
-                if (dev_edit == YACRD_OK && timing)
-                    std::fprintf(stdout, "[info] device editor + deflate: %llu of %llu lines kept, %llu of %llu bytes -> %llu bytes, %llu members "
-                                         "(%llu stored), inflate %.1f ms, text %.1f ms, table %.1f ms, editor kernels %.1f ms, encoder kernels %.1f ms, "
-                                         "out %.1f ms, text_reused=%d\n",
-                                 (unsigned long long)es.n_kept, (unsigned long long)es.n_lines, (unsigned long long)es.kept_bytes,
-                                 (unsigned long long)es.text_bytes, (unsigned long long)gs.out_bytes, (unsigned long long)gs.n_members,
-                                 (unsigned long long)gs.n_stored, tx == &text ? 0.0 : inflate_ms, es.text_ms, es.table_ms, es.kernel_ms, gs.kernel_ms,
-                                 es.out_ms, tx == &text ? 1 : 0);
+                if (rc != YACRD_OK && rc != YACRD_EFALLBACK) die(yacrd_last_error());
+                return rc;
+            };
+            // (on stdout: a stderr line that begins "[info] device editor" is the plain editor's — what reads the timing
+            // output tells the two paths apart by it — and no sub-command writes data to stdout)
+            auto report = [&](double inflate_ms, bool text_reused, bool resident, bool dev_inflate) {
+                if (!timing) return;
+                std::fprintf(stdout, "[info] device editor + deflate: %llu of %llu lines kept, %llu of %llu bytes -> %llu bytes, %llu members "
+                                     "(%llu stored), inflate %.1f ms, text %.1f ms, table %.1f ms, editor kernels %.1f ms, encoder kernels %.1f ms, "
+                                     "out %.1f ms, text_reused=%d resident=%d device_inflate=%d\n",
+                             (unsigned long long)es.n_kept, (unsigned long long)es.n_lines, (unsigned long long)es.kept_bytes,
+                             (unsigned long long)es.text_bytes, (unsigned long long)gs.out_bytes, (unsigned long long)gs.n_members,
+                             (unsigned long long)gs.n_stored, inflate_ms, es.text_ms, es.table_ms, es.kernel_ms, gs.kernel_ms, es.out_ms,
+                             text_reused ? 1 : 0, resident ? 1 : 0, dev_inflate ? 1 : 0);
+            };
+            // done on the device, nothing inflated on the host: the text the ingest left in HBM, or another BGZF file as it is
+            if (ovl_resident && sub_same_file) {
+                dev_edit = settled(yacrd_engine_edit_overlaps_resident_file(engines[0], op, &tt, 1, sub_out.c_str(), &es, &gs), "the host inflate");
+                if (dev_edit == YACRD_OK) report(0.0, true, true, true);
+            } else if (inflate_on && !sub_same_file) {
+                GzipMap gm;
+                yacrd_gunzip_stats us{};
+                if (gm.open(sub_in.c_str())) {
+                    dev_edit = settled(yacrd_engine_edit_overlaps_bgzf_file(engines[0], op, gm.data(), gm.n, sub_fmt_ovl, &tt, 1, sub_out.c_str(), &es, &gs, &us),
+                                       "the host inflate");
+                    if (dev_edit == YACRD_OK && timing) print_device_inflate(us);
+                    if (dev_edit == YACRD_OK) report(0.0, false, false, true);
+                }
             }
-            yacrd_text_free(&own);
+            // else the route of before: the detection's host text, or the file inflated here
+            if (dev_edit != YACRD_OK) {
+                const auto t_in = std::chrono::steady_clock::now();
+                yacrd_text own{};
+                const yacrd_text *tx = nullptr;
+                if (text.data && sub_same_file) tx = &text;
+                else {
+                    const int rct = yacrd_text_from_file(sub_in.c_str(), threads == 1 ? 0 : (int)threads, &own);
+                    if (rct == 1) die(yacrd_host_last_error());
+                    if (rct == 0) tx = &own;
+                }
+                const double inflate_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count();
+                if (tx) {
+                    dev_edit = settled(yacrd_engine_edit_overlaps_gzip_file(engines[0], op, tx->data, tx->n, sub_fmt_ovl, &tt, sub_out.c_str(), &es, &gs),
+                                       "the host loop");
+                    if (dev_edit == YACRD_OK) report(tx == &text ? 0.0 : inflate_ms, tx == &text, false, false);
+                }
+                yacrd_text_free(&own);
+            }
         } else if (dev_ed) {
             const yacrd_type_table tt = {bp.n_reads, bp.name_off, bp.names, bp.read_type};
             yacrd_edit_stats es{};

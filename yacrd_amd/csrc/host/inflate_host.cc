@@ -14,6 +14,11 @@
 #include "../inflate_block.h"
 #include "host_common.h"
 
+namespace yke { // inflate_sample.cc (also part of the engine library, which declares it in engine_internal.h)
+int bgzf_text_ends(const unsigned char *comp, uint64_t comp_bytes, const yif::InfMember *members, uint64_t n_members, uint64_t max_text,
+                   unsigned char delim, uint32_t *n_fields, bool *ends_nl, uint32_t *status);
+}
+
 extern "C" {
 
 int yacrd_bgzf_decode_host(const char *data, uint64_t n, char **out, uint64_t *out_bytes)
@@ -73,6 +78,24 @@ int yacrd_bgzf_plan_segments(const char *data, uint64_t n, const uint64_t *lande
         mo[4 * k] = members[k].in_off, mo[4 * k + 1] = members[k].csize, mo[4 * k + 2] = members[k].isize, mo[4 * k + 3] = members[k].out_off;
     if (!steps.empty()) std::memcpy(so, steps.data(), steps.size() * sizeof(uint64_t));
     *members_out = mo, *n_members = members.size(), *steps_out = so, *n_steps = steps.size() / 8;
+    return 0;
+}
+
+int yacrd_bgzf_text_ends(const char *data, uint64_t n, int delim, uint32_t *n_fields, int *ends_nl)
+{
+    if ((!data && n) || !n_fields || !ends_nl || delim < 0 || delim > 255) return yh::fail("bad argument");
+    *n_fields = 0, *ends_nl = 1;
+    const unsigned char *d = reinterpret_cast<const unsigned char *>(data ? data : "");
+    std::vector<yif::InfMember> members;
+    uint64_t total = 0;
+    if (!ybw::walk(d, n, members, &total)) return yh::fail("not BGZF");
+    bool nl = true;
+    uint32_t status = 0;
+    const int rc = yke::bgzf_text_ends(d, n, members.data(), members.size(), (uint64_t)1 << 20, (unsigned char)delim, n_fields, &nl, &status);
+    if (rc == 1) return yh::fail(std::string("a BGZF member the device decoder does not take (") + yif::inf_status_name(status) + ")");
+    if (rc == 2) return yh::fail("the first non-empty line is not complete within the first MiB of the text");
+    if (rc) return yh::fail("host allocation failed");
+    *ends_nl = nl ? 1 : 0;
     return 0;
 }
 

@@ -55,6 +55,8 @@ EXPORTED_SYMBOLS = [
     "yacrd_engine_ingest_report", "yacrd_engine_ingest_report_mem", "yacrd_engine_write_report", "yacrd_engine_write_report_mem",
     "yacrd_engine_edit_overlaps", "yacrd_engine_edit_overlaps_mem", "yacrd_edit_text_free",
     "yacrd_engine_edit_overlaps_gzip_mem", "yacrd_engine_edit_overlaps_gzip_file",
+    "yacrd_engine_edit_overlaps_bgzf_mem", "yacrd_engine_edit_overlaps_bgzf_file",
+    "yacrd_engine_edit_overlaps_resident_mem", "yacrd_engine_edit_overlaps_resident_file",
     "yacrd_engine_edit_fastq", "yacrd_engine_edit_fastq_mem", "yacrd_engine_edit_fastq_gzip_mem", "yacrd_engine_edit_fastq_gzip_file",
     "yacrd_engine_edit_fasta", "yacrd_engine_edit_fasta_mem", "yacrd_engine_edit_fasta_gzip_mem", "yacrd_engine_edit_fasta_gzip_file",
     "yacrd_engine_gunzip_mem", "yacrd_engine_edit_fastq_bgzf_mem", "yacrd_engine_edit_fastq_bgzf_file",
@@ -346,6 +348,18 @@ def load_library():
     lib.yacrd_engine_edit_overlaps_gzip_file.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
                                                          ctypes.POINTER(_TypeTable), ctypes.c_char_p, ctypes.POINTER(_EditStats),
                                                          ctypes.POINTER(_GzipStats)]
+    lib.yacrd_engine_edit_overlaps_bgzf_mem.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                                        ctypes.POINTER(_TypeTable), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
+                                                        ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_EditStats), ctypes.POINTER(_GzipStats),
+                                                        ctypes.POINTER(_GunzipStats)]
+    lib.yacrd_engine_edit_overlaps_bgzf_file.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                                         ctypes.POINTER(_TypeTable), ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(_EditStats),
+                                                         ctypes.POINTER(_GzipStats), ctypes.POINTER(_GunzipStats)]
+    lib.yacrd_engine_edit_overlaps_resident_mem.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(_TypeTable), ctypes.c_int,
+                                                            ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64),
+                                                            ctypes.POINTER(_EditStats), ctypes.POINTER(_GzipStats)]
+    lib.yacrd_engine_edit_overlaps_resident_file.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(_TypeTable), ctypes.c_int,
+                                                             ctypes.c_char_p, ctypes.POINTER(_EditStats), ctypes.POINTER(_GzipStats)]
     lib.yacrd_edit_text_free.argtypes = [ctypes.c_void_p]
     lib.yacrd_engine_edit_fastq.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int,
                                             ctypes.POINTER(_ReportTable), ctypes.POINTER(_SeqEditStats)]
@@ -862,6 +876,59 @@ class Engine:
             return self.edit_stats, self.gzip_stats
         try:
             return ctypes.string_at(out.value, int(n_out.value))
+        finally:
+            self._lib.yacrd_edit_text_free(out)
+
+    def edit_overlaps_bgzf(self, op, blob, names, read_type, fmt, out_path=None, gzip_out=True):
+        """yacrd_engine_edit_overlaps_bgzf_mem / _file: filter (op 1) / extract (op 2) the COMPRESSED overlap file `blob` (BGZF;
+        bytes or anything else with the buffer protocol, which is not copied; fmt 1 = PAF, 2 = M4 / MHAP): it crosses the link
+        as it is and is inflated on the device, the host inflates nothing.  gzip_out: the result is edit_overlaps_gzip's for
+        the inflated text (one BGZF stream), else edit_overlaps_text's (the kept bytes).  Without out_path -> those bytes; with
+        it they are written there and (edit stats, gzip stats) returned.  The stats are also in self.edit_stats,
+        self.gzip_stats and self.inflate_stats.  Raises NeedsHostParser, with nothing written, when the text is the host
+        loop's, `blob` is not BGZF or holds a member the device decoder does not take."""
+        tt, keep = self._type_table(names, read_type)
+        st, gs, us = _EditStats(), _GzipStats(), _GunzipStats()
+        buf = np.frombuffer(blob, dtype=np.uint8)  # (no copy)
+        n = int(buf.size)
+        addr = ctypes.c_void_p(buf.ctypes.data if n else None)
+        out, n_out = ctypes.c_void_p(), ctypes.c_uint64()
+        if out_path is None:
+            rc = self._lib.yacrd_engine_edit_overlaps_bgzf_mem(self._h, int(op), addr, n, int(fmt), ctypes.byref(tt), int(bool(gzip_out)),
+                                                               ctypes.byref(out), ctypes.byref(n_out), ctypes.byref(st), ctypes.byref(gs),
+                                                               ctypes.byref(us))
+        else:
+            rc = self._lib.yacrd_engine_edit_overlaps_bgzf_file(self._h, int(op), addr, n, int(fmt), ctypes.byref(tt), int(bool(gzip_out)),
+                                                                os.fsencode(out_path), ctypes.byref(st), ctypes.byref(gs), ctypes.byref(us))
+        del keep, buf
+        return self._edited_to(rc, st, gs, us, out, n_out, out_path)
+
+    def edit_overlaps_resident(self, op, names, read_type, out_path=None, gzip_out=True):
+        """yacrd_engine_edit_overlaps_resident_mem / _file: the same on the overlap text the engine's last successful overlap
+        ingest (ingest_paf, ingest_text, ingest_bgzf) left in HBM: nothing goes up (edit_stats["mirror_reused"] == 1).  Returns
+        as edit_overlaps_bgzf does.  Raises EngineError — not NeedsHostParser: the caller's logic is wrong — when no overlap
+        text is resident."""
+        tt, keep = self._type_table(names, read_type)
+        st, gs = _EditStats(), _GzipStats()
+        out, n_out = ctypes.c_void_p(), ctypes.c_uint64()
+        if out_path is None:
+            rc = self._lib.yacrd_engine_edit_overlaps_resident_mem(self._h, int(op), ctypes.byref(tt), int(bool(gzip_out)), ctypes.byref(out),
+                                                                   ctypes.byref(n_out), ctypes.byref(st), ctypes.byref(gs))
+        else:
+            rc = self._lib.yacrd_engine_edit_overlaps_resident_file(self._h, int(op), ctypes.byref(tt), int(bool(gzip_out)),
+                                                                    os.fsencode(out_path), ctypes.byref(st), ctypes.byref(gs))
+        del keep
+        return self._edited_to(rc, st, gs, None, out, n_out, out_path)
+
+    def _edited_to(self, rc, st, gs, us, out, n_out, out_path):
+        self._edited(rc, st)
+        self.gzip_stats = {f: getattr(gs, f) for f, _ in _GzipStats._fields_}
+        if us is not None:
+            self.inflate_stats = {f: getattr(us, f) for f, _ in _GunzipStats._fields_}
+        if out_path is not None:
+            return self.edit_stats, self.gzip_stats
+        try:
+            return ctypes.string_at(out.value, int(n_out.value)) if n_out.value else b""
         finally:
             self._lib.yacrd_edit_text_free(out)
 

@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "yacrd_edit_file", "yacrd_edit_file_mt", "yacrd_text_from_file", "yacrd_text_free", "yacrd_report_read", "yacrd_report_get", "yacrd_report_free",
     "yacrd_edit_file_to", "yacrd_file_compression", "yacrd_bgzf_encode_host", "yacrd_bgzf_decode_host", "yacrd_bytes_free", "yacrd_deflate_code_lengths",
     "yacrd_synth_fastq", "yacrd_ingest_stream", "yacrd_ingest_stream_memory", "yacrd_csr_handle_map", "yacrd_bgzf_plan_segments",
+    "yacrd_bgzf_text_ends",
 ]
 
 OP_SCRUBB, OP_FILTER, OP_EXTRACT, OP_SPLIT = 0, 1, 2, 3
@@ -164,6 +165,8 @@ def load_library():
         lib.yacrd_bgzf_plan_segments.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
                                                  ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64),
                                                  ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)]
+        lib.yacrd_bgzf_text_ends.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32),
+                                             ctypes.POINTER(ctypes.c_int)]
         lib.yacrd_bytes_free.argtypes = [ctypes.c_void_p]
         lib.yacrd_bytes_free.restype = None
         lib.yacrd_deflate_code_lengths.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
@@ -401,6 +404,19 @@ def bgzf_plan_segments(data, landed, chunk=0, seg_chunks=0):
         lib.yacrd_bytes_free(mo)
         lib.yacrd_bytes_free(so)
     return members, steps
+
+
+def bgzf_text_ends(blob, delim):
+    """yacrd_bgzf_text_ends: what the device overlap editor asks of a BGZF text before its first launch -> (the field count
+    under `delim` (one byte, or its code) of the first non-empty line, 0 when there is none; whether the text's last byte is a
+    newline, True for a text of no bytes).  Raises HostError for a stream that is not BGZF, a sampled member the decoder does
+    not take, or a first non-empty line that is not complete within the first MiB of a text that goes on."""
+    lib = load_library()
+    blob = bytes(blob)
+    d = delim if isinstance(delim, int) else ord(delim)
+    nf, nl = ctypes.c_uint32(), ctypes.c_int()
+    _check(lib, lib.yacrd_bgzf_text_ends(blob, len(blob), int(d), ctypes.byref(nf), ctypes.byref(nl)))
+    return int(nf.value), bool(nl.value)
 
 
 def deflate_code_lengths(freq, limit):
