@@ -645,9 +645,16 @@ int yacrd_engine_write_report_mem(yacrd_engine *e, const yacrd_report_table *t /
  * with a name and no blank directly in front of its newline, every third line exactly `+`, sequence and quality of equal
  * length (0 is allowed); a cut position beyond the record's sequence or a region with begin > end (the host words both);
  * 2^31 records or output records; a compressed or non-regular input, or one whose name does not say FASTQ, to the file form;
- * an out_path that is the input or exists and is no regular file; a text and output beyond the device's free memory (both
- * lie in HBM whole; decided before anything is written).  The caller then runs yacrd_edit_file, which owns the syntax, the
+ * an out_path that is the input or exists and is no regular file.  Memory is no cause for these four forms: a text that does
+ * not fit the device's free memory with its output is edited window by window (128 MiB of text at a time, in a ring of
+ * buffers: DESIGN 7k), with the same bytes; what is left of it is a single record of more than 128 MiB ("a record longer
+ * than a window"), and the ring itself not fitting.  In windows a cause may be found after earlier windows' output has
+ * left the device: the file beside out_path is then dropped, the _mem buffer freed, the stats zeroed — nothing written,
+ * nothing left beside out_path, as before.  (The BGZF-in forms below and FASTA hold text and output in HBM whole, and say
+ * YACRD_EFALLBACK when they do not fit.)  The caller then runs yacrd_edit_file, which owns the syntax, the
  * codecs and the messages.  An empty text is an empty output.
+ * In windows the stats' counts and bytes are sums over the windows, kernel_ms the sum of the windows' event pairs, text_ms the
+ * time this thread spent landing windows, out_ms the writer thread's busy time.
  * The file form writes beside out_path and renames when the last byte is in; buffers of the _mem forms: yacrd_edit_text_free.
  * The gzip forms mirror yacrd_engine_edit_overlaps_gzip_*: `text` is the inflated FASTQ, the finished output is deflated
  * where it lies and only members come home; the result is ONE BGZF stream, byte for byte yacrd_engine_gzip_mem of the plain

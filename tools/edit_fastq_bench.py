@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/edit_fastq_bench.py --parent-bin PATH [--parent-again] [--fasta] [--reads R] [--overlaps O] [--runs K] [--ops scrubb,filter] [--forms plain,gzip1,bgzf] [--json PATH]
+"""tools/edit_fastq_bench.py --parent-bin PATH [--parent-again] [--fasta] [--window BYTES] [--reads R] [--overlaps O] [--runs K] [--ops scrubb,filter] [--forms plain,gzip1,bgzf] [--json PATH]
 scrubb / filter on a FASTQ through the COMMAND, the parent commit's `yacrd` against this tree's, on a synthetic Sequel FASTQ
 (50 000 reads: about 1 GB) in /dev/shm, output there too:
     yacrd -i s.paf -o r.yacrd -c 3 -n 0.4 <op> -i reads.fastq[.gz] -o out.fastq[.gz]
@@ -16,6 +16,10 @@ output is compared with the parent's (gzip: the inflated bytes when the streams 
 appended to --json (default profiles/edit_fastq.json).
 --fasta: the same reads as FASTA, 80 bases a line (reads.fasta[.gz]): the device path is yacrd_engine_edit_fasta, its line
 "[info] device fasta editor:", the default --json profiles/edit_fasta.json.
+--window BYTES: the FASTQ editor's windows against its whole-text run, in the same call: the "new" series runs
+with YACRD_SEQ_WINDOW=18446744073709551615 (never windows), a third series "windowed" with YACRD_SEQ_WINDOW=BYTES; its output
+is compared with the parent's too, and the row says whether the windowed run's slowest `edit` is ahead of the whole-text
+run's fastest (the rule for the default).  The default --json is then profiles/edit_fastq_windows.json.
 --parent-again: a second series of the parent behind the new one ("parent_again" in the row): what drifted meanwhile shows.
 Where the parent has a device editor too, the figure to compare is the `kernels ... ms` of the info lines, not the stage."""
 import argparse, gzip, json, os, re, subprocess, sys, time
@@ -33,10 +37,11 @@ ap.add_argument("--forms", default="plain,gzip1,bgzf")
 ap.add_argument("--parent-bin", default=None)
 ap.add_argument("--fasta", action="store_true")
 ap.add_argument("--parent-again", action="store_true")
+ap.add_argument("--window", type=int, default=0)
 ap.add_argument("--json", default=None)
 a = ap.parse_args()
 kind = "fasta" if a.fasta else "fastq"
-a.json = a.json or os.path.join(ROOT, "profiles", "edit_%s.json" % kind)
+a.json = a.json or os.path.join(ROOT, "profiles", "edit_%s%s.json" % (kind, "_windows" if a.window else ""))
 editor_line = "[info] device %s editor:" % kind
 if not a.parent_bin or not os.access(a.parent_bin, os.X_OK):
     sys.exit("--parent-bin: the yacrd binary built from the parent commit")
@@ -73,14 +78,14 @@ def same(x, y, inflate):
     return all(p == q for p, q in zip(chunks(x), chunks(y)))
 
 
-def run(binary, op, src, out):
+def run(binary, op, src, out, **env):
     rows = []
     for k in range(a.runs + 1):
         fresh(out)
         fresh(rep)
         t0 = time.perf_counter()
         p = subprocess.run([binary, "-i", paf, "-o", rep, "-c", "3", "-n", "0.4", op, "-i", src, "-o", out],
-                           capture_output=True, text=True, env=dict(os.environ, YACRD_CLI_TIMING="1"))
+                           capture_output=True, text=True, env=dict(os.environ, YACRD_CLI_TIMING="1", **env))
         wall = time.perf_counter() - t0
         assert p.returncode == 0, p.stderr
         stages = dict(re.findall(r"^\[timing\] (\S+) ([0-9.]+) s$", p.stderr, re.M))
@@ -120,7 +125,12 @@ try:
             old, new = tag + "old" + ext, tag + "new" + ext
             made.extend([old, new])
             parent = run(a.parent_bin, op, src, old)
-            mine = run(new_bin, op, src, new)
+            mine = run(new_bin, op, src, new, **({"YACRD_SEQ_WINDOW": str(2 ** 64 - 1)} if a.window else {}))
+            windowed = None
+            if a.window:
+                assert same(old, new, False) or (form != "plain" and same(old, new, True)), "the whole-text run's output differs from the parent's"
+                windowed = run(new_bin, op, src, new, YACRD_SEQ_WINDOW=str(a.window))
+                assert all(int(l.rsplit("windows=", 1)[1]) > 1 for r in windowed for l in r["info"] if l.startswith(editor_line)), "not in windows"
             again = run(a.parent_bin, op, src, old) if a.parent_again else None
             assert any(l.startswith(editor_line) for l in mine[-1]["info"]), "the device editor did not run"
             assert same(old, new, False) or (form != "plain" and same(old, new, True)), "the new path's output differs from the parent's"
@@ -129,6 +139,11 @@ try:
                    "out_bytes": os.path.getsize(new), "parent": parent, "new": mine, "edit_stage_slowest_new_s": worst_new,
                    "edit_stage_fastest_parent_s": best_old, "ratio": round(best_old / worst_new, 2),
                    "wall_slowest_new_s": max(r["wall_s"] for r in mine), "wall_fastest_parent_s": min(r["wall_s"] for r in parent)}
+            if windowed:
+                worst_w, best_whole = max(r["edit_s"] for r in windowed), min(r["edit_s"] for r in mine)
+                row.update({"window_bytes": a.window, "windowed": windowed, "edit_stage_slowest_windowed_s": worst_w,
+                            "edit_stage_fastest_whole_s": best_whole, "windowed_ahead": worst_w < best_whole,
+                            "ratio_windowed": round(best_old / worst_w, 2), "wall_slowest_windowed_s": max(r["wall_s"] for r in windowed)})
             if again:
                 row["parent_again"] = again
             line = json.dumps(row)

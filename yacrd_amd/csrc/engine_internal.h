@@ -384,6 +384,10 @@ struct yacrd_engine {
         if (scratch[k].p) scratch[k].destroy(scratch[k].p);
         scratch[k].p = nullptr;
     }
+    // the FASTQ editor's windows (gpu_seq_edit.hip): the switch yacrd_debug_seq_window set (0: the policy; UINT64_MAX: never
+    // windows; else the window's bytes) and what yacrd_debug_seq_windows reports of the last sequence edit
+    uint64_t seq_window = 0;
+    uint64_t seq_windows[4] = {0, 0, 0, 0};
     bool gzip_busy = false; // a yacrd_gzip_writer or an edit to gzip holds the kGzip slot: trim leaves it alone
 };
 

@@ -27,7 +27,10 @@
 //            walks on from there; every 4-byte word of the tile is composed in LDS — header bytes formatted, text bytes fetched
 //            with aligned 4-byte loads (neighbouring lanes read neighbouring words) — and the tile is stored with 16-byte stores;
 //            the bytes stored are counted, a total that differs from the scan's is YACRD_EINTERNAL
-// In this version index, plan, pieces and copy wait for the last segment of text, and the text and the whole output lie in HBM.
+// In the whole-text run index, plan, pieces and copy wait for the last segment of text, and the text and the whole output lie in
+// HBM.  A FASTQ of more than one window whose text comes from a file or from host memory may instead run WINDOW BY WINDOW
+// (SeqRun::run_windows): the same kernels on bytes [lo, hi) of a text slot, a carry kernel between windows, two
+// text slots and two output slots, a writer thread on the way out; always where the whole text finds no room.
 // What the path does not take — a CR, a line count that is no multiple of four, a header without '@' or without a name, a
 // "@name \n", a '+' line that is not bare, sequence and quality of different lengths, a cut position beyond the read, a region
 // with begin > end — comes back as YACRD_EFALLBACK with nothing written: the caller runs the host loop.
@@ -50,7 +53,9 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <deque>
 #include <initializer_list>
+#include <mutex>
 #include <type_traits>
 
 using namespace yke;
@@ -58,8 +63,10 @@ using namespace yke;
 namespace yk {
 
 constexpr u32 kSqNeedHost = 1u;
+constexpr u32 kSqCarryLong = 2u;      // status: what a window leaves for the next one is longer than a window (sq_carry_kernel)
 constexpr int kSqOutTile = kGpT * 16; // bytes of output per workgroup of the copy pass
 constexpr u32 kSqCopy = 1u;           // SqPiece::flags: the record as it stands in the text
+constexpr u32 kSqRaw = 2u;            // ... bytes [rec, rec + len) of SqArgs::raw, not of the text: the output tail of the window before
 constexpr u64 kSqMaxRecord = 0xFF000000ull; // bytes of a record, of a piece: offsets inside them are u32
 
 struct SqPiece { // one record of the output
@@ -92,10 +99,15 @@ struct SeqArgs { // what the kernels of both formats read; SqArgs and FaArgs (be
 struct SqArgs : SeqArgs {
     u64 n;     // bytes of text
     u64 avail; // bytes [0, avail) have landed (== n for the last segment)
+    u64 lo;    // the text's first byte: 0, or where a window's carry begins in its slot (what lies below is stale)
     u32 *tile_nl;        // per text tile: its newlines
     const u64 *tile_l0;  // their exclusive scan
     u32 tile0;           // the launch's first text tile
     SqPiece *pieces;
+    // a window of a gzip run (run_windows): piece 0 is `out0` bytes at `raw`, the records' pieces and bytes lie behind it
+    const unsigned char *raw;
+    u64 out0;   // bytes of the output slot in front of the first record's
+    u32 piece0; // pieces in front of the first record's (0 or 1)
 };
 static_assert(std::is_trivially_copyable<SqArgs>::value, "a kernel argument by value");
 
@@ -108,17 +120,19 @@ __device__ __forceinline__ void seq_status(unsigned long long *ctl, u32 status)
 
 // the tile's newline masks (a u16 per 16 bytes) -> nlm; returns the thread's newline count and ORs a CR into `cr`.  The
 // mirror is padded by 64 zero bytes and the last step is clipped to whole 16-byte pieces inside it; an inner segment's
-// `avail` is a chunk boundary.
+// `avail` is a chunk boundary.  A byte below a.lo gives no bit: a piece wholly below it is not loaded, the one it cuts is masked.
 __device__ __forceinline__ u32 sq_stage(const SqArgs &a, u64 tile0, unsigned short *nlm, u32 &cr)
 {
     const u64 lim = a.avail == a.n ? ((a.n + 63) & ~(u64)15) : a.avail;
     u32 cnt = 0;
     for (u32 i = threadIdx.x * 16u; i < (u32)kGpTile; i += (u32)kGpT * 16u) {
         u32 nlb = 0;
-        if (tile0 + i < lim) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(a.text + tile0 + i);
-            nlb = gp_eq16(v, '\n');
-            cr |= gp_eq16(v, '\r');
+        const u64 at = tile0 + i;
+        if (at < lim && at + 16u > a.lo) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(a.text + at);
+            const u32 keep = at < a.lo ? ~0u << (u32)(a.lo - at) : ~0u;
+            nlb = gp_eq16(v, '\n') & keep;
+            cr |= gp_eq16(v, '\r') & keep;
         }
         if (nlm) nlm[i >> 4] = (unsigned short)nlb;
         cnt += (u32)__popc(nlb);
@@ -143,7 +157,7 @@ __global__ __launch_bounds__(kGpT) void sq_index_kernel(SqArgs a)
 {
     __shared__ __attribute__((aligned(16))) unsigned short nlm[kGpTile / 16];
     __shared__ u32 sw[kGpT / 64];
-    const u32 gt = blockIdx.x;
+    const u32 gt = a.tile0 + blockIdx.x;
     const u64 tile0 = (u64)gt * (u64)kGpTile;
     u32 cr = 0;
     (void)sq_stage(a, tile0, nlm, cr);
@@ -270,6 +284,46 @@ __device__ __forceinline__ u32 sq_load4(const unsigned char *src)
     return word;
 }
 
+// ---- carry: what a window leaves behind its last whole record -> the front of the next window's slot ---------------------------
+// Window k's text is bytes [lo, hi) of its slot; its n_rec whole records end at line_end[4 n_rec - 1].  The bytes behind them,
+// [cb, hi), are moved to end at offset W of the next slot — in front of the new bytes, which land at W whatever the carry's
+// length turns out to be.  Every thread reads cb itself; thread 0 reports the length and sets kSqCarryLong when the carry
+// area (W bytes) does not hold it: nothing is moved then.  The destination's end is 16-byte aligned, so the move is whole
+// aligned 16-byte stores and bytes in the first, cut piece; a piece is loaded with one 16-byte load when source and
+// destination are aligned alike, else as four words put together from aligned 4-byte loads (sq_load4: at most 7 bytes
+// behind hi are read, inside the slot's 64 bytes of padding).  The two slots are different buffers: nothing overlaps.
+struct SqCarry {
+    const u64 *line_end;
+    u64 n_rec, lo, hi, W;
+    const unsigned char *src; // this window's slot
+    unsigned char *dst;       // the next window's
+    unsigned long long *ctl;  // [0] status, [2] the carry's bytes
+};
+__global__ __launch_bounds__(256) void sq_carry_kernel(SqCarry c)
+{
+    const u64 cb = c.n_rec ? c.line_end[4 * c.n_rec - 1] + 1 : c.lo;
+    const u64 len = c.hi - cb;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        c.ctl[2] = len;
+        if (len > c.W) atomicOr(c.ctl, (unsigned long long)kSqCarryLong);
+    }
+    if (len > c.W) return;
+    const u64 d0 = c.W - len;
+    const unsigned char *from = c.src + cb - d0; // (byte o of the destination is from[o], d0 <= o < W)
+    const bool alike = ((cb ^ d0) & 15u) == 0;
+    for (u64 q = (d0 >> 4) + (u64)blockIdx.x * 256u + threadIdx.x; q < (c.W >> 4); q += (u64)gridDim.x * 256u) {
+        const u64 o = q << 4;
+        if (o < d0) { // the piece the carry's first byte cuts
+            for (u64 b = d0; b < o + 16u; b++) c.dst[b] = from[b];
+            continue;
+        }
+        uint4 v;
+        if (alike) v = *reinterpret_cast<const uint4 *>(from + o);
+        else v = make_uint4(sq_load4(from + o), sq_load4(from + o + 4), sq_load4(from + o + 8), sq_load4(from + o + 12));
+        *reinterpret_cast<uint4 *>(c.dst + o) = v;
+    }
+}
+
 // the composed tile -> the output, 16 bytes per thread; the bytes the workgroup composed -> ctl[1], one add per workgroup
 __device__ __forceinline__ void sq_store_tile(unsigned char *out, u64 total, unsigned long long *ctl, const u32 *tile, u32 *sw, u64 tile0, u32 stored)
 {
@@ -344,7 +398,7 @@ struct Fastq {
     static __device__ __forceinline__ u32 record(const SqArgs &a, u64 r)
     {
         const unsigned char *t = a.text;
-        const u64 s = r ? a.line_end[4 * r - 1] + 1 : 0;
+        const u64 s = r ? a.line_end[4 * r - 1] + 1 : a.lo;
         const u64 e0 = a.line_end[4 * r], e1 = a.line_end[4 * r + 1], e2 = a.line_end[4 * r + 2], e3 = a.line_end[4 * r + 3];
         if (!EMIT) a.rec_pieces[r] = 0u, a.rec_bytes[r] = 0u;
         const u64 rec_len = e3 + 1 - s;
@@ -372,8 +426,8 @@ struct Fastq {
             if (!EMIT) a.rec_pieces[r] = 1u, a.rec_bytes[r] = (u32)rec_len;
             else {
                 SqPiece p{};
-                p.out = a.byte_off[r], p.rec = s, p.len = (u32)rec_len, p.flags = kSqCopy;
-                a.pieces[a.piece_off[r]] = p;
+                p.out = a.out0 + a.byte_off[r], p.rec = s, p.len = (u32)rec_len, p.flags = kSqCopy;
+                a.pieces[a.piece0 + a.piece_off[r]] = p;
             }
             return 0u;
         }
@@ -382,11 +436,11 @@ struct Fastq {
             const u64 plen = (u64)head + 2u + sq_digits(p0) + sq_digits(p1) + 2ull * (p1 - p0) + 4u;
             if (EMIT) {
                 SqPiece p{};
-                p.out = a.byte_off[r] + at, p.rec = s, p.len = (u32)plen, p.flags = 0u;
+                p.out = a.out0 + a.byte_off[r] + at, p.rec = s, p.len = (u32)plen, p.flags = 0u;
                 p.name_len = name_len, p.desc_len = desc_len;
                 p.seq_rel = (u32)(e0 + 1 - s), p.qual_rel = (u32)(e2 + 1 - s);
                 p.p0 = p0, p.p1 = p1;
-                a.pieces[a.piece_off[r] + k] = p;
+                a.pieces[a.piece0 + a.piece_off[r] + k] = p;
             }
             return plen;
         });
@@ -394,8 +448,8 @@ struct Fastq {
 
     static __device__ __forceinline__ void at(const SqArgs &a, const SqPiece &p, u32 k, Cursor &, const unsigned char *&src, u32 &rem, u32 &lit)
     {
-        const unsigned char *rec = a.text + p.rec;
-        if (p.flags & kSqCopy) {
+        const unsigned char *rec = (p.flags & kSqRaw ? a.raw : a.text) + p.rec;
+        if (p.flags & (kSqCopy | kSqRaw)) {
             src = rec + k, rem = p.len - k;
             return;
         }
@@ -664,6 +718,8 @@ namespace {
 
 constexpr size_t kOutPiece = (size_t)4 << 20; // (_PIECE of the tests: what one copy home moves)
 constexpr u64 kGzBatchBlocks = 2048;          // blocks of 65 280 bytes per batch of the encoder
+// whether a FASTQ that fits whole runs in windows all the same (the switch aside): decided by measurement, DESIGN 7k
+constexpr bool kSeqWindowsWhenFits = false;
 
 struct SeqEditScratch { // the editor's buffers; they stay with the engine (grow-only), go with yacrd_engine_trim / destroy
     static constexpr yacrd_engine::Slot kScratchSlot = yacrd_engine::kSeqEdit;
@@ -671,6 +727,7 @@ struct SeqEditScratch { // the editor's buffers; they stay with the engine (grow
     EdTableOwner table; // the reads' names and types, the id table over them
     DevBuf ln_head, ln_bases, ln_rec, base_before, rec_line, rec_width; // FASTA: per line, per record
     PinBuf pin; // two output pieces + the control words
+    DevBuf wtext[2], wout[2]; // a run in windows (SeqRun::run_windows): its two text slots, its two output slots
 };
 
 using yseg::Sink;
@@ -698,13 +755,14 @@ struct SeqRun {
     Sink &sink;
     yacrd_seq_edit_stats *stats;
     SeqEditScratch &S;
+    u64 W = 0; // 0: the whole text at once; else the run goes window by window, this many new bytes each (run_windows)
     u64 R = 0, G = 0, name_bytes = 0, cap = 1024;
     u64 n_tiles = 0, n_lines = 0, n_rec = 0, n_pieces = 0, total = 0;
     size_t n_segs = 0;
     bool blit = false;
     yk::SqArgs ga{};
     yk::FaArgs fa{}; // (FASTA: what the kernels behind the line index take)
-    volatile u64 *h_ctl = nullptr; // pinned: [0..3] what a phase brings home, [4..7] the encoder's words of two batches
+    volatile u64 *h_ctl = nullptr; // pinned: [0..3] what a phase brings home, [4..7] the encoder's words of two batches, [8..11] the copy pass's of two windows
     Events ev;                     // pairs around the kernels of a phase (timing)
     Events wev;                    // a pinned piece has landed (two; no timing)
     Events gev, gdone;             // the encoder's batches: pairs around their kernels; behind their sizes' way home
@@ -725,11 +783,18 @@ struct SeqRun {
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return true; // (the reserves then say)
         return need * 1.125 + (double)((size_t)64 << 20) <= (double)free_b + held;
     }
-    static int no_room() { return fail(YACRD_EFALLBACK, "the text and its output do not fit this device's free memory: the host loop streams them"); }
+    bool room_failed = false; // the whole-text run found no room (run_seq_edit: a FASTQ of more than a window then runs in windows)
+    int no_room()
+    {
+        room_failed = true;
+        return no_room_message();
+    }
+    static int no_room_message() { return fail(YACRD_EFALLBACK, "the text and its output do not fit this device's free memory: the host loop streams them"); }
 
     bool ev_open()
     {
-        return n_ev + 2 <= ev.v.size() && hipEventRecord(ev[n_ev], e->stream) == hipSuccess;
+        if (n_ev + 2 > ev.v.size() && !ev.add(2)) return false; // (a run in windows: its pairs are as many as its windows make them)
+        return hipEventRecord(ev[n_ev], e->stream) == hipSuccess;
     }
     bool ev_close()
     {
@@ -781,11 +846,19 @@ struct SeqRun {
             if (!src.fetch(&last, 1, n - 1)) return fail(YACRD_EINVAL, "read error in the sequence file");
             if (last != '\n') return fail(YACRD_EFALLBACK, "the text's last line has no newline: the host loop's case");
         }
+        while (cap < 2 * R) cap <<= 1;
+        t_start = now_ms();
+        if (W) { // in windows: the ring's slots, two of text and two of output (sized for a window that goes out as it came in), and a window's tables
+            n_tiles = (2 * W + yk::kGpTile - 1) / yk::kGpTile;
+            const double ring = 2.0 * (2.0 * (double)W + 64.0) + 2.0 * (double)W + (double)W * 0.25;
+            const double held_w = (double)S.wtext[0].cap + (double)S.wtext[1].cap + (double)S.wout[0].cap + (double)S.wout[1].cap +
+                                  (double)S.table.names.cap + (double)S.table.slots.cap + (double)S.bad_reg.cap;
+            if (!fits(ring + (double)name_bytes + (double)cap * 4.0 + (double)R * 21.0 + (double)G * 8.0, held_w)) return no_room_message();
+            return YACRD_OK;
+        }
         n_tiles = (n + yk::kGpTile - 1) / yk::kGpTile;
         if (n_tiles >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "file too large for the device editor");
         n_segs = (size_t)((n + kTextChunk * kTextSeg - 1) / (kTextChunk * kTextSeg));
-        while (cap < 2 * R) cap <<= 1;
-        t_start = now_ms();
         const double held = (double)S.text.cap + (double)S.table.names.cap + (double)S.table.slots.cap + (double)S.bad_reg.cap + (double)S.tile_l0.cap;
         // (the output is at least... unknown yet: asked for again when it is; here the text, the table and the tiles' words)
         const double comp = job.bgzf ? (double)job.bgzf_bytes + (double)job.members->size() * (double)sizeof(yif::InfMember) : 0.0; // (the inflate scratch's)
@@ -798,15 +871,15 @@ struct SeqRun {
     {
         const yacrd_report_table &t = *job.table;
         const void *mirror_before = S.text.p;
-        HIP_TRY(S.text.reserve((size_t)n + 64));
+        if (!W) HIP_TRY(S.text.reserve((size_t)n + 64));
         blit = S.text.p != mirror_before; // a fresh mirror fills faster by copy kernel (gpu_paf.hip)
         HIP_TRY(S.tile_nl.reserve((size_t)(n_tiles + 1) * sizeof(u32)));
         HIP_TRY(S.tile_l0.reserve((size_t)(n_tiles + 2) * sizeof(u64)));
-        HIP_TRY(S.ctl.reserve(64));
-        HIP_TRY(hipMemsetAsync(S.ctl.p, 0, 64, e->stream));
-        HIP_TRY(S.pin.reserve(2 * kOutPiece + 8 * sizeof(u64)));
+        HIP_TRY(S.ctl.reserve(4 * 64)); // (a run in windows: four windows' words in turn)
+        HIP_TRY(hipMemsetAsync(S.ctl.p, 0, 4 * 64, e->stream));
+        HIP_TRY(S.pin.reserve(2 * kOutPiece + 12 * sizeof(u64) + 2 * sizeof(yk::SqPiece))); // (the raw pieces of two windows: run_windows)
         h_ctl = reinterpret_cast<volatile u64 *>(S.pin.as<char>() + 2 * kOutPiece);
-        for (int i = 0; i < 8; i++) h_ctl[i] = 0;
+        for (int i = 0; i < 12; i++) h_ctl[i] = 0;
         if (!side.add(job.gzip ? 2 : 1) || !wev.add(2, hipEventDisableTiming) || !ev.add(2 * n_segs + 10)) HIP_TRY(why_not_added());
         HIP_TRY(S.lengths.reserve((size_t)(R + 1) * sizeof(u32)));
         HIP_TRY(S.bad_off.reserve((size_t)(R + 1) * sizeof(u64)));
@@ -903,6 +976,7 @@ struct SeqRun {
 
     void launch_index()
     {
+        ga.tile0 = 0;
         if (n_tiles) hipLaunchKernelGGL(yk::sq_index_kernel, dim3((u32)n_tiles), dim3(yk::kGpT), 0, e->stream, ga);
     }
 
@@ -1064,6 +1138,314 @@ struct SeqRun {
         return rc;
     }
 
+    // ==== the run in windows (FASTQ, text from a file or from memory) =====================================================
+    // Window k's new bytes are text[kW, min((k + 1) W, n)); its text is the carry of window k - 1 — the bytes behind that
+    // window's last whole record — and then its new bytes.  A text slot is [carry area: W][new bytes: W][64 zero bytes]: the
+    // new bytes always land at offset W, the carry is moved on the device to END at W (sq_carry_kernel), so a window is bytes
+    // [lo, hi) of its slot, lo = W - carry, and by induction begins on a record boundary: its records are its lines 4j .. 4j + 3.
+    //
+    // Who runs beside whom.  THIS thread lands window k (move_text: its threads and copy streams), launches k's kernels on the
+    // engine's stream and waits for it twice — line count; pieces, bytes, status, carry —, then launches k's pieces and copy
+    // passes and goes on to land window k + 1 WITHOUT waiting for them.  The WRITER thread takes the windows in order behind
+    // the event of their copy pass: the bytes go home through the two pinned pieces into the sink or, gzip out, through the
+    // encoder on its own stream first.  So window k + 1 lands while k is gathered and while k and k - 1 leave.
+    //
+    // Why nothing is freed or overwritten under a kernel (the engine's stream runs in order; S(k) is this thread's second wait
+    // of window k, W1(k) its first — both leave the engine's stream empty):
+    //   text slots, two   window k + 1 is written — its carry by k's carry kernel, its new bytes by the mover — into the slot
+    //                     window k - 1 lay in.  Its last reader is the copy pass of k - 1.  The carry kernel of k is enqueued
+    //                     behind that pass on the same stream; the mover starts behind S(k), which the pass precedes.
+    //   a window's tables line_end, rec_*, *_off, pieces, tile_* are one set, reserved behind W1(k) (pieces: behind S(k)): every
+    //                     kernel of window k - 1 has ended by then, and the writer never reads them.
+    //   `part`            (the scans' scratch) is reserved inside a scan; the scans of a window follow W1(k) or S(k - 1) with
+    //                     no other scan in flight.
+    //   output slots, two slot k & 1 is read by the writer (way home, encoder) for window k and, gzip out, by the copy pass of
+    //                     window k + 1 (the raw piece: k's ragged tail).  This thread reserves and refills it for window k + 2
+    //                     behind S(k + 2) — the copy pass of k + 1 has ended — and behind the writer's release of window k,
+    //                     given when the last copy home or the last batch of the encoder that reads the slot has been waited for.
+    //   control words     four sets in turn; a set is zeroed for window k + 4 behind the release of window k + 1.
+    struct WinPost { // a window handed to the writer
+        int slot;
+        u64 len; // bytes in the output slot: the tail of the window before (gzip out) and this window's output
+        bool last;
+    };
+    std::mutex win_mu;
+    std::deque<WinPost> win_posted;
+    std::atomic<size_t> win_n_posted{0}, win_released{0};
+    std::atomic<bool> win_no_more{false};
+    std::atomic<int> win_stop{0}; // the way home gives up (HomeLink::stop): this thread found a cause, or the writer did
+    int w_rc = YACRD_OK;          // the writer's code and message: fail() speaks on the thread that calls it
+    std::string w_msg;
+    Streams lanes;                // the mover's copy streams: made by the first window, kept for the run
+    Events cdone;                 // behind a window's copy pass and its words' way home, per output slot
+    std::vector<long> gz_batch_win; // per batch of the encoder: the window whose output slot it is the last to read, or -1
+    size_t gz_sent = 0, gz_got = 0;
+    std::vector<u64> gz_eof;
+
+    void writer_fail(int code, const char *msg)
+    {
+        if (w_rc == YACRD_OK) w_rc = code, w_msg = msg;
+        win_stop = 1;
+    }
+    // bring_home on the writer thread: its failures are kept, not spoken
+    bool writer_home(const char *base, u64 len)
+    {
+        HomeLink dma{base, side[0], {wev[0], wev[1]}, &win_stop};
+        const int rc = yseg::pump(len, kOutPiece, S.pin.as<char>(), dma, sink, [&](auto put) {
+            const double tp = now_ms();
+            put();
+            put_ms += now_ms() - tp;
+        });
+        if (rc == yseg::kLinkFailed) writer_fail(YACRD_ENODEV, "sequence editor: a HIP call failed on the way home");
+        if (rc == yseg::kSinkFailed) writer_fail(YACRD_EINVAL, "Error during writing of the output file");
+        return rc == yseg::kPumped;
+    }
+    bool writer_encode(const unsigned char *text, u64 len, bool last, long releases)
+    {
+        const size_t b = gz_sent;
+        if (!gev.add(2) || !gdone.add(1, hipEventDisableTiming)) return writer_fail(YACRD_ENODEV, "sequence editor: a HIP event could not be created"), false;
+        volatile u64 *w = h_ctl + 4 + 2 * (b & 1);
+        w[0] = w[1] = 0;
+        if (gzip_device_encode(e, gz, side[1], text, len, last, (int)(b & 1), gev[2 * b], gev[2 * b + 1], w, w + 1) != YACRD_OK ||
+            hipEventRecord(gdone[b], side[1]) != hipSuccess)
+            return writer_fail(YACRD_ENODEV, "sequence editor: a HIP call failed in the encoder"), false;
+        gz_batch_win.push_back(releases), gz_eof.push_back(last ? ydf::kEofBytes : 0u);
+        gz_members += (len + ydf::kBlock - 1) / ydf::kBlock;
+        gz_sent = b + 1;
+        return true;
+    }
+    bool writer_fetch()
+    {
+        const size_t b = gz_got;
+        if (hipEventSynchronize(gdone[b]) != hipSuccess) return writer_fail(YACRD_ENODEV, "sequence editor: a HIP call failed in the encoder"), false;
+        volatile u64 *w = h_ctl + 4 + 2 * (b & 1);
+        const u64 bytes = w[0] + gz_eof[b];
+        if (bytes > gz.max_blocks * ydf::kSlot + ydf::kEofBytes)
+            return writer_fail(YACRD_EINTERNAL, "device deflate: more bytes than the members' slots hold"), false;
+        gz_stored = w[1];
+        if (gz_batch_win[b] >= 0) win_released.store((size_t)gz_batch_win[b] + 1, std::memory_order_release); // (the encoder has read the slot)
+        gz_got = b + 1;
+        return writer_home(reinterpret_cast<const char *>(gz.out[b & 1]), bytes);
+    }
+    // the writer thread: one, in order
+    void window_writer()
+    {
+        if (hipSetDevice(e->device) != hipSuccess) writer_fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
+        const u64 per = job.gzip ? gz.max_blocks * ydf::kBlock : 0;
+        for (size_t k = 0; !win_stop.load(); k++) {
+            while (win_n_posted.load(std::memory_order_acquire) <= k && !win_no_more.load() && !win_stop.load()) {
+                struct timespec ts = {0, 50000};
+                nanosleep(&ts, nullptr);
+            }
+            if (win_n_posted.load(std::memory_order_acquire) <= k || win_stop.load()) break;
+            WinPost p;
+            {
+                std::lock_guard<std::mutex> g(win_mu);
+                p = win_posted[k];
+            }
+            if (hipEventSynchronize(cdone[(size_t)p.slot]) != hipSuccess) {
+                writer_fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
+                break;
+            }
+            // the per-window check: what the copy pass stored against what the scans counted, before a byte of the window leaves
+            if (h_ctl[8 + 2 * p.slot] || h_ctl[8 + 2 * p.slot + 1] != p.len) {
+                writer_fail(YACRD_EINTERNAL, "sequence editor: the copy pass stored other bytes than the plan counted");
+                break;
+            }
+            const double t0 = now_ms();
+            const char *base = S.wout[p.slot].as<char>();
+            if (!job.gzip) {
+                if (!writer_home(base, p.len)) break;
+                win_released.store(k + 1, std::memory_order_release);
+            } else {
+                // every whole block of the slot (the last window: its tail too, and the EOF member), batch by batch; the batch
+                // before comes home while this one is encoded — the last batch of a window while the next window's first is
+                const u64 whole = p.last ? p.len : p.len / ydf::kBlock * ydf::kBlock;
+                const size_t nb = (size_t)((whole + per - 1) / per) + (p.last && !whole ? 1u : 0u);
+                bool ok = true;
+                for (size_t b = 0; b < nb && ok; b++) {
+                    const u64 from = (u64)b * per, len = std::min(per, whole - from);
+                    ok = writer_encode(reinterpret_cast<const unsigned char *>(base) + from, len, p.last && b + 1 == nb, b + 1 == nb ? (long)k : -1);
+                    while (ok && gz_got + 1 < gz_sent) ok = writer_fetch();
+                }
+                if (!nb || p.last)
+                    while (ok && gz_got < gz_sent) ok = writer_fetch();
+                if (!ok) break;
+                if (!nb) win_released.store(k + 1, std::memory_order_release); // (nothing of this slot is the encoder's to read)
+            }
+            out_busy_ms += now_ms() - t0;
+        }
+        (void)hipStreamSynchronize(side[0]);
+        if (job.gzip) (void)hipStreamSynchronize(side[1]);
+    }
+
+    // window by window on this thread; the code of what it found, or the writer's
+    int windows_loop()
+    {
+        const u64 n_win = (n + W - 1) / W;
+        const size_t chunk = (size_t)std::min<u64>(kTextChunk, W);
+        const u32 w_tile = (u32)(W / yk::kGpTile);
+        static const char *const not_taken =
+            "a record that is not \"@name[ desc]\\nseq\\n+\\nqual\\n\", a cut position beyond its read or a region with begin > end: the host loop decides";
+        u64 carry = 0, tail = 0, tail_at = 0; // of the window before: its carry; its ragged output tail and where it lies in its slot
+        u64 sum_rec = 0, sum_pieces = 0, sum_total = 0, max_carry = 0;
+        double text_ms = 0;
+        for (u64 k = 0; k < n_win; k++) {
+            if (win_stop.load()) return YACRD_OK; // (the writer's code: run_windows)
+            const bool last = k + 1 == n_win;
+            const int ts = (int)(k & 1), os = (int)(k & 1);
+            const u64 n_new = std::min(W, n - k * W), lo = W - carry, hi = W + n_new;
+            const u32 t_lo = (u32)(lo / yk::kGpTile), t_hi = (u32)((hi + yk::kGpTile - 1) / yk::kGpTile);
+            unsigned long long *ctl = S.ctl.as<unsigned long long>() + 8 * (k & 3);
+            char *slot = S.wtext[ts].as<char>();
+            HIP_TRY(hipMemsetAsync(ctl, 0, 64, e->stream));
+            HIP_TRY(hipMemsetAsync(slot + hi, 0, 64, e->stream));
+            ga.text = reinterpret_cast<const unsigned char *>(slot), ga.n = hi, ga.lo = lo, ga.ctl = ctl;
+            ga.raw = nullptr, ga.out0 = 0, ga.piece0 = 0;
+            bool ok = ev_open();
+            if (t_lo < w_tile) { // the carry's tiles
+                ga.avail = W, ga.tile0 = t_lo;
+                hipLaunchKernelGGL(yk::sq_lines_kernel, dim3(w_tile - t_lo), dim3(yk::kGpT), 0, e->stream, ga);
+            }
+            ok = ok && ev_close();
+            const double tm = now_ms();
+            const int moved = move_text(
+                e, src, k * W, n_new, slot + W, win_fresh[ts], job.n_threads,
+                [&](u64 seg_begin, u64 seg_end, u64 avail) {
+                    const bool end = seg_end >= n_new;
+                    const u32 t0 = w_tile + (u32)(seg_begin / yk::kGpTile), t1 = end ? t_hi : w_tile + (u32)(seg_end / yk::kGpTile);
+                    ga.avail = end ? hi : W + std::min<u64>(avail, seg_end); // (a tile of this segment reads nothing behind it)
+                    ga.tile0 = t0;
+                    ok = ok && ev_open();
+                    if (t1 > t0) hipLaunchKernelGGL(yk::sq_lines_kernel, dim3(t1 - t0), dim3(yk::kGpT), 0, e->stream, ga);
+                    ok = ok && ev_close();
+                },
+                chunk, &lanes);
+            win_fresh[ts] = false;
+            text_ms += now_ms() - tm;
+            if (moved == 2) return fail(YACRD_EINVAL, "read error in the sequence file");
+            if (moved == 3) return fail(YACRD_ENOMEM, "sequence text to HBM: no pinned memory");
+            if (moved || !ok) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
+            // the scan of the tiles' counts; the first wait: lines
+            ga.avail = hi;
+            ok = ev_open();
+            if (const int rc = scan_u32_to_u64(e, S.tile_nl.as<u32>() + t_lo, (u64)(t_hi - t_lo), S.tile_l0.as<u64>() + t_lo, S.part)) return rc;
+            ok = ok && ev_close();
+            if (const int rc = bring_words(ok, {S.tile_l0.as<u64>() + t_hi, ctl})) return rc;
+            n_lines = h_ctl[0];
+            if (h_ctl[1] & yk::kSqNeedHost) return fail(YACRD_EFALLBACK, "the text holds a CR: the host loop decides");
+            if (last && n_lines % 4) return fail(YACRD_EFALLBACK, "the line count is no multiple of four: the host loop decides");
+            n_rec = n_lines / 4;
+            // the window's tables (the engine's stream is empty: nothing reads the ones they replace)
+            HIP_TRY(S.line_end.reserve((size_t)(n_lines + 1) * sizeof(u64)));
+            HIP_TRY(S.rec_pieces.reserve((size_t)(n_rec + 1) * sizeof(u32)));
+            HIP_TRY(S.rec_bytes.reserve((size_t)(n_rec + 1) * sizeof(u32)));
+            HIP_TRY(S.piece_off.reserve((size_t)(n_rec + 2) * sizeof(u64)));
+            HIP_TRY(S.byte_off.reserve((size_t)(n_rec + 2) * sizeof(u64)));
+            ga.line_end = S.line_end.as<u64>(), ga.n_lines = n_lines, ga.n_rec = n_rec;
+            ga.rec_pieces = S.rec_pieces.as<u32>(), ga.rec_bytes = S.rec_bytes.as<u32>();
+            ga.piece_off = S.piece_off.as<u64>(), ga.byte_off = S.byte_off.as<u64>();
+            ga.tile0 = t_lo;
+            ok = ev_open();
+            hipLaunchKernelGGL(yk::sq_index_kernel, dim3(t_hi - t_lo), dim3(yk::kGpT), 0, e->stream, ga);
+            if (!last) { // (the last window: its lines are whole records and its last byte is a newline — nothing is left)
+                yk::SqCarry c{ga.line_end, n_rec, lo, hi, W, ga.text, S.wtext[ts ^ 1].as<unsigned char>(), ctl};
+                hipLaunchKernelGGL(yk::sq_carry_kernel, dim3(64), dim3(256), 0, e->stream, c);
+            }
+            launch_plan<yk::Fastq, false>();
+            if (const int rc = scan_u32_to_u64(e, ga.rec_pieces, n_rec, S.piece_off.as<u64>(), S.part)) return rc;
+            if (const int rc = scan_u32_to_u64(e, ga.rec_bytes, n_rec, S.byte_off.as<u64>(), S.part)) return rc;
+            ok = ok && ev_close();
+            // the second wait: pieces, bytes, status, carry
+            if (const int rc = bring_words(ok, {S.piece_off.as<u64>() + n_rec, S.byte_off.as<u64>() + n_rec, ctl, ctl + 2})) return rc;
+            const u64 w_pieces = h_ctl[0], w_total = h_ctl[1];
+            if (h_ctl[2] & yk::kSqCarryLong) return fail(YACRD_EFALLBACK, "a record longer than a window: the host loop's case");
+            if (h_ctl[2] & yk::kSqNeedHost) return fail(YACRD_EFALLBACK, not_taken);
+            carry = last ? 0 : h_ctl[3];
+            max_carry = std::max(max_carry, carry);
+            // the output slot: the writer has let go of what window k - 2 left in it
+            while (k >= 2 && win_released.load(std::memory_order_acquire) < k - 1 && !win_stop.load()) {
+                struct timespec tsl = {0, 20000};
+                nanosleep(&tsl, nullptr);
+            }
+            if (win_stop.load()) return YACRD_OK;
+            const u64 raw = job.gzip ? tail : 0, len = raw + w_total;
+            if (w_pieces + 1 >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "more output records than the device editor numbers");
+            HIP_TRY(S.wout[os].reserve((size_t)((len + 15) & ~(u64)15) + 64));
+            HIP_TRY(S.pieces.reserve((size_t)(w_pieces + 2) * sizeof(yk::SqPiece)));
+            ga.pieces = S.pieces.as<yk::SqPiece>(), ga.out = S.wout[os].as<unsigned char>();
+            ga.n_pieces = w_pieces + (raw ? 1 : 0), ga.total = len;
+            ga.raw = S.wout[os ^ 1].as<unsigned char>(), ga.out0 = raw, ga.piece0 = raw ? 1u : 0u;
+            if (raw) { // piece 0: the tail of the window before, where it lies in that window's slot
+                yk::SqPiece *p0 = reinterpret_cast<yk::SqPiece *>(const_cast<u64 *>(h_ctl + 12)) + os; // (pinned; window k - 2's copy has ended)
+                *p0 = yk::SqPiece{};
+                p0->out = 0, p0->rec = tail_at, p0->len = (u32)raw, p0->flags = yk::kSqRaw;
+                HIP_TRY(hipMemcpyAsync(ga.pieces, p0, sizeof *p0, hipMemcpyHostToDevice, e->stream));
+            }
+            ok = ev_open();
+            if (len) {
+                launch_plan<yk::Fastq, true>();
+                hipLaunchKernelGGL(yk::seq_copy_kernel<yk::Fastq>, dim3((u32)((len + yk::kSqOutTile - 1) / yk::kSqOutTile)), dim3(yk::kGpT), 0, e->stream, ga);
+            }
+            ok = ok && ev_close();
+            HIP_TRY(hipMemcpyAsync((void *)(h_ctl + 8 + 2 * os), ctl, 2 * sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipEventRecord(cdone[(size_t)os], e->stream));
+            if (!ok) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
+            {
+                std::lock_guard<std::mutex> g(win_mu);
+                win_posted.push_back(WinPost{os, len, last});
+            }
+            win_n_posted.store((size_t)k + 1, std::memory_order_release);
+            tail_at = last ? 0 : len / ydf::kBlock * ydf::kBlock, tail = job.gzip ? len - tail_at : 0;
+            sum_rec += n_rec, sum_pieces += w_pieces, sum_total += w_total;
+        }
+        n_rec = sum_rec, n_pieces = sum_pieces, total = sum_total;
+        win_count = n_win, win_max_carry = max_carry, win_text_ms = text_ms;
+        return YACRD_OK;
+    }
+
+    bool win_fresh[2] = {false, false}; // a text slot that is a new allocation fills faster by copy kernel, once
+    double win_text_ms = 0;
+    u64 win_count = 0, win_max_carry = 0;
+
+    // the ring, the writer thread, the windows; then what the two threads found
+    int run_windows()
+    {
+        for (int i = 0; i < 2; i++) {
+            const void *before = S.wtext[i].p;
+            HIP_TRY(S.wtext[i].reserve((size_t)(2 * W + 64)));
+            win_fresh[i] = S.wtext[i].p != before;
+            HIP_TRY(S.wout[i].reserve(64));
+        }
+        if (!cdone.add(2, hipEventDisableTiming)) HIP_TRY(why_not_added());
+        if (job.gzip) {
+            if (const int rcg = gzip_device_open(e, std::min<u64>(kGzBatchBlocks, 2 * W / ydf::kBlock + 2), &gz)) return rcg;
+            gz_hold.e = e;
+            HIP_TRY(hipStreamSynchronize(e->stream)); // (gzip_device_open's memset)
+        }
+        std::thread wt([this] { window_writer(); });
+        int rc = windows_loop();
+        if (rc != YACRD_OK) win_stop = 1;
+        win_no_more = true;
+        wt.join();
+        (void)hipStreamSynchronize(e->stream);
+        if (rc == YACRD_OK && w_rc != YACRD_OK) rc = fail(w_rc, w_msg);
+        if (rc != YACRD_OK) return rc;
+        if ((job.gzip ? gz_got != gz_sent : sink.at != total)) return fail(YACRD_EINTERNAL, "sequence editor: fewer bytes written than counted");
+        for (size_t b = 0; b < gz_sent; b++) gz_kernel_ms += ev_ms(gev[2 * b], gev[2 * b + 1]);
+        e->seq_windows[0] = win_count, e->seq_windows[1] = win_max_carry;
+        e->seq_windows[2] = S.wtext[0].cap + S.wtext[1].cap, e->seq_windows[3] = S.wout[0].cap + S.wout[1].cap;
+        fill_gzip_stats(job.gzip_stats, total, sink.at, gz_members, gz_stored, gz_kernel_ms, out_busy_ms, put_ms);
+        if (stats) {
+            stats->text_bytes = n, stats->out_bytes = total, stats->n_records = n_rec, stats->n_out_records = n_pieces;
+            stats->text_ms = (float)win_text_ms, stats->table_ms = (float)(t_table - t_start);
+            float km = 0;
+            for (size_t i = 0; i + 1 < n_ev; i += 2) km += ev_ms(ev[i], ev[i + 1]);
+            stats->kernel_ms = km, stats->out_ms = (float)out_busy_ms;
+        }
+        return YACRD_OK;
+    }
+
     int deliver()
     {
         const double t0 = now_ms();
@@ -1101,17 +1483,39 @@ int run_seq_edit(yacrd_engine *e, const SeqJob &job, const TextSource &src, u64 
     DeviceGuard guard(e->device);
     SeqEditScratch *S = scratch_of<SeqEditScratch>(e);
     if (!S) return fail(YACRD_ENOMEM, "host allocation failed");
+    // The route.  FASTQ with its text in a file or in host memory runs in windows when the text is longer than a
+    // window and either the switch names a window or the whole-text run finds no room; every other text runs whole.
+    const u64 sw = e->seq_window;
+    for (u64 &w : e->seq_windows) w = 0;
+    const bool may_window = !job.fasta && !job.bgzf && sw != UINT64_MAX;
+    const u64 W = sw == 0 || sw == UINT64_MAX ? (u64)(kTextChunk * kTextSeg) : (sw + yk::kGpTile - 1) / yk::kGpTile * yk::kGpTile;
+    bool windows = may_window && n > W && (sw != 0 || kSeqWindowsWhenFits);
+    auto finish = [&](SeqRun &r, int rc) {
+        (void)hipStreamSynchronize(e->stream); // (whatever failed: nothing of this call is in flight when its events go)
+        for (hipStream_t s : r.side.v) (void)hipStreamSynchronize(s);
+        (void)hipGetLastError();
+        return rc;
+    };
+    if (!windows) {
+        SeqRun r{e, job, src, n, sink, stats, *S};
+        int rc = r.plan();
+        if (rc == YACRD_OK) rc = r.upload_table();
+        if (rc == YACRD_OK) rc = r.move_and_count();
+        if (rc == YACRD_OK) rc = r.size_output();
+        if (rc == YACRD_OK) rc = r.gather();
+        if (rc == YACRD_OK) rc = r.deliver();
+        rc = finish(r, rc);
+        // no room: nothing has left the device yet, and what the run holds goes before the windows take their ring
+        if (!(rc == YACRD_EFALLBACK && r.room_failed && may_window && n > W)) return rc;
+        windows = true;
+    }
+    S->text.release(), S->out.release(); // (the whole-text run's: the ring is what a run in windows holds)
     SeqRun r{e, job, src, n, sink, stats, *S};
+    r.W = W;
     int rc = r.plan();
     if (rc == YACRD_OK) rc = r.upload_table();
-    if (rc == YACRD_OK) rc = r.move_and_count();
-    if (rc == YACRD_OK) rc = r.size_output();
-    if (rc == YACRD_OK) rc = r.gather();
-    if (rc == YACRD_OK) rc = r.deliver();
-    (void)hipStreamSynchronize(e->stream); // (whatever failed: nothing of this call is in flight when its events go)
-    for (hipStream_t s : r.side.v) (void)hipStreamSynchronize(s);
-    (void)hipGetLastError();
-    return rc;
+    if (rc == YACRD_OK) rc = r.run_windows();
+    return finish(r, rc);
 }
 
 int seq_edit_args(bool fasta, yacrd_engine *e, int op, const yacrd_report_table *t, yacrd_seq_edit_stats *st)
@@ -1250,6 +1654,17 @@ int edit_seq_gzip_file(bool fasta, yacrd_engine *e, int op, const char *text, ui
 } // namespace
 
 extern "C" {
+
+int yacrd_debug_seq_window(yacrd_engine *e, uint64_t window_bytes)
+{
+    if (!e) return fail(YACRD_EINVAL, "null argument");
+    e->seq_window = window_bytes;
+    return YACRD_OK;
+}
+void yacrd_debug_seq_windows(const yacrd_engine *e, uint64_t out[4])
+{
+    for (int i = 0; i < 4; i++) out[i] = e ? e->seq_windows[i] : 0;
+}
 
 int yacrd_engine_edit_fastq(yacrd_engine *e, int op, const char *in_path, const char *out_path, int n_threads, const yacrd_report_table *t,
                             yacrd_seq_edit_stats *st)

@@ -218,11 +218,16 @@ static_assert(kTextChunk % yk::kGpTile == 0, "segments begin on tile boundaries"
 // may lie beyond n — for every kTextSeg chunks as soon as they and the chunk behind them have landed (`avail`: the bytes
 // [0, avail) have), with the engine's stream made to wait for those chunks' copy events: what on_segment launches on
 // e->stream sees the text, the host waits for nothing.  Returns 0, 1 (a HIP call failed), 2 (read error) or 3 (no pinned memory).
+// `chunk`: what one pread and one copy move, a multiple of the tile and at most kTextChunk (the sequence editor's windows may
+// be smaller than a chunk: gpu_seq_edit.hip).  `lanes`: copy streams the caller keeps between calls (a run that moves its text
+// in many calls makes them once); without it the call makes its own and destroys them.
 template <class OnSegment>
-int move_text(yacrd_engine *e, const TextSource &src, u64 begin, u64 n, char *mirror, bool blit, int n_threads, OnSegment &&on_segment)
+int move_text(yacrd_engine *e, const TextSource &src, u64 begin, u64 n, char *mirror, bool blit, int n_threads, OnSegment &&on_segment,
+              size_t chunk = kTextChunk, Streams *lanes = nullptr)
 {
     // (the pinned arena stays with the engine: pinning 100 MB costs more than moving 367 MB through it)
-    constexpr size_t kChunk = kTextChunk, kSeg = kTextSeg;
+    const size_t kChunk = chunk;
+    constexpr size_t kSeg = kTextSeg;
     const size_t n_chunks = (size_t)((n + kChunk - 1) / kChunk);
     unsigned T = n_threads > 0 ? (unsigned)n_threads : 6u; // (more threads only get in each other's way: 367 MB in 10 ms with 4-8)
     T = (unsigned)std::max<size_t>(1, std::min<size_t>(std::min(T, 32u), std::max<size_t>(n_chunks, 1)));
@@ -230,12 +235,13 @@ int move_text(yacrd_engine *e, const TextSource &src, u64 begin, u64 n, char *mi
     if (e->paf_arena.reserve(n_buf * kChunk) != hipSuccess) return 3;
     char *arena = e->paf_arena.as<char>();
     Events ev; // one per chunk: recorded behind its copy
-    Streams copy;
+    Streams own;
+    Streams &copy = lanes ? *lanes : own;
     std::unique_ptr<std::atomic<int>[]> landed(new std::atomic<int>[n_chunks + 1]);
     for (size_t c = 0; c <= n_chunks; c++) landed[c].store(0);
     std::atomic<size_t> next(0);
     std::atomic<int> bad(0);
-    if (!copy.add(T) || !ev.add(n_chunks, hipEventDisableTiming)) bad = 1;
+    if ((copy.v.size() < T && !copy.add(T - copy.v.size())) || !ev.add(n_chunks, hipEventDisableTiming)) bad = 1;
     auto work = [&](unsigned t) { // thread t owns buffers 2t and 2t + 1: one fills while the other flies
         if (hipSetDevice(e->device) != hipSuccess) bad = 1;
         long prev[2] = {-1, -1}; // the chunk that last flew from each buffer
@@ -280,8 +286,8 @@ int move_text(yacrd_engine *e, const TextSource &src, u64 begin, u64 n, char *mi
         if (bad.load()) break;
         on_segment((u64)c0 * kChunk, (u64)c1 * kChunk, std::min<u64>(n, (u64)need * kChunk));
     }
-    for (auto &x : th) x.join();
-    copy.clear();
+    for (auto &x : th) x.join(); // (every thread has waited for its stream)
+    own.clear();
     if (bad.load()) (void)hipStreamSynchronize(e->stream); // (kernels may still wait on events about to go, with `ev`)
     (void)hipGetLastError();
     return bad.load();

@@ -23,6 +23,7 @@
 #include <unistd.h>
 
 #include "../../../include/yacrd_engine.h"
+#include "../../../include/yacrd_engine_debug.h" // (YACRD_SEQ_WINDOW: the FASTQ editor's window, an A/B and test switch)
 #include "../../../include/yacrd_host.h"
 
 namespace {
@@ -550,6 +551,9 @@ int main(int argc, char **argv)
             yacrd_gunzip_stats us{};
             double inflate_ms = 0;
             bool text_reused = false, dev_inflate = false;
+            // YACRD_SEQ_WINDOW=<bytes>: the FASTQ editor's window (yacrd_debug_seq_window; A/B and tests, like YACRD_NO_DEVICE_EDITOR)
+            if (const char *sw = std::getenv("YACRD_SEQ_WINDOW"))
+                if (*sw) (void)yacrd_debug_seq_window(engines[0], std::strtoull(sw, nullptr, 10));
             if (sub_comp == 1) {
                 const auto t_in = std::chrono::steady_clock::now();
                 yacrd_text own{};
@@ -599,10 +603,12 @@ int main(int argc, char **argv)
             }
             if (dev_edit != YACRD_OK && dev_edit != YACRD_EFALLBACK) die(yacrd_last_error());
             if (dev_edit == YACRD_OK && timing) {
+                uint64_t sw4[4] = {0, 0, 0, 0}; // (how the edit ran: its windows, 0 for the whole text at once)
+                yacrd_debug_seq_windows(engines[0], sw4);
                 std::fprintf(stderr, "[info] device %s editor: %llu records -> %llu, %llu bytes -> %llu bytes, text %.1f ms, table %.1f ms, "
-                                     "kernels %.1f ms, out %.1f ms\n",
+                                     "kernels %.1f ms, out %.1f ms, windows=%llu\n",
                              sub_fmt, (unsigned long long)ss.n_records, (unsigned long long)ss.n_out_records, (unsigned long long)ss.text_bytes,
-                             (unsigned long long)ss.out_bytes, ss.text_ms, ss.table_ms, ss.kernel_ms, ss.out_ms);
+                             (unsigned long long)ss.out_bytes, ss.text_ms, ss.table_ms, ss.kernel_ms, ss.out_ms, (unsigned long long)sw4[0]);
                 if (dev_inflate)
                     print_device_inflate(us);
                 if (sub_comp == 1) // (the encoder's line as the host loop's writer words it: the output lay in HBM, nothing went up)

@@ -37,6 +37,7 @@ F_NO_SCREEN_DIRECT = 16777216  # ... never (A/B)
 DEBUG_SYMBOLS = [
     "yacrd_debug_sort_pairs", "yacrd_debug_last_counters", "yacrd_debug_last_input_csr", "yacrd_debug_peer_copy_counts",
     "yacrd_debug_live_bytes", "yacrd_debug_direct_runs", "yacrd_debug_big_routes",
+    "yacrd_debug_seq_window", "yacrd_debug_seq_windows",
 ]
 F_ONE_LAUNCH = 4194304  # include/yacrd_engine.h: a short batch as ONE kernel launch (csrc/one_batch.h)
 
@@ -803,6 +804,23 @@ class Engine:
         self._lib.yacrd_debug_big_routes.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         self._lib.yacrd_debug_big_routes(self._h, out)
         return tuple(int(v) for v in out)
+
+    def debug_seq_window(self, window_bytes):
+        """yacrd_debug_seq_window (tests, A/B): the FASTQ editor's window.  0: the policy (128 MiB windows where the whole text
+        finds no room); 2**64 - 1: never windows; any other value: rounded up to a 32 KiB tile, and every FASTQ text longer
+        than it is edited window by window (csrc/gpu_seq_edit.hip: run_windows).  The bytes written do not depend on it."""
+        self._lib.yacrd_debug_seq_window.restype = ctypes.c_int
+        self._lib.yacrd_debug_seq_window.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
+        _check(self._lib, self._lib.yacrd_debug_seq_window(self._h, int(window_bytes)))
+
+    def seq_windows(self):
+        """yacrd_debug_seq_windows (tests, tools): what the last sequence edit ran as: its windows (0: the whole text at
+        once), the longest carry in bytes, the device bytes of its text ring and of its output ring."""
+        out = (ctypes.c_uint64 * 4)()
+        self._lib.yacrd_debug_seq_windows.restype = None
+        self._lib.yacrd_debug_seq_windows.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._lib.yacrd_debug_seq_windows(self._h, out)
+        return dict(zip(("windows", "max_carry", "text_ring_bytes", "out_ring_bytes"), (int(v) for v in out)))
 
     def _type_table(self, names, read_type):
         """(names, read_type) -> a yacrd_type_table and what keeps its memory alive; names: str or bytes, one per read."""
