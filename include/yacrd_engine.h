@@ -650,8 +650,8 @@ int yacrd_engine_write_report_mem(yacrd_engine *e, const yacrd_report_table *t /
  * buffers: DESIGN 7k), with the same bytes; what is left of it is a single record of more than 128 MiB ("a record longer
  * than a window"), and the ring itself not fitting.  In windows a cause may be found after earlier windows' output has
  * left the device: the file beside out_path is then dropped, the _mem buffer freed, the stats zeroed — nothing written,
- * nothing left beside out_path, as before.  (The BGZF-in forms below and FASTA hold text and output in HBM whole, and say
- * YACRD_EFALLBACK when they do not fit.)  The caller then runs yacrd_edit_file, which owns the syntax, the
+ * nothing left beside out_path, as before.  (The BGZF-in forms below hold text and output in HBM whole, and say
+ * YACRD_EFALLBACK when they do not fit; FASTA runs in windows like FASTQ: DESIGN 7l.)  The caller then runs yacrd_edit_file, which owns the syntax, the
  * codecs and the messages.  An empty text is an empty output.
  * In windows the stats' counts and bytes are sums over the windows, kernel_ms the sum of the windows' event pairs, text_ms the
  * time this thread spent landing windows, out_ms the writer thread's busy time.
@@ -708,7 +708,10 @@ int yacrd_engine_edit_fastq_bgzf_file(yacrd_engine *e, int op, const char *bgzf,
  * writes them back); a cut position beyond the record's sequence or a region with begin > end; 2^31 records or output records;
  * a record, or a read's output, of 0xFF000000 bytes or more; to the file form a compressed or non-regular input, a name that
  * yacrd_edit_file would not take for FASTA (.fastq / .fq / .paf / .m4 / .mhap / .yacrd win over .fa) and an out_path that is
- * the input or no regular file; text, line tables (32 bytes a line) and output beyond the device's free memory.
+ * the input or no regular file.  Memory: a text that does not fit the device's free memory with its line tables (32 bytes a
+ * line) and its output is edited window by window, as for FASTQ above: a window completes the records in front
+ * of its last '>' line and hands the rest to the next; what is left is a record of more than 128 MiB ("a record longer than
+ * a window"), a ring or a window's tables that do not fit, and the BGZF-in forms, which hold text and output whole.
  * An empty text and a text of blank lines are an empty output. */
 int yacrd_engine_edit_fasta(yacrd_engine *e, int op, const char *in_path, const char *out_path, int n_threads,
                             const yacrd_report_table *t, yacrd_seq_edit_stats *st /* may be NULL */);

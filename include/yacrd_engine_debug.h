@@ -105,7 +105,7 @@ uint64_t yacrd_debug_direct_runs(const yacrd_engine *e);
  * After a missed class prediction the device-wide screen goes out twice: the final pass is reported, not the sum.  A
  * batch that ran as one launch (YACRD_F_ONE_LAUNCH) has no such reads: all four are 0. */
 void yacrd_debug_big_routes(const yacrd_engine *e, uint64_t out[4]);
-/* the FASTQ editor's windows (csrc/gpu_seq_edit.hip): yacrd_engine_edit_fastq, _mem, _gzip_mem and _gzip_file run a
+/* the sequence editors' windows (csrc/gpu_seq_edit.hip): yacrd_engine_edit_fastq / _fasta, _mem, _gzip_mem and _gzip_file run a
  * text of more than one window window by window, in a bounded ring of buffers; the bytes written do not depend on it.
  *   window_bytes == 0            the policy: a window of 128 MiB, taken where the whole-text run finds no room (and, if the
  *                                build's measured default says so, for every text of more than one window);

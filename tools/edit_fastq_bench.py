@@ -16,10 +16,11 @@ output is compared with the parent's (gzip: the inflated bytes when the streams 
 appended to --json (default profiles/edit_fastq.json).
 --fasta: the same reads as FASTA, 80 bases a line (reads.fasta[.gz]): the device path is yacrd_engine_edit_fasta, its line
 "[info] device fasta editor:", the default --json profiles/edit_fasta.json.
---window BYTES: the FASTQ editor's windows against its whole-text run, in the same call: the "new" series runs
+--window BYTES: the editor's windows (with --fasta 7l) against its whole-text run, in the same call: the "new" series runs
 with YACRD_SEQ_WINDOW=18446744073709551615 (never windows), a third series "windowed" with YACRD_SEQ_WINDOW=BYTES; its output
 is compared with the parent's too, and the row says whether the windowed run's slowest `edit` is ahead of the whole-text
-run's fastest (the rule for the default).  The default --json is then profiles/edit_fastq_windows.json.
+run's fastest (the rule for the default).  The default --json is then profiles/edit_fastq_windows.json, with --fasta
+profiles/edit_fasta_windows.json.
 --parent-again: a second series of the parent behind the new one ("parent_again" in the row): what drifted meanwhile shows.
 Where the parent has a device editor too, the figure to compare is the `kernels ... ms` of the info lines, not the stage."""
 import argparse, gzip, json, os, re, subprocess, sys, time

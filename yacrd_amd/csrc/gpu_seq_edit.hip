@@ -28,8 +28,8 @@
 //            with aligned 4-byte loads (neighbouring lanes read neighbouring words) — and the tile is stored with 16-byte stores;
 //            the bytes stored are counted, a total that differs from the scan's is YACRD_EINTERNAL
 // In the whole-text run index, plan, pieces and copy wait for the last segment of text, and the text and the whole output lie in
-// HBM.  A FASTQ of more than one window whose text comes from a file or from host memory may instead run WINDOW BY WINDOW
-// (SeqRun::run_windows): the same kernels on bytes [lo, hi) of a text slot, a carry kernel between windows, two
+// HBM.  A FASTQ or FASTA of more than one window whose text comes from a file or from host memory may instead run WINDOW BY
+// WINDOW (SeqRun::run_windows): the same kernels on bytes [lo, hi) of a text slot, a carry kernel between windows, two
 // text slots and two output slots, a writer thread on the way out; always where the whole text finds no room.
 // What the path does not take — a CR, a line count that is no multiple of four, a header without '@' or without a name, a
 // "@name \n", a '+' line that is not bare, sequence and quality of different lengths, a cut position beyond the read, a region
@@ -94,20 +94,20 @@ struct SeqArgs { // what the kernels of both formats read; SqArgs and FaArgs (be
     unsigned char *out;
     unsigned long long *ctl; // [0] status, [1] bytes the copy pass stored
     u32 op;
+    u64 lo;    // the text's first byte: 0, or where a window's carry begins in its slot (what lies below is stale)
+    // a window of a gzip run (run_windows): piece 0 is `out0` bytes at `raw`, the records' pieces and bytes lie behind it
+    const unsigned char *raw;
+    u64 out0;   // bytes of the output slot in front of the first record's
+    u32 piece0; // pieces in front of the first record's (0 or 1)
 };
 
 struct SqArgs : SeqArgs {
     u64 n;     // bytes of text
     u64 avail; // bytes [0, avail) have landed (== n for the last segment)
-    u64 lo;    // the text's first byte: 0, or where a window's carry begins in its slot (what lies below is stale)
     u32 *tile_nl;        // per text tile: its newlines
     const u64 *tile_l0;  // their exclusive scan
     u32 tile0;           // the launch's first text tile
     SqPiece *pieces;
-    // a window of a gzip run (run_windows): piece 0 is `out0` bytes at `raw`, the records' pieces and bytes lie behind it
-    const unsigned char *raw;
-    u64 out0;   // bytes of the output slot in front of the first record's
-    u32 piece0; // pieces in front of the first record's (0 or 1)
 };
 static_assert(std::is_trivially_copyable<SqArgs>::value, "a kernel argument by value");
 
@@ -285,7 +285,8 @@ __device__ __forceinline__ u32 sq_load4(const unsigned char *src)
 }
 
 // ---- carry: what a window leaves behind its last whole record -> the front of the next window's slot ---------------------------
-// Window k's text is bytes [lo, hi) of its slot; its n_rec whole records end at line_end[4 n_rec - 1].  The bytes behind them,
+// Window k's text is bytes [lo, hi) of its slot; its n_rec whole records end at line_end[4 n_rec - 1] (FASTQ; FASTA: in front
+// of the window's last header line, fa_carry_kernel).  The bytes behind them,
 // [cb, hi), are moved to end at offset W of the next slot — in front of the new bytes, which land at W whatever the carry's
 // length turns out to be.  Every thread reads cb itself; thread 0 reports the length and sets kSqCarryLong when the carry
 // area (W bytes) does not hold it: nothing is moved then.  The destination's end is 16-byte aligned, so the move is whole
@@ -299,9 +300,9 @@ struct SqCarry {
     unsigned char *dst;       // the next window's
     unsigned long long *ctl;  // [0] status, [2] the carry's bytes
 };
-__global__ __launch_bounds__(256) void sq_carry_kernel(SqCarry c)
+// the move, from the carry's first byte on: the format's kernel says where that is
+__device__ __forceinline__ void sq_carry_from(const SqCarry &c, const u64 cb)
 {
-    const u64 cb = c.n_rec ? c.line_end[4 * c.n_rec - 1] + 1 : c.lo;
     const u64 len = c.hi - cb;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         c.ctl[2] = len;
@@ -323,6 +324,7 @@ __global__ __launch_bounds__(256) void sq_carry_kernel(SqCarry c)
         *reinterpret_cast<uint4 *>(c.dst + o) = v;
     }
 }
+__global__ __launch_bounds__(256) void sq_carry_kernel(SqCarry c) { sq_carry_from(c, c.n_rec ? c.line_end[4 * c.n_rec - 1] + 1 : c.lo); }
 
 // the composed tile -> the output, 16 bytes per thread; the bytes the workgroup composed -> ctl[1], one add per workgroup
 __device__ __forceinline__ void sq_store_tile(unsigned char *out, u64 total, unsigned long long *ctl, const u32 *tile, u32 *sw, u64 tile0, u32 stored)
@@ -446,6 +448,13 @@ struct Fastq {
         });
     }
 
+    static SqPiece raw_piece(u64 at, u32 len) // (host) `len` bytes at `at` of SeqArgs::raw, first in the output
+    {
+        SqPiece p{};
+        p.rec = at, p.len = len, p.flags = kSqRaw;
+        return p;
+    }
+
     static __device__ __forceinline__ void at(const SqArgs &a, const SqPiece &p, u32 k, Cursor &, const unsigned char *&src, u32 &rem, u32 &lit)
     {
         const unsigned char *rec = (p.flags & kSqRaw ? a.raw : a.text) + p.rec;
@@ -514,15 +523,22 @@ struct Fastq {
 //            base_before is not beyond that base holds it.  A thread keeps the line it last read from, tries the one behind
 //            it and searches what is left of the record otherwise (a walk forward from the tile's first search measured
 //            slower: 3.22 against 2.93 ms); a record whose lines all have one width is addressed without the tables (fa_widths_kernel)
+// In a window (run_windows) "the text" is the bytes of a slot from a.lo on and every table is the window's own: lines,
+// ordinals and bases count from a.lo.  A window that is not the last has H header lines among its whole lines and completes
+// n_rec = max(H - 1, 0) records: nothing in it says that the byte behind it is a '>', so its last record waits for the next
+// window (fa_carry_kernel), and the kernels leave the lines of that record alone.  One thing can say so: a partial last line
+// that begins with '>' (fa_mark_kernel reports it).  Then all H records are whole and only that line waits — without this a
+// record of exactly a window's bytes with a '>' behind it would make a carry of more than a window, and "a record of at most
+// a window is always taken" would not hold.
 constexpr u32 kFaWidth = 80; // noodles::fasta::Writer's line
 
 struct FaPiece { // one record of the output
     u64 out;     // where its first byte goes
-    u64 hdr;     // the input record's '>'
-    u64 base0;   // the ordinal, in the whole text, of the record's first base
+    u64 hdr;     // the input record's '>'; kSqRaw: where the bytes lie in FaArgs::raw
+    u64 base0;   // the ordinal, in the text (a window: from its first byte), of the record's first base
     u64 line0, line1; // the record's lines behind its header
     u32 len;     // its bytes
-    u32 flags;   // kSqCopy: the whole record with its description; else the piece [p0, p1) named name_p0_p1
+    u32 flags;   // kSqCopy: the whole record with its description; kSqRaw: bytes [hdr, hdr + len) of `raw`; else the piece [p0, p1) named name_p0_p1
     u32 name_len, desc_len;
     u32 p0, p1;
     u32 width;   // every line of the record but the last holds this many bases, the last 1 to `width`; 0: its lines differ
@@ -534,9 +550,11 @@ struct FaArgs : SeqArgs {
     u32 *head, *bases;      // [n_lines]
     const u64 *line_rec;    // [n_lines + 1]: headers in front of line g
     const u64 *base_before; // [n_lines + 1]
-    u64 *rec_line;          // [n_rec + 1]: the line of header r; n_lines closes the list
+    u64 *rec_line;          // [n_rec + 1]: the line of header r; n_lines closes the list, or the line of header n_rec (n_head > n_rec)
     u32 *rec_width;         // [n_rec]: the one width of the record's lines, or 0 (fa_widths_kernel)
     FaPiece *pieces;
+    u64 n_head;             // header lines: n_rec, or n_rec + 1 in a window whose last record waits
+    u64 hi;                 // a window that is not the last: its end in the slot (mark: is there a partial line behind the last newline); else 0
 };
 static_assert(std::is_trivially_copyable<FaArgs>::value, "a kernel argument by value");
 
@@ -545,11 +563,13 @@ __global__ __launch_bounds__(256) void fa_mark_kernel(FaArgs a)
     const u64 g = (u64)blockIdx.x * 256u + threadIdx.x;
     u32 status = 0;
     if (g < a.n_lines) {
-        const u64 s = g ? a.line_end[g - 1] + 1 : 0, len = a.line_end[g] - s;
+        const u64 s = g ? a.line_end[g - 1] + 1 : a.lo, len = a.line_end[g] - s;
         const bool head = len && a.text[s] == '>';
         if (len >= kSqMaxRecord) status = kSqNeedHost;
         a.head[g] = head ? 1u : 0u;
         a.bases[g] = head || status ? 0u : (u32)len;
+        // a window: the partial line behind its last newline begins with '>' -> ctl[3] (zeroed with the window's words)
+        if (g + 1 == a.n_lines && a.line_end[g] + 1 < a.hi && a.text[a.line_end[g] + 1] == '>') a.ctl[3] = 1ull;
     }
     seq_status(a.ctl, status);
 }
@@ -560,12 +580,29 @@ __global__ __launch_bounds__(256) void fa_heads_kernel(FaArgs a)
     u32 status = 0;
     if (g < a.n_lines) {
         if (a.head[g]) {
-            a.rec_line[a.line_rec[g]] = g;
-            a.rec_width[a.line_rec[g]] = g + 1 < a.n_lines && !a.head[g + 1] ? a.bases[g + 1] : 0u; // (its first line's; fa_widths_kernel)
-        } else if (a.bases[g] && a.line_rec[g] == 0) status = kSqNeedHost; // bases in front of the first header
-        if (g == 0) a.rec_line[a.n_rec] = a.n_lines;
+            // header n_rec (a window that is not the last): the record that waits; its line closes the list, it has no width
+            const u64 r = a.line_rec[g];
+            if (r <= a.n_rec) a.rec_line[r] = g;
+            if (r < a.n_rec) a.rec_width[r] = g + 1 < a.n_lines && !a.head[g + 1] ? a.bases[g + 1] : 0u; // (its first line's; fa_widths_kernel)
+        } else if (a.bases[g] && a.line_rec[g] == 0) status = kSqNeedHost; // bases in front of the first header (a window behind
+                                                                           // one with a header begins with a header: never there)
+        if (g == 0 && a.n_head == a.n_rec) a.rec_line[a.n_rec] = a.n_lines; // (else header n_rec's thread writes this element)
     }
     seq_status(a.ctl, status);
+}
+
+// ---- carry, FASTA: from the window's last header line on; all of the window when it has none -------------------------------------
+// Runs behind fa_heads_kernel (rec_line[n_rec] is that header's line — or, where the partial last line is a header's and
+// every record is whole, n_lines: the carry is that line) and, like sq_carry_kernel, in front of nothing that overwrites
+// the slot.  A partial last line lies inside the carry whatever it holds.
+struct FaCarry : SqCarry {
+    const u64 *rec_line;
+    u64 n_head;
+};
+__global__ __launch_bounds__(256) void fa_carry_kernel(FaCarry c)
+{
+    const u64 l = c.n_head ? c.rec_line[c.n_rec] : 0; // (l >= 1 lines lie in front of it, or it is the window's first)
+    sq_carry_from(c, l ? c.line_end[l - 1] + 1 : c.lo);
 }
 
 // The one width of a record's lines, or 0: every line but the last holds as many bases as the first, the last 1 to as many,
@@ -577,7 +614,9 @@ __global__ __launch_bounds__(256) void fa_widths_kernel(FaArgs a)
 {
     const u64 g = (u64)blockIdx.x * 256u + threadIdx.x;
     if (g >= a.n_lines || a.head[g] || a.line_rec[g] == 0) return;
-    const u64 r = a.line_rec[g] - 1, l0 = a.rec_line[r], l1 = a.rec_line[r + 1];
+    const u64 r = a.line_rec[g] - 1;
+    if (r >= a.n_rec) return; // (a line of the record that waits for the next window: rec_line[r + 1], rec_width[r] are not there)
+    const u64 l0 = a.rec_line[r], l1 = a.rec_line[r + 1];
     const u32 w = a.bases[l0 + 1], n = a.bases[g]; // (l0 + 1 <= g: the record has this line)
     if (w == 0u || (g + 1 < l1 ? n != w : n == 0u || n > w)) a.rec_width[r] = 0u;
 }
@@ -624,7 +663,7 @@ struct Fasta {
     {
         const unsigned char *t = a.text;
         const u64 l0 = a.rec_line[r], l1 = a.rec_line[r + 1];
-        const u64 s = l0 ? a.line_end[l0 - 1] + 1 : 0, e0 = a.line_end[l0];
+        const u64 s = l0 ? a.line_end[l0 - 1] + 1 : a.lo, e0 = a.line_end[l0];
         if (!EMIT) a.rec_pieces[r] = 0u, a.rec_bytes[r] = 0u;
         if (a.line_end[l1 - 1] + 1 - s >= kSqMaxRecord) return kSqNeedHost;
         u64 sep = s + 1; // the name's end: the first blank, tab or form feed
@@ -644,8 +683,8 @@ struct Fasta {
             if (bytes >= kSqMaxRecord) return kSqNeedHost;
             if (!EMIT) a.rec_pieces[r] = 1u, a.rec_bytes[r] = (u32)bytes;
             else {
-                p.out = a.byte_off[r], p.len = (u32)bytes, p.flags = kSqCopy, p.desc_len = desc_len, p.p0 = 0u, p.p1 = seq_len;
-                a.pieces[a.piece_off[r]] = p;
+                p.out = a.out0 + a.byte_off[r], p.len = (u32)bytes, p.flags = kSqCopy, p.desc_len = desc_len, p.p0 = 0u, p.p1 = seq_len;
+                a.pieces[a.piece0 + a.piece_off[r]] = p;
             }
             return 0u;
         }
@@ -653,15 +692,26 @@ struct Fasta {
             const u32 L = p1 - p0;
             const u64 plen = 1ull + name_len + 2u + sq_digits(p0) + sq_digits(p1) + 1u + L + fa_rows(L);
             if (EMIT) {
-                p.out = a.byte_off[r] + at, p.len = (u32)plen, p.flags = 0u, p.desc_len = 0u, p.p0 = p0, p.p1 = p1;
-                a.pieces[a.piece_off[r] + k] = p;
+                p.out = a.out0 + a.byte_off[r] + at, p.len = (u32)plen, p.flags = 0u, p.desc_len = 0u, p.p0 = p0, p.p1 = p1;
+                a.pieces[a.piece0 + a.piece_off[r] + k] = p;
             }
             return plen;
         });
     }
 
+    static FaPiece raw_piece(u64 at, u32 len) // (host) `len` bytes at `at` of SeqArgs::raw, first in the output
+    {
+        FaPiece p{};
+        p.hdr = at, p.len = len, p.flags = kSqRaw;
+        return p;
+    }
+
     static __device__ __forceinline__ void at(const FaArgs &a, const FaPiece &p, u32 k, FaLine &ln, const unsigned char *&src, u32 &rem, u32 &lit)
     {
+        if (p.flags & kSqRaw) { // the output tail of the window before, as it lies in that window's slot
+            src = a.raw + p.hdr + k, rem = p.len - k;
+            return;
+        }
         const unsigned char *rec = a.text + p.hdr;
         src = nullptr, rem = 1, lit = '\n';
         if (k == 0) {
@@ -718,7 +768,7 @@ namespace {
 
 constexpr size_t kOutPiece = (size_t)4 << 20; // (_PIECE of the tests: what one copy home moves)
 constexpr u64 kGzBatchBlocks = 2048;          // blocks of 65 280 bytes per batch of the encoder
-// whether a FASTQ that fits whole runs in windows all the same (the switch aside): decided by measurement, DESIGN 7k
+// whether a text that fits whole runs in windows all the same (the switch aside): decided by measurement, DESIGN 7k, 7l
 constexpr bool kSeqWindowsWhenFits = false;
 
 struct SeqEditScratch { // the editor's buffers; they stay with the engine (grow-only), go with yacrd_engine_trim / destroy
@@ -783,12 +833,16 @@ struct SeqRun {
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return true; // (the reserves then say)
         return need * 1.125 + (double)((size_t)64 << 20) <= (double)free_b + held;
     }
-    bool room_failed = false; // the whole-text run found no room (run_seq_edit: a FASTQ of more than a window then runs in windows)
+    bool room_failed = false; // the whole-text run found no room (run_seq_edit: a text of more than a window then runs in windows)
     int no_room()
     {
         room_failed = true;
         return no_room_message();
     }
+    // (a window's tables: asked for only where a reserve would have to grow them)
+    static bool room_for(double need, double held) { return need <= held || fits(need, held); }
+    double held_line_tables() const { return (double)S.line_end.cap + (double)S.ln_head.cap + (double)S.ln_bases.cap + (double)S.ln_rec.cap + (double)S.base_before.cap; }
+    double held_record_tables() const { return (double)S.rec_line.cap + (double)S.rec_width.cap + (double)S.piece_off.cap + (double)S.byte_off.cap; }
     static int no_room_message() { return fail(YACRD_EFALLBACK, "the text and its output do not fit this device's free memory: the host loop streams them"); }
 
     bool ev_open()
@@ -850,9 +904,15 @@ struct SeqRun {
         t_start = now_ms();
         if (W) { // in windows: the ring's slots, two of text and two of output (sized for a window that goes out as it came in), and a window's tables
             n_tiles = (2 * W + yk::kGpTile - 1) / yk::kGpTile;
-            const double ring = 2.0 * (2.0 * (double)W + 64.0) + 2.0 * (double)W + (double)W * 0.25;
+            // FASTA: a window's tables too — 32 bytes a line; 36 bytes a record and 4 of rec_width —, here for the 2 W bytes a
+            // window may hold, wrapped at 60 columns (2 W / 61 lines) with a record every ten lines: per line 32 bytes and a tenth
+            // of a record's 40, the 4.0 below.  A window's own line and header counts decide when they are known (window_records:
+            // a text of shorter lines or records may find no room there)
+            const double fa_tables = job.fasta ? 2.0 * (double)W / 61.0 * (32.0 + 4.0) : 0.0;
+            const double ring = 2.0 * (2.0 * (double)W + 64.0) + 2.0 * (double)W + (double)W * 0.25 + fa_tables;
             const double held_w = (double)S.wtext[0].cap + (double)S.wtext[1].cap + (double)S.wout[0].cap + (double)S.wout[1].cap +
-                                  (double)S.table.names.cap + (double)S.table.slots.cap + (double)S.bad_reg.cap;
+                                  (double)S.table.names.cap + (double)S.table.slots.cap + (double)S.bad_reg.cap +
+                                  (job.fasta ? held_line_tables() + held_record_tables() : 0.0);
             if (!fits(ring + (double)name_bytes + (double)cap * 4.0 + (double)R * 21.0 + (double)G * 8.0, held_w)) return no_room_message();
             return YACRD_OK;
         }
@@ -877,7 +937,7 @@ struct SeqRun {
         HIP_TRY(S.tile_l0.reserve((size_t)(n_tiles + 2) * sizeof(u64)));
         HIP_TRY(S.ctl.reserve(4 * 64)); // (a run in windows: four windows' words in turn)
         HIP_TRY(hipMemsetAsync(S.ctl.p, 0, 4 * 64, e->stream));
-        HIP_TRY(S.pin.reserve(2 * kOutPiece + 12 * sizeof(u64) + 2 * sizeof(yk::SqPiece))); // (the raw pieces of two windows: run_windows)
+        HIP_TRY(S.pin.reserve(2 * kOutPiece + 12 * sizeof(u64) + 2 * sizeof(yk::FaPiece))); // (the raw pieces of two windows, of the larger kind: run_windows)
         h_ctl = reinterpret_cast<volatile u64 *>(S.pin.as<char>() + 2 * kOutPiece);
         for (int i = 0; i < 12; i++) h_ctl[i] = 0;
         if (!side.add(job.gzip ? 2 : 1) || !wev.add(2, hipEventDisableTiming) || !ev.add(2 * n_segs + 10)) HIP_TRY(why_not_added());
@@ -986,9 +1046,7 @@ struct SeqRun {
         if (!fits((double)n_lines * 8.0 + (double)n_rec * 24.0, (double)S.line_end.cap + (double)S.piece_off.cap + (double)S.byte_off.cap)) return no_room();
         HIP_TRY(S.line_end.reserve((size_t)(n_lines + 1) * sizeof(u64)));
         ga.line_end = S.line_end.as<u64>();
-        return size_records<yk::Fastq>([&] { launch_index(); },
-                                       "a record that is not \"@name[ desc]\\nseq\\n+\\nqual\\n\", a cut position beyond its read or a region with "
-                                       "begin > end: the host loop decides");
+        return size_records<yk::Fastq>([&] { launch_index(); });
     }
 
     // FASTA's front: index, mark and the two scans over the lines — how many records —, then heads and widths in the bracket of the plan
@@ -997,14 +1055,7 @@ struct SeqRun {
         const double line_tables = (double)n_lines * 32.0;
         if (!fits(line_tables, (double)S.line_end.cap + (double)S.ln_head.cap + (double)S.ln_bases.cap + (double)S.ln_rec.cap + (double)S.base_before.cap))
             return no_room();
-        HIP_TRY(S.line_end.reserve((size_t)(n_lines + 1) * sizeof(u64)));
-        HIP_TRY(S.ln_head.reserve((size_t)(n_lines + 1) * sizeof(u32)));
-        HIP_TRY(S.ln_bases.reserve((size_t)(n_lines + 1) * sizeof(u32)));
-        HIP_TRY(S.ln_rec.reserve((size_t)(n_lines + 2) * sizeof(u64)));
-        HIP_TRY(S.base_before.reserve((size_t)(n_lines + 2) * sizeof(u64)));
-        ga.line_end = S.line_end.as<u64>();
-        fa.head = S.ln_head.as<u32>(), fa.bases = S.ln_bases.as<u32>();
-        fa.line_rec = S.ln_rec.as<u64>(), fa.base_before = S.base_before.as<u64>();
+        if (const int rc = reserve_line_tables()) return rc;
         const dim3 line_grid((u32)((n_lines + 255) / 256));
         bool ok = ev_open();
         launch_index();
@@ -1020,20 +1071,25 @@ struct SeqRun {
         if (!fits((double)n_rec * 36.0, (double)S.rec_line.cap + (double)S.piece_off.cap + (double)S.byte_off.cap)) return no_room();
         HIP_TRY(S.rec_line.reserve((size_t)(n_rec + 1) * sizeof(u64)));
         HIP_TRY(S.rec_width.reserve((size_t)(n_rec + 1) * sizeof(u32)));
-        fa.rec_line = S.rec_line.as<u64>(), fa.rec_width = S.rec_width.as<u32>();
+        fa.rec_line = S.rec_line.as<u64>(), fa.rec_width = S.rec_width.as<u32>(), fa.n_head = n_rec;
         return size_records<yk::Fasta>(
             [&] {
                 if (n_lines) hipLaunchKernelGGL(yk::fa_heads_kernel, line_grid, dim3(256), 0, e->stream, args(yk::Fasta{}));
                 if (n_rec) hipLaunchKernelGGL(yk::fa_widths_kernel, line_grid, dim3(256), 0, e->stream, args(yk::Fasta{}));
-            },
-            "bases in front of the first header, a header without a name, a cut position beyond its read or a region with "
-            "begin > end: the host loop decides");
+            });
     }
 
-    // what both formats do once the records are numbered: in one bracket the format's own kernels (`front`), the plan and the
-    // two scans; how many output records, how many bytes.  `not_taken`: what the plan's status bit says in this format
-    template <class Format, class Front>
-    int size_records(Front &&front, const char *not_taken)
+    // what the plan's status bit says, by format
+    static const char *not_taken(yk::Fastq)
+    {
+        return "a record that is not \"@name[ desc]\\nseq\\n+\\nqual\\n\", a cut position beyond its read or a region with begin > end: the host loop decides";
+    }
+    static const char *not_taken(yk::Fasta)
+    {
+        return "bases in front of the first header, a header without a name, a cut position beyond its read or a region with begin > end: the host loop decides";
+    }
+    // the per-record tables both formats' plans fill, for n_rec records
+    int reserve_record_tables()
     {
         HIP_TRY(S.rec_pieces.reserve((size_t)(n_rec + 1) * sizeof(u32)));
         HIP_TRY(S.rec_bytes.reserve((size_t)(n_rec + 1) * sizeof(u32)));
@@ -1042,6 +1098,28 @@ struct SeqRun {
         ga.n_rec = n_rec;
         ga.rec_pieces = S.rec_pieces.as<u32>(), ga.rec_bytes = S.rec_bytes.as<u32>();
         ga.piece_off = S.piece_off.as<u64>(), ga.byte_off = S.byte_off.as<u64>();
+        return YACRD_OK;
+    }
+    // FASTA's tables per line, for n_lines lines
+    int reserve_line_tables()
+    {
+        HIP_TRY(S.line_end.reserve((size_t)(n_lines + 1) * sizeof(u64)));
+        HIP_TRY(S.ln_head.reserve((size_t)(n_lines + 1) * sizeof(u32)));
+        HIP_TRY(S.ln_bases.reserve((size_t)(n_lines + 1) * sizeof(u32)));
+        HIP_TRY(S.ln_rec.reserve((size_t)(n_lines + 2) * sizeof(u64)));
+        HIP_TRY(S.base_before.reserve((size_t)(n_lines + 2) * sizeof(u64)));
+        ga.line_end = S.line_end.as<u64>();
+        fa.head = S.ln_head.as<u32>(), fa.bases = S.ln_bases.as<u32>();
+        fa.line_rec = S.ln_rec.as<u64>(), fa.base_before = S.base_before.as<u64>();
+        return YACRD_OK;
+    }
+
+    // what both formats do once the records are numbered: in one bracket the format's own kernels (`front`), the plan and the
+    // two scans; how many output records, how many bytes
+    template <class Format, class Front>
+    int size_records(Front &&front)
+    {
+        if (const int rc = reserve_record_tables()) return rc;
         bool ok = ev_open();
         front();
         launch_plan<Format, false>();
@@ -1050,7 +1128,7 @@ struct SeqRun {
         ok = ok && ev_close();
         if (const int rc = bring_words(ok, {S.piece_off.as<u64>() + n_rec, S.byte_off.as<u64>() + n_rec, S.ctl.p})) return rc;
         n_pieces = h_ctl[0], total = h_ctl[1];
-        if (h_ctl[2] & yk::kSqNeedHost) return fail(YACRD_EFALLBACK, not_taken);
+        if (h_ctl[2] & yk::kSqNeedHost) return fail(YACRD_EFALLBACK, not_taken(Format{}));
         if (n_pieces >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "more output records than the device editor numbers");
         return YACRD_OK;
     }
@@ -1138,14 +1216,18 @@ struct SeqRun {
         return rc;
     }
 
-    // ==== the run in windows (FASTQ, text from a file or from memory) =====================================================
+    // ==== the run in windows (text from a file or from memory; DESIGN 7k, FASTA: 7l) ==================================================
     // Window k's new bytes are text[kW, min((k + 1) W, n)); its text is the carry of window k - 1 — the bytes behind that
     // window's last whole record — and then its new bytes.  A text slot is [carry area: W][new bytes: W][64 zero bytes]: the
     // new bytes always land at offset W, the carry is moved on the device to END at W (sq_carry_kernel), so a window is bytes
     // [lo, hi) of its slot, lo = W - carry, and by induction begins on a record boundary: its records are its lines 4j .. 4j + 3.
+    // FASTA: a window's whole records are those in front of its last header line — the record behind that line may go on in
+    // the next window even where it ends with this one —, the carry begins at that line (fa_carry_kernel), and a window
+    // begins with a header or, while no header has been seen, with what may stand in front of the first.
     //
     // Who runs beside whom.  THIS thread lands window k (move_text: its threads and copy streams), launches k's kernels on the
-    // engine's stream and waits for it twice — line count; pieces, bytes, status, carry —, then launches k's pieces and copy
+    // engine's stream and waits for it twice — line count; pieces, bytes, status, carry; FASTA waits once more in between, for
+    // the header count that sizes the record tables, S'(k) —, then launches k's pieces and copy
     // passes and goes on to land window k + 1 WITHOUT waiting for them.  The WRITER thread takes the windows in order behind
     // the event of their copy pass: the bytes go home through the two pinned pieces into the sink or, gzip out, through the
     // encoder on its own stream first.  So window k + 1 lands while k is gathered and while k and k - 1 leave.
@@ -1157,8 +1239,13 @@ struct SeqRun {
     //                     behind that pass on the same stream; the mover starts behind S(k), which the pass precedes.
     //   a window's tables line_end, rec_*, *_off, pieces, tile_* are one set, reserved behind W1(k) (pieces: behind S(k)): every
     //                     kernel of window k - 1 has ended by then, and the writer never reads them.
-    //   `part`            (the scans' scratch) is reserved inside a scan; the scans of a window follow W1(k) or S(k - 1) with
-    //                     no other scan in flight.
+    //   FASTA's tables    ln_head, ln_bases, ln_rec, base_before (per line) are reserved with line_end behind W1(k); rec_line,
+    //                     rec_width and the rec_* / *_off above behind S'(k), which leaves the stream empty too: index, mark and
+    //                     the line scans of window k have ended, and heads, widths, carry and plan — their first readers and
+    //                     writers — are enqueued behind the reserve.  The copy pass of k reads line_end and base_before; it has
+    //                     ended by W1(k + 1), in front of the next reserve of either.
+    //   `part`            (the scans' scratch) is reserved inside a scan; the scans of a window follow W1(k), S'(k) or S(k - 1)
+    //                     with no other scan in flight but one over as many elements.
     //   output slots, two slot k & 1 is read by the writer (way home, encoder) for window k and, gzip out, by the copy pass of
     //                     window k + 1 (the raw piece: k's ragged tail).  This thread reserves and refills it for window k + 2
     //                     behind S(k + 2) — the copy pass of k + 1 has ended — and behind the writer's release of window k,
@@ -1279,14 +1366,77 @@ struct SeqRun {
         if (job.gzip) (void)hipStreamSynchronize(side[1]);
     }
 
+    struct WinAt { // window k as its kernels see it: bytes [lo, hi) of text slot ts, tiles [t_lo, t_hi), its control words
+        bool last;
+        int ts;
+        u64 lo, hi;
+        u32 t_lo, t_hi;
+        unsigned long long *ctl;
+    };
+    // A window's records numbered, by format.  Behind the first wait — n_lines is known, the engine's stream is empty — the
+    // window's tables are sized; then the line index and what is the format's own in front of the plan, the carry kernel
+    // last.  Leaves the plan's bracket open (`ok`).  FASTQ: n_rec follows from n_lines.
+    int window_records(yk::Fastq, const WinAt &w, bool &ok)
+    {
+        if (w.last && n_lines % 4) return fail(YACRD_EFALLBACK, "the line count is no multiple of four: the host loop decides");
+        n_rec = n_lines / 4;
+        HIP_TRY(S.line_end.reserve((size_t)(n_lines + 1) * sizeof(u64)));
+        if (const int rc = reserve_record_tables()) return rc;
+        ga.line_end = S.line_end.as<u64>(), ga.n_lines = n_lines;
+        ga.tile0 = w.t_lo;
+        ok = ev_open();
+        hipLaunchKernelGGL(yk::sq_index_kernel, dim3(w.t_hi - w.t_lo), dim3(yk::kGpT), 0, e->stream, ga);
+        if (!w.last) { // (the last window: its lines are whole records and its last byte is a newline — nothing is left)
+            yk::SqCarry c{ga.line_end, n_rec, w.lo, w.hi, W, ga.text, S.wtext[w.ts ^ 1].as<unsigned char>(), w.ctl};
+            hipLaunchKernelGGL(yk::sq_carry_kernel, dim3(64), dim3(256), 0, e->stream, c);
+        }
+        return YACRD_OK;
+    }
+    // FASTA: index, mark and the two line scans, then a wait of its own — the window's headers H —: n_rec = H in the last
+    // window and where a header's partial line ends the window, else H - 1 (the record behind the last header waits); then
+    // heads, widths and the carry
+    int window_records(yk::Fasta, const WinAt &w, bool &ok)
+    {
+        if (!room_for((double)n_lines * 32.0, held_line_tables())) return no_room_message();
+        if (const int rc = reserve_line_tables()) return rc;
+        ga.n_lines = n_lines, ga.n_rec = 0, ga.tile0 = w.t_lo;
+        fa.hi = w.last ? 0 : w.hi;
+        const dim3 line_grid((u32)((n_lines + 255) / 256));
+        ok = ev_open();
+        hipLaunchKernelGGL(yk::sq_index_kernel, dim3(w.t_hi - w.t_lo), dim3(yk::kGpT), 0, e->stream, ga);
+        if (n_lines) hipLaunchKernelGGL(yk::fa_mark_kernel, line_grid, dim3(256), 0, e->stream, args(yk::Fasta{}));
+        if (const int rc = scan_u32_to_u64(e, fa.head, n_lines, S.ln_rec.as<u64>(), S.part)) return rc;
+        if (const int rc = scan_u32_to_u64(e, fa.bases, n_lines, S.base_before.as<u64>(), S.part)) return rc;
+        ok = ok && ev_close();
+        if (const int rc = bring_words(ok, {S.ln_rec.as<u64>() + n_lines, w.ctl, w.ctl + 3})) return rc;
+        const u64 n_head = h_ctl[0];
+        const bool open_head = h_ctl[2] != 0; // the partial last line is the next record's header: every record of the window is whole
+        win_seen_head = win_seen_head || n_head != 0;
+        if (h_ctl[1] & yk::kSqNeedHost) return fail(YACRD_EFALLBACK, "a line longer than the device editor's offsets: the host loop decides");
+        n_rec = w.last || open_head || !n_head ? n_head : n_head - 1;
+        if (!room_for((double)n_rec * 40.0, held_record_tables())) return no_room_message();
+        HIP_TRY(S.rec_line.reserve((size_t)(n_rec + 1) * sizeof(u64)));
+        HIP_TRY(S.rec_width.reserve((size_t)(n_rec + 1) * sizeof(u32)));
+        if (const int rc = reserve_record_tables()) return rc;
+        fa.rec_line = S.rec_line.as<u64>(), fa.rec_width = S.rec_width.as<u32>(), fa.n_head = n_head;
+        ok = ev_open();
+        if (n_lines) hipLaunchKernelGGL(yk::fa_heads_kernel, line_grid, dim3(256), 0, e->stream, args(yk::Fasta{}));
+        if (n_lines && n_rec) hipLaunchKernelGGL(yk::fa_widths_kernel, line_grid, dim3(256), 0, e->stream, args(yk::Fasta{}));
+        if (!w.last) {
+            yk::FaCarry c{{ga.line_end, n_rec, w.lo, w.hi, W, ga.text, S.wtext[w.ts ^ 1].as<unsigned char>(), w.ctl}, fa.rec_line, n_head};
+            hipLaunchKernelGGL(yk::fa_carry_kernel, dim3(64), dim3(256), 0, e->stream, c);
+        }
+        return YACRD_OK;
+    }
+
     // window by window on this thread; the code of what it found, or the writer's
+    template <class Format>
     int windows_loop()
     {
+        using Piece = typename Format::Piece;
         const u64 n_win = (n + W - 1) / W;
         const size_t chunk = (size_t)std::min<u64>(kTextChunk, W);
         const u32 w_tile = (u32)(W / yk::kGpTile);
-        static const char *const not_taken =
-            "a record that is not \"@name[ desc]\\nseq\\n+\\nqual\\n\", a cut position beyond its read or a region with begin > end: the host loop decides";
         u64 carry = 0, tail = 0, tail_at = 0; // of the window before: its carry; its ragged output tail and where it lies in its slot
         u64 sum_rec = 0, sum_pieces = 0, sum_total = 0, max_carry = 0;
         double text_ms = 0;
@@ -1334,33 +1484,20 @@ struct SeqRun {
             if (const int rc = bring_words(ok, {S.tile_l0.as<u64>() + t_hi, ctl})) return rc;
             n_lines = h_ctl[0];
             if (h_ctl[1] & yk::kSqNeedHost) return fail(YACRD_EFALLBACK, "the text holds a CR: the host loop decides");
-            if (last && n_lines % 4) return fail(YACRD_EFALLBACK, "the line count is no multiple of four: the host loop decides");
-            n_rec = n_lines / 4;
-            // the window's tables (the engine's stream is empty: nothing reads the ones they replace)
-            HIP_TRY(S.line_end.reserve((size_t)(n_lines + 1) * sizeof(u64)));
-            HIP_TRY(S.rec_pieces.reserve((size_t)(n_rec + 1) * sizeof(u32)));
-            HIP_TRY(S.rec_bytes.reserve((size_t)(n_rec + 1) * sizeof(u32)));
-            HIP_TRY(S.piece_off.reserve((size_t)(n_rec + 2) * sizeof(u64)));
-            HIP_TRY(S.byte_off.reserve((size_t)(n_rec + 2) * sizeof(u64)));
-            ga.line_end = S.line_end.as<u64>(), ga.n_lines = n_lines, ga.n_rec = n_rec;
-            ga.rec_pieces = S.rec_pieces.as<u32>(), ga.rec_bytes = S.rec_bytes.as<u32>();
-            ga.piece_off = S.piece_off.as<u64>(), ga.byte_off = S.byte_off.as<u64>();
-            ga.tile0 = t_lo;
-            ok = ev_open();
-            hipLaunchKernelGGL(yk::sq_index_kernel, dim3(t_hi - t_lo), dim3(yk::kGpT), 0, e->stream, ga);
-            if (!last) { // (the last window: its lines are whole records and its last byte is a newline — nothing is left)
-                yk::SqCarry c{ga.line_end, n_rec, lo, hi, W, ga.text, S.wtext[ts ^ 1].as<unsigned char>(), ctl};
-                hipLaunchKernelGGL(yk::sq_carry_kernel, dim3(64), dim3(256), 0, e->stream, c);
-            }
-            launch_plan<yk::Fastq, false>();
+            // the window's tables (the engine's stream is empty: nothing reads the ones they replace), its records, its carry
+            if (const int rc = window_records(Format{}, WinAt{last, ts, lo, hi, t_lo, t_hi, ctl}, ok)) return rc;
+            launch_plan<Format, false>();
             if (const int rc = scan_u32_to_u64(e, ga.rec_pieces, n_rec, S.piece_off.as<u64>(), S.part)) return rc;
             if (const int rc = scan_u32_to_u64(e, ga.rec_bytes, n_rec, S.byte_off.as<u64>(), S.part)) return rc;
             ok = ok && ev_close();
-            // the second wait: pieces, bytes, status, carry
+            // the second wait (FASTA: the third): pieces, bytes, status, carry
             if (const int rc = bring_words(ok, {S.piece_off.as<u64>() + n_rec, S.byte_off.as<u64>() + n_rec, ctl, ctl + 2})) return rc;
             const u64 w_pieces = h_ctl[0], w_total = h_ctl[1];
-            if (h_ctl[2] & yk::kSqCarryLong) return fail(YACRD_EFALLBACK, "a record longer than a window: the host loop's case");
-            if (h_ctl[2] & yk::kSqNeedHost) return fail(YACRD_EFALLBACK, not_taken);
+            if (h_ctl[2] & yk::kSqCarryLong) // (FASTA with no whole header line so far: what was carried is no record)
+                return fail(YACRD_EFALLBACK, std::is_same<Format, yk::Fasta>::value && !win_seen_head
+                                                 ? "more than two windows in front of the first header's newline: the host loop's case"
+                                                 : "a record longer than a window: the host loop's case");
+            if (h_ctl[2] & yk::kSqNeedHost) return fail(YACRD_EFALLBACK, not_taken(Format{}));
             carry = last ? 0 : h_ctl[3];
             max_carry = std::max(max_carry, carry);
             // the output slot: the writer has let go of what window k - 2 left in it
@@ -1371,21 +1508,20 @@ struct SeqRun {
             if (win_stop.load()) return YACRD_OK;
             const u64 raw = job.gzip ? tail : 0, len = raw + w_total;
             if (w_pieces + 1 >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "more output records than the device editor numbers");
-            HIP_TRY(S.wout[os].reserve((size_t)((len + 15) & ~(u64)15) + 64));
-            HIP_TRY(S.pieces.reserve((size_t)(w_pieces + 2) * sizeof(yk::SqPiece)));
-            ga.pieces = S.pieces.as<yk::SqPiece>(), ga.out = S.wout[os].as<unsigned char>();
+            HIP_TRY(S.wout[os].reserve((size_t)((len + 15) & ~(u64)15) + 64)); // (grow-only, by the scanned total: FASTA written again may be longer than its text)
+            HIP_TRY(S.pieces.reserve((size_t)(w_pieces + 2) * sizeof(Piece)));
+            args(Format{}).pieces = S.pieces.as<Piece>(), ga.out = S.wout[os].as<unsigned char>();
             ga.n_pieces = w_pieces + (raw ? 1 : 0), ga.total = len;
             ga.raw = S.wout[os ^ 1].as<unsigned char>(), ga.out0 = raw, ga.piece0 = raw ? 1u : 0u;
             if (raw) { // piece 0: the tail of the window before, where it lies in that window's slot
-                yk::SqPiece *p0 = reinterpret_cast<yk::SqPiece *>(const_cast<u64 *>(h_ctl + 12)) + os; // (pinned; window k - 2's copy has ended)
-                *p0 = yk::SqPiece{};
-                p0->out = 0, p0->rec = tail_at, p0->len = (u32)raw, p0->flags = yk::kSqRaw;
-                HIP_TRY(hipMemcpyAsync(ga.pieces, p0, sizeof *p0, hipMemcpyHostToDevice, e->stream));
+                Piece *p0 = reinterpret_cast<Piece *>(const_cast<u64 *>(h_ctl + 12)) + os; // (pinned; window k - 2's copy has ended)
+                *p0 = Format::raw_piece(tail_at, (u32)raw);
+                HIP_TRY(hipMemcpyAsync(S.pieces.p, p0, sizeof *p0, hipMemcpyHostToDevice, e->stream));
             }
             ok = ev_open();
             if (len) {
-                launch_plan<yk::Fastq, true>();
-                hipLaunchKernelGGL(yk::seq_copy_kernel<yk::Fastq>, dim3((u32)((len + yk::kSqOutTile - 1) / yk::kSqOutTile)), dim3(yk::kGpT), 0, e->stream, ga);
+                launch_plan<Format, true>();
+                hipLaunchKernelGGL(yk::seq_copy_kernel<Format>, dim3((u32)((len + yk::kSqOutTile - 1) / yk::kSqOutTile)), dim3(yk::kGpT), 0, e->stream, args(Format{}));
             }
             ok = ok && ev_close();
             HIP_TRY(hipMemcpyAsync((void *)(h_ctl + 8 + 2 * os), ctl, 2 * sizeof(u64), hipMemcpyDeviceToHost, e->stream));
@@ -1407,6 +1543,7 @@ struct SeqRun {
     bool win_fresh[2] = {false, false}; // a text slot that is a new allocation fills faster by copy kernel, once
     double win_text_ms = 0;
     u64 win_count = 0, win_max_carry = 0;
+    bool win_seen_head = false; // FASTA: a window so far had a whole header line
 
     // the ring, the writer thread, the windows; then what the two threads found
     int run_windows()
@@ -1424,7 +1561,7 @@ struct SeqRun {
             HIP_TRY(hipStreamSynchronize(e->stream)); // (gzip_device_open's memset)
         }
         std::thread wt([this] { window_writer(); });
-        int rc = windows_loop();
+        int rc = job.fasta ? windows_loop<yk::Fasta>() : windows_loop<yk::Fastq>();
         if (rc != YACRD_OK) win_stop = 1;
         win_no_more = true;
         wt.join();
@@ -1483,11 +1620,12 @@ int run_seq_edit(yacrd_engine *e, const SeqJob &job, const TextSource &src, u64 
     DeviceGuard guard(e->device);
     SeqEditScratch *S = scratch_of<SeqEditScratch>(e);
     if (!S) return fail(YACRD_ENOMEM, "host allocation failed");
-    // The route.  FASTQ with its text in a file or in host memory runs in windows when the text is longer than a
-    // window and either the switch names a window or the whole-text run finds no room; every other text runs whole.
+    // The route.  A FASTQ or FASTA with its text in a file or in host memory runs in windows when the text is
+    // longer than a window and either the switch names a window or the whole-text run finds no room; every other text — BGZF
+    // in among them — runs whole.
     const u64 sw = e->seq_window;
     for (u64 &w : e->seq_windows) w = 0;
-    const bool may_window = !job.fasta && !job.bgzf && sw != UINT64_MAX;
+    const bool may_window = !job.bgzf && sw != UINT64_MAX;
     const u64 W = sw == 0 || sw == UINT64_MAX ? (u64)(kTextChunk * kTextSeg) : (sw + yk::kGpTile - 1) / yk::kGpTile * yk::kGpTile;
     bool windows = may_window && n > W && (sw != 0 || kSeqWindowsWhenFits);
     auto finish = [&](SeqRun &r, int rc) {
@@ -1508,6 +1646,8 @@ int run_seq_edit(yacrd_engine *e, const SeqJob &job, const TextSource &src, u64 
         // no room: nothing has left the device yet, and what the run holds goes before the windows take their ring
         if (!(rc == YACRD_EFALLBACK && r.room_failed && may_window && n > W)) return rc;
         windows = true;
+        if (job.fasta) // the whole text's tables, 32 bytes a line: a window sizes its own
+            for (DevBuf *b : {&S->line_end, &S->ln_head, &S->ln_bases, &S->ln_rec, &S->base_before, &S->rec_line, &S->rec_width}) b->release();
     }
     S->text.release(), S->out.release(); // (the whole-text run's: the ring is what a run in windows holds)
     SeqRun r{e, job, src, n, sink, stats, *S};

@@ -23,7 +23,7 @@
 #include <unistd.h>
 
 #include "../../../include/yacrd_engine.h"
-#include "../../../include/yacrd_engine_debug.h" // (YACRD_SEQ_WINDOW: the FASTQ editor's window, an A/B and test switch)
+#include "../../../include/yacrd_engine_debug.h" // (YACRD_SEQ_WINDOW: the FASTQ and FASTA editors' window, an A/B and test switch)
 #include "../../../include/yacrd_host.h"
 
 namespace {
@@ -551,7 +551,7 @@ int main(int argc, char **argv)
             yacrd_gunzip_stats us{};
             double inflate_ms = 0;
             bool text_reused = false, dev_inflate = false;
-            // YACRD_SEQ_WINDOW=<bytes>: the FASTQ editor's window (yacrd_debug_seq_window; A/B and tests, like YACRD_NO_DEVICE_EDITOR)
+            // YACRD_SEQ_WINDOW=<bytes>: the FASTQ and FASTA editors' window (yacrd_debug_seq_window; A/B and tests, like YACRD_NO_DEVICE_EDITOR)
             if (const char *sw = std::getenv("YACRD_SEQ_WINDOW"))
                 if (*sw) (void)yacrd_debug_seq_window(engines[0], std::strtoull(sw, nullptr, 10));
             if (sub_comp == 1) {

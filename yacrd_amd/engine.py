@@ -806,8 +806,8 @@ class Engine:
         return tuple(int(v) for v in out)
 
     def debug_seq_window(self, window_bytes):
-        """yacrd_debug_seq_window (tests, A/B): the FASTQ editor's window.  0: the policy (128 MiB windows where the whole text
-        finds no room); 2**64 - 1: never windows; any other value: rounded up to a 32 KiB tile, and every FASTQ text longer
+        """yacrd_debug_seq_window (tests, A/B): the FASTQ and FASTA editors' window.  0: the policy (128 MiB windows where the whole text
+        finds no room); 2**64 - 1: never windows; any other value: rounded up to a 32 KiB tile, and every FASTQ or FASTA text longer
         than it is edited window by window (csrc/gpu_seq_edit.hip: run_windows).  The bytes written do not depend on it."""
         self._lib.yacrd_debug_seq_window.restype = ctypes.c_int
         self._lib.yacrd_debug_seq_window.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
