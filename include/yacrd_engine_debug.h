@@ -105,18 +105,22 @@ uint64_t yacrd_debug_direct_runs(const yacrd_engine *e);
  * After a missed class prediction the device-wide screen goes out twice: the final pass is reported, not the sum.  A
  * batch that ran as one launch (YACRD_F_ONE_LAUNCH) has no such reads: all four are 0. */
 void yacrd_debug_big_routes(const yacrd_engine *e, uint64_t out[4]);
-/* the sequence editors' windows (csrc/gpu_seq_edit.hip): yacrd_engine_edit_fastq / _fasta, _mem, _gzip_mem and _gzip_file run a
- * text of more than one window window by window, in a bounded ring of buffers; the bytes written do not depend on it.
+/* the sequence editors' windows (csrc/gpu_seq_edit.hip): yacrd_engine_edit_fastq / _fasta, _mem, _gzip_mem,
+ * _gzip_file, _bgzf_mem and _bgzf_file run a text of more than one window window by window, in a bounded ring of buffers; the
+ * bytes written do not depend on it.
  *   window_bytes == 0            the policy: a window of 128 MiB, taken where the whole-text run finds no room (and, if the
  *                                build's measured default says so, for every text of more than one window);
  *   window_bytes == UINT64_MAX   never windows: the whole text at once, YACRD_EFALLBACK where it finds no room;
  *   any other value              rounded up to a whole 32 KiB tile; every text longer than it runs in windows (tests: 32 KiB to
  *                                4 MiB; the mover's chunk becomes min(4 MiB, the window)).
- * The BGZF-in forms and FASTA always run whole.  Stays with the engine until set again.  Tests and A/B runs only. */
+ * The BGZF-in forms (their text: the bytes the members inflate to) take a window of at least 64 KiB — the largest member — and
+ * end every window where a member ends (csrc/bgzf_windows.h), so a window brings at most window_bytes of text and of
+ * compressed stream, possibly no text at all.  Stays with the engine until set again.  Tests and A/B runs only. */
 int yacrd_debug_seq_window(yacrd_engine *e, uint64_t window_bytes);
 /* what the engine's last sequence edit (FASTQ or FASTA, any form) ran as: [0] its windows (0: the whole text at once), [1] the
  * longest carry — the bytes a window left behind its last whole record for the next one —, [2] device bytes its two text
- * slots held, [3] device bytes its two output slots held.  A failed edit in windows leaves [0] = 0. */
+ * slots held (BGZF in: with the compressed slot and the member slice), [3] device bytes its two output slots held.  A failed
+ * edit in windows leaves [0] = 0. */
 void yacrd_debug_seq_windows(const yacrd_engine *e, uint64_t out[4]);
 /* YACRD_TEST_REPORT_SEGMENT=<bytes> (environment, tests; read at every call): the size of the segments in which
  * yacrd_engine_write_report[_mem] brings the formatted text home, instead of 64 MiB (csrc/gpu_report_write.hip: kReportSegment;

@@ -172,6 +172,12 @@ int yacrd_bgzf_plan_segments(const char *data, uint64_t n, const uint64_t *lande
  * BGZF; one of those members is not taken by the decoder (the message names the cause); the first non-empty line is not
  * complete within the sample although the text goes on. */
 int yacrd_bgzf_text_ends(const char *data, uint64_t n, int delim, uint32_t *n_fields, int *ends_nl);
+/* Where the windows of a BGZF text end (csrc/bgzf_windows.h): a member inflates as a unit, so a window ends on a member
+ * border.  Greedy: a window takes members while its text and its part of the compressed stream are both at most
+ * window_bytes, and always one.  cuts_out, six words per window: the member range [m0, m1), the stream's bytes [c0, c1)
+ * that hold those members' whole frames, the text's bytes [t0, t1).  Through yacrd_bytes_free.  Non-zero: not BGZF, or
+ * window_bytes under 65 536 (the largest frame and the largest ISIZE). */
+int yacrd_bgzf_window_cuts(const char *data, uint64_t n, uint64_t window_bytes, uint64_t **cuts_out, uint64_t *n_cuts);
 /* The encoder's code-length construction: freq[n] -> len[n] with no length above `limit` (n in 2..286, limit in 5..15,
  * 2^limit >= n).  Fewer than two used symbols are given company, as zlib does, so the code is always complete. */
 int yacrd_deflate_code_lengths(const uint32_t *freq, uint32_t n, uint32_t limit, uint8_t *len);

@@ -8,7 +8,9 @@
 // cases.bin (tests/inflate_cases.py: write_check_file): u64 count, then per record u64 stream bytes, u8 has_text, u64 text
 // bytes, the stream, the text.  has_text 1: the helper must answer, for a tab and for a space as the delimiter, what the
 // plain rule (below: gpu_edit.hip's first_line_fields, restated) answers on the text; 0: it must refuse the stream (not
-// BGZF, a sampled member not taken, a first line that outgrows the sample).  Every stream and every member table lies in an
+// BGZF, a sampled member not taken, a first line that outgrows the sample).  bgzf_last_byte — the last byte alone, what a BGZF
+// FASTQ / FASTA in windows asks — runs over the same records: the text's last byte where has_text is 1; elsewhere an answer or a
+// status that agree, under the sanitizers.  Every stream and every member table lies in an
 // allocation of exactly its size.  Exit status 0: every record came out as expected.
 #include <cstdio>
 #include <cstdlib>
@@ -60,6 +62,7 @@ int main(int argc, char **argv)
         std::vector<yif::InfMember> walked;
         uint64_t total = 0;
         bool ok = ybw::walk(blob, n, walked, &total);
+        const bool is_bgzf = ok;
         const size_t M = walked.size();
         yif::InfMember *mem = (yif::InfMember *)std::malloc(M ? M * sizeof(yif::InfMember) : 1); // exactly M members
         if (!mem) return 2;
@@ -79,6 +82,19 @@ int main(int argc, char **argv)
             if (total != text.size()) why = "the walk's text size is not the text's";
             else if (nf != want_nf) why = "another field count than the plain rule's";
             else if (nl != want_nl) why = "another last byte than the plain rule's";
+        }
+        if (!why && ok && has_text == 1) { // bgzf_last_byte: the second answer alone, from the last member that holds text
+            bool nl = false;
+            uint32_t status = 77;
+            if (yke::bgzf_last_byte(blob, n, mem, M, &nl, &status) != 0 || status != yif::kInfOk) why = "bgzf_last_byte refused a text that is answered";
+            else if (nl != (text.empty() || text.back() == '\n')) why = "bgzf_last_byte: another last byte than the text's";
+        }
+        if (is_bgzf && has_text != 1) { // a stream to refuse: whatever its last member holds, an answer or a status, nothing else
+            bool nl = false;
+            uint32_t status = 77;
+            const int rc = yke::bgzf_last_byte(blob, n, mem, M, &nl, &status);
+            if (rc != 0 && rc != 1) why = "bgzf_last_byte: neither an answer nor a status";
+            else if ((rc == 1) != (status != yif::kInfOk)) why = "bgzf_last_byte: code and status disagree";
         }
         if (!why && ok != (has_text == 1)) why = ok ? "answered, expected a refusal" : "refused, expected an answer";
         if (why) {

@@ -21,6 +21,10 @@ with YACRD_SEQ_WINDOW=18446744073709551615 (never windows), a third series "wind
 is compared with the parent's too, and the row says whether the windowed run's slowest `edit` is ahead of the whole-text
 run's fastest (the rule for the default).  The default --json is then profiles/edit_fastq_windows.json, with --fasta
 profiles/edit_fasta_windows.json.
+--window BYTES --forms bgzf: the BGZF-in form in windows, FASTQ or --fasta: the windows are cut where members end,
+every window's members inflated on the device.  Both new series must show the "[info] device inflate:" line — a run that fell
+back to the host inflate would report windows too, the gzip form's — and the default --json is profiles/edit_bgzf_windows.json
+for both formats (the rows say which: "kind").
 --parent-again: a second series of the parent behind the new one ("parent_again" in the row): what drifted meanwhile shows.
 Where the parent has a device editor too, the figure to compare is the `kernels ... ms` of the info lines, not the stage."""
 import argparse, gzip, json, os, re, subprocess, sys, time
@@ -42,7 +46,7 @@ ap.add_argument("--window", type=int, default=0)
 ap.add_argument("--json", default=None)
 a = ap.parse_args()
 kind = "fasta" if a.fasta else "fastq"
-a.json = a.json or os.path.join(ROOT, "profiles", "edit_%s%s.json" % (kind, "_windows" if a.window else ""))
+a.json = a.json or os.path.join(ROOT, "profiles", "edit_%s%s.json" % ("bgzf" if a.window and a.forms == "bgzf" else kind, "_windows" if a.window else ""))
 editor_line = "[info] device %s editor:" % kind
 if not a.parent_bin or not os.access(a.parent_bin, os.X_OK):
     sys.exit("--parent-bin: the yacrd binary built from the parent commit")
@@ -132,6 +136,8 @@ try:
                 assert same(old, new, False) or (form != "plain" and same(old, new, True)), "the whole-text run's output differs from the parent's"
                 windowed = run(new_bin, op, src, new, YACRD_SEQ_WINDOW=str(a.window))
                 assert all(int(l.rsplit("windows=", 1)[1]) > 1 for r in windowed for l in r["info"] if l.startswith(editor_line)), "not in windows"
+                if form == "bgzf":  # (the windows of the device inflate, not the gzip form's behind a host inflate)
+                    assert all(any(l.startswith("[info] device inflate:") for l in r["info"]) for r in mine + windowed), "the device inflate did not run"
             again = run(a.parent_bin, op, src, old) if a.parent_again else None
             assert any(l.startswith(editor_line) for l in mine[-1]["info"]), "the device editor did not run"
             assert same(old, new, False) or (form != "plain" and same(old, new, True)), "the new path's output differs from the parent's"

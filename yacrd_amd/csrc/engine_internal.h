@@ -482,6 +482,32 @@ bool bgzf_head_lines(const unsigned char *comp, uint64_t comp_bytes, const yif::
 // 2 the first non-empty line is not complete inside max_text bytes and the text goes on; 3 no memory)
 int bgzf_text_ends(const unsigned char *comp, uint64_t comp_bytes, const yif::InfMember *members, uint64_t n_members, uint64_t max_text,
                    unsigned char delim, uint32_t *n_fields, bool *ends_nl, uint32_t *status);
+// (bgzf_text_ends' second answer alone — whether the text's last byte is a newline — from the last member that holds text:
+// what a BGZF FASTQ / FASTA in windows asks before its first launch.  0; 1 that member not taken, *status the cause; 3 no memory)
+int bgzf_last_byte(const unsigned char *comp, uint64_t comp_bytes, const yif::InfMember *members, uint64_t n_members, bool *ends_nl,
+                   uint32_t *status);
+// A BGZF text inflated window by window (gpu_inflate.hip; used by gpu_seq_edit.hip; the cuts: bgzf_windows.h).
+// open takes, in the engine's inflate scratch, ONE compressed slot of W + 64 bytes (16-byte aligned) and zeroes the status
+// word on the engine's stream (release_whole, before it: the whole-stream buffer and table of inflate_device_open go).  Per
+// window the caller lands the stream's bytes [c0, c1) at w.comp and calls run_window with the window's slice of the member
+// table — its offsets absolute, as the walk gave them — and the window's bases: the slice goes up into a grow-only table,
+// 64 zero bytes are put behind the slot's c1 - c0 bytes, and the decoder is launched on stream `st`: member m's text to
+// d_text + (out_off - t0), nothing beyond d_text[0, t1 - t0).  The kernel checks every member against the window's extents
+// before it reads or stores a byte: one outside them leaves kInfTable in the status word.  The inflate of the window before
+// — the last reader of the slot and of the table — must have ended when the caller lands the next window's bytes and calls
+// run_window (the caller's waits: gpu_seq_edit.hip argues it); other work may still be enqueued on the stream.
+struct InflateWindow {
+    unsigned char *comp = nullptr;
+    u32 *status = nullptr;
+    u64 W = 0;
+    bool fresh = false; // `comp` is a new allocation (move_text's `blit`)
+};
+void inflate_device_release_whole(yacrd_engine *e);
+int inflate_window_open(yacrd_engine *e, u64 W, InflateWindow *w);
+int inflate_device_run_window(yacrd_engine *e, const InflateWindow &w, hipStream_t st, const yif::InfMember *slice, u64 n_slice, u64 c0, u64 c1,
+                              u64 t0, u64 t1, unsigned char *d_text);
+// device bytes the window form holds: the compressed slot and the member table
+u64 inflate_window_held(yacrd_engine *e);
 struct BgzfMove {
     InflateDevice d;
     Events ev; // a timed pair around every launch

@@ -47,6 +47,31 @@ __global__ __launch_bounds__(64) void inf_kernel(const unsigned char *comp, u64 
     if (st != yif::kInfOk && lane == 0) atomicMax(status, st);
 }
 
+// The same for one WINDOW of a text: `members` is the window's slice of the table, n_members of them, with the
+// offsets the walk gave — absolute in the stream and in the text; `comp` holds the stream's bytes [c0, c0 + comp_bytes) and
+// `text` takes the text's bytes [t0, t0 + text_bytes).  Every member is checked against the WINDOW's extents before a byte
+// is read or stored: one that does not lie inside both leaves kInfTable, never an access out of range.
+__global__ __launch_bounds__(64) void inf_window_kernel(const unsigned char *comp, u64 c0, u64 comp_bytes, const yif::InfMember *members, u32 n_members,
+                                                         unsigned char *text, u64 t0, u64 text_bytes, u32 *status)
+{
+    __shared__ yif::InfShared sh;
+    const u32 m = blockIdx.x;
+    if (m >= n_members) return; // (uniform)
+    const yif::InfMember mm = members[m];
+    const u32 lane = threadIdx.x;
+    const u32 csize = YI_UNI(mm.csize), n = YI_UNI(mm.isize);
+    u32 st = yif::kInfTable;
+    if (n <= yif::kMaxOut && mm.in_off >= c0 && mm.out_off >= t0) {
+        const u64 in = mm.in_off - c0, out = mm.out_off - t0; // (in the slots)
+        if (in <= comp_bytes && comp_bytes - in >= (u64)csize + 8u && out <= text_bytes && text_bytes - out >= n) {
+            const unsigned char *p = comp + in;
+            const u32 crc = (u32)p[csize] | ((u32)p[csize + 1] << 8) | ((u32)p[csize + 2] << 16) | ((u32)p[csize + 3] << 24);
+            st = yif::inf_decode_member(sh, p, csize, n, YI_UNI(crc), text + out);
+        }
+    }
+    if (st != yif::kInfOk && lane == 0) atomicMax(status, st);
+}
+
 } // namespace yk
 
 namespace {
@@ -57,6 +82,7 @@ struct InflateScratch { // stays with the engine (grow-only); goes with yacrd_en
     static constexpr yacrd_engine::Slot kScratchSlot = yacrd_engine::kInflate;
     DevBuf comp, members, status;
     DevBuf text; // yacrd_engine_gunzip_mem's (the editors inflate into their own text buffer)
+    DevBuf wcomp, wmembers; // a text in windows (inflate_window_open): the one compressed slot, the window's slice of the table
     PinBuf pin;  // two pieces on their way home, the status word
 };
 
@@ -103,6 +129,51 @@ u64 inflate_device_held(yacrd_engine *e)
     const auto &s = e->scratch[InflateScratch::kScratchSlot];
     const InflateScratch *S = static_cast<const InflateScratch *>(s.p);
     return S ? (u64)S->comp.cap + (u64)S->members.cap : 0;
+}
+
+void inflate_device_release_whole(yacrd_engine *e)
+{
+    if (InflateScratch *S = static_cast<InflateScratch *>(e->scratch[InflateScratch::kScratchSlot].p)) S->comp.release(), S->members.release();
+}
+
+int inflate_window_open(yacrd_engine *e, u64 W, InflateWindow *w)
+{
+    InflateScratch *S = scratch_of<InflateScratch>(e);
+    if (!S) return fail(YACRD_ENOMEM, "host allocation failed");
+    const void *before = S->wcomp.p;
+    HIP_TRY(S->wcomp.reserve((size_t)W + 64));
+    HIP_TRY(S->wmembers.reserve(64 * sizeof(yif::InfMember)));
+    HIP_TRY(S->status.reserve(64));
+    HIP_TRY(hipMemsetAsync(S->status.p, 0, 64, e->stream));
+    w->comp = S->wcomp.as<unsigned char>(), w->status = S->status.as<u32>(), w->W = W, w->fresh = S->wcomp.p != before;
+    return YACRD_OK;
+}
+
+int inflate_device_run_window(yacrd_engine *e, const InflateWindow &w, hipStream_t st, const yif::InfMember *slice, u64 n_slice, u64 c0, u64 c1,
+                              u64 t0, u64 t1, unsigned char *d_text)
+{
+    InflateScratch *S = scratch_of<InflateScratch>(e);
+    if (!S || S->wcomp.as<unsigned char>() != w.comp) return fail(YACRD_EINTERNAL, "device inflate: the window's slot is not open");
+    if (c1 < c0 || c1 - c0 > w.W || t1 < t0 || t1 - t0 > w.W || n_slice >= 0x7FFFFFFFull)
+        return fail(YACRD_EINTERNAL, "device inflate: a window larger than its slots");
+    HIP_TRY(S->wmembers.reserve((size_t)(n_slice + 1) * sizeof(yif::InfMember))); // (grow-only; its last reader, the inflate of the window before, has ended: the header's contract)
+    HIP_TRY(hipMemsetAsync(w.comp + (c1 - c0), 0, 64, st));
+    if (!n_slice) return YACRD_OK;
+    if (st == e->stream) {
+        if (const int rc = h2d(e, S->wmembers.p, slice, (size_t)n_slice * sizeof(yif::InfMember))) return rc;
+    } else
+        HIP_TRY(hipMemcpyAsync(S->wmembers.p, slice, (size_t)n_slice * sizeof(yif::InfMember), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(yk::inf_window_kernel, dim3((u32)n_slice), dim3(64), 0, st, w.comp, c0, c1 - c0, S->wmembers.as<yif::InfMember>(), (u32)n_slice,
+                       d_text, t0, t1 - t0, w.status);
+    HIP_TRY(hipGetLastError());
+    return YACRD_OK;
+}
+
+u64 inflate_window_held(yacrd_engine *e)
+{
+    const auto &s = e->scratch[InflateScratch::kScratchSlot];
+    const InflateScratch *S = static_cast<const InflateScratch *>(s.p);
+    return S ? (u64)S->wcomp.cap + (u64)S->wmembers.cap : 0;
 }
 
 float BgzfMove::kernel_ms() const

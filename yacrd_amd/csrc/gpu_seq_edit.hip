@@ -48,6 +48,7 @@
 #include "gpu_text.h"
 #include "edit_table.h"
 #include "bgzf_walk.h"
+#include "bgzf_windows.h"
 #include "host/beside_file.h"
 #include "host/segment_pump.h"
 
@@ -900,6 +901,14 @@ struct SeqRun {
             if (!src.fetch(&last, 1, n - 1)) return fail(YACRD_EINVAL, "read error in the sequence file");
             if (last != '\n') return fail(YACRD_EFALLBACK, "the text's last line has no newline: the host loop's case");
         }
+        if (n && job.bgzf && W) { // BGZF in windows: no launch has run yet — the last member that holds text, decoded on the host
+            bool nl = true;
+            u32 status = 0;
+            const int rcl = bgzf_last_byte(reinterpret_cast<const unsigned char *>(job.bgzf), job.bgzf_bytes, job.members->data(), job.members->size(), &nl, &status);
+            if (rcl == 1) return inflate_not_taken(status);
+            if (rcl) return fail(YACRD_ENOMEM, "host allocation failed");
+            if (!nl) return fail(YACRD_EFALLBACK, "the text's last line has no newline: the host loop's case");
+        }
         while (cap < 2 * R) cap <<= 1;
         t_start = now_ms();
         if (W) { // in windows: the ring's slots, two of text and two of output (sized for a window that goes out as it came in), and a window's tables
@@ -909,10 +918,20 @@ struct SeqRun {
             // of a record's 40, the 4.0 below.  A window's own line and header counts decide when they are known (window_records:
             // a text of shorter lines or records may find no room there)
             const double fa_tables = job.fasta ? 2.0 * (double)W / 61.0 * (32.0 + 4.0) : 0.0;
-            const double ring = 2.0 * (2.0 * (double)W + 64.0) + 2.0 * (double)W + (double)W * 0.25 + fa_tables;
+            // BGZF in: the windows end where members end (bgzf_windows.h); the compressed slot and the largest slice of the member
+            // table count, not the whole stream
+            double bgzf_ring = 0.0;
+            if (job.bgzf) {
+                if (!ybw::window_cuts(job.members->data(), job.members->size(), W, cuts)) return fail(YACRD_ENOMEM, "host allocation failed");
+                u64 slice = 0;
+                for (const ybw::WindowCut &c : cuts) slice = std::max(slice, c.m1 - c.m0);
+                if (slice >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "more BGZF members than the device decoder numbers");
+                bgzf_ring = (double)W + 64.0 + (double)(slice + 1) * (double)sizeof(yif::InfMember);
+            }
+            const double ring = 2.0 * (2.0 * (double)W + 64.0) + 2.0 * (double)W + (double)W * 0.25 + fa_tables + bgzf_ring;
             const double held_w = (double)S.wtext[0].cap + (double)S.wtext[1].cap + (double)S.wout[0].cap + (double)S.wout[1].cap +
                                   (double)S.table.names.cap + (double)S.table.slots.cap + (double)S.bad_reg.cap +
-                                  (job.fasta ? held_line_tables() + held_record_tables() : 0.0);
+                                  (job.fasta ? held_line_tables() + held_record_tables() : 0.0) + (job.bgzf ? (double)inflate_window_held(e) : 0.0);
             if (!fits(ring + (double)name_bytes + (double)cap * 4.0 + (double)R * 21.0 + (double)G * 8.0, held_w)) return no_room_message();
             return YACRD_OK;
         }
@@ -1251,6 +1270,23 @@ struct SeqRun {
     //                     behind S(k + 2) — the copy pass of k + 1 has ended — and behind the writer's release of window k,
     //                     given when the last copy home or the last batch of the encoder that reads the slot has been waited for.
     //   control words     four sets in turn; a set is zeroed for window k + 4 behind the release of window k + 1.
+    //
+    // BGZF in.  The windows are the cuts of bgzf_windows.h: window k's new bytes are text[t0, t1) of cut k, at most
+    // W and possibly none, and they are not moved but inflated: this thread lands the stream's bytes [c0, c1) in the compressed
+    // slot (the mover, as above), brings the cut's slice of the member table up and launches inf_window_kernel and then
+    // sq_lines_kernel over the new tiles on the engine's stream, which waits for the landing's copy events.  The decoder's
+    // status word comes home with W1(k) and is read before the line count.  From W1(k) on the window is the one above.
+    //   compressed slot,  written by the mover for window k + 1 behind S(k); its last reader is the inflate of window k, which
+    //   one               was enqueued in front of W1(k): the engine's stream was empty at W1(k), at S'(k) and at S(k).  One slot
+    //                     suffices for that reason: nothing is gained by landing k + 1 while k inflates that the text slots'
+    //                     own order (land behind S(k)) would allow.
+    //   member slice      (grow-only, in the inflate scratch) reserved and filled behind S(k - 1), in front of window k's inflate.
+    //                     The engine's stream is NOT empty then — the pieces and copy pass of k - 1 are still enqueued —, but they
+    //                     never read the slice: its last reader, the inflate of k - 1, has ended by W1(k - 1), so a reserve that
+    //                     grows it frees nothing a kernel uses, and the refill is ordered on the same stream.
+    //   text slots        the inflate of window k writes slot k & 1 from offset W on — on the engine's stream, behind the copy
+    //                     pass of k - 2 (its last reader) and behind the carry kernel of k - 1, which wrote in front of W.
+    //   status word       one for the run, zeroed by inflate_window_open; only ever raised (atomicMax).
     struct WinPost { // a window handed to the writer
         int slot;
         u64 len; // bytes in the output slot: the tail of the window before (gzip out) and this window's output
@@ -1385,7 +1421,7 @@ struct SeqRun {
         ga.line_end = S.line_end.as<u64>(), ga.n_lines = n_lines;
         ga.tile0 = w.t_lo;
         ok = ev_open();
-        hipLaunchKernelGGL(yk::sq_index_kernel, dim3(w.t_hi - w.t_lo), dim3(yk::kGpT), 0, e->stream, ga);
+        if (w.t_hi > w.t_lo) hipLaunchKernelGGL(yk::sq_index_kernel, dim3(w.t_hi - w.t_lo), dim3(yk::kGpT), 0, e->stream, ga); // (BGZF in: a window of no bytes at all)
         if (!w.last) { // (the last window: its lines are whole records and its last byte is a newline — nothing is left)
             yk::SqCarry c{ga.line_end, n_rec, w.lo, w.hi, W, ga.text, S.wtext[w.ts ^ 1].as<unsigned char>(), w.ctl};
             hipLaunchKernelGGL(yk::sq_carry_kernel, dim3(64), dim3(256), 0, e->stream, c);
@@ -1403,7 +1439,7 @@ struct SeqRun {
         fa.hi = w.last ? 0 : w.hi;
         const dim3 line_grid((u32)((n_lines + 255) / 256));
         ok = ev_open();
-        hipLaunchKernelGGL(yk::sq_index_kernel, dim3(w.t_hi - w.t_lo), dim3(yk::kGpT), 0, e->stream, ga);
+        if (w.t_hi > w.t_lo) hipLaunchKernelGGL(yk::sq_index_kernel, dim3(w.t_hi - w.t_lo), dim3(yk::kGpT), 0, e->stream, ga);
         if (n_lines) hipLaunchKernelGGL(yk::fa_mark_kernel, line_grid, dim3(256), 0, e->stream, args(yk::Fasta{}));
         if (const int rc = scan_u32_to_u64(e, fa.head, n_lines, S.ln_rec.as<u64>(), S.part)) return rc;
         if (const int rc = scan_u32_to_u64(e, fa.bases, n_lines, S.base_before.as<u64>(), S.part)) return rc;
@@ -1429,12 +1465,49 @@ struct SeqRun {
         return YACRD_OK;
     }
 
+    // BGZF in: window `c`'s bytes of the compressed stream into the one compressed slot, its members inflated into
+    // the text slot's new bytes `dst` (one launch), the lines of the new tiles counted (one launch, avail = hi).  The engine's
+    // code of what failed, like every phase.  No launch per landed chunk: the window is the unit.
+    int inflate_window(const ybw::WindowCut &c, u64 k, char *dst, u64 hi, u32 w_tile, u32 t_hi, size_t chunk, bool &ok)
+    {
+        TextSource comp_src;
+        comp_src.mem = job.bgzf;
+        const double t0 = now_ms();
+        // (c0 is any byte of the stream: the mover reads the source with memcpy into its pinned arena and stores from the slot's
+        // first byte, which is 16-byte aligned — the copy kernel's only demand —, so nothing is rounded)
+        const int moved = move_text(e, comp_src, c.c0, c.c1 - c.c0, reinterpret_cast<char *>(iw.comp), comp_fresh, job.n_threads, [](u64, u64, u64) {}, chunk, &lanes);
+        comp_fresh = false;
+        inf_h2d_ms += (float)(now_ms() - t0);
+        if (const int rc = moved_code(moved)) return rc;
+        if (iev.v.size() < 2 * (size_t)k + 2 && !iev.add(2 * (size_t)k + 2 - iev.v.size())) HIP_TRY(why_not_added());
+        HIP_TRY(hipEventRecord(iev[2 * (size_t)k], e->stream));
+        if (const int rc = inflate_device_run_window(e, iw, e->stream, job.members->data() + c.m0, c.m1 - c.m0, c.c0, c.c1, c.t0, c.t1,
+                                                     reinterpret_cast<unsigned char *>(dst)))
+            return rc;
+        HIP_TRY(hipEventRecord(iev[2 * (size_t)k + 1], e->stream));
+        n_iev = 2 * (size_t)k + 2;
+        ga.avail = hi, ga.tile0 = w_tile;
+        ok = ok && ev_open();
+        if (t_hi > w_tile) hipLaunchKernelGGL(yk::sq_lines_kernel, dim3(t_hi - w_tile), dim3(yk::kGpT), 0, e->stream, ga);
+        ok = ok && ev_close();
+        return YACRD_OK;
+    }
+    // move_text's codes as the engine's, in one place
+    static int moved_code(int moved)
+    {
+        if (moved == 2) return fail(YACRD_EINVAL, "read error in the sequence file");
+        if (moved == 3) return fail(YACRD_ENOMEM, "sequence text to HBM: no pinned memory");
+        if (moved) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
+        return YACRD_OK;
+    }
+
     // window by window on this thread; the code of what it found, or the writer's
     template <class Format>
     int windows_loop()
     {
         using Piece = typename Format::Piece;
-        const u64 n_win = (n + W - 1) / W;
+        const bool bz = job.bgzf != nullptr; // the new bytes are inflated into the slot, window cuts[k] (plan), not moved
+        const u64 n_win = bz ? (u64)cuts.size() : (n + W - 1) / W;
         const size_t chunk = (size_t)std::min<u64>(kTextChunk, W);
         const u32 w_tile = (u32)(W / yk::kGpTile);
         u64 carry = 0, tail = 0, tail_at = 0; // of the window before: its carry; its ragged output tail and where it lies in its slot
@@ -1444,7 +1517,7 @@ struct SeqRun {
             if (win_stop.load()) return YACRD_OK; // (the writer's code: run_windows)
             const bool last = k + 1 == n_win;
             const int ts = (int)(k & 1), os = (int)(k & 1);
-            const u64 n_new = std::min(W, n - k * W), lo = W - carry, hi = W + n_new;
+            const u64 n_new = bz ? cuts[k].t1 - cuts[k].t0 : std::min(W, n - k * W), lo = W - carry, hi = W + n_new; // (BGZF in: n_new <= W, 0 too)
             const u32 t_lo = (u32)(lo / yk::kGpTile), t_hi = (u32)((hi + yk::kGpTile - 1) / yk::kGpTile);
             unsigned long long *ctl = S.ctl.as<unsigned long long>() + 8 * (k & 3);
             char *slot = S.wtext[ts].as<char>();
@@ -1459,7 +1532,7 @@ struct SeqRun {
             }
             ok = ok && ev_close();
             const double tm = now_ms();
-            const int moved = move_text(
+            const int rc_new = bz ? inflate_window(cuts[k], k, slot + W, hi, w_tile, t_hi, chunk, ok) : moved_code(move_text(
                 e, src, k * W, n_new, slot + W, win_fresh[ts], job.n_threads,
                 [&](u64 seg_begin, u64 seg_end, u64 avail) {
                     const bool end = seg_end >= n_new;
@@ -1470,18 +1543,21 @@ struct SeqRun {
                     if (t1 > t0) hipLaunchKernelGGL(yk::sq_lines_kernel, dim3(t1 - t0), dim3(yk::kGpT), 0, e->stream, ga);
                     ok = ok && ev_close();
                 },
-                chunk, &lanes);
+                chunk, &lanes));
             win_fresh[ts] = false;
             text_ms += now_ms() - tm;
-            if (moved == 2) return fail(YACRD_EINVAL, "read error in the sequence file");
-            if (moved == 3) return fail(YACRD_ENOMEM, "sequence text to HBM: no pinned memory");
-            if (moved || !ok) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
-            // the scan of the tiles' counts; the first wait: lines
+            if (rc_new) return rc_new;
+            if (!ok) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
+            // the scan of the tiles' counts; the first wait: lines (BGZF in: and the decoder's status word, read before anything the text says)
             ga.avail = hi;
             ok = ev_open();
             if (const int rc = scan_u32_to_u64(e, S.tile_nl.as<u32>() + t_lo, (u64)(t_hi - t_lo), S.tile_l0.as<u64>() + t_lo, S.part)) return rc;
             ok = ok && ev_close();
-            if (const int rc = bring_words(ok, {S.tile_l0.as<u64>() + t_hi, ctl})) return rc;
+            if (bz) {
+                if (const int rc = bring_words(ok, {S.tile_l0.as<u64>() + t_hi, ctl, iw.status})) return rc;
+                if ((u32)h_ctl[2]) return inflate_not_taken((u32)h_ctl[2]);
+            } else if (const int rc = bring_words(ok, {S.tile_l0.as<u64>() + t_hi, ctl}))
+                return rc;
             n_lines = h_ctl[0];
             if (h_ctl[1] & yk::kSqNeedHost) return fail(YACRD_EFALLBACK, "the text holds a CR: the host loop decides");
             // the window's tables (the engine's stream is empty: nothing reads the ones they replace), its records, its carry
@@ -1544,6 +1620,10 @@ struct SeqRun {
     double win_text_ms = 0;
     u64 win_count = 0, win_max_carry = 0;
     bool win_seen_head = false; // FASTA: a window so far had a whole header line
+    std::vector<ybw::WindowCut> cuts; // BGZF in: the windows (plan)
+    InflateWindow iw;                 // the compressed slot, the status word
+    bool comp_fresh = false;
+    size_t n_iev = 0; // the events of `iev` that were recorded: a pair per window's inflate
 
     // the ring, the writer thread, the windows; then what the two threads found
     int run_windows()
@@ -1553,6 +1633,10 @@ struct SeqRun {
             HIP_TRY(S.wtext[i].reserve((size_t)(2 * W + 64)));
             win_fresh[i] = S.wtext[i].p != before;
             HIP_TRY(S.wout[i].reserve(64));
+        }
+        if (job.bgzf) {
+            if (const int rcw = inflate_window_open(e, W, &iw)) return rcw;
+            comp_fresh = iw.fresh;
         }
         if (!cdone.add(2, hipEventDisableTiming)) HIP_TRY(why_not_added());
         if (job.gzip) {
@@ -1571,8 +1655,14 @@ struct SeqRun {
         if ((job.gzip ? gz_got != gz_sent : sink.at != total)) return fail(YACRD_EINTERNAL, "sequence editor: fewer bytes written than counted");
         for (size_t b = 0; b < gz_sent; b++) gz_kernel_ms += ev_ms(gev[2 * b], gev[2 * b + 1]);
         e->seq_windows[0] = win_count, e->seq_windows[1] = win_max_carry;
-        e->seq_windows[2] = S.wtext[0].cap + S.wtext[1].cap, e->seq_windows[3] = S.wout[0].cap + S.wout[1].cap;
+        e->seq_windows[2] = S.wtext[0].cap + S.wtext[1].cap + (job.bgzf ? inflate_window_held(e) : 0), e->seq_windows[3] = S.wout[0].cap + S.wout[1].cap;
         fill_gzip_stats(job.gzip_stats, total, sink.at, gz_members, gz_stored, gz_kernel_ms, out_busy_ms, put_ms);
+        if (job.gunzip_stats) { // as the whole-text run fills them (deliver), summed over the windows' landings and launches
+            for (size_t i = 0; i + 1 < n_iev; i += 2) inf_kernel_ms += ev_ms(iev[i], iev[i + 1]);
+            yacrd_gunzip_stats &u = *job.gunzip_stats; // (walk_ms: the caller's)
+            u.in_bytes = job.bgzf_bytes, u.out_bytes = n, u.n_members = job.members->size();
+            u.h2d_ms = inf_h2d_ms, u.kernel_ms = inf_kernel_ms, u.d2h_ms = 0.f;
+        }
         if (stats) {
             stats->text_bytes = n, stats->out_bytes = total, stats->n_records = n_rec, stats->n_out_records = n_pieces;
             stats->text_ms = (float)win_text_ms, stats->table_ms = (float)(t_table - t_start);
@@ -1620,13 +1710,15 @@ int run_seq_edit(yacrd_engine *e, const SeqJob &job, const TextSource &src, u64 
     DeviceGuard guard(e->device);
     SeqEditScratch *S = scratch_of<SeqEditScratch>(e);
     if (!S) return fail(YACRD_ENOMEM, "host allocation failed");
-    // The route.  A FASTQ or FASTA with its text in a file or in host memory runs in windows when the text is
-    // longer than a window and either the switch names a window or the whole-text run finds no room; every other text — BGZF
-    // in among them — runs whole.
+    // The route.  A FASTQ or FASTA — its text in a file, in host memory or, BGZF in, the Σ ISIZE bytes its
+    // members inflate to — runs in windows when the text is longer than a window and either the switch names a window or the
+    // whole-text run finds no room; every other text runs whole.  BGZF in: a window ends where a member ends (bgzf_windows.h)
+    // and is at least two tiles, the largest frame and the largest ISIZE.
     const u64 sw = e->seq_window;
     for (u64 &w : e->seq_windows) w = 0;
-    const bool may_window = !job.bgzf && sw != UINT64_MAX;
-    const u64 W = sw == 0 || sw == UINT64_MAX ? (u64)(kTextChunk * kTextSeg) : (sw + yk::kGpTile - 1) / yk::kGpTile * yk::kGpTile;
+    const bool may_window = sw != UINT64_MAX;
+    u64 W = sw == 0 || sw == UINT64_MAX ? (u64)(kTextChunk * kTextSeg) : (sw + yk::kGpTile - 1) / yk::kGpTile * yk::kGpTile;
+    if (job.bgzf) W = std::max<u64>(W, (ybw::kMinWindow + yk::kGpTile - 1) / yk::kGpTile * yk::kGpTile);
     bool windows = may_window && n > W && (sw != 0 || kSeqWindowsWhenFits);
     auto finish = [&](SeqRun &r, int rc) {
         (void)hipStreamSynchronize(e->stream); // (whatever failed: nothing of this call is in flight when its events go)
@@ -1650,6 +1742,7 @@ int run_seq_edit(yacrd_engine *e, const SeqJob &job, const TextSource &src, u64 
             for (DevBuf *b : {&S->line_end, &S->ln_head, &S->ln_bases, &S->ln_rec, &S->base_before, &S->rec_line, &S->rec_width}) b->release();
     }
     S->text.release(), S->out.release(); // (the whole-text run's: the ring is what a run in windows holds)
+    if (job.bgzf) inflate_device_release_whole(e); // (and the whole stream's buffer and member table in the inflate scratch)
     SeqRun r{e, job, src, n, sink, stats, *S};
     r.W = W;
     int rc = r.plan();

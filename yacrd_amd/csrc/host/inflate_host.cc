@@ -11,6 +11,7 @@
 #include "../../../include/yacrd_host.h"
 #include "../bgzf_plan.h"
 #include "../bgzf_walk.h"
+#include "../bgzf_windows.h"
 #include "../inflate_block.h"
 #include "host_common.h"
 
@@ -78,6 +79,27 @@ int yacrd_bgzf_plan_segments(const char *data, uint64_t n, const uint64_t *lande
         mo[4 * k] = members[k].in_off, mo[4 * k + 1] = members[k].csize, mo[4 * k + 2] = members[k].isize, mo[4 * k + 3] = members[k].out_off;
     if (!steps.empty()) std::memcpy(so, steps.data(), steps.size() * sizeof(uint64_t));
     *members_out = mo, *n_members = members.size(), *steps_out = so, *n_steps = steps.size() / 8;
+    return 0;
+}
+
+int yacrd_bgzf_window_cuts(const char *data, uint64_t n, uint64_t window_bytes, uint64_t **cuts_out, uint64_t *n_cuts)
+{
+    if ((!data && n) || !cuts_out || !n_cuts) return yh::fail("bad argument");
+    *cuts_out = nullptr, *n_cuts = 0;
+    std::vector<yif::InfMember> members;
+    uint64_t total = 0;
+    if (!ybw::walk(reinterpret_cast<const unsigned char *>(data ? data : ""), n, members, &total)) return yh::fail("not BGZF");
+    if (window_bytes < ybw::kMinWindow) return yh::fail("a BGZF window is at least 65 536 bytes");
+    std::vector<ybw::WindowCut> cuts;
+    if (!ybw::window_cuts(members.data(), members.size(), window_bytes, cuts)) return yh::fail("host allocation failed");
+    uint64_t *co = (uint64_t *)std::malloc((cuts.size() * 6 + 1) * sizeof(uint64_t));
+    if (!co) return yh::fail("host allocation failed");
+    for (size_t k = 0; k < cuts.size(); k++) {
+        const ybw::WindowCut &w = cuts[k];
+        uint64_t *o = co + 6 * k;
+        o[0] = w.m0, o[1] = w.m1, o[2] = w.c0, o[3] = w.c1, o[4] = w.t0, o[5] = w.t1;
+    }
+    *cuts_out = co, *n_cuts = cuts.size();
     return 0;
 }
 

@@ -89,4 +89,30 @@ YK_LOCAL int bgzf_text_ends(const unsigned char *comp, uint64_t comp_bytes, cons
     return 0;
 }
 
+// bgzf_text_ends' second answer alone, for a caller that asks nothing of the first line (gpu_seq_edit.hip: a BGZF FASTQ /
+// FASTA in windows, before its first launch): *ends_nl, whether the text's last byte is a newline (true for a text of no
+// bytes), from the last member that holds text.  Returns 0; 1: the decoder does not take that member (*status says which
+// cause); 3: no memory.
+YK_LOCAL int bgzf_last_byte(const unsigned char *comp, uint64_t comp_bytes, const yif::InfMember *members, uint64_t n_members, bool *ends_nl,
+                            uint32_t *status)
+{
+    *ends_nl = true, *status = yif::kInfOk;
+    uint64_t last = n_members;
+    while (last > 0 && !members[last - 1].isize) last--;
+    if (!last) return 0; // a text of no bytes
+    const yif::InfMember &m = members[last - 1];
+    if (m.isize > yif::kMaxOut || m.in_off > comp_bytes || comp_bytes - m.in_off < (uint64_t)m.csize + 8u) {
+        *status = yif::kInfTable;
+        return 1;
+    }
+    std::unique_ptr<yif::InfShared> sh(new (std::nothrow) yif::InfShared());
+    std::unique_ptr<unsigned char[]> out(new (std::nothrow) unsigned char[yif::kMaxOut]);
+    if (!sh || !out) return 3;
+    const unsigned char *t = comp + m.in_off + m.csize;
+    const uint32_t crc = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+    if ((*status = yif::inf_decode_member(*sh, comp + m.in_off, m.csize, m.isize, crc, out.get())) != yif::kInfOk) return 1;
+    *ends_nl = out[m.isize - 1] == '\n';
+    return 0;
+}
+
 } // namespace yke

@@ -808,14 +808,16 @@ class Engine:
     def debug_seq_window(self, window_bytes):
         """yacrd_debug_seq_window (tests, A/B): the FASTQ and FASTA editors' window.  0: the policy (128 MiB windows where the whole text
         finds no room); 2**64 - 1: never windows; any other value: rounded up to a 32 KiB tile, and every FASTQ or FASTA text longer
-        than it is edited window by window (csrc/gpu_seq_edit.hip: run_windows).  The bytes written do not depend on it."""
+        than it is edited window by window (csrc/gpu_seq_edit.hip: run_windows).  The BGZF-in forms take at least 64 KiB and end
+        their windows where members end (host.bgzf_window_cuts).  The bytes written do not depend on it."""
         self._lib.yacrd_debug_seq_window.restype = ctypes.c_int
         self._lib.yacrd_debug_seq_window.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
         _check(self._lib, self._lib.yacrd_debug_seq_window(self._h, int(window_bytes)))
 
     def seq_windows(self):
         """yacrd_debug_seq_windows (tests, tools): what the last sequence edit ran as: its windows (0: the whole text at
-        once), the longest carry in bytes, the device bytes of its text ring and of its output ring."""
+        once), the longest carry in bytes, the device bytes of its text ring (BGZF in: with the compressed slot and the member
+        slice) and of its output ring."""
         out = (ctypes.c_uint64 * 4)()
         self._lib.yacrd_debug_seq_windows.restype = None
         self._lib.yacrd_debug_seq_windows.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
@@ -1028,12 +1030,14 @@ class Engine:
     def edit_fastq_bgzf(self, op, blob, names, lengths, result, out_path=None):
         """yacrd_engine_edit_fastq_bgzf_mem / _file: edit_fastq_gzip over the COMPRESSED file `blob` (BGZF; bytes or anything
         else with the buffer protocol): it crosses the link as it is and is inflated on the device.  The result is
-        edit_fastq_gzip's for the inflated text; the inflate's stats are in self.gunzip_stats.  Raises NeedsHostParser, with
-        nothing written, also when `blob` is not BGZF or holds a member the device decoder does not take."""
+        edit_fastq_gzip's for the inflated text; the inflate's stats are in self.gunzip_stats.  A text of more than a window
+        that finds no room whole (or with debug_seq_window set) is inflated and edited window by window, the windows cut where
+        members end (host.bgzf_window_cuts; seq_windows() says how the edit ran).  Raises NeedsHostParser, with nothing
+        written, also when `blob` is not BGZF or holds a member the device decoder does not take."""
         return self._edit_seq_gzip("fastq", op, blob, names, lengths, result, out_path, bgzf=True)
 
     def edit_fasta_bgzf(self, op, blob, names, lengths, result, out_path=None):
-        """yacrd_engine_edit_fasta_bgzf_mem / _file: edit_fastq_bgzf for FASTA."""
+        """yacrd_engine_edit_fasta_bgzf_mem / _file: edit_fastq_bgzf for FASTA, in windows under the same rule."""
         return self._edit_seq_gzip("fasta", op, blob, names, lengths, result, out_path, bgzf=True)
 
     def gunzip(self, data):

@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = [
     "yacrd_edit_file", "yacrd_edit_file_mt", "yacrd_text_from_file", "yacrd_text_free", "yacrd_report_read", "yacrd_report_get", "yacrd_report_free",
     "yacrd_edit_file_to", "yacrd_file_compression", "yacrd_bgzf_encode_host", "yacrd_bgzf_decode_host", "yacrd_bytes_free", "yacrd_deflate_code_lengths",
     "yacrd_synth_fastq", "yacrd_ingest_stream", "yacrd_ingest_stream_memory", "yacrd_csr_handle_map", "yacrd_bgzf_plan_segments",
-    "yacrd_bgzf_text_ends",
+    "yacrd_bgzf_text_ends", "yacrd_bgzf_window_cuts",
 ]
 
 OP_SCRUBB, OP_FILTER, OP_EXTRACT, OP_SPLIT = 0, 1, 2, 3
@@ -167,6 +167,8 @@ def load_library():
                                                  ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)]
         lib.yacrd_bgzf_text_ends.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32),
                                              ctypes.POINTER(ctypes.c_int)]
+        lib.yacrd_bgzf_window_cuts.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p),
+                                               ctypes.POINTER(ctypes.c_uint64)]
         lib.yacrd_bytes_free.argtypes = [ctypes.c_void_p]
         lib.yacrd_bytes_free.restype = None
         lib.yacrd_deflate_code_lengths.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
@@ -417,6 +419,22 @@ def bgzf_text_ends(blob, delim):
     nf, nl = ctypes.c_uint32(), ctypes.c_int()
     _check(lib, lib.yacrd_bgzf_text_ends(blob, len(blob), int(d), ctypes.byref(nf), ctypes.byref(nl)))
     return int(nf.value), bool(nl.value)
+
+
+def bgzf_window_cuts(blob, W):
+    """yacrd_bgzf_window_cuts: where the windows of a BGZF text end (csrc/bgzf_windows.h) -> [(m0, m1, c0, c1, t0, t1)], one
+    per window: its members, its bytes of the compressed stream, its bytes of the text.  A window takes members while both
+    its text and its stream bytes are at most W, and always one.  Raises HostError for a stream that is not BGZF and for
+    W < 65 536."""
+    lib = load_library()
+    blob = bytes(blob)
+    co, nc = ctypes.c_void_p(), ctypes.c_uint64()
+    _check(lib, lib.yacrd_bgzf_window_cuts(blob, len(blob), int(W), ctypes.byref(co), ctypes.byref(nc)))
+    try:
+        cuts = np.frombuffer(ctypes.string_at(co.value, int(nc.value) * 48), dtype=np.uint64).reshape(-1, 6)
+        return [tuple(int(x) for x in row) for row in cuts]
+    finally:
+        lib.yacrd_bytes_free(co)
 
 
 def deflate_code_lengths(freq, limit):
