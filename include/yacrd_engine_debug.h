@@ -117,6 +117,21 @@ void yacrd_debug_big_routes(const yacrd_engine *e, uint64_t out[4]);
  * end every window where a member ends (csrc/bgzf_windows.h), so a window brings at most window_bytes of text and of
  * compressed stream, possibly no text at all.  Stays with the engine until set again.  Tests and A/B runs only. */
 int yacrd_debug_seq_window(yacrd_engine *e, uint64_t window_bytes);
+/* the batch size from which THIS engine takes the long-batch forms of the plan and of the follow-on step (csrc/plan_compact.h:
+ * plan_kernel<4>; csrc/finish_compact.h: mark_list_kernel, deferred_list_kernel — the deferred reads two per wavefront through the
+ * filtered exact sweep of csrc/sweep_filtered.h — and scan_compact_kernel<4>): batches of `min_reads` reads and more do, smaller
+ * ones take the short forms.  The result does not depend on it.
+ *   min_reads == 0            every batch is long;
+ *   min_reads == UINT64_MAX   the default again: 400 000 reads (kPlanSmallReads), or what YACRD_SPLIT_MIN_READS said when the
+ *                             library was loaded;
+ * Which batches go out DIRECT (YACRD_F_SCREEN_DIRECT above) and which as one launch keep their own size rules.  Not while a
+ * submitted batch is pending (YACRD_EINVAL).  Stays with the engine until set again.  Tests and A/B runs only: with
+ * YACRD_F_COUNT_PREFILTERED the counter block's deferred_sorted (yacrd_debug_last_counters) then says how many of the deferred
+ * reads the filtered sweep left to the whole-read sort. */
+int yacrd_debug_long_min_reads(yacrd_engine *e, uint64_t min_reads);
+/* the compute units the engine sizes its resident grids by (deferred_list_kernel: YK_LIST_OCC * 256 / YK_LIST_THREADS workgroups on
+ * each); tests: whether a batch's list of marked reads is long enough for a workgroup's second turn */
+uint64_t yacrd_debug_compute_units(const yacrd_engine *e);
 /* what the engine's last sequence edit (FASTQ or FASTA, any form) ran as: [0] its windows (0: the whole text at once), [1] the
  * longest carry — the bytes a window left behind its last whole record for the next one —, [2] device bytes its two text
  * slots held (BGZF in: with the compressed slot and the member slice), [3] device bytes its two output slots held.  A failed

@@ -187,10 +187,9 @@ def test_paths_agree_with_each_other(engine, engine_general, engine_lds):
 
 
 # ---- edge cases -------------------------------------------------------------------------------
-def test_region_buffer_outgrown_and_counters_handed_over():
-    """bad_regions starts at 4 R + 1024 entries; reads with hundreds of gaps each outgrow it: the follow-on kernel's
-    last slab hands the counters over with the overflow flag derived from the total (finish_compact.h), the host
-    grows the buffer and redoes the follow-on kernel only.  A fresh engine per case (buffers only grow)."""
+def _region_outgrowing_inputs():
+    """(n_reads, per_read, cov, (offsets, intervals, lengths), the oracle's answer): reads with hundreds of gaps each, which
+    outgrow the 4 R + 1024 entries bad_regions starts with (tests/test_gpu_follow_on.py runs them on the long-batch form too)"""
     for n_reads, per_read, cov in ((50, 400, 0), (1500, 120, 0), (3000, 9, 0), (40, 3000, 1)):
         rng = np.random.default_rng(n_reads)
         offs, ivs, lens = [0], [], []
@@ -207,6 +206,14 @@ def test_region_buffer_outgrown_and_counters_handed_over():
         ln = np.array(lens, np.uint32)
         want = oracle.run(off, iv, ln.astype(np.uint64), cov, 0.4, n_threads=2)
         assert int(want[0][-1]) > 4 * n_reads + 1024  # the case does outgrow the first allocation
+        yield n_reads, per_read, cov, (off, iv, ln), want
+
+
+def test_region_buffer_outgrown_and_counters_handed_over():
+    """bad_regions starts at 4 R + 1024 entries; reads with hundreds of gaps each outgrow it: the follow-on kernel's
+    last slab hands the counters over with the overflow flag derived from the total (finish_compact.h), the host
+    grows the buffer and redoes the follow-on kernel only.  A fresh engine per case (buffers only grow)."""
+    for n_reads, per_read, cov, (off, iv, ln), want in _region_outgrowing_inputs():
         with yacrd_amd.Engine() as e:
             assert_same(e.run(off, iv, ln, cov, 0.4), want, "first run %d x %d" % (n_reads, per_read))
             assert_same(e.run(off, iv, ln, cov, 0.4), want, "second run")
@@ -297,6 +304,15 @@ def test_class_prediction_is_validated(flags):
     waiting for the plan; a batch whose classes differ must still come out bit-exact.  With the
     deferring build as well: its remainder launches (SweepArgs.first > 0) mark and finish their own
     reads."""
+    with yacrd_amd.Engine(flags=flags) as e, yacrd_amd.Engine(flags=flags | yacrd_amd.F_NO_PREDICTION) as ref:
+        for rep, csr, want in _prediction_batches():
+            assert_same(e.run(*csr, 3, 0.4), want, "predicted run %d" % rep)
+            assert_same(ref.run(*csr, 3, 0.4), want, "unpredicted run %d" % rep)
+
+
+def _prediction_batches():
+    """(rep, csr, the oracle's answer at c = 3): thirteen batches of 600 reads and 60 000 intervals whose classes change from one
+    to the next (tests/test_gpu_follow_on.py runs them on the long-batch form too)"""
     R = 600
     a_sizes = [100] * R                                    # everything in one class
     b_sizes = [10] * 300 + [190] * 299 + [60000 - 3000 - 299 * 190]  # same totals, other classes
@@ -306,14 +322,12 @@ def test_class_prediction_is_validated(flags):
     d_sizes = [100] * 200 + [36] * 200 + [164] * 200
     e_sizes = [100] * 400 + [36] * 100 + [164] * 100
     assert sum(d_sizes) == sum(e_sizes) == 60000
-    with yacrd_amd.Engine(flags=flags) as e, yacrd_amd.Engine(flags=flags | yacrd_amd.F_NO_PREDICTION) as ref:
-        for rep, sizes in enumerate([a_sizes, a_sizes, b_sizes, b_sizes, c_sizes, a_sizes, c_sizes,
-                                     d_sizes, d_sizes, e_sizes, e_sizes, a_sizes, d_sizes]):
-            csr = make_csr(1200 + rep, sizes, REGULAR_MODES + ("degenerate",), len_lo=300000,
-                           len_hi=900000)
-            want = oracle.run(csr[0], csr[1], csr[2].astype(np.uint64), 3, 0.4, n_threads=4)
-            assert_same(e.run(*csr, 3, 0.4), want, "predicted run %d" % rep)
-            assert_same(ref.run(*csr, 3, 0.4), want, "unpredicted run %d" % rep)
+    for rep, sizes in enumerate([a_sizes, a_sizes, b_sizes, b_sizes, c_sizes, a_sizes, c_sizes,
+                                 d_sizes, d_sizes, e_sizes, e_sizes, a_sizes, d_sizes]):
+        csr = make_csr(1200 + rep, sizes, REGULAR_MODES + ("degenerate",), len_lo=300000,
+                       len_hi=900000)
+        want = oracle.run(csr[0], csr[1], csr[2].astype(np.uint64), 3, 0.4, n_threads=4)
+        yield rep, csr, want
 
 
 def _crafted_screen_reads(ns=(65, 100, 128, 129, 200, 256), Ls=(1, 7, 15, 16, 17, 33, 1000, 65537, 10**6),

@@ -103,6 +103,9 @@ struct Counters {
     // them held a 10 us kernel for 22 us, 3 300 returning ones a 20 us kernel for 45 us; and on the cache
     // line of n[], which every wavefront of a sweep reads when it starts, they stall those loads as well.)
     alignas(128) u32 deferred;
+    // of those, the reads deferred_list_kernel's filtered sweep (sweep_filtered.h) left and the kernel sorted whole: one atomic
+    // per workgroup, only counted when asked (prefilter == 2).  (In what was padding: no other field moves.)
+    u32 deferred_sorted;
     u64 deferred_iv;
 };
 

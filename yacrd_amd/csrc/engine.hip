@@ -56,7 +56,8 @@ static uint64_t defer_min_intervals()
 static constexpr uint32_t kProbeEvery = 16;
 
 // Batches of this many reads and more take the follow-on step as kernels of its own (finish_compact.h: mark_list_kernel +
-// deferred_list_kernel + scan_compact_kernel); YACRD_SPLIT_MIN_READS overrides (A/B: 0 = always, a huge number = never).
+// deferred_list_kernel + scan_compact_kernel) and the plan as plan_kernel<4>; YACRD_SPLIT_MIN_READS overrides (A/B: 0 = always, a
+// huge number = never).  The default of yacrd_engine::long_min_reads, which yacrd_debug_long_min_reads sets per engine (tests).
 static uint64_t split_min_reads()
 {
     static const uint64_t v = env_u64("YACRD_SPLIT_MIN_READS", (uint64_t)yk::kPlanSmallReads);
@@ -132,7 +133,7 @@ int launch_compact(yacrd_engine *e, const Run &R)
 {
     const u32 n_reads = R.n_reads;
     const yk::CompactArgs2 ca = compact_args(e, R);
-    if (R.n_reads64 >= split_min_reads()) {
+    if (R.long_form) {
         if (R.screened) {
             // the marks listed, the list dealt out evenly over a grid that is resident as a whole (finish_compact.h)
             const u32 slabs = (n_reads + yk::kMarkReads - 1) / yk::kMarkReads;
@@ -408,7 +409,8 @@ int reserve_buffers(yacrd_engine *e, Run &R)
     constexpr int kLists = yk::CLS_COUNT + 9; // class lists + three rejection lists + M2 overflow + what the screens leave of M1 / M2 / BIG + what the one-wavefront screen leaves of M1 / M2
     HIP_TRY(e->lists.reserve((size_t)kLists * n_reads * sizeof(u32)));
     // (long batches: + the shard counters of the follow-on step's list of marked reads, behind the scan words)
-    const size_t shard_ctr_bytes = (!R.one_launch && n_reads64 >= split_min_reads()) ? (size_t)yk::kDeferShards * yk::kDeferShardStride * sizeof(u32) : 0;
+    R.long_form = n_reads64 >= e->long_min_reads;
+    const size_t shard_ctr_bytes = (!R.one_launch && R.long_form) ? (size_t)yk::kDeferShards * yk::kDeferShardStride * sizeof(u32) : 0;
     R.ctrl_bytes = (sizeof(yk::Counters) + (size_t)R.nb * sizeof(u64) + shard_ctr_bytes + 255) & ~(size_t)255;
     e->compact_calls = 0;
     e->ctrl_cur ^= 1;
@@ -484,7 +486,7 @@ int launch_plan(yacrd_engine *e, Run &R)
         if (R.full) HIP_TRY(hipEventRecord(e->ev[EV_PLAN], e->side));
         return YACRD_OK;
     }
-    if (n_reads < yk::kPlanSmallReads)
+    if (!R.long_form)
         hipLaunchKernelGGL((yk::plan_kernel<1, yk::kPlanSmallBlock>), dim3((n_reads + yk::kPlanSmallBlock - 1) / yk::kPlanSmallBlock),
                            dim3(yk::kPlanSmallBlock), 0, e->stream, R.d_off, n_reads, R.lists, R.ctr, plan_mode, e->ctrl2[other].as<u32>(), (u32)(R.other_bytes / 4), e->counts.as<u32>(), e->mrec.as<uint4>(), R.mrec_cap1, R.mrec_cap2);
     else // (eight reads per thread — 611 workgroups instead of 1 221 on configs[4] — measured 32.0 us against 29.9: profiles/r05/m_*)
@@ -1488,6 +1490,15 @@ int yacrd_debug_last_input_csr(yacrd_engine *e, uint64_t *n_reads, uint64_t *n_i
 
 /* include/yacrd_engine_debug.h: what DevBuf / PinBuf hold, process-wide (tests) */
 uint64_t yacrd_debug_direct_runs(const yacrd_engine *e) { return e ? e->direct_runs : 0; }
+uint64_t yacrd_debug_compute_units(const yacrd_engine *e) { return e ? (uint64_t)e->num_cu : 0; }
+/* include/yacrd_engine_debug.h: the batch size from which this engine takes the long-batch forms (tests) */
+int yacrd_debug_long_min_reads(yacrd_engine *e, uint64_t n)
+{
+    if (!e) return fail(YACRD_EINVAL, "null argument");
+    if (e->pending.active || e->host_pending) return fail(YACRD_EINVAL, "the engine has a submitted batch pending");
+    e->long_min_reads = n == UINT64_MAX ? split_min_reads() : n;
+    return YACRD_OK;
+}
 void yacrd_debug_big_routes(const yacrd_engine *e, uint64_t out[4])
 {
     for (int i = 0; i < 4; i++) out[i] = e ? e->big_routes[i] : 0;
@@ -1521,6 +1532,7 @@ int yacrd_engine_create(const yacrd_engine_cfg *cfg, yacrd_engine **out)
     if (!e) return fail(YACRD_ENOMEM, "host allocation failed");
     e->device = dev;
     e->flags = cfg ? cfg->flags : 0;
+    e->long_min_reads = split_min_reads();
     e->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     {
         int xcc = 0;

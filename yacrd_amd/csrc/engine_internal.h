@@ -230,6 +230,7 @@ struct Run {
     bool tight_grids = false; // predicted register classes get grids with a margin, not grids for every read
     u32 prefilter = 0;        // SweepArgs.prefilter
     bool one_launch = false;  // the batch goes out as one_batch_kernel (one_batch.h)
+    bool long_form = false;   // the plan and the follow-on step take their long-batch forms (yacrd_engine::long_min_reads, as reserve_buffers found it)
     // the control block in use, its scan-state words, and what the plan zeroes of the other block
     yk::Counters *ctr = nullptr;
     u32 nb = 0, ob_slabs = 0;
@@ -388,6 +389,9 @@ struct yacrd_engine {
     // windows; else the window's bytes) and what yacrd_debug_seq_windows reports of the last sequence edit
     uint64_t seq_window = 0;
     uint64_t seq_windows[4] = {0, 0, 0, 0};
+    // batches of this many reads and more take the long-batch forms of the plan and the follow-on step (engine.hip:
+    // split_min_reads is the default; yacrd_debug_long_min_reads sets it, tests)
+    uint64_t long_min_reads = 0;
     bool gzip_busy = false; // a yacrd_gzip_writer or an edit to gzip holds the kGzip slot: trim leaves it alone
 };
 

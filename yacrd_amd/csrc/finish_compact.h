@@ -382,7 +382,7 @@ __global__ __launch_bounds__(kListThreads, YK_LIST_OCC) void deferred_list_kerne
     __shared__ u32 sc[kWaves + 1];
     __shared__ uint4 s_list[kListThreads]; // read, intervals, length
     __shared__ unsigned short s_fb[kListThreads];
-    __shared__ u32 s_nfb;
+    __shared__ u32 s_nfb, s_sorted;
     __shared__ unsigned long long s_iv;
     const u32 tid = threadIdx.x, lane = lane_id(), wv = tid >> 6;
     u32 total;
@@ -396,7 +396,7 @@ __global__ __launch_bounds__(kListThreads, YK_LIST_OCC) void deferred_list_kerne
     const u32 lo = (u32)min((u64)total, (u64)blockIdx.x * per), hi = (u32)min((u64)total, (u64)lo + per);
     if (lo >= hi) return; // (uniform)
     const LaneConst lcf = make_lane_const(lane);
-    if (tid == 0) s_iv = 0;
+    if (tid == 0) s_iv = 0, s_sorted = 0;
     for (u32 c0 = lo; c0 < hi; c0 += (u32)kListThreads) { // (uniform)
         __syncthreads(); // (s_pre is written; the last round's lists are done with — every wavefront has read its s_nfb)
         if (tid == 0) s_nfb = 0; // (behind the barrier: ADVICE r5 — in front of it, a wavefront still on its way to the last round's
@@ -424,6 +424,7 @@ __global__ __launch_bounds__(kListThreads, YK_LIST_OCC) void deferred_list_kerne
         }
         __syncthreads();
         const u32 nfb = s_nfb;
+        if (a.prefilter == 2 && tid == 0) s_sorted += nfb; // (only counted when asked; nobody else touches it before the kernel's end)
         for (u32 i = wv; i < nfb; i += kWaves) { // (uniform in the wavefront): sorted whole, one read per wavefront
             const uint4 q = s_list[s_fb[i]];
             const u64 o = a.off[q.x];
@@ -435,6 +436,7 @@ __global__ __launch_bounds__(kListThreads, YK_LIST_OCC) void deferred_list_kerne
     if (tid == 0) {
         atomicAdd((unsigned long long *)&a.ctr->deferred_iv, s_iv);
         atomicAdd(&a.ctr->deferred, hi - lo);
+        if (a.prefilter == 2) atomicAdd(&a.ctr->deferred_sorted, s_sorted);
     }
 }
 

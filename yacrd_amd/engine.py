@@ -37,7 +37,7 @@ F_NO_SCREEN_DIRECT = 16777216  # ... never (A/B)
 DEBUG_SYMBOLS = [
     "yacrd_debug_sort_pairs", "yacrd_debug_last_counters", "yacrd_debug_last_input_csr", "yacrd_debug_peer_copy_counts",
     "yacrd_debug_live_bytes", "yacrd_debug_direct_runs", "yacrd_debug_big_routes",
-    "yacrd_debug_seq_window", "yacrd_debug_seq_windows",
+    "yacrd_debug_seq_window", "yacrd_debug_seq_windows", "yacrd_debug_long_min_reads", "yacrd_debug_compute_units",
 ]
 F_ONE_LAUNCH = 4194304  # include/yacrd_engine.h: a short batch as ONE kernel launch (csrc/one_batch.h)
 
@@ -777,13 +777,17 @@ class Engine:
                         ("scan_ticket", ctypes.c_uint32), ("ob_unsupported", ctypes.c_uint32), ("prefiltered", ctypes.c_uint32),
                         ("over_med", ctypes.c_uint32), ("fb_med", ctypes.c_uint32 * 2), ("fb_big", ctypes.c_uint32),
                         ("fbq_head", ctypes.c_uint32 * 2), ("fbq_done", ctypes.c_uint32 * 2), ("bs_chunks", ctypes.c_uint32),
-                        ("fused_gave_up", ctypes.c_uint32), ("total_regions", ctypes.c_uint64)]
+                        ("fused_gave_up", ctypes.c_uint32), ("total_regions", ctypes.c_uint64), ("fb_stream", ctypes.c_uint32 * 2),
+                        ("_pad", ctypes.c_uint32 * 26),  # (alignas(128): deferred begins a cache line)
+                        ("deferred", ctypes.c_uint32), ("deferred_sorted", ctypes.c_uint32), ("deferred_iv", ctypes.c_uint64)]
         c = _Counters()
         self._lib.yacrd_debug_last_counters.restype = ctypes.c_uint64
         self._lib.yacrd_debug_last_counters.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
         self._lib.yacrd_debug_last_counters(self._h, ctypes.byref(c), ctypes.sizeof(c))
         out = {}
         for n, _ in _Counters._fields_:
+            if n == "_pad":
+                continue
             v = getattr(c, n)
             out[n] = list(v) if hasattr(v, "__len__") else int(v)
         return out
@@ -813,6 +817,21 @@ class Engine:
         self._lib.yacrd_debug_seq_window.restype = ctypes.c_int
         self._lib.yacrd_debug_seq_window.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
         _check(self._lib, self._lib.yacrd_debug_seq_window(self._h, int(window_bytes)))
+
+    def debug_long_min_reads(self, min_reads):
+        """yacrd_debug_long_min_reads (tests, A/B): batches of `min_reads` reads and more take the long-batch forms of the plan and
+        the follow-on step on this engine (csrc/finish_compact.h: the marks listed, the deferred reads through the filtered exact
+        sweep, what it leaves sorted whole — debug_counters()["deferred_sorted"] with F_COUNT_PREFILTERED).  0: every batch;
+        2**64 - 1: the default again (400 000 reads, or YACRD_SPLIT_MIN_READS).  The result does not depend on it."""
+        self._lib.yacrd_debug_long_min_reads.restype = ctypes.c_int
+        self._lib.yacrd_debug_long_min_reads.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
+        _check(self._lib, self._lib.yacrd_debug_long_min_reads(self._h, int(min_reads)))
+
+    def compute_units(self):
+        """yacrd_debug_compute_units (tests): the compute units the engine sizes its resident grids by."""
+        self._lib.yacrd_debug_compute_units.restype = ctypes.c_uint64
+        self._lib.yacrd_debug_compute_units.argtypes = [ctypes.c_void_p]
+        return int(self._lib.yacrd_debug_compute_units(self._h))
 
     def seq_windows(self):
         """yacrd_debug_seq_windows (tests, tools): what the last sequence edit ran as: its windows (0: the whole text at
