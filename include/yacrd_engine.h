@@ -397,9 +397,14 @@ int yacrd_engine_trim(yacrd_engine *e);
  * hand out), read_type[r] its type.
  * YACRD_EFALLBACK, with nothing written: a '"' or a CR anywhere in the text, a line whose field count differs from the first
  * non-empty line's or is too small to hold the second id, a line that reaches more than 4 MiB beyond its 128 MiB segment, a
- * compressed or non-regular input, an output path that exists and is no regular file (or is the input), device memory that does
- * not hold the text, as many bytes again and an eighth.  The caller then runs yacrd_edit_file, which knows the csv syntax, the
- * codecs and the reference's messages.  The file form writes beside out_path and renames when the last byte is in.
+ * compressed or non-regular input, an output path that exists and is no regular file (or is the input).  The caller then runs
+ * yacrd_edit_file, which knows the csv syntax, the codecs and the reference's messages.  The file form writes beside out_path
+ * and renames when the last byte is in.
+ * Memory: the run holds the text, as many bytes again and an eighth.  A plain text of more than 128 MiB that finds no such
+ * room is edited window by window instead (128 MiB of text at a time in a ring of about 0.55 GB, the same
+ * bytes; this form without the mirror, _mem, _gzip_mem and _gzip_file): a line may then reach 4 MiB into the next window, one
+ * that reaches farther is YACRD_EFALLBACK like the line above.  YACRD_EFALLBACK for room is left to a device that does not
+ * hold the ring, and to the _bgzf_ and _resident_ forms and the edit from the mirror, which always run whole.
  * When in_path is the very file (device, inode, size, mtime) the engine's last yacrd_engine_ingest_overlaps parsed and its mirror
  * is still in HBM, the text is not moved again (stats: mirror_reused = 1).
  * op: YACRD_OP_FILTER (1) or YACRD_OP_EXTRACT (2) of yacrd_host.h; format: 0 = by name, 1 = PAF, 2 = M4 / MHAP; n_threads: copy

@@ -137,6 +137,21 @@ uint64_t yacrd_debug_compute_units(const yacrd_engine *e);
  * slots held (BGZF in: with the compressed slot and the member slice), [3] device bytes its two output slots held.  A failed
  * edit in windows leaves [0] = 0. */
 void yacrd_debug_seq_windows(const yacrd_engine *e, uint64_t out[4]);
+/* the overlap editor's windows (csrc/gpu_edit.hip): yacrd_engine_edit_overlaps, _mem, _gzip_mem and _gzip_file
+ * run a text of more than one window window by window, in a bounded ring of buffers; the bytes written do not depend on it.
+ * The _bgzf_ and _resident_ forms and an edit from the parser's mirror always run whole.
+ *   window_bytes == 0            the policy: a window of 128 MiB, taken where the whole-text run finds no room (and, if the
+ *                                build's measured default says so, for every text of more than one window);
+ *   window_bytes == UINT64_MAX   never windows: the whole text at once, YACRD_EFALLBACK where it finds no room;
+ *   any other value              rounded up to a whole 32 KiB tile; every text longer than it runs in windows.  The mover's
+ *                                chunk becomes min(4 MiB, the window): a line may reach that far into the next window, one
+ *                                that reaches farther is YACRD_EFALLBACK.
+ * Stays with the engine until set again.  Tests and A/B runs only. */
+int yacrd_debug_edit_window(yacrd_engine *e, uint64_t window_bytes);
+/* what the engine's last overlap edit (any form) ran as: [0] its windows (0: the whole text at once), [1] the farthest a line
+ * that began in one window reached into the next, in bytes, [2] device bytes of its two text slots, [3] device bytes of
+ * its two output slots.  A failed edit in windows leaves [0] = 0. */
+void yacrd_debug_edit_windows(const yacrd_engine *e, uint64_t out[4]);
 /* YACRD_TEST_REPORT_SEGMENT=<bytes> (environment, tests; read at every call): the size of the segments in which
  * yacrd_engine_write_report[_mem] brings the formatted text home, instead of 64 MiB (csrc/gpu_report_write.hip: kReportSegment;
  * 1 .. 2^30).  The bytes written do not depend on it: tests/test_gpu_report_write.py cuts lines at hundreds of borders. */

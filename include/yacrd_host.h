@@ -178,6 +178,13 @@ int yacrd_bgzf_text_ends(const char *data, uint64_t n, int delim, uint32_t *n_fi
  * that hold those members' whole frames, the text's bytes [t0, t1).  Through yacrd_bytes_free.  Non-zero: not BGZF, or
  * window_bytes under 65 536 (the largest frame and the largest ISIZE). */
 int yacrd_bgzf_window_cuts(const char *data, uint64_t n, uint64_t window_bytes, uint64_t **cuts_out, uint64_t *n_cuts);
+/* How the device overlap editor runs a plain text of `n` bytes (csrc/edit_route.h): returns 0 the whole text at
+ * once, 1 in windows of *window_bytes, 2 not on the device (YACRD_EFALLBACK: the host loop).  `window_switch` is what
+ * yacrd_debug_edit_window holds (0 the policy, UINT64_MAX never windows, else the window, rounded up to a 32 KiB tile);
+ * whole_fits / ring_fits: whether the whole-text run, and the ring of a run in windows, find room in the device's free
+ * memory.  *window_bytes (may be null): the window, *chunk_bytes (may be null): the mover's chunk, which is also how far a
+ * window's lines may reach into the next one.  A pure function: nothing is asked of any device. */
+int yacrd_edit_window_route(uint64_t n, uint64_t window_switch, int whole_fits, int ring_fits, uint64_t *window_bytes, uint64_t *chunk_bytes);
 /* The encoder's code-length construction: freq[n] -> len[n] with no length above `limit` (n in 2..286, limit in 5..15,
  * 2^limit >= n).  Fewer than two used symbols are given company, as zlib does, so the code is always complete. */
 int yacrd_deflate_code_lengths(const uint32_t *freq, uint32_t n, uint32_t limit, uint8_t *len);

@@ -24,7 +24,19 @@ with the parent's, byte for byte.  One JSON line per form (appended to --json wh
 with the stages inflate + detect + edit of YACRD_CLI_TIMING as the figure compared (slowest (b) against fastest (a)), the
 editor's and the decoder's own stats per run, every output compared byte for byte (-c 4 -n 0.4 here).  One JSON line per case, and one
 more for the same calls warm in ONE process: Engine.ingest_bgzf + edit_overlaps_resident, and edit_overlaps_bgzf, K runs after a warm-up.
---parent-again: a second series of the parent behind the new one ("parent_again" in the row): what drifted meanwhile shows."""
+--parent-again: a second series of the parent behind the new one ("parent_again" in the row): what drifted meanwhile shows.
+--window BYTES --parent-bin PATH [--gzip]: the overlap editor in windows against the whole-text run.  The command
+    yacrd -i r.yacrd -o r2.yacrd -t 0 <op> -i ovl.paf -o kept.paf
+(the detection read from a report: the text is moved, no mirror serves) on the synthetic PAF — with --gzip on its gzip -1 form, which
+the command inflates on the host, edits as text and deflates on the device —, K timed rounds after one warm-up, every round running
+  (i)   parent    PATH: the `yacrd` of the parent commit, the whole text at once
+  (ii)  whole     this tree's yacrd with YACRD_EDIT_WINDOW=18446744073709551615: never windows
+  (iii) windows   this tree's yacrd with YACRD_EDIT_WINDOW=BYTES
+one behind the other, so that what drifts meanwhile touches all three alike.  Per run the `edit` stage and the wall time, the
+stages of the editor's info line and its windows; then, in this process, what the device held for (ii) and (iii) and the ring's
+bytes (Engine.edit_windows).  Every output is compared with the parent's byte for byte.  The two conditions of DESIGN 7n are
+worked out in the row: whether (ii)'s kernel_ms and wall time lie within the spread of (i)'s runs, and whether the slowest (iii)
+is under the fastest whole-text run.  One JSON line (appended to --json when given)."""
 import argparse, json, os, re, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -42,6 +54,7 @@ ap.add_argument("--bgzf-in", action="store_true")
 ap.add_argument("--parent-bin", default=None)
 ap.add_argument("--parent-again", action="store_true")
 ap.add_argument("--forms", default="gzip1,bgzf")
+ap.add_argument("--window", type=int, default=0)
 a = ap.parse_args()
 op = {"filter": host.OP_FILTER, "extract": host.OP_EXTRACT}[a.op]
 d = os.environ.get("YACRD_EDIT_BENCH_DIR", "/dev/shm")
@@ -246,6 +259,94 @@ def bgzf_in_bench():
             fresh(x)
 
 
+def window_bench():
+    """--window: the command's edit of a plain (or, --gzip, a gzip -1) overlap file: parent, this tree whole, this tree in windows"""
+    import ctypes
+    import numpy as np
+    new_bin = os.path.join(ROOT, "yacrd_amd", "bin", "yacrd")
+    if not a.parent_bin or not os.access(a.parent_bin, os.X_OK):
+        sys.exit("--window needs --parent-bin: the yacrd binary built from the parent commit")
+    ext = ".paf.gz" if a.gzip else ".paf"
+    src, rep, rep2 = (tag + "in.paf.gz" if a.gzip else paf), tag + "r.yacrd", tag + "r2.yacrd"
+    outs = {"parent": tag + "old" + ext, "whole": tag + "whole" + ext, "windows": tag + "win" + ext}
+    made = [paf, src, rep, rep2] + list(outs.values())
+    never = str(2 ** 64 - 1)
+    routes = (("parent", a.parent_bin, {}), ("whole", new_bin, {"YACRD_EDIT_WINDOW": never}), ("windows", new_bin, {"YACRD_EDIT_WINDOW": str(a.window)}))
+    line_tag = "[info] device editor + deflate:" if a.gzip else "[info] device editor:"
+    kernels = "editor kernels" if a.gzip else "kernels"
+    base = {k: v for k, v in os.environ.items() if k != "YACRD_EDIT_WINDOW"}
+    try:
+        host.synth_paf(host.SYNTH_SEQUEL, a.reads, a.overlaps, 20241108 + 5, paf)
+        size = os.path.getsize(paf)
+        p = subprocess.run([new_bin, "-i", paf, "-o", rep, "-t", "0", "-c", "3", "-n", "0.4"], capture_output=True, text=True)
+        assert p.returncode == 0, p.stderr
+        if a.gzip:
+            with open(src, "wb") as f:
+                subprocess.check_call(["gzip", "-1", "-c", paf], stdout=f)
+        rows = {name: [] for name, _, _ in routes}
+        for k in range(a.runs + 1):
+            for name, binary, env in routes:
+                fresh(outs[name])
+                fresh(rep2)
+                t0 = time.perf_counter()
+                p = subprocess.run([binary, "-i", rep, "-o", rep2, "-t", "0", a.op, "-i", src, "-o", outs[name]], capture_output=True, text=True,
+                                   env=dict(base, YACRD_CLI_TIMING="1", **env))
+                wall = time.perf_counter() - t0
+                assert p.returncode == 0, p.stderr
+                stages = dict(re.findall(r"^\[timing\] (\S+) ([0-9.]+) s$", p.stderr, re.M))
+                info = [l for l in (p.stdout + p.stderr).splitlines() if l.startswith(line_tag)]
+                assert len(info) == 1, p.stdout + p.stderr  # (the device editor ran: no fallback to the host loop)
+                row = {"edit_s": float(stages["edit"]), "wall_s": round(wall, 3)}
+                for label, key in (("text", "text_ms"), ("table", "table_ms"), (kernels, "kernel_ms"), ("encoder kernels", "encoder_kernel_ms"), ("out", "out_ms")):
+                    m = re.search(r", %s ([0-9.]+) ms" % label, info[0])
+                    if m:
+                        row[key] = float(m.group(1))
+                m = re.search(r" windows=(\d+)$", info[0])
+                row["windows"] = int(m.group(1)) if m else 0  # (the parent's line does not say: it has none)
+                if k:
+                    rows[name].append(row)
+        assert same(outs["parent"], outs["whole"]) and same(outs["parent"], outs["windows"]), "this tree's file differs from the parent's"
+        assert all(r["windows"] == 0 for r in rows["whole"]) and all(r["windows"] == (size + a.window - 1) // a.window for r in rows["windows"])
+        # in this process: what the device holds for the two routes of this tree (plain text out; with --gzip the members)
+        held = {}
+        if a.gzip:
+            text = host.text_from_file(src)
+        with yacrd_amd.Engine(device_id=0) as e:
+            res, names, lengths, _ = e.ingest_paf(paf, 3, 0.4)
+            for name, sw in (("whole", 2 ** 64 - 1), ("windows", a.window)):
+                e.trim()  # (the parser's mirror goes with it: the text is moved)
+                before = yacrd_amd.engine.live_bytes()[0]
+                e.debug_edit_window(sw)
+                fresh(got)
+                if a.gzip:
+                    buf = np.ctypeslib.as_array(ctypes.cast(text.address, ctypes.POINTER(ctypes.c_uint8)), shape=(text.n_bytes,))
+                    e.edit_overlaps_gzip(op, buf, names, res.read_type, 1, out_path=got)
+                else:
+                    e.edit_overlaps(op, paf, got, names, res.read_type)
+                held[name] = {"device_bytes": int(yacrd_amd.engine.live_bytes()[0] - before), **e.edit_windows()}
+            e.trim()
+        fresh(got)
+        whole_like = rows["parent"] + rows["whole"]
+        spread = lambda key: (min(r[key] for r in rows["parent"]), max(r[key] for r in rows["parent"]))  # noqa: E731
+        row = {"reads": a.reads, "overlaps": a.overlaps, "op": a.op, "gzip": bool(a.gzip), "window": a.window, "text_bytes": size,
+               "out_bytes": os.path.getsize(outs["parent"]), **rows, "held": held,
+               "whole_kernel_ms_within_parent_spread": all(spread("kernel_ms")[0] <= r["kernel_ms"] <= spread("kernel_ms")[1] for r in rows["whole"]),
+               "whole_wall_s_within_parent_spread": all(r["wall_s"] <= spread("wall_s")[1] for r in rows["whole"]),
+               "slowest_windows_edit_s": max(r["edit_s"] for r in rows["windows"]), "fastest_whole_edit_s": min(r["edit_s"] for r in whole_like),
+               "windows_when_fits_by_the_rule": max(r["edit_s"] for r in rows["windows"]) < min(r["edit_s"] for r in whole_like)}
+        line = json.dumps(row)
+        print(line, flush=True)
+        if a.json:
+            with open(a.json, "a") as f:
+                f.write(line + "\n")
+    finally:
+        for x in made + [got]:
+            fresh(x)
+
+
+if a.window:
+    window_bench()
+    sys.exit(0)
 if a.bgzf_in:
     bgzf_in_bench()
     sys.exit(0)

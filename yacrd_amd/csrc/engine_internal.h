@@ -389,6 +389,10 @@ struct yacrd_engine {
     // windows; else the window's bytes) and what yacrd_debug_seq_windows reports of the last sequence edit
     uint64_t seq_window = 0;
     uint64_t seq_windows[4] = {0, 0, 0, 0};
+    // the overlap editor's windows (gpu_edit.hip): the switch yacrd_debug_edit_window set, with the same three meanings,
+    // and what yacrd_debug_edit_windows reports of the last overlap edit
+    uint64_t edit_window = 0;
+    uint64_t edit_windows[4] = {0, 0, 0, 0};
     // batches of this many reads and more take the long-batch forms of the plan and the follow-on step (engine.hip:
     // split_min_reads is the default; yacrd_debug_long_min_reads sets it, tests)
     uint64_t long_min_reads = 0;

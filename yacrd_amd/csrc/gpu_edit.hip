@@ -42,9 +42,16 @@
 // bytes of earlier segments — the file beside out_path goes, the buffer is freed.
 // Resident (yacrd_engine_edit_overlaps_resident_mem / _file): the mirror of the engine's last one-engine overlap ingest, with
 // the plan's facts recorded beside it (engine_internal.h: mirror); nothing goes up.
+// In windows (EditRun::windows_loop; the route: edit_route.h): a plain text of more than one window that finds no
+// room whole — or with yacrd_debug_edit_window set — goes through two text slots and two output slots whose size does not
+// depend on it.  A window is to that run what a segment is to the whole-text run: one round of the same kernels, over
+// positions that count from the window's first byte, with the first chunk of the next window behind it as look-ahead.  The
+// byte in front of a window, the verdict that runs into it, the kept bytes so far and (gzip out) the ragged tail behind the
+// last whole block are handed from window to window on the device.  The BGZF-in and resident forms always run whole.
 #include "engine_internal.h"
 #include "gpu_text.h"
 #include "edit_table.h"
+#include "edit_route.h"
 #include "host/beside_file.h"
 #include "host/segment_pump.h"
 
@@ -76,7 +83,19 @@ struct EdArgs {
     u32 tile0;       // the launch's first tile
     u32 seg;
     u32 delim, ib, n_fields, keep_good; // keep_good: filter (keep when both reads are good); else extract
+    // A run in windows (EditRun::windows_loop): `text` is a window's first byte in its slot and every position, n,
+    // nl, avail and the tiles count from there; the byte in front of it lies in the slot's front pad.
+    u64 pos0; // the text position of text[0] (0: nothing precedes it, it begins a line)
+    u64 wend; // the window's bytes: a line that ends behind them reaches into the next window (~0: the text is whole)
+    unsigned long long *win; // the words handed from window to window (kEdWin*, by parity), nullptr for a whole text
+    u32 wpar;                // the window's parity: it reads words [.. + wpar], writes [.. + (wpar ^ 1)]
 };
+// the words of EdArgs::win, two of each: window k reads the one of parity k & 1 and writes the other for window k + 1
+constexpr u32 kEdWinVerdict = 0; // the verdict of the last line start so far: it runs into the window
+constexpr u32 kEdWinKept = 2;    // kept bytes in front of the window
+constexpr u32 kEdWinBase = 4;    // where the window's kept bytes begin in its output slot (gzip out: behind the tail; else 0)
+constexpr u32 kEdWinTailAt = 6;  // gzip out: where the tail the window takes over lies in the slot of the window before
+constexpr u32 kEdWinWords = 8;
 
 // The tile [tile0, tile0 + want) -> LDS, 16 bytes per thread and step (the mirror is padded by 64 zero bytes and the last
 // step is clipped to whole 16-byte pieces inside it; an inner segment's `avail` is a chunk boundary); the newline mask of
@@ -115,8 +134,8 @@ __device__ __forceinline__ EdMasks ed_starts(const EdArgs &a, u64 tile0, const u
     const u64 left = lo < a.nl ? a.nl - lo : 0;
     m.v[0] = left >= 64 ? ~0ull : ((1ull << left) - 1ull);
     m.v[1] = left >= 128 ? ~0ull : left > 64 ? ((1ull << (left - 64)) - 1ull) : 0ull;
-    u64 prev = 1; // position 0 starts a line; any other does when a newline precedes it
-    if (lo != 0) prev = (threadIdx.x ? (u32)win[threadIdx.x * 128u - 1u] : (u32)a.text[lo - 1]) == '\n' ? 1ull : 0ull;
+    u64 prev = 1; // position 0 starts a line; any other does when a newline precedes it (a window's byte 0: the front pad's last)
+    if (a.pos0 + lo != 0) prev = (threadIdx.x ? (u32)win[threadIdx.x * 128u - 1u] : (u32)(a.text - 1)[lo]) == '\n' ? 1ull : 0ull;
     m.s[0] = ((m.nl[0] << 1) | prev) & m.v[0];
     m.s[1] = ((m.nl[1] << 1) | (m.nl[0] >> 63)) & m.v[1];
     return m;
@@ -203,6 +222,7 @@ __global__ __launch_bounds__(kGpT) void ed_mark_kernel(EdArgs a)
                 }
             }
             if (nf == a.ib + 1) end_b = i;
+            if (i >= a.wend) atomicMax(a.ctl + 3, (unsigned long long)(min(i + 1, a.n) - a.wend)); // (its bytes in the next window)
             if (nf != a.n_fields || nf <= a.ib) { // (csv, not flexible: the host loop words the error)
                 status |= kEdNeedHost;
                 continue;
@@ -246,7 +266,7 @@ __global__ __launch_bounds__(256) void ed_carry_kernel(EdArgs a, u32 t_end)
 {
     const u32 t = a.tile0 + blockIdx.x * 256u + threadIdx.x;
     if (t >= t_end) return;
-    u32 cin = 0;
+    u32 cin = a.win ? (u32)a.win[kEdWinVerdict + a.wpar] : 0u; // (a window: what the windows before it hand over)
     for (u32 q = t; q-- > 0u;) { // (one step, unless a line is longer than a tile)
         const u32 f = a.tile[q].z;
         if (f & 1u) {
@@ -257,6 +277,31 @@ __global__ __launch_bounds__(256) void ed_carry_kernel(EdArgs a, u32 t_end)
     const uint4 rec = a.tile[t];
     a.tile_kept[t] = rec.x + (cin ? rec.y : 0u);
     a.tile_cin[t] = cin;
+    // the window's last tile hands on the verdict of the last line start so far: its own, or — a window without one — what came in
+    if (a.win && t + 1u == t_end) a.win[kEdWinVerdict + (a.wpar ^ 1u)] = (rec.z & 1u) ? (rec.z >> 1) & 1u : cin;
+}
+// a window's other words for the next one: kept bytes so far; gzip out (block != 0): the ragged tail behind the slot's last
+// whole block — it is encoded with the next window's bytes, at the front of that window's slot
+__global__ void ed_window_base_kernel(unsigned long long *win, u32 par, const u64 *kept_in_window, u32 block, u32 last)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const u64 kept = *kept_in_window, filled = win[kEdWinBase + par] + kept;
+    const u64 tail = block && !last ? filled % block : 0;
+    win[kEdWinKept + (par ^ 1u)] = win[kEdWinKept + par] + kept;
+    win[kEdWinBase + (par ^ 1u)] = tail;
+    win[kEdWinTailAt + (par ^ 1u)] = filled - tail;
+}
+// gzip out: the tail the window of parity `par` takes over, from the slot of the window before (a multiple of the block, so
+// of 16) to offset 0 of its own; its length is on the device alone
+__global__ __launch_bounds__(256) void ed_tail_kernel(unsigned char *dst, const unsigned char *src, const unsigned long long *win, u32 par)
+{
+    const u64 len = win[kEdWinBase + par];
+    src += win[kEdWinTailAt + par];
+    for (u64 i = ((u64)blockIdx.x * 256u + threadIdx.x) * 16u; i < len; i += (u64)gridDim.x * 256u * 16u) {
+        if (i + 16u <= len) *reinterpret_cast<uint4 *>(dst + i) = *reinterpret_cast<const uint4 *>(src + i);
+        else
+            for (u64 b = i; b < len; b++) dst[b] = src[b];
+    }
 }
 __global__ void ed_base_kernel(u64 *seg_base, u32 seg, const u64 *seg_total)
 {
@@ -340,10 +385,13 @@ namespace {
 
 constexpr size_t kOutPiece = (size_t)4 << 20;
 constexpr u64 kSegBytes = (u64)(kTextChunk * kTextSeg); // the mover's segment: what one round of mark, carry, scan and pack covers
+static_assert(yer::kTile == (u64)yk::kGpTile && yer::kChunkMax == (u64)kTextChunk && yer::kWindowDefault == kSegBytes && yer::kGzBlock == (u64)ydf::kBlock,
+              "edit_route.h restates the tile, the chunk, the segment and the encoder's block");
 
 struct EditScratch { // the editor's buffers; they stay with the engine (grow-only), go with yacrd_engine_trim / destroy
     static constexpr yacrd_engine::Slot kScratchSlot = yacrd_engine::kEdit;
     DevBuf text, out, kbits, tile, tile_kept, tile_cin, tile_off, ctl, part;
+    DevBuf wtext[2], wout[2]; // a run in windows (EditRun::windows_loop): its two text slots, its two output slots
     EdTableOwner table; // the reads' names and types, the id table over them
     PinBuf pin; // two output pieces + the per-segment control words
 };
@@ -378,6 +426,10 @@ struct EditRun {
     u64 gz_blocks = 0;         // gzip out: a batch is at most a segment's kept bytes and the tail carried into it
     u32 n_fields = 0;
     double t_start = 0, t_table = 0;
+    u64 W = 0;  // 0: the whole text at once; else the run goes window by window, this many bytes each (windows_loop)
+    u64 wt = 0; // ... tiles of a window
+    bool win_fresh[2] = {false, false}; // a text slot that is a new allocation fills faster by copy kernel, once
+    std::atomic<u64> win_released{0};   // the writer has let go of the output of every window below this one
     // reserve(), upload_table()
     bool blit = false; // a fresh mirror fills faster by copy kernel (gpu_paf.hip)
     yk::EdArgs ga{};
@@ -434,15 +486,37 @@ struct EditRun {
         ga.delim = (u32)(unsigned char)delim, ga.ib = ib, ga.n_fields = n_fields, ga.keep_good = job.op == 1 ? 1u : 0u;
         t_start = now_ms();
         // HBM: the text (unless the parser's mirror serves), as many bytes again for what is kept, a bit per byte, the table
+        // The route (edit_route.h): a plain text of more than one window runs in windows where the whole-text need
+        // finds no room, where the switch names a window, or — kEdWindowsWhenFits — always.  The BGZF-in and resident forms and
+        // an edit from the parser's mirror run whole, as before.
+        const u64 sw = tp.bgzf || job.use_mirror ? UINT64_MAX : e->edit_window;
+        const u64 Wn = yer::window_of(sw), w_tiles = Wn / yk::kGpTile + 2;
+        const u64 w_gz_blocks = job.gzip ? (yer::out_slot_bytes(Wn, true) + ydf::kBlock - 1) / ydf::kBlock : 0;
+        bool whole_fits = true, ring_fits = true;
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            const double table_need = (double)name_bytes * 1.125 + (double)cap * 4.0 + (double)R * 10.0 + (double)((size_t)64 << 20);
             // (a BGZF stream: its compressed bytes and the member table lie in HBM beside the text; the inflate scratch counts as held)
             const double have = (double)free_b + (double)S.text.cap + (double)S.out.cap + (double)S.kbits.cap + (double)S.table.names.cap +
                                 (double)S.table.slots.cap + (tp.bgzf ? (double)inflate_device_held(e) : 0.0);
-            const double need = (job.use_mirror ? 0.0 : (double)n) + (tp.bgzf ? tp.bgzf->device_bytes() : 0.0) + (double)nl * 1.125 + (double)nl / 8.0 * 1.125 + (double)name_bytes * 1.125 +
-                                (double)cap * 4.0 + (double)R * 10.0 + (double)n_tiles * 40.0 + (double)((size_t)64 << 20) +
+            const double need = (job.use_mirror ? 0.0 : (double)n) + (tp.bgzf ? tp.bgzf->device_bytes() : 0.0) + (double)nl * 1.125 + (double)nl / 8.0 * 1.125 +
+                                table_need + (double)n_tiles * 40.0 +
                                 (double)gz_blocks * (double)ydf::kSlot * 3.0 * 1.125; // (the members' slots and two batches of members)
-            if (need > have) return fail(YACRD_EFALLBACK, "the file is too large to be edited in this device's free memory: the host loop streams it");
+            whole_fits = need <= have;
+            // the ring: two text and two output slots, one window's tables (the whole text's buffers go before it is taken)
+            const double ring_have = have + (double)S.wtext[0].cap + (double)S.wtext[1].cap + (double)S.wout[0].cap + (double)S.wout[1].cap;
+            const double ring_need = 2.0 * (double)yer::text_slot_bytes(Wn) + 2.0 * (double)yer::out_slot_bytes(Wn, job.gzip) +
+                                     (double)w_tiles * ((double)yk::kGpT * 16.0 + 40.0) * 1.125 + table_need +
+                                     (double)w_gz_blocks * (double)ydf::kSlot * 3.0 * 1.125;
+            ring_fits = ring_need <= ring_have;
+        }
+        const yer::Route route = yer::route(n, sw, whole_fits, ring_fits);
+        if (route == yer::kFallback) return fail(YACRD_EFALLBACK, "the file is too large to be edited in this device's free memory: the host loop streams it");
+        if (route == yer::kWindows) {
+            W = Wn, wt = Wn / yk::kGpTile;
+            n_segs = (size_t)((n + W - 1) / W); // (a window is what a segment is to the whole-text run: one round of the kernels)
+            n_batches = n_segs + 1;
+            gz_blocks = w_gz_blocks;
         }
         return YACRD_OK;
     }
@@ -451,16 +525,29 @@ struct EditRun {
     int reserve()
     {
         const void *mirror_before = S.text.p;
-        if (!job.use_mirror) HIP_TRY(S.text.reserve((size_t)n + 64));
-        blit = !job.use_mirror && S.text.p != mirror_before;
-        if (!job.use_mirror) HIP_TRY(hipMemsetAsync(S.text.as<char>() + n, 0, 64, e->stream));
-        HIP_TRY(S.out.reserve((size_t)nl + 64));
-        HIP_TRY(S.kbits.reserve((size_t)(n_tiles + 1) * yk::kGpT * sizeof(uint4)));
-        HIP_TRY(S.tile.reserve((size_t)(n_tiles + 1) * sizeof(uint4)));
-        HIP_TRY(S.tile_kept.reserve((size_t)(n_tiles + 1) * sizeof(u32)));
-        HIP_TRY(S.tile_cin.reserve((size_t)(n_tiles + 1) * sizeof(u32)));
-        HIP_TRY(S.tile_off.reserve((size_t)(n_tiles + n_segs + 2) * sizeof(u64)));
-        const size_t ctl_words = 8 + n_segs + 2;
+        if (W) {
+            // the ring is what a run in windows holds: the whole-text run's two buffers go first; the slots are exactly their
+            // size (no slack: the ring's bytes are a function of W alone)
+            S.text.release(), S.out.release();
+            for (int i = 0; i < 2; i++) {
+                const void *before = S.wtext[i].p;
+                HIP_TRY(S.wtext[i].reserve_exact((size_t)yer::text_slot_bytes(W)));
+                win_fresh[i] = S.wtext[i].p != before;
+                HIP_TRY(S.wout[i].reserve_exact((size_t)yer::out_slot_bytes(W, job.gzip)));
+            }
+        } else {
+            if (!job.use_mirror) HIP_TRY(S.text.reserve((size_t)n + 64));
+            blit = !job.use_mirror && S.text.p != mirror_before;
+            if (!job.use_mirror) HIP_TRY(hipMemsetAsync(S.text.as<char>() + n, 0, 64, e->stream));
+            HIP_TRY(S.out.reserve((size_t)nl + 64));
+        }
+        const u64 tiles = W ? wt + 1 : n_tiles; // (a window: its tiles and the one the newline the last line lacks may open)
+        HIP_TRY(S.kbits.reserve((size_t)(tiles + 1) * yk::kGpT * sizeof(uint4)));
+        HIP_TRY(S.tile.reserve((size_t)(tiles + 1) * sizeof(uint4)));
+        HIP_TRY(S.tile_kept.reserve((size_t)(tiles + 1) * sizeof(u32)));
+        HIP_TRY(S.tile_cin.reserve((size_t)(tiles + 1) * sizeof(u32)));
+        HIP_TRY(S.tile_off.reserve((size_t)(tiles + (W ? 0 : n_segs) + 2) * sizeof(u64)));
+        const size_t ctl_words = 8 + (W ? (size_t)yk::kEdWinWords : n_segs + 2);
         HIP_TRY(S.ctl.reserve(ctl_words * sizeof(u64)));
         HIP_TRY(hipMemsetAsync(S.ctl.p, 0, ctl_words * sizeof(u64), e->stream));
         HIP_TRY(S.pin.reserve(2 * kOutPiece + (n_segs + 2) * 4 * sizeof(u64) + (job.gzip ? n_batches * 2 * sizeof(u64) : 0) + sizeof(u64)));
@@ -493,6 +580,7 @@ struct EditRun {
         seg_base = S.ctl.as<u64>() + 8;
         ga.seg_base = seg_base;
         ga.out = S.out.as<unsigned char>();
+        ga.pos0 = 0, ga.wend = ~0ull, ga.win = nullptr, ga.wpar = 0; // (a run in windows sets them window by window)
         return YACRD_OK;
     }
 
@@ -518,6 +606,101 @@ struct EditRun {
         dispatched.store(s + 1, std::memory_order_release);
     }
 
+    // ---- a run in windows ------------------------------------------------------------------------------------
+    u64 win_tail = 0; // gzip out, the writer's: the kept bytes behind the last encoded block (what the device holds in kEdWinBase)
+    unsigned char *wslot(u64 k) const { return S.wtext[k & 1].as<unsigned char>() + 16; } // window k's byte 0 (behind the front pad)
+    u64 wlen(u64 k) const { return std::min<u64>(W, n - k * W); }                         // its bytes
+
+    // Window k lies in its slot with `ahead` bytes of window k + 1 behind it: the same mark, carry, scan and pack as a segment
+    // of the whole-text run, over positions that count from the window's byte 0.  What it takes from the windows before it
+    // and leaves for the next lies on the device (EdArgs::win); its counts go to the host behind the pack, as a segment's do.
+    void launch_window(u64 k, u64 ahead)
+    {
+        const bool last = k + 1 == n_segs;
+        const u32 par = (u32)(k & 1);
+        const u64 n_loc = n - k * W, nl_loc = nl - k * W;
+        const u32 t1 = last ? (u32)((nl_loc + yk::kGpTile - 1) / yk::kGpTile) : (u32)wt; // (at most wt + 1: reserve())
+        unsigned long long *win = S.ctl.as<unsigned long long>() + 8;
+        ga.text = wslot(k), ga.n = n_loc, ga.nl = nl_loc;
+        ga.avail = last ? n_loc : W + ahead; // (== n_loc where the look-ahead holds the text's end: position n_loc then ends a line)
+        ga.tile0 = 0, ga.seg = 0, ga.pos0 = k * W, ga.wend = last ? ~0ull : W, ga.win = win, ga.wpar = par;
+        ga.seg_base = reinterpret_cast<const u64 *>(win + yk::kEdWinBase + par);
+        ga.out = S.wout[par].as<unsigned char>();
+        bool ok = hipEventRecord(ev0[k], e->stream) == hipSuccess;
+        // (the 64 zero bytes ed_stage's last 16-byte steps read behind the text's end: inside the slot, n_loc <= W + C here)
+        if (ga.avail == n_loc) ok = ok && hipMemsetAsync(wslot(k) + n_loc, 0, 64, e->stream) == hipSuccess;
+        if (job.gzip && k)
+            hipLaunchKernelGGL(yk::ed_tail_kernel, dim3(16), dim3(256), 0, e->stream, ga.out, S.wout[par ^ 1].as<unsigned char>(), win, par);
+        hipLaunchKernelGGL(yk::ed_mark_kernel, dim3(t1), dim3(yk::kGpT), 0, e->stream, ga);
+        hipLaunchKernelGGL(yk::ed_carry_kernel, dim3((t1 + 255) / 256), dim3(256), 0, e->stream, ga, t1);
+        u64 *off = S.tile_off.as<u64>();
+        ok = ok && scan_u32_to_u64(e, S.tile_kept.as<u32>(), (u64)t1, off, S.part) == YACRD_OK;
+        hipLaunchKernelGGL(yk::ed_window_base_kernel, dim3(1), dim3(64), 0, e->stream, win, par, off + t1, job.gzip ? (u32)ydf::kBlock : 0u, last ? 1u : 0u);
+        hipLaunchKernelGGL(yk::ed_pack_kernel, dim3(t1), dim3(yk::kGpT), 0, e->stream, ga);
+        ok = ok && hipMemcpyAsync((void *)(h_seg + 4 * k), S.ctl.p, 3 * sizeof(u64), hipMemcpyDeviceToHost, e->stream) == hipSuccess;
+        ok = ok && hipMemcpyAsync((void *)(h_seg + 4 * k + 3), win + yk::kEdWinKept + (par ^ 1u), sizeof(u64), hipMemcpyDeviceToHost, e->stream) == hipSuccess;
+        ok = ok && hipEventRecord(ev1[k], e->stream) == hipSuccess;
+        if (!ok) bad = 1;
+        dispatched.store((size_t)k + 1, std::memory_order_release);
+    }
+
+    // The windows, on the launching thread; move_text's code.  Window k's text lands in slot k & 1 in two moves: its first
+    // chunk C = min(4 MiB, W) while window k - 1 waits for it as its look-ahead, the rest afterwards, beside window k - 1's
+    // kernels.  Then window k + 1's first chunk lands in the other slot, is copied on the device behind window k's W bytes
+    // — with window k's last byte to the other slot's front pad —, and window k's kernels follow those copies on the
+    // engine's stream.  A line that starts in window k is marked in window k and may end up to C bytes into window k + 1;
+    // one that reaches farther sets kEdNeedHost, as in the whole-text run a line that reaches beyond the chunk behind its
+    // segment does.  Who may write which slot when:
+    //   text slot k & 1       Read by window k's kernels (mark, pack); window k - 2's were the last before them.  Its bytes
+    //     [0, C) are written by window k's first move, which begins after this thread has waited for window k - 2's
+    //     event (ev1: behind its pack); its bytes [C, W) by the second move, later still.  The look-ahead [W, W + C) and
+    //     the front pad are written by copies on the engine's stream, behind window k - 2's kernels and in front of
+    //     window k's.  Both moves end (move_text waits for its copy streams) before the copies that read them are enqueued.
+    //   text slot (k + 1) & 1  While window k's kernels run it takes window k + 1's rest: they read of it only what the
+    //     device copies took before them — nothing.
+    //   output slot k & 1     Written by window k's tail copy and pack, behind the wait below for win_released > k - 2:
+    //     the writer has brought window k - 2's bytes home (plain) or has fetched the batch encoded from them (gzip out),
+    //     and window k - 1's tail copy, the only other reader, ran on the engine's stream in front of window k's launches.
+    //     The writer reads it behind ev1[k].
+    //   the per-window tables, the words of EdArgs::win   One stream, in order; a word read by window k + 1 is written by
+    //     window k and overwritten by window k + 2 at the earliest.  The pinned words are per window.
+    int windows_loop()
+    {
+        const u64 K = n_segs, C = yer::chunk_of(W);
+        Streams lanes; // the mover's copy streams, made once for all the moves
+        auto land = [&](u64 k, u64 from, u64 upto) -> int { // bytes [from, upto) of window k -> its slot
+            if (upto <= from) return 0;
+            return move_text(e, tp.src, k * W + from, upto - from, reinterpret_cast<char *>(wslot(k)) + from, win_fresh[k & 1], job.n_threads,
+                             [](u64, u64, u64) {}, (size_t)C, &lanes);
+        };
+        auto nap = [] {
+            struct timespec ts = {0, 20000};
+            nanosleep(&ts, nullptr);
+        };
+        int rc = land(0, 0, std::min(C, wlen(0)));
+        for (u64 k = 0; k < K && !rc && !bad.load(); k++) {
+            const bool last = k + 1 == K;
+            rc = land(k, C, wlen(k));
+            win_fresh[k & 1] = false;
+            u64 ahead = 0;
+            if (!rc && !last) {
+                if (k >= 1 && hipEventSynchronize(ev1[k - 1]) != hipSuccess) bad = 1; // (the other text slot: window k - 1's pack has read it)
+                if (bad.load()) break;
+                ahead = std::min(C, wlen(k + 1));
+                rc = land(k + 1, 0, ahead);
+                if (rc) break;
+                if (hipMemcpyAsync(wslot(k) + W, wslot(k + 1), (size_t)ahead, hipMemcpyDeviceToDevice, e->stream) != hipSuccess ||
+                    hipMemcpyAsync(wslot(k + 1) - 1, wslot(k) + W - 1, 1, hipMemcpyDeviceToDevice, e->stream) != hipSuccess)
+                    bad = 1;
+            }
+            while (k >= 2 && win_released.load(std::memory_order_acquire) < k - 1 && !bad.load()) nap(); // (the output slot)
+            if (rc || bad.load()) break;
+            launch_window(k, ahead);
+        }
+        (void)hipStreamSynchronize(e->stream); // (the copy streams go with `lanes`; nothing of theirs is pending: move_text waits)
+        return rc;
+    }
+
     // base[from, upto) in HBM -> the sink through the two pinned pieces: one flies while the other is written (host/segment_pump.h)
     void bring_home(const char *base, u64 from, u64 upto)
     {
@@ -534,16 +717,15 @@ struct EditRun {
     // gzip out (both run on the writer thread).  encode: kept bytes [gz_text, upto) -> a batch of members, on the encoder's
     // stream; the pack that wrote them has finished (the writer has waited for the segment's event).  fetch_batch: the
     // oldest batch not yet fetched -> the sink.
-    void encode(u64 upto, bool last)
+    void encode(const unsigned char *src, u64 len, bool last)
     {
         const size_t b = gz_sent;
-        const u64 len = upto - gz_text;
         if (b >= n_batches || len > gz.max_blocks * ydf::kBlock) {
             bad = 1;
             return;
         }
         h_gz[2 * b] = h_gz[2 * b + 1] = 0;
-        if (gzip_device_encode(e, gz, gstream(), S.out.as<unsigned char>() + gz_text, len, last, (int)(b & 1), gev0[b], gev1[b], h_gz + 2 * b,
+        if (gzip_device_encode(e, gz, gstream(), src, len, last, (int)(b & 1), gev0[b], gev1[b], h_gz + 2 * b,
                                h_gz + 2 * b + 1) != YACRD_OK ||
             hipEventRecord(gdone[b], gstream()) != hipSuccess) {
             bad = 1;
@@ -551,7 +733,7 @@ struct EditRun {
         }
         gz_eof[b] = last ? ydf::kEofBytes : 0u;
         gz_members += (len + ydf::kBlock - 1) / ydf::kBlock;
-        gz_text = upto, gz_sent = b + 1;
+        gz_text += len, gz_sent = b + 1;
     }
     void fetch_batch()
     {
@@ -596,13 +778,30 @@ struct EditRun {
                 break;
             }
             const double t0 = now_ms();
-            if (!job.gzip) bring_home(S.out.as<char>(), from, upto);
+            if (W) {
+                // a window's kept bytes lie in its own slot, from 0 (gzip out: behind the tail of the window before, which
+                // ed_tail_kernel has put there).  The slot is let go when nothing reads it any more: plain, when its bytes
+                // are home; gzip out, when the batch encoded from it has been fetched — one window later, so that a batch
+                // is encoded while the one before it comes home, as in the whole-text run
+                const bool last = s + 1 == n_segs;
+                if (!job.gzip) {
+                    bring_home(S.wout[s & 1].as<char>(), 0, upto - from);
+                    win_released.store((u64)s + 1, std::memory_order_release);
+                } else {
+                    const u64 filled = win_tail + (upto - from), whole = last ? filled : filled / ydf::kBlock * ydf::kBlock;
+                    const size_t sent_before = gz_sent;
+                    if (whole || last) encode(S.wout[s & 1].as<unsigned char>(), whole, last);
+                    while (gz_got + (gz_sent - sent_before) < gz_sent && !bad.load()) fetch_batch(); // (every batch but this window's)
+                    win_tail = filled - whole;
+                    win_released.store((u64)s, std::memory_order_release);
+                }
+            } else if (!job.gzip) bring_home(S.out.as<char>(), from, upto);
             else {
                 // every whole block that now lies complete behind the last encoded one (the last segment: the tail too, and
                 // the EOF member) goes to the encoder; the batch before it comes home while this one is encoded
                 const bool last = s + 1 == n_segs;
                 const u64 whole = last ? upto : upto / ydf::kBlock * ydf::kBlock;
-                if (whole > gz_text || last) encode(whole, last);
+                if (whole > gz_text || last) encode(S.out.as<unsigned char>() + gz_text, whole - gz_text, last);
                 while (gz_got + 1 < gz_sent && !bad.load()) fetch_batch();
             }
             from = upto, seen = s + 1;
@@ -610,7 +809,7 @@ struct EditRun {
         }
         if (job.gzip && !bad.load() && seen == n_segs) {
             const double t0 = now_ms();
-            if (n_segs == 0) encode(0, true); // (an empty text: the EOF member alone)
+            if (n_segs == 0) encode(S.out.as<unsigned char>(), 0, true); // (an empty text: the EOF member alone)
             while (gz_got < gz_sent && !bad.load()) fetch_batch();
             out_busy_ms += now_ms() - t0;
         }
@@ -625,7 +824,8 @@ struct EditRun {
             setup_ok = setup_ok && side.add(1) && gev0.add(n_batches) && gev1.add(n_batches) && gdone.add(n_batches, hipEventDisableTiming);
         if (!setup_ok) return false;
         std::thread wt([this] { writer(); });
-        if (job.use_mirror) {
+        if (W) moved = windows_loop();
+        else if (job.use_mirror) {
             for (size_t s = 0; s < n_segs && !bad.load(); s++) launch_segment((u64)s * kSegBytes, (u64)(s + 1) * kSegBytes, n);
         } else {
             // (a BGZF stream: the segments are the inflated text's, each behind the launches that decoded it; the decoder's
@@ -675,6 +875,12 @@ struct EditRun {
         if ((job.gzip ? gz_text : sink.at) != h_bytes) return fail(YACRD_EINTERNAL, "overlap editor: fewer bytes written than kept");
         if (job.gzip && gz_got != gz_sent) return fail(YACRD_EINTERNAL, "overlap editor: a batch of members was not fetched");
         fill_gzip_stats(job.gzip_stats, gz_text, sink.at, gz_members, gz_stored, gz_kernel_ms, out_busy_ms, put_ms);
+        if (W) { // how the edit ran (yacrd_debug_edit_windows); the farthest reach lies in the control words behind the last pack
+            u64 reach = 0;
+            HIP_TRY(hipMemcpy(&reach, S.ctl.as<u64>() + 3, sizeof reach, hipMemcpyDeviceToHost));
+            e->edit_windows[0] = n_segs, e->edit_windows[1] = reach;
+            e->edit_windows[2] = S.wtext[0].cap + S.wtext[1].cap, e->edit_windows[3] = S.wout[0].cap + S.wout[1].cap;
+        }
         if (stats) {
             stats->text_bytes = n;
             stats->kept_bytes = h_bytes;
@@ -694,6 +900,7 @@ int run_edit(yacrd_engine *e, const EditJob &job, TextProducer &tp, u64 n, Sink 
     DeviceGuard guard(e->device);
     EditScratch *S = scratch_of<EditScratch>(e);
     if (!S) return fail(YACRD_ENOMEM, "host allocation failed");
+    for (u64 &w : e->edit_windows) w = 0;
     EditRun r{e, job, tp, n, sink, stats, *S};
     if (const int rc = r.plan()) return rc;
     if (const int rc = r.reserve()) return rc;
@@ -947,5 +1154,16 @@ int yacrd_engine_edit_overlaps_resident_file(yacrd_engine *e, int op, const yacr
 }
 
 void yacrd_edit_text_free(char *p) { std::free(p); }
+
+int yacrd_debug_edit_window(yacrd_engine *e, uint64_t window_bytes)
+{
+    if (!e) return fail(YACRD_EINVAL, "null argument");
+    e->edit_window = window_bytes;
+    return YACRD_OK;
+}
+void yacrd_debug_edit_windows(const yacrd_engine *e, uint64_t out[4])
+{
+    for (int i = 0; i < 4; i++) out[i] = e ? e->edit_windows[i] : 0;
+}
 
 } // extern "C"

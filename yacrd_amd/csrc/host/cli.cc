@@ -443,6 +443,15 @@ int main(int argc, char **argv)
         const char *no_df = std::getenv("YACRD_NO_DEVICE_DEFLATE");
         const bool sub_ovl = has(sub_in, ".m4") || has(sub_in, ".mhap") || has(sub_in, ".paf");
         const bool dev_ed = sub_ovl && (op == YACRD_OP_FILTER || op == YACRD_OP_EXTRACT) && !(no_ed && *no_ed == '1');
+        // YACRD_EDIT_WINDOW=<bytes>: the overlap editor's window (yacrd_debug_edit_window; A/B and tests, like YACRD_SEQ_WINDOW below)
+        if (const char *ew = std::getenv("YACRD_EDIT_WINDOW"))
+            if (dev_ed && *ew) (void)yacrd_debug_edit_window(engines[0], std::strtoull(ew, nullptr, 10));
+        // (how the last overlap edit ran: its windows, 0 for the whole text at once — the info lines end in it)
+        auto edit_windows_of = [](const yacrd_engine *en) {
+            uint64_t w4[4] = {0, 0, 0, 0};
+            yacrd_debug_edit_windows(en, w4);
+            return w4[0];
+        };
         // ... and on a gzip one (what minimap2 | gzip leaves): the inflated text goes to HBM — the detection's, when it read this
         // very file and still holds it, else inflated here, BGZF member-parallel — and the kept bytes are deflated where the
         // device packs them: only BGZF members come back (yacrd_engine_edit_overlaps_gzip_file).  What it does not take, no
@@ -474,11 +483,11 @@ int main(int argc, char **argv)
                 if (!timing) return;
                 std::fprintf(stdout, "[info] device editor + deflate: %llu of %llu lines kept, %llu of %llu bytes -> %llu bytes, %llu members "
                                      "(%llu stored), inflate %.1f ms, text %.1f ms, table %.1f ms, editor kernels %.1f ms, encoder kernels %.1f ms, "
-                                     "out %.1f ms, text_reused=%d resident=%d device_inflate=%d\n",
+                                     "out %.1f ms, text_reused=%d resident=%d device_inflate=%d windows=%llu\n",
                              (unsigned long long)es.n_kept, (unsigned long long)es.n_lines, (unsigned long long)es.kept_bytes,
                              (unsigned long long)es.text_bytes, (unsigned long long)gs.out_bytes, (unsigned long long)gs.n_members,
                              (unsigned long long)gs.n_stored, inflate_ms, es.text_ms, es.table_ms, es.kernel_ms, gs.kernel_ms, es.out_ms,
-                             text_reused ? 1 : 0, resident ? 1 : 0, dev_inflate ? 1 : 0);
+                             text_reused ? 1 : 0, resident ? 1 : 0, dev_inflate ? 1 : 0, (unsigned long long)edit_windows_of(engines[0]));
             };
             // done on the device, nothing inflated on the host: the text the ingest left in HBM, or another BGZF file as it is
             if (ovl_resident && sub_same_file) {
@@ -527,9 +536,10 @@ int main(int argc, char **argv)
             if (dev_edit != YACRD_OK && dev_edit != YACRD_EFALLBACK) die(yacrd_last_error());
             if (dev_edit == YACRD_OK && timing)
                 std::fprintf(stderr, "[info] device editor: %llu of %llu lines kept, %llu of %llu bytes, text %.1f ms, table %.1f ms, kernels %.1f ms, "
-                                     "out %.1f ms, mirror_reused=%u\n",
+                                     "out %.1f ms, mirror_reused=%u windows=%llu\n",
                              (unsigned long long)es.n_kept, (unsigned long long)es.n_lines, (unsigned long long)es.kept_bytes,
-                             (unsigned long long)es.text_bytes, es.text_ms, es.table_ms, es.kernel_ms, es.out_ms, es.mirror_reused);
+                             (unsigned long long)es.text_bytes, es.text_ms, es.table_ms, es.kernel_ms, es.out_ms, es.mirror_reused,
+                             (unsigned long long)edit_windows_of(engines[0]));
         }
         // All four sub-commands on a FASTQ: the text goes to HBM, the device cuts it into records, decides, sizes and gathers the
         // output (yacrd_engine_edit_fastq).  A gzip FASTQ is inflated here — BGZF member-parallel; the detection's text when it

@@ -12,6 +12,7 @@
 #include "../bgzf_plan.h"
 #include "../bgzf_walk.h"
 #include "../bgzf_windows.h"
+#include "../edit_route.h"
 #include "../inflate_block.h"
 #include "host_common.h"
 
@@ -101,6 +102,14 @@ int yacrd_bgzf_window_cuts(const char *data, uint64_t n, uint64_t window_bytes, 
     }
     *cuts_out = co, *n_cuts = cuts.size();
     return 0;
+}
+
+int yacrd_edit_window_route(uint64_t n, uint64_t window_switch, int whole_fits, int ring_fits, uint64_t *window_bytes, uint64_t *chunk_bytes)
+{
+    const uint64_t W = yer::window_of(window_switch);
+    if (window_bytes) *window_bytes = W;
+    if (chunk_bytes) *chunk_bytes = yer::chunk_of(W);
+    return (int)yer::route(n, window_switch, whole_fits != 0, ring_fits != 0);
 }
 
 int yacrd_bgzf_text_ends(const char *data, uint64_t n, int delim, uint32_t *n_fields, int *ends_nl)

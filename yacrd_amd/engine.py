@@ -38,6 +38,7 @@ DEBUG_SYMBOLS = [
     "yacrd_debug_sort_pairs", "yacrd_debug_last_counters", "yacrd_debug_last_input_csr", "yacrd_debug_peer_copy_counts",
     "yacrd_debug_live_bytes", "yacrd_debug_direct_runs", "yacrd_debug_big_routes",
     "yacrd_debug_seq_window", "yacrd_debug_seq_windows", "yacrd_debug_long_min_reads", "yacrd_debug_compute_units",
+    "yacrd_debug_edit_window", "yacrd_debug_edit_windows",
 ]
 F_ONE_LAUNCH = 4194304  # include/yacrd_engine.h: a short batch as ONE kernel launch (csrc/one_batch.h)
 
@@ -842,6 +843,25 @@ class Engine:
         self._lib.yacrd_debug_seq_windows.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         self._lib.yacrd_debug_seq_windows(self._h, out)
         return dict(zip(("windows", "max_carry", "text_ring_bytes", "out_ring_bytes"), (int(v) for v in out)))
+
+    def debug_edit_window(self, window_bytes):
+        """yacrd_debug_edit_window (tests, A/B): the overlap editor's window.  0: the policy (128 MiB windows where the whole text
+        finds no room); 2**64 - 1: never windows; any other value: rounded up to a 32 KiB tile, and every plain overlap text
+        longer than it is edited window by window (csrc/gpu_edit.hip: windows_loop; the BGZF-in and resident forms and an edit
+        from the parser's mirror run whole).  The bytes written do not depend on it."""
+        self._lib.yacrd_debug_edit_window.restype = ctypes.c_int
+        self._lib.yacrd_debug_edit_window.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
+        _check(self._lib, self._lib.yacrd_debug_edit_window(self._h, int(window_bytes)))
+
+    def edit_windows(self):
+        """yacrd_debug_edit_windows (tests, tools): what the last overlap edit ran as: its windows (0: the whole text at once),
+        the farthest a line that began in one window reached into the next, the device bytes of its text ring and of its
+        output ring."""
+        out = (ctypes.c_uint64 * 4)()
+        self._lib.yacrd_debug_edit_windows.restype = None
+        self._lib.yacrd_debug_edit_windows.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._lib.yacrd_debug_edit_windows(self._h, out)
+        return dict(zip(("windows", "max_reach", "text_ring_bytes", "out_ring_bytes"), (int(v) for v in out)))
 
     def _type_table(self, names, read_type):
         """(names, read_type) -> a yacrd_type_table and what keeps its memory alive; names: str or bytes, one per read."""

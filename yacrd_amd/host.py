@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = [
     "yacrd_edit_file", "yacrd_edit_file_mt", "yacrd_text_from_file", "yacrd_text_free", "yacrd_report_read", "yacrd_report_get", "yacrd_report_free",
     "yacrd_edit_file_to", "yacrd_file_compression", "yacrd_bgzf_encode_host", "yacrd_bgzf_decode_host", "yacrd_bytes_free", "yacrd_deflate_code_lengths",
     "yacrd_synth_fastq", "yacrd_ingest_stream", "yacrd_ingest_stream_memory", "yacrd_csr_handle_map", "yacrd_bgzf_plan_segments",
-    "yacrd_bgzf_text_ends", "yacrd_bgzf_window_cuts",
+    "yacrd_bgzf_text_ends", "yacrd_bgzf_window_cuts", "yacrd_edit_window_route",
 ]
 
 OP_SCRUBB, OP_FILTER, OP_EXTRACT, OP_SPLIT = 0, 1, 2, 3
@@ -169,6 +169,8 @@ def load_library():
                                              ctypes.POINTER(ctypes.c_int)]
         lib.yacrd_bgzf_window_cuts.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p),
                                                ctypes.POINTER(ctypes.c_uint64)]
+        lib.yacrd_edit_window_route.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64),
+                                                ctypes.POINTER(ctypes.c_uint64)]
         lib.yacrd_bytes_free.argtypes = [ctypes.c_void_p]
         lib.yacrd_bytes_free.restype = None
         lib.yacrd_deflate_code_lengths.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
@@ -435,6 +437,20 @@ def bgzf_window_cuts(blob, W):
         return [tuple(int(x) for x in row) for row in cuts]
     finally:
         lib.yacrd_bytes_free(co)
+
+
+EDIT_WHOLE, EDIT_WINDOWS, EDIT_FALLBACK = 0, 1, 2
+
+
+def edit_window_route(n, window_switch, whole_fits, ring_fits):
+    """yacrd_edit_window_route (csrc/edit_route.h): how the device overlap editor runs a plain text of `n` bytes
+    -> (EDIT_WHOLE / EDIT_WINDOWS / EDIT_FALLBACK, the window's bytes, the mover's chunk: how far a line may reach into
+    the next window).  window_switch: what Engine.debug_edit_window holds; whole_fits / ring_fits: whether the whole-text
+    run and the ring of a run in windows find room.  Asks nothing of any device."""
+    lib = load_library()
+    W, C = ctypes.c_uint64(), ctypes.c_uint64()
+    r = lib.yacrd_edit_window_route(int(n), int(window_switch), int(bool(whole_fits)), int(bool(ring_fits)), ctypes.byref(W), ctypes.byref(C))
+    return int(r), int(W.value), int(C.value)
 
 
 def deflate_code_lengths(freq, limit):
