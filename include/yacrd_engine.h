@@ -402,9 +402,10 @@ int yacrd_engine_trim(yacrd_engine *e);
  * and renames when the last byte is in.
  * Memory: the run holds the text, as many bytes again and an eighth.  A plain text of more than 128 MiB that finds no such
  * room is edited window by window instead (128 MiB of text at a time in a ring of about 0.55 GB, the same
- * bytes; this form without the mirror, _mem, _gzip_mem and _gzip_file): a line may then reach 4 MiB into the next window, one
- * that reaches farther is YACRD_EFALLBACK like the line above.  YACRD_EFALLBACK for room is left to a device that does not
- * hold the ring, and to the _bgzf_ and _resident_ forms and the edit from the mirror, which always run whole.
+ * bytes; every form: _mem, _gzip_mem, _gzip_file, and — DESIGN.md 7o — the edit from the mirror and the _resident_ forms,
+ * which hold no text ring, and the _bgzf_ forms, whose windows end where members end): a line may then reach 4 MiB into the
+ * next window (BGZF in: at most the next window's bytes), one that reaches farther is YACRD_EFALLBACK like the line above.
+ * YACRD_EFALLBACK for room is left to a device that does not hold the ring.
  * When in_path is the very file (device, inode, size, mtime) the engine's last yacrd_engine_ingest_overlaps parsed and its mirror
  * is still in HBM, the text is not moved again (stats: mirror_reused = 1).
  * op: YACRD_OP_FILTER (1) or YACRD_OP_EXTRACT (2) of yacrd_host.h; format: 0 = by name, 1 = PAF, 2 = M4 / MHAP; n_threads: copy

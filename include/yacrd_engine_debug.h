@@ -139,7 +139,10 @@ uint64_t yacrd_debug_compute_units(const yacrd_engine *e);
 void yacrd_debug_seq_windows(const yacrd_engine *e, uint64_t out[4]);
 /* the overlap editor's windows (csrc/gpu_edit.hip): yacrd_engine_edit_overlaps, _mem, _gzip_mem and _gzip_file
  * run a text of more than one window window by window, in a bounded ring of buffers; the bytes written do not depend on it.
- * The _bgzf_ and _resident_ forms and an edit from the parser's mirror always run whole.
+ * So do the _resident_ forms and an edit from the parser's mirror — the text lies in HBM already: no text slot
+ * is held, window k is the mirror's bytes from k windows on — and the _bgzf_ forms: their window is at least 64 KiB, their
+ * windows are the cuts of csrc/bgzf_windows.h that hold text (a window ends where a member ends), and a line may reach
+ * min(chunk, the next window's bytes) into the next window.
  *   window_bytes == 0            the policy: a window of 128 MiB, taken where the whole-text run finds no room (and, if the
  *                                build's measured default says so, for every text of more than one window);
  *   window_bytes == UINT64_MAX   never windows: the whole text at once, YACRD_EFALLBACK where it finds no room;
@@ -149,8 +152,9 @@ void yacrd_debug_seq_windows(const yacrd_engine *e, uint64_t out[4]);
  * Stays with the engine until set again.  Tests and A/B runs only. */
 int yacrd_debug_edit_window(yacrd_engine *e, uint64_t window_bytes);
 /* what the engine's last overlap edit (any form) ran as: [0] its windows (0: the whole text at once), [1] the farthest a line
- * that began in one window reached into the next, in bytes, [2] device bytes of its two text slots, [3] device bytes of
- * its two output slots.  A failed edit in windows leaves [0] = 0. */
+ * that began in one window reached into the next, in bytes, [2] device bytes of its two text slots (BGZF in: with the
+ * decoder's compressed slot and member slice; from the mirror: 0), [3] device bytes of its two output slots.  A failed edit in
+ * windows leaves [0] = 0. */
 void yacrd_debug_edit_windows(const yacrd_engine *e, uint64_t out[4]);
 /* YACRD_TEST_REPORT_SEGMENT=<bytes> (environment, tests; read at every call): the size of the segments in which
  * yacrd_engine_write_report[_mem] brings the formatted text home, instead of 64 MiB (csrc/gpu_report_write.hip: kReportSegment;

@@ -36,7 +36,11 @@ one behind the other, so that what drifts meanwhile touches all three alike.  Pe
 stages of the editor's info line and its windows; then, in this process, what the device held for (ii) and (iii) and the ring's
 bytes (Engine.edit_windows).  Every output is compared with the parent's byte for byte.  The two conditions of DESIGN 7n are
 worked out in the row: whether (ii)'s kernel_ms and wall time lie within the spread of (i)'s runs, and whether the slowest (iii)
-is under the fastest whole-text run.  One JSON line (appended to --json when given)."""
+is under the fastest whole-text run.  One JSON line (appended to --json when given).
+--bgzf-in --window BYTES --parent-bin PATH [--resident]: the same three columns on the synthetic PAF as BGZF.  Without
+--resident the command is the one above on the BGZF file — the editor's own _bgzf_ form inflates it in HBM, window by window in
+(iii); with it the detection reads the BGZF file itself (YACRD_DEVICE_INFLATE=1: ingested compressed) and the edit runs on the text
+the ingest left in HBM, in windows from that mirror in (iii).  Per run also the decoder's kernel time; `held` as above."""
 import argparse, json, os, re, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -55,6 +59,7 @@ ap.add_argument("--parent-bin", default=None)
 ap.add_argument("--parent-again", action="store_true")
 ap.add_argument("--forms", default="gzip1,bgzf")
 ap.add_argument("--window", type=int, default=0)
+ap.add_argument("--resident", action="store_true")
 a = ap.parse_args()
 op = {"filter": host.OP_FILTER, "extract": host.OP_EXTRACT}[a.op]
 d = os.environ.get("YACRD_EDIT_BENCH_DIR", "/dev/shm")
@@ -259,6 +264,102 @@ def bgzf_in_bench():
             fresh(x)
 
 
+def bgzf_window_bench():
+    """--bgzf-in --window [--resident]: the command's edit of a BGZF overlap file: parent, this tree whole, this tree in windows"""
+    import numpy as np
+    new_bin = os.path.join(ROOT, "yacrd_amd", "bin", "yacrd")
+    if not a.parent_bin or not os.access(a.parent_bin, os.X_OK):
+        sys.exit("--window needs --parent-bin: the yacrd binary built from the parent commit")
+    src, rep, rep2 = tag + "in.paf.gz", tag + "r.yacrd", tag + "r2.yacrd"
+    outs = {"parent": tag + "old.paf.gz", "whole": tag + "whole.paf.gz", "windows": tag + "win.paf.gz"}
+    made = [paf, src, rep, rep2] + list(outs.values())
+    never = str(2 ** 64 - 1)
+    routes = (("parent", a.parent_bin, {}), ("whole", new_bin, {"YACRD_EDIT_WINDOW": never}), ("windows", new_bin, {"YACRD_EDIT_WINDOW": str(a.window)}))
+    base = {k: v for k, v in os.environ.items() if k not in ("YACRD_EDIT_WINDOW", "YACRD_DEVICE_INFLATE", "YACRD_NO_DEVICE_INFLATE")}
+    more = {"YACRD_DEVICE_INFLATE": "1"} if a.resident else {}
+    try:
+        host.synth_paf(host.SYNTH_SEQUEL, a.reads, a.overlaps, 20241108 + 5, paf)
+        size = os.path.getsize(paf)
+        p = subprocess.run([new_bin, "-i", paf, "-o", rep, "-t", "0", "-c", "3", "-n", "0.4"], capture_output=True, text=True)
+        assert p.returncode == 0, p.stderr
+        with yacrd_amd.Engine(device_id=0) as e, e.gzip_writer(src) as w, open(paf, "rb") as f:
+            while True:
+                piece = f.read(1 << 26)
+                if not piece:
+                    break
+                w.write(piece)
+        fresh(paf)
+        det = ["-i", src, "-o", rep2, "-t", "0", "-c", "3", "-n", "0.4"] if a.resident else ["-i", rep, "-o", rep2, "-t", "0"]
+        rows = {name: [] for name, _, _ in routes}
+        for k in range(a.runs + 1):
+            for name, binary, env in routes:
+                fresh(outs[name])
+                fresh(rep2)
+                t0 = time.perf_counter()
+                p = subprocess.run([binary] + det + [a.op, "-i", src, "-o", outs[name]], capture_output=True, text=True,
+                                   env=dict(base, YACRD_CLI_TIMING="1", **more, **env))
+                wall = time.perf_counter() - t0
+                assert p.returncode == 0, p.stderr
+                stages = dict(re.findall(r"^\[timing\] (\S+) ([0-9.]+) s$", p.stderr, re.M))
+                info = [l for l in p.stdout.splitlines() if l.startswith("[info] device editor + deflate:")]
+                assert len(info) == 1, p.stdout + p.stderr  # (the device editor ran: no fallback to the host inflate or the host loop)
+                row = {"edit_s": float(stages["edit"]), "wall_s": round(wall, 3)}
+                for label, key in (("text", "text_ms"), ("table", "table_ms"), ("editor kernels", "kernel_ms"), ("encoder kernels", "encoder_kernel_ms"), ("out", "out_ms")):
+                    m = re.search(r", %s ([0-9.]+) ms" % label, info[0])
+                    if m:
+                        row[key] = float(m.group(1))
+                for flag in ("resident", "device_inflate"):
+                    row[flag] = int(re.search(r"%s=(\d)" % flag, info[0]).group(1))
+                inf = [re.match(r"\[info\] device inflate: .* walk ([0-9.]+) ms, h2d ([0-9.]+) ms, kernels ([0-9.]+) ms", l) for l in p.stderr.splitlines()]
+                inf = [m for m in inf if m]
+                if inf:  # (the last one: the edit's, or — resident — the ingest's, the only one)
+                    row["inflate_h2d_ms"], row["inflate_kernel_ms"] = float(inf[-1].group(2)), float(inf[-1].group(3))
+                m = re.search(r" windows=(\d+)$", info[0])
+                row["windows"] = int(m.group(1)) if m else 0  # (the parent's line does not say: it has none)
+                if k:
+                    rows[name].append(row)
+        assert same(outs["parent"], outs["whole"]) and same(outs["parent"], outs["windows"]), "this tree's file differs from the parent's"
+        assert all(r["resident"] == (1 if a.resident else 0) and r["device_inflate"] == 1 for rs in rows.values() for r in rs)
+        assert all(r["windows"] == 0 for r in rows["whole"]) and all(r["windows"] > 1 for r in rows["windows"])
+        # in this process: what the device holds behind the edit for the two routes of this tree
+        held = {}
+        blob = np.fromfile(src, dtype=np.uint8)
+        with yacrd_amd.Engine(device_id=0) as e:
+            res, names, lengths, _ = e.ingest_bgzf((blob.ctypes.data, int(blob.size)), 3, 0.4)
+            for name, sw in (("whole", 2 ** 64 - 1), ("windows", a.window)):
+                e.trim()  # (the parser's mirror goes with it)
+                if a.resident:
+                    e.ingest_bgzf((blob.ctypes.data, int(blob.size)), 3, 0.4)
+                before = yacrd_amd.engine.live_bytes()[0]
+                e.debug_edit_window(sw)
+                fresh(got)
+                if a.resident:
+                    e.edit_overlaps_resident(op, names, res.read_type, out_path=got)
+                else:
+                    e.edit_overlaps_bgzf(op, blob, names, res.read_type, 1, out_path=got)
+                held[name] = {"device_bytes_beside_what_was_held": int(yacrd_amd.engine.live_bytes()[0] - before), "live_bytes": int(yacrd_amd.engine.live_bytes()[0]),
+                              **e.edit_windows()}
+            e.trim()
+        fresh(got)
+        whole_like = rows["parent"] + rows["whole"]
+        spread = lambda key: (min(r[key] for r in rows["parent"]), max(r[key] for r in rows["parent"]))  # noqa: E731
+        row = {"reads": a.reads, "overlaps": a.overlaps, "op": a.op, "bgzf_in": True, "resident": bool(a.resident), "window": a.window, "text_bytes": size,
+               "bgzf_in_bytes": os.path.getsize(src), "out_bytes": os.path.getsize(outs["parent"]), **rows, "held": held,
+               "whole_kernel_ms_within_parent_spread": all(spread("kernel_ms")[0] <= r["kernel_ms"] <= spread("kernel_ms")[1] for r in rows["whole"]),
+               "whole_edit_s_within_parent_spread": all(r["edit_s"] <= spread("edit_s")[1] for r in rows["whole"]),
+               "whole_wall_s_within_parent_spread": all(r["wall_s"] <= spread("wall_s")[1] for r in rows["whole"]),
+               "slowest_windows_edit_s": max(r["edit_s"] for r in rows["windows"]), "fastest_whole_edit_s": min(r["edit_s"] for r in whole_like),
+               "windows_when_fits_by_the_rule": max(r["edit_s"] for r in rows["windows"]) < min(r["edit_s"] for r in whole_like)}
+        line = json.dumps(row)
+        print(line, flush=True)
+        if a.json:
+            with open(a.json, "a") as f:
+                f.write(line + "\n")
+    finally:
+        for x in made + [got]:
+            fresh(x)
+
+
 def window_bench():
     """--window: the command's edit of a plain (or, --gzip, a gzip -1) overlap file: parent, this tree whole, this tree in windows"""
     import ctypes
@@ -344,6 +445,9 @@ def window_bench():
             fresh(x)
 
 
+if a.window and a.bgzf_in:
+    bgzf_window_bench()
+    sys.exit(0)
 if a.window:
     window_bench()
     sys.exit(0)

@@ -15,6 +15,8 @@ constexpr uint64_t kGzBlock = 65280;                 // deflate_block.h: ydf::kB
 // CLI's routes are decided by: true only if the slowest run in windows is under the fastest whole-text run on both files of
 // DESIGN 7b.  Measured (DESIGN 7n's table): on a par, not under — false.
 constexpr bool kEdWindowsWhenFits = false;
+// The same question for a BGZF text, by the same rule.  Not measured under its fastest whole-text run — false.
+constexpr bool kEdBgzfWindowsWhenFits = false;
 
 enum Route { kWhole = 0, kWindows = 1, kFallback = 2 };
 

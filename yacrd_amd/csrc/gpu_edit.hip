@@ -47,11 +47,16 @@
 // depend on it.  A window is to that run what a segment is to the whole-text run: one round of the same kernels, over
 // positions that count from the window's first byte, with the first chunk of the next window behind it as look-ahead.  The
 // byte in front of a window, the verdict that runs into it, the kept bytes so far and (gzip out) the ragged tail behind the
-// last whole block are handed from window to window on the device.  The BGZF-in and resident forms always run whole.
+// last whole block are handed from window to window on the device.  The resident forms and an edit from the parser's mirror
+// take the same route: their text lies whole in HBM already, so window k is the mirror's bytes from k W on, no text
+// slot is held and nothing is moved; only the output ring and one window's tables are allocated.  BGZF in: the windows are the
+// cuts of bgzf_windows.h that hold text — a window ends where a member ends, anywhere inside a tile —, each inflated into its
+// text slot from byte 0 out of ONE compressed slot (gpu_inflate.hip: inflate_device_run_window); EditRun::bgzf_windows_loop.
 #include "engine_internal.h"
 #include "gpu_text.h"
 #include "edit_table.h"
 #include "edit_route.h"
+#include "bgzf_windows.h"
 #include "host/beside_file.h"
 #include "host/segment_pump.h"
 
@@ -429,6 +434,11 @@ struct EditRun {
     u64 W = 0;  // 0: the whole text at once; else the run goes window by window, this many bytes each (windows_loop)
     u64 wt = 0; // ... tiles of a window
     bool win_fresh[2] = {false, false}; // a text slot that is a new allocation fills faster by copy kernel, once
+    // BGZF in, in windows: the cuts of the member table, those of them that hold text (the edit's windows), the
+    // decoder's one compressed slot
+    std::vector<ybw::WindowCut> cuts;
+    std::vector<size_t> wcut;
+    InflateWindow iw;
     std::atomic<u64> win_released{0};   // the writer has let go of the output of every window below this one
     // reserve(), upload_table()
     bool blit = false; // a fresh mirror fills faster by copy kernel (gpu_paf.hip)
@@ -487,10 +497,25 @@ struct EditRun {
         t_start = now_ms();
         // HBM: the text (unless the parser's mirror serves), as many bytes again for what is kept, a bit per byte, the table
         // The route (edit_route.h): a plain text of more than one window runs in windows where the whole-text need
-        // finds no room, where the switch names a window, or — kEdWindowsWhenFits — always.  The BGZF-in and resident forms and
-        // an edit from the parser's mirror run whole, as before.
-        const u64 sw = tp.bgzf || job.use_mirror ? UINT64_MAX : e->edit_window;
+        // finds no room, where the switch names a window, or — kEdWindowsWhenFits — always.  The resident forms and an edit from
+        // the parser's mirror take the same route with the text left out of both needs: it lies in HBM already.
+        // BGZF in: the window is at least bgzf_windows.h's smallest (a member inflates as a unit), the windows are the cuts
+        // that hold text, and the ring counts the decoder's compressed slot and the largest slice of the member table.
+        u64 sw = e->edit_window;
+        if (tp.bgzf && sw != 0 && sw != UINT64_MAX && yer::window_of(sw) < ybw::kMinWindow) sw = ybw::kMinWindow;
         const u64 Wn = yer::window_of(sw), w_tiles = Wn / yk::kGpTile + 2;
+        u64 max_slice = 0;
+        if (tp.bgzf && n > Wn && sw != UINT64_MAX) {
+            if (!ybw::window_cuts(tp.bgzf->members.data(), tp.bgzf->members.size(), Wn, cuts)) return fail(YACRD_ENOMEM, "host allocation failed");
+            try {
+                for (size_t i = 0; i < cuts.size(); i++) {
+                    max_slice = std::max<u64>(max_slice, cuts[i].m1 - cuts[i].m0);
+                    if (cuts[i].t1 > cuts[i].t0) wcut.push_back(i);
+                }
+            } catch (...) {
+                return fail(YACRD_ENOMEM, "host allocation failed");
+            }
+        }
         const u64 w_gz_blocks = job.gzip ? (yer::out_slot_bytes(Wn, true) + ydf::kBlock - 1) / ydf::kBlock : 0;
         bool whole_fits = true, ring_fits = true;
         size_t free_b = 0, total_b = 0;
@@ -503,18 +528,22 @@ struct EditRun {
                                 table_need + (double)n_tiles * 40.0 +
                                 (double)gz_blocks * (double)ydf::kSlot * 3.0 * 1.125; // (the members' slots and two batches of members)
             whole_fits = need <= have;
-            // the ring: two text and two output slots, one window's tables (the whole text's buffers go before it is taken)
-            const double ring_have = have + (double)S.wtext[0].cap + (double)S.wtext[1].cap + (double)S.wout[0].cap + (double)S.wout[1].cap;
-            const double ring_need = 2.0 * (double)yer::text_slot_bytes(Wn) + 2.0 * (double)yer::out_slot_bytes(Wn, job.gzip) +
+            // the ring: two text and two output slots, one window's tables (the whole text's buffers go before it is taken);
+            // from the mirror: the two output slots alone (text slots an earlier run left go as well)
+            const double ring_have = have + (double)S.wtext[0].cap + (double)S.wtext[1].cap + (double)S.wout[0].cap + (double)S.wout[1].cap +
+                                     (tp.bgzf ? (double)inflate_window_held(e) : 0.0);
+            const double ring_need = (job.use_mirror ? 0.0 : 2.0 * (double)yer::text_slot_bytes(Wn)) + 2.0 * (double)yer::out_slot_bytes(Wn, job.gzip) +
+                                     (tp.bgzf ? ((double)Wn + 64.0 + (double)(max_slice + 64) * sizeof(yif::InfMember)) * 1.125 : 0.0) +
                                      (double)w_tiles * ((double)yk::kGpT * 16.0 + 40.0) * 1.125 + table_need +
                                      (double)w_gz_blocks * (double)ydf::kSlot * 3.0 * 1.125;
             ring_fits = ring_need <= ring_have;
         }
-        const yer::Route route = yer::route(n, sw, whole_fits, ring_fits);
+        const yer::Route route = yer::route(n, sw, whole_fits, ring_fits, tp.bgzf ? yer::kEdBgzfWindowsWhenFits : yer::kEdWindowsWhenFits);
         if (route == yer::kFallback) return fail(YACRD_EFALLBACK, "the file is too large to be edited in this device's free memory: the host loop streams it");
         if (route == yer::kWindows) {
             W = Wn, wt = Wn / yk::kGpTile;
-            n_segs = (size_t)((n + W - 1) / W); // (a window is what a segment is to the whole-text run: one round of the kernels)
+            // (a window is what a segment is to the whole-text run: one round of the kernels)
+            n_segs = tp.bgzf ? wcut.size() : (size_t)((n + W - 1) / W);
             n_batches = n_segs + 1;
             gz_blocks = w_gz_blocks;
         }
@@ -529,10 +558,15 @@ struct EditRun {
             // the ring is what a run in windows holds: the whole-text run's two buffers go first; the slots are exactly their
             // size (no slack: the ring's bytes are a function of W alone)
             S.text.release(), S.out.release();
+            if (tp.bgzf) {
+                inflate_device_release_whole(e); // (and the whole stream's buffer and member table in the inflate scratch)
+                if (const int rcw = inflate_window_open(e, W, &iw)) return rcw;
+            }
             for (int i = 0; i < 2; i++) {
                 const void *before = S.wtext[i].p;
-                HIP_TRY(S.wtext[i].reserve_exact((size_t)yer::text_slot_bytes(W)));
-                win_fresh[i] = S.wtext[i].p != before;
+                if (job.use_mirror) S.wtext[i].release(); // (the windows are the mirror's own bytes: no text slot is held)
+                else HIP_TRY(S.wtext[i].reserve_exact((size_t)yer::text_slot_bytes(W)));
+                win_fresh[i] = !job.use_mirror && S.wtext[i].p != before;
                 HIP_TRY(S.wout[i].reserve_exact((size_t)yer::out_slot_bytes(W, job.gzip)));
             }
         } else {
@@ -608,27 +642,42 @@ struct EditRun {
 
     // ---- a run in windows ------------------------------------------------------------------------------------
     u64 win_tail = 0; // gzip out, the writer's: the kept bytes behind the last encoded block (what the device holds in kEdWinBase)
-    unsigned char *wslot(u64 k) const { return S.wtext[k & 1].as<unsigned char>() + 16; } // window k's byte 0 (behind the front pad)
-    u64 wlen(u64 k) const { return std::min<u64>(W, n - k * W); }                         // its bytes
+    unsigned char *wslot(u64 k) const // window k's byte 0: behind its slot's front pad, or where it lies in the mirror
+    {
+        return job.use_mirror ? const_cast<unsigned char *>(e->mirror.p) + k * W /* (read only) */ : S.wtext[k & 1].as<unsigned char>() + 16;
+    }
+    // window k's first text position and its bytes (BGZF in: those of the k-th cut that holds text, at most W)
+    u64 wbase(u64 k) const { return tp.bgzf ? cuts[wcut[k]].t0 : k * W; }
+    u64 wlen(u64 k) const { return tp.bgzf ? cuts[wcut[k]].t1 - cuts[wcut[k]].t0 : std::min<u64>(W, n - k * W); }
 
     // Window k lies in its slot with `ahead` bytes of window k + 1 behind it: the same mark, carry, scan and pack as a segment
     // of the whole-text run, over positions that count from the window's byte 0.  What it takes from the windows before it
     // and leaves for the next lies on the device (EdArgs::win); its counts go to the host behind the pack, as a segment's do.
+    // From the mirror the window lies where the ingest left it: W is a multiple of the tile, so its byte 0 is as aligned as the
+    // mirror's, the byte in front of it and the look-ahead are the mirror's own, and the 64 zero bytes behind the text's end
+    // are the ones the ingest put there (gpu_paf.hip: ingest_text).
     void launch_window(u64 k, u64 ahead)
     {
         const bool last = k + 1 == n_segs;
         const u32 par = (u32)(k & 1);
-        const u64 n_loc = n - k * W, nl_loc = nl - k * W;
-        const u32 t1 = last ? (u32)((nl_loc + yk::kGpTile - 1) / yk::kGpTile) : (u32)wt; // (at most wt + 1: reserve())
+        // BGZF in: a window that is not the last ends where a member ends, anywhere inside a tile.  Its `nl` is its own bytes L:
+        // ed_starts' mask of positions below nl then keeps every position >= L from being a line start, from being counted
+        // and from being packed, the last tile's `valid` is min(tile, L - tile0) and its flags — so the verdict handed on —
+        // come from the window's last line start.  The line walk reads up to avail = L + ahead as before.  (nl > n, the
+        // newline the text's last line lacks, only ever concerns the last window.)
+        const u64 base = wbase(k), L = wlen(k);
+        const u64 n_loc = n - base, nl_loc = tp.bgzf && !last ? L : nl - base;
+        const u32 t1 = last || tp.bgzf ? (u32)((nl_loc + yk::kGpTile - 1) / yk::kGpTile) : (u32)wt; // (at most wt + 1: reserve())
         unsigned long long *win = S.ctl.as<unsigned long long>() + 8;
         ga.text = wslot(k), ga.n = n_loc, ga.nl = nl_loc;
-        ga.avail = last ? n_loc : W + ahead; // (== n_loc where the look-ahead holds the text's end: position n_loc then ends a line)
-        ga.tile0 = 0, ga.seg = 0, ga.pos0 = k * W, ga.wend = last ? ~0ull : W, ga.win = win, ga.wpar = par;
+        ga.avail = last ? n_loc : L + ahead; // (== n_loc where the look-ahead holds the text's end: position n_loc then ends a line)
+        ga.tile0 = 0, ga.seg = 0, ga.pos0 = base, ga.wend = last ? ~0ull : L, ga.win = win, ga.wpar = par;
         ga.seg_base = reinterpret_cast<const u64 *>(win + yk::kEdWinBase + par);
         ga.out = S.wout[par].as<unsigned char>();
         bool ok = hipEventRecord(ev0[k], e->stream) == hipSuccess;
         // (the 64 zero bytes ed_stage's last 16-byte steps read behind the text's end: inside the slot, n_loc <= W + C here)
-        if (ga.avail == n_loc) ok = ok && hipMemsetAsync(wslot(k) + n_loc, 0, 64, e->stream) == hipSuccess;
+        // (BGZF in: avail is no multiple of 16, so those steps read up to 15 bytes behind it wherever it lies: L + ahead <= W + C)
+        if ((ga.avail == n_loc || tp.bgzf) && !job.use_mirror) ok = ok && hipMemsetAsync(wslot(k) + ga.avail, 0, 64, e->stream) == hipSuccess;
         if (job.gzip && k)
             hipLaunchKernelGGL(yk::ed_tail_kernel, dim3(16), dim3(256), 0, e->stream, ga.out, S.wout[par ^ 1].as<unsigned char>(), win, par);
         hipLaunchKernelGGL(yk::ed_mark_kernel, dim3(t1), dim3(yk::kGpT), 0, e->stream, ga);
@@ -664,18 +713,30 @@ struct EditRun {
     //     The writer reads it behind ev1[k].
     //   the per-window tables, the words of EdArgs::win   One stream, in order; a word read by window k + 1 is written by
     //     window k and overwritten by window k + 2 at the earliest.  The pinned words are per window.
+    // From the mirror there is no text slot and no move: the text is read-only for the whole run and lay complete
+    // before it began (the ingest that left it has returned), so of the above only the output slots and the per-window tables
+    // remain, argued as they are there.
     int windows_loop()
     {
         const u64 K = n_segs, C = yer::chunk_of(W);
+        auto nap = [] {
+            struct timespec ts = {0, 20000};
+            nanosleep(&ts, nullptr);
+        };
+        if (job.use_mirror) {
+            for (u64 k = 0; k < K && !bad.load(); k++) {
+                while (k >= 2 && win_released.load(std::memory_order_acquire) < k - 1 && !bad.load()) nap(); // (the output slot)
+                if (bad.load()) break;
+                launch_window(k, k + 1 == K ? 0 : std::min(C, wlen(k + 1)));
+            }
+            (void)hipStreamSynchronize(e->stream);
+            return 0;
+        }
         Streams lanes; // the mover's copy streams, made once for all the moves
         auto land = [&](u64 k, u64 from, u64 upto) -> int { // bytes [from, upto) of window k -> its slot
             if (upto <= from) return 0;
             return move_text(e, tp.src, k * W + from, upto - from, reinterpret_cast<char *>(wslot(k)) + from, win_fresh[k & 1], job.n_threads,
                              [](u64, u64, u64) {}, (size_t)C, &lanes);
-        };
-        auto nap = [] {
-            struct timespec ts = {0, 20000};
-            nanosleep(&ts, nullptr);
         };
         int rc = land(0, 0, std::min(C, wlen(0)));
         for (u64 k = 0; k < K && !rc && !bad.load(); k++) {
@@ -698,6 +759,89 @@ struct EditRun {
             launch_window(k, ahead);
         }
         (void)hipStreamSynchronize(e->stream); // (the copy streams go with `lanes`; nothing of theirs is pending: move_text waits)
+        return rc;
+    }
+
+    // BGZF in, in windows, on the launching thread; move_text's code.  The cuts of the member table are taken in
+    // order; cut i's bytes [c0, c1) of the stream land in the ONE compressed slot, its slice of the member table goes up and its
+    // members are inflated on the engine's stream.  A cut that holds text is the edit's window k: it is inflated into text slot
+    // k & 1 from byte 0 (tile-aligned), not moved.  A cut without text (a trailing EOF member in a cut of its own, more than W
+    // bytes of empty members) is inflated and checked like any other, stores nothing, launches no edit kernel and is
+    // invisible to the look-ahead and to the words of EdArgs::win.  Window k's look-ahead is the first ahead = min(C, L(k + 1))
+    // bytes of window k + 1, copied on the device behind window k's L(k) bytes, and window k's last byte goes to the other
+    // slot's front pad: 7n's two copies with L(k) in place of W.  Everything the device does here is enqueued on the engine's
+    // stream, in this order per window k: [inflate of the cuts up to window k + 1's] [the two copies] [window k's kernels].
+    // Who may write which buffer when:
+    //   compressed slot   Written by this thread's move (move_text waits for its copy streams) for cut i only after it has
+    //     waited for the event behind the inflate of cut i - 1, the slot's only reader.  That inflate stands in the stream in
+    //     front of window k - 1's kernels, so the landing of window k + 1's cut runs beside them.
+    //   member slice      (grow-only, in the inflate scratch) reserved and filled inside inflate_device_run_window, behind the
+    //     same wait: the inflate of cut i - 1, its last reader, has ended, so a reserve that grows it frees nothing a kernel
+    //     reads; the refill is ordered on the engine's stream.
+    //   text slot (k + 1) & 1   Written by the inflate of window k + 1, enqueued behind window k - 1's kernels (mark, pack:
+    //     its last readers) on the same stream, so behind ev1[k - 1]; its front pad by the one-byte copy behind that inflate.
+    //     Read by the look-ahead copy and by window k + 1's kernels, both enqueued later.
+    //   text slot k & 1   Its bytes [L(k), L(k) + ahead + 64) are written by the look-ahead copy and launch_window's memset,
+    //     behind the inflate of window k (which stored [0, L(k)) only) and in front of window k's kernels.
+    //   status word       One for the run, zeroed by inflate_window_open on the engine's stream; only ever raised.  It comes
+    //     home behind the last launch and verdict() reads it before anything the text says is believed: output of earlier
+    //     windows may have left by then, which is what bad = 3's path is for (the file beside out_path goes, the buffer is freed).
+    //   output slots, the per-window tables, the words of EdArgs::win   As in windows_loop.
+    int bgzf_windows_loop()
+    {
+        const u64 K = n_segs, C = yer::chunk_of(W);
+        BgzfIn &in = *tp.bgzf;
+        Streams lanes;
+        TextSource comp_src;
+        comp_src.mem = in.comp;
+        bool comp_fresh = iw.fresh;
+        size_t next_cut = 0; // the first cut not yet inflated
+        auto inflate_cut = [&](size_t i, unsigned char *dst) -> int {
+            const ybw::WindowCut &c = cuts[i];
+            if (i && hipEventSynchronize(in.move.ev[2 * i - 1]) != hipSuccess) return 1; // (the compressed slot, the member slice)
+            const double t0 = now_ms();
+            const int moved_c = move_text(e, comp_src, c.c0, c.c1 - c.c0, reinterpret_cast<char *>(iw.comp), comp_fresh, job.n_threads, [](u64, u64, u64) {},
+                                          (size_t)C, &lanes);
+            comp_fresh = false;
+            in.move.h2d_ms += (float)(now_ms() - t0);
+            if (moved_c) return moved_c;
+            if (!in.move.ev.add(2) || hipEventRecord(in.move.ev[2 * i], e->stream) != hipSuccess) return 1;
+            if (const int rcw = inflate_device_run_window(e, iw, e->stream, in.members.data() + c.m0, c.m1 - c.m0, c.c0, c.c1, c.t0, c.t1, dst)) {
+                rc_open = rcw;
+                return 1;
+            }
+            if (hipEventRecord(in.move.ev[2 * i + 1], e->stream) != hipSuccess) return 1;
+            in.move.n_ev = 2 * i + 2, in.move.n_launches++;
+            return 0;
+        };
+        auto inflate_upto = [&](u64 k) -> int { // every cut not yet inflated up to window k's own; that one into window k's slot
+            for (; next_cut <= wcut[k]; next_cut++)
+                if (const int r = inflate_cut(next_cut, wslot(k))) return r;
+            return 0;
+        };
+        auto nap = [] {
+            struct timespec ts = {0, 20000};
+            nanosleep(&ts, nullptr);
+        };
+        int rc = inflate_upto(0);
+        for (u64 k = 0; k < K && !rc && !bad.load(); k++) {
+            u64 ahead = 0;
+            if (k + 1 < K) {
+                rc = inflate_upto(k + 1);
+                if (rc) break;
+                ahead = std::min(C, wlen(k + 1));
+                if (hipMemcpyAsync(wslot(k) + wlen(k), wslot(k + 1), (size_t)ahead, hipMemcpyDeviceToDevice, e->stream) != hipSuccess ||
+                    hipMemcpyAsync(wslot(k + 1) - 1, wslot(k) + wlen(k) - 1, 1, hipMemcpyDeviceToDevice, e->stream) != hipSuccess)
+                    bad = 1;
+            } else // (the cuts behind the last window: no text, their members inflated and checked all the same)
+                for (; next_cut < cuts.size() && !rc; next_cut++) rc = inflate_cut(next_cut, wslot(k + 1));
+            while (k >= 2 && win_released.load(std::memory_order_acquire) < k - 1 && !bad.load()) nap(); // (the output slot)
+            if (rc || bad.load()) break;
+            launch_window(k, ahead);
+        }
+        *h_inflate = 0;
+        if (hipMemcpyAsync(const_cast<u32 *>(h_inflate), iw.status, sizeof(u32), hipMemcpyDeviceToHost, e->stream) != hipSuccess && !rc) rc = 1;
+        (void)hipStreamSynchronize(e->stream);
         return rc;
     }
 
@@ -824,7 +968,7 @@ struct EditRun {
             setup_ok = setup_ok && side.add(1) && gev0.add(n_batches) && gev1.add(n_batches) && gdone.add(n_batches, hipEventDisableTiming);
         if (!setup_ok) return false;
         std::thread wt([this] { writer(); });
-        if (W) moved = windows_loop();
+        if (W) moved = tp.bgzf ? bgzf_windows_loop() : windows_loop();
         else if (job.use_mirror) {
             for (size_t s = 0; s < n_segs && !bad.load(); s++) launch_segment((u64)s * kSegBytes, (u64)(s + 1) * kSegBytes, n);
         } else {
@@ -879,7 +1023,9 @@ struct EditRun {
             u64 reach = 0;
             HIP_TRY(hipMemcpy(&reach, S.ctl.as<u64>() + 3, sizeof reach, hipMemcpyDeviceToHost));
             e->edit_windows[0] = n_segs, e->edit_windows[1] = reach;
-            e->edit_windows[2] = S.wtext[0].cap + S.wtext[1].cap, e->edit_windows[3] = S.wout[0].cap + S.wout[1].cap;
+            // (from the mirror: no text ring; BGZF in: the decoder's compressed slot and member slice count with the text ring)
+            e->edit_windows[2] = S.wtext[0].cap + S.wtext[1].cap + (tp.bgzf ? inflate_window_held(e) : 0);
+            e->edit_windows[3] = S.wout[0].cap + S.wout[1].cap;
         }
         if (stats) {
             stats->text_bytes = n;

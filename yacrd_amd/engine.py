@@ -847,16 +847,17 @@ class Engine:
     def debug_edit_window(self, window_bytes):
         """yacrd_debug_edit_window (tests, A/B): the overlap editor's window.  0: the policy (128 MiB windows where the whole text
         finds no room); 2**64 - 1: never windows; any other value: rounded up to a 32 KiB tile, and every plain overlap text
-        longer than it is edited window by window (csrc/gpu_edit.hip: windows_loop; the BGZF-in and resident forms and an edit
-        from the parser's mirror run whole).  The bytes written do not depend on it."""
+        longer than it is edited window by window (csrc/gpu_edit.hip: windows_loop).  The resident forms and an edit from the
+        parser's mirror take their windows from the text in HBM and hold no text ring; for the BGZF-in forms the window is at
+        least 64 KiB and the windows end where members end.  The bytes written do not depend on it."""
         self._lib.yacrd_debug_edit_window.restype = ctypes.c_int
         self._lib.yacrd_debug_edit_window.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
         _check(self._lib, self._lib.yacrd_debug_edit_window(self._h, int(window_bytes)))
 
     def edit_windows(self):
         """yacrd_debug_edit_windows (tests, tools): what the last overlap edit ran as: its windows (0: the whole text at once),
-        the farthest a line that began in one window reached into the next, the device bytes of its text ring and of its
-        output ring."""
+        the farthest a line that began in one window reached into the next, the device bytes of its text ring (BGZF in: with
+        the decoder's compressed slot and member slice; from the mirror: 0) and of its output ring."""
         out = (ctypes.c_uint64 * 4)()
         self._lib.yacrd_debug_edit_windows.restype = None
         self._lib.yacrd_debug_edit_windows.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
