@@ -25,6 +25,7 @@ with the stages inflate + detect + edit of YACRD_CLI_TIMING as the figure compar
 editor's and the decoder's own stats per run, every output compared byte for byte (-c 4 -n 0.4 here).  One JSON line per case, and one
 more for the same calls warm in ONE process: Engine.ingest_bgzf + edit_overlaps_resident, and edit_overlaps_bgzf, K runs after a warm-up.
 --parent-again: a second series of the parent behind the new one ("parent_again" in the row): what drifted meanwhile shows.
+  (--window without --bgzf-in, where the routes take turns: the parent once more at the end of every turn)
 --window BYTES --parent-bin PATH [--gzip]: the overlap editor in windows against the whole-text run.  The command
     yacrd -i r.yacrd -o r2.yacrd -t 0 <op> -i ovl.paf -o kept.paf
 (the detection read from a report: the text is moved, no mirror serves) on the synthetic PAF — with --gzip on its gzip -1 form, which
@@ -370,9 +371,12 @@ def window_bench():
     ext = ".paf.gz" if a.gzip else ".paf"
     src, rep, rep2 = (tag + "in.paf.gz" if a.gzip else paf), tag + "r.yacrd", tag + "r2.yacrd"
     outs = {"parent": tag + "old" + ext, "whole": tag + "whole" + ext, "windows": tag + "win" + ext}
-    made = [paf, src, rep, rep2] + list(outs.values())
     never = str(2 ** 64 - 1)
     routes = (("parent", a.parent_bin, {}), ("whole", new_bin, {"YACRD_EDIT_WINDOW": never}), ("windows", new_bin, {"YACRD_EDIT_WINDOW": str(a.window)}))
+    if a.parent_again:  # (the parent once more in every turn, behind this tree's two: what drifts within a turn shows)
+        routes += (("parent_again", a.parent_bin, {}),)
+        outs["parent_again"] = tag + "old2" + ext
+    made = [paf, src, rep, rep2] + list(outs.values())
     line_tag = "[info] device editor + deflate:" if a.gzip else "[info] device editor:"
     kernels = "editor kernels" if a.gzip else "kernels"
     base = {k: v for k, v in os.environ.items() if k != "YACRD_EDIT_WINDOW"}
@@ -406,7 +410,7 @@ def window_bench():
                 row["windows"] = int(m.group(1)) if m else 0  # (the parent's line does not say: it has none)
                 if k:
                     rows[name].append(row)
-        assert same(outs["parent"], outs["whole"]) and same(outs["parent"], outs["windows"]), "this tree's file differs from the parent's"
+        assert all(same(outs["parent"], outs[name]) for name in outs), "a file differs from the parent's first"
         assert all(r["windows"] == 0 for r in rows["whole"]) and all(r["windows"] == (size + a.window - 1) // a.window for r in rows["windows"])
         # in this process: what the device holds for the two routes of this tree (plain text out; with --gzip the members)
         held = {}

@@ -57,8 +57,8 @@
 #include "edit_table.h"
 #include "edit_route.h"
 #include "bgzf_windows.h"
+#include "gpu_out.h"
 #include "host/beside_file.h"
-#include "host/segment_pump.h"
 
 #include <condition_variable>
 #include <cstdio>
@@ -388,7 +388,6 @@ __global__ __launch_bounds__(kGpT) void ed_pack_kernel(EdArgs a)
 
 namespace {
 
-constexpr size_t kOutPiece = (size_t)4 << 20;
 constexpr u64 kSegBytes = (u64)(kTextChunk * kTextSeg); // the mover's segment: what one round of mark, carry, scan and pack covers
 static_assert(yer::kTile == (u64)yk::kGpTile && yer::kChunkMax == (u64)kTextChunk && yer::kWindowDefault == kSegBytes && yer::kGzBlock == (u64)ydf::kBlock,
               "edit_route.h restates the tile, the chunk, the segment and the encoder's block");
@@ -426,7 +425,7 @@ struct EditRun {
     // plan(): sizes
     u64 R = 0, name_bytes = 0; // reads of the type table, their names' bytes
     u64 nl = 0, n_tiles = 0;   // n, or n + 1 when the last line lacks its newline; tiles of that
-    size_t n_segs = 0, n_batches = 0; // gzip out: a batch per segment, or the one that only holds the EOF member
+    size_t n_segs = 0;
     u64 cap = 1024;            // slots of the id table
     u64 gz_blocks = 0;         // gzip out: a batch is at most a segment's kept bytes and the tail carried into it
     u32 n_fields = 0;
@@ -445,28 +444,18 @@ struct EditRun {
     yk::EdArgs ga{};
     u64 *seg_base = nullptr;
     volatile u64 *h_seg = nullptr; // pinned, per segment: lines, kept, status, kept bytes so far
-    volatile u64 *h_gz = nullptr;  // pinned, per batch: its members' bytes, stored members so far
     volatile u32 *h_inflate = nullptr; // pinned: the decoder's status word (a BGZF text), fetched behind the last segment
     int rc_open = YACRD_OK;            // the code of an inflate that could not be set up
-    GzDevice gz;
-    GzHold gz_hold;
     // run(): the segments' kernels on the engine's stream, the writer thread behind their events
     Events ev0, ev1;           // around a segment's kernels (timing)
-    Events wev;                // a pinned piece has landed (two; no timing)
-    Events gev0, gev1, gdone;  // around the kernels of every batch of the encoder (timing); behind its sizes' way home (no timing)
-    Streams side;              // [0] the way home; [1] the encoder (gzip out)
     std::atomic<int> bad{0};   // 1 a HIP call failed, 2 the output could not be written, 3 the text is not for this path
+    OutDevice od;              // the way out of HBM (gpu_out.h; the order and the release rule: host/way_out.h)
+    Out out{od, sink};
     std::atomic<size_t> dispatched{0};
     std::atomic<bool> no_more{false};
     int moved = 0; // move_text's verdict
-    double out_busy_ms = 0, put_ms = 0;
-    u64 gz_text = 0, gz_members = 0, gz_stored = 0; // gzip out: kept bytes encoded, their members, the stored ones
-    size_t gz_sent = 0, gz_got = 0;                 // batches launched / fetched
-    std::vector<u64> gz_eof;                        // per batch: the EOF member's bytes behind its members
-    float kernel_ms = 0, gz_kernel_ms = 0;
-
-    hipStream_t wstream() const { return side[0]; }
-    hipStream_t gstream() const { return side[1]; }
+    double out_busy_ms = 0;
+    float kernel_ms = 0;
 
     // sizes, and whether this device's free memory takes the edit
     int plan()
@@ -490,7 +479,6 @@ struct EditRun {
         n_tiles = (nl + yk::kGpTile - 1) / yk::kGpTile;
         if (n_tiles >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "file too large for the device editor");
         n_segs = (size_t)((n + kSegBytes - 1) / kSegBytes);
-        n_batches = n_segs + 1;
         while (cap < 2 * R) cap <<= 1;
         gz_blocks = job.gzip ? (std::min<u64>(nl, kSegBytes) + ydf::kBlock - 1) / ydf::kBlock + 1 : 0;
         ga.delim = (u32)(unsigned char)delim, ga.ib = ib, ga.n_fields = n_fields, ga.keep_good = job.op == 1 ? 1u : 0u;
@@ -544,7 +532,6 @@ struct EditRun {
             W = Wn, wt = Wn / yk::kGpTile;
             // (a window is what a segment is to the whole-text run: one round of the kernels)
             n_segs = tp.bgzf ? wcut.size() : (size_t)((n + W - 1) / W);
-            n_batches = n_segs + 1;
             gz_blocks = w_gz_blocks;
         }
         return YACRD_OK;
@@ -584,16 +571,16 @@ struct EditRun {
         const size_t ctl_words = 8 + (W ? (size_t)yk::kEdWinWords : n_segs + 2);
         HIP_TRY(S.ctl.reserve(ctl_words * sizeof(u64)));
         HIP_TRY(hipMemsetAsync(S.ctl.p, 0, ctl_words * sizeof(u64), e->stream));
-        HIP_TRY(S.pin.reserve(2 * kOutPiece + (n_segs + 2) * 4 * sizeof(u64) + (job.gzip ? n_batches * 2 * sizeof(u64) : 0) + sizeof(u64)));
+        HIP_TRY(S.pin.reserve(2 * kOutPiece + (n_segs + 2) * 4 * sizeof(u64) + (job.gzip ? 4 * sizeof(u64) : 0) + sizeof(u64)));
         h_seg = reinterpret_cast<volatile u64 *>(S.pin.as<char>() + 2 * kOutPiece);
-        h_gz = h_seg + (n_segs + 2) * 4;
-        h_inflate = reinterpret_cast<volatile u32 *>(h_gz + (job.gzip ? n_batches * 2 : 0));
+        volatile u64 *h_gz = h_seg + (n_segs + 2) * 4; // gzip out: the encoder's two pairs of words
+        h_inflate = reinterpret_cast<volatile u32 *>(h_gz + (job.gzip ? 4 : 0));
         *h_inflate = 0;
-        if (job.gzip) {
-            if (const int rcg = gzip_device_open(e, gz_blocks, &gz)) return rcg;
-            gz_hold.e = e;
-            gz_eof.assign(n_batches, 0);
-        }
+        // (no wait for the engine's stream behind the open: upload_table() waits for it, in front of the first segment)
+        if (job.gzip)
+            if (const int rcg = od.open(e, gz_blocks, false)) return rcg;
+        od.stop = &bad;
+        out.bind(S.pin.as<char>(), h_gz);
         return YACRD_OK;
     }
 
@@ -707,10 +694,9 @@ struct EditRun {
     //     window k's.  Both moves end (move_text waits for its copy streams) before the copies that read them are enqueued.
     //   text slot (k + 1) & 1  While window k's kernels run it takes window k + 1's rest: they read of it only what the
     //     device copies took before them — nothing.
-    //   output slot k & 1     Written by window k's tail copy and pack, behind the wait below for win_released > k - 2:
-    //     the writer has brought window k - 2's bytes home (plain) or has fetched the batch encoded from them (gzip out),
-    //     and window k - 1's tail copy, the only other reader, ran on the engine's stream in front of window k's launches.
-    //     The writer reads it behind ev1[k].
+    //   output slot k & 1     Written by window k's tail copy and pack, behind the wait below for win_released > k - 2 (when
+    //     the writer lets a slot go: host/way_out.h), and window k - 1's tail copy, the only other reader, ran on the
+    //     engine's stream in front of window k's launches.  The writer reads it behind ev1[k].
     //   the per-window tables, the words of EdArgs::win   One stream, in order; a word read by window k + 1 is written by
     //     window k and overwritten by window k + 2 at the earliest.  The pinned words are per window.
     // From the mirror there is no text slot and no move: the text is read-only for the whole run and lay complete
@@ -786,7 +772,7 @@ struct EditRun {
     //   status word       One for the run, zeroed by inflate_window_open on the engine's stream; only ever raised.  It comes
     //     home behind the last launch and verdict() reads it before anything the text says is believed: output of earlier
     //     windows may have left by then, which is what bad = 3's path is for (the file beside out_path goes, the buffer is freed).
-    //   output slots, the per-window tables, the words of EdArgs::win   As in windows_loop.
+    //   output slots (host/way_out.h), the per-window tables, the words of EdArgs::win   As in windows_loop.
     int bgzf_windows_loop()
     {
         const u64 K = n_segs, C = yer::chunk_of(W);
@@ -845,55 +831,11 @@ struct EditRun {
         return rc;
     }
 
-    // base[from, upto) in HBM -> the sink through the two pinned pieces: one flies while the other is written (host/segment_pump.h)
-    void bring_home(const char *base, u64 from, u64 upto)
+    // what the way out says (host/way_out.h) as this run's code; a stop is another thread's code, which stays
+    void took(yout::Result r)
     {
-        HomeLink dma{base + from, wstream(), {wev[0], wev[1]}, &bad};
-        const int rc = yseg::pump(upto - from, kOutPiece, S.pin.as<char>(), dma, sink, [&](auto put) {
-            const double tp = now_ms();
-            put();
-            put_ms += now_ms() - tp;
-        });
-        if (rc == yseg::kLinkFailed && !bad.load()) bad = 1; // (wait also gives up when another thread has set a code: that code stays)
-        if (rc == yseg::kSinkFailed) bad = 2;
-    }
-
-    // gzip out (both run on the writer thread).  encode: kept bytes [gz_text, upto) -> a batch of members, on the encoder's
-    // stream; the pack that wrote them has finished (the writer has waited for the segment's event).  fetch_batch: the
-    // oldest batch not yet fetched -> the sink.
-    void encode(const unsigned char *src, u64 len, bool last)
-    {
-        const size_t b = gz_sent;
-        if (b >= n_batches || len > gz.max_blocks * ydf::kBlock) {
-            bad = 1;
-            return;
-        }
-        h_gz[2 * b] = h_gz[2 * b + 1] = 0;
-        if (gzip_device_encode(e, gz, gstream(), src, len, last, (int)(b & 1), gev0[b], gev1[b], h_gz + 2 * b,
-                               h_gz + 2 * b + 1) != YACRD_OK ||
-            hipEventRecord(gdone[b], gstream()) != hipSuccess) {
-            bad = 1;
-            return;
-        }
-        gz_eof[b] = last ? ydf::kEofBytes : 0u;
-        gz_members += (len + ydf::kBlock - 1) / ydf::kBlock;
-        gz_text += len, gz_sent = b + 1;
-    }
-    void fetch_batch()
-    {
-        const size_t b = gz_got;
-        if (hipEventSynchronize(gdone[b]) != hipSuccess) { // (not the stream: the next batch is being encoded on it)
-            bad = 1;
-            return;
-        }
-        const u64 bytes = h_gz[2 * b] + gz_eof[b];
-        if (bytes > gz.max_blocks * ydf::kSlot + ydf::kEofBytes) {
-            bad = 1;
-            return;
-        }
-        gz_stored = h_gz[2 * b + 1];
-        bring_home(reinterpret_cast<const char *>(gz.out[b & 1]), 0, bytes);
-        gz_got = b + 1;
+        if (r == yout::kSinkFailed) bad = 2;
+        else if ((r == yout::kDeviceFailed || r == yout::kBoundBroken) && !bad.load()) bad = 1;
     }
 
     // the writer thread: segment by segment, in order, what the pack has finished goes home (or to the encoder)
@@ -922,39 +864,35 @@ struct EditRun {
                 break;
             }
             const double t0 = now_ms();
+            const bool last = s + 1 == n_segs;
             if (W) {
                 // a window's kept bytes lie in its own slot, from 0 (gzip out: behind the tail of the window before, which
                 // ed_tail_kernel has put there).  The slot is let go when nothing reads it any more: plain, when its bytes
-                // are home; gzip out, when the batch encoded from it has been fetched — one window later, so that a batch
+                // are home; gzip out, one window later, when every batch but this window's has been fetched — so that a batch
                 // is encoded while the one before it comes home, as in the whole-text run
-                const bool last = s + 1 == n_segs;
                 if (!job.gzip) {
-                    bring_home(S.wout[s & 1].as<char>(), 0, upto - from);
+                    took(out.home(S.wout[s & 1].as<char>(), upto - from));
                     win_released.store((u64)s + 1, std::memory_order_release);
                 } else {
                     const u64 filled = win_tail + (upto - from), whole = last ? filled : filled / ydf::kBlock * ydf::kBlock;
-                    const size_t sent_before = gz_sent;
-                    if (whole || last) encode(S.wout[s & 1].as<unsigned char>(), whole, last);
-                    while (gz_got + (gz_sent - sent_before) < gz_sent && !bad.load()) fetch_batch(); // (every batch but this window's)
+                    took(out.text(S.wout[s & 1].as<unsigned char>(), whole, last, yout::kNoTag));
                     win_tail = filled - whole;
                     win_released.store((u64)s, std::memory_order_release);
                 }
-            } else if (!job.gzip) bring_home(S.out.as<char>(), from, upto);
+            } else if (!job.gzip) took(out.home(S.out.as<char>() + from, upto - from));
             else {
                 // every whole block that now lies complete behind the last encoded one (the last segment: the tail too, and
                 // the EOF member) goes to the encoder; the batch before it comes home while this one is encoded
-                const bool last = s + 1 == n_segs;
                 const u64 whole = last ? upto : upto / ydf::kBlock * ydf::kBlock;
-                if (whole > gz_text || last) encode(S.out.as<unsigned char>() + gz_text, whole - gz_text, last);
-                while (gz_got + 1 < gz_sent && !bad.load()) fetch_batch();
+                if (whole > out.text_bytes || last) took(out.text(S.out.as<unsigned char>() + out.text_bytes, whole - out.text_bytes, last, yout::kNoTag));
             }
             from = upto, seen = s + 1;
             out_busy_ms += now_ms() - t0;
         }
         if (job.gzip && !bad.load() && seen == n_segs) {
             const double t0 = now_ms();
-            if (n_segs == 0) encode(S.out.as<unsigned char>(), 0, true); // (an empty text: the EOF member alone)
-            while (gz_got < gz_sent && !bad.load()) fetch_batch();
+            if (n_segs == 0) took(out.text(S.out.as<unsigned char>(), 0, true, yout::kNoTag)); // (an empty text: the EOF member alone)
+            took(out.drain());
             out_busy_ms += now_ms() - t0;
         }
     }
@@ -963,10 +901,7 @@ struct EditRun {
     // segments, the writer thread takes them from their events.  false: a stream or an event could not be created
     bool run()
     {
-        bool setup_ok = side.add(1) && wev.add(2, hipEventDisableTiming) && ev0.add(n_segs) && ev1.add(n_segs);
-        if (job.gzip)
-            setup_ok = setup_ok && side.add(1) && gev0.add(n_batches) && gev1.add(n_batches) && gdone.add(n_batches, hipEventDisableTiming);
-        if (!setup_ok) return false;
+        if (!od.make(job.gzip) || !ev0.add(n_segs) || !ev1.add(n_segs)) return false;
         std::thread wt([this] { writer(); });
         if (W) moved = tp.bgzf ? bgzf_windows_loop() : windows_loop();
         else if (job.use_mirror) {
@@ -982,14 +917,13 @@ struct EditRun {
         const double t_text_done = now_ms();
         wt.join();
         (void)hipStreamSynchronize(e->stream);
-        if (job.gzip) (void)hipStreamSynchronize(gstream());
+        od.quiet();
         if (stats) stats->text_ms = job.use_mirror ? 0.0f : (float)(t_text_done - t_table);
         if (!bad.load() && !moved) {
             for (size_t s = 0; s < n_segs; s++) {
                 float ms = 0;
                 if (hipEventElapsedTime(&ms, ev0[s], ev1[s]) == hipSuccess) kernel_ms += ms;
             }
-            for (size_t b = 0; b < gz_sent; b++) gz_kernel_ms += ev_ms(gev0[b], gev1[b]);
         }
         return true;
     }
@@ -1016,9 +950,9 @@ struct EditRun {
             return fail(YACRD_EFALLBACK, "the text holds a '\"', a CR, a line whose field count differs from the first line's or one that is "
                                          "megabytes long: the host loop decides");
         if (h_status) return fail(YACRD_EINTERNAL, "overlap editor: the mark and the pack pass disagree");
-        if ((job.gzip ? gz_text : sink.at) != h_bytes) return fail(YACRD_EINTERNAL, "overlap editor: fewer bytes written than kept");
-        if (job.gzip && gz_got != gz_sent) return fail(YACRD_EINTERNAL, "overlap editor: a batch of members was not fetched");
-        fill_gzip_stats(job.gzip_stats, gz_text, sink.at, gz_members, gz_stored, gz_kernel_ms, out_busy_ms, put_ms);
+        if ((job.gzip ? out.text_bytes : sink.at) != h_bytes) return fail(YACRD_EINTERNAL, "overlap editor: fewer bytes written than kept");
+        if (job.gzip && out.got != out.sent) return fail(YACRD_EINTERNAL, "overlap editor: a batch of members was not fetched");
+        fill_gzip_stats(job.gzip_stats, out.text_bytes, sink.at, out.members, out.stored, od.kernel_ms(), out_busy_ms, out.put_ms);
         if (W) { // how the edit ran (yacrd_debug_edit_windows); the farthest reach lies in the control words behind the last pack
             u64 reach = 0;
             HIP_TRY(hipMemcpy(&reach, S.ctl.as<u64>() + 3, sizeof reach, hipMemcpyDeviceToHost));
@@ -1053,16 +987,12 @@ int run_edit(yacrd_engine *e, const EditJob &job, TextProducer &tp, u64 n, Sink 
     if (const int rc = r.upload_table()) return rc;
     return r.verdict(r.run());
 }
-int run_edit(yacrd_engine *e, const EditJob &job, const TextSource &src, u64 n, Sink &sink, yacrd_edit_stats *stats)
-{
-    TextProducer tp(src);
-    return run_edit(e, job, tp, n, sink, stats);
-}
 
 int edit_args(yacrd_engine *e, int op, const yacrd_type_table *types, yacrd_edit_stats *stats);
 
-// ---- what the _bgzf_ and _resident_ forms share: where the output goes ------------------------------------------------------
-// memory: the kept bytes are at most the text and its added newline; members start at a quarter of the text and grow
+// ---- what every form shares: where the output goes --------------------------------------------------------------------------
+// memory: the kept bytes are at most the text and its added newline; members start at a quarter of the text (PAF text shrinks
+// to about that) and grow
 int edit_to_mem(yacrd_engine *e, const EditJob &job, TextProducer &tp, u64 n, char **out, uint64_t *out_bytes, yacrd_edit_stats *es)
 {
     Sink sink;
@@ -1077,7 +1007,8 @@ int edit_to_mem(yacrd_engine *e, const EditJob &job, TextProducer &tp, u64 n, ch
     *out = sink.mem, *out_bytes = sink.at;
     return YACRD_OK;
 }
-// a file: yacrd_engine_edit_overlaps_gzip_file's rules — written beside its place and moved there when every byte is in it
+// a file: written beside its place and moved there when every byte (gzip out: the EOF member) is in it — a text that turns out
+// not to be for this path (a later segment may say so, with earlier ones already written) leaves nothing behind
 int edit_to_file(yacrd_engine *e, const EditJob &job, TextProducer &tp, u64 n, const char *out_path, yacrd_edit_stats *es)
 {
     struct stat ost;
@@ -1176,25 +1107,18 @@ int yacrd_engine_edit_overlaps(yacrd_engine *e, int op, const char *in_path, con
     struct stat st, ost;
     if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) return fail(YACRD_EFALLBACK, "not a regular file: the host loop reads it");
     if (is_compressed_magic(fd)) return fail(YACRD_EFALLBACK, "a compressed file: the host loop inflates it and deflates what it keeps");
-    // the output: written beside its place and moved there when every byte is in it — a text that turns out not to be for
-    // this path (the last segment may say so) leaves nothing behind.  Anything but a new or a regular file is the host loop's.
-    if (lstat(out_path, &ost) == 0) {
-        if (!S_ISREG(ost.st_mode)) return fail(YACRD_EFALLBACK, "the output is not a regular file: the host loop writes it");
-        if (ost.st_dev == st.st_dev && ost.st_ino == st.st_ino) return fail(YACRD_EFALLBACK, "input and output are one file: the host loop's case");
-    }
-    yseg::BesideFile file;
-    if (!file.open(out_path)) return fail(YACRD_EFALLBACK, std::string("cannot create a file beside ") + out_path + ": the host loop words the error");
+    // the output: written beside its place and moved there when every byte is in it (edit_to_file) — a text that turns out not
+    // to be for this path (the last segment may say so) leaves nothing behind.  Anything but a new or a regular file is the host
+    // loop's, and so is a regular one that is the input
+    if (lstat(out_path, &ost) == 0 && S_ISREG(ost.st_mode) && ost.st_dev == st.st_dev && ost.st_ino == st.st_ino)
+        return fail(YACRD_EFALLBACK, "input and output are one file: the host loop's case");
     // (a mirror that did not come from a file has no identity: it never matches one)
     job.use_mirror = e->mirror.valid && e->mirror.from_file && e->mirror.p && e->mirror.n == (u64)st.st_size && e->mirror.dev == (u64)st.st_dev &&
                      e->mirror.ino == (u64)st.st_ino && e->mirror.mtime_s == (int64_t)st.st_mtim.tv_sec &&
                      e->mirror.mtime_ns == (int64_t)st.st_mtim.tv_nsec;
-    TextSource src;
-    src.fd = fd;
-    Sink sink;
-    sink.fd = file.fd;
-    int rc = run_edit(e, job, src, (u64)st.st_size, sink, stats);
-    if (rc == YACRD_OK && !file.commit()) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
-    return rc;
+    TextProducer tp;
+    tp.src.fd = fd;
+    return edit_to_file(e, job, tp, (u64)st.st_size, out_path, stats);
 }
 
 int yacrd_engine_edit_overlaps_mem(yacrd_engine *e, int op, const char *text, uint64_t n, int format, const yacrd_type_table *types,
@@ -1206,18 +1130,9 @@ int yacrd_engine_edit_overlaps_mem(yacrd_engine *e, int op, const char *text, ui
     EditJob job;
     job.op = op, job.types = types;
     if (const int rcf = overlap_format(nullptr, format, job.m4)) return rcf;
-    TextSource src;
-    src.mem = text ? text : "";
-    Sink sink;
-    sink.mem = (char *)std::malloc((size_t)n + 2);
-    if (!sink.mem) return fail(YACRD_ENOMEM, "host allocation failed");
-    const int rc = run_edit(e, job, src, n, sink, stats);
-    if (rc != YACRD_OK) {
-        std::free(sink.mem);
-        return rc;
-    }
-    *out = sink.mem, *out_bytes = sink.at;
-    return YACRD_OK;
+    TextProducer tp;
+    tp.src.mem = text ? text : "";
+    return edit_to_mem(e, job, tp, n, out, out_bytes, stats);
 }
 
 int yacrd_engine_edit_overlaps_gzip_mem(yacrd_engine *e, int op, const char *text, uint64_t n, int format, const yacrd_type_table *types,
@@ -1230,20 +1145,11 @@ int yacrd_engine_edit_overlaps_gzip_mem(yacrd_engine *e, int op, const char *tex
     EditJob job;
     job.op = op, job.types = types, job.gzip = true, job.gzip_stats = gs;
     if (const int rcf = overlap_format(nullptr, format, job.m4)) return rcf;
-    TextSource src;
-    src.mem = text ? text : "";
-    Sink sink;
-    sink.cap = (size_t)(n / 4 + 4096); // (PAF text shrinks to about a quarter; the sink grows when it does not)
-    sink.mem = (char *)std::malloc((size_t)sink.cap);
-    if (!sink.mem) return fail(YACRD_ENOMEM, "host allocation failed");
-    const int rc = run_edit(e, job, src, n, sink, es);
-    if (rc != YACRD_OK) { // (members of earlier segments may lie in the buffer: it goes)
-        std::free(sink.mem);
-        if (gs) std::memset(gs, 0, sizeof(*gs));
-        return rc;
-    }
-    *out = sink.mem, *out_bytes = sink.at;
-    return YACRD_OK;
+    TextProducer tp;
+    tp.src.mem = text ? text : "";
+    const int rc = edit_to_mem(e, job, tp, n, out, out_bytes, es);
+    if (rc != YACRD_OK && gs) std::memset(gs, 0, sizeof(*gs));
+    return rc;
 }
 
 int yacrd_engine_edit_overlaps_gzip_file(yacrd_engine *e, int op, const char *text, uint64_t n, int format, const yacrd_type_table *types,
@@ -1255,18 +1161,9 @@ int yacrd_engine_edit_overlaps_gzip_file(yacrd_engine *e, int op, const char *te
     EditJob job;
     job.op = op, job.types = types, job.gzip = true, job.gzip_stats = gs;
     if (const int rcf = overlap_format(nullptr, format, job.m4)) return rcf;
-    struct stat ost;
-    if (lstat(out_path, &ost) == 0 && !S_ISREG(ost.st_mode)) return fail(YACRD_EFALLBACK, "the output is not a regular file: the host loop writes it");
-    // written beside its place and moved there when the EOF member is in: a text that turns out not to be for this path
-    // (a later segment may say so, with members of earlier ones already written) leaves nothing behind
-    yseg::BesideFile file;
-    if (!file.open(out_path)) return fail(YACRD_EFALLBACK, std::string("cannot create a file beside ") + out_path + ": the host loop words the error");
-    TextSource src;
-    src.mem = text ? text : "";
-    Sink sink;
-    sink.fd = file.fd;
-    int rc = run_edit(e, job, src, n, sink, es);
-    if (rc == YACRD_OK && !file.commit()) rc = fail(YACRD_EINVAL, "Error during writing of the output file");
+    TextProducer tp;
+    tp.src.mem = text ? text : "";
+    const int rc = edit_to_file(e, job, tp, n, out_path, es);
     if (rc != YACRD_OK && gs) std::memset(gs, 0, sizeof(*gs));
     return rc;
 }

@@ -49,8 +49,8 @@
 #include "edit_table.h"
 #include "bgzf_walk.h"
 #include "bgzf_windows.h"
+#include "gpu_out.h"
 #include "host/beside_file.h"
-#include "host/segment_pump.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -767,7 +767,6 @@ struct Fasta {
 
 namespace {
 
-constexpr size_t kOutPiece = (size_t)4 << 20; // (_PIECE of the tests: what one copy home moves)
 constexpr u64 kGzBatchBlocks = 2048;          // blocks of 65 280 bytes per batch of the encoder
 // whether a text that fits whole runs in windows all the same (the switch aside): decided by measurement, DESIGN 7k, 7l
 constexpr bool kSeqWindowsWhenFits = false;
@@ -813,17 +812,12 @@ struct SeqRun {
     bool blit = false;
     yk::SqArgs ga{};
     yk::FaArgs fa{}; // (FASTA: what the kernels behind the line index take)
-    volatile u64 *h_ctl = nullptr; // pinned: [0..3] what a phase brings home, [4..7] the encoder's words of two batches, [8..11] the copy pass's of two windows
+    volatile u64 *h_ctl = nullptr; // pinned: [0..3] what a phase brings home, [4..7] the way out's (the encoder's words), [8..11] the copy pass's of two windows
     Events ev;                     // pairs around the kernels of a phase (timing)
-    Events wev;                    // a pinned piece has landed (two; no timing)
-    Events gev, gdone;             // the encoder's batches: pairs around their kernels; behind their sizes' way home
-    Streams side;                  // [0] the way home; [1] the encoder
     size_t n_ev = 0;
-    GzDevice gz;
-    GzHold gz_hold;
-    double t_start = 0, t_table = 0, t_text = 0, out_busy_ms = 0, put_ms = 0;
-    u64 gz_members = 0, gz_stored = 0;
-    float gz_kernel_ms = 0;
+    OutDevice od;                  // the way out of HBM (gpu_out.h; the order and the release rule: host/way_out.h)
+    Out out{od, sink};
+    double t_start = 0, t_table = 0, t_text = 0, out_busy_ms = 0;
     Events iev; // around the inflate kernel
     float inf_h2d_ms = 0, inf_kernel_ms = 0;
 
@@ -959,7 +953,7 @@ struct SeqRun {
         HIP_TRY(S.pin.reserve(2 * kOutPiece + 12 * sizeof(u64) + 2 * sizeof(yk::FaPiece))); // (the raw pieces of two windows, of the larger kind: run_windows)
         h_ctl = reinterpret_cast<volatile u64 *>(S.pin.as<char>() + 2 * kOutPiece);
         for (int i = 0; i < 12; i++) h_ctl[i] = 0;
-        if (!side.add(job.gzip ? 2 : 1) || !wev.add(2, hipEventDisableTiming) || !ev.add(2 * n_segs + 10)) HIP_TRY(why_not_added());
+        if (!od.make(job.gzip) || !ev.add(2 * n_segs + 10)) HIP_TRY(why_not_added());
         HIP_TRY(S.lengths.reserve((size_t)(R + 1) * sizeof(u32)));
         HIP_TRY(S.bad_off.reserve((size_t)(R + 1) * sizeof(u64)));
         HIP_TRY(S.bad_reg.reserve((size_t)(2 * G + 2) * sizeof(u32)));
@@ -1165,10 +1159,9 @@ struct SeqRun {
         const u64 padded = (total + 15) & ~(u64)15;
         HIP_TRY(S.out.reserve((size_t)padded + 64));
         HIP_TRY(S.pieces.reserve((size_t)(n_pieces + 1) * sizeof(Piece)));
-        if (job.gzip) {
-            if (const int rcg = gzip_device_open(e, gz_blocks, &gz)) return rcg;
-            gz_hold.e = e;
-        }
+        if (job.gzip)
+            if (const int rcg = od.open(e, gz_blocks, true)) return rcg;
+        out.bind(S.pin.as<char>(), h_ctl + 4);
         ga.n_pieces = n_pieces, ga.total = total, ga.out = S.out.as<unsigned char>();
         args(Format{}).pieces = S.pieces.as<Piece>();
         bool ok = ev_open();
@@ -1183,56 +1176,18 @@ struct SeqRun {
     }
     int gather() { return job.fasta ? gather<yk::Fasta>() : gather<yk::Fastq>(); }
 
-    // base[0, len) in HBM -> the sink through the two pinned pieces: one flies while the other is written (host/segment_pump.h)
-    int bring_home(const char *base, u64 len)
+    // what the way out says (host/way_out.h) as this editor's code and message; a stop is the other thread's code.  A call
+    // of the encoder's that failed: the whole-text run returns what the call said, the writer thread of a run in windows its own words
+    int out_says(yout::Result r, const char **msg) const
     {
-        HomeLink dma{base, side[0], {wev[0], wev[1]}};
-        const int rc = yseg::pump(len, kOutPiece, S.pin.as<char>(), dma, sink, [&](auto put) {
-            const double tp = now_ms();
-            put();
-            put_ms += now_ms() - tp;
-        });
-        if (rc == yseg::kLinkFailed) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed on the way home");
-        if (rc == yseg::kSinkFailed) return fail(YACRD_EINVAL, "Error during writing of the output file");
+        *msg = "";
+        if (r == yout::kDeviceFailed && out.on_way_home) return *msg = "sequence editor: a HIP call failed on the way home", YACRD_ENODEV;
+        if (r == yout::kDeviceFailed && !W) return *msg = od.msg.c_str(), od.code;
+        if (r == yout::kDeviceFailed) return *msg = od.no_event ? "sequence editor: a HIP event could not be created" : "sequence editor: a HIP call failed in the encoder", YACRD_ENODEV;
+        if (r == yout::kSinkFailed) return *msg = "Error during writing of the output file", YACRD_EINVAL;
+        if (r == yout::kBoundBroken && out.out_of_order) return *msg = "sequence editor: a batch was to be encoded with two still out", YACRD_EINTERNAL;
+        if (r == yout::kBoundBroken) return *msg = "device deflate: more bytes than the members' slots hold", YACRD_EINTERNAL;
         return YACRD_OK;
-    }
-
-    // gzip out: the output, batch by batch, through the encoder on its own stream; batch b comes home while b + 1 is encoded
-    int deflate_home()
-    {
-        const u64 per = gz.max_blocks * ydf::kBlock;
-        const size_t nb = (size_t)std::max<u64>(1, (total + per - 1) / per);
-        if (!gev.add(2 * nb) || !gdone.add(nb, hipEventDisableTiming)) HIP_TRY(why_not_added());
-        HIP_TRY(hipStreamSynchronize(e->stream)); // (gzip_device_open's memset)
-        auto encode = [&](size_t b) -> int {
-            const u64 from = (u64)b * per, len = std::min(per, total - from);
-            volatile u64 *w = h_ctl + 4 + 2 * (b & 1);
-            w[0] = w[1] = 0;
-            if (const int rc = gzip_device_encode(e, gz, side[1], S.out.as<unsigned char>() + from, len, b + 1 == nb, (int)(b & 1), gev[2 * b],
-                                                  gev[2 * b + 1], w, w + 1))
-                return rc;
-            HIP_TRY(hipEventRecord(gdone[b], side[1]));
-            gz_members += (len + ydf::kBlock - 1) / ydf::kBlock;
-            return YACRD_OK;
-        };
-        auto fetch = [&](size_t b) -> int {
-            HIP_TRY(hipEventSynchronize(gdone[b]));
-            volatile u64 *w = h_ctl + 4 + 2 * (b & 1);
-            const u64 bytes = w[0] + (b + 1 == nb ? ydf::kEofBytes : 0u);
-            if (bytes > gz.max_blocks * ydf::kSlot + ydf::kEofBytes) return fail(YACRD_EINTERNAL, "device deflate: more bytes than the members' slots hold");
-            gz_stored = w[1];
-            return bring_home(reinterpret_cast<const char *>(gz.out[b & 1]), bytes);
-        };
-        int rc = YACRD_OK;
-        for (size_t b = 0; b < nb && rc == YACRD_OK; b++) {
-            rc = encode(b);
-            if (rc == YACRD_OK && b) rc = fetch(b - 1);
-        }
-        if (rc == YACRD_OK) rc = fetch(nb - 1);
-        (void)hipStreamSynchronize(side[1]);
-        if (rc == YACRD_OK)
-            for (size_t b = 0; b < nb; b++) gz_kernel_ms += ev_ms(gev[2 * b], gev[2 * b + 1]);
-        return rc;
     }
 
     // ==== the run in windows (text from a file or from memory; DESIGN 7k, FASTA: 7l) ==================================================
@@ -1265,10 +1220,9 @@ struct SeqRun {
     //                     ended by W1(k + 1), in front of the next reserve of either.
     //   `part`            (the scans' scratch) is reserved inside a scan; the scans of a window follow W1(k), S'(k) or S(k - 1)
     //                     with no other scan in flight but one over as many elements.
-    //   output slots, two slot k & 1 is read by the writer (way home, encoder) for window k and, gzip out, by the copy pass of
-    //                     window k + 1 (the raw piece: k's ragged tail).  This thread reserves and refills it for window k + 2
-    //                     behind S(k + 2) — the copy pass of k + 1 has ended — and behind the writer's release of window k,
-    //                     given when the last copy home or the last batch of the encoder that reads the slot has been waited for.
+    //   output slots, two slot k & 1 is read by the writer for window k and, gzip out, by the copy pass of window k + 1 (the
+    //                     raw piece: k's ragged tail).  This thread reserves and refills it for window k + 2 behind S(k + 2) —
+    //                     the copy pass of k + 1 has ended — and behind the writer's release of window k (host/way_out.h).
     //   control words     four sets in turn; a set is zeroed for window k + 4 behind the release of window k + 1.
     //
     // BGZF in.  The windows are the cuts of bgzf_windows.h: window k's new bytes are text[t0, t1) of cut k, at most
@@ -1287,7 +1241,7 @@ struct SeqRun {
     //   text slots        the inflate of window k writes slot k & 1 from offset W on — on the engine's stream, behind the copy
     //                     pass of k - 2 (its last reader) and behind the carry kernel of k - 1, which wrote in front of W.
     //   status word       one for the run, zeroed by inflate_window_open; only ever raised (atomicMax).
-    struct WinPost { // a window handed to the writer
+    struct WinPost { // a window handed to the writer (when its output slot is let go: host/way_out.h)
         int slot;
         u64 len; // bytes in the output slot: the tail of the window before (gzip out) and this window's output
         bool last;
@@ -1301,60 +1255,23 @@ struct SeqRun {
     std::string w_msg;
     Streams lanes;                // the mover's copy streams: made by the first window, kept for the run
     Events cdone;                 // behind a window's copy pass and its words' way home, per output slot
-    std::vector<long> gz_batch_win; // per batch of the encoder: the window whose output slot it is the last to read, or -1
-    size_t gz_sent = 0, gz_got = 0;
-    std::vector<u64> gz_eof;
 
     void writer_fail(int code, const char *msg)
     {
         if (w_rc == YACRD_OK) w_rc = code, w_msg = msg;
         win_stop = 1;
     }
-    // bring_home on the writer thread: its failures are kept, not spoken
-    bool writer_home(const char *base, u64 len)
+    // the way out on the writer thread: its failures are kept, not spoken
+    bool went(yout::Result r)
     {
-        HomeLink dma{base, side[0], {wev[0], wev[1]}, &win_stop};
-        const int rc = yseg::pump(len, kOutPiece, S.pin.as<char>(), dma, sink, [&](auto put) {
-            const double tp = now_ms();
-            put();
-            put_ms += now_ms() - tp;
-        });
-        if (rc == yseg::kLinkFailed) writer_fail(YACRD_ENODEV, "sequence editor: a HIP call failed on the way home");
-        if (rc == yseg::kSinkFailed) writer_fail(YACRD_EINVAL, "Error during writing of the output file");
-        return rc == yseg::kPumped;
-    }
-    bool writer_encode(const unsigned char *text, u64 len, bool last, long releases)
-    {
-        const size_t b = gz_sent;
-        if (!gev.add(2) || !gdone.add(1, hipEventDisableTiming)) return writer_fail(YACRD_ENODEV, "sequence editor: a HIP event could not be created"), false;
-        volatile u64 *w = h_ctl + 4 + 2 * (b & 1);
-        w[0] = w[1] = 0;
-        if (gzip_device_encode(e, gz, side[1], text, len, last, (int)(b & 1), gev[2 * b], gev[2 * b + 1], w, w + 1) != YACRD_OK ||
-            hipEventRecord(gdone[b], side[1]) != hipSuccess)
-            return writer_fail(YACRD_ENODEV, "sequence editor: a HIP call failed in the encoder"), false;
-        gz_batch_win.push_back(releases), gz_eof.push_back(last ? ydf::kEofBytes : 0u);
-        gz_members += (len + ydf::kBlock - 1) / ydf::kBlock;
-        gz_sent = b + 1;
-        return true;
-    }
-    bool writer_fetch()
-    {
-        const size_t b = gz_got;
-        if (hipEventSynchronize(gdone[b]) != hipSuccess) return writer_fail(YACRD_ENODEV, "sequence editor: a HIP call failed in the encoder"), false;
-        volatile u64 *w = h_ctl + 4 + 2 * (b & 1);
-        const u64 bytes = w[0] + gz_eof[b];
-        if (bytes > gz.max_blocks * ydf::kSlot + ydf::kEofBytes)
-            return writer_fail(YACRD_EINTERNAL, "device deflate: more bytes than the members' slots hold"), false;
-        gz_stored = w[1];
-        if (gz_batch_win[b] >= 0) win_released.store((size_t)gz_batch_win[b] + 1, std::memory_order_release); // (the encoder has read the slot)
-        gz_got = b + 1;
-        return writer_home(reinterpret_cast<const char *>(gz.out[b & 1]), bytes);
+        const char *msg;
+        if (const int code = out_says(r, &msg)) writer_fail(code, msg);
+        return r == yout::kWent;
     }
     // the writer thread: one, in order
     void window_writer()
     {
         if (hipSetDevice(e->device) != hipSuccess) writer_fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
-        const u64 per = job.gzip ? gz.max_blocks * ydf::kBlock : 0;
         for (size_t k = 0; !win_stop.load(); k++) {
             while (win_n_posted.load(std::memory_order_acquire) <= k && !win_no_more.load() && !win_stop.load()) {
                 struct timespec ts = {0, 50000};
@@ -1378,28 +1295,18 @@ struct SeqRun {
             const double t0 = now_ms();
             const char *base = S.wout[p.slot].as<char>();
             if (!job.gzip) {
-                if (!writer_home(base, p.len)) break;
+                if (!went(out.home(base, p.len))) break;
                 win_released.store(k + 1, std::memory_order_release);
             } else {
                 // every whole block of the slot (the last window: its tail too, and the EOF member), batch by batch; the batch
-                // before comes home while this one is encoded — the last batch of a window while the next window's first is
+                // before comes home while this one is encoded — the last batch of a window while the next window's first is.
+                // The slot is released by the fetch of its last batch; a window that encodes nothing, at once
                 const u64 whole = p.last ? p.len : p.len / ydf::kBlock * ydf::kBlock;
-                const size_t nb = (size_t)((whole + per - 1) / per) + (p.last && !whole ? 1u : 0u);
-                bool ok = true;
-                for (size_t b = 0; b < nb && ok; b++) {
-                    const u64 from = (u64)b * per, len = std::min(per, whole - from);
-                    ok = writer_encode(reinterpret_cast<const unsigned char *>(base) + from, len, p.last && b + 1 == nb, b + 1 == nb ? (long)k : -1);
-                    while (ok && gz_got + 1 < gz_sent) ok = writer_fetch();
-                }
-                if (!nb || p.last)
-                    while (ok && gz_got < gz_sent) ok = writer_fetch();
-                if (!ok) break;
-                if (!nb) win_released.store(k + 1, std::memory_order_release); // (nothing of this slot is the encoder's to read)
+                if (!went(out.text(reinterpret_cast<const unsigned char *>(base), whole, p.last, (long)k)) || (p.last && !went(out.drain()))) break;
             }
             out_busy_ms += now_ms() - t0;
         }
-        (void)hipStreamSynchronize(side[0]);
-        if (job.gzip) (void)hipStreamSynchronize(side[1]);
+        od.quiet();
     }
 
     struct WinAt { // window k as its kernels see it: bytes [lo, hi) of text slot ts, tiles [t_lo, t_hi), its control words
@@ -1639,11 +1546,10 @@ struct SeqRun {
             comp_fresh = iw.fresh;
         }
         if (!cdone.add(2, hipEventDisableTiming)) HIP_TRY(why_not_added());
-        if (job.gzip) {
-            if (const int rcg = gzip_device_open(e, std::min<u64>(kGzBatchBlocks, 2 * W / ydf::kBlock + 2), &gz)) return rcg;
-            gz_hold.e = e;
-            HIP_TRY(hipStreamSynchronize(e->stream)); // (gzip_device_open's memset)
-        }
+        if (job.gzip)
+            if (const int rcg = od.open(e, std::min<u64>(kGzBatchBlocks, 2 * W / ydf::kBlock + 2), true)) return rcg;
+        od.stop = &win_stop, od.slots_below = &win_released;
+        out.bind(S.pin.as<char>(), h_ctl + 4);
         std::thread wt([this] { window_writer(); });
         int rc = job.fasta ? windows_loop<yk::Fasta>() : windows_loop<yk::Fastq>();
         if (rc != YACRD_OK) win_stop = 1;
@@ -1652,11 +1558,10 @@ struct SeqRun {
         (void)hipStreamSynchronize(e->stream);
         if (rc == YACRD_OK && w_rc != YACRD_OK) rc = fail(w_rc, w_msg);
         if (rc != YACRD_OK) return rc;
-        if ((job.gzip ? gz_got != gz_sent : sink.at != total)) return fail(YACRD_EINTERNAL, "sequence editor: fewer bytes written than counted");
-        for (size_t b = 0; b < gz_sent; b++) gz_kernel_ms += ev_ms(gev[2 * b], gev[2 * b + 1]);
+        if ((job.gzip ? out.got != out.sent : sink.at != total)) return fail(YACRD_EINTERNAL, "sequence editor: fewer bytes written than counted");
         e->seq_windows[0] = win_count, e->seq_windows[1] = win_max_carry;
         e->seq_windows[2] = S.wtext[0].cap + S.wtext[1].cap + (job.bgzf ? inflate_window_held(e) : 0), e->seq_windows[3] = S.wout[0].cap + S.wout[1].cap;
-        fill_gzip_stats(job.gzip_stats, total, sink.at, gz_members, gz_stored, gz_kernel_ms, out_busy_ms, put_ms);
+        fill_gzip_stats(job.gzip_stats, total, sink.at, out.members, out.stored, od.kernel_ms(), out_busy_ms, out.put_ms);
         if (job.gunzip_stats) { // as the whole-text run fills them (deliver), summed over the windows' landings and launches
             for (size_t i = 0; i + 1 < n_iev; i += 2) inf_kernel_ms += ev_ms(iev[i], iev[i + 1]);
             yacrd_gunzip_stats &u = *job.gunzip_stats; // (walk_ms: the caller's)
@@ -1676,19 +1581,19 @@ struct SeqRun {
     int deliver()
     {
         const double t0 = now_ms();
-        int rc = YACRD_OK;
-        if (job.gzip) rc = deflate_home();
-        else {
-            if (sink.fd < 0 && !sink.mem) { // the memory form: the size is known now
-                sink.mem = (char *)std::malloc((size_t)total + 1);
-                if (!sink.mem) return fail(YACRD_ENOMEM, "host allocation failed");
-            }
-            rc = bring_home(S.out.as<char>(), total);
-            if (rc == YACRD_OK && sink.at != total) rc = fail(YACRD_EINTERNAL, "sequence editor: fewer bytes written than counted");
+        if (!job.gzip && sink.fd < 0 && !sink.mem) { // the memory form: the size is known now
+            sink.mem = (char *)std::malloc((size_t)total + 1);
+            if (!sink.mem) return fail(YACRD_ENOMEM, "host allocation failed");
         }
+        // gzip out: batch b comes home while b + 1 is encoded
+        if (job.gzip) out.text(S.out.as<unsigned char>(), total, true, yout::kNoTag);
+        const char *msg;
+        int rc = out_says(job.gzip ? out.drain() : out.home(S.out.as<char>(), total), &msg);
+        if (rc) rc = fail(rc, msg);
+        else if (!job.gzip && sink.at != total) rc = fail(YACRD_EINTERNAL, "sequence editor: fewer bytes written than counted");
         out_busy_ms = now_ms() - t0;
         if (rc) return rc;
-        fill_gzip_stats(job.gzip_stats, total, sink.at, gz_members, gz_stored, gz_kernel_ms, out_busy_ms, put_ms);
+        fill_gzip_stats(job.gzip_stats, total, sink.at, out.members, out.stored, od.kernel_ms(), out_busy_ms, out.put_ms);
         if (job.gunzip_stats) {
             yacrd_gunzip_stats &u = *job.gunzip_stats; // (walk_ms: the caller's)
             u.in_bytes = job.bgzf_bytes, u.out_bytes = n, u.n_members = job.members->size();
@@ -1722,7 +1627,7 @@ int run_seq_edit(yacrd_engine *e, const SeqJob &job, const TextSource &src, u64 
     bool windows = may_window && n > W && (sw != 0 || kSeqWindowsWhenFits);
     auto finish = [&](SeqRun &r, int rc) {
         (void)hipStreamSynchronize(e->stream); // (whatever failed: nothing of this call is in flight when its events go)
-        for (hipStream_t s : r.side.v) (void)hipStreamSynchronize(s);
+        r.od.quiet();
         (void)hipGetLastError();
         return rc;
     };

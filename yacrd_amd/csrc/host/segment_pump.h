@@ -1,8 +1,9 @@
 // segment_pump.h — a text of `total` bytes leaves its source in segments through the two halves of one buffer: the copy of
 // segment i + 1 is started before segment i is handed to the sink, so the source's link and the sink work side by side.
-// Plain C++, no device call: gpu_report_write.hip and gpu_edit.hip plug a DMA into `Link`, tools/segment_pump_check.cc a memcpy
-// (the stand-alone program that runs this arithmetic under -fsanitize=address,undefined).  `Sink` is where every text path's
-// bytes end up (gpu_deflate.hip's writer puts into one without the pump).
+// Plain C++, no device call: gpu_report_write.hip, gpu_inflate.hip and — for every editor, through way_out.h — gpu_out.h plug a
+// DMA into `Link` (gpu_text.h: HomeLink), tools/segment_pump_check.cc a memcpy (the stand-alone program that runs this
+// arithmetic under -fsanitize=address,undefined).  `Sink` is where every text path's bytes end up (gpu_deflate.hip's writer
+// puts into one without the pump).
 //
 //   Link::start(i, dst, at, len)   begin copying text[at, at + len) to dst; false: the link failed
 //   Link::wait(i)                  the copy of segment i has landed; false: the link failed
