@@ -470,6 +470,35 @@ typedef struct {
 int yacrd_engine_gunzip_mem(yacrd_engine *e, const char *bgzf, uint64_t n_bytes,
                             char **out, uint64_t *out_bytes, yacrd_gunzip_stats *st /* may be NULL */);
 
+/* ---- plain gzip inflated on the GPU (csrc/gpu_gunzip_stream.hip, csrc/inflate_stream.h, csrc/gzip_walk.h) ------------
+ * ONE plain gzip member — what `gzip` and `minimap2 | gzip` write — in host memory -> its text.  yacrd_engine_gunzip_mem
+ * and every _bgzf_ form keep refusing it; this is a route of its own.  The host walks the header (`1f 8b 08 FLG`, reserved
+ * FLG bits zero; FEXTRA, FNAME, FCOMMENT and FHCRC skipped), the member crosses the link compressed, and the deflate stream
+ * is decoded in parallel in five steps, each its own launches: block starts are FOUND per chunk of compressed
+ * bytes (dynamic, non-final headers, judged in registers), the spans between them are SIZED without storing a byte and
+ * chained from bit 0 by the host (a guess the chain does not confirm is dropped; a block start the chain proves and no span
+ * begins on is sized in one more round), decoded again into 16-bit SYMBOLS where a byte from in front of its span is a
+ * marker, the last 32 768 symbols of every span are resolved in order (WINDOWS), and the BYTES go out position-parallel with
+ * the CRC-32 summed on the way.  ISIZE is checked before a byte is stored, the CRC-32 behind the last one.  A wrong guess
+ * costs time, never bytes.  YACRD_EFALLBACK, with nothing returned and the engine usable: not one gzip member (a header
+ * cut short, reserved bits, fewer than header + 8 bytes); concatenated members, trailing bytes or a BGZF stream ("bytes left
+ * over": the final block must end in the payload's last byte); yacrd_engine_gunzip_mem's list of payload faults; more than
+ * 64 wrong block starts; a span (the stretch one wavefront decodes: an all-stored or all-fixed stream is one) of more than 32 MiB compressed or 64 MiB of text; a payload beyond 2^40 bytes;
+ * text + 2 x text + compressed bytes beyond the device's free memory.  Never more lenient than zlib.  The caller then takes
+ * libyacrd_host's reader, which owns the messages.  `out`: yacrd_edit_text_free.  The buffers stay with the engine:
+ * yacrd_engine_trim.  Additive: found by the symbol. */
+typedef struct {
+    uint64_t in_bytes, out_bytes, n_chunks;
+    uint64_t n_spans;        /* true spans: the pieces decoded in parallel */
+    uint64_t n_false_starts; /* finds the chain stepped over */
+    uint64_t rounds;         /* launches of the sizing step: 1, and one per proven start that had no span */
+    uint64_t n_blocks;
+    float find_ms, size_ms, symbols_ms, windows_ms, bytes_ms; /* device events */
+    float h2d_ms, d2h_ms;
+} yacrd_gunzip_stream_stats;
+int yacrd_engine_gunzip_stream_mem(yacrd_engine *e, const char *gz, uint64_t n_bytes,
+                                   char **out, uint64_t *out_bytes, yacrd_gunzip_stream_stats *st /* may be NULL */);
+
 /* yacrd_engine_ingest_overlaps_mem and yacrd_engine_ingest_report_mem over a BGZF stream as it lies in host memory (read
  * or mapped: no host inflate).  The host walks the members, the COMPRESSED bytes go up in the mover's 4 MiB chunks, and for
  * every 128 MiB of them that has landed the members that have become complete are decoded by one launch on the engine's
@@ -736,6 +765,28 @@ int yacrd_engine_edit_fasta_bgzf_mem(yacrd_engine *e, int op, const char *bgzf, 
 int yacrd_engine_edit_fasta_bgzf_file(yacrd_engine *e, int op, const char *bgzf, uint64_t n_bytes, const yacrd_report_table *t,
                                       const char *out_path, yacrd_seq_edit_stats *st /* may be NULL */,
                                       yacrd_gzip_stats *gs /* may be NULL */, yacrd_gunzip_stats *us /* may be NULL */);
+/* The plain-gzip forms, for FASTQ and FASTA: the _bgzf_ forms' arguments, with `gz`, n_bytes ONE plain gzip member in host
+ * memory and yacrd_gunzip_stream_stats in place of yacrd_gunzip_stats.  The member goes up and is sized and chained on the
+ * device (yacrd_engine_gunzip_stream_mem's first steps) before anything is made beside out_path; its symbols, windows and
+ * bytes go into the editor's text buffer, the decoder's status and the CRC-32 are read before anything is sized from the
+ * text, and from there the run is the gzip form's: the output is byte for byte that of the gzip form given the inflated
+ * text.  The whole-text run only: a text that would run in windows (it finds no room whole, or yacrd_debug_seq_window names
+ * a window it outgrows) is YACRD_EFALLBACK, as are the gzip form's causes and yacrd_engine_gunzip_stream_mem's.  Nothing is
+ * written and nothing is left beside out_path, and a call that fails frees the compressed bytes and the symbol scratch it
+ * took at once: the host route that follows finds the device memory it would have found without the attempt.  ss->d2h_ms
+ * is 0.  Additive: found by the symbol. */
+int yacrd_engine_edit_fastq_gz_mem(yacrd_engine *e, int op, const char *gz, uint64_t n_bytes, const yacrd_report_table *t,
+                                   char **out, uint64_t *out_bytes, yacrd_seq_edit_stats *st /* may be NULL */,
+                                   yacrd_gzip_stats *gs /* may be NULL */, yacrd_gunzip_stream_stats *ss /* may be NULL */);
+int yacrd_engine_edit_fastq_gz_file(yacrd_engine *e, int op, const char *gz, uint64_t n_bytes, const yacrd_report_table *t,
+                                    const char *out_path, yacrd_seq_edit_stats *st /* may be NULL */,
+                                    yacrd_gzip_stats *gs /* may be NULL */, yacrd_gunzip_stream_stats *ss /* may be NULL */);
+int yacrd_engine_edit_fasta_gz_mem(yacrd_engine *e, int op, const char *gz, uint64_t n_bytes, const yacrd_report_table *t,
+                                   char **out, uint64_t *out_bytes, yacrd_seq_edit_stats *st /* may be NULL */,
+                                   yacrd_gzip_stats *gs /* may be NULL */, yacrd_gunzip_stream_stats *ss /* may be NULL */);
+int yacrd_engine_edit_fasta_gz_file(yacrd_engine *e, int op, const char *gz, uint64_t n_bytes, const yacrd_report_table *t,
+                                    const char *out_path, yacrd_seq_edit_stats *st /* may be NULL */,
+                                    yacrd_gzip_stats *gs /* may be NULL */, yacrd_gunzip_stream_stats *ss /* may be NULL */);
 
 /* Copy the last device result to host (allocates like yacrd_engine_run). */
 int yacrd_engine_fetch(yacrd_engine *e, yacrd_result *out);

@@ -156,6 +156,11 @@ int yacrd_debug_edit_window(yacrd_engine *e, uint64_t window_bytes);
  * decoder's compressed slot and member slice; from the mirror: 0), [3] device bytes of its two output slots.  A failed edit in
  * windows leaves [0] = 0. */
 void yacrd_debug_edit_windows(const yacrd_engine *e, uint64_t out[4]);
+/* the plain-gzip decoder's chunk (csrc/gpu_gunzip_stream.hip): block starts are looked for once per `bytes` of
+ * compressed payload.  0: YACRD_GUNZIP_CHUNK=<bytes> from the environment (read at every call; values under 1 024 count as
+ * 1 024), else the default, 32 768; any other value is at least 1 024 (YACRD_EINVAL below it).  The text does not depend
+ * on it; the spans, and so the counters, do.  Stays with the engine until set again.  Tests and A/B runs only. */
+int yacrd_debug_gunzip_chunk(yacrd_engine *e, uint32_t bytes);
 /* YACRD_TEST_REPORT_SEGMENT=<bytes> (environment, tests; read at every call): the size of the segments in which
  * yacrd_engine_write_report[_mem] brings the formatted text home, instead of 64 MiB (csrc/gpu_report_write.hip: kReportSegment;
  * 1 .. 2^30).  The bytes written do not depend on it: tests/test_gpu_report_write.py cuts lines at hundreds of borders. */

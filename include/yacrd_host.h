@@ -157,6 +157,14 @@ void yacrd_bytes_free(char *p);
  * non-zero, with nothing returned, for a stream that is not BGZF or holds a member the decoder does not take (the message
  * names the member and the cause).  Stricter than zlib in places, never more lenient.  `out`: yacrd_bytes_free. */
 int yacrd_bgzf_decode_host(const char *data, uint64_t n, char **out, uint64_t *out_bytes);
+/* The device decoder of ONE plain gzip member (csrc/gzip_walk.h: the framing; csrc/inflate_stream.h: block starts found per
+ * chunk of `chunk` compressed bytes (0: the default, 32 768; at least 1 024), spans sized and chained from bit 0, symbols,
+ * windows, bytes) run by one host thread: the text, with the trailer's CRC-32 and ISIZE checked.  counters (may be NULL):
+ * n_chunks, n_spans (true spans), n_false_starts, rounds, n_blocks, out_bytes — what yacrd_engine_gunzip_stream_mem
+ * reports for the same chunk.  Non-zero, with nothing returned, for what is not one gzip member ("not a gzip member") or
+ * a payload the decoder does not take ("gzip stream not taken: <cause>": concatenated members, trailing bytes and BGZF are
+ * "bytes left over").  Never more lenient than zlib.  `out`: yacrd_bytes_free. */
+int yacrd_gzip_stream_decode_host(const char *data, uint64_t n, uint32_t chunk, char **out, uint64_t *out_bytes, uint64_t counters[6]);
 /* The planner of the segment-wise device inflate (csrc/bgzf_plan.h) over a BGZF stream and a schedule: landed[k] is the
  * number of compressed bytes in HBM at call k (it never falls).  chunk / seg_chunks: the text segments' unit and length in
  * units; 0 = the mover's (4 MiB, 32).  members_out: in_off, csize, isize, out_off per member of the walk; steps_out, eight

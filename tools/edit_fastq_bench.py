@@ -94,7 +94,7 @@ def run(binary, op, src, out, **env):
         wall = time.perf_counter() - t0
         assert p.returncode == 0, p.stderr
         stages = dict(re.findall(r"^\[timing\] (\S+) ([0-9.]+) s$", p.stderr, re.M))
-        info = [l for l in p.stderr.splitlines() if l.startswith(editor_line) or l.startswith("[info] device deflate:") or l.startswith("[info] device inflate:")]
+        info = [l for l in p.stderr.splitlines() if l.startswith(editor_line) or l.startswith("[info] device deflate:") or l.startswith("[info] device inflate:") or l.startswith("[info] device gunzip:")]
         row = {"edit_s": float(stages["edit"]), "wall_s": round(wall, 3), "info": info}
         if k:
             rows.append(row)

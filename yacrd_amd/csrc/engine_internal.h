@@ -375,7 +375,7 @@ struct yacrd_engine {
     // what the text paths keep between calls (their own types, whose members own their device and pinned buffers, events and
     // streams; nothing in them outlives a call except capacity), made on first use by yke::scratch_of; yacrd_engine_trim and
     // yacrd_engine_destroy delete them (drop_scratch), the next use after a trim makes a fresh one
-    enum Slot { kPaf = 0, kEdit, kGzip, kReport, kReportWrite, kSeqEdit, kInflate, kSlots };
+    enum Slot { kPaf = 0, kEdit, kGzip, kReport, kReportWrite, kSeqEdit, kInflate, kGunzipStream, kSlots };
     struct {
         void *p = nullptr;
         void (*destroy)(void *) = nullptr;
@@ -396,6 +396,8 @@ struct yacrd_engine {
     // batches of this many reads and more take the long-batch forms of the plan and the follow-on step (engine.hip:
     // split_min_reads is the default; yacrd_debug_long_min_reads sets it, tests)
     uint64_t long_min_reads = 0;
+    // the plain-gzip decoder's chunk (gpu_gunzip_stream.hip): what yacrd_debug_gunzip_chunk set; 0: YACRD_GUNZIP_CHUNK, or the default
+    uint32_t gunzip_chunk = 0;
     bool gzip_busy = false; // a yacrd_gzip_writer or an edit to gzip holds the kGzip slot: trim leaves it alone
 };
 
@@ -525,4 +527,24 @@ struct BgzfMove {
 };
 int move_bgzf_text(yacrd_engine *e, const char *comp_src, u64 comp_bytes, const std::vector<yif::InfMember> &members, unsigned char *d_text,
                    u64 text_bytes, int n_threads, const std::function<void(u64, u64, u64)> &on_text_segment, BgzfMove &bm, int *rc);
+// ONE plain gzip member in host memory -> its text in HBM (gpu_gunzip_stream.hip; inflate_stream.h: the five steps; used by
+// gpu_seq_edit.hip's _gz_ forms).  Mirrors inflate_device_open / _run.  open walks the header (gzip_walk.h), moves the
+// compressed bytes up through move_text, FINDs block starts per chunk, SIZEs the spans with the chain's repair rounds, checks
+// ISIZE, and takes the symbol scratch (2 bytes per text byte): behind it s->text_bytes is the text's exact size and the
+// chain is proven, before a byte is stored.  `text_copies`: how many buffers of the text's size the caller will take beside the
+// symbols (the primitive: its text; an editor: its text and an output that may be as long) and `held` the device bytes it already
+// holds for them: where (text_copies + 2) x text does not fit beside the compressed bytes, YACRD_EFALLBACK, with nothing reserved.
+// stream_inflate_release frees the compressed bytes and the symbols at once (a caller that hands the input on to the host route).
+// run enqueues SYMBOLS, WINDOWS and BYTES on the engine's stream into d_text (16-byte aligned, text_bytes of it are written),
+// brings the status word and the CRC home and WAITS: YACRD_OK means the text is the member's, checked against the trailer;
+// the status is read before the caller sizes anything from the text.  YACRD_EFALLBACK: not one gzip member, or a payload the
+// decoder does not take (the message names the cause).  Nothing is held between calls but capacity (slot kGunzipStream).
+struct StreamInflate {
+    u64 text_bytes = 0, n_true = 0;
+    u32 crc = 0;
+    yacrd_gunzip_stream_stats stats = {};
+};
+int stream_inflate_open(yacrd_engine *e, const char *gz, u64 n_bytes, int n_threads, double text_copies, double held, StreamInflate *s);
+void stream_inflate_release(yacrd_engine *e);
+int stream_inflate_run(yacrd_engine *e, StreamInflate &s, unsigned char *d_text);
 } // namespace yke

@@ -794,6 +794,9 @@ struct SeqJob {
     u64 bgzf_bytes = 0;
     const std::vector<yif::InfMember> *members = nullptr;
     yacrd_gunzip_stats *gunzip_stats = nullptr;
+    // plain gzip in (the _gz_ forms): the member as stream_inflate_open left it in HBM, sized and chained; the run's `n` is its text
+    StreamInflate *stream = nullptr;
+    yacrd_gunzip_stream_stats *stream_stats = nullptr;
 };
 
 // One edit on its way through the device: built once per call (run_seq_edit), its phases in the order they run.
@@ -890,7 +893,7 @@ struct SeqRun {
             if (G >= 0x7FFFFFFFull) return fail(YACRD_EFALLBACK, "more regions than the device table holds");
             if (G && !t.bad_regions) return fail(YACRD_EINVAL, "the report table is incomplete");
         }
-        if (n && !job.bgzf) { // (BGZF in: the last byte comes back from the device behind the inflate, inflate_text)
+        if (n && !job.bgzf && !job.stream) { // (BGZF / gzip in: the last byte comes back from the device behind the inflate, inflate_text / stream_text)
             char last = 0;
             if (!src.fetch(&last, 1, n - 1)) return fail(YACRD_EINVAL, "read error in the sequence file");
             if (last != '\n') return fail(YACRD_EFALLBACK, "the text's last line has no newline: the host loop's case");
@@ -1008,6 +1011,26 @@ struct SeqRun {
         return YACRD_OK;
     }
 
+    // plain gzip in: the member lies in HBM, sized and chained (stream_inflate_open); its symbols, windows and bytes into the text
+    // buffer, the decoder's status and CRC checked behind them (stream_inflate_run waits), the text's last byte; then the lines
+    int stream_text()
+    {
+        HIP_TRY(hipMemsetAsync(S.text.as<char>() + n, 0, 64, e->stream));
+        if (const int rc = stream_inflate_run(e, *job.stream, S.text.as<unsigned char>())) return rc;
+        if (n) {
+            HIP_TRY(hipMemcpyAsync((void *)(h_ctl + 3), S.text.as<char>() + (n - 1), 1, hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            if ((char)(h_ctl[3] & 255u) != '\n') return fail(YACRD_EFALLBACK, "the text's last line has no newline: the host loop's case");
+        }
+        ga.avail = n, ga.tile0 = 0;
+        bool ok = ev_open();
+        if (n_tiles) hipLaunchKernelGGL(yk::sq_lines_kernel, dim3((u32)n_tiles), dim3(yk::kGpT), 0, e->stream, ga);
+        ok = ok && ev_close();
+        t_text = now_ms();
+        if (!ok) return fail(YACRD_ENODEV, "sequence editor: a HIP call failed");
+        return YACRD_OK;
+    }
+
     // the text into HBM; the lines of every segment counted as it lands
     int move_text_in()
     {
@@ -1031,7 +1054,7 @@ struct SeqRun {
     // the text into HBM (moved, or inflated there) with its tiles' lines counted; then the scan of the tiles' counts
     int move_and_count()
     {
-        if (const int rc = job.bgzf ? inflate_text() : move_text_in()) return rc;
+        if (const int rc = job.bgzf ? inflate_text() : job.stream ? stream_text() : move_text_in()) return rc;
         ga.avail = n;
         bool ok = ev_open();
         if (const int rc = scan_u32_to_u64(e, S.tile_nl.as<u32>(), n_tiles, S.tile_l0.as<u64>(), S.part)) return rc;
@@ -1599,6 +1622,7 @@ struct SeqRun {
             u.in_bytes = job.bgzf_bytes, u.out_bytes = n, u.n_members = job.members->size();
             u.h2d_ms = inf_h2d_ms, u.kernel_ms = inf_kernel_ms, u.d2h_ms = 0.f;
         }
+        if (job.stream_stats) *job.stream_stats = job.stream->stats; // (d2h_ms 0: the text stays in HBM)
         if (stats) {
             stats->text_bytes = n, stats->out_bytes = total, stats->n_records = n_rec, stats->n_out_records = n_pieces;
             stats->text_ms = (float)(t_text - t_table), stats->table_ms = (float)(t_table - t_start);
@@ -1625,6 +1649,8 @@ int run_seq_edit(yacrd_engine *e, const SeqJob &job, const TextSource &src, u64 
     u64 W = sw == 0 || sw == UINT64_MAX ? (u64)(kTextChunk * kTextSeg) : (sw + yk::kGpTile - 1) / yk::kGpTile * yk::kGpTile;
     if (job.bgzf) W = std::max<u64>(W, (ybw::kMinWindow + yk::kGpTile - 1) / yk::kGpTile * yk::kGpTile);
     bool windows = may_window && n > W && (sw != 0 || kSeqWindowsWhenFits);
+    // plain gzip in: the whole-text run only (its spans are cut where blocks begin, not where a window would end)
+    if (job.stream && windows) return fail(YACRD_EFALLBACK, "a gzip text that would run in windows: the host reader streams it");
     auto finish = [&](SeqRun &r, int rc) {
         (void)hipStreamSynchronize(e->stream); // (whatever failed: nothing of this call is in flight when its events go)
         r.od.quiet();
@@ -1641,7 +1667,7 @@ int run_seq_edit(yacrd_engine *e, const SeqJob &job, const TextSource &src, u64 
         if (rc == YACRD_OK) rc = r.deliver();
         rc = finish(r, rc);
         // no room: nothing has left the device yet, and what the run holds goes before the windows take their ring
-        if (!(rc == YACRD_EFALLBACK && r.room_failed && may_window && n > W)) return rc;
+        if (!(rc == YACRD_EFALLBACK && r.room_failed && may_window && n > W) || job.stream) return rc;
         windows = true;
         if (job.fasta) // the whole text's tables, 32 bytes a line: a window sizes its own
             for (DevBuf *b : {&S->line_end, &S->ln_head, &S->ln_bases, &S->ln_rec, &S->base_before, &S->rec_line, &S->rec_width}) b->release();
@@ -1683,6 +1709,9 @@ struct SeqCall {
     yacrd_seq_edit_stats *st;
     yacrd_gzip_stats *gs;
     yacrd_gunzip_stats *us;
+    yacrd_gunzip_stream_stats *ss = nullptr;
+    StreamInflate stream;
+    yacrd_engine *gz_engine = nullptr; // plain gzip in: the engine whose stream scratch this call filled
     SeqJob job;
     std::vector<yif::InfMember> members;
     TextSource src;
@@ -1693,14 +1722,30 @@ struct SeqCall {
     {
         if (gs) std::memset(gs, 0, sizeof(*gs));
         if (us) std::memset(us, 0, sizeof(*us));
+        if (ss) std::memset(ss, 0, sizeof(*ss));
         if (const int rc = seq_edit_args(fasta, e, op, t, st)) return rc;
         job.op = op, job.table = t, job.fasta = fasta, job.gzip = gzip, job.gzip_stats = gs;
         return YACRD_OK;
     }
     // the text in memory.  BGZF in: `text`, `n` are the compressed file; the walk — before a file is made beside an out_path:
     // what is not BGZF leaves nothing — fills `members` and the job's BGZF fields, and `n` becomes the text's bytes
-    int text_in(const char *text, uint64_t &n, bool bgzf)
+    // Plain gzip in (`gz`, the _gz_ forms): the member goes up and is sized and chained on the device here (stream_inflate_open),
+    // also before a file is made: what is not one gzip member, or a payload not taken as far as sizing tells, leaves nothing
+    int text_in(yacrd_engine *e, const char *text, uint64_t &n, bool bgzf, bool gz)
     {
+        if (gz) {
+            DeviceGuard guard(e->device);
+            SeqEditScratch *S = scratch_of<SeqEditScratch>(e);
+            if (!S) return fail(YACRD_ENOMEM, "host allocation failed");
+            gz_engine = e; // (from here on a call that fails gives the compressed bytes and the symbols back: leave)
+            // beside the symbols: the text itself and an output that may be as long (the run's own plan() asks again, with the tables)
+            const int rc = stream_inflate_open(e, text, n, job.n_threads, 2.0, (double)S->text.cap + (double)S->out.cap, &stream);
+            (void)hipStreamSynchronize(e->stream);
+            (void)hipGetLastError();
+            if (rc) return rc;
+            job.stream = &stream, job.stream_stats = ss;
+            text = "", n = stream.text_bytes;
+        }
         if (bgzf) {
             const double t0 = now_ms();
             u64 total = 0;
@@ -1719,6 +1764,9 @@ struct SeqCall {
         if (st) std::memset(st, 0, sizeof(*st));
         if (gs) std::memset(gs, 0, sizeof(*gs));
         if (us) std::memset(us, 0, sizeof(*us));
+        if (ss) std::memset(ss, 0, sizeof(*ss));
+        // plain gzip in: the caller takes the host route next, which wants the memory the compressed bytes and the symbols hold
+        if (gz_engine) stream_inflate_release(gz_engine);
         if (sink.fd < 0) std::free(sink.mem), sink.mem = nullptr;
         return rc;
     }
@@ -1760,13 +1808,14 @@ int edit_seq_file(bool fasta, yacrd_engine *e, int op, const char *in_path, cons
 }
 
 int edit_seq_mem(bool fasta, yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, char **out, uint64_t *out_bytes,
-                 yacrd_seq_edit_stats *st, bool gzip = false, yacrd_gzip_stats *gs = nullptr, bool bgzf = false, yacrd_gunzip_stats *us = nullptr)
+                 yacrd_seq_edit_stats *st, bool gzip = false, yacrd_gzip_stats *gs = nullptr, bool bgzf = false, yacrd_gunzip_stats *us = nullptr,
+                 bool gz = false, yacrd_gunzip_stream_stats *ss = nullptr)
 {
-    SeqCall c{st, gs, us};
+    SeqCall c{st, gs, us, ss};
     if (const int rca = c.enter(fasta, e, op, t, gzip)) return rca;
     if ((!text && n) || !out || !out_bytes) return fail(YACRD_EINVAL, "null argument");
     *out = nullptr, *out_bytes = 0;
-    if (const int rcw = c.text_in(text, n, bgzf)) return rcw;
+    if (const int rcw = c.text_in(e, text, n, bgzf, gz)) return gz ? c.leave(rcw) : rcw;
     if (gzip) { // (plain: the run sizes the memory when it knows the output's bytes)
         c.sink.cap = (size_t)(n / 3 + 4096); // (the sink grows when the members need more)
         c.sink.mem = (char *)std::malloc((size_t)c.sink.cap);
@@ -1778,12 +1827,13 @@ int edit_seq_mem(bool fasta, yacrd_engine *e, int op, const char *text, uint64_t
 }
 
 int edit_seq_gzip_file(bool fasta, yacrd_engine *e, int op, const char *text, uint64_t n, const yacrd_report_table *t, const char *out_path,
-                       yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs, bool bgzf = false, yacrd_gunzip_stats *us = nullptr)
+                       yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs, bool bgzf = false, yacrd_gunzip_stats *us = nullptr, bool gz = false,
+                       yacrd_gunzip_stream_stats *ss = nullptr)
 {
-    SeqCall c{st, gs, us};
+    SeqCall c{st, gs, us, ss};
     if (const int rca = c.enter(fasta, e, op, t, true)) return rca;
     if ((!text && n) || !out_path) return fail(YACRD_EINVAL, "null argument");
-    if (const int rcw = c.text_in(text, n, bgzf)) return rcw;
+    if (const int rcw = c.text_in(e, text, n, bgzf, gz)) return gz ? c.leave(rcw) : rcw;
     struct stat ost;
     if (lstat(out_path, &ost) == 0 && !S_ISREG(ost.st_mode)) return fail(YACRD_EFALLBACK, "the output is not a regular file: the host loop writes it");
     return c.run_to_file(e, n, out_path);
@@ -1865,6 +1915,28 @@ int yacrd_engine_edit_fasta_bgzf_file(yacrd_engine *e, int op, const char *bgzf,
                                       yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs, yacrd_gunzip_stats *us)
 {
     return edit_seq_gzip_file(true, e, op, bgzf, n, t, out_path, st, gs, true, us);
+}
+
+// plain gzip in: the _bgzf_ forms' arguments with yacrd_gunzip_stream_stats in place of yacrd_gunzip_stats
+int yacrd_engine_edit_fastq_gz_mem(yacrd_engine *e, int op, const char *gz, uint64_t n, const yacrd_report_table *t, char **out,
+                                   uint64_t *out_bytes, yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs, yacrd_gunzip_stream_stats *ss)
+{
+    return edit_seq_mem(false, e, op, gz, n, t, out, out_bytes, st, true, gs, false, nullptr, true, ss);
+}
+int yacrd_engine_edit_fastq_gz_file(yacrd_engine *e, int op, const char *gz, uint64_t n, const yacrd_report_table *t, const char *out_path,
+                                    yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs, yacrd_gunzip_stream_stats *ss)
+{
+    return edit_seq_gzip_file(false, e, op, gz, n, t, out_path, st, gs, false, nullptr, true, ss);
+}
+int yacrd_engine_edit_fasta_gz_mem(yacrd_engine *e, int op, const char *gz, uint64_t n, const yacrd_report_table *t, char **out,
+                                   uint64_t *out_bytes, yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs, yacrd_gunzip_stream_stats *ss)
+{
+    return edit_seq_mem(true, e, op, gz, n, t, out, out_bytes, st, true, gs, false, nullptr, true, ss);
+}
+int yacrd_engine_edit_fasta_gz_file(yacrd_engine *e, int op, const char *gz, uint64_t n, const yacrd_report_table *t, const char *out_path,
+                                    yacrd_seq_edit_stats *st, yacrd_gzip_stats *gs, yacrd_gunzip_stream_stats *ss)
+{
+    return edit_seq_gzip_file(true, e, op, gz, n, t, out_path, st, gs, false, nullptr, true, ss);
 }
 
 } // extern "C"

@@ -106,6 +106,29 @@ void print_device_inflate(const yacrd_gunzip_stats &us)
                  us.kernel_ms);
 }
 
+// whether a gzip file's first member carries BGZF's `BC` subfield: such a file is the _bgzf_ route's, and what that route
+// hands back of it is not retried as plain gzip (it would go up again only to end as "bytes left over")
+bool first_member_is_bgzf(const unsigned char *p, size_t n)
+{
+    if (n < 12 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) return false;
+    const size_t end = 12 + ((size_t)p[10] | ((size_t)p[11] << 8));
+    for (size_t q = 12; q + 4 <= end && q + 4 <= n;) {
+        const size_t slen = (size_t)p[q + 2] | ((size_t)p[q + 3] << 8);
+        if (p[q] == 'B' && p[q + 1] == 'C' && slen == 2) return true;
+        q += 4 + slen;
+    }
+    return false;
+}
+
+void print_device_gunzip(const yacrd_gunzip_stream_stats &zs)
+{
+    std::fprintf(stderr, "[info] device gunzip: %llu -> %llu bytes, %llu chunks, %llu spans (%llu false starts, %llu rounds), %llu blocks, h2d %.1f ms, "
+                         "find %.1f ms, size %.1f ms, symbols %.1f ms, windows %.1f ms, bytes %.1f ms\n",
+                 (unsigned long long)zs.in_bytes, (unsigned long long)zs.out_bytes, (unsigned long long)zs.n_chunks, (unsigned long long)zs.n_spans,
+                 (unsigned long long)zs.n_false_starts, (unsigned long long)zs.rounds, (unsigned long long)zs.n_blocks, zs.h2d_ms, zs.find_ms, zs.size_ms,
+                 zs.symbols_ms, zs.windows_ms, zs.bytes_ms);
+}
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -559,8 +582,9 @@ int main(int argc, char **argv)
             yacrd_seq_edit_stats ss{};
             yacrd_gzip_stats gs{};
             yacrd_gunzip_stats us{};
+            yacrd_gunzip_stream_stats zs{};
             double inflate_ms = 0;
-            bool text_reused = false, dev_inflate = false;
+            bool text_reused = false, dev_inflate = false, dev_gunzip = false;
             // YACRD_SEQ_WINDOW=<bytes>: the FASTQ and FASTA editors' window (yacrd_debug_seq_window; A/B and tests, like YACRD_NO_DEVICE_EDITOR)
             if (const char *sw = std::getenv("YACRD_SEQ_WINDOW"))
                 if (*sw) (void)yacrd_debug_seq_window(engines[0], std::strtoull(sw, nullptr, 10));
@@ -577,7 +601,11 @@ int main(int argc, char **argv)
                 // a text the editor hands back, no memory — leaves nothing behind and takes the path below, unchanged.
                 // The default, by DESIGN §7h's rows: the slowest `edit` of three with it is under the fastest of three without, on
                 // scrubb and filter, FASTQ and FASTA.  YACRD_NO_DEVICE_INFLATE=1: the path below outright.
-                const char *no_inf = std::getenv("YACRD_NO_DEVICE_INFLATE");
+                // What that call hands back as YACRD_EFALLBACK goes, with YACRD_DEVICE_GUNZIP=1, to the plain-gzip form over the
+                // same bytes (yacrd_engine_edit_fastq_gz_file: one gzip member decoded from block starts found in parallel,
+                // DESIGN §7q), and only then below.  Opt-in: §7q's rows meet §7h's rule for the default; the switch is a change of its own.
+                // A file whose first member is BGZF is the route's above alone: it is not sent up a second time.
+                const char *no_inf = std::getenv("YACRD_NO_DEVICE_INFLATE"), *yes_gz = std::getenv("YACRD_DEVICE_GUNZIP");
                 if (!tx && !(no_inf && *no_inf == '1')) {
                     const int fd = ::open(sub_in.c_str(), O_RDONLY);
                     struct stat sf;
@@ -586,16 +614,22 @@ int main(int argc, char **argv)
                         if (m != MAP_FAILED) {
                             dev_edit = (sub_fa ? yacrd_engine_edit_fasta_bgzf_file : yacrd_engine_edit_fastq_bgzf_file)(
                                 engines[0], op, static_cast<const char *>(m), (uint64_t)sf.st_size, &rt, sub_out.c_str(), &ss, &gs, &us);
-                            ::munmap(m, (size_t)sf.st_size);
                             dev_inflate = dev_edit == YACRD_OK;
+                            if (dev_edit == YACRD_EFALLBACK && yes_gz && *yes_gz == '1' &&
+                                !first_member_is_bgzf(static_cast<const unsigned char *>(m), (size_t)sf.st_size)) {
+                                dev_edit = (sub_fa ? yacrd_engine_edit_fasta_gz_file : yacrd_engine_edit_fastq_gz_file)(
+                                    engines[0], op, static_cast<const char *>(m), (uint64_t)sf.st_size, &rt, sub_out.c_str(), &ss, &gs, &zs);
+                                dev_gunzip = dev_edit == YACRD_OK;
+                            }
+                            ::munmap(m, (size_t)sf.st_size);
                             if (dev_edit == YACRD_ENOMEM)
                                 for (yacrd_engine *en : engines) (void)yacrd_engine_trim(en);
-                            if (!dev_inflate) dev_edit = YACRD_EFALLBACK;
+                            if (!dev_inflate && !dev_gunzip) dev_edit = YACRD_EFALLBACK;
                         }
                     }
                     if (fd >= 0) ::close(fd);
                 }
-                if (!dev_inflate) {
+                if (!dev_inflate && !dev_gunzip) {
                     if (!tx && yacrd_text_from_file(sub_in.c_str(), threads == 1 ? 0 : (int)threads, &own) == 0)
                         tx = &own; // (a file that cannot be inflated: the host loop below words the error)
                     inflate_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count();
@@ -621,6 +655,7 @@ int main(int argc, char **argv)
                              (unsigned long long)ss.out_bytes, ss.text_ms, ss.table_ms, ss.kernel_ms, ss.out_ms, (unsigned long long)sw4[0]);
                 if (dev_inflate)
                     print_device_inflate(us);
+                if (dev_gunzip) print_device_gunzip(zs);
                 if (sub_comp == 1) // (the encoder's line as the host loop's writer words it: the output lay in HBM, nothing went up)
                     std::fprintf(stderr, "[info] device deflate: %llu -> %llu bytes, %llu members (%llu stored), h2d %.1f ms, kernels %.1f ms, "
                                          "d2h %.1f ms, write %.1f ms, inflate %.1f ms, text_reused=%d\n",

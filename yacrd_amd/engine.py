@@ -38,7 +38,7 @@ DEBUG_SYMBOLS = [
     "yacrd_debug_sort_pairs", "yacrd_debug_last_counters", "yacrd_debug_last_input_csr", "yacrd_debug_peer_copy_counts",
     "yacrd_debug_live_bytes", "yacrd_debug_direct_runs", "yacrd_debug_big_routes",
     "yacrd_debug_seq_window", "yacrd_debug_seq_windows", "yacrd_debug_long_min_reads", "yacrd_debug_compute_units",
-    "yacrd_debug_edit_window", "yacrd_debug_edit_windows",
+    "yacrd_debug_edit_window", "yacrd_debug_edit_windows", "yacrd_debug_gunzip_chunk",
 ]
 F_ONE_LAUNCH = 4194304  # include/yacrd_engine.h: a short batch as ONE kernel launch (csrc/one_batch.h)
 
@@ -62,7 +62,8 @@ EXPORTED_SYMBOLS = [
     "yacrd_engine_edit_fastq", "yacrd_engine_edit_fastq_mem", "yacrd_engine_edit_fastq_gzip_mem", "yacrd_engine_edit_fastq_gzip_file",
     "yacrd_engine_edit_fasta", "yacrd_engine_edit_fasta_mem", "yacrd_engine_edit_fasta_gzip_mem", "yacrd_engine_edit_fasta_gzip_file",
     "yacrd_engine_gunzip_mem", "yacrd_engine_edit_fastq_bgzf_mem", "yacrd_engine_edit_fastq_bgzf_file",
-    "yacrd_engine_edit_fasta_bgzf_mem", "yacrd_engine_edit_fasta_bgzf_file",
+    "yacrd_engine_edit_fasta_bgzf_mem", "yacrd_engine_edit_fasta_bgzf_file", "yacrd_engine_gunzip_stream_mem",
+    "yacrd_engine_edit_fastq_gz_mem", "yacrd_engine_edit_fastq_gz_file", "yacrd_engine_edit_fasta_gz_mem", "yacrd_engine_edit_fasta_gz_file",
     "yacrd_engine_gzip_mem", "yacrd_gzip_writer_open", "yacrd_gzip_writer_write", "yacrd_gzip_writer_sink", "yacrd_gzip_writer_close",
     "yacrd_gzip_writer_abort",
     "yacrd_stream_device_of", "yacrd_stream_group_open", "yacrd_stream_group_sink", "yacrd_stream_group_finish",
@@ -124,6 +125,11 @@ class _GzipStats(ctypes.Structure):
 class _GunzipStats(ctypes.Structure):  # yacrd_gunzip_stats
     _fields_ = [(n, ctypes.c_uint64) for n in ("in_bytes", "out_bytes", "n_members")] + \
                [(n, ctypes.c_float) for n in ("walk_ms", "h2d_ms", "kernel_ms", "d2h_ms")]
+
+
+class _GunzipStreamStats(ctypes.Structure):  # yacrd_gunzip_stream_stats
+    _fields_ = [(n, ctypes.c_uint64) for n in ("in_bytes", "out_bytes", "n_chunks", "n_spans", "n_false_starts", "rounds", "n_blocks")] + \
+               [(n, ctypes.c_float) for n in ("find_ms", "size_ms", "symbols_ms", "windows_ms", "bytes_ms", "h2d_ms", "d2h_ms")]
 
 
 from .host import ByteSink  # noqa: E402  (yacrd_byte_sink: one structure, declared in both headers)
@@ -381,10 +387,14 @@ def load_library():
     lib.yacrd_edit_text_free.restype = None
     lib.yacrd_engine_gunzip_mem.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p),
                                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_GunzipStats)]
+    lib.yacrd_engine_gunzip_stream_mem.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p),
+                                                   ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_GunzipStreamStats)]
     for fmt in ("fastq", "fasta"):  # (the gzip forms' arguments and a trailing yacrd_gunzip_stats)
         for form in ("mem", "file"):
             getattr(lib, "yacrd_engine_edit_%s_bgzf_%s" % (fmt, form)).argtypes = \
                 getattr(lib, "yacrd_engine_edit_%s_gzip_%s" % (fmt, form)).argtypes + [ctypes.POINTER(_GunzipStats)]
+            getattr(lib, "yacrd_engine_edit_%s_gz_%s" % (fmt, form)).argtypes = \
+                getattr(lib, "yacrd_engine_edit_%s_gzip_%s" % (fmt, form)).argtypes + [ctypes.POINTER(_GunzipStreamStats)]
     lib.yacrd_engine_gzip_mem.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p),
                                           ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_GzipStats)]
     lib.yacrd_gzip_writer_open.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
@@ -1100,11 +1110,51 @@ class Engine:
         finally:
             self._lib.yacrd_edit_text_free(out)
 
-    def _edit_seq_gzip(self, fmt, op, text, names, lengths, result, out_path, bgzf=False):
+    def gunzip_stream(self, data):
+        """yacrd_engine_gunzip_stream_mem: ONE plain gzip member (bytes) -> its text (bytes), inflated on the device from block
+        starts found in parallel; the stats are in self.gunzip_stream_stats.  Raises NeedsHostParser, with nothing returned,
+        when `data` is not one gzip member (BGZF and concatenated members among them) or its payload is one the device decoder
+        does not take (host.text_from_file reads those)."""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        n = int(buf.size)
+        st = _GunzipStreamStats()
+        out, n_out = ctypes.c_void_p(), ctypes.c_uint64()
+        rc = self._lib.yacrd_engine_gunzip_stream_mem(self._h, ctypes.c_void_p(buf.ctypes.data if n else None), n, ctypes.byref(out),
+                                                      ctypes.byref(n_out), ctypes.byref(st))
+        del buf
+        if rc == E_FALLBACK:
+            raise NeedsHostParser(self._lib.yacrd_last_error().decode())
+        _check(self._lib, rc)
+        self.gunzip_stream_stats = {f: getattr(st, f) for f, _ in _GunzipStreamStats._fields_}
+        try:
+            return ctypes.string_at(out.value, int(n_out.value)) if n_out.value else b""
+        finally:
+            self._lib.yacrd_edit_text_free(out)
+
+    def debug_gunzip_chunk(self, n_bytes):
+        """yacrd_debug_gunzip_chunk (tests, A/B): gunzip_stream looks for a block start once per `n_bytes` of compressed payload
+        (at least 1024; 0: YACRD_GUNZIP_CHUNK or the default, 32 KiB).  The text does not depend on it."""
+        self._lib.yacrd_debug_gunzip_chunk.restype = ctypes.c_int
+        self._lib.yacrd_debug_gunzip_chunk.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+        _check(self._lib, self._lib.yacrd_debug_gunzip_chunk(self._h, int(n_bytes)))
+
+    def edit_fastq_gz(self, op, blob, names, lengths, result, out_path=None):
+        """yacrd_engine_edit_fastq_gz_mem / _file: edit_fastq_gzip over ONE plain gzip member `blob` (bytes or anything else
+        with the buffer protocol): it crosses the link as it is and is inflated on the device (gunzip_stream's steps).  The
+        result is edit_fastq_gzip's for the inflated text; the inflate's stats are in self.gunzip_stream_stats.  The
+        whole-text run only.  Raises NeedsHostParser, with nothing written, also when `blob` is not one gzip member or its
+        payload is one the device decoder does not take."""
+        return self._edit_seq_gzip("fastq", op, blob, names, lengths, result, out_path, gz=True)
+
+    def edit_fasta_gz(self, op, blob, names, lengths, result, out_path=None):
+        """yacrd_engine_edit_fasta_gz_mem / _file: edit_fastq_gz for FASTA."""
+        return self._edit_seq_gzip("fasta", op, blob, names, lengths, result, out_path, gz=True)
+
+    def _edit_seq_gzip(self, fmt, op, text, names, lengths, result, out_path, bgzf=False, gz=False):
         t, keep = self._seq_table(names, lengths, result)
-        st, gs, us = _SeqEditStats(), _GzipStats(), _GunzipStats()
-        more = (ctypes.byref(us),) if bgzf else ()
-        kind = "bgzf" if bgzf else "gzip"
+        st, gs, us = _SeqEditStats(), _GzipStats(), _GunzipStreamStats() if gz else _GunzipStats()
+        more = (ctypes.byref(us),) if bgzf or gz else ()
+        kind = "bgzf" if bgzf else "gz" if gz else "gzip"
         buf = np.frombuffer(text, dtype=np.uint8)
         n = int(buf.size)
         addr = ctypes.c_void_p(buf.ctypes.data if n else None)
@@ -1119,6 +1169,8 @@ class Engine:
         self._seq_edited(rc, st)
         if bgzf:
             self.gunzip_stats = {f: getattr(us, f) for f, _ in _GunzipStats._fields_}
+        if gz:
+            self.gunzip_stream_stats = {f: getattr(us, f) for f, _ in _GunzipStreamStats._fields_}
         self.gzip_stats = {f: getattr(gs, f) for f, _ in _GzipStats._fields_}
         if out_path is not None:
             return self.seq_edit_stats, self.gzip_stats

@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = [
     "yacrd_edit_file", "yacrd_edit_file_mt", "yacrd_text_from_file", "yacrd_text_free", "yacrd_report_read", "yacrd_report_get", "yacrd_report_free",
     "yacrd_edit_file_to", "yacrd_file_compression", "yacrd_bgzf_encode_host", "yacrd_bgzf_decode_host", "yacrd_bytes_free", "yacrd_deflate_code_lengths",
     "yacrd_synth_fastq", "yacrd_ingest_stream", "yacrd_ingest_stream_memory", "yacrd_csr_handle_map", "yacrd_bgzf_plan_segments",
-    "yacrd_bgzf_text_ends", "yacrd_bgzf_window_cuts", "yacrd_edit_window_route",
+    "yacrd_bgzf_text_ends", "yacrd_bgzf_window_cuts", "yacrd_edit_window_route", "yacrd_gzip_stream_decode_host",
 ]
 
 OP_SCRUBB, OP_FILTER, OP_EXTRACT, OP_SPLIT = 0, 1, 2, 3
@@ -162,6 +162,8 @@ def load_library():
         lib.yacrd_file_compression.argtypes = [ctypes.c_char_p]
         lib.yacrd_bgzf_encode_host.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)]
         lib.yacrd_bgzf_decode_host.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)]
+        lib.yacrd_gzip_stream_decode_host.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p),
+                                                      ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         lib.yacrd_bgzf_plan_segments.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
                                                  ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64),
                                                  ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)]
@@ -386,6 +388,25 @@ def bgzf_decode_host(data):
     _check(lib, lib.yacrd_bgzf_decode_host(data, len(data), ctypes.byref(out), ctypes.byref(n)))
     try:
         return ctypes.string_at(out.value, int(n.value))
+    finally:
+        lib.yacrd_bytes_free(out)
+
+
+GZIP_STREAM_COUNTERS = ("n_chunks", "n_spans", "n_false_starts", "rounds", "n_blocks", "out_bytes")
+
+
+def gzip_stream_decode_host(data, chunk=0):
+    """yacrd_gzip_stream_decode_host: the plain-gzip device decoder's text run by one host thread, block starts looked for
+    per `chunk` compressed bytes (0: the default) -> (the text, {counter: value} with GZIP_STREAM_COUNTERS' names): the bytes
+    and counters Engine.gunzip_stream gives.  Raises HostError (the message names the cause) for what is not one gzip member
+    or a payload the decoder does not take."""
+    lib = load_library()
+    data = bytes(data)
+    out, n = ctypes.c_void_p(), ctypes.c_uint64()
+    counters = (ctypes.c_uint64 * 6)()
+    _check(lib, lib.yacrd_gzip_stream_decode_host(data, len(data), int(chunk), ctypes.byref(out), ctypes.byref(n), counters))
+    try:
+        return ctypes.string_at(out.value, int(n.value)), dict(zip(GZIP_STREAM_COUNTERS, (int(v) for v in counters)))
     finally:
         lib.yacrd_bytes_free(out)
 
